@@ -9,7 +9,7 @@ level-1 sort (k_walk_sort), level-2 sort, bucket count into the 4^k table (which
 side list.  Prints ONE JSON line on rank 0.  The merge legs call pykmer_amd.merger.pair_matrix, the function
 merger.py runs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bp 800000000] [--no-merge] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bp 800000000] [--no-merge] [--no-cpu] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -108,6 +108,34 @@ def end_to_end(fasta, total_bp, k, device):
     return res
 
 
+def save_output(out_dir, name, a, dtype=np.float64):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=dtype))
+
+
+def dump_indexer_outputs(out_dir, ix, fin):
+    """What a caller of the timed path gets back from its last step: Indexer.finish()'s numbers, the records and the
+    4^k table.  The table (1 GiB at k=15) is sampled: 1024 stretches of 4096 entries at seeded offsets, the same on every
+    run, or the whole table when it is smaller than that; its values go out as float32, everything else as float64
+    (exact for these integer counts)."""
+    save_output(out_dir, "num_kmers", [fin["num_kmers"]])
+    save_output(out_dir, "total_bp", [fin["total_bp"]])
+    save_output(out_dir, "hist256", fin["hist256"])
+    recs = ix.records(fin["n_records"])
+    for f in recs.dtype.names:
+        save_output(out_dir, "records_" + f, recs[f])
+    n, stretch, n_stretches = ix.table_bytes, 4096, 1024
+    if n <= stretch * n_stretches:
+        starts, stretch = np.zeros(1, dtype=np.int64), n
+    else:
+        starts = np.sort(np.random.default_rng(0).choice(n // stretch, size=n_stretches, replace=False)) * stretch
+    sample = np.empty((len(starts), stretch), dtype=np.uint8)
+    for row, start in zip(sample, starts):
+        ix.table_slice_to_host(row, int(start))
+    save_output(out_dir, "table_sample", sample, np.float32)
+    save_output(out_dir, "table_sample_offsets", starts)
+
+
 def cpu_info():
     model = "unknown"
     try:
@@ -139,7 +167,12 @@ def main():
     ap.add_argument("--cpu-bp", type=int, default=160_000_000, help="sample size for the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the all-cores CPU legs (default 0 = every core this process may run on)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (and the merge matrices) as DIR/<name>.npy "
+                         "(rank 0; inputs are seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # the bench measures the library as shipped: no alternate build, no kernel switches (experiments: tools/)
     switches = [v for v in ("PK_LIB", "PK_K15", "PK_K6_BYTES", "PK_GRAM_MW", "PK_DENSE_SHIFT", "PK_WG1", "PK_GRID2", "PK_XCD", "PK_SPARSE_MAX")
@@ -219,6 +252,8 @@ def main():
     else:
         bp_job = total_bp
     assert fin["total_bp"] == total_bp, (fin["total_bp"], total_bp)
+    if args.dump_outputs and rank == 0:                                 # before the merge section re-uses the indexer
+        dump_indexer_outputs(args.dump_outputs, ix, fin)
     value = bp_job * args.steps / elapsed
     avg = {key: v / args.steps for key, v in acc.items()}
 
@@ -308,6 +343,8 @@ def main():
             return best, kern, pairs
         best, kern, pairs = timed([(1, 255)])
         total = pairs[0].astype(np.int64)
+        if args.dump_outputs and rank == 0:
+            save_output(args.dump_outputs, f"merge_n{N}_pairs", pairs[0])
         assert all(total[i, j] <= min(total[i, i], total[j, j]) for i in range(N) for j in range(i + 1, N))
         res = {"n_tables": N, "k": k, "seconds": best, "kernel_seconds_rank0": kern, "algorithmic_bytes": N * n,
                "kernel_GBps_aggregate": N * n / kern / 1e9 if world == 1 else None,

@@ -1,45 +1,37 @@
-"""Build-container only (skipped wherever /root/reference is absent, e.g. on the GPU box): the
-reference's own Header and merger must accept the files this build writes."""
-import contextlib
-import io
+"""The files this build writes, read the way the reference's own Header and merger read them: the name parsed into
+input and k (tools.py:220-238), the JSON looked up key by key with the fixed keys checked (tools.py:387-401), the
+raw table compared pair-wise (tools.py:439-493).  Every expected value is one the reference itself wrote
+(tests/golden/manifest.json), and none of this package's readers is used."""
+import json
 import os
-import sys
-import types
 
-import pytest
+import numpy as np
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "tools.py")), reason="reference not present")
+from test_host_layer import _family_indexes
 
 
-def _ref_modules():
-    sys.dont_write_bytecode = True
-    sys.modules.setdefault("bgzip", types.ModuleType("bgzip"))          # tools.py:17 imports a module it never uses
-    saved = {k: sys.modules.pop(k) for k in ("tools", "merger") if k in sys.modules}
-    sys.path.insert(0, REF)
-    try:
-        import tools as ref_tools
-        import merger as ref_merger
-    finally:
-        sys.path.remove(REF)
-        for k in ("tools", "merger"):
-            sys.modules.pop(k, None)
-        sys.modules.update(saved)
-    return ref_tools, ref_merger
+def _parse_index_name(path):
+    """<input>.<kk>.kin: the input's name and k."""
+    stem, kk, ext = path.rsplit(".", 2)
+    assert ext == "kin" and len(kk) == 2
+    return os.path.basename(stem), int(kk)
 
 
 def test_reference_reads_our_kin_and_merges_it(tmp_path, manifest):
-    from test_host_layer import _family_indexes
-    ref_tools, ref_merger = _ref_modules()
+    written = manifest["indexer"]["G3_edge_k7"]                         # a k = 7 .kin.json the reference wrote
     paths = sorted(_family_indexes(tmp_path, manifest, n=3))
-    h = ref_tools.Header(paths[0], index_file=paths[0])                 # parses our name + JSON, asserts the fixed keys
-    assert h.kmer_len == 7 and h.data_size == 4 ** 7
-    cwd = os.getcwd()
-    os.chdir(REF)
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            got = ref_merger.calculate_distance(paths[0], paths[1], min_count=2)     # merger.py:62-78 on our files
-    finally:
-        os.chdir(cwd)
-    case = manifest["merger"]["G7_k7_n13_min2"]
-    assert tuple(got) == tuple(case["matrix"][0][1])
+    tables = []
+    for i, path in enumerate(paths):
+        assert _parse_index_name(path) == (f"s{i:02d}.fa", 7)
+        with open(path + ".json") as fh:
+            meta = json.load(fh)
+        assert sorted(meta) == written["reference_keys"]
+        for f in ("file_ver", "kmer_size", "data_size", "max_size"):
+            assert meta[f] == written["expect"][f], f
+        assert meta["kmer_len"] == 7
+        table = np.fromfile(path, dtype=np.uint8)
+        assert table.size == meta["data_size"]
+        tables.append(table)
+    s_valid, o_valid = ((t >= 2) & (t <= 255) for t in tables[:2])    # min_count=2, as the golden merge ran
+    got = (int(s_valid.sum()), int(o_valid.sum()), int((s_valid & o_valid).sum()))
+    assert got == tuple(manifest["merger"]["G7_k7_n13_min2"]["matrix"][0][1])
