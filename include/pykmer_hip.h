@@ -173,8 +173,8 @@ int pk_bgzf_deflate(const uint8_t *src, uint64_t n_bytes, int level, uint32_t bl
                     uint64_t *c_sizes_out, uint64_t *total_out, int threads);
 
 /* ---- diagnostics (tools/, tests/): no reference counterpart, no effect on any result.
- * pk_diag_occupancy: workgroups per CU the runtime grants kernel `which` (0 k_bucket_count_half, 1 k_bucket_count_bytes,
- * 2 k_bucket_count_half_lean, 3 k_scatter2<claim>); negative = HIP error.
+ * pk_diag_occupancy: workgroups per CU the runtime grants kernel `which` (0 k_bucket_count, 1 k_bucket_count_bytes,
+ * 2 k_bucket_count_half_lean, 3 k_scatter2), each at the dynamic LDS size it is launched with; negative = HIP error.
  * pk_diag_plan: the partition plan of ONE feed of n_bytes (0 = the largest piece a feed is cut into) at kmer_len k:
  * out = { largest piece, level-1 record capacity, final-bucket record capacity, level-1 buckets, level-2 digits,
  * address bits per final bucket, 16 KiB chunks, 1 if every record position fits 32 bits }. */

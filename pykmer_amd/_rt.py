@@ -4,7 +4,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PK_LIB: another build of the same library (kernel experiments: tools/build_variant.sh); never a CPU stand-in --
+# PK_LIB: another build of the same library (to measure one build against another); never a CPU stand-in --
 # open_library() refuses one that does not answer pk_version() with this ABI or lacks the device entry points
 LIB_PATH = os.environ.get("PK_LIB") or os.path.join(_HERE, "libpykmer_hip.so")
 ABI_VERSION = 3                      # PK_ABI_VERSION of include/pykmer_hip.h

@@ -30,7 +30,6 @@
 // A bucket that outgrows its room raises a flag (its runs go to a dump area, nothing is overwritten); every
 // later kernel of the feed then returns at once and the host repeats from here with stride 1, i.e. with
 // exact sizes.  Inputs below 1024 chunks are counted exactly straight away.
-#include <cstdlib>
 #include "part_common.h"
 
 namespace pk {
@@ -82,12 +81,9 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
     // k as a literal pays (k = 15: 1.39 -> 1.33 ms, k = 17: 2.25 -> 2.03); the digit position as a literal on top of it
     // pays for the 64-bit kernel only (k = 15: 1.33 -> 1.37 with it)
     // (the same literals in the level-2 kernel change nothing: 1.213 ms either way)
-#ifndef PK_LIT15
-#define PK_LIT15 0
-#endif
-    const uint32_t B = KC == 17 ? 512u : (PK_LIT15 && KC == 15) ? 128u : pl.B1, shift = KC == 17 ? 25u : (PK_LIT15 && KC == 15) ? 23u : pl.addr_bits - pl.b1;
+    const uint32_t B = KC == 17 ? 512u : pl.B1, shift = KC == 17 ? 25u : pl.addr_bits - pl.b1;
     const uint32_t low_mask = shift >= 32 ? 0xffffffffu : ((1u << shift) - 1u);
-    const bool out16 = (KC == 17 || (PK_LIT15 && KC == 15)) ? false : pl.b2 == 0;
+    const bool out16 = KC == 17 ? false : pl.b2 == 0;
     const KT mask = (KT)((2u * k >= sizeof(KT) * 8u) ? ~(KT)0 : (((KT)1 << (2u * k)) - 1));
     const KT local_mask = (KT)((pl.addr_bits >= sizeof(KT) * 8u) ? ~(KT)0 : (((KT)1 << pl.addr_bits) - 1));   // SLICED: address inside the range
     uint32_t t = threadIdx.x;                                             // COUNT: the thread's place in the slot its WAVE samples (see locate)
@@ -141,13 +137,7 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
     bool ok_n = false;
     if (i_lo < i_hi) { ok_n = locate(i_lo, c_n, t_n); if (ok_n) fetch(c_n, t_n, nxt); }
     settle();
-#ifdef PK_PHASE_PROF
-    unsigned long long phase_prof[5] = {0, 0, 0, 0, 0};                   // thread 0: assembly, count, scan, park, store (cycles)
-#endif
     for (uint32_t it = i_lo; it < i_hi; it += i_step) {
-#ifdef PK_PHASE_PROF
-        const unsigned long long tile_t0 = __builtin_readcyclecounter();
-#endif
         const Fetched me = nxt;
         const uint32_t c = c_n;
         const bool ok = ok_n;
@@ -353,15 +343,10 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
         }
         // 32-bit k-mers with a second level to come: 3-byte records in two planes (part_common.h)
         uint8_t *out_hi = (!WIDE && !out16) ? reinterpret_cast<uint8_t *>(out) + level1_hi_plane_offset(pl.capacity1) : nullptr;
-#ifdef PK_PHASE_PROF
-        unsigned long long *prof = phase_prof;
-        if (threadIdx.x == 0) { const unsigned long long pn = __builtin_readcyclecounter(); prof[0] += pn - tile_t0; }
-#else
-        unsigned long long *prof = nullptr;
-#endif
         bool hot_full = false;                                            // uniform: see scatter_tile (`watch`)
-        scatter_tile<KT, WIDE, NT, PER, NB, false, PK_PB_L1, (WIDE ? 0 : PK_SB_L1), !WIDE>(L, r, okm, ~0u, shift, B, low_mask, out16, out, settle, cursor1, cap_end, dump, flags, out_hi, prof,
-                                                                                          &hot.used, HS / 2, &hot_full);
+        // write-out batches of 8 for 32-bit k-mers only (the 64-bit kernel loses with them: 2.22 -> 2.29 ms)
+        scatter_tile<KT, WIDE, NT, PER, NB, false, (WIDE ? 0 : 8), !WIDE>(L, r, okm, ~0u, shift, B, low_mask, out16, out, settle, cursor1, cap_end, dump, flags, out_hi,
+                                                                         &hot.used, HS / 2, &hot_full);
         if (hot_full) hot_flush(hot, side, side_n, side_cap);             // (starts and ends with a barrier of its own)
     }
     if (COUNT) {
@@ -370,10 +355,6 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
         return;
     }
     hot_flush(hot, side, side_n, side_cap);
-#ifdef PK_PHASE_PROF
-    if (threadIdx.x == 0)                                                  // behind side_n (u64) and the flags: words 4.. of the 256-byte flag area
-        for (int i = 0; i < 5; i++) atomicAdd(side_n + 4 + i, phase_prof[i]);
-#endif
 }
 
 // ------------------------------------------------------------------ bucket layout ---------------
@@ -478,24 +459,16 @@ __global__ __launch_bounds__(1024) void k_provision(const uint32_t *__restrict__
     }
 }
 
-// after the level-1 sort: how full every bucket got, the level-2 work split (bucket d gets ceil(n_d / R2)
-// workgroups) and, for the layouts that are compact again from here on, the exclusive scan of the sizes
+// after the level-1 sort: where every bucket's records end, and the level-2 work split -- bucket b gets ceil(n_b / R2)
+// work items, counted up with the buckets in XCD-class order (b % 8 major), which is the order the persistent level-2
+// launch walks them in (kmer_part.hip: k_scatter2)
 __global__ __launch_bounds__(1024) void k_level1_finish(const uint32_t *__restrict__ cursor1, const uint32_t *__restrict__ bucket_base,
                                                         const uint32_t *__restrict__ cap_end, PartPlan pl, uint32_t *__restrict__ bucket_end,
-                                                        uint32_t *__restrict__ compact_base, uint32_t *__restrict__ wg2_start,
-                                                        const uint32_t *__restrict__ flags) {
+                                                        uint32_t *__restrict__ wg2_start, const uint32_t *__restrict__ flags) {
     __shared__ uint32_t wsum[16];
     if (flags[0]) return;
     const uint32_t d = threadIdx.x, B1 = pl.B1;
-    uint32_t size = 0;
-    if (d < B1) size = min(cursor1[d], cap_end[d]) - bucket_base[d];
-    const uint32_t g = (uint32_t)(((uint64_t)size + pl.R2 - 1) / pl.R2);
-    uint32_t sum_n, sum_g;
-    const uint32_t cb = block_excl_scan_1024(size, wsum, sum_n);
-    const uint32_t ws = block_excl_scan_1024(g, wsum, sum_g);
-    if (d < B1) { bucket_end[d] = bucket_base[d] + size; compact_base[d] = cb; wg2_start[d] = ws; }
-    if (d == 0) { compact_base[B1] = sum_n; wg2_start[B1] = sum_g; }
-    // the same running count with the buckets in XCD-class order (b % 8 major): what the persistent level-2 launch walks
+    if (d < B1) bucket_end[d] = min(cursor1[d], cap_end[d]);
     if (B1 >= 8u) {
         const uint32_t per = B1 >> 3;
         uint32_t g2 = 0;
@@ -506,9 +479,8 @@ __global__ __launch_bounds__(1024) void k_level1_finish(const uint32_t *__restri
         }
         uint32_t sum_g2;
         const uint32_t ps = block_excl_scan_1024(g2, wsum, sum_g2);
-        uint32_t *pos = wg2_start + B1 + 1;
-        if (d < B1) pos[d] = ps;
-        if (d == 0) pos[B1] = sum_g2;
+        if (d < B1) wg2_start[d] = ps;
+        if (d == 0) wg2_start[B1] = sum_g2;
     }
 }
 
@@ -555,20 +527,17 @@ void fuse_set_attributes() {
     set((const void *)PK_WS_DEEP(false), SCATTER_LDS_WIDE); set((const void *)PK_WS_DEEP(true), 65536);
 }
 
-// PK_K15=0: the generic instantiations for k = 15 / 17 as well (comparison runs)
-static bool pk_k15_enabled() { static const bool on = !(getenv("PK_K15") && atoi(getenv("PK_K15")) == 0); return on; }
-
 template <bool COUNT, typename... Args>
 static void launch_ws(const PartPlan &pl, uint32_t grid, size_t lds, hipStream_t s, Args... args) {
     const bool sliced = pl.slice_bits != 0;
     if (pl.k > 17) hipLaunchKernelGGL((PK_WS_DEEP(COUNT)), dim3(grid), dim3(1024), lds, s, args...);
     else if (pl.k > 15) {
         if (sliced) hipLaunchKernelGGL((PK_WS_WIDE(COUNT, true)), dim3(grid), dim3(1024), lds, s, args...);
-        else if (pl.k == 17 && pl.b1 == 9 && pk_k15_enabled()) hipLaunchKernelGGL((PK_WS_K17(COUNT)), dim3(grid), dim3(1024), lds, s, args...);
+        else if (pl.k == 17 && pl.b1 == 9) hipLaunchKernelGGL((PK_WS_K17(COUNT)), dim3(grid), dim3(1024), lds, s, args...);
         else hipLaunchKernelGGL((PK_WS_WIDE(COUNT, false)), dim3(grid), dim3(1024), lds, s, args...);
     } else {
         if (sliced) hipLaunchKernelGGL((PK_WS_NARROW(COUNT, true)), dim3(grid), dim3(512), lds, s, args...);
-        else if (pl.k == 15 && pl.b1 == 7 && pk_k15_enabled()) hipLaunchKernelGGL((PK_WS_K15(COUNT)), dim3(grid), dim3(512), lds, s, args...);
+        else if (pl.k == 15 && pl.b1 == 7) hipLaunchKernelGGL((PK_WS_K15(COUNT)), dim3(grid), dim3(512), lds, s, args...);
         else hipLaunchKernelGGL((PK_WS_NARROW(COUNT, false)), dim3(grid), dim3(512), lds, s, args...);
     }
 }
@@ -591,13 +560,12 @@ void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uin
 
 void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
                       uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *compact_base, uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
-                      hipStream_t s) {
+                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap, hipStream_t s) {
     const uint32_t dump = (uint32_t)pl.capacity1;
     launch_ws<false>(pl, pl.n_wg1, pl.k > 15 ? SCATTER_LDS_WIDE : FUSE_LDS_NARROW, s, codes, restarts, n_bases, st2, pl, pl.n_chunks, 1u, out1, cursor1,
                      cap_end, dump, flags, 0u, 0u, (uint32_t *)nullptr, side, side_n, side_cap);
-    hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)cursor1, bucket_base, cap_end, pl, bucket_end, compact_base,
-                       wg2_start, (const uint32_t *)flags);
+    hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)cursor1, bucket_base, cap_end, pl, bucket_end, wg2_start,
+                       (const uint32_t *)flags);
 }
 
 }  // namespace pk

@@ -17,16 +17,13 @@
 // Per-record tallies (seq_len, number of valid windows, header extent: indexer.py:75-95,349-351) are
 // taken here too, where the text is in hand.  0.38 bytes written per base instead of one 4-byte record;
 // kmer_fuse.hip assembles the k-mers from the slots with no dependence between its threads.
-#include <cstdlib>
 #include "fasta_fsm.h"
 #include "kmer_walk.h"
 #include "pk_kernels.h"
 
-#ifndef PK_LB_SQ
-#define PK_LB_SQ 4   // waves per SIMD the squeeze kernel is compiled for (3, 5, 6 and 8 all give 0.31 ms instead of 0.21)
-#endif
-
 namespace pk {
+
+constexpr int SQUEEZE_WAVES = 4;   // waves per SIMD the squeeze kernel is compiled for (3, 5, 6 and 8 all give 0.31 ms instead of 0.21)
 
 // exclusive scan of a small count over the 256 lanes of the workgroup (sh: 4 words; one barrier)
 __device__ __forceinline__ uint32_t wg_excl_scan_u32(uint32_t v, uint32_t *sh, uint32_t &total) {
@@ -211,7 +208,7 @@ __device__ __forceinline__ void stage_image(const uint8_t *__restrict__ fasta, u
 }
 
 template <uint32_t KC>                   // k as a literal (0: the argument)
-__global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restrict__ fasta, uint64_t n_bytes, uint64_t stream_off,
+__global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__restrict__ fasta, uint64_t n_bytes, uint64_t stream_off,
                                                 const LaneState *__restrict__ lane_state, const PiecePack *__restrict__ packs,
                                                 const L2 *__restrict__ chunk_l2_state,
                                                 const uint32_t *__restrict__ chunk_odd, uint32_t k_arg, uint32_t n_chunks, uint32_t chunks_per_wg,
@@ -264,12 +261,6 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
     }
     settle();
     __syncthreads();
-#ifdef PK_PHASE_PROF      // where a workgroup's time goes, in cycles of its thread 0 (experiment builds; printed by pk_api.hip)
-    unsigned long long sq_prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, sq_t = __builtin_readcyclecounter();
-#define SQ_MARK(i) do { if (threadIdx.x == 0) { const unsigned long long n_ = __builtin_readcyclecounter(); sq_prof[i] += n_ - sq_t; sq_t = n_; } } while (0)
-#else
-#define SQ_MARK(i) do { } while (0)
-#endif
     for (uint32_t c = c_lo; c < c_hi; c++) {
         const uint64_t base = (uint64_t)c * CHUNK;
         uint8_t *buf = image[(c - c_lo) & 1u];
@@ -284,7 +275,6 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
             if (threadIdx.x == 0) racc.rec0 = first_rec;
             __syncthreads();
         }
-        SQ_MARK(0);                                        // image barrier + record-window move
         const Fetched me = nxt;
         if (c + 1 < c_hi) {
             // the other image is free: its readers passed the barriers of the chunk before this one
@@ -312,12 +302,10 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
             pk.restart = ((unsigned long long)me.p1.y << 32) | me.p1.x; pk.meta = me.p1.z; pk.pad_ = 0;
             if (all_clean || __any(clean)) squeeze_apply(pk, wk, pb, clean);
         }
-        SQ_MARK(1);                                        // state composition + clean pieces
         if (!all_clean) {
             if (!clean) queue[atomicAdd(&n_queued, 1u)] = (uint16_t)threadIdx.x;
             __syncthreads();
             const uint32_t n_q = n_queued;
-            SQ_MARK(8);
             for (uint32_t q0 = (threadIdx.x >> 6) * 64u; q0 < n_q; q0 += WG) {        // wave-uniform
                 const uint32_t qi = q0 + (threadIdx.x & 63u);
                 const bool work = qi < n_q;
@@ -332,9 +320,7 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
                 uint8_t *pq = buf + pc * PIECE;
                 PieceBases rb;
                 rb.clear();
-                SQ_MARK(9);
                 if (__any(by_masks)) squeeze_header_piece(pq, wq, rb, by_masks);
-                SQ_MARK(10);
                 if (__any(nbq != 0u))
                     for_each_byte_of(pq, nbq, [&](uint32_t i, uint32_t ch, bool act) {
                         uint32_t code;
@@ -342,25 +328,20 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
                         const bool take = wq.step(i, ch, act, code, rst);
                         rb.push(take, code, rst);
                     });
-                SQ_MARK(11);
                 wq.flush_rec_wave();
-                SQ_MARK(12);
                 wk.seq_tot += wq.seq_tot; wk.kmer_tot += wq.kmer_tot;                  // stream totals travel with the lane that did the work
                 if (work) {
                     unsigned long long *res = reinterpret_cast<unsigned long long *>(pq);
                     res[0] = rb.code_lo; res[1] = rb.code_hi; res[2] = rb.restart; res[3] = rb.n;
                 }
             }
-            SQ_MARK(13);
             __syncthreads();
-            SQ_MARK(14);
             if (!clean) {
                 const unsigned long long *res = reinterpret_cast<const unsigned long long *>(piece);
                 pb.code_lo = res[0]; pb.code_hi = res[1]; pb.restart = res[2]; pb.n = (uint32_t)res[3];
             }
             if (threadIdx.x == 0) n_queued = 0;                                       // read again only after the next barrier
         }
-        SQ_MARK(2);                                        // queued pieces (+ two barriers)
         wk.flush_rec_wave();
         // where the lane's bases go in the chunk's slot: exclusive prefix of the counts over the workgroup
         uint32_t total;
@@ -368,9 +349,7 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
         lds_or_bits(slot_codes, 2u * at, pb.code_lo, pb.code_hi, 2u * pb.n);
         lds_or_bits(slot_rst, at, pb.restart, 0ull, pb.n);
         __syncthreads();
-        SQ_MARK(3);                                        // record tallies, scan, bit packing into the slot image
         settle();
-        SQ_MARK(4);                                        // delivery of the next chunk's loads
         // slot -> HBM, 16 bytes per lane, only the words that hold bases; the LDS copy is cleared for the next chunk
         const uint32_t code_q = (total + 63u) / 64u, rst_q = (total + 127u) / 128u;      // uint4 groups in use
         // (the lane's byte offset is formed here, opaque to the compiler: as a loop invariant the two lane addresses were
@@ -389,12 +368,7 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
             reinterpret_cast<uint4 *>(slot_rst)[threadIdx.x] = make_uint4(0, 0, 0, 0);
         }
         if (threadIdx.x == 0) n_bases[c] = total;
-        SQ_MARK(5);                                        // slot store
     }
-#ifdef PK_PHASE_PROF
-    if (threadIdx.x == 0)
-        for (int i = 0; i < 16; i++) atomicAdd(reinterpret_cast<unsigned long long *>(flags) - 1 + 14 + i, sq_prof[i]);
-#endif
     wk.finish();
     recacc_finish(racc, recs, recs_cap, carry);
 }
@@ -402,11 +376,10 @@ __global__ __launch_bounds__(WG, PK_LB_SQ) void k_squeeze(const uint8_t *__restr
 void launch_squeeze(const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state, const PiecePack *packs, const L2 *st2,
                     const uint32_t *chunk_odd, uint32_t k, uint32_t n_chunks, uint32_t n_wg, uint32_t chunks_per_wg, uint32_t *codes, uint32_t *restarts, uint32_t *n_bases,
                     DevRec *recs, uint64_t recs_cap, Carry *carry, uint32_t *flags, hipStream_t s) {
-    static const bool lit = !(getenv("PK_K15") && atoi(getenv("PK_K15")) == 0);
 #define PK_SQUEEZE(KC) hipLaunchKernelGGL(k_squeeze<KC>, dim3(n_wg), dim3(WG), 0, s, fasta, n, stream_off, lane_state, packs, st2, chunk_odd, k, n_chunks, \
                                           chunks_per_wg, codes, restarts, n_bases, recs, recs_cap, carry, flags)
-    if (lit && k == 15) PK_SQUEEZE(15);
-    else if (lit && k == 17) PK_SQUEEZE(17);
+    if (k == 15) PK_SQUEEZE(15);
+    else if (k == 17) PK_SQUEEZE(17);
     else PK_SQUEEZE(0);
 #undef PK_SQUEEZE
 }

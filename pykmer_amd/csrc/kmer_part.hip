@@ -7,11 +7,11 @@
 //   kmer_pack.hip  k_squeeze     FASTA text -> packed valid bases (2-bit codes + restart bits), per-record tallies
 //   kmer_fuse.hip  k_walk_sort   packed bases -> canonical k-mers (in registers) -> LDS counting sort by the level-1
 //                                digit (top b1 address bits) -> coalesced run writes into provisioned buckets
-//      k_count2 / k_rows2_scan   (k = 17)  per-workgroup histogram of the level-2 digit (next b2 bits)
-//                    inside each level-1 bucket, per-bucket column scan -> offsets + final bucket starts
-//   K5 k_scatter2    second pass, 16-bit records (address inside the final bucket).  k <= 15: the final buckets were
-//                    laid out from the same sampled estimate as the level-1 ones; every tile claims room for its
-//                    runs from their cursors (atomicAdd), there is no counting pass
+//      k_sample2 / k_rooms2 / k_bases2 / k_starts2   (2^15 < final buckets <= 2^18: k = 17, slices of k = 19) final-bucket
+//                    rooms from a sample of the level-1 records
+//   K5 k_scatter2    second pass by the next b2 address bits, 16-bit records (address inside the final bucket).  The final
+//                    buckets were laid out from an estimate (k <= 15: the same sample as the level-1 ones); every tile
+//                    claims room for its runs from their cursors (atomicAdd), there is no counting pass
 //   K6 k_bucket_count one workgroup per final bucket of 2^16 addresses: the slice of the u8 table
 //                    lives in LDS as 16-bit counters, ds_add per record, clamp, slice written to HBM
 //                    (read back first when an earlier feed already wrote it)
@@ -25,79 +25,13 @@
 // `flags[0]` is raised by the level-1 sort when a provisioned bucket ran out of room (kmer_fuse.hip); every
 // kernel below then returns without touching anything and the host repeats the level with exact sizes.
 #include <cstddef>
-#include <cstdlib>
 #include "part_common.h"
 
 namespace pk {
 
-// level-2 work split: bucket b is covered by workgroups wg2_start[b] .. wg2_start[b+1]-1, R2 records each
-__device__ __forceinline__ bool wg2_range(const uint32_t *__restrict__ wg2_start, const uint32_t *__restrict__ bucket_base,
-                                          const uint32_t *__restrict__ bucket_end, const PartPlan &pl, uint32_t &b, uint32_t &lo,
-                                          uint32_t &hi) {
-    const uint32_t w = blockIdx.x;
-    if (w >= wg2_start[pl.B1]) return false;
-    uint32_t a = 0, z = pl.B1;                              // last b with wg2_start[b] <= w
-    while (z - a > 1) { uint32_t m = (a + z) >> 1; if (wg2_start[m] <= w) a = m; else z = m; }
-    b = a;
-    uint64_t s = (uint64_t)bucket_base[b] + (uint64_t)(w - wg2_start[b]) * pl.R2;
-    uint64_t e = s + pl.R2;
-    if (e > bucket_end[b]) e = bucket_end[b];              // the bucket's records; the rest of its room stays unused
-    lo = (uint32_t)s; hi = (uint32_t)e;
-    return true;
-}
-
-__global__ __launch_bounds__(WG) void k_count2(const uint32_t *__restrict__ in, const uint32_t *__restrict__ wg2_start,
-                                               const uint32_t *__restrict__ bucket_base, const uint32_t *__restrict__ bucket_end, PartPlan pl,
-                                               uint32_t *__restrict__ hist_rows, const uint32_t *__restrict__ flags) {
-    __shared__ uint32_t h[512];
-    if (flags[0]) return;
-    for (uint32_t d = threadIdx.x; d < pl.B2; d += WG) h[d] = 0;
-    __syncthreads();
-    uint32_t b, lo, hi;
-    const bool live = wg2_range(wg2_start, bucket_base, bucket_end, pl, b, lo, hi);
-    const uint32_t shift = pl.fb_bits;
-    if (live) {
-        const uint32_t mask = pl.B2 - 1u;
-        for (uint32_t i = (lo & ~3u) + threadIdx.x * 4u; i < hi; i += WG * 4u) {      // 16 B per lane; edges masked
-            const uint4 v = *reinterpret_cast<const uint4 *>(in + i);
-            const uint32_t r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                if (i + q >= lo && i + q < hi) atomicAdd(&h[(r[q] >> shift) & mask], 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t d = threadIdx.x; d < pl.B2; d += WG) hist_rows[(uint64_t)blockIdx.x * pl.B2 + d] = live ? h[d] : 0u;
-}
-
-// K4: one workgroup per level-1 bucket, one thread per level-2 digit.
-// The level-2 output is compact again: final bucket starts count up from compact_base[b], the number of records in
-// the level-1 buckets before b.
-__global__ __launch_bounds__(512) void k_rows2_scan(const uint32_t *__restrict__ hist_rows, uint32_t *__restrict__ rowoff,
-                                                    const uint32_t *__restrict__ wg2_start, const uint32_t *__restrict__ compact_base,
-                                                    PartPlan pl, uint32_t *__restrict__ final_start, const uint32_t *__restrict__ flags) {
-    __shared__ uint32_t tot[512];
-    if (flags[0]) return;
-    const uint32_t b = blockIdx.x, d = threadIdx.x;
-    uint32_t acc = 0;
-    if (d < pl.B2)
-        for (uint32_t w = wg2_start[b]; w < wg2_start[b + 1]; w++) {
-            uint32_t v = hist_rows[(uint64_t)w * pl.B2 + d];
-            rowoff[(uint64_t)w * pl.B2 + d] = acc;
-            acc += v;
-        }
-    tot[d] = d < pl.B2 ? acc : 0;
-    __syncthreads();
-    if (d == 0) {
-        uint32_t a = compact_base[b];
-        for (uint32_t i = 0; i < pl.B2; i++) { uint32_t n = tot[i]; final_start[(uint64_t)b * pl.B2 + i] = a; a += n; }
-        if (b == pl.B1 - 1) final_start[(uint64_t)pl.B1 * pl.B2] = a;
-    }
-}
-
 // ---- sample2: final-bucket sizes from a sample of the level-1 records (2^15 < final buckets <= 2^18: k = 17, slices of k = 19).
 // One workgroup per level-1 bucket tallies the level-2 digit of every stride2-th group of 256 records in LDS (stride2 = 1:
-// all of them, i.e. exact).  It replaces the exact counting pass over ALL level-1 records (k_count2: 0.66 ms at k = 17).
+// all of them, i.e. exact).  It replaced an exact counting pass over ALL level-1 records (0.66 ms at k = 17).
 __global__ __launch_bounds__(1024) void k_sample2(const uint32_t *__restrict__ in, const uint32_t *__restrict__ bucket_base,
                                                   const uint32_t *__restrict__ bucket_end, PartPlan pl, uint32_t stride2,
                                                   uint32_t *__restrict__ tally, uint32_t *__restrict__ sampled_n,
@@ -214,25 +148,24 @@ __global__ __launch_bounds__(1024) void k_starts2(uint32_t n_final, const uint32
     final_start[i] = a; cursor2[i] = a; cap2_end[i] = a + cap2_end[i];
 }
 
-// CLAIM: no precomputed offsets; every tile claims room for its runs from the final buckets' cursors, inside the
-// room k_provision gave each of them (cap_end; a bucket that outgrows it raises flags[0], see part_common.h).  Where
+// No precomputed offsets: every tile claims room for its runs from the final buckets' cursors, inside the room
+// k_provision / k_rooms2 gave each of them (cap_end; a bucket that outgrows it raises flags[0], see part_common.h).  Where
 // a record lands inside its final bucket then depends on timing -- the bucket's contents as a multiset do not.
-// The CLAIM launch is persistent (two workgroups per CU) over work items of R2 records and XCD-affine: workgroup x
-// runs on XCD x % 8 (round-robin dispatch), and takes items of the level-1 buckets b with b % 8 == x % 8 only.  All
-// writers of one final bucket then share one L2: the partly written cache lines where one tile's run ends and the
-// next one's begins are merged there instead of travelling to HBM twice, and a bucket's cursor lives in one L2.
-// `pos` (wg2_start + B1 + 1) is the running item count over the buckets in that order (k_level1_finish).
-// NT threads x PER records = one tile.  The CLAIM launch runs as 512 x 32: two workgroups share a CU (72 KiB of LDS and
+// The launch is persistent (two workgroups per CU) over work items of R2 records and XCD-affine: workgroup x runs on
+// XCD x % 8 (round-robin dispatch), and takes items of the level-1 buckets b with b % 8 == x % 8 only.  All writers of
+// one final bucket then share one L2: the partly written cache lines where one tile's run ends and the next one's
+// begins are merged there instead of travelling to HBM twice, and a bucket's cursor lives in one L2.
+// `pos` (wg2_start) is the running item count over the buckets in that order (k_level1_finish).
+// NT threads x PER records = one tile.  The launch runs as 512 x 32: two workgroups share a CU (72 KiB of LDS and
 // 128 registers each), so one sorts while the other waits at a barrier or for its stores.
 // REC24: the level-1 records are 3-byte records in two planes (32-bit k-mers; part_common.h), `in` is the 16-bit plane.
 // (Measured and kept out: the claiming launch as 1024 x 16 at 64 registers -- two workgroups = 32 waves per CU instead of 16:
 // 1.14 -> 1.19 ms with write-out batches of four, 2.1 ms with eight (46 spilled registers).)
-template <bool CLAIM, int NT, int PER, bool REC24 = false>
+template <int NT, int PER, bool REC24 = false>
 __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__ in, const uint32_t *__restrict__ wg2_start,
-                                                   const uint32_t *__restrict__ bucket_base, const uint32_t *__restrict__ bucket_end,
-                                                   const uint32_t *__restrict__ rowoff, const uint32_t *__restrict__ final_start, PartPlan pl,
+                                                   const uint32_t *__restrict__ bucket_base, const uint32_t *__restrict__ bucket_end, PartPlan pl,
                                                    void *__restrict__ out, uint32_t *__restrict__ cursor, const uint32_t *__restrict__ cap_end,
-                                                   uint32_t dump, uint32_t *__restrict__ flags, uint32_t xcd_affine) {
+                                                   uint32_t dump, uint32_t *__restrict__ flags) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     ScatterLds &L = *reinterpret_cast<ScatterLds *>(smem);
     if (flags[0]) return;
@@ -240,9 +173,6 @@ __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__
     const uint32_t low_mask = (1u << shift) - 1u;
     for (uint32_t i = threadIdx.x; i < 512; i += NT) { L.hist[i] = 0; L.run[i] = 0; }
     __syncthreads();
-#ifdef PK_PHASE_PROF
-    unsigned long long phase_prof[5] = {0, 0, 0, 0, 0};                   // thread 0: unpack, count, scan, park, store (cycles)
-#endif
     // records [lo, hi) of level-1 bucket b: 16-byte aligned windows of TILE records, the first / last partly masked.
     // The next window's loads are issued before the current tile is sorted, so they fly during its barriers.
     typedef uint32_t Quad __attribute__((ext_vector_type(4)));
@@ -275,9 +205,6 @@ __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__
         fetch(lo & ~3u, nxt);
         settle();
         for (uint32_t win = lo & ~3u; win < hi; win += TILE) {
-#ifdef PK_PHASE_PROF
-            const unsigned long long tile_t0 = __builtin_readcyclecounter();
-#endif
             const uint32_t v_lo = max(lo, win), v_hi = min(hi, win + (uint32_t)TILE);
             const uint32_t n_tile = v_hi - v_lo;
             uint32_t r[PER];
@@ -301,30 +228,15 @@ __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__
                 }
             }
             if (win + TILE < hi) fetch(win + TILE, nxt);
-            uint32_t *cl = CLAIM ? cursor + (uint64_t)b * B : nullptr;
-            const uint32_t *ce = CLAIM ? cap_end + (uint64_t)b * B : nullptr;
-#ifdef PK_PHASE_PROF
-            if (threadIdx.x == 0) phase_prof[0] += __builtin_readcyclecounter() - tile_t0;
-            unsigned long long *prof = phase_prof;
-#else
-            unsigned long long *prof = nullptr;
-#endif
-            if (full) scatter_tile<uint32_t, false, NT, PER, 512, true, PK_PB_L2, PK_SB_L2, REC24>(L, r, 0u, n_tile, shift, B, low_mask, true, out, settle, cl, ce, dump, flags, nullptr, prof);
-            else scatter_tile<uint32_t, false, NT, PER, 512, false, PK_PB_L2, PK_SB_L2, REC24>(L, r, okm, n_tile, shift, B, low_mask, true, out, settle, cl, ce, dump, flags, nullptr, prof);
+            uint32_t *cl = cursor + (uint64_t)b * B;
+            const uint32_t *ce = cap_end + (uint64_t)b * B;
+            if (full) scatter_tile<uint32_t, false, NT, PER, 512, true, 8, REC24>(L, r, 0u, n_tile, shift, B, low_mask, true, out, settle, cl, ce, dump, flags);
+            else scatter_tile<uint32_t, false, NT, PER, 512, false, 8, REC24>(L, r, okm, n_tile, shift, B, low_mask, true, out, settle, cl, ce, dump, flags);
         }
     };
-    if (!CLAIM) {
-        uint32_t b, lo, hi;
-        if (!wg2_range(wg2_start, bucket_base, bucket_end, pl, b, lo, hi)) return;  // uniform per workgroup
-        if (threadIdx.x < B) L.run[threadIdx.x] = final_start[(uint64_t)b * B + threadIdx.x] + rowoff[(uint64_t)blockIdx.x * B + threadIdx.x];
-        __syncthreads();
-        item(b, lo, hi);
-        return;
-    }
-    const uint32_t *pos = wg2_start + pl.B1 + 1;
+    const uint32_t *pos = wg2_start;
     const uint32_t per = pl.B1 >> 3;                                     // level-1 buckets per XCD class (B1 >= 16 with two levels)
-    uint32_t o_lo = 0, o_hi = pl.B1, first = blockIdx.x, step = gridDim.x;
-    if (xcd_affine) { const uint32_t c = blockIdx.x & 7u; o_lo = c * per; o_hi = o_lo + per; first = blockIdx.x >> 3; step = gridDim.x >> 3; }
+    const uint32_t o_lo = (blockIdx.x & 7u) * per, o_hi = o_lo + per, first = blockIdx.x >> 3, step = gridDim.x >> 3;
     const uint32_t w_end = pos[o_hi];
     for (uint32_t w = pos[o_lo] + first; w < w_end; w += step) {         // uniform per workgroup
         uint32_t a = o_lo, z = o_hi;                                     // last position with pos[a] <= w
@@ -334,10 +246,6 @@ __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__
         const uint64_t e = min(s + pl.R2, (uint64_t)bucket_end[b]);
         item(b, (uint32_t)s, (uint32_t)e);
     }
-#ifdef PK_PHASE_PROF
-    if (threadIdx.x == 0)
-        for (int i = 0; i < 5; i++) atomicAdd(reinterpret_cast<unsigned long long *>(flags) - 1 + 9 + i, phase_prof[i]);   // behind the level-1 kernel's five
-#endif
 }
 
 // ------------------------------------------------------------------ K6: count in LDS ------------
@@ -412,8 +320,8 @@ struct SliceTally {
 // bucket's (few) records but counting only its own part of the address range -- the LDS counters shrink
 // with the part, so several workgroups fit on a CU and hide each other's phases.
 // LEAN (whole-bucket kernel, i.e. dense tables): records of a dense bucket are counted by eight no-return LDS adds and nothing
-// else.  The half-bucket kernel (sparse tables, 64 registers) keeps the form it was tuned with: the same change there moved its
-// register allocation and cost 11 % (5.3 -> 5.9 ms at k = 17).
+// else.  The half-bucket form (the recount of k_bucket_count_bytes) keeps the form it was tuned with: the same change there
+// cost the half-bucket kernel of the time 11 % (5.3 -> 5.9 ms at k = 17) by moving its register allocation.
 template <int T, bool LEAN, bool NOREC = false>
 __device__ __forceinline__ void bucket_count_body(const uint16_t *__restrict__ recs, const uint32_t *__restrict__ final_start,
                                                   const uint32_t *__restrict__ final_end, uint32_t fb_bits, uint32_t split_bits,
@@ -604,9 +512,8 @@ __device__ __forceinline__ void bucket_count_body(const uint16_t *__restrict__ r
     }
 }
 
-// Two entry points for the same body.  A whole bucket (dense tables) needs all 128 KiB of LDS a workgroup may
-// have, so one workgroup sits on a CU whatever its register count -- no cap.  Half buckets (sparse tables) are
-// meant to run two to a CU, which takes at most 64 vector registers.
+// A whole bucket of 2^16 addresses needs all 128 KiB of LDS a workgroup may have, so one workgroup sits on a CU whatever
+// its register count -- no cap.
 template <int T>
 __global__ __launch_bounds__(T) void k_bucket_count(const uint16_t *__restrict__ recs, const uint32_t *__restrict__ final_start,
                                                     const uint32_t *__restrict__ final_end, uint32_t fb_bits, uint32_t split_bits,
@@ -617,17 +524,6 @@ __global__ __launch_bounds__(T) void k_bucket_count(const uint16_t *__restrict__
     if (flags[0]) return;
     bucket_count_body<T, true>(recs, final_start, final_end, fb_bits, split_bits, table8, fresh, hist_rep, smem, dh, blockIdx.x);
 }
-template <int T>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
-void k_bucket_count_half(const uint16_t *__restrict__ recs, const uint32_t *__restrict__ final_start, const uint32_t *__restrict__ final_end,
-                         uint32_t fb_bits, uint32_t split_bits, uint8_t *__restrict__ table8, uint32_t fresh, unsigned long long *__restrict__ hist_rep,
-                         const uint32_t *__restrict__ flags) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ int dh[256];
-    if (flags[0]) return;
-    bucket_count_body<T, false>(recs, final_start, final_end, fb_bits, split_bits, table8, fresh, hist_rep, smem, dh, blockIdx.x);
-}
-
 template <int T, bool FRESH>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_bucket_count_half_lean(const uint16_t *__restrict__ recs, const uint32_t *__restrict__ final_start, const uint32_t *__restrict__ final_end,
@@ -645,8 +541,8 @@ void k_bucket_count_half_lean(const uint16_t *__restrict__ recs, const uint32_t 
 // bucket keeps the bucket's 64 KiB slice of the table in LDS *as it will lie in HBM*: a record adds 1 << 8 * (a & 3) to
 // the dword holding its byte, the add returns the byte's previous value (which is what the histogram needs), and the
 // slice leaves LDS by a straight 16-byte copy -- no 16-bit counters to clamp and pack, no second workgroup reading the
-// same records, half the LDS zeroing per table byte (k_bucket_count_half: two workgroups per bucket, each with 2^15 16-bit
-// counters, each reading all of the bucket's records).
+// same records, half the LDS zeroing per table byte (than the earlier half-bucket kernel: two workgroups per bucket, each
+// with 2^15 16-bit counters, each reading all of the bucket's records).
 // A byte cannot saturate: the add that finds 255 wraps it and carries into its neighbour.  That add SEES the 255, so it
 // raises a flag, and the workgroup then throws its LDS image away and counts the bucket again the old way (both halves,
 // one after the other, 16-bit counters with clamping).  Hot k-mers of period <= 3 never get here (side list), so this is
@@ -832,9 +728,8 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
     pl.fb_bits = pl.addr_bits < 16 ? pl.addr_bits : 16;
     // Dense tables of 32-bit k-mers (>= 1 input byte per 8 addresses, e.g. a genome at k = 15): final buckets of 2^15
     // addresses, so that TWO bucket-count workgroups (64 KiB of counters each) share a CU and one's load / count /
-    // write-back phases hide behind the other's.  Sparse tables get there by other means (k_bucket_count_half).
-    static const uint32_t dense_shift = getenv("PK_DENSE_SHIFT") ? (uint32_t)atoi(getenv("PK_DENSE_SHIFT")) : 3u;
-    if (k <= 15 && pl.addr_bits >= 24 && n_bytes >= (((uint64_t)1 << pl.addr_bits) >> dense_shift)) pl.fb_bits = 15;
+    // write-back phases hide behind the other's.  Sparse tables get there by other means (k_bucket_count_bytes).
+    if (k <= 15 && pl.addr_bits >= 24 && n_bytes >= (((uint64_t)1 << pl.addr_bits) >> 3)) pl.fb_bits = 15;
     const uint32_t bucket_bits = pl.addr_bits - pl.fb_bits;
     // one level while its digits fit the LDS arrays of the sort kernel that runs level 1 (kmer_fuse.hip: 128 digits for
     // 32-bit k-mers, 512 for 64-bit ones), two levels of about equal width otherwise
@@ -849,24 +744,17 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
     if (pl.n_wg0 == 0) pl.n_wg0 = 1;
     pl.G = (pl.n_chunks + pl.n_wg0 - 1) / pl.n_wg0;
     if (pl.G == 0) pl.G = 1;
-    static const uint32_t wg1_env = getenv("PK_WG1") ? (uint32_t)atoi(getenv("PK_WG1")) : 0u;
-    const uint32_t wg1 = wg1_env ? wg1_env : 4096u;       // shorter stretches per workgroup even out the last round (1024: 1.42 ms, 4096: 1.39)
+    const uint32_t wg1 = 4096u;                            // shorter stretches per workgroup even out the last round (1024: 1.42 ms, 4096: 1.39)
     pl.n_wg1 = pl.n_chunks < wg1 ? pl.n_chunks : wg1;
     if (pl.n_wg1 == 0) pl.n_wg1 = 1;
     pl.G1 = (pl.n_chunks + pl.n_wg1 - 1) / pl.n_wg1;
     if (pl.G1 == 0) pl.G1 = 1;
-    uint64_t r2 = (n_bytes + 1023) / 1024;
-    pl.R2 = r2 < (uint64_t)TILE ? (uint64_t)TILE : ((r2 + TILE - 1) / TILE) * TILE;
-    pl.n_wg2_max = (uint32_t)(n_bytes / pl.R2) + pl.B1 + 1;
+    pl.R2 = 4u * TILE;                                     // level 2 claims its room tile by tile: small work items for a persistent grid
     // bucket sizes are estimated from every 16th slot; small inputs are counted exactly
     pl.sample_stride = pl.n_chunks >= 1024u ? 16u : 1u;
     const uint64_t nfb = (uint64_t)pl.B1 * pl.B2;
     pl.n_tally = (pl.b2 && nfb <= 32768 && pl.addr_bits <= 30) ? (uint32_t)nfb : pl.B1;
     pl.sample2 = (pl.b2 && pl.n_tally == pl.B1 && nfb <= 262144 && pl.B1 >= 8u) ? 1u : 0u;
-    if (pl.n_tally > pl.B1 || pl.sample2) {                // level 2 claims its room tile by tile: small work items for a persistent grid
-        pl.R2 = 4u * TILE;
-        pl.n_wg2_max = (uint32_t)(n_bytes / pl.R2) + pl.B1 + 1;
-    }
     // room for the buckets: the sampled estimate can reach the slot capacity (+1 per bucket from rounding up), each
     // bucket gets 12.5 % + a constant + alignment on top of it (k_provision)
     const uint64_t est1 = (uint64_t)pl.n_chunks * TILE + pl.B1, est2 = (uint64_t)pl.n_chunks * TILE + nfb;
@@ -878,7 +766,6 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
 size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace *lay) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const uint64_t nfb = (uint64_t)pl.B1 * pl.B2;
-    const bool laid_out2 = pl.n_tally > pl.B1 || pl.sample2; // final buckets provisioned from an estimate
     size_t o = 0;
     lay->codes = o; o += up((size_t)pl.n_chunks * SLOT_CODE_WORDS * 4);
     lay->restarts = o; o += up((size_t)pl.n_chunks * SLOT_RST_WORDS * 4);
@@ -887,10 +774,9 @@ size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace 
     lay->tally_tot = o; o += up(pl.sample2 ? (size_t)nfb * 4 + (size_t)(pl.B1 + 1024) * 4 : (size_t)pl.n_tally * 4);   // sample2: + sampled counts, block totals
     lay->bucket_base = o; o += up((size_t)(pl.B1 + 1) * 4);
     lay->bucket_end = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->compact_base = o; o += up((size_t)(pl.B1 + 1) * 4);
     lay->cursor1 = o; o += up((size_t)(pl.B1 + 1) * 4);
     lay->cap_end = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->wg2_start = o; o += up((size_t)(pl.B1 + 1) * 8);   // by bucket, and in XCD-class order
+    lay->wg2_start = o; o += up((size_t)(pl.B1 + 1) * 4);   // level-2 work items, buckets in XCD-class order
     lay->final_start = o; o += up((size_t)(nfb + 1) * 4);
     lay->cursor2 = o; o += up((size_t)(nfb + 1) * 4);
     lay->cap2_end = o; o += up((size_t)(nfb + 1) * 4);
@@ -899,9 +785,7 @@ size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace 
     lay->out1 = o; o += !pl.b2 ? up((size_t)(pl.capacity1 + TILE + 64) * 2)
                      : pl.k <= 15 ? level1_hi_plane_offset(pl.capacity1) + up((size_t)(pl.capacity1 + TILE + 64))
                                   : up((size_t)(pl.capacity1 + TILE + 64) * 4);
-    lay->hist2 = o; o += up(laid_out2 ? 256 : (size_t)pl.n_wg2_max * pl.B2 * 4);          // per-workgroup digit counts: only without claims
-    lay->rowoff2 = o; o += up(laid_out2 ? 256 : (size_t)pl.n_wg2_max * pl.B2 * 4);
-    lay->out2 = o; o += up(!pl.b2 ? 256 : laid_out2 ? (size_t)(pl.capacity2 + TILE + 64) * 2 : (size_t)(n_bytes + 64) * 2);
+    lay->out2 = o; o += up(!pl.b2 ? 256 : (size_t)(pl.capacity2 + TILE + 64) * 2);
     lay->side_cap = n_bytes + 16;                          // every side entry stands for >= 1 k-mer
     lay->side = o; o += up((size_t)lay->side_cap * 8);
     lay->side_n = o; o += 256;                             // side-list length (u64), then the flags word
@@ -910,11 +794,9 @@ size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace 
 
 void part_set_attributes() {
     fuse_set_attributes();
-    hipFuncSetAttribute((const void *)k_scatter2<false, SC_T, SC_PER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCATTER_LDS_NARROW);
-    hipFuncSetAttribute((const void *)k_scatter2<true, 512, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCATTER_LDS_NARROW);
-    hipFuncSetAttribute((const void *)k_scatter2<true, 512, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCATTER_LDS_NARROW);
+    hipFuncSetAttribute((const void *)k_scatter2<512, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCATTER_LDS_NARROW);
+    hipFuncSetAttribute((const void *)k_scatter2<512, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCATTER_LDS_NARROW);
     hipFuncSetAttribute((const void *)k_bucket_count<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    hipFuncSetAttribute((const void *)k_bucket_count_half<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     hipFuncSetAttribute((const void *)k_bucket_count_half_lean<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     hipFuncSetAttribute((const void *)k_bucket_count_half_lean<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     hipFuncSetAttribute((const void *)k_bucket_count_bytes<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, K6_BYTES_LDS);
@@ -925,16 +807,11 @@ void part_set_attributes() {
 extern "C" int pk_diag_occupancy(int which) {
     int n = -1;
     hipError_t e = hipErrorInvalidValue;
-    if (which == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_bucket_count_half<1024>, 1024, 65536);
+    if (which == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_bucket_count<1024>, 1024, 128 * 1024);
     if (which == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_bucket_count_bytes<1024>, 1024, K6_BYTES_LDS);
     if (which == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_bucket_count_half_lean<1024, true>, 1024, 65536);
-    if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_scatter2<true, 512, 32>, 512, SCATTER_LDS_NARROW);
+    if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_scatter2<512, 32>, 512, SCATTER_LDS_NARROW);
     return e == hipSuccess ? n : -(int)e;
-}
-
-static bool pk_bytes_enabled() {                                         // PK_K6_BYTES=0: the two-halves kernel for sparse tables (comparison runs)
-    static const bool on = !(getenv("PK_K6_BYTES") && atoi(getenv("PK_K6_BYTES")) == 0);
-    return on;
 }
 
 // Everything behind the squeeze pass for one feed: bucket layout (sampled with `stride`; 1 = exact), the fused
@@ -947,23 +824,24 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
     const uint32_t *n_bases = (const uint32_t *)(ws + lay.n_bases);
     uint32_t *tally_rows = (uint32_t *)(ws + lay.tally_rows), *tally_tot = (uint32_t *)(ws + lay.tally_tot);
     uint32_t *bucket_base = (uint32_t *)(ws + lay.bucket_base), *bucket_end = (uint32_t *)(ws + lay.bucket_end);
-    uint32_t *compact_base = (uint32_t *)(ws + lay.compact_base), *cursor1 = (uint32_t *)(ws + lay.cursor1), *cap_end = (uint32_t *)(ws + lay.cap_end);
+    uint32_t *cursor1 = (uint32_t *)(ws + lay.cursor1), *cap_end = (uint32_t *)(ws + lay.cap_end);
     uint32_t *wg2_start = (uint32_t *)(ws + lay.wg2_start), *final_start = (uint32_t *)(ws + lay.final_start);
     uint32_t *cursor2 = (uint32_t *)(ws + lay.cursor2), *cap2_end = (uint32_t *)(ws + lay.cap2_end);
-    uint32_t *hist2 = (uint32_t *)(ws + lay.hist2), *rowoff2 = (uint32_t *)(ws + lay.rowoff2);
     void *out1 = ws + lay.out1, *out2 = ws + lay.out2;
     unsigned long long *side = (unsigned long long *)(ws + lay.side), *side_n = (unsigned long long *)(ws + lay.side_n);
     uint32_t *flags = (uint32_t *)(side_n + 1);
     const uint32_t nfb = pl.B1 * pl.B2;
     const bool laid_out2 = pl.n_tally > pl.B1 || pl.sample2;
     if (pl.B1 > (pl.k <= 15 ? 128u : 512u) || pl.B2 > 512u || pl.fb_bits > 16u) return -3;   // what the kernels' LDS arrays are sized for
-    if (pl.k <= 15 && pl.b2 && (!laid_out2 || pl.addr_bits - pl.b1 > 24u)) return -3;           // 3-byte level-1 records: only the claiming level 2 reads them
+    // Level 2 always claims: check_k caps addr_bits at 34, so a two-level plan has bucket_bits <= 18 and B1 >= 16, and its final
+    // buckets are either tallied while sampling (addr_bits <= 30: B1 * B2 > B1) or sized from the level-1 records (sample2)
+    if (pl.b2 && !laid_out2) return -3;
+    if (pl.k <= 15 && pl.b2 && pl.addr_bits - pl.b1 > 24u) return -3;                           // 3-byte level-1 records (part_common.h)
     if (!armed && hipMemsetAsync(side_n, 0, PART_FLAG_WORDS * 4, s) != hipSuccess) return -2;   // side-list length + flags
     launch_provision(codes, restarts, n_bases, st2, pl, stride, tally_rows, tally_tot, bucket_base, cursor1, cap_end, final_start, cursor2, cap2_end,
                      flags, s);
     if (ev_sort_begin) hipEventRecord(ev_sort_begin, s);
-    launch_walk_sort(codes, restarts, n_bases, st2, pl, out1, cursor1, cap_end, flags, bucket_base, bucket_end, compact_base, wg2_start, side, side_n,
-                     lay.side_cap, s);
+    launch_walk_sort(codes, restarts, n_bases, st2, pl, out1, cursor1, cap_end, flags, bucket_base, bucket_end, wg2_start, side, side_n, lay.side_cap, s);
     if (ev_sort_end) hipEventRecord(ev_sort_end, s);
     const uint16_t *final_recs = (const uint16_t *)out1;
     const uint32_t *k6_start = bucket_base, *k6_end = bucket_end;        // b2 == 0: the level-1 buckets are the final ones
@@ -979,36 +857,25 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
         hipLaunchKernelGGL(k_starts2, dim3(n_blocks), dim3(1024), 0, s, nfb, (const uint32_t *)block_tot, final_start, cursor2, cap2_end,
                            (const uint32_t *)flags);
     }
-    if (laid_out2) {
-        static const uint32_t xcd_affine = getenv("PK_XCD") ? (uint32_t)atoi(getenv("PK_XCD")) : 1u;
+    if (pl.b2) {
         // 512 would be the resident two per CU (1.21 ms); more and shorter walks even out the end: 4096 -> 1.17 ms (k = 17: 1.44 -> 1.38).
+        // A multiple of 8: every XCD class gets the same number of workgroups.
         // Measured and kept out: level 2 launched in 2 / 4 / 8 parts (ranges of level-1 buckets) with the bucket count of part p
         // on a second stream beside level 2 of part p + 1 (one workgroup of each fits a CU's LDS): 1.91 ms for the two
         // stages back to back, 2.03 / 2.12 / 2.44 overlapped -- every part pays its own ragged end, and the two kernels
         // do not hide each other (both live on the LDS pipe).
-        static const uint32_t grid2_env = getenv("PK_GRID2") ? (uint32_t)atoi(getenv("PK_GRID2")) : 4096u;
-        const uint32_t grid2 = grid2_env < 8u ? 8u : (grid2_env & ~7u);    // a multiple of 8: every XCD class gets the same number of workgroups
+        const uint32_t grid2 = 4096u;
         if (pl.k <= 15)
-            hipLaunchKernelGGL((k_scatter2<true, 512, 32, true>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
-                               bucket_base, bucket_end, (const uint32_t *)nullptr, final_start, pl, out2, cursor2, (const uint32_t *)cap2_end,
-                               (uint32_t)pl.capacity2, flags, xcd_affine);
+            hipLaunchKernelGGL((k_scatter2<512, 32, true>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
+                               bucket_base, bucket_end, pl, out2, cursor2, (const uint32_t *)cap2_end, (uint32_t)pl.capacity2, flags);
         else
-            hipLaunchKernelGGL((k_scatter2<true, 512, 32>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
-                               bucket_base, bucket_end, (const uint32_t *)nullptr, final_start, pl, out2, cursor2, (const uint32_t *)cap2_end,
-                               (uint32_t)pl.capacity2, flags, xcd_affine);
+            hipLaunchKernelGGL((k_scatter2<512, 32>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
+                               bucket_base, bucket_end, pl, out2, cursor2, (const uint32_t *)cap2_end, (uint32_t)pl.capacity2, flags);
         final_recs = (const uint16_t *)out2; k6_start = final_start; k6_end = cursor2;   // a final bucket ends where its cursor stopped
-    } else if (pl.b2) {
-        hipLaunchKernelGGL(k_count2, dim3(pl.n_wg2_max), dim3(WG), 0, s, (const uint32_t *)out1, wg2_start, bucket_base, bucket_end, pl, hist2,
-                           (const uint32_t *)flags);
-        hipLaunchKernelGGL(k_rows2_scan, dim3(pl.B1), dim3(512), 0, s, hist2, rowoff2, wg2_start, compact_base, pl, final_start, (const uint32_t *)flags);
-        hipLaunchKernelGGL((k_scatter2<false, SC_T, SC_PER>), dim3(pl.n_wg2_max), dim3(SC_T), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
-                           bucket_base, bucket_end, rowoff2, final_start, pl, out2, (uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, flags, 0u);
-        final_recs = (const uint16_t *)out2; k6_start = final_start; k6_end = nullptr;
     }
     if (ev_part_end) hipEventRecord(ev_part_end, s);
     // sparse tables (few records per 2^16-address bucket, k=17): 2^split workgroups per bucket, see k_bucket_count
-    static const uint64_t sparse_max = getenv("PK_SPARSE_MAX") ? (uint64_t)atoll(getenv("PK_SPARSE_MAX")) : 8192u;
-    const bool sparse = pl.fb_bits == 16 && n_bytes / nfb < sparse_max;
+    const bool sparse = pl.fb_bits == 16 && n_bytes / nfb < 8192u;
     const uint32_t split = sparse ? 1u : 0u;
     const size_t part_addrs = (size_t)1 << (pl.fb_bits - split);
     const size_t lds6 = part_addrs * 2 < 64 ? 64 : part_addrs * 2;
@@ -1020,12 +887,9 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
     else if (pl.fb_bits == 15)
         hipLaunchKernelGGL((k_bucket_count_half_lean<1024, false>), dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
                            fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);
-    else if (split && pk_bytes_enabled())
+    else if (split)
         hipLaunchKernelGGL(k_bucket_count_bytes<1024>, dim3(nfb), dim3(1024), K6_BYTES_LDS, s, final_recs, k6_start, k6_end, table8, fresh ? 1u : 0u, bucket_hist,
                            (const uint32_t *)flags);
-    else if (split)
-        hipLaunchKernelGGL(k_bucket_count_half<1024>, dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
-                           fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);
     else
         hipLaunchKernelGGL(k_bucket_count<1024>, dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
                            fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);

@@ -12,28 +12,6 @@ constexpr int SC_T = 1024;           // threads of the scatter / bucket-count wo
 constexpr int SC_PER = 16;           // records per thread per tile
 constexpr int TILE = SC_T * SC_PER;  // 16384 records per tile = one FASTA chunk's worth (one base per byte at most)
 
-// batch sizes of the sort tile's parking / write-out phases (scatter_tile; 0 = record by record), per level
-#ifndef PK_PB_L1
-#define PK_PB_L1 0
-#endif
-#ifndef PK_SB_L1
-#define PK_SB_L1 8          // 32-bit k-mers only (the 64-bit kernel loses with it: 2.22 -> 2.29 ms)
-#endif
-#ifndef PK_PB_L2
-#define PK_PB_L2 0
-#endif
-#ifndef PK_SB_L2
-#define PK_SB_L2 8
-#endif
-// experiments (tools/build_variant.sh): PK_CNT0 = count phase without per-record branches (empty slots add zero);
-// PK_UFULL = run write-out batches that lie wholly inside the tile skip the per-lane bounds test
-#ifndef PK_CNT0
-#define PK_CNT0 0
-#endif
-#ifndef PK_UFULL
-#define PK_UFULL 1          // k = 15: level 1 1.314 -> 1.285 ms (PK_CNT0: 1.68 ms -- the holes' LDS adds cost more than their branches)
-#endif
-
 // ------------------------------------------------------------------ hot keys ---------------------
 // Tandem repeats (poly-A/T, (AT)n, (AAG)n ...) put tens of millions of identical canonical k-mers on a
 // handful of addresses; routed like everything else they would all land in ONE final bucket, i.e. on
@@ -171,22 +149,14 @@ constexpr size_t SCATTER_LDS_WIDE = sizeof(ScatterLds);            // 104 KiB
 // OFF32: every output index of this kernel is below 2^31 (the host cuts feeds of 32-bit k-mers so that both bucket areas
 // stay below that: feed_piece), so byte offsets fit 32 bits and the stores take a scalar base + a 32-bit lane offset
 // instead of a 64-bit address per record.
-template <typename RIN, bool WIDE, int NT = SC_T, int PER = SC_PER, int NB = 512, bool FULL = false, int PB = 0, int SB = 0, bool OFF32 = false, class Settle>
+template <typename RIN, bool WIDE, int NT = SC_T, int PER = SC_PER, int NB = 512, bool FULL = false, int SB = 0, bool OFF32 = false, class Settle>
 __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[PER], uint32_t okm, uint32_t n_tile,
                                              uint32_t shift, uint32_t B, uint32_t low_mask, bool out16, void *__restrict__ out,
                                              Settle &&settle, uint32_t *claim = nullptr, const uint32_t *__restrict__ cap_end = nullptr,
                                              uint32_t dump = 0, uint32_t *overflow = nullptr, uint8_t *__restrict__ out_hi = nullptr,
-                                             unsigned long long *prof = nullptr, const uint32_t *watch = nullptr, uint32_t watch_limit = 0,
+                                             const uint32_t *watch = nullptr, uint32_t watch_limit = 0,
                                              bool *watch_hit = nullptr) {
     static_assert(NT * PER == TILE, "tile shape");
-    // PK_PHASE_PROF (experiment builds): thread 0 adds the cycles of this tile's phases -- count, scan, park, store, each up to
-    // its closing barrier -- to prof[1..4]
-#ifdef PK_PHASE_PROF
-    unsigned long long pt = __builtin_readcyclecounter();
-#define PK_PROF_MARK(i) do { if (prof && threadIdx.x == 0) { const unsigned long long pn = __builtin_readcyclecounter(); prof[i] += pn - pt; pt = pn; } } while (0)
-#else
-#define PK_PROF_MARK(i) do { } while (0)
-#endif
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t dbits = (uint32_t)__builtin_ctz(B);
     auto digit_of = [&](const RIN &x) -> uint32_t {
@@ -211,18 +181,14 @@ __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[
             __hip_atomic_fetch_add(&L.hist[KEEP_DG ? dg[KEEP_DG ? j : 0] : slot_digit(j)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     } else {
         // 32 records per thread: every record under its own test (32 digits in registers spill; scratch digits instead of
-        // the tests: 1.42 -> 1.60 ms; a wave-uniform path without the tests for waves whose slots are all full: 1.32 -> 1.36)
+        // the tests: 1.42 -> 1.60 ms; a wave-uniform path without the tests for waves whose slots are all full: 1.32 -> 1.36;
+        // empty slots adding zero on their stale digit instead of the tests: 1.31 -> 1.68)
 #pragma unroll
-        for (int j = 0; j < PER; j++) {
-            if (PK_CNT0 && !FULL) {
-                // no branch: an empty slot adds zero to the counter its (stale but in-range) digit names
-                __hip_atomic_fetch_add(&L.hist[digit_of(r[j])], (okm >> j) & 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else if (FULL || ((okm >> j) & 1u)) __hip_atomic_fetch_add(&L.hist[digit_of(r[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        for (int j = 0; j < PER; j++)
+            if (FULL || ((okm >> j) & 1u)) __hip_atomic_fetch_add(&L.hist[digit_of(r[j])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (!FULL && threadIdx.x < 64u) L.off[NB + threadIdx.x] = (uint32_t)TILE + threadIdx.x;   // where empty slots park (adds of zero)
     __syncthreads();
-    PK_PROF_MARK(1);
     // `watch` (the hot-key table's fill): looked at by ONE thread between the tile's first two barriers -- nothing writes it
     // there -- and handed to all behind the second, so the caller's decision to flush is uniform although no barrier
     // closes the tile any more
@@ -262,52 +228,30 @@ __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[
         }
     }
     __syncthreads();
-    PK_PROF_MARK(2);
     if (watch_hit) *watch_hit = L.pad_[0] != 0u;
     if (n_tile == ~0u) n_tile = L.total;
-    if (PK_UFULL) n_tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_tile);   // uniform by construction; now in a scalar register
-    // Parking.  PB == 0: record by record (returning add, then the write it places); every add is waited for on the spot
-    // -- the compiler may not move an LDS write across the next atomic -- so a thread walks a chain of PER LDS round
-    // trips, which the other waves of the CU cover.  PB > 0: PB returning adds back to back, then their PB writes --
-    // measured and not used: level 1 1.47 -> 1.68 ms (PB = 8), 1.65 (PB = 4); level 2 unchanged.
-    if constexpr (PB == 0) {
-        if (BRANCH_FREE) {
+    n_tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_tile);   // uniform by construction; now in a scalar register
+    // Parking, record by record (returning add, then the write it places); every add is waited for on the spot -- the
+    // compiler may not move an LDS write across the next atomic -- so a thread walks a chain of PER LDS round trips, which
+    // the other waves of the CU cover.  (PB returning adds back to back, then their PB writes, measured and not used: level 1
+    // 1.47 -> 1.68 ms with PB = 8, 1.65 with 4; level 2 unchanged.)
+    if (BRANCH_FREE) {
 #pragma unroll
-            for (int j = 0; j < PER; j++) {
-                const uint32_t d = KEEP_DG ? dg[KEEP_DG ? j : 0] : slot_digit(j);
-                const uint32_t p = atomicAdd(&L.off[d], (FULL || ((okm >> j) & 1u)) ? 1u : 0u);
+        for (int j = 0; j < PER; j++) {
+            const uint32_t d = KEEP_DG ? dg[KEEP_DG ? j : 0] : slot_digit(j);
+            const uint32_t p = atomicAdd(&L.off[d], (FULL || ((okm >> j) & 1u)) ? 1u : 0u);
+            if (WIDE) { L.rec[p] = (uint32_t)((uint64_t)r[j] & low_mask); L.dig[p] = (uint16_t)d; }
+            else L.rec[p] = (uint32_t)r[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < PER; j++)
+            if (FULL || ((okm >> j) & 1u)) {
+                const uint32_t d = digit_of(r[j]);
+                const uint32_t p = atomicAdd(&L.off[d], 1u);
                 if (WIDE) { L.rec[p] = (uint32_t)((uint64_t)r[j] & low_mask); L.dig[p] = (uint16_t)d; }
                 else L.rec[p] = (uint32_t)r[j];
             }
-        } else {
-#pragma unroll
-            for (int j = 0; j < PER; j++)
-                if (FULL || ((okm >> j) & 1u)) {
-                    const uint32_t d = digit_of(r[j]);
-                    const uint32_t p = atomicAdd(&L.off[d], 1u);
-                    if (WIDE) { L.rec[p] = (uint32_t)((uint64_t)r[j] & low_mask); L.dig[p] = (uint16_t)d; }
-                    else L.rec[p] = (uint32_t)r[j];
-                }
-        }
-    } else {
-        static_assert(PB == 0 || PER % (PB ? PB : 1) == 0, "parking batch");
-#pragma unroll
-        for (int j0 = 0; j0 < PER; j0 += (PB ? PB : 1)) {
-            uint32_t p[PB ? PB : 1], d[PB ? PB : 1];
-#pragma unroll
-            for (int u = 0; u < PB; u++) {
-                const int j = j0 + u;
-                const bool ok = FULL || ((okm >> j) & 1u);
-                d[u] = KEEP_DG ? dg[KEEP_DG ? j : 0] : (ok ? digit_of(r[j]) : (uint32_t)NB + lane);
-                p[u] = atomicAdd(&L.off[d[u]], ok ? 1u : 0u);         // empty slots: add zero on the lane's scratch digit, park behind the tile
-            }
-#pragma unroll
-            for (int u = 0; u < PB; u++) {
-                const int j = j0 + u;
-                if (WIDE) { L.rec[p[u]] = (uint32_t)((uint64_t)r[j] & low_mask); L.dig[p[u]] = (uint16_t)d[u]; }
-                else L.rec[p[u]] = (uint32_t)r[j];
-            }
-        }
     }
     if (claim && threadIdx.x < B) {
         if (cap_end && run_len && claimed + run_len > room_end) {            // provisioned room exhausted (rare): park the run aside
@@ -317,11 +261,7 @@ __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[
         L.gbase[threadIdx.x] = claimed - my_off;                             // sorted position p of digit d goes to p + gbase[d]
     }
     __syncthreads();
-    PK_PROF_MARK(3);
     settle();
-#ifdef PK_PHASE_PROF
-    if (prof && threadIdx.x == 0) { const unsigned long long pn = __builtin_readcyclecounter(); prof[0] += pn - pt; pt = pn; }   // (delivery of the next tile's loads: booked on phase 0)
-#endif
     // Run write-out, one record per lane and store: 64 consecutive sorted positions are 64 consecutive records of a run
     // (or of two).  32-bit records keep what they had above `low_mask` (narrow: the digit; wide: nothing) -- every
     // reader of 32-bit records masks for itself.  (Storing neighbours pairwise as 8 bytes, as round 1 did, halves the
@@ -366,9 +306,10 @@ __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[
                     const uint32_t d0 = WIDE ? ((uint32_t)L.dig[p] & (uint32_t)(NB - 1)) : __builtin_amdgcn_ubfe(r0[u], shift, dbits);
                     g0[u] = L.gbase[d0];
                 }
-                // PK_UFULL: a batch that ends inside the tile (uniform test) stores without the per-lane bounds test
-                const bool whole = PK_UFULL && !FULL && (uint32_t)(j0 + SB) * NT <= n_tile;
-                if (PK_UFULL && whole) {
+                // a batch that ends inside the tile (uniform test) stores without the per-lane bounds test (k = 15: level 1
+                // 1.314 -> 1.285 ms)
+                const bool whole = !FULL && (uint32_t)(j0 + SB) * NT <= n_tile;
+                if (whole) {
 #pragma unroll
                     for (int u = 0; u < SB; u++) {
                         const uint32_t p = threadIdx.x + (uint32_t)(j0 + u) * NT;
@@ -398,11 +339,6 @@ __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[
     // lies behind that barrier, which no wave passes before all have left this store loop.  Waves that are done start
     // assembling the next tile's k-mers while the slowest still stores: thread 0 spent 31 % of a tile waiting at the
     // first barrier for the slowest wave's assembly.
-#ifndef PK_TAIL_BARRIER
-#define PK_TAIL_BARRIER 0
-#endif
-    if (PK_TAIL_BARRIER) __syncthreads();
-    PK_PROF_MARK(4);
 }
 
 

@@ -441,17 +441,6 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         HIPCHK(hipStreamSynchronize(ix->stream));
         HIPCHK(hipGetLastError());
         time_reset(ix);
-#ifdef PK_PHASE_PROF
-        {   // experiment builds: cycles thread 0 of every level-1 workgroup spent per phase, summed over workgroups and tiles
-            unsigned long long pp[26];
-            HIPCHK(hipMemcpy(pp, flag_words + 8, sizeof pp, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[phase prof] k_walk_sort assembly %llu count %llu scan %llu park %llu store %llu (cycles, all workgroups)\n", pp[0], pp[1], pp[2], pp[3], pp[4]);
-            fprintf(stderr, "[phase prof] k_scatter2  unpack   %llu count %llu scan %llu park %llu store %llu\n", pp[5], pp[6], pp[7], pp[8], pp[9]);
-            fprintf(stderr, "[phase prof] k_squeeze   window %llu clean %llu queued %llu tally+scan+pack %llu delivery %llu store %llu\n",
-                    pp[10], pp[11], pp[12], pp[13], pp[14], pp[15]);
-            fprintf(stderr, "[phase prof]   of queued: barrier1 %llu load+begin %llu masks %llu bytes %llu flush %llu write %llu barrier2 %llu\n", pp[18], pp[19], pp[20], pp[21], pp[22], pp[23], pp[24]);
-        }
-#endif
         if (!got[0]) { ix->recounted += got[1]; break; }
         if (attempt >= 3) return fail(PK_ERR_HIP, "the feed's layout did not settle (internal error, flag %u)", got[0]);
         armed = false;
@@ -786,7 +775,7 @@ extern "C" int pk_gram_device_accumulate(const void *const *dev_tables, int N, u
 }
 
 // Several windows over the same staged slices: one pass per group of windows (k_gram_mw) where the kernel has room for
-// them, one single-window scan each otherwise.  PK_GRAM_MW=0: always one scan per window (comparison runs).
+// them, one single-window scan each otherwise.
 extern "C" int pk_gram_device_accumulate_windows(const void *const *dev_tables, int N, uint64_t n_slice, const int *min_counts,
                                                  const int *max_counts, int n_windows, void *dev_pair_accum, int device,
                                                  double *kernel_seconds_out) {
@@ -798,8 +787,7 @@ extern "C" int pk_gram_device_accumulate_windows(const void *const *dev_tables, 
     if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
     for (int i = 0; i < N; i++)
         if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
-    static const bool mw_on = !(getenv("PK_GRAM_MW") && atoi(getenv("PK_GRAM_MW")) == 0);
-    const int per_pass = mw_on ? gram_windows_per_pass(N) : 0;
+    const int per_pass = gram_windows_per_pass(N);
     HIPCHK(hipSetDevice(device));
     GramCtx *c = nullptr;
     if ((rc = gram_ctx(device, &c))) return rc;

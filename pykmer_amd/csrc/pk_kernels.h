@@ -48,8 +48,7 @@ struct PartPlan {
     uint32_t n_chunks;       // 16 KiB FASTA chunks in this feed
     uint32_t n_wg0, G;       // persistent workgroups of the squeeze kernel and chunks per workgroup
     uint32_t n_wg1, G1;      // the same for the level-1 sort (k_walk_sort)
-    uint64_t R2;             // records per level-2 workgroup
-    uint32_t n_wg2_max;      // upper bound on level-2 workgroups
+    uint64_t R2;             // records per level-2 work item
     uint32_t sample_stride;  // every how-manieth slot is tallied to size the buckets (1 = all: exact)
     uint32_t n_tally;        // what the sampling launch tallies: B1 * B2 final buckets (both levels are then laid out from
                              // the estimate), or just the B1 level-1 buckets (one level, or too many final buckets: k = 17)
@@ -60,8 +59,8 @@ struct PartPlan {
 };
 constexpr uint32_t COUNT_WGS = 256;   // workgroups (= tally rows) of the sampling launch
 struct PartWorkspace {       // byte offsets into one device allocation
-    size_t codes, restarts, n_bases, tally_rows, tally_tot, bucket_base, bucket_end, compact_base, cursor1, cap_end, wg2_start, final_start, cursor2,
-        cap2_end, out1, hist2, rowoff2, out2, side, side_n;
+    size_t codes, restarts, n_bases, tally_rows, tally_tot, bucket_base, bucket_end, cursor1, cap_end, wg2_start, final_start, cursor2, cap2_end,
+        out1, out2, side, side_n;
     uint64_t side_cap;
 };
 PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint32_t slice_index);
@@ -73,19 +72,14 @@ void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uin
                       uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags, hipStream_t s);
 void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
                       uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *compact_base, uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
-                      hipStream_t s);
+                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap, hipStream_t s);
 // `armed`: the side-list length and the flags word were already zeroed on the stream (launch_scan_l1 does it for the first
 // attempt of a feed); a repeat after an overflow zeroes them itself.
 int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint32_t stride, uint8_t *ws, const PartWorkspace &lay, uint8_t *table8,
                        hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
                        unsigned long long *hist, unsigned long long *hist_replicas, bool armed);
 constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
-#ifdef PK_PHASE_PROF
-constexpr uint32_t PART_FLAG_WORDS = 60;  // + 5 + 5 + 8 u64 phase-cycle counters (experiment builds)
-#else
 constexpr uint32_t PART_FLAG_WORDS = 6;   // side_n (u64) + flags[4], zeroed together
-#endif
 
 // gram_scan.hip
 // tables: device array of N device pointers, each n_slice bytes (16-byte aligned).  pair: device N*N u64,

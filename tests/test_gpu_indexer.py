@@ -459,7 +459,7 @@ def test_bucket_overflow_takes_the_exact_relayout(gpu, k, unit_len):
     """Bucket rooms come from a sample (one wave's stretch out of every 16 of a feed of >= 1024 chunks; k = 17: + a sample
     of the level-1 records).  A text whose sampled chunks look nothing like the rest must overflow them: the overflow flag makes every
     later kernel of the feed return untouched and the host repeats the passes with exact sizes (`relayouts`; for k = 17
-    that is the counting pass k_count2 / k_rows2_scan).  Second feed on the same indexer: the same against a table that
+    the level-1 records are then tallied in full, k_sample2 with stride 1).  Second feed on the same indexer: the same against a table that
     is no longer fresh."""
     stretch = 1024 if k == 17 else 2048
     data = inputs.skewed_fasta(20_000_040, unit_len, seed=7 + unit_len, stretch=stretch)
