@@ -154,6 +154,16 @@ int pk_gram_device_accumulate_windows(const void *const *dev_tables, int N, uint
                                       double *kernel_seconds_out);
 int pk_gram_expand(const uint64_t *pair, int N, uint64_t *matrix_out);
 
+/* Joint count spectra of N device-resident slices, ADDED to dev_spec_accum (device, zeroed by the caller):
+ * N*256 u64 value histograms, then N(N-1)/2 * 255 * 255 u64 joint bins for counts 1..255 (pairs i<j row-major).
+ * hist[i][a] = #{x : c_i(x) = a}; joint bin [p][a-1][b-1] of pair p = (i, j) = #{x : c_i(x) = a, c_j(x) = b}, a, b >= 1.
+ * Every --min-count / --max-count window of the pair tally (tools.py:473-482) is a box sum over a pair's spectrum, so one
+ * pass answers the sweeps the reference runs as one whole merge per window (README.md:57-61); the row and column of
+ * count 0 follow from the histograms.  2 <= N <= 128 (PK_ERR_ARG otherwise); beyond 16 tables the pairs are tallied in
+ * groups, each streaming its tables again.  dev_spec_accum holds (N*256 + N(N-1)/2*65025) u64. */
+int pk_spectrum_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice,
+                                  void *dev_spec_accum, int device, double *kernel_seconds_out);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

@@ -52,6 +52,8 @@ _SIGNATURES = {
     "pk_gram_device_accumulate_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pk_gram_expand": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "pk_spectrum_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_double)]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -298,6 +300,21 @@ def gram_device_accumulate_windows(dev_ptrs, n_slice: int, dev_pair_accum: int, 
     secs = ctypes.c_double(0)
     _check(load().pk_gram_device_accumulate_windows(ptrs, N, n_slice, mins, maxs, W, ctypes.c_void_p(dev_pair_accum), device,
                                                     ctypes.byref(secs)))
+    return secs.value
+
+
+def spectrum_words(N: int) -> int:
+    """u64 words of a spectrum accumulator for N tables: N x 256 histograms, then N(N-1)/2 x 255 x 255 joint bins."""
+    return N * 256 + N * (N - 1) // 2 * 255 * 255
+
+
+def spectrum_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: int = 0) -> float:
+    """pk_spectrum_device_accumulate: adds the value histograms and joint count spectra of N device-resident slices to a
+    spectrum_words(N) u64 accumulator in HBM; returns kernel seconds."""
+    N = len(dev_ptrs)
+    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    secs = ctypes.c_double(0)
+    _check(load().pk_spectrum_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
     return secs.value
 
 

@@ -717,6 +717,8 @@ struct GramCtx {
     hipStream_t stream = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     unsigned long long *d_pair = nullptr;      // scratch N x N for callers that only want the host copy
+    const uint8_t **d_gtab = nullptr;          // the tables of each pair group of a spectrum pass (spectrum_groups(128) x 16)
+    std::vector<const uint8_t *> h_gtab;
 };
 constexpr int MAX_DEVICES = 64;
 GramCtx g_gram[MAX_DEVICES];
@@ -732,6 +734,8 @@ int gram_ctx(int device, GramCtx **out) {
         HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
         HIPCHK(hipEventCreate(&c.e0));
         HIPCHK(hipEventCreate(&c.e1));
+        HIPCHK(hipMalloc(&c.d_gtab, (size_t)spectrum_groups(128) * 16 * sizeof(void *)));
+        c.h_gtab.assign((size_t)spectrum_groups(128) * 16, nullptr);
     }
     *out = &c;
     return PK_OK;
@@ -812,6 +816,29 @@ extern "C" int pk_gram_device_accumulate_windows(const void *const *dev_tables, 
         if (lrc) return fail(PK_ERR_HIP, "gram kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         at += take;
     }
+    HIPCHK(hipEventRecord(c->e1, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
+    return PK_OK;
+}
+
+// Joint count spectra (gram_spectrum.hip): one pass per pair group over the staged slices, every tally ADDED to the caller's
+// accumulator -- the slices of a rank, and the ranks by one all-reduce, sum like pk_gram_device_accumulate's.
+extern "C" int pk_spectrum_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, void *dev_spec_accum, int device,
+                                             double *kernel_seconds_out) {
+    if (N < 2 || N > 128) return fail(PK_ERR_ARG, "a spectrum pass takes 2 to 128 tables (got %d)", N);
+    if (!dev_spec_accum) return fail(PK_ERR_ARG, "null accumulator");
+    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
+    for (int i = 0; i < N; i++)
+        if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
+    HIPCHK(hipSetDevice(device));
+    GramCtx *c = nullptr;
+    int rc = gram_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    HIPCHK(hipEventRecord(c->e0, c->stream));
+    if (launch_spectrum(dev_tables, N, n_slice, (unsigned long long *)dev_spec_accum, c->h_gtab.data(), c->d_gtab, c->stream))
+        return fail(PK_ERR_HIP, "spectrum kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(hipEventRecord(c->e1, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }

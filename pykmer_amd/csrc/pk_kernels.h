@@ -94,4 +94,12 @@ int gram_windows_per_pass(int N);
 int launch_gram_windows(const uint8_t *const *dev_tables, int N, uint64_t n_slice, const int *min_counts, const int *max_counts,
                         const int *out_index, int W, unsigned long long *dev_pair, hipStream_t s);
 
+// gram_spectrum.hip -- joint count spectra: ADDS N*256 u64 value histograms, then N(N-1)/2 * 255 * 255 u64 joint bins for
+// counts 1..255 (pairs i < j row-major), to dev_accum.  2 <= N <= 128.
+// dev_tables is a HOST array of N device pointers; host_gtab / dev_gtab hold spectrum_groups(N) * 16 pointers (the tables of each
+// pair group; the host one must stay valid until the stream has copied it).
+int spectrum_groups(int N);
+int launch_spectrum(const void *const *dev_tables, int N, uint64_t n_slice, unsigned long long *dev_accum, const uint8_t **host_gtab,
+                    const uint8_t **dev_gtab, hipStream_t s);
+
 }  // namespace pk

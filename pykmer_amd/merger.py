@@ -57,6 +57,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
     parser.add_argument("--sweep", type=str, default=None,
                         help="several count windows in one run, e.g. 1-255,2-255,1-3 (tables staged once; one .kma each)")
+    parser.add_argument("--spectrum", action="store_true",
+                        help="one pass that tallies every pair's joint count spectrum: writes <P>.kms + .kms.json, from which every "
+                             "requested window's .kma is derived (and any later one, without the .kin files: python -m pykmer_amd.spectrum)")
     parser.add_argument("--gpus", type=int, default=0,
                         help="one process per GPU: the k-mer address range is split over N ranks and the N x N partials are "
                              "summed by one RCCL all-reduce (also entered under torchrun, which sets WORLD_SIZE / RANK)")
@@ -78,11 +81,13 @@ def address_slice(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, min(n, lo + per)
 
 
-def _sub_slices(lo: int, hi: int, n_tables: int, device: int):
+def _sub_slices(lo: int, hi: int, n_tables: int, device: int, reserve: int = 0):
     """[lo, hi) cut so that n_tables slices fit HBM beside each other (the reference streams pairs and takes
     any N, merger.py:139-153; here a k=17 merge of 32 tables is 512 GiB).  Partials add, so the cuts are free.
-    PK_MERGE_HBM_BUDGET (bytes) overrides the 80 % of free HBM used by default."""
+    PK_MERGE_HBM_BUDGET (bytes) overrides the 80 % of free HBM used by default; `reserve` bytes of it are kept for
+    something else (a spectrum accumulator: 41 MB at N = 13, 4.2 GB at N = 128)."""
     budget = int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or int(_lib.mem_info(device)[0] * 0.8)
+    budget -= reserve
     per_table = max(2048, (budget // max(1, n_tables) - 64) & ~2047)
     return [(a, min(hi, a + per_table)) for a in range(lo, hi, per_table)]
 
@@ -197,12 +202,127 @@ def pair_matrix(headers: List[Header], windows, threads: int = DEFAULT_THREADS, 
     return [total[w] for w in range(W)]
 
 
+def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+    """gpu_partial's staging (sub-slices that fit HBM beside the accumulator, only bytes [lo, hi) of each file read or
+    inflated, ResidentTable entries used where they lie) with one spectrum pass per staged piece
+    (pk_spectrum_device_accumulate).  The tallies are accumulated in HBM: at `acc_ptr` (spectrum_words(N) u64, zeroed by
+    the caller) or in a buffer of this call, which is then returned as one flat u64 host array: N x 256 histograms, then
+    N(N-1)/2 x 255 x 255 joint bins.  `stats["kernel_seconds"]` accumulates the passes' kernel time."""
+    N = len(headers)
+    words = _lib.spectrum_words(N)
+    resident = [hasattr(h, "device_slice") for h in headers]
+    assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one merge"
+    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, N, device, reserve=0 if acc_ptr else words * 8)
+    own = None
+    if acc_ptr is None:
+        own = _lib.DeviceBuffer(words * 8, device)
+        own.zero()
+        acc_ptr = own.ptr
+    bufs = [] if all(resident) else [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
+    from . import bgzf
+    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
+    try:
+        pool = ThreadPoolExecutor(max_workers=max(1, threads)) if bufs else None
+        try:
+            for a, b in cuts:
+                if bufs:
+                    list(pool.map(lambda i: bufs[i].upload(headers[i].read_table_slice(a, b, threads=io_threads)), range(N)))
+                    ptrs = [buf.ptr for buf in bufs]
+                else:
+                    ptrs = [h.device_slice(a, b) for h in headers]
+                secs = _lib.spectrum_device_accumulate(ptrs, b - a, acc_ptr, device=device)
+                if stats is not None:
+                    stats["kernel_seconds"] = stats.get("kernel_seconds", 0.0) + secs
+        finally:
+            if pool is not None:
+                pool.shutdown()
+        if own is None:
+            return None
+        return own.download().view(np.uint64).copy()
+    finally:
+        for buf in bufs:
+            buf.free()
+        if own is not None:
+            own.free()
+
+
+def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
+                  stats: dict = None) -> np.ndarray:
+    """The spectrum accumulator of all tables over the whole address range (flat u64, spectrum_partial's layout), split
+    like pair_matrix: over `devices` in one process (partials summed on the host), or with `group` one slice per rank and
+    ONE all-reduce of the accumulator -- on the device over RCCL, through the host over gloo.  `partial_fn(headers, lo, hi,
+    device, threads)` returns one slice's flat accumulator (default: spectrum_partial; the CPU-only tests substitute numpy)."""
+    partial_fn = partial_fn or spectrum_partial
+    n, N = headers[0].data_size, len(headers)
+    assert N >= 2, "a spectrum needs at least two tables"
+    words = _lib.spectrum_words(N)
+    kw = {"stats": stats} if (stats is not None and partial_fn is spectrum_partial) else {}
+    if group is None:
+        plan = [(d,) + address_slice(n, i, len(devices)) for i, d in enumerate(devices)]
+        plan = [p for p in plan if p[2] > p[1]]
+        with ThreadPoolExecutor(max_workers=max(1, len(plan))) as pool:
+            parts = list(pool.map(lambda p: partial_fn(headers, p[1], p[2], p[0], max(1, threads // len(plan)), **kw), plan))
+        total = np.zeros(words, dtype=np.uint64)
+        for part in parts:
+            total += part
+        return total
+
+    import torch
+    import torch.distributed as dist
+    pg = None if group is True else group
+    dev = devices[0]
+    lo, hi = address_slice(n, dist.get_rank(pg), dist.get_world_size(pg))
+    on_gpu = dist.get_backend(pg) == "nccl"
+    if partial_fn is spectrum_partial and on_gpu:
+        acc = torch.zeros(words, dtype=torch.int64, device=torch.device("cuda", dev))
+        torch.cuda.synchronize(dev)                             # zeroed before the passes (their own stream) add to it
+        if hi > lo:
+            spectrum_partial(headers, lo, hi, dev, threads, acc_ptr=acc.data_ptr(), stats=stats)
+        dist.all_reduce(acc, group=pg)                         # RCCL: the accumulator never leaves the device before the sum
+        return acc.cpu().numpy().view(np.uint64)
+    total = np.zeros(words, dtype=np.uint64)
+    if hi > lo:
+        total += partial_fn(headers, lo, hi, dev, threads, **kw)
+    t = torch.from_numpy(total.view(np.int64).copy())
+    if on_gpu:
+        t = t.to(torch.device("cuda", dev))
+    dist.all_reduce(t, group=pg)
+    return t.cpu().numpy().view(np.uint64)
+
+
+def write_kma(project_name: str, mn: int, mx: int, data, matrix: np.ndarray) -> None:
+    """`<project>.<min>-<max>.kma` (key `matrix`, merger.py:207) and its `.kma.json` (merger.py:189-201), each through
+    `.tmp` + rename."""
+    outfile = Path(f"{project_name}.{mn:03d}-{mx:03d}.kma")
+    output = {"project_name": project_name, "min_count": mn, "max_count": mx, "data": data}
+    outfile_json = Path(f"{outfile}.json")
+    outfile_json_tmp = Path(f"{outfile_json}.tmp")
+    print(f"saving {outfile_json}")
+    with outfile_json_tmp.open(mode="wt") as fhd:
+        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
+    outfile_json_tmp.rename(outfile_json)
+    print(f"saving {outfile}")
+    outfile_tmp = Path(f"{outfile}.tmp")
+    with outfile_tmp.open(mode="wb") as fhd:
+        np.savez_compressed(fhd, matrix=matrix)            # merger.py:207: key `matrix`
+    outfile_tmp.rename(outfile)
+
+
+def print_matrix(matrix: np.ndarray) -> None:
+    for k in range(matrix.shape[0] - 1):
+        for l in range(k + 1, matrix.shape[0]):
+            print(f"   matrix Total #{k:3d} {int(matrix[k, l, 0]):15,d} Total #{l:3d} {int(matrix[k, l, 1]):15,d} Shared {int(matrix[k, l, 2]):15,d}")
+
+
 def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_COUNT, max_count: int = DEFAULT_MAX_COUNT,
           buffer_size: int = DEFAULT_BUFFER_SIZE, block_size: int = DEFAULT_BLOCK_SIZE, threads: int = DEFAULT_THREADS,
-          devices=(0,), group=None, partial_fn=None, windows=None):
+          devices=(0,), group=None, partial_fn=None, windows=None, spectrum: bool = False):
     """merger.py:80-210.  `windows` (a list of (min_count, max_count)) turns the call into a sweep: the
     tables are staged once and one `.kma` + `.kma.json` is written per window (the reference re-runs
-    the whole merge per threshold, README.md:57-61); the first window's matrix is returned."""
+    the whole merge per threshold, README.md:57-61); the first window's matrix is returned.
+    `spectrum` makes the one pass tally every pair's joint count spectrum instead (pair_spectrum; `partial_fn` then
+    computes a slice's spectrum): `<project>.kms` + `.kms.json` are written, and every window's `.kma` is derived from
+    the spectrum (pykmer_amd.spectrum), as any later window can be without the tables."""
     windows = [(min_count, max_count)] if not windows else [tuple(w) for w in windows]
     for mn, mx in windows:
         assert mn >= 1
@@ -215,6 +335,10 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
     assert not Path(project_name).exists(), f"project name ({project_name}) is a file. maybe forgot to pass project name as first argument?"
     for outfile in outfiles:
         assert not outfile.exists(), f"project output file ({outfile}) already exists. not overwriting."
+    if spectrum:
+        from . import spectrum as spec
+        for f in spec.spectrum_paths(project_name):
+            assert not f.exists(), f"spectrum output file ({f}) already exists. not overwriting."
 
     indexes = [Path(p) for p in indexes]
     assert all(i.exists() for i in indexes)
@@ -235,13 +359,20 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         data.append({"pos": pos, "index_file": kin, "description_file": desc, "header": header})
     print()
 
-    pairs = pair_matrix(headers, windows, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
+    if spectrum:
+        total = pair_spectrum(headers, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
+        hist, joint = spec.expand_accumulator(total, len(headers), headers[0].data_size)
+        pairs = spec.window_pairs(hist, joint, windows)
+    else:
+        pairs = pair_matrix(headers, windows, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
     for v in data:
         v["header"] = v["header"].to_dict(lean=True)          # merger.py:187-188
     is_writer = True
     if group is not None:
         import torch.distributed as dist
         is_writer = dist.get_rank(None if group is True else group) == 0
+    if spectrum and is_writer:
+        spec.save(project_name, hist, joint, kmer_len, headers[0].data_size, data)
 
     matrices = []
     for (mn, mx), outfile, pair in zip(windows, outfiles, pairs):
@@ -249,23 +380,10 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         # never assigns in its uninitialised array (merger.py:136), is zero here
         matrix = _lib.gram_expand(pair)
         matrices.append(matrix)
-        for k in range(len(data) - 1):
-            for l in range(k + 1, len(data)):
-                print(f"   matrix Total #{k:3d} {int(matrix[k, l, 0]):15,d} Total #{l:3d} {int(matrix[k, l, 1]):15,d} Shared {int(matrix[k, l, 2]):15,d}")
+        print_matrix(matrix)
         if not is_writer:
             continue
-        output = {"project_name": project_name, "min_count": mn, "max_count": mx, "data": data}
-        outfile_json = Path(f"{outfile}.json")
-        outfile_json_tmp = Path(f"{outfile_json}.tmp")
-        print(f"saving {outfile_json}")
-        with outfile_json_tmp.open(mode="wt") as fhd:
-            json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
-        outfile_json_tmp.rename(outfile_json)
-        print(f"saving {outfile}")
-        outfile_tmp = Path(f"{outfile}.tmp")
-        with outfile_tmp.open(mode="wb") as fhd:
-            np.savez_compressed(fhd, matrix=matrix)            # merger.py:207: key `matrix`
-        outfile_tmp.rename(outfile)
+        write_kma(project_name, mn, mx, data, matrix)
     return data, matrices[0]
 
 
@@ -344,7 +462,7 @@ def main(argv: List[str] = None) -> None:
             sys.exit(spawn_ranks(args.gpus, argv))
         devices = tuple(int(d) for d in os.environ.get("PK_DEVICES", "0").split(",") if d != "")
         merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
-              block_size=args.block_size, threads=args.threads, devices=devices or (0,), windows=windows)
+              block_size=args.block_size, threads=args.threads, devices=devices or (0,), windows=windows, spectrum=args.spectrum)
         return
     # one rank of a multi-process merge: every rank validates and scans its address slice, rank 0 prints and writes
     import contextlib
@@ -353,7 +471,8 @@ def main(argv: List[str] = None) -> None:
     try:
         with contextlib.redirect_stdout(None) if rank else contextlib.nullcontext():
             merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
-                  block_size=args.block_size, threads=args.threads, devices=(device,), group=True, windows=windows)
+                  block_size=args.block_size, threads=args.threads, devices=(device,), group=True, windows=windows,
+                  spectrum=args.spectrum)
         dist.barrier()                                         # nobody leaves before rank 0 has renamed the outputs
     finally:
         dist.destroy_process_group()
