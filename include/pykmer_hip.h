@@ -164,6 +164,16 @@ int pk_gram_expand(const uint64_t *pair, int N, uint64_t *matrix_out);
 int pk_spectrum_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice,
                                   void *dev_spec_accum, int device, double *kernel_seconds_out);
 
+/* Occupancy-stratified Gram products of N device-resident slices (kWIP, Murray et al. 2017: the entropy weight of a k-mer
+ * depends only on how many samples hold it), ADDED to dev_accum (device, zeroed by the caller).  With o(x) = #{i : c_i(x) >= 1}:
+ *   occ_hist[N+1]        occ_hist[o] = #{x : o(x) = o}, o = 0..N
+ *   lin[N][N]            lin[o-1][i] = sum_{x : o(x) = o} c_i(x)
+ *   gram[N][N(N+1)/2]    gram[o-1][p] = sum_{x : o(x) = o} c_i(x) c_j(x), p = (i, j), i <= j, row-major upper triangle with the diagonal
+ * all u64, in that order: (N + 1) + N*N + N*N(N+1)/2 words.  Any weighting over occupancy classes, and kWIP's kernel and
+ * distance, follow on the host.  2 <= N <= 128 (PK_ERR_ARG otherwise); table pointers 16-byte aligned. */
+int pk_occgram_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, void *dev_accum, int device,
+                                 double *kernel_seconds_out);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

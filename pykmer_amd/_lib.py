@@ -54,6 +54,8 @@ _SIGNATURES = {
     "pk_gram_expand": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "pk_spectrum_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
                                                       ctypes.POINTER(ctypes.c_double)]),
+    "pk_occgram_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_double)]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -315,6 +317,21 @@ def spectrum_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: i
     ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
     secs = ctypes.c_double(0)
     _check(load().pk_spectrum_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
+    return secs.value
+
+
+def occgram_words(N: int) -> int:
+    """u64 words of an occgram accumulator for N tables: occ_hist (N+1), lin (N x N), gram (N x N(N+1)/2)."""
+    return (N + 1) + N * N + N * (N * (N + 1) // 2)
+
+
+def occgram_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: int = 0) -> float:
+    """pk_occgram_device_accumulate: adds the occupancy-stratified Gram products of N device-resident slices to an
+    occgram_words(N) u64 accumulator in HBM; returns kernel seconds."""
+    N = len(dev_ptrs)
+    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    secs = ctypes.c_double(0)
+    _check(load().pk_occgram_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
     return secs.value
 
 

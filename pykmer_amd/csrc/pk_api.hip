@@ -719,6 +719,8 @@ struct GramCtx {
     unsigned long long *d_pair = nullptr;      // scratch N x N for callers that only want the host copy
     const uint8_t **d_gtab = nullptr;          // the tables of each pair group of a spectrum pass (spectrum_groups(128) x 16)
     std::vector<const uint8_t *> h_gtab;
+    uint8_t *d_occ = nullptr;                  // occupancy bytes of an occgram pass over more than 16 tables (grown on demand)
+    uint64_t occ_cap = 0;
 };
 constexpr int MAX_DEVICES = 64;
 GramCtx g_gram[MAX_DEVICES];
@@ -839,6 +841,38 @@ extern "C" int pk_spectrum_device_accumulate(const void *const *dev_tables, int 
     HIPCHK(hipEventRecord(c->e0, c->stream));
     if (launch_spectrum(dev_tables, N, n_slice, (unsigned long long *)dev_spec_accum, c->h_gtab.data(), c->d_gtab, c->stream))
         return fail(PK_ERR_HIP, "spectrum kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(hipEventRecord(c->e1, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
+    return PK_OK;
+}
+
+// Occupancy-stratified Gram products (gram_occ.hip): every tally ADDED to the caller's accumulator, so slices and ranks sum
+// like pk_spectrum_device_accumulate's.
+extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, void *dev_accum, int device,
+                                            double *kernel_seconds_out) {
+    if (N < 2 || N > 128) return fail(PK_ERR_ARG, "an occgram pass takes 2 to 128 tables (got %d)", N);
+    if (!dev_accum) return fail(PK_ERR_ARG, "null accumulator");
+    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
+    for (int i = 0; i < N; i++)
+        if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
+    HIPCHK(hipSetDevice(device));
+    GramCtx *c = nullptr;
+    int rc = gram_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    const uint64_t need = occgram_scratch_bytes(N, n_slice);
+    if (need > c->occ_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->d_occ) HIPCHK(hipFree(c->d_occ));
+        c->d_occ = nullptr;
+        c->occ_cap = 0;
+        HIPCHK(hipMalloc(&c->d_occ, need));
+        c->occ_cap = need;
+    }
+    HIPCHK(hipEventRecord(c->e0, c->stream));
+    if (launch_occgram(dev_tables, N, n_slice, (unsigned long long *)dev_accum, c->d_ptrs, c->d_occ, c->stream))
+        return fail(PK_ERR_HIP, "occgram kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(hipEventRecord(c->e1, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }

@@ -102,4 +102,11 @@ int spectrum_groups(int N);
 int launch_spectrum(const void *const *dev_tables, int N, uint64_t n_slice, unsigned long long *dev_accum, const uint8_t **host_gtab,
                     const uint8_t **dev_gtab, hipStream_t s);
 
+// gram_occ.hip -- occupancy-stratified Gram products (kWIP): ADDS occ_hist[N+1], lin[N][N] ([o-1][i]) and gram[N][N(N+1)/2]
+// ([o-1][pair i <= j, row-major]) u64 to dev_accum.  2 <= N <= 128.  dev_tables is a HOST array of N device pointers;
+// dev_ptrs holds N device pointers (the occupancy pre-pass's list) and occ_scratch occgram_scratch_bytes(N, n_slice) bytes.
+uint64_t occgram_scratch_bytes(int N, uint64_t n_slice);
+int launch_occgram(const void *const *dev_tables, int N, uint64_t n_slice, unsigned long long *dev_accum, const uint8_t **dev_ptrs,
+                   uint8_t *occ_scratch, hipStream_t s);
+
 }  // namespace pk

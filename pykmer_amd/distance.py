@@ -167,9 +167,25 @@ def load(matrix_file: Path, names_file: Path = None) -> np.ndarray:
     return cluster_distance(matrix_file, basefile, distance, names_file=names_file)
 
 
+def load_kwip(kmo_file: Path, names_file: Path = None) -> np.ndarray:
+    """The same outputs from kWIP's entropy-weighted distance over a `.kmo` (merger.py --kwip), basefile `<P>.kmo.dist.kwip`."""
+    from . import kwip
+    kmo_file = Path(kmo_file)
+    if names_file is None and Path(f"{kmo_file}.names.tsv").exists():
+        names_file = Path(f"{kmo_file}.names.tsv")
+    _, distance = kwip.matrices(kwip.load(kmo_file))
+    basefile = Path(f"{kmo_file}.dist.kwip")
+    with Path(f"{basefile}.npz").open("wb") as fh:
+        np.savez(fh, distance=distance)
+    return cluster_distance(kmo_file, basefile, distance, names_file=names_file)
+
+
 def main(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 1:
-        print("usage: calculate_distance.py <project.MIN-MAX.kma>")
+        print("usage: calculate_distance.py <project.MIN-MAX.kma | project.kmo>")
         sys.exit(1)
-    load(Path(argv[0]))
+    if argv[0].endswith(".kmo"):
+        load_kwip(Path(argv[0]))
+    else:
+        load(Path(argv[0]))

@@ -60,6 +60,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--spectrum", action="store_true",
                         help="one pass that tallies every pair's joint count spectrum: writes <P>.kms + .kms.json, from which every "
                              "requested window's .kma is derived (and any later one, without the .kin files: python -m pykmer_amd.spectrum)")
+    parser.add_argument("--kwip", action="store_true",
+                        help="kWIP's entropy-weighted kernel and distance instead of the pair tally: one pass writes <P>.kmo + "
+                             ".kmo.json (the exact per-occupancy tallies), <P>.kern and <P>.dist, and no .kma (any weighting "
+                             "again, without the .kin files: python -m pykmer_amd.kwip)")
     parser.add_argument("--gpus", type=int, default=0,
                         help="one process per GPU: the k-mer address range is split over N ranks and the N x N partials are "
                              "summed by one RCCL all-reduce (also entered under torchrun, which sets WORLD_SIZE / RANK)")
@@ -202,17 +206,17 @@ def pair_matrix(headers: List[Header], windows, threads: int = DEFAULT_THREADS, 
     return [total[w] for w in range(W)]
 
 
-def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, words: int, accumulate, staged_tables: int,
+                  acc_ptr: int = None, stats: dict = None):
     """gpu_partial's staging (sub-slices that fit HBM beside the accumulator, only bytes [lo, hi) of each file read or
-    inflated, ResidentTable entries used where they lie) with one spectrum pass per staged piece
-    (pk_spectrum_device_accumulate).  The tallies are accumulated in HBM: at `acc_ptr` (spectrum_words(N) u64, zeroed by
-    the caller) or in a buffer of this call, which is then returned as one flat u64 host array: N x 256 histograms, then
-    N(N-1)/2 x 255 x 255 joint bins.  `stats["kernel_seconds"]` accumulates the passes' kernel time."""
+    inflated, ResidentTable entries used where they lie) with one `accumulate(ptrs, n, acc_ptr, device=)` pass per staged
+    piece, adding to a flat u64 accumulator of `words` words: at `acc_ptr` (zeroed by the caller) or in a buffer of this
+    call, which is then returned as one flat u64 host array.  `staged_tables` is what _sub_slices budgets per table byte
+    (more than N when the pass keeps scratch of its own).  `stats["kernel_seconds"]` accumulates the kernel time."""
     N = len(headers)
-    words = _lib.spectrum_words(N)
     resident = [hasattr(h, "device_slice") for h in headers]
     assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one merge"
-    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, N, device, reserve=0 if acc_ptr else words * 8)
+    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, staged_tables, device, reserve=0 if acc_ptr else words * 8)
     own = None
     if acc_ptr is None:
         own = _lib.DeviceBuffer(words * 8, device)
@@ -230,7 +234,7 @@ def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threa
                     ptrs = [buf.ptr for buf in bufs]
                 else:
                     ptrs = [h.device_slice(a, b) for h in headers]
-                secs = _lib.spectrum_device_accumulate(ptrs, b - a, acc_ptr, device=device)
+                secs = accumulate(ptrs, b - a, acc_ptr, device=device)
                 if stats is not None:
                     stats["kernel_seconds"] = stats.get("kernel_seconds", 0.0) + secs
         finally:
@@ -246,17 +250,32 @@ def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threa
             own.free()
 
 
-def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
-                  stats: dict = None) -> np.ndarray:
-    """The spectrum accumulator of all tables over the whole address range (flat u64, spectrum_partial's layout), split
-    like pair_matrix: over `devices` in one process (partials summed on the host), or with `group` one slice per rank and
-    ONE all-reduce of the accumulator -- on the device over RCCL, through the host over gloo.  `partial_fn(headers, lo, hi,
-    device, threads)` returns one slice's flat accumulator (default: spectrum_partial; the CPU-only tests substitute numpy)."""
-    partial_fn = partial_fn or spectrum_partial
-    n, N = headers[0].data_size, len(headers)
-    assert N >= 2, "a spectrum needs at least two tables"
-    words = _lib.spectrum_words(N)
-    kw = {"stats": stats} if (stats is not None and partial_fn is spectrum_partial) else {}
+def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+    """One spectrum pass per staged piece of addresses [lo, hi) (pk_spectrum_device_accumulate; staging as _flat_partial).
+    The tallies are accumulated in HBM: at `acc_ptr` (spectrum_words(N) u64, zeroed by the caller) or in a buffer of this
+    call, which is then returned as one flat u64 host array: N x 256 histograms, then N(N-1)/2 x 255 x 255 joint bins."""
+    return _flat_partial(headers, lo, hi, device, threads, _lib.spectrum_words(len(headers)), _lib.spectrum_device_accumulate,
+                         len(headers), acc_ptr=acc_ptr, stats=stats)
+
+
+def occgram_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+    """One occgram pass per staged piece of addresses [lo, hi) (pk_occgram_device_accumulate; staging as _flat_partial).
+    The tallies are accumulated in HBM: at `acc_ptr` (occgram_words(N) u64, zeroed by the caller) or in a buffer of this
+    call, which is then returned as one flat u64 host array: occ_hist (N+1), lin (N x N), gram (N x N(N+1)/2).  Beyond 16
+    tables the pass keeps one occupancy byte per address in HBM: the sub-slices budget N + 1 tables."""
+    N = len(headers)
+    return _flat_partial(headers, lo, hi, device, threads, _lib.occgram_words(N), _lib.occgram_device_accumulate,
+                         N + 1 if N > 16 else N, acc_ptr=acc_ptr, stats=stats)
+
+
+def _pair_flat(headers: List[Header], words: int, own_partial, threads: int, devices, group, partial_fn, stats) -> np.ndarray:
+    """A flat accumulator of all tables over the whole address range, split like pair_matrix: over `devices` in one process
+    (partials summed on the host), or with `group` one slice per rank and ONE all-reduce of the accumulator -- on the device
+    over RCCL, through the host over gloo.  `partial_fn(headers, lo, hi, device, threads)` returns one slice's flat
+    accumulator (default: `own_partial`; the CPU-only tests substitute numpy)."""
+    partial_fn = partial_fn or own_partial
+    n = headers[0].data_size
+    kw = {"stats": stats} if (stats is not None and partial_fn is own_partial) else {}
     if group is None:
         plan = [(d,) + address_slice(n, i, len(devices)) for i, d in enumerate(devices)]
         plan = [p for p in plan if p[2] > p[1]]
@@ -273,11 +292,11 @@ def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices
     dev = devices[0]
     lo, hi = address_slice(n, dist.get_rank(pg), dist.get_world_size(pg))
     on_gpu = dist.get_backend(pg) == "nccl"
-    if partial_fn is spectrum_partial and on_gpu:
+    if partial_fn is own_partial and on_gpu:
         acc = torch.zeros(words, dtype=torch.int64, device=torch.device("cuda", dev))
         torch.cuda.synchronize(dev)                             # zeroed before the passes (their own stream) add to it
         if hi > lo:
-            spectrum_partial(headers, lo, hi, dev, threads, acc_ptr=acc.data_ptr(), stats=stats)
+            own_partial(headers, lo, hi, dev, threads, acc_ptr=acc.data_ptr(), stats=stats)
         dist.all_reduce(acc, group=pg)                         # RCCL: the accumulator never leaves the device before the sum
         return acc.cpu().numpy().view(np.uint64)
     total = np.zeros(words, dtype=np.uint64)
@@ -288,6 +307,22 @@ def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices
         t = t.to(torch.device("cuda", dev))
     dist.all_reduce(t, group=pg)
     return t.cpu().numpy().view(np.uint64)
+
+
+def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
+                  stats: dict = None) -> np.ndarray:
+    """The spectrum accumulator of all tables over the whole address range (flat u64, spectrum_partial's layout), split
+    as _pair_flat does; `partial_fn` defaults to spectrum_partial."""
+    assert len(headers) >= 2, "a spectrum needs at least two tables"
+    return _pair_flat(headers, _lib.spectrum_words(len(headers)), spectrum_partial, threads, devices, group, partial_fn, stats)
+
+
+def pair_occgram(headers: List[Header], threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
+                 stats: dict = None) -> np.ndarray:
+    """The occgram accumulator of all tables over the whole address range (flat u64, occgram_partial's layout), split
+    as _pair_flat does; `partial_fn` defaults to occgram_partial."""
+    assert 2 <= len(headers) <= 128, "kWIP takes 2 to 128 tables"
+    return _pair_flat(headers, _lib.occgram_words(len(headers)), occgram_partial, threads, devices, group, partial_fn, stats)
 
 
 def write_kma(project_name: str, mn: int, mx: int, data, matrix: np.ndarray) -> None:
@@ -316,13 +351,19 @@ def print_matrix(matrix: np.ndarray) -> None:
 
 def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_COUNT, max_count: int = DEFAULT_MAX_COUNT,
           buffer_size: int = DEFAULT_BUFFER_SIZE, block_size: int = DEFAULT_BLOCK_SIZE, threads: int = DEFAULT_THREADS,
-          devices=(0,), group=None, partial_fn=None, windows=None, spectrum: bool = False):
+          devices=(0,), group=None, partial_fn=None, windows=None, spectrum: bool = False, kwip: bool = False):
     """merger.py:80-210.  `windows` (a list of (min_count, max_count)) turns the call into a sweep: the
     tables are staged once and one `.kma` + `.kma.json` is written per window (the reference re-runs
     the whole merge per threshold, README.md:57-61); the first window's matrix is returned.
     `spectrum` makes the one pass tally every pair's joint count spectrum instead (pair_spectrum; `partial_fn` then
     computes a slice's spectrum): `<project>.kms` + `.kms.json` are written, and every window's `.kma` is derived from
-    the spectrum (pykmer_amd.spectrum), as any later window can be without the tables."""
+    the spectrum (pykmer_amd.spectrum), as any later window can be without the tables.
+    `kwip` makes the one pass tally the occupancy-stratified Gram products instead (pair_occgram; `partial_fn` then computes
+    a slice's accumulator): `<project>.kmo` + `.kmo.json`, `.kern` and `.dist` are written and no `.kma`; the call returns
+    (data, kernel matrix)."""
+    if kwip:
+        assert not spectrum and not windows and (min_count, max_count) == (DEFAULT_MIN_COUNT, DEFAULT_MAX_COUNT), \
+            "kwip takes no count window, sweep or spectrum"
     windows = [(min_count, max_count)] if not windows else [tuple(w) for w in windows]
     for mn, mx in windows:
         assert mn >= 1
@@ -331,7 +372,7 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
     assert block_size > 0
     assert len(indexes) > 0
 
-    outfiles = [Path(f"{project_name}.{mn:03d}-{mx:03d}.kma") for mn, mx in windows]
+    outfiles = [] if kwip else [Path(f"{project_name}.{mn:03d}-{mx:03d}.kma") for mn, mx in windows]
     assert not Path(project_name).exists(), f"project name ({project_name}) is a file. maybe forgot to pass project name as first argument?"
     for outfile in outfiles:
         assert not outfile.exists(), f"project output file ({outfile}) already exists. not overwriting."
@@ -339,6 +380,10 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         from . import spectrum as spec
         for f in spec.spectrum_paths(project_name):
             assert not f.exists(), f"spectrum output file ({f}) already exists. not overwriting."
+    if kwip:
+        from . import kwip as kw
+        for f in kw.kmo_paths(project_name):
+            assert not f.exists(), f"kwip output file ({f}) already exists. not overwriting."
 
     indexes = [Path(p) for p in indexes]
     assert all(i.exists() for i in indexes)
@@ -359,7 +404,11 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         data.append({"pos": pos, "index_file": kin, "description_file": desc, "header": header})
     print()
 
-    if spectrum:
+    if kwip:
+        total = pair_occgram(headers, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
+        occ_hist, lin, gram = kw.split_accumulator(total, len(headers))
+        pairs = []
+    elif spectrum:
         total = pair_spectrum(headers, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
         hist, joint = spec.expand_accumulator(total, len(headers), headers[0].data_size)
         pairs = spec.window_pairs(hist, joint, windows)
@@ -373,6 +422,16 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         is_writer = dist.get_rank(None if group is True else group) == 0
     if spectrum and is_writer:
         spec.save(project_name, hist, joint, kmer_len, headers[0].data_size, data)
+    if kwip:
+        ids = [v["header"]["input_file_name"] for v in data]
+        kern = kw.kernel(lin, gram, kw.weights(len(headers)))
+        dist = kw.distance(kern, ids)
+        if is_writer:
+            kw.save(project_name, occ_hist, lin, gram, kmer_len, headers[0].data_size, data)
+            _, _, kern_path, dist_path = kw.kmo_paths(project_name)
+            kw.write_matrix(kern_path, kern, ids)
+            kw.write_matrix(dist_path, dist, ids)
+        return data, kern
 
     matrices = []
     for (mn, mx), outfile, pair in zip(windows, outfiles, pairs):
@@ -457,12 +516,15 @@ def main(argv: List[str] = None) -> None:
         sys.exit(1)
     indexes.sort()                                             # matrix order = sorted path order (merger.py:228)
     windows = parse_sweep(args.sweep) if args.sweep else None
+    if args.kwip and (args.spectrum or args.sweep or args.min_count != DEFAULT_MIN_COUNT or args.max_count != DEFAULT_MAX_COUNT):
+        build_parser().error("--kwip takes no --spectrum, --sweep, --min-count or --max-count")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(spawn_ranks(args.gpus, argv))
         devices = tuple(int(d) for d in os.environ.get("PK_DEVICES", "0").split(",") if d != "")
         merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
-              block_size=args.block_size, threads=args.threads, devices=devices or (0,), windows=windows, spectrum=args.spectrum)
+              block_size=args.block_size, threads=args.threads, devices=devices or (0,), windows=windows, spectrum=args.spectrum,
+              kwip=args.kwip)
         return
     # one rank of a multi-process merge: every rank validates and scans its address slice, rank 0 prints and writes
     import contextlib
@@ -472,7 +534,7 @@ def main(argv: List[str] = None) -> None:
         with contextlib.redirect_stdout(None) if rank else contextlib.nullcontext():
             merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
                   block_size=args.block_size, threads=args.threads, devices=(device,), group=True, windows=windows,
-                  spectrum=args.spectrum)
+                  spectrum=args.spectrum, kwip=args.kwip)
         dist.barrier()                                         # nobody leaves before rank 0 has renamed the outputs
     finally:
         dist.destroy_process_group()
