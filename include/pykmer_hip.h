@@ -25,8 +25,12 @@ enum {
     PK_ERR_ARG = -1,      /* even / non-positive / unsupported k, bad min/max count, null pointer */
     PK_ERR_HIP = -2,      /* HIP runtime failure (no device, out of memory, launch error)        */
     PK_ERR_RECS_CAP = -3, /* more records than recs_cap; *n_recs_out holds the number needed      */
-    PK_ERR_STATE = -4     /* handle used out of order                                            */
+    PK_ERR_STATE = -4,    /* handle used out of order                                            */
+    PK_ERR_FORMAT = -5    /* malformed input (FASTQ); pk_last_error names the record and the rule  */
 };
+
+#define PK_FORMAT_FASTA 0
+#define PK_FORMAT_FASTQ 1
 
 /* One FASTA record as the reference's parse_fasta yields it (indexer.py:45-99). The caller slices the
  * header text out of its own buffer and drops records with n_valid_kmers == 0 to reproduce the
@@ -85,6 +89,14 @@ int pk_indexer_create(pk_indexer **out, int k, int device);
  * slice; hist256 describes the slice. */
 int pk_indexer_create_slice(pk_indexer **out, int k, int device, int slice_index, int n_slices);
 int pk_indexer_reset(pk_indexer *ix);                       /* zero the table, forget parser state  */
+/* What the feeds hold: PK_FORMAT_FASTA (the default) or PK_FORMAT_FASTQ.  Set after create or reset, before the first
+ * feed (PK_ERR_STATE otherwise); it persists across resets.  A FASTQ stream is counted exactly like the FASTA text it
+ * stands for (README "FASTQ input": 4-line records, line 1 '@' -> '>', lines 3 and 4 dropped), converted on the device.
+ * pk_record.name_off then points into the FASTQ bytes.  A malformed record fails the feed that completes it, or
+ * pk_indexer_finish if the stream stops inside a record, with PK_ERR_FORMAT; pk_indexer_reset clears the error. */
+int pk_indexer_set_format(pk_indexer *ix, int format);
+/* FASTQ indexers: out = { records, lines, FASTQ bytes fed, FASTA bytes emitted to the counting pipeline }. */
+int pk_indexer_fastq_stats(pk_indexer *ix, uint64_t out[4]);
 /* Feed the next n_bytes of the FASTA text.  Chunks may split lines, records and k-mers anywhere.   */
 int pk_indexer_feed(pk_indexer *ix, const uint8_t *host_fasta, uint64_t n_bytes);
 /* Same, but the bytes already sit in device memory on the indexer's device (16-byte aligned).  Work runs on

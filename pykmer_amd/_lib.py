@@ -10,7 +10,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 from ._rt import LIB_PATH, open_library
 
-PK_OK, PK_ERR_ARG, PK_ERR_HIP, PK_ERR_RECS_CAP, PK_ERR_STATE = 0, -1, -2, -3, -4
+PK_OK, PK_ERR_ARG, PK_ERR_HIP, PK_ERR_RECS_CAP, PK_ERR_STATE, PK_ERR_FORMAT = 0, -1, -2, -3, -4, -5
+PK_FORMAT_FASTA, PK_FORMAT_FASTQ = 0, 1
+FORMATS = {"fasta": PK_FORMAT_FASTA, "fastq": PK_FORMAT_FASTQ}
 
 RECORD_DTYPE = np.dtype([("name_off", "<u8"), ("name_len", "<u8"), ("seq_len", "<u8"), ("n_valid_kmers", "<u8")])
 
@@ -31,6 +33,8 @@ _SIGNATURES = {
     "pk_indexer_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     "pk_indexer_create_slice": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "pk_indexer_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "pk_indexer_set_format": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_indexer_fastq_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_indexer_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_indexer_feed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_indexer_finish": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, ctypes.c_void_p, _u64p]),
@@ -155,13 +159,18 @@ class DeviceBuffer:
 
 
 class Indexer:
-    """One 4^k count table resident in HBM on one device (pk_indexer_*)."""
+    """One 4^k count table resident in HBM on one device (pk_indexer_*).  fmt: what the feeds hold, "fasta" or "fastq"
+    (pk_indexer_set_format; it stays across resets)."""
 
-    def __init__(self, k: int, device: int = 0, slice_index: int = 0, n_slices: int = 1):
+    def __init__(self, k: int, device: int = 0, slice_index: int = 0, n_slices: int = 1, fmt: str = "fasta"):
+        if fmt not in FORMATS:
+            raise ValueError(f"unknown input format {fmt!r}: expected one of {sorted(FORMATS)}")
         self._h = ctypes.c_void_p()
-        self.k, self.device, self.slice_index, self.n_slices = k, device, slice_index, n_slices
+        self.k, self.device, self.slice_index, self.n_slices, self.fmt = k, device, slice_index, n_slices, fmt
         self.table_bytes = 4 ** k // n_slices
         _check(load().pk_indexer_create_slice(ctypes.byref(self._h), k, device, slice_index, n_slices))
+        if fmt != "fasta":
+            _check(load().pk_indexer_set_format(self._h, FORMATS[fmt]))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -216,6 +225,12 @@ class Indexer:
 
     def table_slice_to_device(self, dev_dst: int, offset: int, n_bytes: int):
         _check(load().pk_indexer_table_slice_to_device(self._h, ctypes.c_void_p(dev_dst), offset, n_bytes))
+
+    def fastq_stats(self) -> dict:
+        """pk_indexer_fastq_stats of a FASTQ indexer: records, lines, FASTQ bytes fed, FASTA bytes emitted."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(load().pk_indexer_fastq_stats(self._h, out.ctypes.data))
+        return {"records": int(out[0]), "lines": int(out[1]), "bytes_fed": int(out[2]), "bytes_emitted": int(out[3])}
 
     def timings(self) -> dict:
         t = np.zeros(10, dtype=np.float64)

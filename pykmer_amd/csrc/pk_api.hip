@@ -203,7 +203,7 @@ struct pk_indexer {
     hipStream_t stream = nullptr;
     uint8_t *table8 = nullptr;       // the .kin image
     // parser state + running totals, and the value histogram, side by side: one copy brings both to the host, one copy resets both
-    struct Tail { Carry carry; unsigned long long hist[256]; };
+    struct Tail { Carry carry; unsigned long long hist[256]; FqCarry fq; };
     Tail *tail = nullptr, *tail0 = nullptr;   // tail0: the state of an empty stream (a reset is a device-to-device copy, no host wait)
     Carry *carry = nullptr;            // = &tail->carry
     struct Pinned { Tail tail; uint32_t flags[4]; } *pin = nullptr;   // pinned landing zone of the small read-backs
@@ -232,6 +232,21 @@ struct pk_indexer {
     bool table_fresh = true;         // no feed has written the u8 table since the last reset
     uint8_t *ws = nullptr;           // workspace of the partition passes
     size_t ws_cap = 0;
+    // FASTQ input (fastq.hip): each feed is turned into FASTA text in fq_out[fq_buf]; that text is counted by the next
+    // feed (or by finish), whose read-back brings this feed's checks and totals along -- no wait of its own
+    int format = PK_FORMAT_FASTA;
+    bool fed = false;                  // bytes were fed since the last reset
+    FqSum *fq_sums = nullptr;
+    FqState *fq_st = nullptr;
+    uint32_t fq_chunk_cap = 0;
+    uint8_t *fq_out[2] = {nullptr, nullptr};
+    uint64_t fq_out_cap[2] = {0, 0};
+    int fq_buf = 0;
+    uint64_t fq_pending = 0;           // FASTA bytes in fq_out[fq_buf ^ 1] not counted yet
+    FqRec *fq_recs = nullptr;
+    uint64_t fq_recs_cap = 0, fq_need = 0;
+    bool fq_failed = false;
+    std::string fq_err;
 };
 
 static int ix_reset(pk_indexer *ix) {
@@ -251,6 +266,8 @@ static int ix_reset(pk_indexer *ix) {
     ix->table_fresh = true;
     ix->t_scan = ix->t_squeeze = ix->t_sort = ix->t_final = ix->t_part = ix->t_bucket = 0;
     ix->feeds = ix->relayouts = 0; ix->recounted = 0;
+    ix->fed = false;
+    ix->fq_pending = 0; ix->fq_need = 0; ix->fq_failed = false; ix->fq_err.clear();
     return PK_OK;
 }
 
@@ -269,6 +286,7 @@ extern "C" void pk_indexer_destroy(pk_indexer *ix) {
     hipFree(ix->table8); hipFree(ix->tail); hipFree(ix->tail0); hipFree(ix->hist_rep); hipFree(ix->recs);
     if (ix->pin) hipHostFree(ix->pin);
     hipFree(ix->c_l1); hipFree(ix->c_l1s); hipFree(ix->c_l2); hipFree(ix->c_l2s); hipFree(ix->lane_state); hipFree(ix->packs); hipFree(ix->chunk_odd); hipFree(ix->t_l1); hipFree(ix->t_l2); hipFree(ix->staging[0]); hipFree(ix->staging[1]); hipFree(ix->ws);
+    hipFree(ix->fq_sums); hipFree(ix->fq_st); hipFree(ix->fq_out[0]); hipFree(ix->fq_out[1]); hipFree(ix->fq_recs);
     for (auto &e : ix->ev) if (e) hipEventDestroy(e);
     if (ix->stream) hipStreamDestroy(ix->stream);
     delete ix;
@@ -310,6 +328,12 @@ extern "C" int pk_indexer_create_slice(pk_indexer **out, int k, int device, int 
         c.l2.flags = F_NONID | F_PRESET | F_BRK;             // l2_state(0, 0, 0, 0)
         if ((e = hipMemset(ix->tail0, 0, sizeof(pk_indexer::Tail))) != hipSuccess) return bail(e, "hipMemset(carry0)");
         if ((e = hipMemcpy(&ix->tail0->carry, &c, sizeof c, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(carry0)");
+        FqCarry q;
+        memset(&q, 0, sizeof q);
+        q.st.ws = q.in.ws = 1;                               // the open line (none yet) holds no text
+        q.err = q.trail = ~0ull;
+        q.prev4 = q.prev4_in = 0x0a0a0a0au;                  // before the stream: line terminators
+        if ((e = hipMemcpy(&ix->tail0->fq, &q, sizeof q, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(fastq carry0)");
     }
     if ((e = hipMalloc(&ix->hist_rep, (size_t)HIST_REPLICAS * 256 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(hist replicas)");
     if ((e = hipMemset(ix->hist_rep, 0, (size_t)HIST_REPLICAS * 256 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(hist replicas)");
@@ -473,6 +497,146 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     return PK_OK;
 }
 
+
+// ================================================================== FASTQ front end ============
+static const char *fq_rule_text(uint32_t rule) {
+    switch (rule) {
+    case FQ_RULE_AT: return "line 1 must begin with '@' (after an empty line 1 only line terminators may follow)";
+    case FQ_RULE_GT: return "line 2 must not begin with '>'";
+    case FQ_RULE_PLUS: return "line 3 must begin with '+'";
+    case FQ_RULE_LEN: return "line 4 must be as long as line 2";
+    default: return "the stream ends inside the record";
+    }
+}
+
+// the indexer stops at a malformed record until it is reset; rec is 0-based
+static int fq_fail(pk_indexer *ix, uint64_t rec, uint32_t rule) {
+    uint64_t line1 = 0;
+    if (rec < ix->fq_recs_cap) HIPCHK(hipMemcpy(&line1, &ix->fq_recs[rec].line1, sizeof line1, hipMemcpyDeviceToHost));
+    fail(PK_ERR_FORMAT, "malformed FASTQ: record %llu (line 1 at byte %llu): %s", (unsigned long long)rec + 1, (unsigned long long)line1,
+         fq_rule_text(rule));
+    ix->fq_failed = true;
+    ix->fq_err = g_err;
+    return PK_ERR_FORMAT;
+}
+
+// the rules the kernels checked, as the feed's read-back left them in pin
+static int fq_verdict(pk_indexer *ix) {
+    const FqCarry &q = ix->pin->tail.fq;
+    uint64_t rec = ~0ull;
+    uint32_t rule = 0;
+    if (q.err != ~0ull) { rec = q.err >> 3; rule = (uint32_t)(q.err & 7u); }
+    if (q.trail != ~0ull) {                                  // an empty line 1: its record and everything behind it must be blank
+        const uint64_t tr = q.trail / 4u;
+        if (rec != ~0ull && rec >= tr) rec = ~0ull;          // the blank lines there break the record rules, and that is fine
+        if (q.full > q.trail + 1u && tr < rec) { rec = tr; rule = FQ_RULE_AT; }
+    }
+    return rec == ~0ull ? PK_OK : fq_fail(ix, rec, rule);
+}
+
+static int fq_ensure_recs(pk_indexer *ix, uint64_t need) {
+    if (need <= ix->fq_recs_cap) return PK_OK;
+    const uint64_t cap = std::max<uint64_t>(need, 2 * ix->fq_recs_cap);
+    FqRec *nr = nullptr;
+    HIPCHK(hipMalloc(&nr, cap * sizeof(FqRec)));
+    HIPCHK(hipMemsetAsync(nr, 0, cap * sizeof(FqRec), ix->stream));
+    if (ix->fq_recs_cap) HIPCHK(hipMemcpyAsync(nr, ix->fq_recs, ix->fq_recs_cap * sizeof(FqRec), hipMemcpyDeviceToDevice, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    hipFree(ix->fq_recs);
+    ix->fq_recs = nr; ix->fq_recs_cap = cap;
+    return PK_OK;
+}
+
+// the FASTA text of the previous FASTQ feed, if any, into the pipeline; ends with the read-back of the carry
+static int fq_flush(pk_indexer *ix) {
+    if (ix->fq_pending) {
+        const uint64_t n = ix->fq_pending;
+        ix->fq_pending = 0;
+        return feed_piece(ix, ix->fq_out[ix->fq_buf ^ 1], n);
+    }
+    HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    HIPCHK(hipGetLastError());
+    time_reset(ix);
+    ix->tail_on_host = true;
+    return PK_OK;
+}
+
+// one FASTQ piece of at most feed_max_for(k) bytes: the front end turns it into FASTA text in fq_out[fq_buf] while the
+// text of the piece before goes through the FASTA pipeline
+static int fq_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n) {
+    const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
+    if (n_chunks > ix->fq_chunk_cap) {
+        hipFree(ix->fq_sums); hipFree(ix->fq_st); ix->fq_sums = nullptr; ix->fq_st = nullptr; ix->fq_chunk_cap = 0;
+        HIPCHK(hipMalloc(&ix->fq_sums, (size_t)n_chunks * sizeof(FqSum)));
+        HIPCHK(hipMalloc(&ix->fq_st, (size_t)n_chunks * sizeof(FqState)));
+        ix->fq_chunk_cap = n_chunks;
+    }
+    const int b = ix->fq_buf;
+    if (n + 64 > ix->fq_out_cap[b]) {
+        hipFree(ix->fq_out[b]); ix->fq_out[b] = nullptr; ix->fq_out_cap[b] = 0;
+        HIPCHK(hipMalloc(&ix->fq_out[b], n + 64));
+        ix->fq_out_cap[b] = n + 64;
+    }
+    // record slots for what the stream needed so far and one record per 256 bytes of this piece; a piece that needs
+    // more writes its text again once the array has grown
+    int rc = fq_ensure_recs(ix, ix->fq_need + n / 256 + 1024);
+    if (rc) return rc;
+    launch_fq_front(f, n, ix->fq_sums, ix->fq_st, ix->fq_out[b], ix->fq_recs, ix->fq_recs_cap, &ix->tail->fq, ix->stream);
+    HIPCHK(hipGetLastError());
+    if ((rc = fq_flush(ix))) return rc;
+    if (ix->pin->tail.fq.need > ix->fq_recs_cap) {
+        if ((rc = fq_ensure_recs(ix, ix->pin->tail.fq.need + n / 256 + 1024))) return rc;
+        launch_fq_write(f, n, ix->fq_st, ix->fq_out[b], ix->fq_recs, ix->fq_recs_cap, &ix->tail->fq, ix->stream);
+        HIPCHK(hipGetLastError());
+        if ((rc = fq_flush(ix))) return rc;
+    }
+    const FqCarry &q = ix->pin->tail.fq;
+    ix->fq_need = q.need;
+    if ((rc = fq_verdict(ix))) return rc;
+    ix->fq_pending = q.st.out - q.in.out;
+    ix->fq_buf = b ^ 1;
+    return PK_OK;
+}
+
+// end of stream: after the last complete record only line terminators (checked with the feeds), or a last line 4
+// without a terminator
+static int fq_end_check(pk_indexer *ix) {
+    const FqCarry &q = ix->pin->tail.fq;
+    if (q.trail != ~0ull) return PK_OK;
+    const uint32_t role = (uint32_t)(q.st.line & 3u);
+    const uint64_t rec = q.st.line / 4u;
+    if (role == 0u && q.st.curlen == 0) return PK_OK;
+    if (role == 3u && q.st.curlen > 0) {
+        uint64_t len2 = 0;
+        if (rec < ix->fq_recs_cap) HIPCHK(hipMemcpy(&len2, &ix->fq_recs[rec].len2, sizeof len2, hipMemcpyDeviceToHost));
+        return len2 == q.st.curlen ? PK_OK : fq_fail(ix, rec, FQ_RULE_LEN);
+    }
+    return fq_fail(ix, rec, FQ_RULE_END);
+}
+
+extern "C" int pk_indexer_set_format(pk_indexer *ix, int format) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (format != PK_FORMAT_FASTA && format != PK_FORMAT_FASTQ) return fail(PK_ERR_ARG, "unknown input format %d", format);
+    if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the input format is set before the first feed (reset the indexer first)");
+    ix->format = format;
+    return PK_OK;
+}
+
+extern "C" int pk_indexer_fastq_stats(pk_indexer *ix, uint64_t out[4]) {
+    if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
+    if (ix->format != PK_FORMAT_FASTQ) return fail(PK_ERR_STATE, "not a FASTQ indexer");
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (!ix->fed) return PK_OK;
+    const FqCarry &q = ix->pin->tail.fq;                     // every feed ends with its read-back
+    const uint64_t lines = q.st.line + (q.st.curlen > 0 ? 1u : 0u);
+    out[0] = q.trail != ~0ull ? q.trail / 4u : (lines + 3u) / 4u;
+    out[1] = lines;
+    out[2] = q.bytes_fed;
+    out[3] = q.st.out;
+    return PK_OK;
+}
+
 extern "C" int pk_indexer_feed_device(pk_indexer *ix, const void *dev_fasta, uint64_t n_bytes) {
     if (!ix) return fail(PK_ERR_ARG, "null indexer");
     if (ix->finished) return fail(PK_ERR_STATE, "indexer already finished; reset it first");
@@ -482,8 +646,12 @@ extern "C" int pk_indexer_feed_device(pk_indexer *ix, const void *dev_fasta, uin
     HIPCHK(hipSetDevice(ix->device));
     const uint8_t *f = (const uint8_t *)dev_fasta;
     const uint64_t piece_max = feed_max_for(ix->k);                 // a multiple of 16: pieces stay aligned
+    const bool fastq = ix->format == PK_FORMAT_FASTQ;
+    if (fastq && ix->fq_failed) return fail(PK_ERR_FORMAT, "%s", ix->fq_err.c_str());
+    ix->fed = true;
     for (uint64_t off = 0; off < n_bytes; off += piece_max) {
-        int rc = feed_piece(ix, f + off, std::min(piece_max, n_bytes - off));
+        const uint64_t len = std::min(piece_max, n_bytes - off);
+        int rc = fastq ? fq_feed_piece(ix, f + off, len) : feed_piece(ix, f + off, len);
         if (rc) return rc;
     }
     return PK_OK;
@@ -532,6 +700,13 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
                                  uint64_t *n_recs_out) {
     if (!ix) return fail(PK_ERR_ARG, "null indexer");
     HIPCHK(hipSetDevice(ix->device));
+    if (!ix->finished && ix->format == PK_FORMAT_FASTQ) {
+        if (ix->fq_failed) return fail(PK_ERR_FORMAT, "%s", ix->fq_err.c_str());
+        if (ix->fq_pending) {                                // the last feed's text
+            int rc = fq_flush(ix);
+            if (rc) return rc;
+        }
+    }
     if (!ix->finished) {
         if (ix->tail_on_host && !ix->table_fresh) {
             // the usual case: the last feed's read-back already holds the totals and the histogram (kept up to date by
@@ -552,6 +727,10 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
             float ms = 0;
             HIPCHK(hipEventElapsedTime(&ms, ix->ev[4], ix->ev[5]));
             ix->t_final = ms * 1e-3;
+        }
+        if (ix->format == PK_FORMAT_FASTQ) {
+            int rc = fq_end_check(ix);
+            if (rc) return rc;
         }
         ix->finished = true;
     }
@@ -581,6 +760,12 @@ extern "C" int pk_indexer_records(pk_indexer *ix, pk_record *recs_out, uint64_t 
         recs_out[i].name_len = tmp[i].name_end > tmp[i].name_off ? tmp[i].name_end - tmp[i].name_off : 0;
         recs_out[i].seq_len = tmp[i].seq_len;
         recs_out[i].n_valid_kmers = tmp[i].n_valid;
+    }
+    if (ix->format == PK_FORMAT_FASTQ) {                     // FASTQ record i is FASTA record i: names are sliced from the FASTQ
+        if (ix->n_recs > ix->fq_recs_cap) return fail(PK_ERR_HIP, "FASTQ record array too small (internal error)");
+        std::vector<FqRec> fq(ix->n_recs);
+        HIPCHK(hipMemcpy(fq.data(), ix->fq_recs, ix->n_recs * sizeof(FqRec), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < ix->n_recs; i++) recs_out[i].name_off = fq[i].line1 + 1;
     }
     return PK_OK;
 }

@@ -81,6 +81,41 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
 constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
 constexpr uint32_t PART_FLAG_WORDS = 6;   // side_n (u64) + flags[4], zeroed together
 
+// fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
+struct FqState {             // the stream after some prefix of it
+    uint64_t line;           // line terminators seen (the role of the open line is line & 3)
+    uint64_t out;            // bytes emitted to the FASTA pipeline
+    uint64_t curlen;         // bytes of the open line so far
+    uint32_t ws, pad;        // 1: the open line holds nothing but str.strip() whitespace so far
+};
+struct FqSum {               // what a stretch of bytes does to an FqState
+    uint32_t nt;             // terminators
+    uint32_t tail;           // bytes behind the last one (or all of them)
+    uint32_t kept[4];        // bytes kept when entered in role r
+    uint32_t ws, pad;        // 1: the tail holds only whitespace
+};
+struct FqRec {               // per record number
+    uint64_t line1;          // stream offset of line 1
+    uint64_t len2, len4;     // raw lengths of lines 2 and 4
+};
+enum : uint32_t { FQ_RULE_AT = 1, FQ_RULE_GT = 2, FQ_RULE_PLUS = 3, FQ_RULE_LEN = 4, FQ_RULE_END = 5 };
+struct FqCarry {
+    FqState st;              // after everything fed
+    FqState in;              // at the start of the last feed
+    uint64_t bytes_fed, in_bytes;
+    uint64_t err;            // smallest (record << 3 | rule) that broke a rule, ~0: none
+    uint64_t trail;          // the first empty header line (only blank lines may follow it), ~0: none
+    uint64_t full;           // 1 + the last line with a byte that is no terminator
+    uint64_t need;           // record slots the stream needs
+    uint32_t prev4, prev4_in;   // the last 4 bytes of the stream (before the last feed), newest highest
+};
+// k_fq_count + k_fq_scan + launch_fq_write.  out: n + 64 bytes; record slots at or beyond recs_cap are not written
+// (carry->need says how many are needed, and launch_fq_write can be repeated with a larger array).
+void launch_fq_front(const uint8_t *fastq, uint64_t n, FqSum *sums, FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap,
+                     FqCarry *carry, hipStream_t s);
+void launch_fq_write(const uint8_t *fastq, uint64_t n, const FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap, FqCarry *carry,
+                     hipStream_t s);
+
 // gram_scan.hip
 // tables: device array of N device pointers, each n_slice bytes (16-byte aligned).  pair: device N*N u64,
 // zeroed by the launcher when zero_first; [i][i] += total_i, [i][j] (i<j) += shared_ij.

@@ -28,12 +28,21 @@ def _mark(what: str) -> None:
 RESIDENT_LIMIT = 16 << 30       # inputs up to this size (decompressed) are kept in host memory for the header names
 
 
+FASTQ_SUFFIXES = tuple(s + z for s in (".fq", ".fastq") for z in ("", ".gz", ".bgz"))
+
+
+def input_format(input_file: str) -> str:
+    """"fastq" for .fq / .fastq, optionally followed by .gz or .bgz; "fasta" for every other name."""
+    return "fastq" if input_file.endswith(FASTQ_SUFFIXES) else "fasta"
+
+
 def _open_input(input_file: str):
     """indexer.py:101-128: .gz / .bgz through gzip, anything else as is (bytes here, text there)."""
+    label = input_format(input_file).upper()
     if input_file.endswith((".gz", ".bgz")):
-        print(f"READING FASTA FROM PYGZ {input_file}")
+        print(f"READING {label} FROM PYGZ {input_file}")
         return gzip.open(input_file, "rb")
-    print(f"READING FASTA FROM {input_file}")
+    print(f"READING {label} FROM {input_file}")
     return open(input_file, "rb")
 
 
@@ -76,6 +85,8 @@ class _Input:
 
     def __init__(self, input_file: str, keep: bool = True, quiet: bool = False):
         self.path = input_file
+        self.fmt = input_format(input_file)
+        self.label = self.fmt.upper()
         self.gz = input_file.endswith((".gz", ".bgz"))
         self.quiet = quiet
         self.kept, self.kept_bytes = ([] if keep else None), 0   # compressed inputs: pieces in order, or None once they no longer fit
@@ -120,7 +131,7 @@ class _Input:
 
     def pieces(self):
         if not self.gz:
-            self._say(f"READING FASTA FROM {self.path}")
+            self._say(f"READING {self.label} FROM {self.path}")
             if os.path.getsize(self.path) == 0:
                 return
             import mmap
@@ -137,10 +148,10 @@ class _Input:
             return
         from . import bgzf
         if bgzf.is_bgzf(self.path):
-            self._say(f"READING FASTA FROM BGZF {self.path}")
+            self._say(f"READING {self.label} FROM BGZF {self.path}")
             source = bgzf.iter_pieces(self.path, GZ_PIECE)
         else:
-            self._say(f"READING FASTA FROM PYGZ {self.path}")
+            self._say(f"READING {self.label} FROM PYGZ {self.path}")
             source = self._gzip_pieces()
         for piece in source:
             self._keep(piece)
@@ -180,7 +191,7 @@ def n_address_slices(kmer_len: int) -> int:
 
 
 def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str = None, devices=None):
-    """Streams one FASTA file through the GPU indexer.
+    """Streams one FASTA or FASTQ file (input_format: by its name) through the GPU indexer.
 
     Returns (table, summary dict, all_records [(name, seq_len, n_valid)]).  With `table_file` the 4^k-byte
     table is written straight into that file (tools.py:333-341: exactly 4^k bytes, no header) piece by piece as
@@ -220,7 +231,7 @@ def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str 
         as they land, later slices are hashed whole once it is their turn (the file is hashed in address order)."""
         src = source if s == 0 else _Input(input_file, keep=False, quiet=True)   # only slice 0's names and messages are used
         _mark("creating the indexer (library load, HIP start-up, table and workspace allocation)")
-        with _lib.Indexer(kmer_len, device=devices[s % len(devices)], slice_index=s, n_slices=n_slices) as ix:
+        with _lib.Indexer(kmer_len, device=devices[s % len(devices)], slice_index=s, n_slices=n_slices, fmt=src.fmt) as ix:
             _mark("indexer ready")
             for piece in src.pieces():
                 ix.feed(piece)

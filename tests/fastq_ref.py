@@ -1,0 +1,110 @@
+"""Plain-Python restatement of the FASTQ input rules (README "FASTQ input"), for the tests only.
+
+fastq_to_fasta(data) is the FASTA text a FASTQ stream stands for; the GPU front end (fastq.hip) must count a FASTQ
+exactly as the FASTA pipeline counts this text, and emit exactly len(fastq_to_fasta(data)) bytes into it.
+"""
+import re
+from typing import List, Tuple
+
+import numpy as np
+
+WS = b" \t\n\v\f\r\x1c\x1d\x1e\x1f"          # str.strip() whitespace, ASCII
+
+RULES = {
+    1: "line 1 must begin with '@'",
+    2: "line 2 must not begin with '>'",
+    3: "line 3 must begin with '+'",
+    4: "line 4 must be as long as line 2",
+    5: "the stream ends inside the record",
+}
+
+
+class FastqError(ValueError):
+    def __init__(self, record: int, offset: int, rule: int):
+        super().__init__(f"record {record} (line 1 at byte {offset}): {RULES[rule]}")
+        self.record, self.offset, self.rule = record, offset, rule
+
+
+_LINE = re.compile(rb"[^\r\n]*(?:\r\n|\r|\n)|[^\r\n]+$")
+
+
+def lines(data: bytes) -> List[Tuple[int, int, int]]:
+    """(start, end of text, end of terminator) of every line; terminators \\n, \\r\\n and a lone \\r."""
+    out = []
+    for m in _LINE.finditer(data):
+        s, t = m.start(), m.end()
+        e = t - (2 if data.endswith(b"\r\n", s, t) else 1 if t > s and data[t - 1] in (10, 13) else 0)
+        out.append((s, e, t))
+    return out
+
+
+def fastq_to_fasta(data: bytes) -> bytes:
+    """The FASTA text of a FASTQ stream; raises FastqError (1-based record, offset of its line 1, rule) if malformed."""
+    data = bytes(data)
+    ls = lines(data)
+    out = []
+    for r in range(0, len(ls), 4):
+        rec, group = r // 4 + 1, ls[r:r + 4]
+        s1, e1, t1 = group[0]
+        if s1 == e1:                                        # an empty line 1: only line terminators may follow
+            if any(s != e for s, e, _ in ls[r:]):
+                raise FastqError(rec, s1, 1)
+            break
+        if data[s1] != ord("@"):
+            raise FastqError(rec, s1, 1)
+        if len(group) > 1:
+            s2, e2, t2 = group[1]
+            if data[s2:e2].lstrip(WS).startswith(b">"):
+                raise FastqError(rec, s1, 2)
+        if len(group) > 2:
+            s3, e3, _ = group[2]
+            if not data[s3:e3].startswith(b"+"):
+                raise FastqError(rec, s1, 3)
+        if len(group) > 3:
+            s4, e4, _ = group[3]
+            if e4 - s4 != e2 - s2:
+                raise FastqError(rec, s1, 4)
+        if len(group) < 4:
+            raise FastqError(rec, s1, 5)
+        out.append(b">" + data[s1 + 1:t2])
+    return b"".join(out)
+
+
+def stats(data: bytes) -> dict:
+    """What pk_indexer_fastq_stats reports for a well-formed stream."""
+    ls = lines(bytes(data))
+    records = 0
+    for r in range(0, len(ls), 4):
+        if ls[r][0] == ls[r][1]:
+            break
+        records += 1
+    return {"records": records, "lines": len(ls), "bytes_fed": len(data), "bytes_emitted": len(fastq_to_fasta(data))}
+
+
+def read_set(n_reads: int, length: int = 150, seed: int = 0, genome_bp: int = 1 << 20, sub_rate: float = 0.01,
+             n_rate: float = 0.002, crlf: bool = False, genome: np.ndarray = None):
+    """(fastq, fasta): n_reads reads of `length` bp sampled from a random genome (or `genome`, base codes 0..3) on either
+    strand, with substitution errors and some N; the FASTA is what fastq_to_fasta makes of the FASTQ, built directly
+    (fast for large sets)."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    if genome is None:
+        genome = rng.integers(0, 4, genome_bp, dtype=np.uint8)
+    genome_bp = genome.size
+    starts = rng.integers(0, genome_bp - length, n_reads)
+    codes = genome[starts[:, None] + np.arange(length)]
+    rev = rng.random(n_reads) < 0.5
+    codes[rev] = 3 - codes[rev, ::-1]
+    sub = rng.random(codes.shape) < sub_rate
+    codes[sub] = (codes[sub] + rng.integers(1, 4, int(sub.sum()), dtype=np.uint8)) & 3
+    seq = acgt[codes]
+    seq[rng.random(codes.shape) < n_rate] = ord("N")
+    qual = (rng.integers(33, 74, codes.shape, dtype=np.uint8))
+    nl = b"\r\n" if crlf else b"\n"
+    fq, fa = [], []
+    for i in range(n_reads):
+        name = b"read%d/%d len=%d" % (i, seed, length)
+        s = seq[i].tobytes()
+        fq.append(b"@" + name + nl + s + nl + b"+" + nl + qual[i].tobytes() + nl)
+        fa.append(b">" + name + nl + s + nl)
+    return b"".join(fq), b"".join(fa)
