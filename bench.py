@@ -9,7 +9,13 @@ level-1 sort (k_walk_sort), level-2 sort, bucket count into the 4^k table (which
 side list.  Prints ONE JSON line on rank 0.  The merge legs call pykmer_amd.merger.pair_matrix, the function
 merger.py runs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bp 800000000] [--no-merge] [--no-cpu] [--dump-outputs DIR]
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline, the stage
+split of the timed steps and the roofline derived from them.  --full adds what takes runs of its own: the merge legs
+(N=13 and N=32, with the threshold sweep), the CPU baselines with their parity checks against the GPU, and the
+end-to-end timings of the two CLIs; --no-merge / --no-merge32 / --no-cpu / --no-e2e leave pieces of it out.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bp 800000000] [--dump-outputs DIR]
+                    [--full [--no-merge] [--no-merge32] [--no-cpu] [--no-e2e]]
 """
 import argparse
 import json
@@ -160,10 +166,12 @@ def main():
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--merge-n", type=int, default=13)
     ap.add_argument("--merge-bp", type=int, default=40_000_000, help="genome size behind each merge table")
-    ap.add_argument("--no-merge", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the bench line's steps, also run the merge legs, the CPU baselines and the end-to-end CLI timings")
+    ap.add_argument("--no-merge", action="store_true", help="skip the merge legs (and the merge matrices of --dump-outputs)")
     ap.add_argument("--no-merge32", action="store_true", help="skip the 32-table merge (config 5 shape)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (disk -> files) timings of the two CLIs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end (disk -> files) timings of the two CLIs")
     ap.add_argument("--cpu-bp", type=int, default=160_000_000, help="sample size for the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the all-cores CPU legs (default 0 = every core this process may run on)")
@@ -341,11 +349,16 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 best = float(tt.item())
             return best, kern, pairs
-        best, kern, pairs = timed([(1, 255)])
+        if args.full:
+            best, kern, pairs = timed([(1, 255)])
+        else:                                                      # --dump-outputs alone: the matrix from one untimed call
+            pairs = merger.pair_matrix(tabs, [(1, 255)], devices=(local,), group=group)
         total = pairs[0].astype(np.int64)
         if args.dump_outputs and rank == 0:
             save_output(args.dump_outputs, f"merge_n{N}_pairs", pairs[0])
         assert all(total[i, j] <= min(total[i, i], total[j, j]) for i in range(N) for j in range(i + 1, N))
+        if not args.full:
+            return None
         res = {"n_tables": N, "k": k, "seconds": best, "kernel_seconds_rank0": kern, "algorithmic_bytes": N * n,
                "kernel_GBps_aggregate": N * n / kern / 1e9 if world == 1 else None,
                "end_to_end_GBps_aggregate": N * n / best / 1e9,
@@ -384,22 +397,24 @@ def main():
                 "slice_equals_gpu": same, "host": cpu_info()}
         return res
 
-    if not args.no_merge:                                               # secondary objects: never allowed to cost the bench line
+    if not args.no_merge and (args.full or args.dump_outputs):           # secondary objects: never allowed to cost the bench line
         def guarded(n_tables):
             # every rank must take the same path (the sharded merge all-reduces), so errors are not swallowed
-            # when running distributed
-            if dist is not None:
+            # when running distributed; nor when the section only writes outputs, which must not go missing quietly
+            if dist is not None or not args.full:
                 return merge_section(n_tables)
             try:
                 return merge_section(n_tables)
             except Exception as exc:
                 return {"n_tables": n_tables, "error": f"{type(exc).__name__}: {exc}"}
-        out["merge"] = guarded(args.merge_n)
-        if args.merge_n != 32 and not args.no_merge32:
-            out["merge_n32"] = guarded(32)
+        legs = [("merge", args.merge_n)] + ([("merge_n32", 32)] if args.merge_n != 32 and not args.no_merge32 else [])
+        for key, n_tables in legs:
+            res = guarded(n_tables)
+            if res is not None:
+                out[key] = res
 
     # ---- CPU baseline: the oracle's C restatement, one core, bounded sample of the same workload
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             import oracle
             fa, bp = synth.c2(args.cpu_bp, seed=2)
@@ -441,7 +456,7 @@ def main():
     # ---- end to end (t_e2e beside t_kernel).  (1) the one-shot C-ABI call on host buffers: PCIe both ways
     # (0.81 GB up, 1 GiB table down) inside the call; (2) the two CLIs as fresh processes on tmpfs files: process start ->
     # .kin/.kin.json (.kma/.kma.json) renamed, i.e. interpreter + HIP start-up, disk, PCIe, both sha256 sums.
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         try:
             out["e2e"] = end_to_end(fasta, total_bp, k, local)
         except Exception as exc:

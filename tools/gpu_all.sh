@@ -9,7 +9,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu --maxfail=6 -q -s --durations=1
 echo "pytest rc=$?" >> $O/pytest.log
 tail -30 $O/pytest.log
 grep -q "pytest rc=0" $O/pytest.log || exit 1
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 2; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 2; }
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Derive profiles/hbm_traffic.json from the two PMC passes.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D1 -o fetch -- python3 bench.py --steps 2 --warmup 0 --no-cpu
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d D2 -o write -- python3 bench.py --steps 2 --warmup 0 --no-cpu
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d D1 -o fetch -- python3 bench.py --full --steps 2 --warmup 0 --no-cpu
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d D2 -o write -- python3 bench.py --full --steps 2 --warmup 0 --no-cpu
     python tools/hbm_traffic.py fetch_counter_collection.csv write_counter_collection.csv > profiles/hbm_traffic.json
 
 Per kernel the LARGEST dispatch is taken (= the 800 Mbp k=15 step; bench.py also runs 40 Mbp genomes for
@@ -50,7 +50,7 @@ def main() -> None:
     fetch_csv, write_csv = sys.argv[1], sys.argv[2]
     fetch, write = largest(fetch_csv, "FETCH_SIZE"), largest(write_csv, "WRITE_SIZE")
     out = {
-        "_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, `bench.py --steps 2 --warmup 0 --no-cpu`), "
+        "_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, `bench.py --full --steps 2 --warmup 0 --no-cpu`), "
                  "largest dispatch per kernel (= the 800 Mbp step); bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 per "
                  "MI355X_MICROARCH.md HBM section (FETCH_SIZE reads half of a wide coalesced stream on gfx950). "
                  "Calibration: k_gram_blk (N=32) vs 34.36 GB algorithmic; k_chunk_l2 vs 0.813 GB FASTA + 0.102 GB lane states + 0.407 GB piece packs. "

@@ -7,13 +7,13 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 O=gpurun_out/profile_round
 mkdir -p $O
-timeout -k 10 600 python bench.py > $O/bench.json
+timeout -k 10 600 python bench.py --full > $O/bench.json
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o ks -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-merge --no-e2e > $O/bench_under_rocprof.json
 echo "stats done"
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o fetch -- python3 bench.py --steps 2 --warmup 0 --no-cpu --no-e2e > $O/pmc_fetch.log
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o fetch -- python3 bench.py --full --steps 2 --warmup 0 --no-cpu --no-e2e > $O/pmc_fetch.log
 echo "fetch done"
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o write -- python3 bench.py --steps 2 --warmup 0 --no-cpu --no-e2e > $O/pmc_write.log
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o write -- python3 bench.py --full --steps 2 --warmup 0 --no-cpu --no-e2e > $O/pmc_write.log
 echo "write done"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch_k17 -o fetch -- python3 bench.py --k 17 --steps 2 --warmup 0 --no-cpu --no-merge --no-e2e > $O/pmc_fetch_k17.log
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write_k17 -o write -- python3 bench.py --k 17 --steps 2 --warmup 0 --no-cpu --no-merge --no-e2e > $O/pmc_write_k17.log
