@@ -78,17 +78,23 @@ def count_fasta(fasta, k: int, table: np.ndarray = None):
             "records": recs[: nr.value].copy()}
 
 
-def kmer_list(fasta, k: int) -> np.ndarray:
-    """Canonical value of every valid window, in text order (u64) -- for k where the 4^k table is out of reach."""
+def kmer_list(fasta, k: int, records: bool = False):
+    """Canonical value of every valid window, in text order (u64) -- for k where the 4^k table is out of reach.
+    records=True: (kmers, dict(num_kmers, total_bp, records[RECORD_DTYPE])) instead."""
     lib = _load()
     buf = np.frombuffer(fasta, dtype=np.uint8) if isinstance(fasta, (bytes, bytearray)) else np.ascontiguousarray(fasta)
     out = np.zeros(max(1, buf.size), dtype=np.uint64)
     nk, bp, nr = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    rc = lib.pko_count_fasta_ex(buf.ctypes.data, buf.size, k, None, ctypes.byref(nk), ctypes.byref(bp), None, 0, ctypes.byref(nr),
-                                out.ctypes.data, out.size)
+    cap = int(np.count_nonzero(buf == ord(">"))) + 1 if records else 0    # every record opens with a '>'
+    recs = np.zeros(max(1, cap), dtype=RECORD_DTYPE)
+    rc = lib.pko_count_fasta_ex(buf.ctypes.data, buf.size, k, None, ctypes.byref(nk), ctypes.byref(bp),
+                                recs.ctypes.data if records else None, cap, ctypes.byref(nr), out.ctypes.data, out.size)
     if rc != 0:
         raise ValueError(f"oracle rejected k={k}")
-    return out[: nk.value]
+    if not records:
+        return out[: nk.value]
+    assert nr.value <= cap
+    return out[: nk.value], {"num_kmers": int(nk.value), "total_bp": int(bp.value), "records": recs[: nr.value].copy()}
 
 
 def count_fasta_mt(fasta, k: int, threads: int, table: np.ndarray = None):

@@ -29,7 +29,9 @@
 // sorts claim room for every run from per-bucket cursors.
 // A bucket that outgrows its room raises a flag (its runs go to a dump area, nothing is overwritten); every
 // later kernel of the feed then returns at once and the host repeats from here with stride 1, i.e. with
-// exact sizes.  Inputs below 1024 chunks are counted exactly straight away.
+// exact sizes.  Inputs below 1024 chunks are counted exactly straight away.  Every kernel here also returns at once
+// when it finds the flag already raised (flags[0] = 2: the squeeze backed out, so codes / restarts / n_bases still
+// hold an earlier text): a raised flag keeps the value it was raised with until the host has read it.
 #include "part_common.h"
 
 namespace pk {
@@ -70,11 +72,17 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
     uint32_t *tally = reinterpret_cast<uint32_t *>(smem);                 // COUNT only: the sort's LDS is not used then
     __shared__ HotTable<COUNT ? 2u : HS> hot;
     const uint32_t k = KC ? KC : pl.k, km1 = k - 1;                       // KC: k as a literal (the k = 15 instantiation)
+    // A raised flags[0] (the squeeze backed out, or the layout failed) means the workspace does not hold this attempt's
+    // text or rooms: nothing is read or written then.  The sampling launch writes no flag, so every thread sees the
+    // same word; the sorting launch raises flags[0] itself while it runs (part_common.h: scatter_tile), so one thread
+    // reads it for the whole workgroup and the barrier below hands it on (a workgroup that half returned would sort
+    // with counters nobody zeroed).
+    if (COUNT && flags[0]) return;
     if (COUNT) {
         for (uint32_t i = threadIdx.x; i < n_tally; i += NT) tally[i] = 0u;
     } else {
         for (uint32_t i = threadIdx.x; i < HS; i += NT) { hot.key[i] = 0ull; hot.val[i] = 0u; }
-        if (threadIdx.x == 0) hot.used = 0;
+        if (threadIdx.x == 0) { hot.used = 0; L.pad_[1] = flags[0]; }
         for (uint32_t i = threadIdx.x; i < NB; i += NT) { L.hist[i] = 0; L.run[i] = 0; }
     }
     // unsliced k = 15 / 17 tables always split 7 + rest / 9 + rest (make_part_plan): digit position and count as literals
@@ -88,6 +96,7 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
     const KT local_mask = (KT)((pl.addr_bits >= sizeof(KT) * 8u) ? ~(KT)0 : (((KT)1 << pl.addr_bits) - 1));   // SLICED: address inside the range
     uint32_t t = threadIdx.x;                                             // COUNT: the thread's place in the slot its WAVE samples (see locate)
     __syncthreads();
+    if (!COUNT && L.pad_[1]) return;                                      // uniform: one LDS word, behind the barrier
     // items: this workgroup's slots (persistent over a contiguous range), or every stride-th slot when sampling
     const uint32_t i_lo = COUNT ? blockIdx.x : blockIdx.x * pl.G1, i_hi = COUNT ? n_items : min(i_lo + pl.G1, n_items);
     const uint32_t i_step = COUNT ? gridDim.x : 1u;
@@ -394,6 +403,7 @@ __global__ __launch_bounds__(1024) void k_provision(const uint32_t *__restrict__
                                                     uint32_t *__restrict__ cursor2, uint32_t *__restrict__ cap2_end, uint32_t *flags) {
     __shared__ uint32_t wsum[16];
     __shared__ unsigned long long sum1[512];                // sampled tallies per level-1 bucket
+    if (flags[0]) return;                                   // the squeeze backed out: the tallies are not this feed's
     const uint32_t B1 = pl.B1;
     const bool two = n_tally > B1;                          // final-bucket tallies: lay out level 2 as well
     const double scale = (double)pl.n_chunks / (double)n_sampled;

@@ -217,8 +217,9 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
                                                 DevRec *__restrict__ recs, uint64_t recs_cap, Carry *carry, uint32_t *__restrict__ flags) {
     // The record array was sized before this feed's records were counted (no host round trip between the structure pass and
     // this kernel).  The count is known here -- the structure pass's scan left it in `carry` -- so if the array is too
-    // small every workgroup returns before touching anything, flags[0] = 2 keeps the later kernels of the feed away, and
-    // the host grows the array and repeats from here.
+    // small every workgroup returns before touching anything, flags[0] = 2 keeps the later kernels of the feed away (each
+    // of them returns at once on a raised flag and none overwrites it: the workspace still holds an earlier feed's text),
+    // and the host grows the array and repeats from here.
     if (carry->n_recs > recs_cap) {
         if (blockIdx.x == 0 && threadIdx.x == 0) flags[0] = 2u;
         return;

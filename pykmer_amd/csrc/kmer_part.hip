@@ -22,8 +22,9 @@
 // only when a bucket's counters leave LDS (indexer.py:239,262), and K6 folds the slice already in
 // HBM back in, so several feeds accumulate exactly like the reference's flushes.
 //
-// `flags[0]` is raised by the level-1 sort when a provisioned bucket ran out of room (kmer_fuse.hip); every
-// kernel below then returns without touching anything and the host repeats the level with exact sizes.
+// `flags[0]` is raised by the level-1 sort when a provisioned bucket ran out of room (kmer_fuse.hip), or by the squeeze
+// when the record array is too small (kmer_pack.hip, 2); every kernel below then returns without touching anything and
+// the host repeats the level with exact sizes (or the squeeze with a larger array).
 #include <cstddef>
 #include "part_common.h"
 

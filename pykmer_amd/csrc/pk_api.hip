@@ -431,7 +431,9 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     // Nothing between here and the last kernel of the feed waits for the device: the record array was sized from what the
     // feeds so far held (ensure_recs below, after the feed), the squeeze pass checks that against the count the structure
     // pass leaves in `carry` and backs out if it does not fit (flags[0] = 2), the sorts back out if a sampled bucket
-    // room does not hold (flags[0] = 1), and the host reads flags + record count once, behind the last kernel.
+    // room does not hold (flags[0] = 1), and the host reads flags + record count once, behind the last kernel.  Every
+    // kernel behind the squeeze returns at once when it finds flags[0] raised (the workspace then still holds an earlier
+    // feed's squeezed text), so a 2 reaches the host as a 2, whatever that text would have done to the sampled layout.
     HIPCHK(hipEventRecord(ix->ev[0], ix->stream));
     launch_chunk_l1(f, n_bytes, ix->c_l1, n_chunks, ix->stream);
     launch_scan_l1(ix->c_l1, n_chunks, ix->carry, ix->c_l1s, ix->t_l1, flag_words, PART_FLAG_WORDS, ix->stream);
@@ -441,10 +443,12 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     float a = 0, b = 0, c = 0, d = 0, e = 0;
     bool armed = true;                                       // the scan kernel zeroed the flag words for the first attempt
     bool squeeze = true;
+    uint64_t squeezed_cap = 0;                               // record slots the last squeeze of this feed ran with
     uint32_t stride = pl.sample_stride;
     for (int attempt = 0;; attempt++) {
         if (squeeze) {
             if (!armed) HIPCHK(hipMemsetAsync(flag_words, 0, PART_FLAG_WORDS * 4, ix->stream));
+            squeezed_cap = ix->recs_cap;
             HIPCHK(hipEventRecord(ix->ev[2], ix->stream));
             launch_squeeze(f, n_bytes, ix->bytes_fed, ix->lane_state, ix->packs, ix->c_l2s, ix->chunk_odd, (uint32_t)ix->k, n_chunks, pl.n_wg0, pl.G, (uint32_t *)(ix->ws + lay.codes),
                            (uint32_t *)(ix->ws + lay.restarts), (uint32_t *)(ix->ws + lay.n_bases), ix->recs, ix->recs_cap, ix->carry, flags, ix->stream);
@@ -452,7 +456,8 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
             armed = true;
         }
         // the level-1 buckets are laid out from a sample of the slots; if one of them runs out of room every later kernel
-        // returns untouched (flags[0]) and the passes behind the squeeze are repeated with exact sizes
+        // returns untouched (flags[0] = 1) and the passes behind the squeeze are repeated with exact sizes -- on the text
+        // the squeeze of this feed left, so only once that squeeze has run in full (flags[0] = 2 is handled first)
         if (launch_partitioned(ix->c_l2s, n_bytes, pl, stride, ix->ws, lay, ix->table8, ix->stream, ix->ev[10], ix->ev[11], ix->ev[8],
                                ix->table_fresh, ix->hist, ix->hist_rep, armed))
             return fail(PK_ERR_HIP, "partition pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -479,6 +484,10 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
             ix->relayouts++;
         }
     }
+    // the text counted above is this feed's only if its last squeeze had room for every record (it backs out otherwise)
+    if (ix->pin->tail.carry.n_recs > squeezed_cap)
+        return fail(PK_ERR_HIP, "feed counted without its squeeze: %llu records, %llu slots (internal error)",
+                    (unsigned long long)ix->pin->tail.carry.n_recs, (unsigned long long)squeezed_cap);
     const uint64_t recs_before = ix->n_recs;
     ix->n_recs = ix->pin->tail.carry.n_recs;
     ix->tail_on_host = true;

@@ -79,7 +79,10 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
                        hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
                        unsigned long long *hist, unsigned long long *hist_replicas, bool armed);
 constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
-constexpr uint32_t PART_FLAG_WORDS = 6;   // side_n (u64) + flags[4], zeroed together
+// side_n (u64) + flags[4], zeroed together.  flags[0]: 2 = the squeeze backed out (record array too small), 1 = a bucket
+// room or a layout total overflowed; every kernel behind the squeeze returns at once when it finds it raised, so the first
+// value raised is the one the host reads.  flags[1]: buckets recounted (statistics).
+constexpr uint32_t PART_FLAG_WORDS = 6;
 
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it

@@ -100,32 +100,97 @@ def make_input(spec: dict) -> bytes:
     return data
 
 
-def skewed_fasta(n_bp: int, unit_len: int, seed: int = 7, stretch: int = 2048, chunk: int = 16384, stride: int = 16) -> bytes:
+def skewed_fasta(n_bp: int, unit_len: int, seed: int = 7, stretch: int = 2048, chunk: int = 16384, stride: int = 16,
+                 width=60) -> bytes:
     """One record that defeats the bucket-size sample on purpose.  The indexer sizes its buckets from one wave's stretch
     of bases (`stretch`: 64 threads x 32 bases for 32-bit k-mers, x 16 for 64-bit ones) out of every `stride` stretches:
     stretch number q of the text's 16 KiB chunks is sampled iff q % stride == (q // stride) % stride (kmer_fuse.hip,
     locate).  Here exactly those stretches hold uniform random sequence and everything else repeats one `unit_len`-base
     unit (a period the hot-key path does not look for), so the estimate is wrong by an order of magnitude, the buckets
-    overflow and the exact re-layout has to run."""
+    overflow and the exact re-layout has to run.  `width`: bases per line (None: the whole sequence on one line)."""
     import numpy as np
-    assert n_bp % 60 == 0 and chunk % stretch == 0
+    width = n_bp if width is None else width
+    assert n_bp % width == 0 and chunk % stretch == 0
     rng = np.random.default_rng(seed)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     head = b">skewed_against_the_sample\n"
     i = np.arange(n_bp, dtype=np.int64)
-    off = len(head) + i + i // 60                              # byte offset of base i: 60 bases and a newline per line
-    slot = off // chunk
-    first = np.searchsorted(slot, np.arange(slot[-1] + 1))     # index of the first base of every chunk
-    q = slot * (chunk // stretch) + (i - first[slot]) // stretch
-    sampled = q % stride == (q // stride) % stride
+    sampled = _sampled_bases(len(head), n_bp, width, stretch, chunk, stride)
     unit = acgt[rng.integers(0, 4, size=unit_len)]
     seq = acgt[rng.integers(0, 4, size=n_bp)]
     rep = ~sampled
     seq[rep] = unit[i[rep] % unit_len]
-    lines = np.empty((n_bp // 60, 61), dtype=np.uint8)
-    lines[:, :60] = seq.reshape(-1, 60)
-    lines[:, 60] = 10
-    return head + lines.tobytes()
+    return head + _lines(seq, width)
+
+
+def _base_offsets(head_len: int, n_bp: int, width: int):
+    import numpy as np
+    i = np.arange(n_bp, dtype=np.int64)
+    return i, head_len + i + i // width                         # byte offset of base i: `width` bases and a newline per line
+
+
+def _sampled_bases(head_len: int, n_bp: int, width: int, stretch: int = 2048, chunk: int = 16384, stride: int = 16):
+    """Which bases of a one-record text (a `head_len`-byte header, then lines of `width` bases) the bucket-size sample sees."""
+    import numpy as np
+    i, off = _base_offsets(head_len, n_bp, width)
+    slot = off // chunk
+    first = np.searchsorted(slot, np.arange(slot[-1] + 1))     # index of the first base of every chunk
+    q = slot * (chunk // stretch) + (i - first[slot]) // stretch
+    return q % stride == (q // stride) % stride
+
+
+def _lines(seq, width: int) -> bytes:
+    import numpy as np
+    lines = np.empty((seq.size // width, width + 1), dtype=np.uint8)
+    lines[:, :width] = seq.reshape(-1, width)
+    lines[:, width] = 10
+    return lines.tobytes()
+
+
+def headers_on_lines(text: bytes, head_len: int, width: int, line_idx, tag: bytes = b"r") -> bytes:
+    """`text` (a `head_len`-byte header, then lines of `width` bases) with the given sequence lines replaced by header lines
+    of the same length: every byte offset stays where it was, every replaced line opens a record."""
+    import numpy as np
+    body = np.frombuffer(text, dtype=np.uint8, offset=head_len).reshape(-1, width + 1).copy()
+    line_idx = np.asarray(line_idx, dtype=np.int64)
+    heads = b"".join((b">%s%d_" % (tag, n)).ljust(width, b"x") for n in range(line_idx.size))
+    body[line_idx, :width] = np.frombuffer(heads, dtype=np.uint8).reshape(-1, width)
+    return text[:head_len] + body.tobytes()
+
+
+def record_dense_fasta(n_bytes: int, every: int, seed: int = 5, head_len: int = 27, width: int = 60) -> bytes:
+    """Random sequence of exactly `n_bytes` bytes laid out like skewed_fasta (a `head_len`-byte header line, then lines of
+    `width` bases), every `every`-th line a header of the same length: many short records of ordinary sequence."""
+    import numpy as np
+    n_lines = (n_bytes - head_len) // (width + 1)
+    assert head_len + n_lines * (width + 1) == n_bytes
+    rng = np.random.default_rng(seed)
+    seq = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n_lines * width)]
+    head = b">dense".ljust(head_len - 1, b"_") + b"\n"
+    text = head + _lines(seq, width)
+    return headers_on_lines(text, head_len, width, np.arange(every - 1, n_lines, every), tag=b"d")
+
+
+def skewed_fasta_with_records(n_bp: int, unit_len: int, n_records: int, seed: int = 7, stretch: int = 2048,
+                              chunk: int = 16384, stride: int = 16) -> bytes:
+    """skewed_fasta(n_bp, unit_len, ...) with `n_records` of its lines turned into header lines of the same length, all of
+    them behind the last sampled base of their 16 KiB chunk: what the sample sees -- every sampled base at the same
+    place in its chunk's squeezed bases -- stays as it was, so the text still defeats the sample, and it also brings
+    `n_records` + 1 records."""
+    import numpy as np
+    text = skewed_fasta(n_bp, unit_len, seed=seed, stretch=stretch, chunk=chunk, stride=stride)
+    head_len = len(b">skewed_against_the_sample\n")
+    sampled = _sampled_bases(head_len, n_bp, 60, stretch, chunk, stride)
+    i, off = _base_offsets(head_len, n_bp, 60)
+    n_chunks = int(off[-1] // chunk) + 1
+    last = np.full(n_chunks, -1, dtype=np.int64)                # offset of the last sampled base of every chunk
+    np.maximum.at(last, off[sampled] // chunk, off[sampled])
+    line_start = head_len + np.arange(n_bp // 60, dtype=np.int64) * 61
+    c0, c1 = line_start // chunk, (line_start + 60) // chunk     # chunks of the line's first byte and of its newline
+    ok = np.flatnonzero((c0 == c1) & (line_start > last[c0]))
+    assert ok.size >= n_records, (ok.size, n_records)
+    pick = ok[np.linspace(0, ok.size - 1, n_records).astype(np.int64)]
+    return headers_on_lines(text, head_len, 60, np.unique(pick), tag=b"s")
 
 
 def sha256(data) -> str:

@@ -300,3 +300,56 @@ def test_merger_kwip_over_fastq_tables(gpu, tmp_path):
     from pykmer_amd import merger
     tabs = [merger.Header(x, index_file=x).read_table_slice(0, 4 ** 11) for x in sorted(kins)]
     assert np.allclose(k, direct_kernel(tabs), rtol=1e-12, atol=0)
+
+
+def _padded_reads(n_fasta_bytes: int, n_reads: int, length: int, seed: int):
+    """(fastq, fasta): n_reads random reads of `length` bp whose FASTA text is exactly n_fasta_bytes long (the names are
+    padded to make up the difference)."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    name_bytes = n_fasta_bytes - n_reads * (length + 3)                     # '>' + name + '\n' + sequence + '\n'
+    q, r = divmod(name_bytes, n_reads)
+    assert q >= 12
+    seqs = acgt[rng.integers(0, 4, (n_reads, length))]
+    qual = b"I" * length
+    fq, fa = [], []
+    for i in range(n_reads):
+        name = (b"read%d_" % i).ljust(q + (i < r), b"p")
+        s = seqs[i].tobytes()
+        fq.append(b"@" + name + b"\n" + s + b"\n+\n" + qual + b"\n")
+        fa.append(b">" + name + b"\n" + s + b"\n")
+    fa = b"".join(fa)
+    assert len(fa) == n_fasta_bytes
+    return b"".join(fq), fa
+
+
+def test_record_overflow_after_a_relayout_feed(gpu):
+    """FASTQ form of test_gpu_indexer.py's test of the same name: a long read on one line whose FASTA text defeats the bucket
+    sample, then short reads whose FASTA text has the same length and far more records than the array holds.  FASTQ
+    text is counted one call late: the first text's relayout happens in the second feed call, the second text's record
+    retry inside finish."""
+    import inputs
+    from test_gpu_indexer import _record_starts, record_overflows
+    k = 15
+    fa1 = inputs.skewed_fasta(20_000_000, 61, seed=72, width=None)
+    head, seq = fa1.split(b"\n")[:2]
+    fq1 = b"@" + head[1:] + b"\n" + seq + b"\n+\n" + b"I" * len(seq) + b"\n"
+    assert fastq_to_fasta(fq1) == fa1
+    fq2, fa2 = _padded_reads(len(fa1), 120_000, 100, seed=73)
+    fq, fa = fq1 + fq2, fa1 + fa2
+    with _lib().Indexer(k, fmt="fastq") as ix:
+        ix.feed(fq1)
+        ix.feed(fq2)
+        assert ix.timings()["relayouts"] >= 1, "the long read was meant to overflow the sampled layout"
+        fin = ix.finish()
+        got = dict(fin, records=ix.records(fin["n_records"]), stats=ix.fastq_stats(), table=ix.table_to_host())
+    want = oracle.count_fasta(fa, k)
+    assert record_overflows([len(fa1), len(fa2)], _record_starts(want["records"])) == [False, True]
+    assert got["num_kmers"] == want["num_kmers"] and got["total_bp"] == want["total_bp"]
+    assert got["n_records"] == len(want["records"]) == 120_001
+    for f in ("name_len", "seq_len", "n_valid_kmers"):
+        assert np.array_equal(got["records"][f], want["records"][f]), f
+    assert _names(fq, got["records"]) == _names(fa, want["records"])        # name_off: the same names, sliced from the FASTQ
+    assert np.array_equal(got["hist256"][1:], oracle.table_stats(want["table"])[0])
+    assert np.array_equal(got["table"], want["table"])
+    assert got["stats"] == fastq_ref.stats(fq)

@@ -1,5 +1,6 @@
 """GPU parity tests for the indexer path: HIP kernels (through the C-ABI) vs the oracle and vs the
 golden vectors the reference itself produced (tests/golden/, oracle/gen_golden.py).  Bit-exact."""
+import functools
 import hashlib
 
 import numpy as np
@@ -526,3 +527,171 @@ def test_byte_counters_wrap_and_are_recounted(gpu, k):
         assert np.array_equal(table[u.astype(np.int64)], sat)
         step = 1 << 30
         assert sum(int(np.count_nonzero(table[o:o + step])) for o in range(0, table.size, step)) == u.size
+
+
+# ------------------------------------------------------------------ retried feeds -------------------------------------
+# A feed is retried in place when its records do not fit the record array (the squeeze backs out, flags[0] = 2: grow it,
+# squeeze again) or when a sampled bucket room overflows (flags[0] = 1: lay out again with exact sizes, no new squeeze).
+# The tests below make both happen on neighbouring feeds and in one feed, and check every output against the oracle.
+RECS_INITIAL = 4096                                          # pk_indexer_create_slice: record slots of a fresh indexer
+
+
+def record_overflows(lengths, record_starts):
+    """Which of the feeds (byte lengths, in order; 0 = an empty feed, which never reaches the pipeline) bring more records
+    than the record array holds when they arrive -- the capacity rule of pk_api.hip (ensure_recs, feed_piece: after every
+    feed room for as many records again as it brought, times two, + 1024).  `record_starts`: offset of every record's '>'."""
+    starts = np.sort(np.asarray(record_starts, dtype=np.int64))
+    cap, n, end, out = RECS_INITIAL, 0, 0, []
+
+    def grown(cap, need):
+        return cap if need <= cap else max(need, max(1024, 2 * cap))
+
+    for length in lengths:
+        if length == 0:
+            out.append(False)
+            continue
+        end += length
+        n_after = int(np.searchsorted(starts, end))
+        out.append(n_after > cap)
+        cap = grown(cap, n_after)
+        cap = grown(cap, n_after + 2 * (n_after - n) + 1024)
+        n = n_after
+    return out
+
+
+def _record_starts(records):
+    return records["name_off"].astype(np.int64) - 1
+
+
+_RETRY_BP = 20_000_220                                       # skewed text of 20.3 MB, a multiple of 16 bytes
+
+
+@functools.lru_cache(maxsize=None)
+def _retry_inputs(stretch: int):
+    skewed = inputs.skewed_fasta(_RETRY_BP, 61, seed=68, stretch=stretch)
+    dense = inputs.record_dense_fasta(len(skewed), 3, seed=5)          # same length, 111 112 records of random sequence
+    assert len(skewed) % 16 == 0 and len(dense) == len(skewed)
+    return skewed, dense
+
+
+def _check_retried(ix, data, k, n_slices=1, slice_index=0):
+    """finish() of an indexer that was fed `data` (in any cuts) against the oracle: totals, every record field,
+    histogram and table (k = 17 / 19: the non-zero addresses and their number)."""
+    fin = ix.finish()
+    size = 4 ** k // n_slices
+    if k <= 15:
+        want = oracle.count_fasta(data, k)
+        part = want["table"][slice_index * size:(slice_index + 1) * size]
+        u, sat = np.flatnonzero(part), part[part != 0]
+    else:
+        kmers, want = oracle.kmer_list(data, k, records=True)
+        u, c = np.unique(kmers, return_counts=True)
+        sel = u // np.uint64(size) == np.uint64(slice_index)
+        u, sat = (u[sel] - np.uint64(slice_index * size)).astype(np.int64), np.minimum(c[sel], 255).astype(np.uint8)
+    assert fin["num_kmers"] == want["num_kmers"]
+    assert fin["total_bp"] == want["total_bp"]
+    assert fin["n_records"] == len(want["records"])
+    recs = ix.records(fin["n_records"])
+    for f in ("name_off", "name_len", "seq_len", "n_valid_kmers"):
+        assert np.array_equal(recs[f], want["records"][f]), f
+    h = fin["hist256"]
+    assert int(h.sum()) == size
+    assert np.array_equal(h[1:], np.bincount(sat, minlength=256)[1:].astype(np.uint64))
+    table = ix.table_to_host()
+    if k <= 15:
+        assert np.array_equal(table, part)
+    else:
+        assert np.array_equal(table[u], sat)
+        step = 1 << 30
+        assert sum(int(np.count_nonzero(table[o:o + step])) for o in range(0, table.size, step)) == u.size
+    return want
+
+
+def _busiest_slice(data, k, n_slices):
+    """The address slice that holds most of the text's k-mers (there the repeated unit of skewed_fasta overflows the sample)."""
+    kmers = oracle.kmer_list(data, k)
+    return int(np.bincount((kmers // np.uint64(4 ** k // n_slices)).astype(np.int64), minlength=n_slices).argmax())
+
+
+@pytest.mark.parametrize("k,n_slices", [(11, 1), (13, 1), (15, 1), (17, 1), (15, 4), (19, 16)])
+def test_record_overflow_after_a_relayout_feed(gpu, k, n_slices):
+    """Feed 1 defeats the bucket sample (relayout); feed 2 has the same byte length -- the same workspace layout -- and far
+    more records than the array holds, so its squeeze backs out.  Nothing of feed 2 may then be counted from what the
+    workspace still holds of feed 1 (its squeezed text overflows the same sampled rooms again): feed 2's records must be
+    squeezed and counted, feed 1's k-mers only once.  (k = 19: the deep windows of k_walk_sort, one slice of sixteen.)"""
+    skewed, dense = _retry_inputs(1024 if k >= 17 else 2048)
+    data = skewed + dense
+    slice_index = _busiest_slice(skewed, k, n_slices) if n_slices > 1 else 0
+    with gpu.Indexer(k, slice_index=slice_index, n_slices=n_slices) as ix:
+        ix.feed(skewed)
+        assert ix.timings()["relayouts"] >= 1, "feed 1 was meant to overflow the sampled layout"
+        ix.feed(dense)
+        want = _check_retried(ix, data, k, n_slices, slice_index)
+    assert len(want["records"]) >= 100_000
+    assert record_overflows([len(skewed), len(dense)], _record_starts(want["records"])) == [False, True]
+
+
+def test_record_overflow_after_a_relayout_piece_of_one_host_feed(gpu, monkeypatch):
+    """The same two texts as one host feed, cut into pieces by the library itself (PK_FEED_PIECE), as a large assembly is."""
+    k = 15
+    skewed, dense = _retry_inputs(2048)
+    monkeypatch.setenv("PK_FEED_PIECE", str(len(skewed)))
+    with gpu.Indexer(k) as ix:
+        ix.feed(skewed + dense)
+        t = ix.timings()
+        assert t["feeds"] == 2 and t["relayouts"] >= 1
+        want = _check_retried(ix, skewed + dense, k)
+    assert record_overflows([len(skewed), len(dense)], _record_starts(want["records"])) == [False, True]
+
+
+@functools.lru_cache(maxsize=None)
+def _both_retries_feed():
+    return inputs.skewed_fasta_with_records(_RETRY_BP, 61, 90_000, seed=69)
+
+
+def test_both_retries_in_one_feed(gpu):
+    """One feed that overflows the record array of a fresh indexer (attempt 0: flag 2) and then the sampled layout
+    (attempt 1: flag 1) before its exact layout holds (attempt 2)."""
+    k = 15
+    data = _both_retries_feed()
+    with gpu.Indexer(k) as ix:
+        ix.feed(data)
+        assert ix.timings()["relayouts"] == 1, "the feed was meant to overflow the sampled layout"
+        want = _check_retried(ix, data, k)
+    assert len(want["records"]) >= 10_000
+    assert record_overflows([len(data)], _record_starts(want["records"])) == [True]
+
+
+def test_retry_schedule_on_one_indexer(gpu):
+    """A fixed schedule of feeds on one k = 15 indexer: the skewed text (relayout); a same-size record-dense feed (record
+    retry); one byte that opens a header; a feed that ends inside the next record's sequence; the rest of that record
+    with enough records behind it to grow the array again; an empty feed; the feed that takes both retries.  Then a
+    reset and an ordinary stream on the same indexer."""
+    import synth
+    k = 15
+    skewed, _ = _retry_inputs(2048)
+    dense = inputs.record_dense_fasta(len(skewed), 40, seed=6)          # 8 334 records: outgrows the initial 4096
+    rng = np.random.default_rng(70)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    straddle = b">straddling record\n" + b"\n".join(acgt[rng.integers(0, 4, 60)].tobytes() for _ in range(50)) + b"\n"
+    short = b"".join(b">t%d\n%s\n" % (i, acgt[rng.integers(0, 4, 40)].tobytes()) for i in range(20_000))
+    cut = len(b">straddling record\n") + 1500
+    tail = straddle + short
+    both = _both_retries_feed()
+    feeds = [skewed, dense, tail[:1], tail[1:cut], tail[cut:], b"", both]
+    data = b"".join(feeds)
+    with gpu.Indexer(k) as ix:
+        relayouts = []
+        for f in feeds:
+            ix.feed(f)
+            relayouts.append(ix.timings()["relayouts"])
+        assert relayouts[0] >= 1 and relayouts[-1] > relayouts[-2], relayouts
+        want = _check_retried(ix, data, k)
+        assert record_overflows([len(f) for f in feeds], _record_starts(want["records"])) == \
+            [False, True, False, False, True, False, True]
+        ix.reset()
+        plain, _ = synth.c2(3_000_000, seed=71)
+        plain = plain.tobytes()
+        ix.feed(plain[:1_000_003])
+        ix.feed(plain[1_000_003:])
+        _check_retried(ix, plain, k)
