@@ -165,6 +165,7 @@ def pair_matrix(headers: List[Header], windows, threads: int = DEFAULT_THREADS, 
     on devices[0] and the partials of all windows are summed by ONE all-reduce -- over RCCL on the
     accumulator where the kernel left it in HBM.  `partial_fn` computes one slice's tallies (default: gpu_partial,
     looked up when called; the CPU-only tests substitute the oracle)."""
+    assert 1 <= len(headers) <= 128, "a pair tally takes 1 to 128 tables"
     partial_fn = partial_fn or gpu_partial
     n, N, W = headers[0].data_size, len(headers), len(windows)
     if group is None:
@@ -313,7 +314,7 @@ def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices
                   stats: dict = None) -> np.ndarray:
     """The spectrum accumulator of all tables over the whole address range (flat u64, spectrum_partial's layout), split
     as _pair_flat does; `partial_fn` defaults to spectrum_partial."""
-    assert len(headers) >= 2, "a spectrum needs at least two tables"
+    assert 2 <= len(headers) <= 128, "a spectrum takes 2 to 128 tables"
     return _pair_flat(headers, _lib.spectrum_words(len(headers)), spectrum_partial, threads, devices, group, partial_fn, stats)
 
 

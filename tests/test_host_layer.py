@@ -302,6 +302,26 @@ def test_merge_validation(tmp_path, manifest):
     assert args.min_count == 3 and args.max_count == 255 and args.block_size == 100_000_000 and args.threads == 2
 
 
+def test_merge_refuses_129_tables_before_reading_any(tmp_path, monkeypatch):
+    """The kernels take at most 128 tables: the pair, spectrum and kWIP paths of merge() refuse 129 before a table byte is
+    read or a device buffer allocated, with the default (GPU) partials; the tally entry points refuse 0 and 129 tables."""
+    paths = [_write_index(tmp_path, f"t{i:03d}.fa", b">s\nACGTTGCAAC\n", 3)[0].index_file_root for i in range(129)]
+    touched = []
+    monkeypatch.setattr(Header, "read_table_slice", lambda self, *a, **kw: touched.append("read"))
+    monkeypatch.setattr(merger._lib, "DeviceBuffer", lambda *a, **kw: touched.append("alloc"))
+    for kw, msg in (({}, "a pair tally takes 1 to 128 tables"), ({"spectrum": True}, "a spectrum takes 2 to 128 tables"),
+                    ({"kwip": True}, "kWIP takes 2 to 128 tables")):
+        with pytest.raises(AssertionError, match=msg):
+            merger.merge(str(tmp_path / "p"), paths, **kw)
+    assert touched == [] and not list(tmp_path.glob("p.*"))
+    tabs = [merger.ResidentTable(4096, 64, 64)] * 129
+    for fn, args in ((merger.pair_matrix, ([(1, 255)],)), (merger.pair_spectrum, ()), (merger.pair_occgram, ())):
+        for n_tabs in (0, 129):
+            with pytest.raises(AssertionError, match="128 tables"):
+                fn(tabs[:n_tabs], *args, partial_fn=lambda *a, **kw: touched.append("partial"))
+    assert touched == []
+
+
 def _cli_rank(rank, world, port, workdir, argv):
     """One rank of `merger.py` under a launcher's environment, scans stood in for by the oracle (no GPU in this suite)."""
     import sys
