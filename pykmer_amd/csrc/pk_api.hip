@@ -7,7 +7,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/pykmer_hip.h"
@@ -74,9 +77,8 @@ static int check_k(int k, int slice_bits = 0, int slice_index = 0) {
 // The C-ABI takes plain (pageable) host buffers.  One hipMemcpy from pageable memory is a single thread bouncing
 // the bytes through a small pinned buffer; here several host threads each own a pinned bounce buffer (two halves)
 // and a stream, so page-touching memcpy and PCIe DMA of different pieces overlap and the link is what limits.
-#include <mutex>
-#include <thread>
 namespace {
+constexpr int MAX_DEVICES = 64;
 constexpr size_t BOUNCE_HALF = 8u << 20;
 constexpr int MAX_COPY_THREADS = 16;
 struct Bouncer {
@@ -86,10 +88,10 @@ struct Bouncer {
     hipStream_t stream[MAX_COPY_THREADS] = {};
     hipEvent_t ev[MAX_COPY_THREADS][2] = {};
 };
-Bouncer g_bounce[64];
+Bouncer g_bounce[MAX_DEVICES];
 
 int bouncer_for(int device, Bouncer **out) {
-    if (device < 0 || device >= 64) return fail(PK_ERR_ARG, "device ordinal %d out of range", device);
+    if (device < 0 || device >= MAX_DEVICES) return fail(PK_ERR_ARG, "device ordinal %d out of range", device);
     Bouncer &b = g_bounce[device];
     static std::mutex init_mu;                             // several host threads may make their first copy at once
     std::lock_guard<std::mutex> init_lock(init_mu);
@@ -842,15 +844,13 @@ extern "C" int pk_count_fasta(const uint8_t *fasta, uint64_t n_bytes, int k, uin
     } else if ((rc = pk_indexer_reset(ix))) {
         return rc;
     }
-    auto done = [&](int r) { return r; };
-    if ((rc = pk_indexer_feed(ix, fasta, n_bytes))) return done(rc);
+    if ((rc = pk_indexer_feed(ix, fasta, n_bytes))) return rc;
     uint64_t n_recs = 0;
-    if ((rc = pk_indexer_finish(ix, num_kmers_out, total_bp_out, hist256_out, &n_recs))) return done(rc);
+    if ((rc = pk_indexer_finish(ix, num_kmers_out, total_bp_out, hist256_out, &n_recs))) return rc;
     if (n_recs_out) *n_recs_out = n_recs;
-    if ((rc = pk_indexer_table_to_host(ix, table_out))) return done(rc);
-    if (n_recs > recs_cap) return done(fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)n_recs, (unsigned long long)recs_cap));
-    if ((rc = pk_indexer_records(ix, recs_out, recs_cap))) return done(rc);
-    return done(PK_OK);
+    if ((rc = pk_indexer_table_to_host(ix, table_out))) return rc;
+    if (n_recs > recs_cap) return fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)n_recs, (unsigned long long)recs_cap);
+    return pk_indexer_records(ix, recs_out, recs_cap);
 }
 
 // ================================================================== stats ======================
@@ -902,8 +902,6 @@ extern "C" int pk_gram_expand(const uint64_t *pair, int N, uint64_t *matrix_out)
 
 // Per-device scan context: the table-pointer array in HBM, a stream and two events, created once and reused by
 // every scan on that device (a 2 ms kernel should not pay for hipMalloc / hipEventCreate each call).
-#include <mutex>
-#include <thread>
 namespace {
 struct GramCtx {
     std::mutex mu;
@@ -916,7 +914,6 @@ struct GramCtx {
     uint8_t *d_occ = nullptr;                  // occupancy bytes of an occgram pass over more than 16 tables (grown on demand)
     uint64_t occ_cap = 0;
 };
-constexpr int MAX_DEVICES = 64;
 GramCtx g_gram[MAX_DEVICES];
 
 int gram_ctx(int device, GramCtx **out) {
@@ -937,41 +934,60 @@ int gram_ctx(int device, GramCtx **out) {
     return PK_OK;
 }
 
-// one scan of N device-resident slices; `accumulate` adds into dev_pair instead of overwriting it
-int gram_scan_device(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count, uint64_t *pair_out,
-                     void *dev_pair, bool accumulate, int device, double *kernel_seconds_out) {
-    int rc = check_counts(N, min_count, max_count);
-    if (rc) return rc;
+// The frame every merge pass over device-resident slices runs in.  The table pointers are checked and the device's
+// context is locked; then, on its stream: `before` (what the pass needs in place but does not time: the pointer array,
+// scratch), e0, `launch`, e1, `after` (a copy queued behind the pass) and one synchronise.  e0 .. e1 is the pass's kernel
+// time.  `before` and `after` return a PK_* code and may be empty; `launch` returns non-zero when a launch failed.
+using PassStep = std::function<int(GramCtx &)>;
+
+int timed_pass(const char *what, const void *const *dev_tables, int N, int device, double *kernel_seconds_out,
+               const PassStep &before, const PassStep &launch, const PassStep &after = nullptr) {
     if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
     for (int i = 0; i < N; i++)
         if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
     HIPCHK(hipSetDevice(device));
     GramCtx *c = nullptr;
-    if ((rc = gram_ctx(device, &c))) return rc;
+    int rc = gram_ctx(device, &c);
+    if (rc) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
-    unsigned long long *d_pair = dev_pair ? (unsigned long long *)dev_pair : c->d_pair;
-    if (!dev_pair) accumulate = false;
-    HIPCHK(hipMemcpyAsync(c->d_ptrs, dev_tables, N * sizeof(void *), hipMemcpyHostToDevice, c->stream));
+    if (before && (rc = before(*c))) return rc;
     HIPCHK(hipEventRecord(c->e0, c->stream));
-    if (launch_gram(c->d_ptrs, N, n_slice, min_count, max_count, d_pair, !accumulate, c->stream))
-        return fail(PK_ERR_HIP, "gram kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (launch(*c)) return fail(PK_ERR_HIP, "%s kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     HIPCHK(hipEventRecord(c->e1, c->stream));
-    if (pair_out) HIPCHK(hipMemcpyAsync(pair_out, d_pair, (size_t)N * N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (after && (rc = after(*c))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
     return PK_OK;
 }
+
+// the pair scans read their table pointers from HBM: uploaded ahead of e0
+PassStep upload_pointers(const void *const *dev_tables, int N) {
+    return [=](GramCtx &c) -> int {
+        HIPCHK(hipMemcpyAsync(c.d_ptrs, dev_tables, N * sizeof(void *), hipMemcpyHostToDevice, c.stream));
+        return PK_OK;
+    };
+}
 }  // namespace
 
+// One scan of N device-resident slices.  The tallies overwrite dev_pair_out, or the context's scratch for callers that
+// only want the host copy.
 extern "C" int pk_gram_device_partial(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count,
                                       uint64_t *pair_out, void *dev_pair_out, int device, double *kernel_seconds_out) {
-    return gram_scan_device(dev_tables, N, n_slice, min_count, max_count, pair_out, dev_pair_out, false, device, kernel_seconds_out);
+    int rc = check_counts(N, min_count, max_count);
+    if (rc) return rc;
+    auto d_pair = [=](GramCtx &c) { return dev_pair_out ? (unsigned long long *)dev_pair_out : c.d_pair; };
+    return timed_pass(
+        "gram", dev_tables, N, device, kernel_seconds_out, upload_pointers(dev_tables, N),
+        [&](GramCtx &c) { return launch_gram(c.d_ptrs, N, n_slice, min_count, max_count, d_pair(c), true, c.stream); },
+        [&](GramCtx &c) -> int {
+            if (pair_out) HIPCHK(hipMemcpyAsync(pair_out, d_pair(c), (size_t)N * N * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+            return PK_OK;
+        });
 }
 
 extern "C" int pk_gram_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count,
                                          void *dev_pair_accum, int device, double *kernel_seconds_out) {
-    if (!dev_pair_accum) return fail(PK_ERR_ARG, "null accumulator");
-    return gram_scan_device(dev_tables, N, n_slice, min_count, max_count, nullptr, dev_pair_accum, true, device, kernel_seconds_out);
+    return pk_gram_device_accumulate_windows(dev_tables, N, n_slice, &min_count, &max_count, 1, dev_pair_accum, device, kernel_seconds_out);
 }
 
 // Several windows over the same staged slices: one pass per group of windows (k_gram_mw) where the kernel has room for
@@ -984,38 +1000,28 @@ extern "C" int pk_gram_device_accumulate_windows(const void *const *dev_tables, 
     int rc = PK_OK;
     for (int w = 0; w < n_windows; w++)
         if ((rc = check_counts(N, min_counts[w], max_counts[w]))) return rc;
-    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
-    for (int i = 0; i < N; i++)
-        if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
     const int per_pass = gram_windows_per_pass(N);
-    HIPCHK(hipSetDevice(device));
-    GramCtx *c = nullptr;
-    if ((rc = gram_ctx(device, &c))) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
     unsigned long long *acc = (unsigned long long *)dev_pair_accum;
-    HIPCHK(hipMemcpyAsync(c->d_ptrs, dev_tables, N * sizeof(void *), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->e0, c->stream));
-    std::vector<int> order(n_windows);
-    for (int w = 0; w < n_windows; w++) order[w] = w;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return min_counts[a] < min_counts[b]; });
-    for (int at = 0; at < n_windows;) {
-        const int take = (per_pass >= 2 && n_windows - at >= 2) ? std::min(per_pass, n_windows - at) : 1;
-        int lrc;
-        if (take == 1) {
-            const int w = order[at];
-            lrc = launch_gram(c->d_ptrs, N, n_slice, min_counts[w], max_counts[w], acc + (size_t)w * N * N, false, c->stream);
-        } else {
-            int mn[8], mx[8], out[8];
-            for (int i = 0; i < take; i++) { mn[i] = min_counts[order[at + i]]; mx[i] = max_counts[order[at + i]]; out[i] = order[at + i]; }
-            lrc = launch_gram_windows(c->d_ptrs, N, n_slice, mn, mx, out, take, acc, c->stream);
+    return timed_pass("gram", dev_tables, N, device, kernel_seconds_out, upload_pointers(dev_tables, N), [&](GramCtx &c) {
+        std::vector<int> order(n_windows);
+        for (int w = 0; w < n_windows; w++) order[w] = w;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return min_counts[a] < min_counts[b]; });
+        for (int at = 0; at < n_windows;) {
+            const int take = (per_pass >= 2 && n_windows - at >= 2) ? std::min(per_pass, n_windows - at) : 1;
+            int lrc;
+            if (take == 1) {
+                const int w = order[at];
+                lrc = launch_gram(c.d_ptrs, N, n_slice, min_counts[w], max_counts[w], acc + (size_t)w * N * N, false, c.stream);
+            } else {
+                int mn[8], mx[8], out[8];
+                for (int i = 0; i < take; i++) { mn[i] = min_counts[order[at + i]]; mx[i] = max_counts[order[at + i]]; out[i] = order[at + i]; }
+                lrc = launch_gram_windows(c.d_ptrs, N, n_slice, mn, mx, out, take, acc, c.stream);
+            }
+            if (lrc) return lrc;
+            at += take;
         }
-        if (lrc) return fail(PK_ERR_HIP, "gram kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-        at += take;
-    }
-    HIPCHK(hipEventRecord(c->e1, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
-    return PK_OK;
+        return 0;
+    });
 }
 
 // Joint count spectra (gram_spectrum.hip): one pass per pair group over the staged slices, every tally ADDED to the caller's
@@ -1024,21 +1030,9 @@ extern "C" int pk_spectrum_device_accumulate(const void *const *dev_tables, int 
                                              double *kernel_seconds_out) {
     if (N < 2 || N > 128) return fail(PK_ERR_ARG, "a spectrum pass takes 2 to 128 tables (got %d)", N);
     if (!dev_spec_accum) return fail(PK_ERR_ARG, "null accumulator");
-    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
-    for (int i = 0; i < N; i++)
-        if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
-    HIPCHK(hipSetDevice(device));
-    GramCtx *c = nullptr;
-    int rc = gram_ctx(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    HIPCHK(hipEventRecord(c->e0, c->stream));
-    if (launch_spectrum(dev_tables, N, n_slice, (unsigned long long *)dev_spec_accum, c->h_gtab.data(), c->d_gtab, c->stream))
-        return fail(PK_ERR_HIP, "spectrum kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipEventRecord(c->e1, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
-    return PK_OK;
+    return timed_pass("spectrum", dev_tables, N, device, kernel_seconds_out, nullptr, [&](GramCtx &c) {
+        return launch_spectrum(dev_tables, N, n_slice, (unsigned long long *)dev_spec_accum, c.h_gtab.data(), c.d_gtab, c.stream);
+    });
 }
 
 // Occupancy-stratified Gram products (gram_occ.hip): every tally ADDED to the caller's accumulator, so slices and ranks sum
@@ -1047,30 +1041,21 @@ extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N
                                             double *kernel_seconds_out) {
     if (N < 2 || N > 128) return fail(PK_ERR_ARG, "an occgram pass takes 2 to 128 tables (got %d)", N);
     if (!dev_accum) return fail(PK_ERR_ARG, "null accumulator");
-    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
-    for (int i = 0; i < N; i++)
-        if (!dev_tables[i] || ((uintptr_t)dev_tables[i] & 15u)) return fail(PK_ERR_ARG, "table %d: device pointer must be 16-byte aligned", i);
-    HIPCHK(hipSetDevice(device));
-    GramCtx *c = nullptr;
-    int rc = gram_ctx(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(c->mu);
-    const uint64_t need = occgram_scratch_bytes(N, n_slice);
-    if (need > c->occ_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_occ) HIPCHK(hipFree(c->d_occ));
-        c->d_occ = nullptr;
-        c->occ_cap = 0;
-        HIPCHK(hipMalloc(&c->d_occ, need));
-        c->occ_cap = need;
-    }
-    HIPCHK(hipEventRecord(c->e0, c->stream));
-    if (launch_occgram(dev_tables, N, n_slice, (unsigned long long *)dev_accum, c->d_ptrs, c->d_occ, c->stream))
-        return fail(PK_ERR_HIP, "occgram kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipEventRecord(c->e1, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (kernel_seconds_out) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1)); *kernel_seconds_out = ms * 1e-3; }
-    return PK_OK;
+    auto grow_scratch = [&](GramCtx &c) -> int {
+        const uint64_t need = occgram_scratch_bytes(N, n_slice);
+        if (need > c.occ_cap) {
+            HIPCHK(hipStreamSynchronize(c.stream));
+            if (c.d_occ) HIPCHK(hipFree(c.d_occ));
+            c.d_occ = nullptr;
+            c.occ_cap = 0;
+            HIPCHK(hipMalloc(&c.d_occ, need));
+            c.occ_cap = need;
+        }
+        return PK_OK;
+    };
+    return timed_pass("occgram", dev_tables, N, device, kernel_seconds_out, grow_scratch, [&](GramCtx &c) {
+        return launch_occgram(dev_tables, N, n_slice, (unsigned long long *)dev_accum, c.d_ptrs, c.d_occ, c.stream);
+    });
 }
 
 extern "C" int pk_gram(const uint8_t *const *tables, int N, uint64_t n, int min_count, int max_count, uint64_t *matrix_out,

@@ -21,7 +21,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bgzf
 from .header import Header
 
 EXTS = ("." + Header.IND_EXT, "." + Header.IND_EXT + "." + Header.COMP_EXT, ".kma", ".kma." + Header.COMP_EXT)
@@ -110,24 +110,30 @@ class ResidentTable:
         return self.ptr + (lo - self.first)
 
 
-def gpu_partial(headers: List[Header], lo: int, hi: int, windows, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
-    """Stage addresses [lo, hi) of every table in HBM on `device` (sub-slice by sub-slice if they do not all
-    fit) and tally each staged piece for every (min_count, max_count) window in one kernel pass per group of windows
-    (pk_gram_device_accumulate_windows).  Only bytes [lo, hi) of each file are read / inflated; ResidentTable entries are
-    scanned where they lie.  The tallies are accumulated in HBM: at `acc_ptr` (W x N x N u64,
-    zeroed by the caller -- the buffer an RCCL all-reduce then sums) or in a buffer of this call, which is
-    then returned as W host arrays.  `stats["kernel_seconds"]` accumulates the scans' kernel time."""
-    N, W = len(headers), len(windows)
-    own = None
-    if acc_ptr is None:
-        own = _lib.DeviceBuffer(W * N * N * 8, device)
-        own.zero()
-        acc_ptr = own.ptr
+def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, words: int, accumulate, staged_tables: int,
+                  reserve: bool, acc_ptr: int = None, stats: dict = None):
+    """The one staging loop of every merge pass.  Addresses [lo, hi) of every table are staged in HBM on `device`
+    (sub-slice by sub-slice if they do not all fit; only bytes [lo, hi) of each file are read / inflated; ResidentTable
+    entries are scanned where they lie) and `accumulate(ptrs, n, acc_ptr, device=)` runs once per staged piece, adding to a
+    flat u64 accumulator of `words` words: at `acc_ptr` (zeroed by the caller -- the buffer an RCCL all-reduce then sums) or
+    in a buffer of this call, which is then returned as one flat u64 host array.  `accumulate` returns its kernel seconds,
+    which `stats["kernel_seconds"]` accumulates.
+
+    `staged_tables` is how many table slices _sub_slices fits into the HBM budget beside each other: N, or more when the
+    pass keeps scratch per address of its own.  `reserve` keeps room in that budget for the accumulator this call allocates
+    (41 MB of spectrum at N = 13, 4.2 GB at N = 128).  The pair tally passes False: its accumulator is a few KB and its cuts
+    have never counted it; budgeting it would move the cuts, which is a change of behaviour of its own."""
+    N = len(headers)
     resident = [hasattr(h, "device_slice") for h in headers]
     assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one merge"
-    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, N, device)
+    own_bytes = words * 8 if acc_ptr is None else 0
+    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, staged_tables, device, reserve=own_bytes if reserve else 0)
+    own = None
+    if acc_ptr is None:
+        own = _lib.DeviceBuffer(own_bytes, device)
+        own.zero()
+        acc_ptr = own.ptr
     bufs = [] if all(resident) else [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
-    from . import bgzf
     io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
     try:
         pool = ThreadPoolExecutor(max_workers=max(1, threads)) if bufs else None
@@ -140,101 +146,6 @@ def gpu_partial(headers: List[Header], lo: int, hi: int, windows, device: int, t
                     ptrs = [buf.ptr for buf in bufs]
                 else:
                     ptrs = [h.device_slice(a, b) for h in headers]
-                secs = _lib.gram_device_accumulate_windows(ptrs, b - a, acc_ptr, windows, device=device)
-                if stats is not None:
-                    stats["kernel_seconds"] = stats.get("kernel_seconds", 0.0) + secs
-        finally:
-            if pool is not None:
-                pool.shutdown()
-        if own is None:
-            return None
-        return list(own.download().view(np.uint64).reshape(W, N, N))
-    finally:
-        for buf in bufs:
-            buf.free()
-        if own is not None:
-            own.free()
-
-
-def pair_matrix(headers: List[Header], windows, threads: int = DEFAULT_THREADS, devices=(0,), group=None,
-                partial_fn=None, stats: dict = None) -> List[np.ndarray]:
-    """One N x N u64 per (min, max) window: [i][i] = valid addresses of table i, [i][j] (i<j) = addresses valid in both.
-
-    Single process: the address range is split over `devices`, one host thread per device.  With `group`
-    (a torch.distributed process group, or True for the default group) this rank scans only its own slice
-    on devices[0] and the partials of all windows are summed by ONE all-reduce -- over RCCL on the
-    accumulator where the kernel left it in HBM.  `partial_fn` computes one slice's tallies (default: gpu_partial,
-    looked up when called; the CPU-only tests substitute the oracle)."""
-    assert 1 <= len(headers) <= 128, "a pair tally takes 1 to 128 tables"
-    partial_fn = partial_fn or gpu_partial
-    n, N, W = headers[0].data_size, len(headers), len(windows)
-    if group is None:
-        plan = [(d,) + address_slice(n, i, len(devices)) for i, d in enumerate(devices)]
-        plan = [p for p in plan if p[2] > p[1]]
-        kw = {"stats": stats} if (stats is not None and partial_fn is gpu_partial) else {}
-        with ThreadPoolExecutor(max_workers=max(1, len(plan))) as pool:
-            parts = list(pool.map(lambda p: partial_fn(headers, p[1], p[2], windows, p[0], max(1, threads // len(plan)), **kw), plan))
-        total = np.zeros((W, N, N), dtype=np.uint64)
-        for part in parts:
-            for w in range(W):
-                total[w] += part[w]
-        return [total[w] for w in range(W)]
-
-    import torch
-    import torch.distributed as dist
-    pg = None if group is True else group
-    dev = devices[0]
-    lo, hi = address_slice(n, dist.get_rank(pg), dist.get_world_size(pg))
-    on_gpu = dist.get_backend(pg) == "nccl"                    # "nccl" is RCCL on ROCm; gloo only for rehearsals and CPU tests
-    if partial_fn is gpu_partial and on_gpu:
-        acc = torch.zeros((W, N, N), dtype=torch.int64, device=torch.device("cuda", dev))
-        torch.cuda.synchronize(dev)                             # zeroed before the scan (its own stream) adds to it
-        if hi > lo:
-            gpu_partial(headers, lo, hi, windows, dev, threads, acc_ptr=acc.data_ptr(), stats=stats)
-        dist.all_reduce(acc, group=pg)                         # RCCL over xGMI: W x N x N u64, a few KB
-        total = acc.cpu().numpy().view(np.uint64)
-    else:
-        total = np.zeros((W, N, N), dtype=np.uint64)
-        if hi > lo:
-            kw = {"stats": stats} if (stats is not None and partial_fn is gpu_partial) else {}
-            for w, part in enumerate(partial_fn(headers, lo, hi, windows, dev, threads, **kw)):
-                total[w] += part
-        t = torch.from_numpy(total.view(np.int64).copy())
-        if on_gpu:                                             # an RCCL group reduces device tensors only
-            t = t.to(torch.device("cuda", dev))
-        dist.all_reduce(t, group=pg)
-        total = t.cpu().numpy().view(np.uint64)
-    return [total[w] for w in range(W)]
-
-
-def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, words: int, accumulate, staged_tables: int,
-                  acc_ptr: int = None, stats: dict = None):
-    """gpu_partial's staging (sub-slices that fit HBM beside the accumulator, only bytes [lo, hi) of each file read or
-    inflated, ResidentTable entries used where they lie) with one `accumulate(ptrs, n, acc_ptr, device=)` pass per staged
-    piece, adding to a flat u64 accumulator of `words` words: at `acc_ptr` (zeroed by the caller) or in a buffer of this
-    call, which is then returned as one flat u64 host array.  `staged_tables` is what _sub_slices budgets per table byte
-    (more than N when the pass keeps scratch of its own).  `stats["kernel_seconds"]` accumulates the kernel time."""
-    N = len(headers)
-    resident = [hasattr(h, "device_slice") for h in headers]
-    assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one merge"
-    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, staged_tables, device, reserve=0 if acc_ptr else words * 8)
-    own = None
-    if acc_ptr is None:
-        own = _lib.DeviceBuffer(words * 8, device)
-        own.zero()
-        acc_ptr = own.ptr
-    bufs = [] if all(resident) else [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
-    from . import bgzf
-    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
-    try:
-        pool = ThreadPoolExecutor(max_workers=max(1, threads)) if bufs else None
-        try:
-            for a, b in cuts:
-                if bufs:
-                    list(pool.map(lambda i: bufs[i].upload(headers[i].read_table_slice(a, b, threads=io_threads)), range(N)))
-                    ptrs = [buf.ptr for buf in bufs]
-                else:
-                    ptrs = [h.device_slice(a, b) for h in headers]
                 secs = accumulate(ptrs, b - a, acc_ptr, device=device)
                 if stats is not None:
                     stats["kernel_seconds"] = stats.get("kernel_seconds", 0.0) + secs
@@ -243,7 +154,7 @@ def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads:
                 pool.shutdown()
         if own is None:
             return None
-        return own.download().view(np.uint64).copy()
+        return own.download().view(np.uint64)
     finally:
         for buf in bufs:
             buf.free()
@@ -251,12 +162,25 @@ def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads:
             own.free()
 
 
+def gpu_partial(headers: List[Header], lo: int, hi: int, windows, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+    """The pair tally of addresses [lo, hi) for every (min_count, max_count) window: one kernel pass per group of windows
+    over each staged piece (pk_gram_device_accumulate_windows; staging as _flat_partial).  W windows over N tables are a
+    flat accumulator of W x N x N u64: at `acc_ptr` (zeroed by the caller) or in a buffer of this call, which is then
+    returned as W host arrays of N x N."""
+    N, W = len(headers), len(windows)
+
+    def accumulate(ptrs, n, acc, device):
+        return _lib.gram_device_accumulate_windows(ptrs, n, acc, windows, device=device)
+    flat = _flat_partial(headers, lo, hi, device, threads, W * N * N, accumulate, N, False, acc_ptr=acc_ptr, stats=stats)
+    return None if flat is None else list(flat.reshape(W, N, N))
+
+
 def spectrum_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
     """One spectrum pass per staged piece of addresses [lo, hi) (pk_spectrum_device_accumulate; staging as _flat_partial).
     The tallies are accumulated in HBM: at `acc_ptr` (spectrum_words(N) u64, zeroed by the caller) or in a buffer of this
     call, which is then returned as one flat u64 host array: N x 256 histograms, then N(N-1)/2 x 255 x 255 joint bins."""
     return _flat_partial(headers, lo, hi, device, threads, _lib.spectrum_words(len(headers)), _lib.spectrum_device_accumulate,
-                         len(headers), acc_ptr=acc_ptr, stats=stats)
+                         len(headers), True, acc_ptr=acc_ptr, stats=stats)
 
 
 def occgram_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
@@ -266,14 +190,17 @@ def occgram_partial(headers: List[Header], lo: int, hi: int, device: int, thread
     tables the pass keeps one occupancy byte per address in HBM: the sub-slices budget N + 1 tables."""
     N = len(headers)
     return _flat_partial(headers, lo, hi, device, threads, _lib.occgram_words(N), _lib.occgram_device_accumulate,
-                         N + 1 if N > 16 else N, acc_ptr=acc_ptr, stats=stats)
+                         N + 1 if N > 16 else N, True, acc_ptr=acc_ptr, stats=stats)
 
 
 def _pair_flat(headers: List[Header], words: int, own_partial, threads: int, devices, group, partial_fn, stats) -> np.ndarray:
-    """A flat accumulator of all tables over the whole address range, split like pair_matrix: over `devices` in one process
-    (partials summed on the host), or with `group` one slice per rank and ONE all-reduce of the accumulator -- on the device
-    over RCCL, through the host over gloo.  `partial_fn(headers, lo, hi, device, threads)` returns one slice's flat
-    accumulator (default: `own_partial`; the CPU-only tests substitute numpy)."""
+    """The one split-and-reduce of every merge pass: a flat accumulator of `words` u64 of all tables over the whole address
+    range.  Single process: the range is split over `devices`, one host thread per device, and the partials are summed on
+    the host.  With `group` (a torch.distributed process group, or True for the default group) this rank scans only its own
+    slice on devices[0] and ONE all-reduce sums the ranks -- over RCCL ("nccl" on ROCm) on the accumulator where the kernel
+    left it in HBM, through the host over gloo (rehearsals and CPU tests).  `partial_fn(headers, lo, hi, device, threads)`
+    returns one slice's flat accumulator (default: `own_partial`, the only one that is handed `acc_ptr=` and `stats=`;
+    the CPU-only tests substitute numpy)."""
     partial_fn = partial_fn or own_partial
     n = headers[0].data_size
     kw = {"stats": stats} if (stats is not None and partial_fn is own_partial) else {}
@@ -294,20 +221,39 @@ def _pair_flat(headers: List[Header], words: int, own_partial, threads: int, dev
     lo, hi = address_slice(n, dist.get_rank(pg), dist.get_world_size(pg))
     on_gpu = dist.get_backend(pg) == "nccl"
     if partial_fn is own_partial and on_gpu:
-        acc = torch.zeros(words, dtype=torch.int64, device=torch.device("cuda", dev))
+        t = torch.zeros(words, dtype=torch.int64, device=torch.device("cuda", dev))
         torch.cuda.synchronize(dev)                             # zeroed before the passes (their own stream) add to it
         if hi > lo:
-            own_partial(headers, lo, hi, dev, threads, acc_ptr=acc.data_ptr(), stats=stats)
-        dist.all_reduce(acc, group=pg)                         # RCCL: the accumulator never leaves the device before the sum
-        return acc.cpu().numpy().view(np.uint64)
-    total = np.zeros(words, dtype=np.uint64)
-    if hi > lo:
-        total += partial_fn(headers, lo, hi, dev, threads, **kw)
-    t = torch.from_numpy(total.view(np.int64).copy())
-    if on_gpu:
-        t = t.to(torch.device("cuda", dev))
-    dist.all_reduce(t, group=pg)
+            own_partial(headers, lo, hi, dev, threads, acc_ptr=t.data_ptr(), stats=stats)
+    else:
+        total = np.zeros(words, dtype=np.uint64)
+        if hi > lo:
+            total += partial_fn(headers, lo, hi, dev, threads, **kw)
+        t = torch.from_numpy(total.view(np.int64))
+        if on_gpu:                                             # an RCCL group reduces device tensors only
+            t = t.to(torch.device("cuda", dev))
+    dist.all_reduce(t, group=pg)                               # over RCCL the accumulator has not left the device before the sum
     return t.cpu().numpy().view(np.uint64)
+
+
+def pair_matrix(headers: List[Header], windows, threads: int = DEFAULT_THREADS, devices=(0,), group=None,
+                partial_fn=None, stats: dict = None) -> List[np.ndarray]:
+    """One N x N u64 per (min, max) window: [i][i] = valid addresses of table i, [i][j] (i<j) = addresses valid in both:
+    the W x N x N words of all windows as one flat accumulator, split and reduced as _pair_flat does (so the partials of
+    all windows are summed by ONE all-reduce).  `partial_fn(headers, lo, hi, windows, device, threads)` computes one slice's
+    tallies as W arrays (default: gpu_partial, looked up when called; the CPU-only tests substitute the oracle)."""
+    assert 1 <= len(headers) <= 128, "a pair tally takes 1 to 128 tables"
+    N, W = len(headers), len(windows)
+
+    def flat(pair_fn):
+        def partial(headers, lo, hi, device, threads, **kw):
+            parts = pair_fn(headers, lo, hi, windows, device, threads, **kw)
+            return None if parts is None else np.asarray(parts, dtype=np.uint64).reshape(-1)
+        return partial
+    own = gpu_partial
+    total = _pair_flat(headers, W * N * N, flat(own), threads, devices, group,
+                       None if partial_fn in (None, own) else flat(partial_fn), stats)
+    return list(total.reshape(W, N, N))
 
 
 def pair_spectrum(headers: List[Header], threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
