@@ -1,13 +1,17 @@
 // pk_api.hip -- host side of the C-ABI declared in include/pykmer_hip.h.
-// Owns device memory, streams and events; sequences the kernels of kmer_count.hip / gram_scan.hip.
+// Owns device memory, streams and events (every allocation of the library is made here) and sequences the kernels of the
+// indexer (kmer_count.hip, kmer_pack.hip, kmer_fuse.hip, kmer_part.hip, fastq.hip) and of the merger (gram_scan.hip,
+// gram_spectrum.hip, gram_occ.hip).  No kernel is defined in this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -73,6 +77,49 @@ static int check_k(int k, int slice_bits = 0, int slice_index = 0) {
     return PK_OK;
 }
 
+// ================================================================== owned device memory =========
+namespace {
+// "Reserve exactly": nothing at all when the capacity suffices (the steady state of the timed path); otherwise the old
+// block is freed FIRST and exactly `need` bytes are allocated.  The k = 17 indexer sits next to a 16 GiB table: these
+// buffers can afford neither geometric growth nor the old and the new block side by side.  The contents are lost.
+int reserve_exact(void **p, size_t *cap, size_t need) {
+    if (need <= *cap) return PK_OK;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    HIPCHK(hipMalloc(p, need));
+    *cap = need;
+    return PK_OK;
+}
+
+// One device allocation of T and its capacity in bytes.  Move-only; the destructor frees, and leaves g_err alone so that
+// the message of the call that failed survives the clean-up.  Never a member of an object with static storage: the HIP
+// runtime may be gone when static destructors run (Bouncer and GramCtx below keep raw pointers for that reason).
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }   // o's destructor frees what this held
+    ~DevBuf() { if (p) hipFree(p); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    int reserve(size_t need) { return reserve_exact((void **)&p, &bytes, need); }
+    // "Grow and keep": a larger array with the old contents in front and zeros behind, filled on `s`; the host waits for
+    // it, then the old array is freed.  The new one is released if a step fails.
+    int grow_keep(size_t need, hipStream_t s) {
+        if (need <= bytes) return PK_OK;
+        DevBuf larger;
+        int rc = larger.reserve(need);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(larger.p, 0, need, s));
+        if (bytes) HIPCHK(hipMemcpyAsync(larger.p, p, bytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        swap(larger);
+        return PK_OK;
+    }
+};
+}  // namespace
+
 // ================================================================== host <-> HBM copies =========
 // The C-ABI takes plain (pageable) host buffers.  One hipMemcpy from pageable memory is a single thread bouncing
 // the bytes through a small pinned buffer; here several host threads each own a pinned bounce buffer (two halves)
@@ -99,11 +146,23 @@ int bouncer_for(int device, Bouncer **out) {
         const char *env = getenv("PK_COPY_THREADS");
         int t = env ? atoi(env) : 8;
         t = std::max(1, std::min(t, MAX_COPY_THREADS));
-        for (int i = 0; i < t; i++) {
-            HIPCHK(hipHostMalloc((void **)&b.pinned[i], 2 * BOUNCE_HALF, hipHostMallocDefault));
-            HIPCHK(hipStreamCreateWithFlags(&b.stream[i], hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&b.ev[i][0], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&b.ev[i][1], hipEventDisableTiming));
+        auto make = [&]() -> int {
+            for (int i = 0; i < t; i++) {
+                HIPCHK(hipHostMalloc((void **)&b.pinned[i], 2 * BOUNCE_HALF, hipHostMallocDefault));
+                HIPCHK(hipStreamCreateWithFlags(&b.stream[i], hipStreamNonBlocking));
+                HIPCHK(hipEventCreateWithFlags(&b.ev[i][0], hipEventDisableTiming));
+                HIPCHK(hipEventCreateWithFlags(&b.ev[i][1], hipEventDisableTiming));
+            }
+            return PK_OK;
+        };
+        if (int rc = make()) {                             // all or nothing: the next call starts from an empty context again
+            for (int i = 0; i < t; i++) {
+                if (b.pinned[i]) hipHostFree(b.pinned[i]);
+                if (b.stream[i]) hipStreamDestroy(b.stream[i]);
+                for (auto &e : b.ev[i]) if (e) hipEventDestroy(e);
+                b.pinned[i] = nullptr; b.stream[i] = nullptr; b.ev[i][0] = b.ev[i][1] = nullptr;
+            }
+            return rc;
         }
         b.threads = t;
     }
@@ -198,69 +257,102 @@ extern "C" int pk_dev_mem_info(uint64_t *free_out, uint64_t *total_out, int devi
 }
 
 // ================================================================== indexer ====================
+// One counting stream on one device: the .kin image, the scratch of the structure pass (kmer_count.hip), the squeeze
+// (kmer_pack.hip), the partition passes (kmer_fuse.hip, kmer_part.hip) and the FASTQ front end (fastq.hip), and the stream
+// and events that order and time them.  Everything it holds is released by its destructor.
+namespace {
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    ~Stream() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+// the device events of a feed, by what they bracket on the stream
+struct Events {
+    hipEvent_t reset_begin = nullptr, reset_end = nullptr;         // ix_reset
+    hipEvent_t scan_begin = nullptr, scan_end = nullptr;           // structure pass: chunk summaries and their scans
+    hipEvent_t squeeze_begin = nullptr, squeeze_end = nullptr;
+    hipEvent_t sort_begin = nullptr, sort_end = nullptr;           // walk + level-1 sort kernel (inside launch_partitioned)
+    hipEvent_t part_end = nullptr;                                 // bucket layout and level 2 end here, the bucket count begins
+    hipEvent_t bucket_end = nullptr;
+    hipEvent_t final_begin = nullptr, final_end = nullptr;         // pk_indexer_finish
+    Events() = default;
+    Events(const Events &) = delete;
+    ~Events() { for (hipEvent_t *e : all()) if (*e) hipEventDestroy(*e); }
+    std::array<hipEvent_t *, 12> all() {
+        return {&reset_begin, &reset_end, &scan_begin, &scan_end, &squeeze_begin, &squeeze_end, &sort_begin, &sort_end, &part_end, &bucket_end,
+                &final_begin, &final_end};
+    }
+};
+}  // namespace
+
 struct pk_indexer {
     int k = 0, device = 0;
     int slice_bits = 0, slice_index = 0;   // the table holds addresses [slice_index, slice_index + 1) * 4^k / 2^slice_bits
     uint64_t n = 0;                  // table bytes: 4^k / 2^slice_bits
-    hipStream_t stream = nullptr;
-    uint8_t *table8 = nullptr;       // the .kin image
+    // members are destroyed in reverse order of declaration, behind the destructor's wait: the buffers, then the events,
+    // then the stream
+    Stream stream;
+    Events ev;
+    DevBuf<uint8_t> table8;          // the .kin image
     // parser state + running totals, and the value histogram, side by side: one copy brings both to the host, one copy resets both
     struct Tail { Carry carry; unsigned long long hist[256]; FqCarry fq; };
-    Tail *tail = nullptr, *tail0 = nullptr;   // tail0: the state of an empty stream (a reset is a device-to-device copy, no host wait)
-    Carry *carry = nullptr;            // = &tail->carry
+    DevBuf<Tail> tail, tail0;          // tail0: the state of an empty stream (a reset is a device-to-device copy, no host wait)
     struct Pinned { Tail tail; uint32_t flags[4]; } *pin = nullptr;   // pinned landing zone of the small read-backs
     bool tail_on_host = false;         // pin->tail is what the device holds (the last feed brought it along with its flags)
     bool zero_timed = true;            // t_zero of the last reset has been read from its events
-    unsigned long long *hist = nullptr;
-    unsigned long long *hist_rep = nullptr;   // HIST_REPLICAS copies of one feed's histogram change (zero between feeds)
-    DevRec *recs = nullptr;
-    uint64_t recs_cap = 0;
-    L1 *c_l1 = nullptr, *c_l1s = nullptr;
-    L2 *c_l2 = nullptr, *c_l2s = nullptr;
-    LaneState *lane_state = nullptr;   // per 64-byte piece: start state relative to its chunk
-    PiecePack *packs = nullptr;        // per 64-byte piece: its bases, classified and pushed together (structure pass -> squeeze pass)
-    uint32_t *chunk_odd = nullptr;     // per chunk: pieces that are not plain sequence text
-    L1 *t_l1 = nullptr;                // scan scratch: one summary per 1024 chunks
-    L2 *t_l2 = nullptr;
-    uint32_t chunk_cap = 0;
-    uint8_t *staging[2] = {nullptr, nullptr};   // device copies of host-fed pieces (one counted while the next uploads)
-    uint64_t staging_cap[2] = {0, 0};
+    DevBuf<unsigned long long> hist_rep;   // HIST_REPLICAS copies of one feed's histogram change (zero between feeds)
+    DevBuf<DevRec> recs;
+    DevBuf<L1> c_l1, c_l1s;
+    DevBuf<L2> c_l2, c_l2s;
+    DevBuf<LaneState> lane_state;      // per 64-byte piece: start state relative to its chunk
+    DevBuf<PiecePack> packs;           // per 64-byte piece: its bases, classified and pushed together (structure pass -> squeeze pass)
+    DevBuf<uint32_t> chunk_odd;        // per chunk: pieces that are not plain sequence text
+    DevBuf<L1> t_l1;                   // scan scratch: one summary per 1024 chunks
+    DevBuf<L2> t_l2;
+    DevBuf<uint8_t> staging[2];        // device copies of host-fed pieces (one counted while the next uploads)
     uint64_t bytes_fed = 0, n_recs = 0;
     bool finished = false;
-    hipEvent_t ev[12] = {};
     double t_scan = 0, t_squeeze = 0, t_sort = 0, t_final = 0, t_zero = 0, t_part = 0, t_bucket = 0;
     int feeds = 0, relayouts = 0;
     uint64_t recounted = 0;                                // buckets whose byte counters wrapped and were counted again (k_bucket_count_bytes)
     bool table_fresh = true;         // no feed has written the u8 table since the last reset
-    uint8_t *ws = nullptr;           // workspace of the partition passes
-    size_t ws_cap = 0;
+    DevBuf<uint8_t> ws;              // workspace of the partition passes
     // FASTQ input (fastq.hip): each feed is turned into FASTA text in fq_out[fq_buf]; that text is counted by the next
     // feed (or by finish), whose read-back brings this feed's checks and totals along -- no wait of its own
     int format = PK_FORMAT_FASTA;
     bool fed = false;                  // bytes were fed since the last reset
-    FqSum *fq_sums = nullptr;
-    FqState *fq_st = nullptr;
-    uint32_t fq_chunk_cap = 0;
-    uint8_t *fq_out[2] = {nullptr, nullptr};
-    uint64_t fq_out_cap[2] = {0, 0};
+    DevBuf<FqSum> fq_sums;
+    DevBuf<FqState> fq_st;
+    DevBuf<uint8_t> fq_out[2];
     int fq_buf = 0;
     uint64_t fq_pending = 0;           // FASTA bytes in fq_out[fq_buf ^ 1] not counted yet
-    FqRec *fq_recs = nullptr;
-    uint64_t fq_recs_cap = 0, fq_need = 0;
+    DevBuf<FqRec> fq_recs;
+    uint64_t fq_need = 0;
     bool fq_failed = false;
     std::string fq_err;
+
+    uint64_t recs_cap() const { return recs.bytes / sizeof(DevRec); }
+    uint64_t fq_recs_cap() const { return fq_recs.bytes / sizeof(FqRec); }
+    ~pk_indexer() {
+        hipSetDevice(device);
+        if (stream) hipStreamSynchronize(stream);
+        if (pin) hipHostFree(pin);
+    }
 };
 
 static int ix_reset(pk_indexer *ix) {
     HIPCHK(hipSetDevice(ix->device));
-    HIPCHK(hipEventRecord(ix->ev[6], ix->stream));
+    HIPCHK(hipEventRecord(ix->ev.reset_begin, ix->stream));
     // the first feed writes every slice of the u8 table itself (k_bucket_count, fresh); the table is only
     // zeroed if nothing gets fed at all (see pk_indexer_finish).  Nothing here waits for the device: the stream orders
     // the reset behind whatever is still running, and its duration is read at the next point that waits anyway.
-    HIPCHK(hipMemcpyAsync(ix->tail, ix->tail0, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
+    HIPCHK(hipMemcpyAsync(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
     ix->tail_on_host = false;
-    if (ix->recs) HIPCHK(hipMemsetAsync(ix->recs, 0, ix->recs_cap * sizeof(DevRec), ix->stream));
-    HIPCHK(hipEventRecord(ix->ev[7], ix->stream));
+    if (ix->recs.p) HIPCHK(hipMemsetAsync(ix->recs.p, 0, ix->recs.bytes, ix->stream));
+    HIPCHK(hipEventRecord(ix->ev.reset_end, ix->stream));
     ix->zero_timed = false;
     ix->t_zero = 0;
     ix->bytes_fed = ix->n_recs = 0;
@@ -277,22 +369,29 @@ static int ix_reset(pk_indexer *ix) {
 static void time_reset(pk_indexer *ix) {
     if (ix->zero_timed) return;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ix->ev[6], ix->ev[7]) == hipSuccess) ix->t_zero = ms * 1e-3;
+    if (hipEventElapsedTime(&ms, ix->ev.reset_begin, ix->ev.reset_end) == hipSuccess) ix->t_zero = ms * 1e-3;
     ix->zero_timed = true;
 }
 
-extern "C" void pk_indexer_destroy(pk_indexer *ix) {
-    if (!ix) return;
-    hipSetDevice(ix->device);
-    if (ix->stream) hipStreamSynchronize(ix->stream);
-    hipFree(ix->table8); hipFree(ix->tail); hipFree(ix->tail0); hipFree(ix->hist_rep); hipFree(ix->recs);
-    if (ix->pin) hipHostFree(ix->pin);
-    hipFree(ix->c_l1); hipFree(ix->c_l1s); hipFree(ix->c_l2); hipFree(ix->c_l2s); hipFree(ix->lane_state); hipFree(ix->packs); hipFree(ix->chunk_odd); hipFree(ix->t_l1); hipFree(ix->t_l2); hipFree(ix->staging[0]); hipFree(ix->staging[1]); hipFree(ix->ws);
-    hipFree(ix->fq_sums); hipFree(ix->fq_st); hipFree(ix->fq_out[0]); hipFree(ix->fq_out[1]); hipFree(ix->fq_recs);
-    for (auto &e : ix->ev) if (e) hipEventDestroy(e);
-    if (ix->stream) hipStreamDestroy(ix->stream);
-    delete ix;
+// The stream totals, the value histogram and the FASTQ state to the host, behind everything queued so far; the host waits
+// for it.  This is the wait of a feed: it also surfaces a kernel fault and makes the reset's events readable.
+static int read_tail(pk_indexer *ix) {
+    HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    HIPCHK(hipGetLastError());
+    time_reset(ix);
+    ix->tail_on_host = true;
+    return PK_OK;
 }
+
+// the device tallies the values 1 .. 255 only: the zeros are the rest of the n addresses
+static void hist_with_zeros(const unsigned long long *h, uint64_t n, uint64_t hist256_out[256]) {
+    uint64_t nonzero = 0;
+    for (int v = 1; v < 256; v++) { hist256_out[v] = h[v]; nonzero += h[v]; }
+    hist256_out[0] = n - nonzero;
+}
+
+extern "C" void pk_indexer_destroy(pk_indexer *ix) { delete ix; }
 
 extern "C" int pk_indexer_create(pk_indexer **out, int k, int device) { return pk_indexer_create_slice(out, k, device, 0, 1); }
 
@@ -305,50 +404,36 @@ extern "C" int pk_indexer_create_slice(pk_indexer **out, int k, int device, int 
     int rc = check_k(k, slice_bits, slice_index);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
-    pk_indexer *ix = new pk_indexer();
+    std::unique_ptr<pk_indexer> ix(new pk_indexer());        // a failure below destroys what was built so far
     ix->k = k; ix->device = device; ix->slice_bits = slice_bits; ix->slice_index = slice_index;
     ix->n = 1ULL << (2 * k - slice_bits);
-    auto bail = [&](hipError_t e, const char *what) {
-        int r = fail(PK_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-        std::string keep = g_err;
-        pk_indexer_destroy(ix);
-        g_err = keep;
-        return r;
-    };
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    for (auto &ev : ix->ev) if ((e = hipEventCreate(&ev)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipMalloc(&ix->table8, std::max<uint64_t>(ix->n, 16))) != hipSuccess) return bail(e, "hipMalloc(u8 table)");
-    if ((e = hipMalloc(&ix->tail, sizeof(pk_indexer::Tail))) != hipSuccess) return bail(e, "hipMalloc(carry)");
-    if ((e = hipMalloc(&ix->tail0, sizeof(pk_indexer::Tail))) != hipSuccess) return bail(e, "hipMalloc(carry0)");
-    ix->carry = &ix->tail->carry; ix->hist = ix->tail->hist;
-    if ((e = hipHostMalloc(&ix->pin, sizeof(*ix->pin), hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc");
+    HIPCHK(hipStreamCreateWithFlags(&ix->stream.s, hipStreamNonBlocking));
+    for (hipEvent_t *e : ix->ev.all()) HIPCHK(hipEventCreate(e));
+    if ((rc = ix->table8.reserve(std::max<uint64_t>(ix->n, 16)))) return rc;
+    if ((rc = ix->tail.reserve(sizeof(pk_indexer::Tail)))) return rc;
+    if ((rc = ix->tail0.reserve(sizeof(pk_indexer::Tail)))) return rc;
+    HIPCHK(hipHostMalloc(&ix->pin, sizeof(*ix->pin), hipHostMallocDefault));
     {
         Carry c;
         memset(&c, 0, sizeof c);
         c.l1 = 8u | 1u | (LS_START << 1);                    // l1_state(LS_START)
         c.l2.flags = F_NONID | F_PRESET | F_BRK;             // l2_state(0, 0, 0, 0)
-        if ((e = hipMemset(ix->tail0, 0, sizeof(pk_indexer::Tail))) != hipSuccess) return bail(e, "hipMemset(carry0)");
-        if ((e = hipMemcpy(&ix->tail0->carry, &c, sizeof c, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(carry0)");
+        HIPCHK(hipMemset(ix->tail0.p, 0, sizeof(pk_indexer::Tail)));
+        HIPCHK(hipMemcpy(&ix->tail0.p->carry, &c, sizeof c, hipMemcpyHostToDevice));
         FqCarry q;
         memset(&q, 0, sizeof q);
         q.st.ws = q.in.ws = 1;                               // the open line (none yet) holds no text
         q.err = q.trail = ~0ull;
         q.prev4 = q.prev4_in = 0x0a0a0a0au;                  // before the stream: line terminators
-        if ((e = hipMemcpy(&ix->tail0->fq, &q, sizeof q, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(fastq carry0)");
+        HIPCHK(hipMemcpy(&ix->tail0.p->fq, &q, sizeof q, hipMemcpyHostToDevice));
     }
-    if ((e = hipMalloc(&ix->hist_rep, (size_t)HIST_REPLICAS * 256 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(hist replicas)");
-    if ((e = hipMemset(ix->hist_rep, 0, (size_t)HIST_REPLICAS * 256 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(hist replicas)");
-    {
-        // room for the records of small inputs from the start: the squeeze pass checks the capacity itself (see feed_piece)
-        const uint64_t cap = 4096;
-        if ((e = hipMalloc(&ix->recs, cap * sizeof(DevRec))) != hipSuccess) return bail(e, "hipMalloc(records)");
-        ix->recs_cap = cap;
-    }
+    if ((rc = ix->hist_rep.reserve((size_t)HIST_REPLICAS * 256 * sizeof(unsigned long long)))) return rc;
+    HIPCHK(hipMemset(ix->hist_rep.p, 0, ix->hist_rep.bytes));
+    // room for the records of small inputs from the start: the squeeze pass checks the capacity itself (see feed_piece)
+    if ((rc = ix->recs.reserve(4096 * sizeof(DevRec)))) return rc;
     part_set_attributes();                               // dynamic-LDS opt-ins, once per process and device
-    rc = ix_reset(ix);
-    if (rc) { std::string keep = g_err; pk_indexer_destroy(ix); g_err = keep; return rc; }
-    *out = ix;
+    if ((rc = ix_reset(ix.get()))) return rc;
+    *out = ix.release();
     return PK_OK;
 }
 
@@ -357,36 +442,26 @@ extern "C" int pk_indexer_reset(pk_indexer *ix) {
     return ix_reset(ix);
 }
 
+// the scratch of the structure pass for a feed of n_chunks chunks
 static int ensure_chunks(pk_indexer *ix, uint32_t n_chunks) {
-    if (n_chunks <= ix->chunk_cap) return PK_OK;
-    hipFree(ix->c_l1); hipFree(ix->c_l1s); hipFree(ix->c_l2); hipFree(ix->c_l2s); hipFree(ix->lane_state); hipFree(ix->packs); hipFree(ix->chunk_odd); hipFree(ix->t_l1); hipFree(ix->t_l2);
-    ix->c_l1 = ix->c_l1s = nullptr; ix->c_l2 = ix->c_l2s = nullptr; ix->lane_state = nullptr; ix->packs = nullptr; ix->chunk_odd = nullptr; ix->t_l1 = nullptr; ix->t_l2 = nullptr;
-    ix->chunk_cap = 0;
-    HIPCHK(hipMalloc(&ix->c_l1, n_chunks * sizeof(L1)));
-    HIPCHK(hipMalloc(&ix->c_l1s, n_chunks * sizeof(L1)));
-    HIPCHK(hipMalloc(&ix->c_l2, n_chunks * sizeof(L2)));
-    HIPCHK(hipMalloc(&ix->c_l2s, n_chunks * sizeof(L2)));
-    HIPCHK(hipMalloc(&ix->lane_state, (size_t)n_chunks * WG * sizeof(LaneState)));
-    HIPCHK(hipMalloc(&ix->packs, (size_t)n_chunks * WG * sizeof(PiecePack)));
-    HIPCHK(hipMalloc(&ix->chunk_odd, (size_t)n_chunks * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&ix->t_l1, ((size_t)n_chunks / 1024 + 1) * sizeof(L1)));
-    HIPCHK(hipMalloc(&ix->t_l2, ((size_t)n_chunks / 1024 + 1) * sizeof(L2)));
-    ix->chunk_cap = n_chunks;
-    return PK_OK;
+    const size_t n = n_chunks;
+    int rc;
+    if ((rc = ix->c_l1.reserve(n * sizeof(L1)))) return rc;
+    if ((rc = ix->c_l1s.reserve(n * sizeof(L1)))) return rc;
+    if ((rc = ix->c_l2.reserve(n * sizeof(L2)))) return rc;
+    if ((rc = ix->c_l2s.reserve(n * sizeof(L2)))) return rc;
+    if ((rc = ix->lane_state.reserve(n * WG * sizeof(LaneState)))) return rc;
+    if ((rc = ix->packs.reserve(n * WG * sizeof(PiecePack)))) return rc;
+    if ((rc = ix->chunk_odd.reserve(n * sizeof(uint32_t)))) return rc;
+    if ((rc = ix->t_l1.reserve((n / 1024 + 1) * sizeof(L1)))) return rc;
+    return ix->t_l2.reserve((n / 1024 + 1) * sizeof(L2));
 }
 
+// the sizing rules stay with the callers: the capacities the two record arrays reach are part of the retry behaviour
 static int ensure_recs(pk_indexer *ix, uint64_t need) {
-    if (need <= ix->recs_cap) return PK_OK;
-    uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, ix->recs_cap * 2));
-    DevRec *nr = nullptr;
-    HIPCHK(hipMalloc(&nr, cap * sizeof(DevRec)));
-    HIPCHK(hipMemsetAsync(nr, 0, cap * sizeof(DevRec), ix->stream));
-    if (ix->recs && ix->recs_cap)
-        HIPCHK(hipMemcpyAsync(nr, ix->recs, ix->recs_cap * sizeof(DevRec), hipMemcpyDeviceToDevice, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    hipFree(ix->recs);
-    ix->recs = nr; ix->recs_cap = cap;
-    return PK_OK;
+    if (need <= ix->recs_cap()) return PK_OK;
+    const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, ix->recs_cap() * 2));
+    return ix->recs.grow_keep(cap * sizeof(DevRec), ix->stream);
 }
 
 // one feed of at most FEED_MAX bytes: structure pass -> squeeze -> bucket layout -> fused k-mer assembly + level-1
@@ -422,27 +497,24 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     PartPlan pl = make_part_plan((uint32_t)ix->k, n_bytes, (uint32_t)ix->slice_bits, (uint32_t)ix->slice_index);
     if (!plan_fits_u32(pl)) return fail(PK_ERR_ARG, "feed of %llu bytes needs record positions beyond 2^32 (internal limit); split it", (unsigned long long)n_bytes);
     PartWorkspace lay;
-    const size_t need = part_workspace_bytes(pl, n_bytes, &lay);
-    if (need > ix->ws_cap) {
-        hipFree(ix->ws); ix->ws = nullptr; ix->ws_cap = 0;
-        HIPCHK(hipMalloc(&ix->ws, need));
-        ix->ws_cap = need;
-    }
-    uint32_t *flag_words = (uint32_t *)(ix->ws + lay.side_n);              // side-list length (u64), then flags[4]
+    if ((rc = ix->ws.reserve(part_workspace_bytes(pl, n_bytes, &lay)))) return rc;
+    uint8_t *ws = ix->ws.p;
+    uint32_t *flag_words = (uint32_t *)(ws + lay.side_n);                  // side-list length (u64), then flags[4]
     uint32_t *flags = flag_words + 2;
+    Carry *carry = &ix->tail.p->carry;
+    const Events &ev = ix->ev;
     // Nothing between here and the last kernel of the feed waits for the device: the record array was sized from what the
     // feeds so far held (ensure_recs below, after the feed), the squeeze pass checks that against the count the structure
     // pass leaves in `carry` and backs out if it does not fit (flags[0] = 2), the sorts back out if a sampled bucket
     // room does not hold (flags[0] = 1), and the host reads flags + record count once, behind the last kernel.  Every
     // kernel behind the squeeze returns at once when it finds flags[0] raised (the workspace then still holds an earlier
     // feed's squeezed text), so a 2 reaches the host as a 2, whatever that text would have done to the sampled layout.
-    HIPCHK(hipEventRecord(ix->ev[0], ix->stream));
-    launch_chunk_l1(f, n_bytes, ix->c_l1, n_chunks, ix->stream);
-    launch_scan_l1(ix->c_l1, n_chunks, ix->carry, ix->c_l1s, ix->t_l1, flag_words, PART_FLAG_WORDS, ix->stream);
-    launch_chunk_l2(f, n_bytes, ix->c_l1s, ix->c_l2, ix->lane_state, ix->packs, ix->chunk_odd, n_chunks, (uint32_t)ix->k, ix->stream);
-    launch_scan_l2(ix->c_l2, n_chunks, ix->carry, ix->c_l2s, ix->t_l2, (uint32_t)ix->k, ix->stream);
-    HIPCHK(hipEventRecord(ix->ev[1], ix->stream));
-    float a = 0, b = 0, c = 0, d = 0, e = 0;
+    HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
+    launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
+    launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, flag_words, PART_FLAG_WORDS, ix->stream);
+    launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, n_chunks, (uint32_t)ix->k, ix->stream);
+    launch_scan_l2(ix->c_l2.p, n_chunks, carry, ix->c_l2s.p, ix->t_l2.p, (uint32_t)ix->k, ix->stream);
+    HIPCHK(hipEventRecord(ev.scan_end, ix->stream));
     bool armed = true;                                       // the scan kernel zeroed the flag words for the first attempt
     bool squeeze = true;
     uint64_t squeezed_cap = 0;                               // record slots the last squeeze of this feed ran with
@@ -450,28 +522,26 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     for (int attempt = 0;; attempt++) {
         if (squeeze) {
             if (!armed) HIPCHK(hipMemsetAsync(flag_words, 0, PART_FLAG_WORDS * 4, ix->stream));
-            squeezed_cap = ix->recs_cap;
-            HIPCHK(hipEventRecord(ix->ev[2], ix->stream));
-            launch_squeeze(f, n_bytes, ix->bytes_fed, ix->lane_state, ix->packs, ix->c_l2s, ix->chunk_odd, (uint32_t)ix->k, n_chunks, pl.n_wg0, pl.G, (uint32_t *)(ix->ws + lay.codes),
-                           (uint32_t *)(ix->ws + lay.restarts), (uint32_t *)(ix->ws + lay.n_bases), ix->recs, ix->recs_cap, ix->carry, flags, ix->stream);
-            HIPCHK(hipEventRecord(ix->ev[3], ix->stream));
+            squeezed_cap = ix->recs_cap();
+            HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream));
+            launch_squeeze(f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, (uint32_t)ix->k, n_chunks, pl.n_wg0, pl.G,
+                           (uint32_t *)(ws + lay.codes), (uint32_t *)(ws + lay.restarts), (uint32_t *)(ws + lay.n_bases), ix->recs.p, ix->recs_cap(), carry,
+                           flags, ix->stream);
+            HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
             armed = true;
         }
         // the level-1 buckets are laid out from a sample of the slots; if one of them runs out of room every later kernel
         // returns untouched (flags[0] = 1) and the passes behind the squeeze are repeated with exact sizes -- on the text
         // the squeeze of this feed left, so only once that squeeze has run in full (flags[0] = 2 is handled first)
-        if (launch_partitioned(ix->c_l2s, n_bytes, pl, stride, ix->ws, lay, ix->table8, ix->stream, ix->ev[10], ix->ev[11], ix->ev[8],
-                               ix->table_fresh, ix->hist, ix->hist_rep, armed))
+        if (launch_partitioned(ix->c_l2s.p, n_bytes, pl, stride, ws, lay, ix->table8.p, ix->stream, ev.sort_begin, ev.sort_end, ev.part_end,
+                               ix->table_fresh, ix->tail.p->hist, ix->hist_rep.p, armed))
             return fail(PK_ERR_HIP, "partition pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
-        HIPCHK(hipEventRecord(ix->ev[9], ix->stream));
+        HIPCHK(hipEventRecord(ev.bucket_end, ix->stream));
         volatile uint32_t *got = ix->pin->flags;
         // what the host needs of the feed, in two small copies behind the last kernel: the flags, and the stream totals +
         // value histogram (pk_indexer_finish then has nothing left to fetch)
         HIPCHK(hipMemcpyAsync(ix->pin->flags, flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        HIPCHK(hipGetLastError());
-        time_reset(ix);
+        if ((rc = read_tail(ix))) return rc;
         if (!got[0]) { ix->recounted += got[1]; break; }
         if (attempt >= 3) return fail(PK_ERR_HIP, "the feed's layout did not settle (internal error, flag %u)", got[0]);
         armed = false;
@@ -492,17 +562,17 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
                     (unsigned long long)ix->pin->tail.carry.n_recs, (unsigned long long)squeezed_cap);
     const uint64_t recs_before = ix->n_recs;
     ix->n_recs = ix->pin->tail.carry.n_recs;
-    ix->tail_on_host = true;
     // room for the next feed's records before it arrives: as many again as this feed brought, and then some
     rc = ensure_recs(ix, ix->n_recs + 2 * (ix->n_recs - recs_before) + 1024);
     if (rc) return rc;
     ix->table_fresh = false;
-    HIPCHK(hipEventElapsedTime(&a, ix->ev[0], ix->ev[1]));
-    HIPCHK(hipEventElapsedTime(&b, ix->ev[2], ix->ev[3]));
-    HIPCHK(hipEventElapsedTime(&c, ix->ev[3], ix->ev[8]));
-    HIPCHK(hipEventElapsedTime(&d, ix->ev[8], ix->ev[9]));
-    HIPCHK(hipEventElapsedTime(&e, ix->ev[10], ix->ev[11]));
-    ix->t_scan += a * 1e-3; ix->t_squeeze += b * 1e-3; ix->t_part += c * 1e-3; ix->t_bucket += d * 1e-3; ix->t_sort += e * 1e-3;
+    float scan = 0, squeeze_ms = 0, part = 0, bucket = 0, sort = 0;
+    HIPCHK(hipEventElapsedTime(&scan, ev.scan_begin, ev.scan_end));
+    HIPCHK(hipEventElapsedTime(&squeeze_ms, ev.squeeze_begin, ev.squeeze_end));
+    HIPCHK(hipEventElapsedTime(&part, ev.squeeze_end, ev.part_end));
+    HIPCHK(hipEventElapsedTime(&bucket, ev.part_end, ev.bucket_end));
+    HIPCHK(hipEventElapsedTime(&sort, ev.sort_begin, ev.sort_end));
+    ix->t_scan += scan * 1e-3; ix->t_squeeze += squeeze_ms * 1e-3; ix->t_part += part * 1e-3; ix->t_bucket += bucket * 1e-3; ix->t_sort += sort * 1e-3;
     ix->feeds++;
     ix->bytes_fed += n_bytes;
     return PK_OK;
@@ -523,7 +593,7 @@ static const char *fq_rule_text(uint32_t rule) {
 // the indexer stops at a malformed record until it is reset; rec is 0-based
 static int fq_fail(pk_indexer *ix, uint64_t rec, uint32_t rule) {
     uint64_t line1 = 0;
-    if (rec < ix->fq_recs_cap) HIPCHK(hipMemcpy(&line1, &ix->fq_recs[rec].line1, sizeof line1, hipMemcpyDeviceToHost));
+    if (rec < ix->fq_recs_cap()) HIPCHK(hipMemcpy(&line1, &ix->fq_recs.p[rec].line1, sizeof line1, hipMemcpyDeviceToHost));
     fail(PK_ERR_FORMAT, "malformed FASTQ: record %llu (line 1 at byte %llu): %s", (unsigned long long)rec + 1, (unsigned long long)line1,
          fq_rule_text(rule));
     ix->fq_failed = true;
@@ -546,16 +616,8 @@ static int fq_verdict(pk_indexer *ix) {
 }
 
 static int fq_ensure_recs(pk_indexer *ix, uint64_t need) {
-    if (need <= ix->fq_recs_cap) return PK_OK;
-    const uint64_t cap = std::max<uint64_t>(need, 2 * ix->fq_recs_cap);
-    FqRec *nr = nullptr;
-    HIPCHK(hipMalloc(&nr, cap * sizeof(FqRec)));
-    HIPCHK(hipMemsetAsync(nr, 0, cap * sizeof(FqRec), ix->stream));
-    if (ix->fq_recs_cap) HIPCHK(hipMemcpyAsync(nr, ix->fq_recs, ix->fq_recs_cap * sizeof(FqRec), hipMemcpyDeviceToDevice, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    hipFree(ix->fq_recs);
-    ix->fq_recs = nr; ix->fq_recs_cap = cap;
-    return PK_OK;
+    if (need <= ix->fq_recs_cap()) return PK_OK;
+    return ix->fq_recs.grow_keep(std::max<uint64_t>(need, 2 * ix->fq_recs_cap()) * sizeof(FqRec), ix->stream);
 }
 
 // the FASTA text of the previous FASTQ feed, if any, into the pipeline; ends with the read-back of the carry
@@ -563,42 +625,30 @@ static int fq_flush(pk_indexer *ix) {
     if (ix->fq_pending) {
         const uint64_t n = ix->fq_pending;
         ix->fq_pending = 0;
-        return feed_piece(ix, ix->fq_out[ix->fq_buf ^ 1], n);
+        return feed_piece(ix, ix->fq_out[ix->fq_buf ^ 1].p, n);
     }
-    HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    HIPCHK(hipGetLastError());
-    time_reset(ix);
-    ix->tail_on_host = true;
-    return PK_OK;
+    return read_tail(ix);
 }
 
 // one FASTQ piece of at most feed_max_for(k) bytes: the front end turns it into FASTA text in fq_out[fq_buf] while the
 // text of the piece before goes through the FASTA pipeline
 static int fq_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n) {
     const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
-    if (n_chunks > ix->fq_chunk_cap) {
-        hipFree(ix->fq_sums); hipFree(ix->fq_st); ix->fq_sums = nullptr; ix->fq_st = nullptr; ix->fq_chunk_cap = 0;
-        HIPCHK(hipMalloc(&ix->fq_sums, (size_t)n_chunks * sizeof(FqSum)));
-        HIPCHK(hipMalloc(&ix->fq_st, (size_t)n_chunks * sizeof(FqState)));
-        ix->fq_chunk_cap = n_chunks;
-    }
     const int b = ix->fq_buf;
-    if (n + 64 > ix->fq_out_cap[b]) {
-        hipFree(ix->fq_out[b]); ix->fq_out[b] = nullptr; ix->fq_out_cap[b] = 0;
-        HIPCHK(hipMalloc(&ix->fq_out[b], n + 64));
-        ix->fq_out_cap[b] = n + 64;
-    }
+    int rc;
+    if ((rc = ix->fq_sums.reserve((size_t)n_chunks * sizeof(FqSum)))) return rc;
+    if ((rc = ix->fq_st.reserve((size_t)n_chunks * sizeof(FqState)))) return rc;
+    if ((rc = ix->fq_out[b].reserve(n + 64))) return rc;
     // record slots for what the stream needed so far and one record per 256 bytes of this piece; a piece that needs
     // more writes its text again once the array has grown
-    int rc = fq_ensure_recs(ix, ix->fq_need + n / 256 + 1024);
-    if (rc) return rc;
-    launch_fq_front(f, n, ix->fq_sums, ix->fq_st, ix->fq_out[b], ix->fq_recs, ix->fq_recs_cap, &ix->tail->fq, ix->stream);
+    if ((rc = fq_ensure_recs(ix, ix->fq_need + n / 256 + 1024))) return rc;
+    FqCarry *carry = &ix->tail.p->fq;
+    launch_fq_front(f, n, ix->fq_sums.p, ix->fq_st.p, ix->fq_out[b].p, ix->fq_recs.p, ix->fq_recs_cap(), carry, ix->stream);
     HIPCHK(hipGetLastError());
     if ((rc = fq_flush(ix))) return rc;
-    if (ix->pin->tail.fq.need > ix->fq_recs_cap) {
+    if (ix->pin->tail.fq.need > ix->fq_recs_cap()) {
         if ((rc = fq_ensure_recs(ix, ix->pin->tail.fq.need + n / 256 + 1024))) return rc;
-        launch_fq_write(f, n, ix->fq_st, ix->fq_out[b], ix->fq_recs, ix->fq_recs_cap, &ix->tail->fq, ix->stream);
+        launch_fq_write(f, n, ix->fq_st.p, ix->fq_out[b].p, ix->fq_recs.p, ix->fq_recs_cap(), carry, ix->stream);
         HIPCHK(hipGetLastError());
         if ((rc = fq_flush(ix))) return rc;
     }
@@ -620,7 +670,7 @@ static int fq_end_check(pk_indexer *ix) {
     if (role == 0u && q.st.curlen == 0) return PK_OK;
     if (role == 3u && q.st.curlen > 0) {
         uint64_t len2 = 0;
-        if (rec < ix->fq_recs_cap) HIPCHK(hipMemcpy(&len2, &ix->fq_recs[rec].len2, sizeof len2, hipMemcpyDeviceToHost));
+        if (rec < ix->fq_recs_cap()) HIPCHK(hipMemcpy(&len2, &ix->fq_recs.p[rec].len2, sizeof len2, hipMemcpyDeviceToHost));
         return len2 == q.st.curlen ? PK_OK : fq_fail(ix, rec, FQ_RULE_LEN);
     }
     return fq_fail(ix, rec, FQ_RULE_END);
@@ -681,25 +731,21 @@ extern "C" int pk_indexer_feed(pk_indexer *ix, const uint8_t *host_fasta, uint64
     const uint64_t n_pieces = (n_bytes + piece - 1) / piece;
     const uint64_t buf_bytes = std::min(piece, n_bytes) + 64;
     const int n_bufs = n_pieces > 1 ? 2 : 1;
+    int rc = PK_OK;
     for (int i = 0; i < n_bufs; i++)
-        if (buf_bytes > ix->staging_cap[i]) {
-            hipFree(ix->staging[i]); ix->staging[i] = nullptr; ix->staging_cap[i] = 0;
-            HIPCHK(hipMalloc(&ix->staging[i], buf_bytes));
-            ix->staging_cap[i] = buf_bytes;
-        }
+        if ((rc = ix->staging[i].reserve(buf_bytes))) return rc;
     auto upload = [&](uint64_t p) -> int {
         const uint64_t off = p * piece, len = std::min(piece, n_bytes - off);
-        return bounce_copy(ix->staging[p & 1], const_cast<uint8_t *>(host_fasta) + off, len, true, ix->device);
+        return bounce_copy(ix->staging[p & 1].p, const_cast<uint8_t *>(host_fasta) + off, len, true, ix->device);
     };
-    int rc = upload(0);
-    if (rc) return rc;
+    if ((rc = upload(0))) return rc;
     for (uint64_t p = 0; p < n_pieces; p++) {
         int up_rc = PK_OK;
         std::string up_err;
         std::thread next;
         if (p + 1 < n_pieces) next = std::thread([&]() { up_rc = upload(p + 1); if (up_rc) up_err = g_err; });
         const uint64_t off = p * piece, len = std::min(piece, n_bytes - off);
-        rc = pk_indexer_feed_device(ix, ix->staging[p & 1], len);
+        rc = pk_indexer_feed_device(ix, ix->staging[p & 1].p, len);
         if (next.joinable()) next.join();
         if (rc) return rc;
         if (up_rc) { g_err = up_err; return up_rc; }
@@ -724,19 +770,16 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
             // k_bucket_count / k_apply_side: no pass over the table), and every kernel has finished -- nothing to do
             ix->t_final = 0;
         } else {
-            HIPCHK(hipEventRecord(ix->ev[4], ix->stream));
+            HIPCHK(hipEventRecord(ix->ev.final_begin, ix->stream));
             if (ix->table_fresh) {                           // nothing was fed: the table is all zero
-                HIPCHK(hipMemsetAsync(ix->table8, 0, std::max<uint64_t>(ix->n, 16), ix->stream));
+                HIPCHK(hipMemsetAsync(ix->table8.p, 0, ix->table8.bytes, ix->stream));
                 ix->table_fresh = false;
             }
-            HIPCHK(hipEventRecord(ix->ev[5], ix->stream));
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
-            HIPCHK(hipStreamSynchronize(ix->stream));
-            ix->tail_on_host = true;
-            time_reset(ix);
+            HIPCHK(hipEventRecord(ix->ev.final_end, ix->stream));
+            int rc = read_tail(ix);
+            if (rc) return rc;
             float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ix->ev[4], ix->ev[5]));
+            HIPCHK(hipEventElapsedTime(&ms, ix->ev.final_begin, ix->ev.final_end));
             ix->t_final = ms * 1e-3;
         }
         if (ix->format == PK_FORMAT_FASTQ) {
@@ -749,12 +792,7 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
     if (num_kmers_out) *num_kmers_out = c.num_kmers;
     if (total_bp_out) *total_bp_out = c.total_bp;
     if (n_recs_out) *n_recs_out = c.n_recs;
-    if (hist256_out) {
-        const unsigned long long *h = ix->pin->tail.hist;
-        uint64_t nonzero = 0;
-        for (int v = 1; v < 256; v++) { hist256_out[v] = h[v]; nonzero += h[v]; }
-        hist256_out[0] = ix->n - nonzero;                // zeros are not tallied on the device
-    }
+    if (hist256_out) hist_with_zeros(ix->pin->tail.hist, ix->n, hist256_out);
     return PK_OK;
 }
 
@@ -765,7 +803,7 @@ extern "C" int pk_indexer_records(pk_indexer *ix, pk_record *recs_out, uint64_t 
     if (!recs_out) return fail(PK_ERR_ARG, "null records pointer");
     HIPCHK(hipSetDevice(ix->device));
     std::vector<DevRec> tmp(ix->n_recs);
-    HIPCHK(hipMemcpy(tmp.data(), ix->recs, ix->n_recs * sizeof(DevRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), ix->recs.p, ix->n_recs * sizeof(DevRec), hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < ix->n_recs; i++) {
         recs_out[i].name_off = tmp[i].name_off;
         recs_out[i].name_len = tmp[i].name_end > tmp[i].name_off ? tmp[i].name_end - tmp[i].name_off : 0;
@@ -773,9 +811,9 @@ extern "C" int pk_indexer_records(pk_indexer *ix, pk_record *recs_out, uint64_t 
         recs_out[i].n_valid_kmers = tmp[i].n_valid;
     }
     if (ix->format == PK_FORMAT_FASTQ) {                     // FASTQ record i is FASTA record i: names are sliced from the FASTQ
-        if (ix->n_recs > ix->fq_recs_cap) return fail(PK_ERR_HIP, "FASTQ record array too small (internal error)");
+        if (ix->n_recs > ix->fq_recs_cap()) return fail(PK_ERR_HIP, "FASTQ record array too small (internal error)");
         std::vector<FqRec> fq(ix->n_recs);
-        HIPCHK(hipMemcpy(fq.data(), ix->fq_recs, ix->n_recs * sizeof(FqRec), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(fq.data(), ix->fq_recs.p, ix->n_recs * sizeof(FqRec), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < ix->n_recs; i++) recs_out[i].name_off = fq[i].line1 + 1;
     }
     return PK_OK;
@@ -784,20 +822,20 @@ extern "C" int pk_indexer_records(pk_indexer *ix, pk_record *recs_out, uint64_t 
 extern "C" int pk_indexer_table_to_host(pk_indexer *ix, uint8_t *table_out) {
     if (!ix || !table_out) return fail(PK_ERR_ARG, "null argument");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
-    return bounce_copy(ix->table8, table_out, ix->n, false, ix->device);
+    return bounce_copy(ix->table8.p, table_out, ix->n, false, ix->device);
 }
 
 extern "C" int pk_indexer_table_slice_to_host(pk_indexer *ix, uint8_t *dst, uint64_t offset, uint64_t n_bytes) {
     if (!ix || !dst) return fail(PK_ERR_ARG, "null argument");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     if (offset > ix->n || n_bytes > ix->n - offset) return fail(PK_ERR_ARG, "slice outside the table");
-    return bounce_copy(ix->table8 + offset, dst, n_bytes, false, ix->device);
+    return bounce_copy(ix->table8.p + offset, dst, n_bytes, false, ix->device);
 }
 
 extern "C" int pk_indexer_table_device(pk_indexer *ix, const void **dev_table_out) {
     if (!ix || !dev_table_out) return fail(PK_ERR_ARG, "null argument");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
-    *dev_table_out = ix->table8;
+    *dev_table_out = ix->table8.p;
     return PK_OK;
 }
 
@@ -806,7 +844,7 @@ extern "C" int pk_indexer_table_slice_to_device(pk_indexer *ix, void *dev_dst, u
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     if (offset > ix->n || n_bytes > ix->n - offset) return fail(PK_ERR_ARG, "slice outside the table");
     HIPCHK(hipSetDevice(ix->device));
-    HIPCHK(hipMemcpy(dev_dst, ix->table8 + offset, n_bytes, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(dev_dst, ix->table8.p + offset, n_bytes, hipMemcpyDeviceToDevice));
     return PK_OK;
 }
 
@@ -857,25 +895,18 @@ extern "C" int pk_count_fasta(const uint8_t *fasta, uint64_t n_bytes, int k, uin
 extern "C" int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device) {
     if (!hist256_out || (n && !table)) return fail(PK_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(device));
-    unsigned long long *d_hist = nullptr;
-    uint8_t *d_t = nullptr;
-    HIPCHK(hipMalloc(&d_hist, 256 * sizeof(unsigned long long)));
-    hipError_t e = hipMalloc(&d_t, std::max<uint64_t>(n, 16));
-    if (e != hipSuccess) { hipFree(d_hist); return fail(PK_ERR_HIP, "hipMalloc(table) failed: %s", hipGetErrorString(e)); }
-    int rc = PK_OK;
+    DevBuf<unsigned long long> d_hist;
+    DevBuf<uint8_t> d_t;
     unsigned long long h[256];
-    if (hipMemset(d_hist, 0, 256 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemcpy(d_t, table, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(PK_ERR_HIP, "upload failed");
-    if (!rc) {
-        launch_hist8(d_t, n, d_hist, 0);
-        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, d_hist, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(PK_ERR_HIP, "histogram kernel failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    hipFree(d_t); hipFree(d_hist);
-    if (rc) return rc;
-    uint64_t nz = 0;
-    for (int v = 1; v < 256; v++) { hist256_out[v] = h[v]; nz += h[v]; }
-    hist256_out[0] = n - nz;
+    int rc;
+    if ((rc = d_hist.reserve(sizeof h))) return rc;
+    if ((rc = d_t.reserve(std::max<uint64_t>(n, 16)))) return rc;
+    if (hipMemset(d_hist.p, 0, sizeof h) != hipSuccess || hipMemcpy(d_t.p, table, n, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(PK_ERR_HIP, "upload failed");
+    launch_hist8(d_t.p, n, d_hist.p, 0);
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, d_hist.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(PK_ERR_HIP, "histogram kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    hist_with_zeros(h, n, hist256_out);
     return PK_OK;
 }
 
@@ -912,7 +943,7 @@ struct GramCtx {
     const uint8_t **d_gtab = nullptr;          // the tables of each pair group of a spectrum pass (spectrum_groups(128) x 16)
     std::vector<const uint8_t *> h_gtab;
     uint8_t *d_occ = nullptr;                  // occupancy bytes of an occgram pass over more than 16 tables (grown on demand)
-    uint64_t occ_cap = 0;
+    size_t occ_cap = 0;
 };
 GramCtx g_gram[MAX_DEVICES];
 
@@ -1042,16 +1073,9 @@ extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N
     if (N < 2 || N > 128) return fail(PK_ERR_ARG, "an occgram pass takes 2 to 128 tables (got %d)", N);
     if (!dev_accum) return fail(PK_ERR_ARG, "null accumulator");
     auto grow_scratch = [&](GramCtx &c) -> int {
-        const uint64_t need = occgram_scratch_bytes(N, n_slice);
-        if (need > c.occ_cap) {
-            HIPCHK(hipStreamSynchronize(c.stream));
-            if (c.d_occ) HIPCHK(hipFree(c.d_occ));
-            c.d_occ = nullptr;
-            c.occ_cap = 0;
-            HIPCHK(hipMalloc(&c.d_occ, need));
-            c.occ_cap = need;
-        }
-        return PK_OK;
+        const size_t need = occgram_scratch_bytes(N, n_slice);
+        if (need > c.occ_cap) HIPCHK(hipStreamSynchronize(c.stream));
+        return reserve_exact((void **)&c.d_occ, &c.occ_cap, need);
     };
     return timed_pass("occgram", dev_tables, N, device, kernel_seconds_out, grow_scratch, [&](GramCtx &c) {
         return launch_occgram(dev_tables, N, n_slice, (unsigned long long *)dev_accum, c.d_ptrs, c.d_occ, c.stream);
@@ -1083,20 +1107,22 @@ extern "C" int pk_gram(const uint8_t *const *tables, int N, uint64_t n, int min_
             uint64_t sub = hi - lo;
             const uint64_t budget = (uint64_t)(free_b * 0.8);
             if ((uint64_t)N * (sub + 64) > budget) sub = std::max<uint64_t>(1 << 20, (budget / N - 64) & ~2047ULL);
-            std::vector<void *> dptr(N, nullptr);
-            int r = PK_OK;
-            for (int i = 0; i < N && !r; i++)
-                if (hipMalloc(&dptr[i], std::min(sub, hi - lo) + 64) != hipSuccess) r = fail(PK_ERR_HIP, "hipMalloc(table slice) failed");
-            std::vector<uint64_t> one((size_t)N * N);
-            for (uint64_t a = lo; a < hi && !r; a += sub) {
-                const uint64_t b = std::min(hi, a + sub);
-                for (int i = 0; i < N && !r; i++)
-                    if (hipMemcpy(dptr[i], tables[i] + a, b - a, hipMemcpyHostToDevice) != hipSuccess) r = fail(PK_ERR_HIP, "table upload failed");
-                if (!r) r = pk_gram_device_partial((const void *const *)dptr.data(), N, b - a, min_count, max_count, one.data(), nullptr, devices[d], nullptr);
-                if (!r) for (size_t i = 0; i < one.size(); i++) parts[d][i] += one[i];
+            std::vector<DevBuf<uint8_t>> slices(N);
+            std::vector<const void *> dptr(N, nullptr);
+            int r;
+            for (int i = 0; i < N; i++) {
+                if ((r = slices[i].reserve(std::min(sub, hi - lo) + 64))) return r;
+                dptr[i] = slices[i].p;
             }
-            for (auto p : dptr) hipFree(p);
-            return r;
+            std::vector<uint64_t> one((size_t)N * N);
+            for (uint64_t a = lo; a < hi; a += sub) {
+                const uint64_t b = std::min(hi, a + sub);
+                for (int i = 0; i < N; i++)
+                    if (hipMemcpy(slices[i].p, tables[i] + a, b - a, hipMemcpyHostToDevice) != hipSuccess) return fail(PK_ERR_HIP, "table upload failed");
+                if ((r = pk_gram_device_partial(dptr.data(), N, b - a, min_count, max_count, one.data(), nullptr, devices[d], nullptr))) return r;
+                for (size_t i = 0; i < one.size(); i++) parts[d][i] += one[i];
+            }
+            return PK_OK;
         };
         rcs[d] = run();
         if (rcs[d]) errs[d] = g_err;                       // g_err is thread-local: carry the message back
