@@ -257,7 +257,8 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l2_tiles(L2 *__restrict__ tile_
         run = tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) { carry->l2 = run; carry->n_recs = run.rec; }
+    // (deep windows: what the previous feed left as the stream's last bases is what this feed starts from)
+    if (threadIdx.x == 0) { carry->l2 = run; carry->n_recs = run.rec; if (km1 > 16u) carry->deep_in = carry->deep_out; }
 }
 __global__ __launch_bounds__(SCAN_T) void k_scan_l2_apply(const L2 *__restrict__ in, uint32_t n, const L2 *__restrict__ tile_seed,
                                                           L2 *__restrict__ out_state, uint32_t km1) {

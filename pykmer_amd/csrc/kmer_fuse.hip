@@ -48,13 +48,51 @@ __device__ __forceinline__ uint32_t smear_up(uint32_t x, uint32_t n) {
     return acc;
 }
 
+// DEEP: the 32 valid bases of the stream in front of slot c, newest at the top (fields 31 .. 0, older bases lower), whatever
+// restarts lie among them -- the run state says how many may be used.  They are the last bases of the slots before c; where
+// this feed's slots run out (c == 0, a feed that opens with blank chunks, a feed of a few bytes) the rest are the last
+// bases of the feeds before it, which k_deep_tail left in `stream_before` in the same layout.
+__device__ __forceinline__ unsigned long long bases_before_slot(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ n_bases, uint32_t c,
+                                                                const unsigned long long *__restrict__ stream_before) {
+    unsigned long long before = 0;
+    uint32_t have = 0;
+    for (uint32_t cc = c; cc > 0 && have < 32u;) {
+        cc--;
+        const uint32_t n_cc = n_bases[cc];
+        const uint32_t take = min(n_cc, 32u - have);
+        if (take == 0) continue;
+        const uint32_t p0 = n_cc - take, d0 = p0 >> 4, sh = 2u * (p0 & 15u);
+        const uint32_t *pw = codes + (uint64_t)cc * SLOT_CODE_WORDS;
+        const unsigned long long w01 = ((unsigned long long)pw[min(d0 + 1u, SLOT_CODE_WORDS - 1u)] << 32) | pw[d0];
+        const unsigned long long w2 = pw[min(d0 + 2u, SLOT_CODE_WORDS - 1u)];
+        unsigned long long x = sh ? ((w01 >> sh) | (w2 << (64u - sh))) : w01;
+        if (take < 32u) x &= (1ull << (2u * take)) - 1ull;
+        before |= x << (2u * (32u - have - take));                                  // older bases lower
+        have += take;
+    }
+    if (have < 32u) before |= *stream_before >> (2u * have);
+    return before;
+}
+
+// Behind the squeeze of a deep-window feed (k = 19, 21): the last 32 valid bases of the stream up to the end of this feed,
+// for the first slots of the next one.  `before_in` is what the feed found (the structure pass's scan moves the previous
+// feed's result there once per feed, so a repeated attempt starts from the same value).  Nothing is written when the
+// squeeze backed out: the slots then hold an earlier text, and the squeeze runs again.
+__global__ void k_deep_tail(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ n_bases, uint32_t n_chunks,
+                            const unsigned long long *__restrict__ before_in, unsigned long long *__restrict__ before_out,
+                            const uint32_t *__restrict__ flags) {
+    if (threadIdx.x != 0 || flags[0]) return;
+    *before_out = bases_before_slot(codes, n_bases, n_chunks, before_in);
+}
+
 // NT threads, PER bases each (NT * PER = 16384 = one slot); NB = LDS room for level-1 digits; HS = hot-key slots.
 // COUNT: tally only -- `tally` counters in LDS ([n_tally], the final-bucket digit where there are two levels and
 // <= 2^14 final buckets, the level-1 digit otherwise), written out as one row per workgroup.
 // SLICED: the table holds one of 2^slice_bits address ranges; k-mers of the others are dropped, the rest are numbered
 // inside the range.  DEEP (k = 19, 21; always sliced, 1024 x 16): the k-1 bases behind a thread's first one no longer
 // fit one dword, so two are carried and the windows are cut from 96 bits; in front of a slot they come from the slots
-// before it (the chunk state's 32 bits hold 16 bases).
+// before it, and in front of the feed's first slots from the feeds before it (deep_before; the chunk state's 32 bits hold
+// 16 bases).
 template <typename KT, bool COUNT, int NT, int PER, int NB, uint32_t HS, bool SLICED, bool DEEP, uint32_t KC = 0>
 __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
                                                   const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state,
@@ -62,7 +100,8 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
                                                   uint32_t *__restrict__ cursor1, const uint32_t *__restrict__ cap_end, uint32_t dump,
                                                   uint32_t *__restrict__ flags, uint32_t tally_shift, uint32_t n_tally,
                                                   uint32_t *__restrict__ tally_rows, unsigned long long *__restrict__ side,
-                                                  unsigned long long *__restrict__ side_n, uint64_t side_cap) {
+                                                  unsigned long long *__restrict__ side_n, uint64_t side_cap,
+                                                  const unsigned long long *__restrict__ deep_before) {
     static_assert(NT * PER == TILE && PER % 16 == 0, "one slot per workgroup");
     static_assert(!DEEP || (PER == 16 && sizeof(KT) == 8 && SLICED), "deep windows: 64-bit k-mers, one code dword per thread, sliced table");
     constexpr int NW = PER / 16;                                          // code dwords per thread
@@ -194,24 +233,7 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
                 // Up to 16 are in the state's bits; more than that are the last bases of the slots before this one.
                 const uint32_t len = (me.st_flags >> 8) & 0xffu;
                 unsigned long long before = (unsigned long long)revpairs32(me.st_bits) << 32;     // newest base at the top
-                if (len > 16u) {
-                    uint32_t have = 0;
-                    before = 0;
-                    for (uint32_t cc = c; cc > 0 && have < 32u;) {
-                        cc--;
-                        const uint32_t n_cc = n_bases[cc];
-                        const uint32_t take = min(n_cc, 32u - have);
-                        if (take == 0) continue;
-                        const uint32_t p0 = n_cc - take, d0 = p0 >> 4, sh = 2u * (p0 & 15u);
-                        const uint32_t *pw = codes + (uint64_t)cc * SLOT_CODE_WORDS;
-                        const unsigned long long w01 = ((unsigned long long)pw[min(d0 + 1u, SLOT_CODE_WORDS - 1u)] << 32) | pw[d0];
-                        const unsigned long long w2 = pw[min(d0 + 2u, SLOT_CODE_WORDS - 1u)];
-                        unsigned long long x = sh ? ((w01 >> sh) | (w2 << (64u - sh))) : w01;
-                        if (take < 32u) x &= (1ull << (2u * take)) - 1ull;
-                        before |= x << (2u * (32u - have - take));                                  // older bases lower
-                        have += take;
-                    }
-                }
+                if (len > 16u) before = bases_before_slot(codes, n_bases, c, deep_before);
                 const uint32_t va = (uint32_t)(before >> 32), vb = (uint32_t)before;              // the 16 right before the slot, the 16 before those
                 if (t == 0) { prev0 = va; pprev0 = vb; } else { pprev0 = va; }
                 r_before = (len != 0u && len < km1) ? (1u << (32u - len)) : 0u;
@@ -555,14 +577,15 @@ static void launch_ws(const PartPlan &pl, uint32_t grid, size_t lds, hipStream_t
 // sampling launch + bucket layout.  tally_rows: COUNT_WGS x n_tally words of scratch; tally_tot: n_tally words.
 void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl,
                       uint32_t stride, uint32_t *tally_rows, uint32_t *tally_tot, uint32_t *bucket_base, uint32_t *cursor1,
-                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags, hipStream_t s) {
+                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags,
+                      const unsigned long long *deep_before, hipStream_t s) {
     const uint32_t n_sampled = (pl.n_chunks + stride - 1) / stride;
     const uint32_t grid = n_sampled < COUNT_WGS ? n_sampled : COUNT_WGS;
     const uint32_t n_tally = pl.n_tally;
     const uint32_t tally_shift = n_tally > pl.B1 ? pl.fb_bits : pl.addr_bits - pl.b1;
     launch_ws<true>(pl, grid, (size_t)n_tally * 4, s, codes, restarts, n_bases, st2, pl, n_sampled, stride, (void *)nullptr, (uint32_t *)nullptr,
                     (const uint32_t *)nullptr, 0u, flags, tally_shift, n_tally, tally_rows, (unsigned long long *)nullptr,
-                    (unsigned long long *)nullptr, (uint64_t)0);
+                    (unsigned long long *)nullptr, (uint64_t)0, deep_before);
     hipLaunchKernelGGL(k_tally_sum, dim3((n_tally + 255u) / 256u), dim3(256), 0, s, (const uint32_t *)tally_rows, grid, n_tally, tally_tot);
     hipLaunchKernelGGL(k_provision, dim3(1), dim3(1024), 0, s, (const uint32_t *)tally_tot, n_tally, pl, n_sampled, stride, bucket_base, cursor1, cap_end,
                        final_start, cursor2, cap2_end, flags);
@@ -570,12 +593,18 @@ void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uin
 
 void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
                       uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap, hipStream_t s) {
+                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
+                      const unsigned long long *deep_before, hipStream_t s) {
     const uint32_t dump = (uint32_t)pl.capacity1;
     launch_ws<false>(pl, pl.n_wg1, pl.k > 15 ? SCATTER_LDS_WIDE : FUSE_LDS_NARROW, s, codes, restarts, n_bases, st2, pl, pl.n_chunks, 1u, out1, cursor1,
-                     cap_end, dump, flags, 0u, 0u, (uint32_t *)nullptr, side, side_n, side_cap);
+                     cap_end, dump, flags, 0u, 0u, (uint32_t *)nullptr, side, side_n, side_cap, deep_before);
     hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)cursor1, bucket_base, cap_end, pl, bucket_end, wg2_start,
                        (const uint32_t *)flags);
+}
+
+void launch_deep_tail(const uint32_t *codes, const uint32_t *n_bases, uint32_t n_chunks, const unsigned long long *before_in,
+                      unsigned long long *before_out, const uint32_t *flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_deep_tail, dim3(1), dim3(64), 0, s, codes, n_bases, n_chunks, before_in, before_out, flags);
 }
 
 }  // namespace pk

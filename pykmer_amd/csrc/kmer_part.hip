@@ -820,7 +820,7 @@ extern "C" int pk_diag_occupancy(int which) {
 // caller reads the flags word back to learn whether the layout held (flags[0] == 0).
 int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint32_t stride, uint8_t *ws, const PartWorkspace &lay, uint8_t *table8,
                        hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
-                       unsigned long long *hist, unsigned long long *bucket_hist, bool armed) {
+                       unsigned long long *hist, unsigned long long *bucket_hist, bool armed, const unsigned long long *deep_before) {
     const uint32_t *codes = (const uint32_t *)(ws + lay.codes), *restarts = (const uint32_t *)(ws + lay.restarts);
     const uint32_t *n_bases = (const uint32_t *)(ws + lay.n_bases);
     uint32_t *tally_rows = (uint32_t *)(ws + lay.tally_rows), *tally_tot = (uint32_t *)(ws + lay.tally_tot);
@@ -840,9 +840,9 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
     if (pl.k <= 15 && pl.b2 && pl.addr_bits - pl.b1 > 24u) return -3;                           // 3-byte level-1 records (part_common.h)
     if (!armed && hipMemsetAsync(side_n, 0, PART_FLAG_WORDS * 4, s) != hipSuccess) return -2;   // side-list length + flags
     launch_provision(codes, restarts, n_bases, st2, pl, stride, tally_rows, tally_tot, bucket_base, cursor1, cap_end, final_start, cursor2, cap2_end,
-                     flags, s);
+                     flags, deep_before, s);
     if (ev_sort_begin) hipEventRecord(ev_sort_begin, s);
-    launch_walk_sort(codes, restarts, n_bases, st2, pl, out1, cursor1, cap_end, flags, bucket_base, bucket_end, wg2_start, side, side_n, lay.side_cap, s);
+    launch_walk_sort(codes, restarts, n_bases, st2, pl, out1, cursor1, cap_end, flags, bucket_base, bucket_end, wg2_start, side, side_n, lay.side_cap, deep_before, s);
     if (ev_sort_end) hipEventRecord(ev_sort_end, s);
     const uint16_t *final_recs = (const uint16_t *)out1;
     const uint32_t *k6_start = bucket_base, *k6_end = bucket_end;        // b2 == 0: the level-1 buckets are the final ones

@@ -527,6 +527,9 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
             launch_squeeze(f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, (uint32_t)ix->k, n_chunks, pl.n_wg0, pl.G,
                            (uint32_t *)(ws + lay.codes), (uint32_t *)(ws + lay.restarts), (uint32_t *)(ws + lay.n_bases), ix->recs.p, ix->recs_cap(), carry,
                            flags, ix->stream);
+            if (ix->k > 17)                                      // deep windows: the stream's last bases, for the next feed's first slots
+                launch_deep_tail((const uint32_t *)(ws + lay.codes), (const uint32_t *)(ws + lay.n_bases), n_chunks,
+                                 (const unsigned long long *)&carry->deep_in, (unsigned long long *)&carry->deep_out, flags, ix->stream);
             HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
             armed = true;
         }
@@ -534,7 +537,7 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         // returns untouched (flags[0] = 1) and the passes behind the squeeze are repeated with exact sizes -- on the text
         // the squeeze of this feed left, so only once that squeeze has run in full (flags[0] = 2 is handled first)
         if (launch_partitioned(ix->c_l2s.p, n_bytes, pl, stride, ws, lay, ix->table8.p, ix->stream, ev.sort_begin, ev.sort_end, ev.part_end,
-                               ix->table_fresh, ix->tail.p->hist, ix->hist_rep.p, armed))
+                               ix->table_fresh, ix->tail.p->hist, ix->hist_rep.p, armed, (const unsigned long long *)&carry->deep_in))
             return fail(PK_ERR_HIP, "partition pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
         HIPCHK(hipEventRecord(ev.bucket_end, ix->stream));
         volatile uint32_t *got = ix->pin->flags;

@@ -23,6 +23,9 @@ struct Carry {
     uint64_t n_recs;     // = l2.rec, mirrored for the host read-back
     uint64_t total_bp;   // sum of seq_len over all records
     uint64_t num_kmers;  // valid windows counted
+    // k = 19, 21: the last 32 valid bases of the stream, newest at the top, at the start of the feed being counted and at
+    // its end (k_deep_tail).  The run state above says how many of them a window may use; its 32 bits hold only 16.
+    uint64_t deep_in, deep_out;
 };
 
 void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_chunks, hipStream_t s);
@@ -69,15 +72,19 @@ void part_set_attributes();
 void fuse_set_attributes();
 void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl,
                       uint32_t stride, uint32_t *tally_rows, uint32_t *tally_tot, uint32_t *bucket_base, uint32_t *cursor1,
-                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags, hipStream_t s);
+                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags,
+                      const unsigned long long *deep_before, hipStream_t s);
 void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
                       uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap, hipStream_t s);
+                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
+                      const unsigned long long *deep_before, hipStream_t s);
+void launch_deep_tail(const uint32_t *codes, const uint32_t *n_bases, uint32_t n_chunks, const unsigned long long *before_in,
+                      unsigned long long *before_out, const uint32_t *flags, hipStream_t s);
 // `armed`: the side-list length and the flags word were already zeroed on the stream (launch_scan_l1 does it for the first
-// attempt of a feed); a repeat after an overflow zeroes them itself.
+// attempt of a feed); a repeat after an overflow zeroes them itself.  `deep_before`: Carry::deep_in (read by k = 19, 21 only).
 int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint32_t stride, uint8_t *ws, const PartWorkspace &lay, uint8_t *table8,
                        hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
-                       unsigned long long *hist, unsigned long long *hist_replicas, bool armed);
+                       unsigned long long *hist, unsigned long long *hist_replicas, bool armed, const unsigned long long *deep_before);
 constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
 // side_n (u64) + flags[4], zeroed together.  flags[0]: 2 = the squeeze backed out (record array too small), 1 = a bucket
 // room or a layout total overflowed; every kernel behind the squeeze returns at once when it finds it raised, so the first

@@ -193,5 +193,197 @@ def skewed_fasta_with_records(n_bp: int, unit_len: int, n_records: int, seed: in
     return headers_on_lines(text, head_len, 60, np.unique(pick), tag=b"s")
 
 
+def interspersed_repeat(n_copies, unit_len, spacer, seed):
+    """`n_copies` of one unit, each followed by `spacer` random bases: every k-mer of the unit occurs n_copies times, but
+    never with a period of 1-3 bases (the hot-key path does not see it) and never as a long run of records in one bucket."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    unit = acgt[rng.integers(0, 4, size=unit_len)]
+    parts = []
+    for _ in range(n_copies):
+        parts.append(unit)
+        parts.append(acgt[rng.integers(0, 4, size=spacer)])
+    seq = np.concatenate(parts)
+    seq = seq[: seq.size // 60 * 60]
+    return b">interspersed\n" + _lines(seq, 60)
+
+
+SOUP_ALPHABET = b"ACGTacgtNn>> \t\r\n\n\n\x0b\x0cXR"
+
+
+def byte_soup(n: int, seed: int) -> bytes:
+    """Random bytes over the FASTA-relevant alphabet (the soup of test_random_structure_fuzz), behind one header so that
+    none of it is text in front of the first record."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    alphabet = np.frombuffer(SOUP_ALPHABET, dtype=np.uint8)
+    w = rng.random(alphabet.size) ** 3
+    return b">soup\n" + alphabet[rng.choice(alphabet.size, size=n, p=w / w.sum())].tobytes()
+
+
+# ------------------------------------------------------------------ deep windows (k = 19, 21) ------------------------
+# The window that reaches furthest back across a seam (a 16 KiB slot boundary, or the end of a feed) is the one that
+# needs the most history.  The builders below write SEAM_MOTIF where that window begins, so that its canonical k-mer --
+# the forward one unless the window happens to end in the motif's reverse complement -- has the same leading bases at
+# every seam and the seams of a text share one address slice (the tests assert it from the oracle).
+SEAM_MOTIF = b"ACGA"
+
+
+def _rand_bases(rng, n: int) -> bytes:
+    import numpy as np
+    return np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n)].tobytes()
+
+
+def deep_seam_fasta(k: int, seed: int = 19, pad_to_chunks: int = 0, chunk: int = 16384):
+    """(text, sites): one record whose 16 KiB chunk boundaries meet every carried run the deep-window kernel tells apart.
+    `sites` lists (kind, d, offset): at byte `offset` (a multiple of `chunk`) a base follows that has exactly `d` valid
+    bases behind it since the last restart -- or, for the shapes, a long run whose newest bases lie some slots back:
+
+      "line", d = 0 .. k + 3           (not a boundary) d bases behind a line start inside a long run: a place to cut a feed;
+      "N" / "header", d = 0 .. k + 3   the restart is an N / a header line, d bases before the boundary;
+      "newlines" / "blanks"            a whole chunk of line terminators / of trailing blanks in front (no base in it);
+      "thin", d = j                    two empty chunks, a chunk with j bases, an empty chunk: history from >= 3 slots;
+      "long_header"                    a 40 000-byte header line in front: three chunks without a base and a restart;
+      "one_base_lines", "crlf"         lines of one base (8192 bases per slot) / CR LF lines across three boundaries.
+
+    Where the oldest window that crosses the boundary begins, the text holds SEAM_MOTIF.  `pad_to_chunks`: plain sequence
+    lines are appended until the text has that many chunks."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = bytearray(b">deep_seams\n")
+    sites = []
+
+    def fill_to(target):                                    # sequence lines of <= 60 bases up to exactly `target`, ending in a newline
+        n = target - len(out)
+        assert n >= 1, (target, len(out))
+        while n > 0:
+            m = min(61, n)
+            out.extend(_rand_bases(rng, m - 1) + b"\n")
+            n -= m
+
+    def boundary(margin=400):
+        return (len(out) + margin + chunk - 1) // chunk * chunk
+
+    def run_up_to(B, back=k - 1, n=30):                      # n bases on one line that end right at B, the motif `back` bases before B
+        fill_to(B - n)
+        tail = bytearray(_rand_bases(rng, n))
+        if back >= len(SEAM_MOTIF):
+            tail[n - back: n - back + len(SEAM_MOTIF)] = SEAM_MOTIF
+        out.extend(tail)
+        assert len(out) == B
+
+    fill_to(12 + 61 * 120)                                   # plain lines of 60 bases: line i begins at 12 + 61 i
+    for d in range(0, k + 4):                                # "line": d bases behind a line start inside a long run
+        cut = 12 + 61 * (5 + 4 * d) + d
+        at, left = cut, k - 1
+        while left:                                          # k - 1 bases back, over the newline
+            at -= 1
+            left -= out[at] != 10
+        for ch in SEAM_MOTIF:
+            at += out[at] == 10
+            out[at] = ch
+            at += 1
+        sites.append(("line", d, cut))
+    for kind in ("N", "header"):
+        for d in range(0, k + 4):
+            B = boundary()
+            marker = b"N" if kind == "N" else b">h%d\n" % d
+            if kind == "N":
+                fill_to(B - d - 1 - 30)
+                out.extend(_rand_bases(rng, 30))
+            else:
+                fill_to(B - d - len(marker))
+            run = bytearray(_rand_bases(rng, d + 40))        # d bases, the boundary, 40 more on the same line
+            at = max(0, d - (k - 1))                         # where the oldest window across the boundary begins
+            run[at: at + len(SEAM_MOTIF)] = SEAM_MOTIF
+            out.extend(marker + bytes(run) + b"\n")
+            assert len(out) == B + 41
+            sites.append((kind, d, B))
+    for kind, gap in (("newlines", b"\n" * chunk), ("blanks", b" " * (chunk - 1) + b"\n")):
+        B = boundary()
+        run_up_to(B)
+        out.extend(gap + _rand_bases(rng, 40) + b"\n")
+        sites.append((kind, k - 1, B + chunk))
+    for j in (1, 2, 7, 15, 16, 17, 20, 31):
+        B = boundary()
+        run_up_to(B, k - 1 - j)                              # the oldest window across the last boundary: j bases of the thin chunk + k-1-j from here
+        thin = bytearray(_rand_bases(rng, j))
+        if 0 <= j - (k - 1) <= j - len(SEAM_MOTIF):
+            thin[j - (k - 1): j - (k - 1) + len(SEAM_MOTIF)] = SEAM_MOTIF
+        out.extend(b"\n" * (2 * chunk) + bytes(thin) + b"\n" * (chunk - j) + b"\n" * chunk + _rand_bases(rng, 40) + b"\n")
+        sites.append(("thin", j, B + 4 * chunk))
+    B = boundary()
+    run_up_to(B - 1)
+    out.extend(b"\n>" + b"H" * 40000 + b"\n")
+    at = len(out)
+    out.extend(SEAM_MOTIF + _rand_bases(rng, 3 * chunk - 40002 - 1 - len(SEAM_MOTIF)) + b"\n")   # the record's first bases, on one line up to a boundary
+    sites.append(("long_header", 0, at))
+    B = boundary()
+    fill_to(B)
+    one = np.empty((3 * chunk // 2, 2), dtype=np.uint8)
+    one[:, 0] = np.frombuffer(_rand_bases(rng, one.shape[0]), dtype=np.uint8)
+    one[:, 1] = 10
+    out.extend(one.tobytes())
+    sites.append(("one_base_lines", k - 1, B + chunk))
+    B = boundary()
+    fill_to(B)
+    while len(out) < B + 3 * chunk:
+        out.extend(_rand_bases(rng, 70) + b"\r\n")
+    sites.append(("crlf", k - 1, B + chunk))
+    fill_to(max(boundary(), pad_to_chunks * chunk - 100))
+    out.extend(_rand_bases(rng, 57))                         # no newline at the end
+    return bytes(out), sites
+
+
+def plain_sequence_fasta(n_bp: int, seed: int = 3, n_at=(), motif_at=()):
+    """One record, its `n_bp` bases on ONE line.  `n_at`: byte offsets that hold an N instead; `motif_at`: byte offsets where
+    SEAM_MOTIF is written.  Bytes: a 7-byte header line, base i at offset 7 + i."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = bytearray(b">plain\n" + _rand_bases(rng, n_bp) + b"\n")
+    for at in motif_at:
+        assert at >= 7
+        out[at: at + len(SEAM_MOTIF)] = SEAM_MOTIF
+    for x in n_at:
+        out[x] = ord("N")
+    return bytes(out)
+
+
+def deep_tandem_fasta(k: int, seed: int, n_runs: int = 12000) -> bytes:
+    """Thousands of tandem runs of period 1, 2 and 3 and of k - 2 .. k + 40 bases, between spacers of 0 .. 5 bases (so they
+    start at every offset of a code word and cross slot boundaries), an N inside some of them; then runs of A, AT, AAG
+    and ACGT long enough to saturate their addresses."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    parts, line = [b">deep_tandems\n"], []
+    for i in range(n_runs):
+        period = 1 + i % 3
+        motif = _rand_bases(rng, period)
+        n = int(rng.integers(k - 2, k + 41))
+        run = bytearray((motif * (n // period + 1))[:n])
+        if i % 7 == 0:
+            run[int(rng.integers(n))] = ord("N")
+        line.append(bytes(run) + _rand_bases(rng, int(rng.integers(0, 6))))
+        if len(line) == 3:
+            parts.append(b"".join(line) + b"\n")
+            line = []
+    parts.append(b"".join(line) + b"\n")
+    parts.append(b">long_runs\n" + b"A" * 40000 + b"\n" + b"AT" * 12000 + b"\n" + b"AAG" * 9000 + b"\n" + b"ACGT" * 7000 + b"\n")
+    return b"".join(parts)
+
+
+def deep_k21_fasta(seed: int = 2121, body_bp: int = 300_000):
+    """The k = 21 slice text: the parser corners of edge_fasta, a synthetic body with tandem repeats, duplications, N gaps
+    and lower case, poly-A (address 0 saturates) and windows whose k-mer AND reverse complement begin with TTTT (the last
+    of 256 slices).  `body_bp`: size of the synthetic body (0: none; even 30 kbp of text leave hardly any of the 256 slices empty)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    body = synth.generate(94, body_bp, 3, pm_tandem=100, pm_dup=100, pm_ngap=30, pm_lower=50)[0] if body_bp else np.zeros(0, dtype=np.uint8)
+    top = b"N".join(b"TTTT" + _rand_bases(rng, 13) + b"AAAA" for _ in range(40))
+    tail = b">polyA\n" + b"A" * 800 + b"\n" + b"ACGT" * 200 + b"\n>top_slice\n" + top + b"\n" + (b"TTTTGCATGCATGCATGAAAA" + b"N") * 300 + b"\n"
+    return edge_fasta() + body.tobytes() + tail
+
+
 def sha256(data) -> str:
     return hashlib.sha256(data).hexdigest()

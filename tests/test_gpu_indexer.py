@@ -8,6 +8,7 @@ import pytest
 
 import inputs
 import oracle
+import slice_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -486,31 +487,13 @@ def test_bucket_overflow_takes_the_exact_relayout(gpu, k, unit_len):
         assert sum(int(np.count_nonzero(table[o:o + step])) for o in range(0, table.size, step)) == u.size
 
 
-def _interspersed_repeat(n_copies, unit_len, spacer, seed):
-    """`n_copies` of one unit, each followed by `spacer` random bases: every k-mer of the unit occurs n_copies times, but
-    never with a period of 1-3 bases (the hot-key path does not see it) and never as a long run of records in one bucket."""
-    rng = np.random.default_rng(seed)
-    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
-    unit = acgt[rng.integers(0, 4, size=unit_len)]
-    parts = []
-    for _ in range(n_copies):
-        parts.append(unit)
-        parts.append(acgt[rng.integers(0, 4, size=spacer)])
-    seq = np.concatenate(parts)
-    seq = seq[: seq.size // 60 * 60]
-    lines = np.empty((seq.size // 60, 61), dtype=np.uint8)
-    lines[:, :60] = seq.reshape(-1, 60)
-    lines[:, 60] = 10
-    return b">interspersed\n" + lines.tobytes()
-
-
 @pytest.mark.parametrize("k", [9, 17])
 def test_byte_counters_wrap_and_are_recounted(gpu, k):
     """Sparse tables count in byte counters (k_bucket_count_bytes).  A k-mer that occurs more than 254 times in a bucket
     visit wraps its byte; the add that sees 255 raises the flag and the bucket is counted again with 16-bit counters
     (`buckets_recounted`).  Second feed of the same text: the bytes come back from HBM already at 255."""
     copies = 300 if k == 9 else 400
-    data = _interspersed_repeat(copies, 70, 20 if k == 9 else 5000, seed=k)
+    data = inputs.interspersed_repeat(copies, 70, 20 if k == 9 else 5000, seed=k)
     assert k != 9 or len(data) < 4 * 8192                                  # k = 9: four final buckets, still "sparse"
     kmers = oracle.kmer_list(data, k)
     u, c = np.unique(kmers, return_counts=True)
@@ -576,18 +559,16 @@ def _retry_inputs(stretch: int):
 
 def _check_retried(ix, data, k, n_slices=1, slice_index=0):
     """finish() of an indexer that was fed `data` (in any cuts) against the oracle: totals, every record field,
-    histogram and table (k = 17 / 19: the non-zero addresses and their number)."""
+    histogram and table (k >= 17: the non-zero addresses and their number, slice_ref.Expect.check)."""
+    if k > 15:
+        exp = slice_ref.Expect(data, k, n_slices)
+        exp.check(ix, slice_index, full_table=True)
+        return exp.want
     fin = ix.finish()
     size = 4 ** k // n_slices
-    if k <= 15:
-        want = oracle.count_fasta(data, k)
-        part = want["table"][slice_index * size:(slice_index + 1) * size]
-        u, sat = np.flatnonzero(part), part[part != 0]
-    else:
-        kmers, want = oracle.kmer_list(data, k, records=True)
-        u, c = np.unique(kmers, return_counts=True)
-        sel = u // np.uint64(size) == np.uint64(slice_index)
-        u, sat = (u[sel] - np.uint64(slice_index * size)).astype(np.int64), np.minimum(c[sel], 255).astype(np.uint8)
+    want = oracle.count_fasta(data, k)
+    part = want["table"][slice_index * size:(slice_index + 1) * size]
+    sat = part[part != 0]
     assert fin["num_kmers"] == want["num_kmers"]
     assert fin["total_bp"] == want["total_bp"]
     assert fin["n_records"] == len(want["records"])
@@ -597,13 +578,7 @@ def _check_retried(ix, data, k, n_slices=1, slice_index=0):
     h = fin["hist256"]
     assert int(h.sum()) == size
     assert np.array_equal(h[1:], np.bincount(sat, minlength=256)[1:].astype(np.uint64))
-    table = ix.table_to_host()
-    if k <= 15:
-        assert np.array_equal(table, part)
-    else:
-        assert np.array_equal(table[u], sat)
-        step = 1 << 30
-        assert sum(int(np.count_nonzero(table[o:o + step])) for o in range(0, table.size, step)) == u.size
+    assert np.array_equal(ix.table_to_host(), part)
     return want
 
 
@@ -613,12 +588,12 @@ def _busiest_slice(data, k, n_slices):
     return int(np.bincount((kmers // np.uint64(4 ** k // n_slices)).astype(np.int64), minlength=n_slices).argmax())
 
 
-@pytest.mark.parametrize("k,n_slices", [(11, 1), (13, 1), (15, 1), (17, 1), (15, 4), (19, 16)])
+@pytest.mark.parametrize("k,n_slices", [(11, 1), (13, 1), (15, 1), (17, 1), (15, 4), (19, 16), (21, 256)])
 def test_record_overflow_after_a_relayout_feed(gpu, k, n_slices):
     """Feed 1 defeats the bucket sample (relayout); feed 2 has the same byte length -- the same workspace layout -- and far
     more records than the array holds, so its squeeze backs out.  Nothing of feed 2 may then be counted from what the
     workspace still holds of feed 1 (its squeezed text overflows the same sampled rooms again): feed 2's records must be
-    squeezed and counted, feed 1's k-mers only once.  (k = 19: the deep windows of k_walk_sort, one slice of sixteen.)"""
+    squeezed and counted, feed 1's k-mers only once.  (k = 19, 21: the deep windows of k_walk_sort, one slice of 16 / of 256.)"""
     skewed, dense = _retry_inputs(1024 if k >= 17 else 2048)
     data = skewed + dense
     slice_index = _busiest_slice(skewed, k, n_slices) if n_slices > 1 else 0

@@ -116,6 +116,29 @@ def test_c_and_python_oracles_agree_on_fuzz():
             assert [int(x) for x in c["records"]["seq_len"]] == [e[1] for e in everything]
 
 
+@pytest.mark.parametrize("k", [17, 19, 21])
+def test_c_oracle_matches_python_windows_at_deep_k(k):
+    """The goldens pin the C oracle at k <= 17.  k = 19 and 21 have no reference output anywhere, so the k-mer list the
+    GPU tests compare with (oracle.kmer_list, u64 arithmetic in C) is pinned here against the canonical minimum of
+    pyoracle.windows (Python integers, indexer.py:130-160, 341) on the parser corners of edge_fasta and a few kbp of byte
+    soup: every k-mer in text order, and every record."""
+    data = inputs.edge_fasta() + b"\n" + inputs.byte_soup(6000, seed=k)
+    kmers, got = oracle.kmer_list(data, k, records=True)
+    want, recs = [], []
+    for name, seq, seq_len in pyoracle.records(data.decode("utf-8")):
+        n = 0
+        for _, fwd, rev in pyoracle.windows(seq, k):
+            want.append(fwd if fwd < rev else rev)
+            n += 1
+        recs.append((name, seq_len, n))
+    assert len(want) > 10_000 and max(want) >= 4 ** k // 2
+    assert kmers.dtype == np.uint64 and kmers.tolist() == want
+    assert got["num_kmers"] == len(want) and got["total_bp"] == sum(r[1] for r in recs)
+    r = got["records"]
+    assert [data[int(o):int(o) + int(ln)].decode("utf-8") for o, ln in zip(r["name_off"], r["name_len"])] == [x[0] for x in recs]
+    assert r["seq_len"].tolist() == [x[1] for x in recs] and r["n_valid_kmers"].tolist() == [x[2] for x in recs]
+
+
 @pytest.mark.parametrize("tag", ["default", "min2", "max3", "min2max5"])
 def test_merge_oracle_matches_reference(manifest, tag):
     """G7: matrix written by the reference's merger.py for 13 reference-indexed tables (off-diagonal)."""
