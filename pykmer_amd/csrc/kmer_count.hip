@@ -314,10 +314,11 @@ void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_
     hipLaunchKernelGGL(k_chunk_l1, dim3((n_chunks + WG / 64 - 1) / (WG / 64)), dim3(WG), 0, s, fasta, n, n_chunks, chunk_l1);
 }
 // tile_ws: scratch for ceil(n_chunks / 1024) summaries of the respective type
-void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, uint32_t *zero_words, uint32_t n_zero, hipStream_t s) {
+void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, PartSignals *zeroed, hipStream_t s) {
+    static_assert(sizeof(PartSignals) % 4 == 0 && sizeof(PartSignals) / 4 <= SCAN_T, "k_scan_l1_tiles zeroes one word per thread");
     const uint32_t n_tiles = (n_chunks + SCAN_T - 1) / SCAN_T;
     hipLaunchKernelGGL(k_scan_l1_reduce, dim3(n_tiles), dim3(SCAN_T), 0, s, in, n_chunks, tile_ws);
-    hipLaunchKernelGGL(k_scan_l1_tiles, dim3(1), dim3(SCAN_T), 0, s, tile_ws, n_tiles, carry, zero_words, n_zero);
+    hipLaunchKernelGGL(k_scan_l1_tiles, dim3(1), dim3(SCAN_T), 0, s, tile_ws, n_tiles, carry, (uint32_t *)zeroed, (uint32_t)(sizeof(PartSignals) / 4));
     hipLaunchKernelGGL(k_scan_l1_apply, dim3(n_tiles), dim3(SCAN_T), 0, s, in, n_chunks, (const L1 *)tile_ws, out);
 }
 void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd, uint32_t n_chunks,

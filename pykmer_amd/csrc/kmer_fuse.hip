@@ -574,37 +574,33 @@ static void launch_ws(const PartPlan &pl, uint32_t grid, size_t lds, hipStream_t
     }
 }
 
-// sampling launch + bucket layout.  tally_rows: COUNT_WGS x n_tally words of scratch; tally_tot: n_tally words.
-void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl,
-                      uint32_t stride, uint32_t *tally_rows, uint32_t *tally_tot, uint32_t *bucket_base, uint32_t *cursor1,
-                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags,
-                      const unsigned long long *deep_before, hipStream_t s) {
+// sampling launch + bucket layout
+void launch_provision(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint32_t stride, const Carry *carry, hipStream_t s) {
     const uint32_t n_sampled = (pl.n_chunks + stride - 1) / stride;
     const uint32_t grid = n_sampled < COUNT_WGS ? n_sampled : COUNT_WGS;
     const uint32_t n_tally = pl.n_tally;
     const uint32_t tally_shift = n_tally > pl.B1 ? pl.fb_bits : pl.addr_bits - pl.b1;
-    launch_ws<true>(pl, grid, (size_t)n_tally * 4, s, codes, restarts, n_bases, st2, pl, n_sampled, stride, (void *)nullptr, (uint32_t *)nullptr,
-                    (const uint32_t *)nullptr, 0u, flags, tally_shift, n_tally, tally_rows, (unsigned long long *)nullptr,
-                    (unsigned long long *)nullptr, (uint64_t)0, deep_before);
-    hipLaunchKernelGGL(k_tally_sum, dim3((n_tally + 255u) / 256u), dim3(256), 0, s, (const uint32_t *)tally_rows, grid, n_tally, tally_tot);
-    hipLaunchKernelGGL(k_provision, dim3(1), dim3(1024), 0, s, (const uint32_t *)tally_tot, n_tally, pl, n_sampled, stride, bucket_base, cursor1, cap_end,
-                       final_start, cursor2, cap2_end, flags);
+    launch_ws<true>(pl, grid, (size_t)n_tally * 4, s, b.codes, b.restarts, b.n_bases, st2, pl, n_sampled, stride, (void *)nullptr, (uint32_t *)nullptr,
+                    (const uint32_t *)nullptr, 0u, b.flags, tally_shift, n_tally, b.tally_rows, (unsigned long long *)nullptr,
+                    (unsigned long long *)nullptr, (uint64_t)0, (const unsigned long long *)&carry->deep_in);
+    hipLaunchKernelGGL(k_tally_sum, dim3((n_tally + 255u) / 256u), dim3(256), 0, s, (const uint32_t *)b.tally_rows, grid, n_tally, b.tally_tot);
+    hipLaunchKernelGGL(k_provision, dim3(1), dim3(1024), 0, s, (const uint32_t *)b.tally_tot, n_tally, pl, n_sampled, stride, b.bucket_base, b.cursor1,
+                       b.cap_end, b.final_start, b.cursor2, b.cap2_end, b.flags);
 }
 
-void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
-                      uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
-                      const unsigned long long *deep_before, hipStream_t s) {
+void launch_walk_sort(const PartPlan &pl, const PartBuffers &b, const L2 *st2, const Carry *carry, hipStream_t s) {
     const uint32_t dump = (uint32_t)pl.capacity1;
-    launch_ws<false>(pl, pl.n_wg1, pl.k > 15 ? SCATTER_LDS_WIDE : FUSE_LDS_NARROW, s, codes, restarts, n_bases, st2, pl, pl.n_chunks, 1u, out1, cursor1,
-                     cap_end, dump, flags, 0u, 0u, (uint32_t *)nullptr, side, side_n, side_cap, deep_before);
-    hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)cursor1, bucket_base, cap_end, pl, bucket_end, wg2_start,
-                       (const uint32_t *)flags);
+    launch_ws<false>(pl, pl.n_wg1, pl.k > 15 ? SCATTER_LDS_WIDE : FUSE_LDS_NARROW, s, b.codes, b.restarts, b.n_bases, st2, pl, pl.n_chunks, 1u, b.out1,
+                     b.cursor1, (const uint32_t *)b.cap_end, dump, b.flags, 0u, 0u, (uint32_t *)nullptr, b.side, b.side_n, b.side_cap,
+                     (const unsigned long long *)&carry->deep_in);
+    hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)b.cursor1, (const uint32_t *)b.bucket_base,
+                       (const uint32_t *)b.cap_end, pl, b.bucket_end, b.wg2_start, (const uint32_t *)b.flags);
 }
 
-void launch_deep_tail(const uint32_t *codes, const uint32_t *n_bases, uint32_t n_chunks, const unsigned long long *before_in,
-                      unsigned long long *before_out, const uint32_t *flags, hipStream_t s) {
-    hipLaunchKernelGGL(k_deep_tail, dim3(1), dim3(64), 0, s, codes, n_bases, n_chunks, before_in, before_out, flags);
+// deep windows: the stream's last bases, for the next feed's first slots
+void launch_deep_tail(const PartPlan &pl, const PartBuffers &b, Carry *carry, hipStream_t s) {
+    hipLaunchKernelGGL(k_deep_tail, dim3(1), dim3(64), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.n_bases, pl.n_chunks,
+                       (const unsigned long long *)&carry->deep_in, (unsigned long long *)&carry->deep_out, (const uint32_t *)b.flags);
 }
 
 }  // namespace pk

@@ -374,13 +374,12 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
     recacc_finish(racc, recs, recs_cap, carry);
 }
 
-void launch_squeeze(const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state, const PiecePack *packs, const L2 *st2,
-                    const uint32_t *chunk_odd, uint32_t k, uint32_t n_chunks, uint32_t n_wg, uint32_t chunks_per_wg, uint32_t *codes, uint32_t *restarts, uint32_t *n_bases,
-                    DevRec *recs, uint64_t recs_cap, Carry *carry, uint32_t *flags, hipStream_t s) {
-#define PK_SQUEEZE(KC) hipLaunchKernelGGL(k_squeeze<KC>, dim3(n_wg), dim3(WG), 0, s, fasta, n, stream_off, lane_state, packs, st2, chunk_odd, k, n_chunks, \
-                                          chunks_per_wg, codes, restarts, n_bases, recs, recs_cap, carry, flags)
-    if (k == 15) PK_SQUEEZE(15);
-    else if (k == 17) PK_SQUEEZE(17);
+void launch_squeeze(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state,
+                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, DevRec *recs, uint64_t recs_cap, Carry *carry, hipStream_t s) {
+#define PK_SQUEEZE(KC) hipLaunchKernelGGL(k_squeeze<KC>, dim3(pl.n_wg0), dim3(WG), 0, s, fasta, n, stream_off, lane_state, packs, st2, chunk_odd, pl.k, \
+                                          pl.n_chunks, pl.G, b.codes, b.restarts, b.n_bases, recs, recs_cap, carry, b.flags)
+    if (pl.k == 15) PK_SQUEEZE(15);
+    else if (pl.k == 17) PK_SQUEEZE(17);
     else PK_SQUEEZE(0);
 #undef PK_SQUEEZE
 }

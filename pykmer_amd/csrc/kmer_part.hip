@@ -26,9 +26,14 @@
 // when the record array is too small (kmer_pack.hip, 2); every kernel below then returns without touching anything and
 // the host repeats the level with exact sizes (or the squeeze with a larger array).
 #include <cstddef>
+#include <string>
+#include <type_traits>
+#include "../../include/pykmer_hip.h"
 #include "part_common.h"
 
 namespace pk {
+
+int set_error(int code, const std::string &msg);   // pk_api.hip
 
 // ---- sample2: final-bucket sizes from a sample of the level-1 records (2^15 < final buckets <= 2^18: k = 17, slices of k = 19).
 // One workgroup per level-1 bucket tallies the level-2 digit of every stride2-th group of 256 records in LDS (stride2 = 1:
@@ -764,32 +769,59 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
     return pl;
 }
 
-size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace *lay) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const uint64_t nfb = (uint64_t)pl.B1 * pl.B2;
+// sparse tables (few records per 2^16-address bucket, k = 17): 2^split workgroups per bucket, see k_bucket_count
+static uint32_t bucket_split(const PartPlan &pl, uint64_t n_bytes) {
+    return pl.fb_bits == 16 && n_bytes / ((uint64_t)pl.B1 * pl.B2) < 8192u ? 1u : 0u;
+}
+
+// What the kernels are built for beyond what make_part_plan promises.  check_k (pk_api.hip) keeps all of it out of reach:
+// it caps addr_bits at 34, so a two-level plan has bucket_bits <= 18 and B1 >= 16, and its final buckets are either
+// tallied while sampling (addr_bits <= 30: B1 * B2 > B1) or sized from the level-1 records (sample2).
+int part_plan_check(const PartPlan &pl, uint64_t n_bytes) {
+    const auto no = [](const std::string &what) { return set_error(PK_ERR_HIP, "partition plan outside the kernels' limits: " + what); };
+    const uint32_t max_B1 = pl.k <= 15 ? 128u : 512u;
+    if (pl.B1 > max_B1 || pl.B2 > 512u || pl.fb_bits > 16u)
+        return no(std::to_string(pl.B1) + " x " + std::to_string(pl.B2) + " buckets of 2^" + std::to_string(pl.fb_bits) + " addresses; the LDS arrays hold " +
+                  std::to_string(max_B1) + " x 512 of 2^16");
+    if (pl.b2 && pl.n_tally == pl.B1 && !pl.sample2) return no("two levels, but neither the sampling launch nor sample2 lays out the final buckets");
+    if (pl.k <= 15 && pl.b2 && pl.addr_bits - pl.b1 > 24u)                                     // part_common.h
+        return no(std::to_string(pl.addr_bits - pl.b1) + " address bits behind the level-1 digit; its 3-byte records hold 24");
+    if (bucket_split(pl, n_bytes) > 1u) return no("the bucket count is laid out for whole and half buckets");
+    return PK_OK;
+}
+
+// The workspace layout, stated here and nowhere else: every region starts on a 256-byte boundary, in this order.
+size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base, PartBuffers *view) {
+    PartBuffers unused, &b = view ? *view : unused;
+    const size_t nfb = (size_t)pl.B1 * pl.B2, rec1 = (size_t)(pl.capacity1 + TILE + 64);
     size_t o = 0;
-    lay->codes = o; o += up((size_t)pl.n_chunks * SLOT_CODE_WORDS * 4);
-    lay->restarts = o; o += up((size_t)pl.n_chunks * SLOT_RST_WORDS * 4);
-    lay->n_bases = o; o += up((size_t)pl.n_chunks * 4);
-    lay->tally_rows = o; o += up((size_t)COUNT_WGS * pl.n_tally * 4);
-    lay->tally_tot = o; o += up(pl.sample2 ? (size_t)nfb * 4 + (size_t)(pl.B1 + 1024) * 4 : (size_t)pl.n_tally * 4);   // sample2: + sampled counts, block totals
-    lay->bucket_base = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->bucket_end = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->cursor1 = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->cap_end = o; o += up((size_t)(pl.B1 + 1) * 4);
-    lay->wg2_start = o; o += up((size_t)(pl.B1 + 1) * 4);   // level-2 work items, buckets in XCD-class order
-    lay->final_start = o; o += up((size_t)(nfb + 1) * 4);
-    lay->cursor2 = o; o += up((size_t)(nfb + 1) * 4);
-    lay->cap2_end = o; o += up((size_t)(nfb + 1) * 4);
+    const auto place = [&](auto *&p, size_t bytes, bool packed = false) {   // packed: the next region follows without rounding
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + o);
+        o += bytes;
+        if (!packed) o = (o + 255) & ~(size_t)255;
+    };
+    place(b.codes, (size_t)pl.n_chunks * SLOT_CODE_WORDS * 4);
+    place(b.restarts, (size_t)pl.n_chunks * SLOT_RST_WORDS * 4);
+    place(b.n_bases, (size_t)pl.n_chunks * 4);
+    place(b.tally_rows, (size_t)COUNT_WGS * pl.n_tally * 4);
+    // sample2: the tallies of all final buckets, then k_sample2's count per level-1 bucket and k_rooms2's total per 1024 final buckets
+    const bool s2 = pl.sample2 != 0;
+    place(b.tally_tot, (s2 ? nfb : pl.n_tally) * 4, s2);
+    place(b.sampled_n, s2 ? (size_t)pl.B1 * 4 : 0, true);
+    place(b.block_tot, s2 ? 1024 * 4 : 0);
+    if (!s2) b.sampled_n = b.block_tot = nullptr;
+    // (wg2_start: level-2 work items, buckets in XCD-class order)
+    for (uint32_t **p : {&b.bucket_base, &b.bucket_end, &b.cursor1, &b.cap_end, &b.wg2_start}) place(*p, (size_t)(pl.B1 + 1) * 4);
+    for (uint32_t **p : {&b.final_start, &b.cursor2, &b.cap2_end}) place(*p, (nfb + 1) * 4);
     // level-1 buckets + the dump tile: 2-byte records when level 1 is the only level, two planes of 2 + 1 bytes for 32-bit
     // k-mers with a second level (part_common.h), 4-byte records (the low 32 bits) for 64-bit k-mers
-    lay->out1 = o; o += !pl.b2 ? up((size_t)(pl.capacity1 + TILE + 64) * 2)
-                     : pl.k <= 15 ? level1_hi_plane_offset(pl.capacity1) + up((size_t)(pl.capacity1 + TILE + 64))
-                                  : up((size_t)(pl.capacity1 + TILE + 64) * 4);
-    lay->out2 = o; o += up(!pl.b2 ? 256 : (size_t)(pl.capacity2 + TILE + 64) * 2);
-    lay->side_cap = n_bytes + 16;                          // every side entry stands for >= 1 k-mer
-    lay->side = o; o += up((size_t)lay->side_cap * 8);
-    lay->side_n = o; o += 256;                             // side-list length (u64), then the flags word
+    place(b.out1, !pl.b2 ? rec1 * 2 : pl.k <= 15 ? level1_hi_plane_offset(pl.capacity1) + rec1 : rec1 * 4);
+    place(b.out2, !pl.b2 ? 256 : (size_t)(pl.capacity2 + TILE + 64) * 2);
+    b.side_cap = n_bytes + 16;                             // every side entry stands for >= 1 k-mer
+    place(b.side, (size_t)b.side_cap * 8);
+    place(b.signals, sizeof(PartSignals));
+    b.side_n = &b.signals->side_n;
+    b.flags = b.signals->flags;
     return o;
 }
 
@@ -818,45 +850,30 @@ extern "C" int pk_diag_occupancy(int which) {
 // Everything behind the squeeze pass for one feed: bucket layout (sampled with `stride`; 1 = exact), the fused
 // k-mer assembly + level-1 sort, level 2, bucket count, side list.  Returns right after the launches; the
 // caller reads the flags word back to learn whether the layout held (flags[0] == 0).
-int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint32_t stride, uint8_t *ws, const PartWorkspace &lay, uint8_t *table8,
-                       hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
-                       unsigned long long *hist, unsigned long long *bucket_hist, bool armed, const unsigned long long *deep_before) {
-    const uint32_t *codes = (const uint32_t *)(ws + lay.codes), *restarts = (const uint32_t *)(ws + lay.restarts);
-    const uint32_t *n_bases = (const uint32_t *)(ws + lay.n_bases);
-    uint32_t *tally_rows = (uint32_t *)(ws + lay.tally_rows), *tally_tot = (uint32_t *)(ws + lay.tally_tot);
-    uint32_t *bucket_base = (uint32_t *)(ws + lay.bucket_base), *bucket_end = (uint32_t *)(ws + lay.bucket_end);
-    uint32_t *cursor1 = (uint32_t *)(ws + lay.cursor1), *cap_end = (uint32_t *)(ws + lay.cap_end);
-    uint32_t *wg2_start = (uint32_t *)(ws + lay.wg2_start), *final_start = (uint32_t *)(ws + lay.final_start);
-    uint32_t *cursor2 = (uint32_t *)(ws + lay.cursor2), *cap2_end = (uint32_t *)(ws + lay.cap2_end);
-    void *out1 = ws + lay.out1, *out2 = ws + lay.out2;
-    unsigned long long *side = (unsigned long long *)(ws + lay.side), *side_n = (unsigned long long *)(ws + lay.side_n);
-    uint32_t *flags = (uint32_t *)(side_n + 1);
+int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint64_t n_bytes, uint32_t stride, const Carry *carry, uint8_t *table8,
+                       unsigned long long *hist, unsigned long long *hist_rep, bool fresh, const PartEvents &ev, hipStream_t s) {
     const uint32_t nfb = pl.B1 * pl.B2;
-    const bool laid_out2 = pl.n_tally > pl.B1 || pl.sample2;
-    if (pl.B1 > (pl.k <= 15 ? 128u : 512u) || pl.B2 > 512u || pl.fb_bits > 16u) return -3;   // what the kernels' LDS arrays are sized for
-    // Level 2 always claims: check_k caps addr_bits at 34, so a two-level plan has bucket_bits <= 18 and B1 >= 16, and its final
-    // buckets are either tallied while sampling (addr_bits <= 30: B1 * B2 > B1) or sized from the level-1 records (sample2)
-    if (pl.b2 && !laid_out2) return -3;
-    if (pl.k <= 15 && pl.b2 && pl.addr_bits - pl.b1 > 24u) return -3;                           // 3-byte level-1 records (part_common.h)
-    if (!armed && hipMemsetAsync(side_n, 0, PART_FLAG_WORDS * 4, s) != hipSuccess) return -2;   // side-list length + flags
-    launch_provision(codes, restarts, n_bases, st2, pl, stride, tally_rows, tally_tot, bucket_base, cursor1, cap_end, final_start, cursor2, cap2_end,
-                     flags, deep_before, s);
-    if (ev_sort_begin) hipEventRecord(ev_sort_begin, s);
-    launch_walk_sort(codes, restarts, n_bases, st2, pl, out1, cursor1, cap_end, flags, bucket_base, bucket_end, wg2_start, side, side_n, lay.side_cap, deep_before, s);
-    if (ev_sort_end) hipEventRecord(ev_sort_end, s);
-    const uint16_t *final_recs = (const uint16_t *)out1;
-    const uint32_t *k6_start = bucket_base, *k6_end = bucket_end;        // b2 == 0: the level-1 buckets are the final ones
+    const uint32_t *flags = b.flags;
+    const char *failed = nullptr;                                        // the first stage whose launch the runtime refused, and why
+    hipError_t why = hipSuccess;
+    const auto stage = [&](const char *name) { if (!failed && (why = hipGetLastError()) != hipSuccess) failed = name; };
+    launch_provision(pl, b, st2, stride, carry, s);
+    stage("bucket layout");
+    hipEventRecord(ev.sort_begin, s);
+    launch_walk_sort(pl, b, st2, carry, s);
+    stage("level-1 sort");
+    hipEventRecord(ev.sort_end, s);
+    const uint16_t *final_recs = (const uint16_t *)b.out1;
+    const uint32_t *k6_start = b.bucket_base, *k6_end = b.bucket_end;    // b2 == 0: the level-1 buckets are the final ones
     if (pl.sample2) {                                                    // final-bucket rooms from a sample of the level-1 records
         const uint32_t stride2 = stride == 1u ? 1u : 16u, n_blocks = (nfb + 1023u) / 1024u;
-        uint32_t *sampled_n = tally_tot + nfb, *block_tot = sampled_n + pl.B1;
-        hipLaunchKernelGGL(k_sample2, dim3(pl.B1), dim3(1024), 0, s, (const uint32_t *)out1, (const uint32_t *)bucket_base, (const uint32_t *)bucket_end,
-                           pl, stride2, tally_tot, sampled_n, (const uint32_t *)flags);
-        hipLaunchKernelGGL(k_rooms2, dim3(n_blocks), dim3(1024), 0, s, (const uint32_t *)tally_tot, (const uint32_t *)sampled_n,
-                           (const uint32_t *)bucket_base, (const uint32_t *)bucket_end, pl, stride2, nfb, final_start, cap2_end, block_tot,
-                           (const uint32_t *)flags);
-        hipLaunchKernelGGL(k_bases2, dim3(1), dim3(1024), 0, s, n_blocks, nfb, pl, block_tot, final_start, flags);
-        hipLaunchKernelGGL(k_starts2, dim3(n_blocks), dim3(1024), 0, s, nfb, (const uint32_t *)block_tot, final_start, cursor2, cap2_end,
-                           (const uint32_t *)flags);
+        const uint32_t *base1 = b.bucket_base, *end1 = b.bucket_end;
+        hipLaunchKernelGGL(k_sample2, dim3(pl.B1), dim3(1024), 0, s, (const uint32_t *)b.out1, base1, end1, pl, stride2, b.tally_tot, b.sampled_n, flags);
+        hipLaunchKernelGGL(k_rooms2, dim3(n_blocks), dim3(1024), 0, s, (const uint32_t *)b.tally_tot, (const uint32_t *)b.sampled_n, base1, end1, pl, stride2,
+                           nfb, b.final_start, b.cap2_end, b.block_tot, flags);
+        hipLaunchKernelGGL(k_bases2, dim3(1), dim3(1024), 0, s, n_blocks, nfb, pl, b.block_tot, b.final_start, b.flags);
+        hipLaunchKernelGGL(k_starts2, dim3(n_blocks), dim3(1024), 0, s, nfb, (const uint32_t *)b.block_tot, b.final_start, b.cursor2, b.cap2_end, flags);
+        stage("final-bucket rooms");
     }
     if (pl.b2) {
         // 512 would be the resident two per CU (1.21 ms); more and shorter walks even out the end: 4096 -> 1.17 ms (k = 17: 1.44 -> 1.38).
@@ -866,36 +883,29 @@ int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint
         // stages back to back, 2.03 / 2.12 / 2.44 overlapped -- every part pays its own ragged end, and the two kernels
         // do not hide each other (both live on the LDS pipe).
         const uint32_t grid2 = 4096u;
-        if (pl.k <= 15)
-            hipLaunchKernelGGL((k_scatter2<512, 32, true>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
-                               bucket_base, bucket_end, pl, out2, cursor2, (const uint32_t *)cap2_end, (uint32_t)pl.capacity2, flags);
-        else
-            hipLaunchKernelGGL((k_scatter2<512, 32>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s, (const uint32_t *)out1, wg2_start,
-                               bucket_base, bucket_end, pl, out2, cursor2, (const uint32_t *)cap2_end, (uint32_t)pl.capacity2, flags);
-        final_recs = (const uint16_t *)out2; k6_start = final_start; k6_end = cursor2;   // a final bucket ends where its cursor stopped
+        hipLaunchKernelGGL((pl.k <= 15 ? &k_scatter2<512, 32, true> : &k_scatter2<512, 32>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s,
+                           (const uint32_t *)b.out1, b.wg2_start, b.bucket_base, b.bucket_end, pl, b.out2, b.cursor2, (const uint32_t *)b.cap2_end,
+                           (uint32_t)pl.capacity2, b.flags);
+        stage("level 2");
+        final_recs = (const uint16_t *)b.out2; k6_start = b.final_start; k6_end = b.cursor2;   // a final bucket ends where its cursor stopped
     }
-    if (ev_part_end) hipEventRecord(ev_part_end, s);
-    // sparse tables (few records per 2^16-address bucket, k=17): 2^split workgroups per bucket, see k_bucket_count
-    const bool sparse = pl.fb_bits == 16 && n_bytes / nfb < 8192u;
-    const uint32_t split = sparse ? 1u : 0u;
+    hipEventRecord(ev.part_end, s);
+    const uint32_t split = bucket_split(pl, n_bytes);
     const size_t part_addrs = (size_t)1 << (pl.fb_bits - split);
     const size_t lds6 = part_addrs * 2 < 64 ? 64 : part_addrs * 2;
     const uint32_t n_rows6 = (uint32_t)(nfb << split);
-    if (split > 1u) return -3;                                           // the kernels are laid out for whole and half buckets
-    if (pl.fb_bits == 15 && fresh)                                       // 64 KiB of counters: two workgroups per CU
-        hipLaunchKernelGGL((k_bucket_count_half_lean<1024, true>), dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
-                           fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);
-    else if (pl.fb_bits == 15)
-        hipLaunchKernelGGL((k_bucket_count_half_lean<1024, false>), dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
-                           fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);
-    else if (split)
-        hipLaunchKernelGGL(k_bucket_count_bytes<1024>, dim3(nfb), dim3(1024), K6_BYTES_LDS, s, final_recs, k6_start, k6_end, table8, fresh ? 1u : 0u, bucket_hist,
-                           (const uint32_t *)flags);
-    else
-        hipLaunchKernelGGL(k_bucket_count<1024>, dim3(n_rows6), dim3(1024), lds6, s, final_recs, k6_start, k6_end, pl.fb_bits, split, table8,
-                           fresh ? 1u : 0u, bucket_hist, (const uint32_t *)flags);
-    hipLaunchKernelGGL(k_apply_side, dim3(AS_WGS), dim3(WG), 0, s, side, side_n, lay.side_cap, table8, hist, bucket_hist, (const uint32_t *)flags);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    // geometry: fb_bits and split, for the kernels that take them
+    const auto count = [&](auto kernel, uint32_t grid, size_t lds, auto... geometry) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), lds, s, final_recs, k6_start, k6_end, geometry..., table8, fresh ? 1u : 0u, hist_rep, flags);
+    };
+    if (pl.fb_bits == 15 && fresh) count(k_bucket_count_half_lean<1024, true>, n_rows6, lds6, pl.fb_bits, split);   // 64 KiB of counters: two workgroups per CU
+    else if (pl.fb_bits == 15) count(k_bucket_count_half_lean<1024, false>, n_rows6, lds6, pl.fb_bits, split);
+    else if (split) count(k_bucket_count_bytes<1024>, nfb, K6_BYTES_LDS);
+    else count(k_bucket_count<1024>, n_rows6, lds6, pl.fb_bits, split);
+    stage("bucket count");
+    hipLaunchKernelGGL(k_apply_side, dim3(AS_WGS), dim3(WG), 0, s, b.side, b.side_n, b.side_cap, table8, hist, hist_rep, flags);
+    stage("side list");
+    return failed ? set_error(PK_ERR_HIP, std::string("partition pipeline: the launch of the ") + failed + " failed: " + hipGetErrorString(why)) : PK_OK;
 }
 
 }  // namespace pk

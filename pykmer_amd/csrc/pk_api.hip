@@ -496,11 +496,10 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if (rc) return rc;
     PartPlan pl = make_part_plan((uint32_t)ix->k, n_bytes, (uint32_t)ix->slice_bits, (uint32_t)ix->slice_index);
     if (!plan_fits_u32(pl)) return fail(PK_ERR_ARG, "feed of %llu bytes needs record positions beyond 2^32 (internal limit); split it", (unsigned long long)n_bytes);
-    PartWorkspace lay;
-    if ((rc = ix->ws.reserve(part_workspace_bytes(pl, n_bytes, &lay)))) return rc;
-    uint8_t *ws = ix->ws.p;
-    uint32_t *flag_words = (uint32_t *)(ws + lay.side_n);                  // side-list length (u64), then flags[4]
-    uint32_t *flags = flag_words + 2;
+    if ((rc = part_plan_check(pl, n_bytes))) return rc;
+    if ((rc = ix->ws.reserve(part_workspace(pl, n_bytes)))) return rc;
+    PartBuffers pb;
+    part_workspace(pl, n_bytes, ix->ws.p, &pb);
     Carry *carry = &ix->tail.p->carry;
     const Events &ev = ix->ev;
     // Nothing between here and the last kernel of the feed waits for the device: the record array was sized from what the
@@ -511,43 +510,37 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     // feed's squeezed text), so a 2 reaches the host as a 2, whatever that text would have done to the sampled layout.
     HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
     launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
-    launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, flag_words, PART_FLAG_WORDS, ix->stream);
+    launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
     launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, n_chunks, (uint32_t)ix->k, ix->stream);
     launch_scan_l2(ix->c_l2.p, n_chunks, carry, ix->c_l2s.p, ix->t_l2.p, (uint32_t)ix->k, ix->stream);
     HIPCHK(hipEventRecord(ev.scan_end, ix->stream));
-    bool armed = true;                                       // the scan kernel zeroed the flag words for the first attempt
     bool squeeze = true;
     uint64_t squeezed_cap = 0;                               // record slots the last squeeze of this feed ran with
     uint32_t stride = pl.sample_stride;
     for (int attempt = 0;; attempt++) {
+        if (attempt) HIPCHK(hipMemsetAsync(pb.signals, 0, sizeof(PartSignals), ix->stream));   // the scan kernel zeroed them for the first attempt
         if (squeeze) {
-            if (!armed) HIPCHK(hipMemsetAsync(flag_words, 0, PART_FLAG_WORDS * 4, ix->stream));
             squeezed_cap = ix->recs_cap();
             HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream));
-            launch_squeeze(f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, (uint32_t)ix->k, n_chunks, pl.n_wg0, pl.G,
-                           (uint32_t *)(ws + lay.codes), (uint32_t *)(ws + lay.restarts), (uint32_t *)(ws + lay.n_bases), ix->recs.p, ix->recs_cap(), carry,
-                           flags, ix->stream);
-            if (ix->k > 17)                                      // deep windows: the stream's last bases, for the next feed's first slots
-                launch_deep_tail((const uint32_t *)(ws + lay.codes), (const uint32_t *)(ws + lay.n_bases), n_chunks,
-                                 (const unsigned long long *)&carry->deep_in, (unsigned long long *)&carry->deep_out, flags, ix->stream);
+            launch_squeeze(pl, pb, f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, ix->recs.p, squeezed_cap, carry,
+                           ix->stream);
+            if (ix->k > 17) launch_deep_tail(pl, pb, carry, ix->stream);
             HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
-            armed = true;
         }
         // the level-1 buckets are laid out from a sample of the slots; if one of them runs out of room every later kernel
         // returns untouched (flags[0] = 1) and the passes behind the squeeze are repeated with exact sizes -- on the text
         // the squeeze of this feed left, so only once that squeeze has run in full (flags[0] = 2 is handled first)
-        if (launch_partitioned(ix->c_l2s.p, n_bytes, pl, stride, ws, lay, ix->table8.p, ix->stream, ev.sort_begin, ev.sort_end, ev.part_end,
-                               ix->table_fresh, ix->tail.p->hist, ix->hist_rep.p, armed, (const unsigned long long *)&carry->deep_in))
-            return fail(PK_ERR_HIP, "partition pipeline launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if ((rc = launch_partitioned(pl, pb, ix->c_l2s.p, n_bytes, stride, carry, ix->table8.p, ix->tail.p->hist, ix->hist_rep.p, ix->table_fresh,
+                                     {ev.sort_begin, ev.sort_end, ev.part_end}, ix->stream)))
+            return rc;
         HIPCHK(hipEventRecord(ev.bucket_end, ix->stream));
         volatile uint32_t *got = ix->pin->flags;
         // what the host needs of the feed, in two small copies behind the last kernel: the flags, and the stream totals +
         // value histogram (pk_indexer_finish then has nothing left to fetch)
-        HIPCHK(hipMemcpyAsync(ix->pin->flags, flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipMemcpyAsync(ix->pin->flags, pb.flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
         if ((rc = read_tail(ix))) return rc;
         if (!got[0]) { ix->recounted += got[1]; break; }
         if (attempt >= 3) return fail(PK_ERR_HIP, "the feed's layout did not settle (internal error, flag %u)", got[0]);
-        armed = false;
         if (got[0] == 2u) {                                  // more records than the array holds: grow it, squeeze again
             rc = ensure_recs(ix, ix->pin->tail.carry.n_recs);
             if (rc) return rc;

@@ -28,8 +28,17 @@ struct Carry {
     uint64_t deep_in, deep_out;
 };
 
+// What a feed's partition passes signal through, zeroed as one span before every attempt (for the first attempt of a feed
+// by the scan kernel of the structure pass).  flags[0]: 2 = the squeeze backed out (record array too small), 1 = a bucket
+// room or a layout total overflowed; every kernel behind the squeeze returns at once when it finds it raised, so the first
+// value raised is the one the host reads.  flags[1]: buckets recounted (statistics).
+struct PartSignals {
+    unsigned long long side_n;   // entries in the side list
+    uint32_t flags[4];
+};
+
 void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_chunks, hipStream_t s);
-void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, uint32_t *zero_words, uint32_t n_zero, hipStream_t s);
+void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, PartSignals *zeroed, hipStream_t s);
 void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd, uint32_t n_chunks,
                      uint32_t k, hipStream_t s);
 void launch_scan_l2(const L2 *in, uint32_t n_chunks, Carry *carry, L2 *out, L2 *tile_ws, uint32_t k, hipStream_t s);
@@ -38,9 +47,6 @@ void launch_hist8(const uint8_t *table8, uint64_t n, unsigned long long *hist, h
 // kmer_pack.hip -- the packed stream: one slot per 16 KiB text chunk
 constexpr uint32_t SLOT_CODE_WORDS = 1024;   // 16384 bases x 2 bits
 constexpr uint32_t SLOT_RST_WORDS = 512;     // 16384 restart bits
-void launch_squeeze(const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state, const PiecePack *packs, const L2 *st2,
-                    const uint32_t *chunk_odd, uint32_t k, uint32_t n_chunks, uint32_t n_wg, uint32_t chunks_per_wg, uint32_t *codes, uint32_t *restarts, uint32_t *n_bases,
-                    DevRec *recs, uint64_t recs_cap, Carry *carry, uint32_t *flags, hipStream_t s);
 
 // kmer_fuse.hip / kmer_part.hip -- partitioned table update
 struct PartPlan {
@@ -61,35 +67,39 @@ struct PartPlan {
     uint64_t capacity2;      // the same for the final buckets, where they are laid out from the estimate
 };
 constexpr uint32_t COUNT_WGS = 256;   // workgroups (= tally rows) of the sampling launch
-struct PartWorkspace {       // byte offsets into one device allocation
-    size_t codes, restarts, n_bases, tally_rows, tally_tot, bucket_base, bucket_end, cursor1, cap_end, wg2_start, final_start, cursor2, cap2_end,
-        out1, out2, side, side_n;
+constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
+// The workspace of the partition passes: one device allocation, seen through typed pointers.  part_workspace
+// (kmer_part.hip) is the one place that lays it out.
+struct PartBuffers {
+    uint32_t *codes, *restarts, *n_bases;                   // the squeezed text: one slot per chunk
+    uint32_t *tally_rows, *tally_tot;                       // the sampling launch's rows and their column sums
+    uint32_t *sampled_n, *block_tot;                        // sample2 only (null otherwise): records sampled per level-1 bucket, k_rooms2's block totals
+    uint32_t *bucket_base, *bucket_end, *cursor1, *cap_end, *wg2_start;   // level 1, B1 + 1 words each
+    uint32_t *final_start, *cursor2, *cap2_end;             // the final buckets, B1 * B2 + 1 words each
+    void *out1, *out2;                                      // level-1 and final records, each with its dump tile
+    unsigned long long *side, *side_n;                      // hot-key (address, count) entries; side_n = &signals->side_n
     uint64_t side_cap;
+    PartSignals *signals;
+    uint32_t *flags;                                        // = signals->flags
 };
+struct PartEvents { hipEvent_t sort_begin, sort_end, part_end; };   // recorded by launch_partitioned around the level-1 sort and behind level 2
 PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint32_t slice_index);
-size_t part_workspace_bytes(const PartPlan &pl, uint64_t n_bytes, PartWorkspace *lay);
+// PK_OK, or PK_ERR_HIP and a message naming the limit of the kernels that the plan exceeds
+int part_plan_check(const PartPlan &pl, uint64_t n_bytes);
+// the bytes of the workspace for the plan; with `view`, also where its regions lie in an allocation starting at `base`
+size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base = nullptr, PartBuffers *view = nullptr);
 void part_set_attributes();
 void fuse_set_attributes();
-void launch_provision(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl,
-                      uint32_t stride, uint32_t *tally_rows, uint32_t *tally_tot, uint32_t *bucket_base, uint32_t *cursor1,
-                      uint32_t *cap_end, uint32_t *final_start, uint32_t *cursor2, uint32_t *cap2_end, uint32_t *flags,
-                      const unsigned long long *deep_before, hipStream_t s);
-void launch_walk_sort(const uint32_t *codes, const uint32_t *restarts, const uint32_t *n_bases, const L2 *st2, const PartPlan &pl, void *out1,
-                      uint32_t *cursor1, const uint32_t *cap_end, uint32_t *flags, const uint32_t *bucket_base, uint32_t *bucket_end,
-                      uint32_t *wg2_start, unsigned long long *side, unsigned long long *side_n, uint64_t side_cap,
-                      const unsigned long long *deep_before, hipStream_t s);
-void launch_deep_tail(const uint32_t *codes, const uint32_t *n_bases, uint32_t n_chunks, const unsigned long long *before_in,
-                      unsigned long long *before_out, const uint32_t *flags, hipStream_t s);
-// `armed`: the side-list length and the flags word were already zeroed on the stream (launch_scan_l1 does it for the first
-// attempt of a feed); a repeat after an overflow zeroes them itself.  `deep_before`: Carry::deep_in (read by k = 19, 21 only).
-int launch_partitioned(const L2 *st2, uint64_t n_bytes, const PartPlan &pl, uint32_t stride, uint8_t *ws, const PartWorkspace &lay, uint8_t *table8,
-                       hipStream_t s, hipEvent_t ev_sort_begin, hipEvent_t ev_sort_end, hipEvent_t ev_part_end, bool fresh,
-                       unsigned long long *hist, unsigned long long *hist_replicas, bool armed, const unsigned long long *deep_before);
-constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
-// side_n (u64) + flags[4], zeroed together.  flags[0]: 2 = the squeeze backed out (record array too small), 1 = a bucket
-// room or a layout total overflowed; every kernel behind the squeeze returns at once when it finds it raised, so the first
-// value raised is the one the host reads.  flags[1]: buckets recounted (statistics).
-constexpr uint32_t PART_FLAG_WORDS = 6;
+// The launchers take the plan, the view and what lives outside the workspace.  `carry`: its deep_in / deep_out words are
+// touched by k = 19, 21 only.
+void launch_squeeze(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state,
+                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, DevRec *recs, uint64_t recs_cap, Carry *carry, hipStream_t s);
+void launch_deep_tail(const PartPlan &pl, const PartBuffers &b, Carry *carry, hipStream_t s);
+void launch_provision(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint32_t stride, const Carry *carry, hipStream_t s);
+void launch_walk_sort(const PartPlan &pl, const PartBuffers &b, const L2 *st2, const Carry *carry, hipStream_t s);
+// Everything behind the squeeze for one feed, on zeroed signals.  PK_OK, or PK_ERR_HIP and a message naming the stage whose launch failed.
+int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint64_t n_bytes, uint32_t stride, const Carry *carry, uint8_t *table8,
+                       unsigned long long *hist, unsigned long long *hist_rep, bool fresh, const PartEvents &ev, hipStream_t s);
 
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it
