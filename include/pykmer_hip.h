@@ -127,6 +127,29 @@ int pk_indexer_table_slice_to_device(pk_indexer *ix, void *dev_dst, uint64_t off
 int pk_indexer_timings(pk_indexer *ix, double out[10]);
 void pk_indexer_destroy(pk_indexer *ix);
 
+/* ---- query: per-record k-mer hits of a FASTA / FASTQ text against N tables that lie in HBM (no reference counterpart:
+ * README.md stops at the distance matrix).  Let record r, in file order, have the valid windows a_1 .. a_m (m = its
+ * n_valid_kmers, canonical values as indexer.py:341 forms them).  For every record and table t
+ *   hits[r][t]  = #{ j : min_count <= T_t[a_j] <= max_count }     (every window counts: a k-mer twice in r counts twice)
+ *   depth[r][t] = sum of T_t[a_j] over the same j                 (the saturated table counts)
+ * Records without a valid window are listed too, with zeros.
+ *
+ * pk_query_create makes an indexer in query mode: it parses and squeezes the text exactly like pk_indexer_create's, but
+ * allocates no 4^k table and looks the k-mers up instead of counting them.  kmer_len odd, 1 <= k <= 17 (PK_ERR_ARG
+ * otherwise).  set_format, feed, feed_device, finish, records, fastq_stats, reset and destroy work as for any indexer;
+ * finish reports num_kmers, total_bp and the record count and zeroes a non-null hist256_out; the table accessors answer
+ * PK_ERR_STATE.  pk_indexer_timings: [0] [1] [4] as above, [5] the seconds of the lookup kernels (window counts, ordinal
+ * scan, gathers and tallies), [2] [3] as above, the rest 0.
+ * pk_query_set_tables: after create or reset and before the first feed (PK_ERR_STATE otherwise; a feed without tables is
+ * PK_ERR_STATE too).  dev_tables are N >= 1 device buffers of 4^k bytes on the indexer's device; the caller owns them and
+ * keeps them alive through the feeds.  They stay set across resets.  1 <= min_count <= max_count <= 255.  One lookup
+ * launch serves 16 tables; more are looked up group by group inside the feed.
+ * pk_query_results: after pk_indexer_finish.  hits_out / depth_out receive n_recs * N u64 each, row-major [r * N + t];
+ * PK_ERR_RECS_CAP if the stream holds more than recs_cap records. */
+int pk_query_create(pk_indexer **out, int k, int device);
+int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
+int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);
+
 /* ---- stats: replaces Header.update_stats (tools.py:246-263) on a host table of n bytes. */
 int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device);
 

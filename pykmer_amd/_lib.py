@@ -45,6 +45,9 @@ _SIGNATURES = {
     "pk_indexer_table_slice_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
     "pk_indexer_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_indexer_destroy": (None, [ctypes.c_void_p]),
+    "pk_query_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
+    "pk_query_set_tables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pk_query_results": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -237,6 +240,41 @@ class Indexer:
         _check(load().pk_indexer_timings(self._h, t.ctypes.data))
         return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]),
                 "partition_s": t[5], "bucket_s": t[6], "walk_sort_s": t[7], "relayouts": int(t[8]), "buckets_recounted": int(t[9])}
+
+
+class QueryIndexer(Indexer):
+    """An indexer in query mode (pk_query_*): it parses its feeds like an Indexer, holds no table, and tallies per record how
+    many windows hit each of N device-resident 4^k-byte tables.  feed / feed_device / finish / records / reset as Indexer."""
+
+    def __init__(self, k: int, device: int = 0, fmt: str = "fasta"):
+        if fmt not in FORMATS:
+            raise ValueError(f"unknown input format {fmt!r}: expected one of {sorted(FORMATS)}")
+        self._h = ctypes.c_void_p()
+        self.k, self.device, self.slice_index, self.n_slices, self.fmt = k, device, 0, 1, fmt
+        self.table_bytes = 4 ** k if k > 0 else 0
+        self.n_tables = 0
+        _check(load().pk_query_create(ctypes.byref(self._h), k, device))
+        if fmt != "fasta":
+            _check(load().pk_indexer_set_format(self._h, FORMATS[fmt]))
+
+    def set_tables(self, dev_ptrs, min_count: int = 1, max_count: int = 255):
+        """pk_query_set_tables: device pointers of the 4^k-byte tables (the caller keeps them alive through the feeds)."""
+        N = len(dev_ptrs)
+        ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+        _check(load().pk_query_set_tables(self._h, ptrs, N, int(min_count), int(max_count)))
+        self.n_tables = N
+
+    def results(self, n_records: int):
+        """pk_query_results after finish(): (hits, depth), each (n_records, N) uint64."""
+        hits = np.zeros((max(n_records, 1), max(self.n_tables, 1)), dtype=np.uint64)
+        depth = np.zeros_like(hits)
+        _check(load().pk_query_results(self._h, hits.ctypes.data, depth.ctypes.data, n_records))
+        return hits[:n_records, :self.n_tables], depth[:n_records, :self.n_tables]
+
+    def timings(self) -> dict:
+        t = np.zeros(10, dtype=np.float64)
+        _check(load().pk_indexer_timings(self._h, t.ctypes.data))
+        return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]), "lookup_s": t[5]}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

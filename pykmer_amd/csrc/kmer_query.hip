@@ -1,0 +1,326 @@
+// kmer_query.hip -- per-record k-mer hits of a query text against N device-resident 4^k-byte tables.
+//
+// The query path runs the structure pass and the squeeze of the indexer unchanged; where the indexer sorts the packed stream
+// into its own table (kmer_fuse.hip, kmer_part.hip), the kernels here look every canonical k-mer up in the staged tables and
+// tally, per record r and table t,
+//     hits[r][t]  = #{ windows j of r : min <= T_t[a_j] <= max }        depth[r][t] = sum of T_t[a_j] over the same j.
+// Input is the packed stream of kmer_pack.hip: per 16 KiB text chunk a slot of 2-bit codes (base b of the slot in dword
+// b / 16, bits 2 (b % 16)), one restart bit per base and the base count; the k-1 bases in front of a slot are the chunk's
+// start state.  The stream holds only valid bases of live records, so the window ending at base j is a fixed bit field of two
+// dwords, and it is valid iff no restart bit lies among the k-1 positions behind its first base.  k <= 17: the 16 bases
+// before a thread's own 16 are all the history a window needs.
+//
+// The packed stream carries no record identity.  Windows are attributed by ORDINAL: the valid windows of the stream,
+// numbered in text order, belong to record r for ordinals in [P[r], P[r+1]), P[r] = sum of n_valid over the records before
+// r.  The squeeze has written this feed's DevRec.n_valid when these kernels start, and P[r] depends on records before r
+// only, so it is final once r has opened: k_query_scan extends P by the records this feed opened.  A slot's first ordinal
+// is the stream's window count before the feed (the host knows it from the previous feed's read-back) plus the prefix sum
+// of the per-slot window counts (k_query_count, then the same k_query_scan).  Empty records, many records in one 64-byte
+// piece and records that span feeds need nothing else.
+//
+// Three launches per feed and group of <= QUERY_MAX_TABLES tables (count and scan once per feed):
+//   k_query_count   one workgroup per slot: its number of valid windows
+//   k_query_scan    one workgroup: slot_first[] and the new entries of P[]
+//   k_query_lookup  one workgroup per slot, 16 windows per thread: assemble, gather T_t[a] for every table of the group,
+//                   tally.  A wave that lies in one record sums across the wave first; the tallies of a slot meet in an
+//                   LDS accumulator (the slot's first QACC_RECS records, in the spirit of RecAcc, kmer_walk.h) and reach
+//                   HBM as one atomic per record, table and slot.
+// Every kernel returns at once, writing nothing, when it finds flags[0] raised (the squeeze backed out: the slots still
+// hold an earlier text); the host grows the record and accumulator arrays and repeats the feed's squeeze and these kernels.
+#include <type_traits>
+
+#include "pk_kernels.h"
+
+namespace pk {
+
+constexpr int QNT = 1024;                 // threads per slot, 16 bases each
+constexpr uint32_t QACC_RECS = 128;       // records of a slot tallied in LDS; later ones (reads below ~128 bytes) go to HBM directly
+
+// OR of x << s for s = 0 .. n-1 (n <= 16)
+__device__ __forceinline__ uint32_t q_smear(uint32_t x, uint32_t n) {
+    if (n == 0u) return 0u;
+    uint32_t y = x, have = 1u;                               // y covers s < have
+    while (2u * have <= n) { y |= y << have; have *= 2u; }
+    return y | (y << (n - have));                            // n - have < have: the two stretches overlap or touch
+}
+
+// What thread t of a slot works on: its 16 bases, the 16 before them, and which of its bases end a valid window.
+struct QLane { uint32_t cur, prev, ok; };
+__device__ __forceinline__ QLane q_lane(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts, uint32_t nb,
+                                        const L2 *__restrict__ chunk_l2_state, uint32_t c, uint32_t t, uint32_t k) {
+    QLane q; q.cur = 0; q.prev = 0; q.ok = 0;
+    if (16u * t >= nb) return q;                             // words past the base count hold an earlier feed's bits
+    const uint32_t cnt = min(16u, nb - 16u * t), km1 = k - 1u;
+    const uint32_t *cw = codes + (uint64_t)c * SLOT_CODE_WORDS;
+    const uint32_t *rw = restarts + (uint64_t)c * SLOT_RST_WORDS;
+    q.cur = cw[t];
+    const uint32_t rword = rw[t >> 1];
+    uint32_t r;                                              // restart bits: the 16 bases before (low half), the own 16 (high half)
+    if (t == 0u) {
+        // in front of the slot: the chunk's start state, newest base lowest -> stream order; of its bases only the
+        // last `len` belong to the open run
+        const L2 st = chunk_l2_state[c];
+        const uint32_t len = l2_len(st);
+        q.prev = revpairs32(st.bits);
+        r = rword << 16;
+        if (len < km1) r |= 1u << (16u - len);
+    } else {
+        q.prev = cw[t - 1u];
+        r = (t & 1u) ? rword : ((rword << 16) | (rw[(t >> 1) - 1u] >> 16));
+    }
+    q.ok = ~(q_smear(r, km1) >> 16) & ((1u << cnt) - 1u);
+    return q;
+}
+
+// exclusive prefix of v over the workgroup (QNT threads) and its total; wsum: 16 words of LDS
+__device__ __forceinline__ uint32_t q_block_scan(uint32_t v, uint32_t *wsum, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
+    __syncthreads();                                         // wsum may still be read from an earlier call
+    if (lane == 63u) wsum[w] = inc;
+    __syncthreads();
+    uint32_t pre = 0;
+    total = 0;
+    for (uint32_t i = 0; i < QNT / 64; i++) { if (i < w) pre += wsum[i]; total += wsum[i]; }
+    return pre + inc - v;
+}
+
+__global__ __launch_bounds__(QNT) void k_query_count(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
+                                                     const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state, uint32_t k,
+                                                     uint32_t *__restrict__ slot_count, const uint32_t *__restrict__ flags) {
+    __shared__ uint32_t wsum[QNT / 64];
+    if (flags[0]) return;
+    const uint32_t c = blockIdx.x;
+    const QLane q = q_lane(codes, restarts, n_bases[c], chunk_l2_state, c, threadIdx.x, k);
+    uint32_t total;
+    q_block_scan((uint32_t)__builtin_popcount(q.ok), wsum, total);
+    if (threadIdx.x == 0) slot_count[c] = total;
+}
+
+// One workgroup.  slot_first[c] = windows_before + the window counts of the slots before c.  P[r] for the records this feed
+// opened: p_done entries are final already (the records the stream held before this feed; P[0] = 0), the stream now holds
+// carry->n_recs records.
+__global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__ slot_count, uint32_t n_chunks, unsigned long long windows_before,
+                                                    unsigned long long *__restrict__ slot_first, const DevRec *__restrict__ recs,
+                                                    const Carry *__restrict__ carry, unsigned long long p_done, unsigned long long *__restrict__ P,
+                                                    const uint32_t *__restrict__ flags) {
+    __shared__ unsigned long long wsum[QNT / 64];
+    if (flags[0]) return;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    // inclusive scan of v over the workgroup; total: the sum of all
+    auto incl_scan = [&](unsigned long long v, unsigned long long &total) -> unsigned long long {
+        unsigned long long inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
+        __syncthreads();
+        if (lane == 63u) wsum[w] = inc;
+        __syncthreads();
+        unsigned long long pre = 0;
+        total = 0;
+        for (uint32_t i = 0; i < QNT / 64; i++) { if (i < w) pre += wsum[i]; total += wsum[i]; }
+        return pre + inc;
+    };
+    unsigned long long run = windows_before;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += QNT) {
+        const uint32_t c = c0 + threadIdx.x;
+        const unsigned long long v = c < n_chunks ? slot_count[c] : 0ull;
+        unsigned long long total;
+        const unsigned long long inc = incl_scan(v, total);
+        if (c < n_chunks) slot_first[c] = run + inc - v;
+        run += total;
+    }
+    const unsigned long long n_recs = carry->n_recs;
+    unsigned long long r0 = p_done;
+    if (r0 == 0ull) {
+        if (n_recs == 0ull) return;
+        if (threadIdx.x == 0) P[0] = 0ull;
+        r0 = 1ull;
+    }
+    run = r0 > 1ull ? P[r0 - 1ull] : 0ull;                   // (P[0] = 0 may have been written by thread 0 just now)
+    for (unsigned long long b = r0; b < n_recs; b += QNT) {
+        const unsigned long long r = b + threadIdx.x;
+        const unsigned long long v = r < n_recs ? recs[r - 1ull].n_valid : 0ull;
+        unsigned long long total;
+        const unsigned long long inc = incl_scan(v, total);
+        if (r < n_recs) P[r] = run + inc;
+        run += total;
+    }
+}
+
+// the largest r in [lo, hi] with P[r] <= o (P[lo] <= o is given)
+__device__ __forceinline__ unsigned long long q_find(const unsigned long long *__restrict__ P, unsigned long long lo, unsigned long long hi,
+                                                     unsigned long long o) {
+    while (lo < hi) {
+        const unsigned long long mid = lo + (hi - lo + 1ull) / 2ull;
+        if (P[mid] <= o) lo = mid; else hi = mid - 1ull;
+    }
+    return lo;
+}
+
+template <typename KT>
+__global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
+                                                      const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state, uint32_t k,
+                                                      const unsigned long long *__restrict__ slot_first, const unsigned long long *__restrict__ P,
+                                                      const Carry *__restrict__ carry, QueryTables tabs, uint32_t n_tab, uint32_t N, uint32_t t0,
+                                                      uint32_t min_count, uint32_t max_count, unsigned long long *__restrict__ hits,
+                                                      unsigned long long *__restrict__ depth, const uint32_t *__restrict__ flags) {
+    __shared__ uint32_t wsum[QNT / 64];
+    __shared__ uint32_t acc_h[QACC_RECS * QUERY_MAX_TABLES], acc_d[QACC_RECS * QUERY_MAX_TABLES];
+    __shared__ unsigned long long rec_range[2];
+    if (flags[0]) return;
+    const uint32_t c = blockIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t nb = n_bases[c];
+    if (nb == 0u) return;
+    const QLane q = q_lane(codes, restarts, nb, chunk_l2_state, c, threadIdx.x, k);
+    uint32_t total;
+    const uint32_t off = q_block_scan((uint32_t)__builtin_popcount(q.ok), wsum, total);
+    if (total == 0u) return;                                 // uniform
+    const unsigned long long first = slot_first[c];
+    if (threadIdx.x == 0) {
+        const unsigned long long n_recs = carry->n_recs;     // >= 1: a window lies in a record
+        const unsigned long long lo = q_find(P, 0ull, n_recs - 1ull, first);
+        rec_range[0] = lo;
+        rec_range[1] = q_find(P, lo, n_recs - 1ull, first + total - 1ull);
+    }
+    for (uint32_t i = threadIdx.x; i < QACC_RECS * n_tab; i += QNT) { acc_h[i] = 0u; acc_d[i] = 0u; }
+    __syncthreads();
+    const unsigned long long r_lo = rec_range[0], r_hi = rec_range[1];
+
+    // ---- the canonical k-mers of this thread's windows (indexer.py:149-150, 341)
+    const KT mask = (KT)((2u * k >= sizeof(KT) * 8u) ? ~(KT)0 : (((KT)1 << (2u * k)) - 1));
+    const unsigned long long fwd64 = ((unsigned long long)revpairs32(q.prev) << 32) | revpairs32(q.cur);          // first base highest
+    const unsigned long long rev64 = (~(((unsigned long long)q.cur << 32) | q.prev)) >> (2u * (17u - k));       // complemented, first base lowest
+    KT a[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const KT f = (KT)(fwd64 >> (2u * (15u - j))) & mask, rv = (KT)(rev64 >> (2u * j)) & mask;
+        a[j] = f < rv ? f : rv;
+    }
+    // ---- the record of every window, relative to the slot's first
+    uint32_t rr[16];
+    uint32_t rr_first = 0, rr_last = 0;
+    if (r_lo == r_hi) {                                      // uniform: the genome case
+#pragma unroll
+        for (int j = 0; j < 16; j++) rr[j] = 0u;
+    } else if (q.ok) {
+        unsigned long long o = first + off;
+        unsigned long long r = q_find(P, r_lo, r_hi, o);
+        unsigned long long next = r < r_hi ? P[r + 1ull] : ~0ull;
+        bool seen = false;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            rr[j] = 0u;
+            if ((q.ok >> j) & 1u) {
+                while (o >= next) { r++; next = r < r_hi ? P[r + 1ull] : ~0ull; }
+                rr[j] = (uint32_t)(r - r_lo);
+                if (!seen) { rr_first = rr[j]; seen = true; }
+                rr_last = rr[j];
+                o++;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; j++) rr[j] = 0u;
+    }
+    // does the whole wave lie in one record?
+    const bool has = q.ok != 0u;
+    const unsigned long long holders = __ballot(has);
+    if (holders != 0ull) {                                   // wave-uniform; no barrier inside
+        const uint32_t ref = (uint32_t)__shfl((int)rr_first, (int)__builtin_ctzll(holders), 64);
+        const bool wave_one = __all(!has || (rr_first == ref && rr_last == ref));
+        auto add = [&](uint32_t rel, uint32_t tt, uint32_t h, uint32_t d) {
+            if (rel < QACC_RECS) {
+                if (h) atomicAdd(&acc_h[rel * n_tab + tt], h);
+                if (d) atomicAdd(&acc_d[rel * n_tab + tt], d);
+            } else {
+                const unsigned long long at = (r_lo + rel) * N + t0 + tt;
+                if (h) atomicAdd(&hits[at], (unsigned long long)h);
+                if (d) atomicAdd(&depth[at], (unsigned long long)d);
+            }
+        };
+        for (uint32_t tt = 0; tt < n_tab; tt++) {
+            const uint8_t *__restrict__ T = tabs.t[tt];
+            uint32_t cv[16];                                 // all gathers of a table in flight before the first is used
+#pragma unroll
+            for (int j = 0; j < 16; j++) cv[j] = ((q.ok >> j) & 1u) ? (uint32_t)T[a[j]] : 0u;   // a count of 0 lies in no window (min >= 1)
+            if (wave_one) {
+                uint32_t h = 0, d = 0;
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const bool in = cv[j] >= min_count && cv[j] <= max_count;
+                    h += in ? 1u : 0u; d += in ? cv[j] : 0u;
+                }
+                for (int s = 32; s; s >>= 1) { h += __shfl_down(h, s, 64); d += __shfl_down(d, s, 64); }
+                if (lane == 0u) add(ref, tt, h, d);
+            } else if (has) {
+                uint32_t cur = rr_first, h = 0, d = 0;
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    if ((q.ok >> j) & 1u) {
+                        if (rr[j] != cur) { add(cur, tt, h, d); h = 0; d = 0; cur = rr[j]; }
+                        const bool in = cv[j] >= min_count && cv[j] <= max_count;
+                        h += in ? 1u : 0u; d += in ? cv[j] : 0u;
+                    }
+                }
+                add(cur, tt, h, d);
+            }
+        }
+    }
+    __syncthreads();
+    {
+        const unsigned long long span = r_hi - r_lo + 1ull;
+        const uint32_t n_acc = (uint32_t)(span < QACC_RECS ? span : QACC_RECS) * n_tab;
+        for (uint32_t i = threadIdx.x; i < n_acc; i += QNT) {
+            const uint32_t h = acc_h[i], d = acc_d[i];
+            const unsigned long long at = (r_lo + i / n_tab) * N + t0 + i % n_tab;
+            if (h) atomicAdd(&hits[at], (unsigned long long)h);
+            if (d) atomicAdd(&depth[at], (unsigned long long)d);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ host side -------------------
+size_t query_workspace(uint32_t n_chunks, uint8_t *base, PartBuffers *view, QueryBuffers *qview) {
+    PartBuffers unused_p, &b = view ? *view : unused_p;
+    QueryBuffers unused_q, &qb = qview ? *qview : unused_q;
+    size_t o = 0;
+    const auto place = [&](auto *&p, size_t bytes) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + o);
+        o = (o + bytes + 255) & ~(size_t)255;
+    };
+    b = PartBuffers{};
+    place(b.codes, (size_t)n_chunks * SLOT_CODE_WORDS * 4);
+    place(b.restarts, (size_t)n_chunks * SLOT_RST_WORDS * 4);
+    place(b.n_bases, (size_t)n_chunks * 4);
+    place(qb.slot_count, (size_t)n_chunks * 4);
+    place(qb.slot_first, (size_t)n_chunks * 8);
+    place(b.signals, sizeof(PartSignals));
+    b.side_n = &b.signals->side_n;
+    b.flags = b.signals->flags;
+    return o;
+}
+
+void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,
+                       const Carry *carry, uint64_t p_done, unsigned long long *P, hipStream_t s) {
+    hipLaunchKernelGGL(k_query_count, dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.restarts,
+                       (const uint32_t *)b.n_bases, st2, pl.k, qb.slot_count, (const uint32_t *)b.flags);
+    hipLaunchKernelGGL(k_query_scan, dim3(1), dim3(QNT), 0, s, (const uint32_t *)qb.slot_count, pl.n_chunks, (unsigned long long)windows_before,
+                       qb.slot_first, recs, carry, (unsigned long long)p_done, P, (const uint32_t *)b.flags);
+}
+
+void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P, const Carry *carry,
+                         const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
+                         unsigned long long *hits, unsigned long long *depth, hipStream_t s) {
+    QueryTables tabs;
+    for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
+#define PK_QUERY_LOOKUP(KT) hipLaunchKernelGGL(k_query_lookup<KT>, dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.restarts, \
+                                               (const uint32_t *)b.n_bases, st2, pl.k, (const unsigned long long *)qb.slot_first, P, carry, tabs, n_tab, N, t0,  \
+                                               min_count, max_count, hits, depth, (const uint32_t *)b.flags)
+    if (pl.k <= 15) PK_QUERY_LOOKUP(uint32_t);
+    else PK_QUERY_LOOKUP(uint64_t);
+#undef PK_QUERY_LOOKUP
+}
+
+}  // namespace pk

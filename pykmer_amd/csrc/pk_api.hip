@@ -1,7 +1,7 @@
 // pk_api.hip -- host side of the C-ABI declared in include/pykmer_hip.h.
 // Owns device memory, streams and events (every allocation of the library is made here) and sequences the kernels of the
-// indexer (kmer_count.hip, kmer_pack.hip, kmer_fuse.hip, kmer_part.hip, fastq.hip) and of the merger (gram_scan.hip,
-// gram_spectrum.hip, gram_occ.hip).  No kernel is defined in this file.
+// indexer (kmer_count.hip, kmer_pack.hip, kmer_fuse.hip, kmer_part.hip, fastq.hip), of the query path (kmer_query.hip) and of
+// the merger (gram_scan.hip, gram_spectrum.hip, gram_occ.hip).  No kernel is defined in this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -278,12 +278,13 @@ struct Events {
     hipEvent_t part_end = nullptr;                                 // bucket layout and level 2 end here, the bucket count begins
     hipEvent_t bucket_end = nullptr;
     hipEvent_t final_begin = nullptr, final_end = nullptr;         // pk_indexer_finish
+    hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // query mode: the kernels of kmer_query.hip
     Events() = default;
     Events(const Events &) = delete;
     ~Events() { for (hipEvent_t *e : all()) if (*e) hipEventDestroy(*e); }
-    std::array<hipEvent_t *, 12> all() {
+    std::array<hipEvent_t *, 14> all() {
         return {&reset_begin, &reset_end, &scan_begin, &scan_end, &squeeze_begin, &squeeze_end, &sort_begin, &sort_end, &part_end, &bucket_end,
-                &final_begin, &final_end};
+                &final_begin, &final_end, &lookup_begin, &lookup_end};
     }
 };
 }  // namespace
@@ -333,6 +334,14 @@ struct pk_indexer {
     uint64_t fq_need = 0;
     bool fq_failed = false;
     std::string fq_err;
+    // query mode (pk_query_create): no table of its own; every valid window is looked up in the caller's tables and
+    // tallied per record.  q_P, q_hits and q_depth are sized with the record array and grown with it (ensure_recs).
+    bool query = false;
+    std::vector<const uint8_t *> q_tables;                  // the caller's device tables; they stay across resets
+    int q_min = 1, q_max = 255;
+    DevBuf<unsigned long long> q_P;                         // P[r]: valid windows of the stream before record r
+    DevBuf<unsigned long long> q_hits, q_depth;             // row-major [record][table]
+    uint64_t q_windows = 0, q_p_done = 0;                   // valid windows / final entries of P before the next feed
 
     uint64_t recs_cap() const { return recs.bytes / sizeof(DevRec); }
     uint64_t fq_recs_cap() const { return fq_recs.bytes / sizeof(FqRec); }
@@ -352,6 +361,9 @@ static int ix_reset(pk_indexer *ix) {
     HIPCHK(hipMemcpyAsync(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
     ix->tail_on_host = false;
     if (ix->recs.p) HIPCHK(hipMemsetAsync(ix->recs.p, 0, ix->recs.bytes, ix->stream));
+    for (DevBuf<unsigned long long> *b : {&ix->q_P, &ix->q_hits, &ix->q_depth})
+        if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
+    ix->q_windows = ix->q_p_done = 0;
     HIPCHK(hipEventRecord(ix->ev.reset_end, ix->stream));
     ix->zero_timed = false;
     ix->t_zero = 0;
@@ -393,9 +405,20 @@ static void hist_with_zeros(const unsigned long long *h, uint64_t n, uint64_t hi
 
 extern "C" void pk_indexer_destroy(pk_indexer *ix) { delete ix; }
 
-extern "C" int pk_indexer_create(pk_indexer **out, int k, int device) { return pk_indexer_create_slice(out, k, device, 0, 1); }
+static int create_indexer(pk_indexer **out, int k, int device, int slice_index, int n_slices, bool query);
+
+extern "C" int pk_indexer_create(pk_indexer **out, int k, int device) { return create_indexer(out, k, device, 0, 1, false); }
 
 extern "C" int pk_indexer_create_slice(pk_indexer **out, int k, int device, int slice_index, int n_slices) {
+    return create_indexer(out, k, device, slice_index, n_slices, false);
+}
+
+extern "C" int pk_query_create(pk_indexer **out, int k, int device) {
+    if (k > 17) return fail(PK_ERR_ARG, "a query takes kmer_len <= 17 (one unsliced table), got %d", k);
+    return create_indexer(out, k, device, 0, 1, true);
+}
+
+static int create_indexer(pk_indexer **out, int k, int device, int slice_index, int n_slices, bool query) {
     if (!out) return fail(PK_ERR_ARG, "null output pointer");
     *out = nullptr;
     int slice_bits = 0;
@@ -407,9 +430,10 @@ extern "C" int pk_indexer_create_slice(pk_indexer **out, int k, int device, int 
     std::unique_ptr<pk_indexer> ix(new pk_indexer());        // a failure below destroys what was built so far
     ix->k = k; ix->device = device; ix->slice_bits = slice_bits; ix->slice_index = slice_index;
     ix->n = 1ULL << (2 * k - slice_bits);
+    ix->query = query;
     HIPCHK(hipStreamCreateWithFlags(&ix->stream.s, hipStreamNonBlocking));
     for (hipEvent_t *e : ix->ev.all()) HIPCHK(hipEventCreate(e));
-    if ((rc = ix->table8.reserve(std::max<uint64_t>(ix->n, 16)))) return rc;
+    if (!query && (rc = ix->table8.reserve(std::max<uint64_t>(ix->n, 16)))) return rc;
     if ((rc = ix->tail.reserve(sizeof(pk_indexer::Tail)))) return rc;
     if ((rc = ix->tail0.reserve(sizeof(pk_indexer::Tail)))) return rc;
     HIPCHK(hipHostMalloc(&ix->pin, sizeof(*ix->pin), hipHostMallocDefault));
@@ -431,6 +455,7 @@ extern "C" int pk_indexer_create_slice(pk_indexer **out, int k, int device, int 
     HIPCHK(hipMemset(ix->hist_rep.p, 0, ix->hist_rep.bytes));
     // room for the records of small inputs from the start: the squeeze pass checks the capacity itself (see feed_piece)
     if ((rc = ix->recs.reserve(4096 * sizeof(DevRec)))) return rc;
+    if (query && (rc = ix->q_P.reserve(4096 * sizeof(unsigned long long)))) return rc;
     part_set_attributes();                               // dynamic-LDS opt-ins, once per process and device
     if ((rc = ix_reset(ix.get()))) return rc;
     *out = ix.release();
@@ -461,7 +486,13 @@ static int ensure_chunks(pk_indexer *ix, uint32_t n_chunks) {
 static int ensure_recs(pk_indexer *ix, uint64_t need) {
     if (need <= ix->recs_cap()) return PK_OK;
     const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, ix->recs_cap() * 2));
-    return ix->recs.grow_keep(cap * sizeof(DevRec), ix->stream);
+    int rc = ix->recs.grow_keep(cap * sizeof(DevRec), ix->stream);
+    if (rc || !ix->query) return rc;
+    // query mode: the window prefix and the accumulators grow with the record array and keep what they hold
+    const size_t row = ix->q_tables.size() * sizeof(unsigned long long);
+    if ((rc = ix->q_P.grow_keep(cap * sizeof(unsigned long long), ix->stream))) return rc;
+    if ((rc = ix->q_hits.grow_keep(cap * row, ix->stream))) return rc;
+    return ix->q_depth.grow_keep(cap * row, ix->stream);
 }
 
 // one feed of at most FEED_MAX bytes: structure pass -> squeeze -> bucket layout -> fused k-mer assembly + level-1
@@ -490,7 +521,10 @@ extern "C" int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]) {
     return PK_OK;
 }
 
+static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes);
+
 static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
+    if (ix->query) return query_feed_piece(ix, f, n_bytes);
     const uint32_t n_chunks = (uint32_t)((n_bytes + CHUNK - 1) / CHUNK);
     int rc = ensure_chunks(ix, n_chunks);
     if (rc) return rc;
@@ -574,6 +608,102 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     return PK_OK;
 }
 
+// One feed of a query indexer: the structure pass and the squeeze as above, then the lookup kernels (kmer_query.hip) where
+// feed_piece runs launch_partitioned.  There is no sampled layout, so the only flag is 2 (the squeeze backed out): the
+// record array, the window prefix and the accumulators grow, and the squeeze and the lookups run again.
+static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
+    if (ix->q_tables.empty()) return fail(PK_ERR_STATE, "pk_query_set_tables comes before the first feed");
+    const uint32_t n_chunks = (uint32_t)((n_bytes + CHUNK - 1) / CHUNK);
+    int rc = ensure_chunks(ix, n_chunks);
+    if (rc) return rc;
+    const PartPlan pl = make_part_plan((uint32_t)ix->k, n_bytes, 0u, 0u);   // the squeeze's launch shape; nothing is partitioned
+    if ((rc = ix->ws.reserve(query_workspace(n_chunks)))) return rc;
+    PartBuffers pb;
+    QueryBuffers qb;
+    query_workspace(n_chunks, ix->ws.p, &pb, &qb);
+    Carry *carry = &ix->tail.p->carry;
+    const Events &ev = ix->ev;
+    const uint32_t N = (uint32_t)ix->q_tables.size();
+    HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
+    launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
+    launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
+    launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, n_chunks, (uint32_t)ix->k, ix->stream);
+    launch_scan_l2(ix->c_l2.p, n_chunks, carry, ix->c_l2s.p, ix->t_l2.p, (uint32_t)ix->k, ix->stream);
+    HIPCHK(hipEventRecord(ev.scan_end, ix->stream));
+    uint64_t squeezed_cap = 0;
+    for (int attempt = 0;; attempt++) {
+        if (attempt) HIPCHK(hipMemsetAsync(pb.signals, 0, sizeof(PartSignals), ix->stream));
+        squeezed_cap = ix->recs_cap();
+        HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream));
+        launch_squeeze(pl, pb, f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, ix->recs.p, squeezed_cap, carry,
+                       ix->stream);
+        HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
+        HIPCHK(hipEventRecord(ev.lookup_begin, ix->stream));
+        launch_query_scan(pl, pb, qb, ix->c_l2s.p, ix->q_windows, ix->recs.p, carry, ix->q_p_done, ix->q_P.p, ix->stream);
+        for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
+            launch_query_lookup(pl, pb, qb, ix->c_l2s.p, ix->q_P.p, carry, ix->q_tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
+                                (uint32_t)ix->q_min, (uint32_t)ix->q_max, ix->q_hits.p, ix->q_depth.p, ix->stream);
+        HIPCHK(hipEventRecord(ev.lookup_end, ix->stream));
+        HIPCHK(hipGetLastError());
+        volatile uint32_t *got = ix->pin->flags;
+        HIPCHK(hipMemcpyAsync(ix->pin->flags, pb.flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
+        if ((rc = read_tail(ix))) return rc;
+        if (!got[0]) break;
+        if (got[0] != 2u || attempt >= 3) return fail(PK_ERR_HIP, "the query feed did not settle (internal error, flag %u)", got[0]);
+        if ((rc = ensure_recs(ix, ix->pin->tail.carry.n_recs))) return rc;
+    }
+    if (ix->pin->tail.carry.n_recs > squeezed_cap)
+        return fail(PK_ERR_HIP, "feed looked up without its squeeze: %llu records, %llu slots (internal error)",
+                    (unsigned long long)ix->pin->tail.carry.n_recs, (unsigned long long)squeezed_cap);
+    const uint64_t recs_before = ix->n_recs;
+    ix->n_recs = ix->pin->tail.carry.n_recs;
+    ix->q_windows = ix->pin->tail.carry.num_kmers;
+    ix->q_p_done = ix->n_recs;
+    if ((rc = ensure_recs(ix, ix->n_recs + 2 * (ix->n_recs - recs_before) + 1024))) return rc;
+    float scan = 0, squeeze_ms = 0, lookup = 0;
+    HIPCHK(hipEventElapsedTime(&scan, ev.scan_begin, ev.scan_end));
+    HIPCHK(hipEventElapsedTime(&squeeze_ms, ev.squeeze_begin, ev.squeeze_end));
+    HIPCHK(hipEventElapsedTime(&lookup, ev.lookup_begin, ev.lookup_end));
+    ix->t_scan += scan * 1e-3; ix->t_squeeze += squeeze_ms * 1e-3; ix->t_part += lookup * 1e-3;
+    ix->feeds++;
+    ix->bytes_fed += n_bytes;
+    return PK_OK;
+}
+
+extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables, int N, int min_count, int max_count) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the tables are set before the first feed (reset the indexer first)");
+    if (N < 1 || !dev_tables) return fail(PK_ERR_ARG, "need at least one table");
+    if (min_count < 1 || max_count > 255 || min_count > max_count) return fail(PK_ERR_ARG, "count window must satisfy 1 <= min <= max <= 255, got %d-%d", min_count, max_count);
+    for (int i = 0; i < N; i++)
+        if (!dev_tables[i]) return fail(PK_ERR_ARG, "table %d is a null pointer", i);
+    HIPCHK(hipSetDevice(ix->device));
+    ix->q_tables.assign((const uint8_t *const *)dev_tables, (const uint8_t *const *)dev_tables + N);
+    ix->q_min = min_count; ix->q_max = max_count;
+    // the accumulators of an empty stream for this many tables (a reset zeroed them, but N may have changed)
+    const size_t need = ix->recs_cap() * (size_t)N * sizeof(unsigned long long);
+    for (DevBuf<unsigned long long> *b : {&ix->q_hits, &ix->q_depth}) {
+        int rc = b->reserve(need);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
+    }
+    return PK_OK;
+}
+
+extern "C" int pk_query_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
+    if (ix->n_recs > recs_cap) return fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)ix->n_recs, (unsigned long long)recs_cap);
+    if (ix->n_recs == 0) return PK_OK;
+    if (!hits_out || !depth_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const size_t n = ix->n_recs * ix->q_tables.size() * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(hits_out, ix->q_hits.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(depth_out, ix->q_depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
 
 // ================================================================== FASTQ front end ============
 static const char *fq_rule_text(uint32_t rule) {
@@ -761,13 +891,13 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
         }
     }
     if (!ix->finished) {
-        if (ix->tail_on_host && !ix->table_fresh) {
+        if (ix->tail_on_host && (!ix->table_fresh || ix->query)) {
             // the usual case: the last feed's read-back already holds the totals and the histogram (kept up to date by
             // k_bucket_count / k_apply_side: no pass over the table), and every kernel has finished -- nothing to do
             ix->t_final = 0;
         } else {
             HIPCHK(hipEventRecord(ix->ev.final_begin, ix->stream));
-            if (ix->table_fresh) {                           // nothing was fed: the table is all zero
+            if (ix->table_fresh && !ix->query) {             // nothing was fed: the table is all zero
                 HIPCHK(hipMemsetAsync(ix->table8.p, 0, ix->table8.bytes, ix->stream));
                 ix->table_fresh = false;
             }
@@ -788,7 +918,10 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
     if (num_kmers_out) *num_kmers_out = c.num_kmers;
     if (total_bp_out) *total_bp_out = c.total_bp;
     if (n_recs_out) *n_recs_out = c.n_recs;
-    if (hist256_out) hist_with_zeros(ix->pin->tail.hist, ix->n, hist256_out);
+    if (hist256_out) {
+        if (ix->query) memset(hist256_out, 0, 256 * sizeof(uint64_t));   // no table of its own
+        else hist_with_zeros(ix->pin->tail.hist, ix->n, hist256_out);
+    }
     return PK_OK;
 }
 
@@ -817,12 +950,14 @@ extern "C" int pk_indexer_records(pk_indexer *ix, pk_record *recs_out, uint64_t 
 
 extern "C" int pk_indexer_table_to_host(pk_indexer *ix, uint8_t *table_out) {
     if (!ix || !table_out) return fail(PK_ERR_ARG, "null argument");
+    if (ix->query) return fail(PK_ERR_STATE, "a query indexer holds no table");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     return bounce_copy(ix->table8.p, table_out, ix->n, false, ix->device);
 }
 
 extern "C" int pk_indexer_table_slice_to_host(pk_indexer *ix, uint8_t *dst, uint64_t offset, uint64_t n_bytes) {
     if (!ix || !dst) return fail(PK_ERR_ARG, "null argument");
+    if (ix->query) return fail(PK_ERR_STATE, "a query indexer holds no table");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     if (offset > ix->n || n_bytes > ix->n - offset) return fail(PK_ERR_ARG, "slice outside the table");
     return bounce_copy(ix->table8.p + offset, dst, n_bytes, false, ix->device);
@@ -830,6 +965,7 @@ extern "C" int pk_indexer_table_slice_to_host(pk_indexer *ix, uint8_t *dst, uint
 
 extern "C" int pk_indexer_table_device(pk_indexer *ix, const void **dev_table_out) {
     if (!ix || !dev_table_out) return fail(PK_ERR_ARG, "null argument");
+    if (ix->query) return fail(PK_ERR_STATE, "a query indexer holds no table");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     *dev_table_out = ix->table8.p;
     return PK_OK;
@@ -837,6 +973,7 @@ extern "C" int pk_indexer_table_device(pk_indexer *ix, const void **dev_table_ou
 
 extern "C" int pk_indexer_table_slice_to_device(pk_indexer *ix, void *dev_dst, uint64_t offset, uint64_t n_bytes) {
     if (!ix || !dev_dst) return fail(PK_ERR_ARG, "null argument");
+    if (ix->query) return fail(PK_ERR_STATE, "a query indexer holds no table");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     if (offset > ix->n || n_bytes > ix->n - offset) return fail(PK_ERR_ARG, "slice outside the table");
     HIPCHK(hipSetDevice(ix->device));

@@ -101,6 +101,25 @@ void launch_walk_sort(const PartPlan &pl, const PartBuffers &b, const L2 *st2, c
 int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint64_t n_bytes, uint32_t stride, const Carry *carry, uint8_t *table8,
                        unsigned long long *hist, unsigned long long *hist_rep, bool fresh, const PartEvents &ev, hipStream_t s);
 
+// kmer_query.hip -- per-record k-mer hits against device-resident tables.  The query path squeezes a feed
+// like the indexer and then runs these where the indexer runs launch_partitioned.
+constexpr uint32_t QUERY_MAX_TABLES = 16;                   // tables per lookup launch; more are looked up group by group
+struct QueryTables { const uint8_t *t[QUERY_MAX_TABLES]; };
+struct QueryBuffers {
+    uint32_t *slot_count;                                   // valid windows per slot
+    unsigned long long *slot_first;                         // stream ordinal of a slot's first valid window
+};
+// the workspace of a query feed: the squeezed text and the signals (the PartBuffers fields the squeeze uses; the rest stay
+// null) and the per-slot window counts
+size_t query_workspace(uint32_t n_chunks, uint8_t *base = nullptr, PartBuffers *view = nullptr, QueryBuffers *qview = nullptr);
+// per-slot window counts -> slot_first; P[p_done .. carry->n_recs) from recs[].n_valid (P[r] = valid windows before record r)
+void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,
+                       const Carry *carry, uint64_t p_done, unsigned long long *P, hipStream_t s);
+// tables[0 .. n_tab) are columns t0 .. t0 + n_tab of the row-major [record][N] u64 accumulators hits / depth
+void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P, const Carry *carry,
+                         const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
+                         unsigned long long *hits, unsigned long long *depth, hipStream_t s);
+
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it
     uint64_t line;           // line terminators seen (the role of the open line is line & 3)

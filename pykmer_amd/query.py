@@ -1,0 +1,251 @@
+"""Query host side: a FASTA / FASTQ file and N `.kin[.bgz]` tables in, per-record k-mer hits out.
+
+For every record r of the query (file order; records without a valid window included) and every table t:
+    hits[r][t]  = number of valid windows of r whose canonical k-mer has min_count <= T_t[a] <= max_count
+    depth[r][t] = sum of T_t[a] over those windows (depth / hits = mean count of the matched k-mers)
+The reference has no such tool (its README stops at the distance matrix); the text is parsed exactly as the indexer parses
+it (pk_query_* in include/pykmer_hip.h: the indexer's structure pass and squeeze, then lookups instead of counting).
+
+The tables are staged in HBM the way the merger stages them (raw `.kin` mapped, `.kin.bgz` inflated block-parallel).  When
+they do not all fit the HBM budget they are staged in groups and the query is streamed once per group: the columns are
+independent, so the results concatenate.  One device (PK_DEVICE).
+"""
+import argparse
+import json
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, bgzf
+from .header import Header
+from .indexer import _Input, _mark
+from .merger import DEFAULT_THREADS, EXTS, _Encoder
+
+MAX_KMER_LEN = 17                   # one unsliced 4^k-byte table per sample
+WORKSPACE_RESERVE = 4 << 30         # of the free HBM, kept for the feed's workspace when the budget is taken from mem_info
+
+
+def _name_of(table) -> str:
+    return str(getattr(table, "index_file", None) or getattr(table, "project_name", table))
+
+
+def load_header(path, device: int = 0) -> Header:
+    """The Header of one `.kin[.bgz]`; what the Header refuses (no metadata, an even kmer_len) is reported with the file's name."""
+    kins = str(path)
+    if not kins.endswith(EXTS[:2]):
+        raise ValueError(f"all tables must be .{Header.IND_EXT}[.{Header.COMP_EXT}] files: {kins}")
+    if not os.path.exists(kins):
+        raise ValueError(f"table file does not exist: {kins}")
+    try:
+        return Header(kins, index_file=kins, device=device)
+    except AssertionError as exc:
+        raise ValueError(f"{kins}: not a usable k-mer table (kmer_len must be positive and odd): {exc}") from exc
+
+
+def validate(tables: Sequence, min_count: int, max_count: int) -> int:
+    """The checks that need no device; returns the common kmer_len.  `tables`: Headers (or anything with kmer_len)."""
+    if not 1 <= min_count <= max_count <= 255:
+        raise ValueError(f"the count window must satisfy 1 <= min <= max <= 255, got {min_count}-{max_count}")
+    if len(tables) < 1:
+        raise ValueError("a query needs at least one table")
+    kmer_len = None
+    for t in tables:
+        k = int(t.kmer_len)
+        if k < 1 or k % 2 == 0:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} is not positive and odd")
+        if k > MAX_KMER_LEN:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} is beyond the query path (at most {MAX_KMER_LEN}: one unsliced table)")
+        if kmer_len is None:
+            kmer_len = k
+        elif k != kmer_len:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} differs from the {kmer_len} of {_name_of(tables[0])}")
+    return kmer_len
+
+
+def table_groups(n_tables: int, table_bytes: int, budget: int) -> List[Tuple[int, int]]:
+    """[lo, hi) index ranges of the tables staged together: as many as fit `budget` bytes, at least one."""
+    per = max(1, int(budget) // max(1, int(table_bytes)))
+    return [(lo, min(n_tables, lo + per)) for lo in range(0, n_tables, per)]
+
+
+class Staged:
+    """Device pointers of one group of tables and the buffers behind them (none for tables that were resident already)."""
+
+    def __init__(self, ptrs, bufs=()):
+        self.ptrs, self.bufs = list(ptrs), list(bufs)
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) -> Staged:
+    """Whole tables into HBM, `threads` at a time, as merger._flat_partial stages slices; a merger.ResidentTable is used
+    where it lies."""
+    if all(hasattr(t, "device_slice") for t in tables):
+        return Staged([t.device_slice(t.first, t.first + t.n) for t in tables])
+    assert not any(hasattr(t, "device_slice") for t in tables), "resident and file-backed tables cannot be mixed in one group"
+    n = tables[0].data_size
+    bufs = [_lib.DeviceBuffer(n, device) for _ in tables]
+    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, len(tables))))
+    try:
+        with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+            list(pool.map(lambda i: bufs[i].upload(tables[i].read_table_slice(0, n, threads=io_threads)), range(len(tables))))
+    except BaseException:
+        for b in bufs:
+            b.free()
+        raise
+    return Staged([b.ptr for b in bufs], bufs)
+
+
+def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True) -> dict:
+    """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
+    same query only add columns)."""
+    src = _Input(query_file, keep=first, quiet=not first)
+    with _lib.QueryIndexer(kmer_len, device=device, fmt=src.fmt) as q:
+        q.set_tables(ptrs, min_count, max_count)
+        for piece in src.pieces():
+            q.feed(piece)
+        fin = q.finish()
+        recs = q.records(fin["n_records"])
+        hits, depth = q.results(fin["n_records"])
+        timings = q.timings()
+    out = {"seq_len": recs["seq_len"].astype(np.uint64), "n_valid": recs["n_valid_kmers"].astype(np.uint64), "hits": hits.copy(),
+           "depth": depth.copy(), "num_kmers": fin["num_kmers"], "total_bp": fin["total_bp"], "timings": timings}
+    if first:
+        out["names"] = [nm.decode("utf-8", "replace") for nm in src.names(recs)]
+    return out
+
+
+def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
+                  threads: int = DEFAULT_THREADS, stage=None, run=None) -> dict:
+    """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
+    merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
+    kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
+
+    `hbm_budget` (bytes; default PK_MERGE_HBM_BUDGET, else 80 % of the free HBM less the feed's workspace) bounds the tables
+    staged beside each other; more are staged group after group, the query streamed once per group.
+    `stage(tables, device)` -> Staged and `run(query_file, kmer_len, ptrs, min_count, max_count, device, first)` -> dict
+    default to stage_tables / run_query (the CPU-only tests substitute both)."""
+    tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
+    kmer_len = validate(tables, min_count, max_count)
+    stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
+    run = run or run_query
+    if all(hasattr(t, "device_slice") for t in tables):
+        groups = [(0, len(tables))]                          # resident already: nothing to fit
+    else:
+        budget = hbm_budget or int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or \
+            max(0, int(_lib.mem_info(device)[0] * 0.8) - WORKSPACE_RESERVE)
+        groups = table_groups(len(tables), 4 ** kmer_len, budget)
+    result, lookup_s = None, 0.0
+    for g, (lo, hi) in enumerate(groups):
+        staged = stage(tables[lo:hi], device)
+        _mark(f"tables {lo}..{hi - 1} staged")
+        try:
+            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0)
+        finally:
+            staged.free()
+        _mark(f"query streamed against tables {lo}..{hi - 1}")
+        lookup_s += float(part.get("timings", {}).get("lookup_s", 0.0))
+        if result is None:
+            result = part
+        else:
+            assert np.array_equal(part["n_valid"], result["n_valid"]) and np.array_equal(part["seq_len"], result["seq_len"]), \
+                "query changed between table groups"
+            result["hits"] = np.concatenate([result["hits"], part["hits"]], axis=1)
+            result["depth"] = np.concatenate([result["depth"], part["depth"]], axis=1)
+    result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
+    return result
+
+
+def kmq_paths(project_name: str) -> Tuple[Path, Path, Path]:
+    return Path(f"{project_name}.kmq"), Path(f"{project_name}.kmq.json"), Path(f"{project_name}.kmq.tsv")
+
+
+def write_kmq(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
+    """`<project>.kmq` (np.savez_compressed), `.kmq.json` and `.kmq.tsv`, each through `.tmp` + rename."""
+    kmq, meta, tsv = kmq_paths(project_name)
+    hits = np.ascontiguousarray(result["hits"], dtype=np.uint64)
+    depth = np.ascontiguousarray(result["depth"], dtype=np.uint64)
+    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
+    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
+    names = [n.strip() for n in result["names"]]
+    assert hits.shape == depth.shape == (len(names), len(columns)) and n_valid.shape == seq_len.shape == (len(names),)
+    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
+              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data}
+    print(f"saving {meta}")
+    tmp = Path(f"{meta}.tmp")
+    with tmp.open(mode="wt") as fhd:
+        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
+    tmp.rename(meta)
+    print(f"saving {tsv}")
+    tmp = Path(f"{tsv}.tmp")
+    with tmp.open(mode="wt") as fhd:
+        fhd.write("\t".join(["record", "seq_len", "n_valid"] + [str(c) for c in columns]) + "\n")
+        for r, name in enumerate(names):
+            fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in hits[r]]) + "\n")
+    tmp.rename(tsv)
+    print(f"saving {kmq}")
+    tmp = Path(f"{kmq}.tmp")
+    with tmp.open(mode="wb") as fhd:
+        np.savez_compressed(fhd, hits=hits, depth=depth, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
+                            min_count=np.int64(result["min_count"]), max_count=np.int64(result["max_count"]))
+    tmp.rename(kmq)
+
+
+def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
+          threads: int = DEFAULT_THREADS, hbm_budget: int = None) -> dict:
+    """The CLI's work: validate, query, write the three files; returns query_records' result."""
+    for f in kmq_paths(project_name):
+        if f.exists():
+            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+    if not os.path.exists(query_file):
+        raise ValueError(f"query file does not exist: {query_file}")
+    if len(indexes) < 1:
+        raise ValueError("a query needs at least one table")
+    data, headers = [], []
+    for pos, kin in enumerate(indexes):
+        print(f"verifying {kin}")
+        header = load_header(kin, device)
+        kins = str(kin)
+        desc = Path((kins[:-(len(Header.COMP_EXT) + 1)] if kins.endswith("." + Header.COMP_EXT) else kins) + "." + Header.DESC_EXT)
+        headers.append(header)
+        data.append({"pos": pos, "index_file": Path(kin), "description_file": desc, "header": header})
+    validate(headers, min_count, max_count)
+    _mark("tables verified")
+    result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads)
+    columns = [str(h.project_name) for h in headers]
+    for v in data:
+        v["header"] = v["header"].to_dict(lean=True)
+    write_kmq(project_name, result, query_file, data, columns)
+    _mark("files renamed")
+    return result
+
+
+def build_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Per-record k-mer hits of a FASTA/FASTQ file against kmer databases.")
+    parser.add_argument("Project_Name", metavar="P", type=str, help="Project name (prefix of the output files)")
+    parser.add_argument("Query", metavar="Q", type=str, help="queries.fa|.fq[.gz|.bgz]")
+    parser.add_argument("Kmer_N", metavar="K", type=Path, nargs="+", help="List of kin files")
+    parser.add_argument("--min-count", type=int, default=1, help="Minimum Kmer Count [1]")
+    parser.add_argument("--max-count", type=int, default=255, help="Maximum Kmer Count [255]")
+    parser.add_argument("--threads", type=int, default=DEFAULT_THREADS, help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
+    return parser
+
+
+def main(argv: List[str] = None) -> None:
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    try:
+        result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
+                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads)
+    except ValueError as exc:
+        print(f"error: {exc}", file=sys.stderr)
+        sys.exit(1)
+    hits = result["hits"]
+    print(f"{len(result['names'])} records, {int(result['n_valid'].sum()):,d} k-mers, {hits.shape[1]} tables, "
+          f"{result['n_groups']} table group(s)")

@@ -1,0 +1,125 @@
+"""Times the query path (kmer_query.hip) at k = 15 against N = 13 tables that lie in HBM, the query text in HBM too.
+
+Two query shapes: the 800 Mbp synthetic genome of bench.py (synth.c2) and a read set of 400 000 records of 1 kbp
+(synth.generate(34, 400_000_000, 400_000), as tools/reads_probe.py).  The tables are counted on the GPU from 13 members of
+synth.family and copied to buffers of their own.  Per shape: one warm-up, then the median of 5 timed runs of
+reset + feed_device + finish + results (wall clock around calls that block until the device is done), and the library's own
+HIP-event times of the structure pass, the squeeze and the lookup kernels (pk_indexer_timings) of the last run.
+
+    python tools/query_bench.py [out.json]     both shapes, then one `rocprofv3 --kernel-trace --stats` run of a child
+                                               (`--once genome`), whose kernel stats go to profiles/query_genome_kernel_stats.csv
+    python tools/query_bench.py --once SHAPE   warm-up + one run of one shape (what the profiled child runs)
+    PK_QUERY_BENCH_BP / PK_QUERY_BENCH_TABLE_BP scale the genome and the table genomes down for a rehearsal.
+
+Writes profiles/query_k15_n13.json (or out.json)."""
+import csv
+import glob
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+import synth  # noqa: E402
+from pykmer_amd import _lib  # noqa: E402
+
+K, N = 15, 13
+
+
+def stage_tables(table_bp: int):
+    bufs = []
+    with _lib.Indexer(K) as ix:
+        for i in range(N):
+            fa, _ = synth.family(i, table_bp)
+            ix.reset()
+            ix.feed(fa)
+            ix.finish()
+            b = _lib.DeviceBuffer(4 ** K)
+            ix.table_slice_to_device(b.ptr, 0, 4 ** K)
+            bufs.append(b)
+    return bufs
+
+
+def shapes(genome_bp: int):
+    yield "genome", lambda: synth.c2(genome_bp, seed=2)
+    yield "reads", lambda: synth.generate(34, genome_bp // 2, max(1, genome_bp // 2000))
+
+
+def run_shape(make, ptrs, runs: int):
+    fa, bp = make()
+    text = _lib.DeviceBuffer(len(fa) + 64)
+    text.upload(np.asarray(fa))
+    try:
+        with _lib.QueryIndexer(K) as q:
+            times = []
+            for i in range(runs + 1):                                     # the first run warms up: allocations, code load
+                q.reset()
+                q.set_tables(ptrs, 1, 255)
+                t0 = time.perf_counter()
+                q.feed_device(text.ptr, len(fa))
+                fin = q.finish()
+                hits, depth = q.results(fin["n_records"])
+                if i:
+                    times.append(time.perf_counter() - t0)
+            t = q.timings()
+        med = statistics.median(times) if times else float("nan")
+        front = t["scan_s"] + t["squeeze_s"]
+        return {"bp": int(bp), "text_bytes": len(fa), "records": fin["n_records"], "windows": fin["num_kmers"], "tables": len(ptrs),
+                "runs": times, "median_s": med, "best_s": min(times) if times else med, "bp_per_s": bp / med,
+                "lookups_per_s": fin["num_kmers"] * len(ptrs) / med,
+                "device_s": {"structure_pass": t["scan_s"], "squeeze": t["squeeze_s"], "lookup_kernels": t["lookup_s"]},
+                "lookup_share_of_device_time": t["lookup_s"] / (front + t["lookup_s"]),
+                "lookup_over_structure_plus_squeeze": t["lookup_s"] / front,
+                "lookups_per_s_kernels_only": fin["num_kmers"] * len(ptrs) / t["lookup_s"],
+                "hit_fraction_table0": float(hits[:, 0].sum()) / max(1, fin["num_kmers"])}
+    finally:
+        text.free()
+
+
+def kernel_stats(argv, dest):
+    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    d = tempfile.mkdtemp(prefix="qprof")
+    subprocess.run([prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "q", "--"] + argv, check=True, timeout=1500, cwd=ROOT)
+    path = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)[0]
+    with open(path) as fh:
+        rows = list(csv.DictReader(fh))
+    shutil.copy(path, dest)
+    shutil.rmtree(d, ignore_errors=True)
+    return rows
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    genome_bp = int(os.environ.get("PK_QUERY_BENCH_BP", 800_000_000))
+    table_bp = int(os.environ.get("PK_QUERY_BENCH_TABLE_BP", 40_000_000))
+    bufs = stage_tables(table_bp)
+    ptrs = [b.ptr for b in bufs]
+    if "--once" in sys.argv:
+        run_shape(dict(shapes(genome_bp))[args[0]], ptrs, 1)
+        return
+    out = {"k": K, "n_tables": N, "table_genome_bp": table_bp, "layout": "one 4^k-byte table per sample (not interleaved)",
+           "method": "1 warm-up + median of 5 runs of reset/feed_device/finish/results; device_s from HIP events (pk_indexer_timings)"}
+    for name, make in shapes(genome_bp):
+        out[name] = run_shape(make, ptrs, 5)
+        print(name, json.dumps(out[name]), flush=True)
+    for b in bufs:
+        b.free()
+    rows = kernel_stats([sys.executable, os.path.abspath(__file__), "--once", "genome"], os.path.join(ROOT, "profiles", "query_genome_kernel_stats.csv"))
+    out["genome_kernel_trace_ms_per_call"] = {r["Name"].split("(")[0][:60]: round(float(r["AverageNs"]) / 1e6, 4) for r in rows
+                                               if "k_query" in r["Name"] or "k_squeeze" in r["Name"]}
+    path = args[0] if args else os.path.join(ROOT, "profiles", "query_k15_n13.json")
+    with open(path + ".tmp", "w") as fh:
+        json.dump(out, fh, indent=1)
+    os.replace(path + ".tmp", path)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
