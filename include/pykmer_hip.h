@@ -209,6 +209,29 @@ int pk_spectrum_device_accumulate(const void *const *dev_tables, int N, uint64_t
 int pk_occgram_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, void *dev_accum, int device,
                                  double *kernel_seconds_out);
 
+/* ---- extract: the k-mers behind a condition over N device-resident slices (no reference counterpart: a `jellyfish dump`
+ * / `kmc_tools` style answer).  dev_tables lists n_present "present" tables, then n_absent "absent" ones
+ * (n_present >= 1, n_present + n_absent <= 128), each n_slice bytes whose first byte is address first_addr of the 4^k-byte
+ * table; pointers 16-byte aligned.  With 1 <= min_count <= max_count <= 255, 1 <= min_present <= n_present and
+ * 0 <= max_absent <= n_absent, for every address x of the slice
+ *   p(x) = #{ i present : min_count <= T_i[x] <= max_count }   (the validity test of the pair tally, tools.py:473-475)
+ *   q(x) = #{ j absent  : T_j[x] >= 1 }                        (held at any count: the window does not apply)
+ * and x is selected iff p(x) >= min_present and q(x) <= max_absent.  *n_selected_out always receives the exact number of
+ * selected addresses M of the slice.  If M <= cap, dev_addr_out (device, cap u64) receives the selected addresses
+ * first_addr + offset in ascending order and dev_counts_out (device, cap * n_present bytes) row r = the raw bytes T_i[x_r] of
+ * the present tables, in or out of the window; both 16-byte aligned.  If M > cap the call writes nothing to either array
+ * and returns PK_ERR_RECS_CAP; cap = 0 with both arrays null asks for the count alone (PK_OK).  Bad arguments are
+ * PK_ERR_ARG before anything is queued.  The call keeps one bit per address of the slice (plus 8 bytes per 16384
+ * addresses) in HBM while it runs.
+ * pk_extract_text: m addresses (device, u64) -> m lines of k letters and '\n' at dev_text_out (device, m * (k + 1) bytes,
+ * 16-byte aligned): codes 0,1,2,3 = A,C,G,T, first base in the highest bits, the inverse of
+ * the indexer's encoding (indexer.py:131: weight 4^(k-p-1) for base p; AAACC = 5); 1 <= k <= 32. */
+int pk_extract_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice, uint64_t first_addr,
+                      int min_count, int max_count, int min_present, int max_absent,
+                      void *dev_addr_out, void *dev_counts_out, uint64_t cap, uint64_t *n_selected_out,
+                      int device, double *kernel_seconds_out);
+int pk_extract_text(const void *dev_addr, uint64_t m, int k, void *dev_text_out, int device);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

@@ -63,6 +63,10 @@ _SIGNATURES = {
                                                       ctypes.POINTER(ctypes.c_double)]),
     "pk_occgram_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_double)]),
+    "pk_extract_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_double)]),
+    "pk_extract_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -386,6 +390,29 @@ def occgram_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: in
     secs = ctypes.c_double(0)
     _check(load().pk_occgram_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
     return secs.value
+
+
+def extract_device(dev_ptrs, n_present: int, n_slice: int, first_addr: int, min_count: int, max_count: int, min_present: int,
+                   max_absent: int, dev_addr_out: int = None, dev_counts_out: int = None, cap: int = 0, device: int = 0):
+    """pk_extract_device on device-resident slices (`n_present` present tables first, then the absent ones) ->
+    (n_selected, fits, kernel_seconds).  `fits`: the addresses and count rows were written to the two device arrays
+    (n_selected <= cap); with cap = 0 and no arrays the call only counts and `fits` is False unless nothing is selected."""
+    N = len(dev_ptrs)
+    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    count, secs = ctypes.c_uint64(0), ctypes.c_double(0)
+    rc = load().pk_extract_device(ptrs, int(n_present), N - int(n_present), int(n_slice), int(first_addr), int(min_count), int(max_count),
+                                  int(min_present), int(max_absent), ctypes.c_void_p(dev_addr_out) if dev_addr_out else None,
+                                  ctypes.c_void_p(dev_counts_out) if dev_counts_out else None, int(cap), ctypes.byref(count), device,
+                                  ctypes.byref(secs))
+    if rc != PK_ERR_RECS_CAP:
+        _check(rc)
+    return int(count.value), rc == PK_OK and int(count.value) <= int(cap), secs.value
+
+
+def extract_text(dev_addr: int, m: int, k: int, dev_text_out: int, device: int = 0) -> None:
+    """pk_extract_text: m u64 addresses in HBM -> m lines of k letters + newline in HBM."""
+    _check(load().pk_extract_text(ctypes.c_void_p(dev_addr) if dev_addr else None, int(m), int(k),
+                                  ctypes.c_void_p(dev_text_out) if dev_text_out else None, device))
 
 
 def bgzf_scan(buf: np.ndarray):

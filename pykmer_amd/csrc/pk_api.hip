@@ -1215,6 +1215,72 @@ extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N
     });
 }
 
+// The k-mers behind a presence / absence condition (kmer_extract.hip): count, scan and -- when the caller's arrays hold
+// the total -- write, all queued behind each other; the host only reads the total back.
+extern "C" int pk_extract_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice, uint64_t first_addr,
+                                 int min_count, int max_count, int min_present, int max_absent, void *dev_addr_out, void *dev_counts_out,
+                                 uint64_t cap, uint64_t *n_selected_out, int device, double *kernel_seconds_out) {
+    if (n_present < 1 || n_absent < 0 || n_present > 128 || n_absent > 128 || n_present + n_absent > 128)
+        return fail(PK_ERR_ARG, "an extraction takes 1 to 128 tables, at least one of them present (got %d present, %d absent)", n_present, n_absent);
+    if (min_count < 1 || max_count > 255 || min_count > max_count)
+        return fail(PK_ERR_ARG, "the count window must satisfy 1 <= min <= max <= 255 (got %d-%d)", min_count, max_count);
+    if (min_present < 1 || min_present > n_present) return fail(PK_ERR_ARG, "min_present must lie in 1..%d (got %d)", n_present, min_present);
+    if (max_absent < 0 || max_absent > n_absent) return fail(PK_ERR_ARG, "max_absent must lie in 0..%d (got %d)", n_absent, max_absent);
+    if (!n_selected_out) return fail(PK_ERR_ARG, "null n_selected_out");
+    if (n_slice > (1ull << 40) || first_addr + n_slice < first_addr) return fail(PK_ERR_ARG, "slice of %llu addresses is out of range", (unsigned long long)n_slice);
+    if (cap && (!dev_addr_out || !dev_counts_out || ((uintptr_t)dev_addr_out & 15u) || ((uintptr_t)dev_counts_out & 15u)))
+        return fail(PK_ERR_ARG, "a capacity needs both output arrays, 16-byte aligned");
+    if (cap > (1ull << 40)) return fail(PK_ERR_ARG, "capacity out of range");
+    const int N = n_present + n_absent;
+    const uint32_t n_wg = extract_workgroups(n_slice);
+    DevBuf<uint16_t> d_masks;
+    DevBuf<unsigned long long> d_wg;
+    unsigned long long total = 0;
+    if (n_slice == 0) {
+        if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
+        *n_selected_out = 0;
+        return PK_OK;
+    }
+    int rc = timed_pass(
+        "extract", dev_tables, N, device, kernel_seconds_out,
+        [&](GramCtx &c) -> int {
+            int r = upload_pointers(dev_tables, N)(c);
+            if (!r) r = d_wg.reserve(((size_t)n_wg + 1) * sizeof(unsigned long long));
+            if (!r && cap) r = d_masks.reserve(extract_mask_words(n_slice) * sizeof(uint16_t));
+            return r;
+        },
+        [&](GramCtx &c) {
+            return launch_extract(c.d_ptrs, n_present, n_absent, n_slice, first_addr, min_count, max_count, min_present, max_absent, d_masks.p, d_wg.p,
+                                  (unsigned long long *)dev_addr_out, (uint8_t *)dev_counts_out, cap, c.stream);
+        },
+        [&](GramCtx &c) -> int {
+            HIPCHK(hipMemcpyAsync(&total, d_wg.p + n_wg, sizeof total, hipMemcpyDeviceToHost, c.stream));
+            return PK_OK;
+        });
+    if (rc) return rc;
+    *n_selected_out = total;
+    if (total > cap && (cap || dev_addr_out || dev_counts_out))
+        return fail(PK_ERR_RECS_CAP, "%llu addresses selected, room for %llu", total, (unsigned long long)cap);
+    return PK_OK;
+}
+
+extern "C" int pk_extract_text(const void *dev_addr, uint64_t m, int k, void *dev_text_out, int device) {
+    if (k < 1 || k > 32) return fail(PK_ERR_ARG, "kmer_len must lie in 1..32 (got %d)", k);
+    if (m > (1ull << 40)) return fail(PK_ERR_ARG, "too many addresses");
+    if (m == 0) return PK_OK;
+    if (!dev_addr || !dev_text_out || ((uintptr_t)dev_addr & 7u) || ((uintptr_t)dev_text_out & 15u))
+        return fail(PK_ERR_ARG, "address array (8-byte aligned) and text array (16-byte aligned) must not be null");
+    HIPCHK(hipSetDevice(device));
+    GramCtx *c = nullptr;
+    int rc = gram_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (launch_extract_text((const unsigned long long *)dev_addr, m, k, (uint8_t *)dev_text_out, c->stream))
+        return fail(PK_ERR_HIP, "extract text kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return PK_OK;
+}
+
 extern "C" int pk_gram(const uint8_t *const *tables, int N, uint64_t n, int min_count, int max_count, uint64_t *matrix_out,
                        const int *devices, int n_devices) {
     int rc = check_counts(N, min_count, max_count);

@@ -183,4 +183,16 @@ uint64_t occgram_scratch_bytes(int N, uint64_t n_slice);
 int launch_occgram(const void *const *dev_tables, int N, uint64_t n_slice, unsigned long long *dev_accum, const uint8_t **dev_ptrs,
                    uint8_t *occ_scratch, hipStream_t s);
 
+// kmer_extract.hip -- the addresses that satisfy a presence / absence condition over N slices, and their count rows
+// (DESIGN.md 4.11).  tables: device array of P present, then A absent table pointers (n_slice bytes each, 16-byte aligned).
+// masks: extract_mask_words(n_slice) u16; wg: extract_workgroups(n_slice) + 1 u64, whose last word receives the number
+// selected.  addr_out (u64) / counts_out (P bytes per row) are written only when that number is <= cap; cap = 0: count only.
+uint32_t extract_workgroups(uint64_t n_slice);
+uint64_t extract_mask_words(uint64_t n_slice);
+int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, uint64_t first_addr, int min_count, int max_count, int min_present,
+                   int max_absent, uint16_t *masks, unsigned long long *wg, unsigned long long *addr_out, uint8_t *counts_out, uint64_t cap,
+                   hipStream_t s);
+// m addresses -> m lines of k letters + '\n' (text 16-byte aligned)
+int launch_extract_text(const unsigned long long *addr, uint64_t m, int k, uint8_t *text, hipStream_t s);
+
 }  // namespace pk

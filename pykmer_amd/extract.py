@@ -1,0 +1,297 @@
+"""Extract host side: the k-mers that tell sample groups apart.  P "present" and A "absent" `.kin[.bgz]` tables in, the list
+of k-mers behind the condition out.
+
+With a count window min..max, `min_present` (default P) and `max_absent` (default 0), for every address x in [0, 4^k), the
+canonical k-mer value exactly as a `.kin` is addressed:
+    p(x) = #{ i present : min <= T_i[x] <= max }      (the validity test of the pair tally, tools.py:473-475)
+    q(x) = #{ j absent  : T_j[x] >= 1 }               (an absent table holds x at any count; the window does not apply)
+    x is selected iff p(x) >= min_present and q(x) <= max_absent
+The result is the selected addresses in ascending order and, with each, the P raw bytes T_i[x] of the present tables,
+inside the window or not.  P = 1 and A = 0 is a plain windowed dump of one table.  The reference has no such tool (its
+README stops at the distance matrix); no table is written or changed.
+
+The tables are staged in HBM slice by slice as the merger stages them (merger._staged_pieces); one streaming pass per piece
+(pk_extract_device) compacts the selected addresses and their count rows in HBM, and pk_extract_text turns the addresses
+into letters there.  One device (PK_DEVICE).
+"""
+import argparse
+import json
+import os
+import sys
+from pathlib import Path
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, merger
+from .header import Header
+from .indexer import _mark
+from .merger import DEFAULT_THREADS, _Encoder
+from .query import load_header, _name_of
+
+MAX_TABLES = 128                    # P + A: what one pk_extract_device call takes
+MAX_KMER_LEN = 17                   # one unsliced 4^k-byte table per sample
+PIECE_ALIGN = 2048                  # addresses: what the cuts of a piece are multiples of (and what always fits the output)
+INITIAL_ROWS = 1 << 22              # output rows the first call has room for (fewer if the output budget holds fewer)
+OUTPUT_SHARE = 8                    # the output arrays get 1 / OUTPUT_SHARE of the HBM budget, the staged slices the rest
+
+
+def _kmer_len_of(table) -> int:
+    k = getattr(table, "kmer_len", None)
+    if k is not None:
+        return int(k)
+    size, k = int(table.data_size), 0                        # a merger.ResidentTable knows only its 4^k
+    while 4 ** k < size:
+        k += 1
+    if 4 ** k != size:
+        raise ValueError(f"{_name_of(table)}: a table of {size} bytes is no 4^k")
+    return k
+
+
+def _file_of(table):
+    f = getattr(table, "index_file", None)
+    return os.path.abspath(str(f)) if f else None
+
+
+def kmx_paths(project_name: str) -> Tuple[Path, Path, Path]:
+    return Path(f"{project_name}.kmx"), Path(f"{project_name}.kmx.json"), Path(f"{project_name}.kmx.txt")
+
+
+def validate(present: Sequence, absent: Sequence, min_count: int = 1, max_count: int = 255, min_present: int = None, max_absent: int = 0,
+             project_name: str = None) -> Tuple[int, int]:
+    """The checks that need no device; returns (kmer_len, min_present with its default filled in).  `present` / `absent`:
+    Headers, merger.ResidentTables or anything with kmer_len (or data_size).  `project_name`: also refuse to overwrite its
+    output files."""
+    P, A = len(present), len(absent)
+    if not 1 <= min_count <= max_count <= 255:
+        raise ValueError(f"the count window must satisfy 1 <= min <= max <= 255, got {min_count}-{max_count}")
+    if P < 1:
+        raise ValueError("an extraction needs at least one present table")
+    if P + A > MAX_TABLES:
+        raise ValueError(f"an extraction takes at most {MAX_TABLES} tables, got {P} present + {A} absent")
+    min_present = P if min_present is None else int(min_present)
+    if not 1 <= min_present <= P:
+        raise ValueError(f"min_present must lie in 1..{P} (the present tables), got {min_present}")
+    if not 0 <= int(max_absent) <= A:
+        raise ValueError(f"max_absent must lie in 0..{A} (the absent tables), got {max_absent}")
+    tables = list(present) + list(absent)
+    kmer_len = None
+    for t in tables:
+        k = _kmer_len_of(t)
+        if k < 1 or k % 2 == 0:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} is not positive and odd")
+        if k > MAX_KMER_LEN:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} is beyond the extract path (at most {MAX_KMER_LEN}: one unsliced table)")
+        if kmer_len is None:
+            kmer_len = k
+        elif k != kmer_len:
+            raise ValueError(f"{_name_of(t)}: kmer_len {k} differs from the {kmer_len} of {_name_of(tables[0])}")
+    files = [f for f in map(_file_of, tables) if f]
+    for f in files:
+        if files.count(f) > 1:
+            raise ValueError(f"{f} is named twice: a table is present or absent, and listed once")
+    if project_name is not None:
+        for f in kmx_paths(project_name):
+            if f.exists():
+                raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+    return kmer_len, min_present
+
+
+class DeviceCall:
+    """pk_extract_device on one address range of a staged piece, with output arrays in HBM that grow to the capacity asked
+    for.  call(ptrs, off, n, first_addr, cap) -> (n_selected, None) when more than `cap` addresses are selected, else
+    (n_selected, (addr, counts, text or None)) downloaded.  extract_kmers' `call=` substitutes anything of this shape."""
+
+    def __init__(self, n_present: int, kmer_len: int, min_count: int, max_count: int, min_present: int, max_absent: int, device: int = 0,
+                 text: bool = False):
+        self.P, self.k, self.device, self.text = n_present, kmer_len, device, text
+        self.params = (min_count, max_count, min_present, max_absent)
+        self.cap, self.bufs, self.kernel_seconds = 0, [], 0.0
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.cap, self.bufs = 0, []
+
+    def _reserve(self, cap: int):
+        if cap <= self.cap:
+            return
+        self.free()                                          # first: the old and the new arrays need not fit beside each other
+        sizes = [cap * 8, cap * self.P] + ([cap * (self.k + 1)] if self.text else [])
+        self.bufs = [_lib.DeviceBuffer((s + 15) & ~15, self.device) for s in sizes]
+        self.cap = cap
+
+    def __call__(self, ptrs, off: int, n: int, first_addr: int, cap: int):
+        self._reserve(max(1, cap))
+        count, fits, secs = _lib.extract_device([p + off for p in ptrs], self.P, n, first_addr, *self.params, dev_addr_out=self.bufs[0].ptr,
+                                                dev_counts_out=self.bufs[1].ptr, cap=max(1, cap), device=self.device)
+        self.kernel_seconds += secs
+        if not fits:
+            return count, None
+        _mark(f"addresses {first_addr}..{first_addr + n - 1}: {count} selected")
+        if count == 0:
+            return 0, (np.zeros(0, dtype=np.uint64), np.zeros((0, self.P), dtype=np.uint8), np.zeros((0, self.k + 1), dtype=np.uint8) if self.text else None)
+        text = None
+        if self.text:
+            _lib.extract_text(self.bufs[0].ptr, count, self.k, self.bufs[2].ptr, device=self.device)
+            text = self.bufs[2].download(count * (self.k + 1)).reshape(count, self.k + 1)
+        addr = self.bufs[0].download(count * 8).view(np.uint64)
+        counts = self.bufs[1].download(count * self.P).reshape(count, self.P)
+        _mark(f"{count} rows downloaded")
+        return count, (addr, counts, text)
+
+
+def _extract_range(call, ptrs, off: int, n: int, first_addr: int, state: dict, parts: list) -> None:
+    """Addresses [first_addr, first_addr + n), which lie `off` bytes into the staged piece: call with the current capacity;
+    grow it to the reported count if the output budget holds that many rows, else halve the range (cuts at multiples of
+    PIECE_ALIGN; pointer offset and first address advance together) and take the halves in ascending order."""
+    state["calls"] += 1
+    count, res = call(ptrs, off, n, first_addr, state["cap"])
+    if res is None and (count <= state["max_rows"] or n <= PIECE_ALIGN):
+        state["cap"] = count                                 # PIECE_ALIGN addresses always fit: max_rows >= PIECE_ALIGN
+        state["calls"] += 1
+        count, res = call(ptrs, off, n, first_addr, state["cap"])
+        assert res is not None, "the selection changed between two calls on the same slices"
+    if res is None:
+        half = (n // 2 + PIECE_ALIGN - 1) // PIECE_ALIGN * PIECE_ALIGN
+        _extract_range(call, ptrs, off, half, first_addr, state, parts)
+        _extract_range(call, ptrs, off + half, n - half, first_addr + half, state, parts)
+        return
+    parts.append(res)
+
+
+def extract_kmers(present: Sequence, absent: Sequence = (), min_count: int = 1, max_count: int = 255, min_present: int = None,
+                  max_absent: int = 0, device: int = 0, hbm_budget: int = None, threads: int = DEFAULT_THREADS, text: bool = False,
+                  initial_rows: int = INITIAL_ROWS, stage=None, call=None) -> dict:
+    """The selected k-mers of `present` / `absent`: Headers, merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(addr
+    (M,) uint64 ascending, counts (M, P) uint8 -- column i is present table i --, text (M, k + 1) uint8 lines of k letters +
+    newline if `text`, kmer_len, min_count, max_count, min_present, max_absent, n_present, n_absent, n_selected, ...).
+
+    `hbm_budget` (bytes; default PK_MERGE_HBM_BUDGET, else 80 % of the free HBM) holds the staged slices and the output
+    arrays: 1 / OUTPUT_SHARE of it is the output's (never less than PIECE_ALIGN rows), the slices are cut to fit the rest.
+    A piece that selects more rows than the output holds is taken in halves.
+    `stage(tables, lo, hi, device, threads, reserve, budget)` -> iterable of (ptrs, a, b) and `call` (see DeviceCall)
+    default to merger._staged_pieces and a DeviceCall (the CPU-only tests substitute both)."""
+    present = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in present]
+    absent = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in absent]
+    kmer_len, min_present = validate(present, absent, min_count, max_count, min_present, max_absent)
+    tables, P = present + absent, len(present)
+    row_bytes = 8 + P + (kmer_len + 1 if text else 0)
+    budget = int(hbm_budget or 0) or merger.hbm_budget(device)
+    out_budget = max(PIECE_ALIGN * row_bytes, budget // OUTPUT_SHARE)
+    state = {"max_rows": out_budget // row_bytes, "calls": 0}
+    state["cap"] = max(1, min(state["max_rows"], int(initial_rows)))
+    own = None
+    if call is None:
+        call = own = DeviceCall(P, kmer_len, min_count, max_count, min_present, int(max_absent), device=device, text=text)
+    stage = stage or merger._staged_pieces
+    parts, n_pieces = [], 0
+    try:
+        for ptrs, a, b in stage(tables, 0, 4 ** kmer_len, device, threads, out_budget, budget):
+            _mark(f"addresses {a}..{b - 1} staged")
+            n_pieces += 1
+            _extract_range(call, ptrs, 0, b - a, a, state, parts)
+    finally:
+        if own is not None:
+            own.free()
+    addr = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, dtype=np.uint64)
+    counts = np.concatenate([p[1] for p in parts]) if parts else np.zeros((0, P), dtype=np.uint8)
+    result = {"addr": np.ascontiguousarray(addr, dtype=np.uint64), "counts": np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1, P),
+              "kmer_len": kmer_len, "min_count": int(min_count), "max_count": int(max_count), "min_present": min_present,
+              "max_absent": int(max_absent), "n_present": P, "n_absent": len(absent), "n_selected": int(addr.size), "n_pieces": n_pieces,
+              "n_calls": state["calls"], "kernel_seconds": own.kernel_seconds if own is not None else 0.0}
+    if text:
+        lines = np.concatenate([p[2] for p in parts]) if parts else np.zeros((0, kmer_len + 1), dtype=np.uint8)
+        result["text"] = np.ascontiguousarray(lines, dtype=np.uint8).reshape(-1, kmer_len + 1)
+    return result
+
+
+SCALARS = ("kmer_len", "min_count", "max_count", "min_present", "max_absent", "n_present", "n_absent")
+
+
+def write_kmx(project_name: str, result: dict, data: list) -> None:
+    """`<project>.kmx` (np.savez_compressed: addr, counts and the scalars), `.kmx.json` (the scalars, n_selected and the
+    tables' metadata, present tables first: the order of the columns of counts) and, when the result holds the text,
+    `.kmx.txt` (one k-mer per line, in addr order); each through `.tmp` + rename."""
+    kmx, meta, txt = kmx_paths(project_name)
+    addr = np.ascontiguousarray(result["addr"], dtype=np.uint64)
+    counts = np.ascontiguousarray(result["counts"], dtype=np.uint8)
+    assert counts.shape == (addr.size, int(result["n_present"])) and len(data) == int(result["n_present"]) + int(result["n_absent"])
+    output = {"project_name": project_name, "n_selected": int(addr.size), "data": data}
+    output.update({key: int(result[key]) for key in SCALARS})
+    print(f"saving {meta}")
+    tmp = Path(f"{meta}.tmp")
+    with tmp.open(mode="wt") as fhd:
+        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
+    tmp.rename(meta)
+    if result.get("text") is not None:
+        lines = np.ascontiguousarray(result["text"], dtype=np.uint8)
+        assert lines.shape == (addr.size, int(result["kmer_len"]) + 1)
+        print(f"saving {txt}")
+        tmp = Path(f"{txt}.tmp")
+        with tmp.open(mode="wb") as fhd:
+            lines.tofile(fhd)
+        tmp.rename(txt)
+    print(f"saving {kmx}")
+    tmp = Path(f"{kmx}.tmp")
+    with tmp.open(mode="wb") as fhd:
+        np.savez_compressed(fhd, addr=addr, counts=counts, **{key: np.int64(result[key]) for key in SCALARS})
+    tmp.rename(kmx)
+
+
+def extract(project_name: str, present: List[Path], absent: List[Path] = (), min_count: int = 1, max_count: int = 255, min_present: int = None,
+            max_absent: int = 0, kmers: bool = False, device: int = 0, threads: int = DEFAULT_THREADS, hbm_budget: int = None) -> dict:
+    """The CLI's work: validate, extract, write the files; returns extract_kmers' result."""
+    for f in kmx_paths(project_name):
+        if f.exists():
+            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+    data, headers = [], []
+    for role, kins in (("present", present), ("absent", absent)):
+        for kin in kins:
+            print(f"verifying {kin}")
+            header = load_header(kin, device)
+            name = str(kin)
+            desc = Path((name[:-(len(Header.COMP_EXT) + 1)] if name.endswith("." + Header.COMP_EXT) else name) + "." + Header.DESC_EXT)
+            headers.append(header)
+            data.append({"pos": len(data), "role": role, "index_file": Path(kin), "description_file": desc, "header": header})
+    n_present = len(list(present))
+    validate(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, project_name=project_name)
+    _mark("tables verified")
+    result = extract_kmers(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, device=device,
+                           hbm_budget=hbm_budget, threads=threads, text=kmers)
+    for v in data:
+        v["header"] = v["header"].to_dict(lean=True)
+    write_kmx(project_name, result, data)
+    _mark("files renamed")
+    return result
+
+
+def build_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Extract the k-mers present in some kmer databases and absent from others.")
+    parser.add_argument("Project_Name", metavar="P", type=str, help="Project name (prefix of the output files)")
+    parser.add_argument("--present", metavar="K", type=Path, nargs="+", required=True, help="kin files that must hold the k-mer (in the count window)")
+    parser.add_argument("--absent", metavar="K", type=Path, nargs="*", default=[], help="kin files that must not hold it (at any count)")
+    parser.add_argument("--min-count", type=int, default=1, help="Minimum Kmer Count in a present table [1]")
+    parser.add_argument("--max-count", type=int, default=255, help="Maximum Kmer Count in a present table [255]")
+    parser.add_argument("--min-present", type=int, default=None, help="present tables that must hold the k-mer [all of them]")
+    parser.add_argument("--max-absent", type=int, default=0, help="absent tables that may hold it all the same [0]")
+    parser.add_argument("--kmers", action="store_true", help="also write <P>.kmx.txt: the k-mers as letters, one per line")
+    parser.add_argument("--threads", type=int, default=DEFAULT_THREADS, help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
+    return parser
+
+
+def main(argv: List[str] = None) -> None:
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    try:
+        result = extract(args.Project_Name, args.present, args.absent, min_count=args.min_count, max_count=args.max_count,
+                         min_present=args.min_present, max_absent=args.max_absent, kmers=args.kmers,
+                         device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads)
+    except ValueError as exc:
+        print(f"error: {exc}", file=sys.stderr)
+        sys.exit(1)
+    print(f"{result['n_selected']:,d} k-mers selected, {result['n_present']} present + {result['n_absent']} absent tables, "
+          f"{result['n_pieces']} staged piece(s)")
+
+
+if __name__ == "__main__":
+    main()

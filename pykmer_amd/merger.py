@@ -85,12 +85,18 @@ def address_slice(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, min(n, lo + per)
 
 
-def _sub_slices(lo: int, hi: int, n_tables: int, device: int, reserve: int = 0):
+def hbm_budget(device: int, budget: int = None) -> int:
+    """The bytes of HBM a pass may fill with staged slices and what it keeps beside them: `budget` if given, else
+    PK_MERGE_HBM_BUDGET, else 80 % of the free HBM."""
+    return int(budget or 0) or int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or int(_lib.mem_info(device)[0] * 0.8)
+
+
+def _sub_slices(lo: int, hi: int, n_tables: int, device: int, reserve: int = 0, budget: int = None):
     """[lo, hi) cut so that n_tables slices fit HBM beside each other (the reference streams pairs and takes
     any N, merger.py:139-153; here a k=17 merge of 32 tables is 512 GiB).  Partials add, so the cuts are free.
-    PK_MERGE_HBM_BUDGET (bytes) overrides the 80 % of free HBM used by default; `reserve` bytes of it are kept for
-    something else (a spectrum accumulator: 41 MB at N = 13, 4.2 GB at N = 128)."""
-    budget = int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or int(_lib.mem_info(device)[0] * 0.8)
+    PK_MERGE_HBM_BUDGET (bytes) overrides the 80 % of free HBM used by default (`budget` overrides both); `reserve` bytes
+    of it are kept for something else (a spectrum accumulator: 41 MB at N = 13, 4.2 GB at N = 128)."""
+    budget = hbm_budget(device, budget)
     budget -= reserve
     per_table = max(2048, (budget // max(1, n_tables) - 64) & ~2047)
     return [(a, min(hi, a + per_table)) for a in range(lo, hi, per_table)]
@@ -160,6 +166,30 @@ def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads:
             buf.free()
         if own is not None:
             own.free()
+
+
+def _staged_pieces(headers: List[Header], lo: int, hi: int, device: int, threads: int, reserve: int = 0, budget: int = None):
+    """_flat_partial's staging for a pass that accumulates nothing: yields (ptrs, a, b) for every staged piece [a, b) of
+    [lo, hi), in ascending order, so the pass learns each piece's first address.  The cuts are _sub_slices' (N slices beside
+    each other, `reserve` bytes of `budget` kept for the caller's own buffers); ResidentTable entries are one piece, where
+    they lie.  The buffers are freed when the generator is exhausted or closed."""
+    N = len(headers)
+    resident = [hasattr(h, "device_slice") for h in headers]
+    assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one pass"
+    if all(resident):
+        yield [h.device_slice(lo, hi) for h in headers], lo, hi
+        return
+    cuts = _sub_slices(lo, hi, N, device, reserve=reserve, budget=budget)
+    bufs = [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
+    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
+    try:
+        with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+            for a, b in cuts:
+                list(pool.map(lambda i: bufs[i].upload(headers[i].read_table_slice(a, b, threads=io_threads)), range(N)))
+                yield [buf.ptr for buf in bufs], a, b
+    finally:
+        for buf in bufs:
+            buf.free()
 
 
 def gpu_partial(headers: List[Header], lo: int, hi: int, windows, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
