@@ -133,6 +133,47 @@ def test_addresses_beyond_32_bits(gpu):
     _check(tables[:2], tables[2:], 2, 200, 1, 0, first_addr=first)
 
 
+# ------------------------------------------------------------------ 3b. row widths -----------------
+@pytest.mark.parametrize("P", [3, 5, 6, 7, 9, 127])
+def test_row_widths(gpu, P):
+    """Rows of P bytes, P not 1, 2 or a multiple of 4: a tile's byte range [g0, g1) of the count array starts at every
+    offset within a dword that P allows, its dwords start in the middle of a row, and rows wrap inside a dword."""
+    present, absent, residues = extract_ref.row_width_case(P)
+    assert residues == ({0, 2} if P == 6 else {0, 1, 2, 3})
+    n = present[0].size
+    assert n % extract_ref.TILE == 17 and n > 4 * extract_ref.TILE           # two workgroups or more, the last tile 17 addresses
+    m = _check(present, absent, 2, 200, 1, 0)
+    assert n // 5 < m < n // 2
+    if P == 3:
+        _check(present, absent, 2, 200, 1, 0, first_addr=2 ** 33 + 2048)
+
+
+# ------------------------------------------------------------------ 3c. short ranges ---------------
+PER_TILE = [2, 1, 0, 1,  3, 2, 1, 3,  0, 0, 0, 0,  1, 3, 0, 2,  1]    # selected addresses per tile; four tiles are a workgroup
+
+
+@pytest.mark.parametrize("P", [1, 3])
+def test_ranges_inside_one_dword(gpu, P):
+    """One, two or three rows per tile: byte ranges shorter than the dword they lie in, and short ranges with an unaligned
+    head and tail.  P = 1 gives a range that starts off a dword boundary and ends before the next one; three bytes that
+    start off a boundary end at the next one at the earliest, so for P = 3 the range inside one dword ends on it, and only
+    P = 3 (nine bytes from three rows) has a whole dword between an unaligned head and an unaligned tail."""
+    present, absent, mask = extract_ref.sparse_tiles(PER_TILE, P, seed=20 + P)
+    per = np.add.reduceat(mask.astype(np.int64), np.arange(0, mask.size, extract_ref.TILE))
+    assert per.tolist() == PER_TILE and mask.size == 16 * extract_ref.TILE + 17
+    assert per[2] == 0 and per[1] and per[3]                            # an empty tile inside a workgroup that selects
+    assert per[8:12].sum() == 0 and per[4:8].sum() and per[12:16].sum()   # an empty workgroup between two that select
+    g0, g1 = extract_ref.tile_ranges(mask, P)
+    dword = g0 & ~3
+    one_dword = (g1 > g0) & (g0 % 4 != 0) & (g1 <= dword + 4)
+    around = (g0 % 4 != 0) & (g1 % 4 != 0) & (((g0 + 3) & ~3) + 4 <= (g1 & ~3))
+    if P == 1:
+        assert (one_dword & (g1 < dword + 4)).any()
+    else:
+        assert one_dword.any() and around.any()
+    assert _check(present, absent, 1, 255) == sum(PER_TILE)
+
+
 # ------------------------------------------------------------------ 4. counter edges ---------------
 def test_counters_reach_128(gpu):
     n = 4100
@@ -238,8 +279,11 @@ def test_bad_arguments_are_refused(gpu):
 
 
 # ------------------------------------------------------------------ 8. text ------------------------
-@pytest.mark.parametrize("k", [1, 9, 15, 17])
+@pytest.mark.parametrize("k", list(range(1, 32, 2)) + [32])
 def test_text(gpu, k):
+    """Every odd k and the largest one: a thread writes 16 bytes and a line is k + 1, so where lines end inside a thread's
+    bytes differs with (k + 1) mod 16; from k = 18 on the addresses need more than 35 bits.  1000 lines are two
+    workgroups or more from k = 5 on."""
     lib = _lib()
     rng = np.random.default_rng(k)
     for m in (1, 2, 7, 1000):

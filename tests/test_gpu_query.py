@@ -76,7 +76,7 @@ def _same(got, want):
 
 
 # ------------------------------------------------------------------ 1. edge grammar ----------------
-@pytest.mark.parametrize("k", [3, 9])
+@pytest.mark.parametrize("k", [1, 3, 5, 7, 9, 11])
 def test_edge_grammar(gpu, k):
     tables = query_ref.random_tables(k, 3, seed=k)
     texts = [inputs.edge_fasta(), inputs.byte_soup(40_000, 11), inputs.byte_soup(40_000, 12)]
@@ -105,19 +105,74 @@ def _seam_text(k: int) -> bytes:
     return head + body
 
 
-@pytest.mark.parametrize("k", [9, 15])
+@pytest.mark.parametrize("k", [1, 9, 13, 15, 17])
 def test_slot_seams(gpu, k):
+    if k == 17:
+        return _slot_seams_k17()
     text = _seam_text(k)
     assert len(text) > 6 * CHUNK
-    if k == 9:
+    if k <= 9:
         tables = query_ref.random_tables(k, 2, seed=21)
-    else:                                                    # 1 GiB each: cheap to fill, every count-window edge frequent
+    else:                                                    # 64 MiB / 1 GiB each: cheap to fill, every count-window edge frequent
         pool = np.array([0, 1, 254, 255, 7, 0, 1, 255], dtype=np.uint8)
         tables = [np.tile(np.roll(pool, i), 4 ** k // 8) for i in range(2)]
         tables[1] = np.roll(tables[1], 3)
     with _Device(tables) as dev:
         for mn, mx in ((1, 255), (2, 254)):
             _same(_query(text, k, dev.ptrs, mn, mx), query_ref.expected(text, k, tables, mn, mx))
+
+
+def _slot_seams_k17():
+    """k = 17: the window history is all 16 bases in front of a thread's own, so the chunk start state decides the first
+    windows of every slot.  The table is counted on the GPU from stretches of the seam text around every chunk boundary:
+    windows across the boundaries without an N hit, and so do the windows next to the two seams.  Feeds cut 3 bytes before
+    and behind the seams' chunk boundaries give the same result."""
+    lib = _lib()
+    k = 17
+    text = _seam_text(k)
+    counted = query_ref.counted_text_for(text, k, seed=1700)
+    sparse = [query_ref.SparseTable(oracle.kmer_list(counted, k))]
+    kmers = oracle.kmer_list(text, k)
+    start, straddles, first_base = query_ref.straddling_windows(text, k)
+    assert start.size == kmers.size
+    count = sparse[0][kmers]
+    across = {b: count[straddles == b] for b in range(CHUNK, len(text), CHUNK)}
+    for b, c in across.items():                              # no valid window lies across a seam; k - 1 lie across any other boundary
+        assert c.size == (0 if b in (2 * CHUNK, 5 * CHUNK) else k - 1), b
+    assert all((across[b] == 1).all() for b in (CHUNK, 3 * CHUNK)) and all((across[b] == 2).all() for b in (4 * CHUNK, 6 * CHUNK))
+    for b in (2 * CHUNK, 5 * CHUNK):                         # the nearest windows on either side of a seam hit
+        i = int(np.searchsorted(start, first_base[b])) - 1
+        assert start[i] + k <= first_base[b] < start[i + 1] and count[i] >= 1 and count[i + 1] >= 1, b
+    assert 0 < np.count_nonzero(count) < count.size // 10
+    with lib.Indexer(k, device=0) as ix:
+        ix.feed(counted)
+        ix.finish()
+        ptrs = [ix.table_device_ptr()]
+        for mn, mx in ((1, 255), (2, 254)):
+            want = query_ref.expected(text, k, sparse, mn, mx)
+            assert want["hits"][0, 0] > 0
+            whole = _query(text, k, ptrs, mn, mx)
+            _same(whole, want)
+            for sign in (-3, 3):
+                cut = _query(text, k, ptrs, mn, mx, cuts=[2 * CHUNK + sign, 5 * CHUNK + sign])
+                assert np.array_equal(cut["hits"], whole["hits"]) and np.array_equal(cut["depth"], whole["depth"]), sign
+                assert np.array_equal(cut["records"], whole["records"])
+
+
+# ------------------------------------------------------------------ 2b. a long record late in a slot
+@pytest.mark.parametrize("ragged", [False, True])
+@pytest.mark.parametrize("s", [126, 127, 128, 129, 200])
+def test_long_record_behind_short_ones(gpu, s, ragged):
+    """A record of 12 000 bases as record s of its slot: whole waves of it are summed across the wave and added by one lane,
+    to the slot's LDS tallies below index 128 and to HBM from there on (tests/test_query_host.py checks the layout)."""
+    k = 9
+    text, index = query_ref.long_after_short(s, seed=300 + s, ragged=ragged)
+    tables = query_ref.random_tables(k, 2, seed=22)
+    with _Device(tables) as dev:
+        for mn, mx in ((1, 255), (2, 254)):
+            want = query_ref.expected(text, k, tables, mn, mx)
+            assert want["n_valid"][index] == 12_000 - k + 1 and want["hits"][index].all()
+            _same(_query(text, k, dev.ptrs, mn, mx), want)
 
 
 # ------------------------------------------------------------------ 3. many records ----------------

@@ -140,3 +140,27 @@ def test_table_groups_concatenate_like_one_group():
         for key in ("hits", "depth", "n_valid", "seq_len"):
             assert np.array_equal(got[key], want[key]), key
     assert query.table_groups(13, 1 << 30, 5 << 30) == [(0, 5), (5, 10), (10, 13)]
+
+
+@pytest.mark.parametrize("ragged", [False, True])
+@pytest.mark.parametrize("s", [126, 127, 128, 129, 200])
+def test_long_after_short_puts_a_long_record_late_in_the_first_chunk(s, ragged):
+    """The builder of the GPU test of that name: the long record lies whole in the first 16 KiB chunk, it is record s
+    counted from the chunk's first record with a window, and whole 1024-base waves of the chunk hold nothing else."""
+    import oracle
+    k, chunk = 9, 16384
+    text, index = query_ref.long_after_short(s, seed=300 + s, ragged=ragged)
+    recs = oracle.kmer_list(text, k, records=True)[1]["records"]
+    assert len(recs) == s + 2 and index == s
+    long_, tail = recs[index], recs[index + 1]
+    assert text[int(long_["name_off"]):int(long_["name_off"]) + int(long_["name_len"])] == b"long"
+    assert int(long_["seq_len"]) == 12_000 and int(long_["n_valid_kmers"]) == 12_000 - k + 1
+    end = int(tail["name_off"]) - 1                          # the '>' of the next record
+    assert 0 < int(long_["name_off"]) < end < chunk < len(text) - 100 and int(tail["seq_len"]) == 3000
+    first_with_window = int(np.flatnonzero(recs["n_valid_kmers"] > 0)[0])
+    assert first_with_window == 0 and index - first_with_window == s
+    without = int(np.count_nonzero(recs["n_valid_kmers"][:s] == 0))
+    assert without == (len(range(1, s, 3)) if ragged else 0)
+    # bases of the chunk in front of the long record: all of them, or at least those of the reads that have a window
+    for before in (int(recs["seq_len"][:s].sum()), int(recs["seq_len"][:s][recs["n_valid_kmers"][:s] > 0].sum())):
+        assert (before + 12_000) // 1024 - -(-before // 1024) >= 2
