@@ -77,8 +77,12 @@ def scan_blocks(buf) -> List[Tuple[int, int]]:
             return []
         xlen = struct.unpack_from("<H", buf, pos + 10)[0]
         x, end, bsize = pos + 12, pos + 12 + xlen, None
+        if end > n:                                          # the extra field runs past the data: truncated header
+            return []
         while x + 4 <= end:
             si1, si2, slen = buf[x], buf[x + 1], struct.unpack_from("<H", buf, x + 2)[0]
+            if x + 4 + slen > end:                           # a subfield that ends behind the extra field: truncated header
+                return []
             if si1 == 66 and si2 == 67 and slen == 2:
                 bsize = struct.unpack_from("<H", buf, x + 4)[0] + 1
             x += 4 + slen

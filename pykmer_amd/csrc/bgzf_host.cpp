@@ -40,6 +40,8 @@ extern "C" int pk_bgzf_scan(const uint8_t *src, uint64_t n_bytes, uint64_t cap, 
         if (end > n_bytes) return pk::set_error(PK_ERR_ARG, "truncated BGZF header");
         while (x + 4 <= end) {
             const uint32_t slen = rd16(src + x + 2);
+            // every subfield must end inside the extra field
+            if (x + 4 + slen > end) return pk::set_error(PK_ERR_ARG, "truncated BGZF header");
             if (src[x] == 66 && src[x + 1] == 67 && slen == 2) bsize = (uint64_t)rd16(src + x + 4) + 1;
             x += 4 + slen;
         }

@@ -298,7 +298,8 @@ __device__ __forceinline__ L1 piece_l1_at(const uint8_t *mine, uint32_t nb, bool
     dirty = d;
     return nb ? l1_make(ht, st) : 0u;
 }
-// SWAR helpers: 0x80 in every byte of v that is zero / below n (n <= 128); exact, no cross-byte borrows
+// SWAR helpers: 0x80 in every byte of v that is zero / below n (n <= 128); exact, no cross-byte borrows.  Bit 7 of the
+// byte itself is kept out of the arithmetic and decides last (the `| v`): a byte >= 0x80 is neither zero nor below n.
 __device__ __forceinline__ uint32_t swar_zero(uint32_t v) { return ~(((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v | 0x7f7f7f7fu); }
 __device__ __forceinline__ uint32_t swar_less(uint32_t v, uint32_t n_rep) {
     return ~((((v & 0x7f7f7f7fu) | 0x80808080u) - n_rep) | v) & 0x80808080u;

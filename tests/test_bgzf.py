@@ -212,3 +212,45 @@ def test_native_reader_rejects_a_lying_index_and_corrupt_blocks(tmp_path):
     assert gzip.decompress(open(m_dst, "rb").read()) == mix.tobytes()
     sizes = bgzf.block_index(m_dst)[1]
     assert sizes.max() <= 0x10000 and sizes[0] < 30_000 and sizes[-1] < 30_000
+
+
+def _two_block_image():
+    """A valid BGZF image of two data blocks (no end-of-file block) and its block list."""
+    from pykmer_amd import _lib
+    data = _table(150, 9)
+    raw, sizes = _lib.bgzf_deflate(data, 6, 100, 1)
+    assert len(sizes) == 2 and int(sizes.sum()) == raw.size and gzip.decompress(raw.tobytes()) == data.tobytes()
+    return raw.copy(), [(0, int(sizes[0])), (int(sizes[0]), int(sizes[1]))]
+
+
+def _scan_both(buf: np.ndarray):
+    """The native header walk and the Python one on the same bytes: the block list, or None for "not BGZF" (ValueError /
+    an empty list).  Anything else -- another exception, a crash -- is the failure this guards against."""
+    from pykmer_amd import _lib
+    try:
+        off, size, _ = _lib.bgzf_scan(np.ascontiguousarray(buf))
+        native = list(zip(off.tolist(), size.tolist()))
+    except ValueError:
+        native = None
+    python = bgzf.scan_blocks(memoryview(buf.tobytes())) or None
+    assert native == python or (native == [] and python is None)
+    return native
+
+
+def test_header_walk_stays_inside_the_extra_field():
+    """A BC subfield whose two data bytes would lie behind the end of the extra field (and of the buffer) is a truncated
+    header, not a block size: pk_bgzf_scan used to read src[x+4..x+5] unchecked (found with a sanitizer build of a
+    stand-alone caller; the plain call returned PK_ERR_ARG either way, so this test pins the outcome, not the read)."""
+    tail_bc = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 8, 0]) + b"XY\x00\x00" + b"BC\x02\x00"
+    assert len(tail_bc) == 20
+    assert _scan_both(np.frombuffer(tail_bc, dtype=np.uint8)) is None
+    raw, blocks = _two_block_image()
+    for n in range(raw.size + 1):                                        # every prefix: whole blocks, or an error
+        got = _scan_both(raw[:n])
+        ends = [0, blocks[0][1], raw.size]
+        assert got == (blocks[:ends.index(n)] if n in ends else None), n
+    for at in range(10, 18):                                             # XLEN, SI1, SI2, SLEN, BSIZE of the first header
+        for v in (0x00, 0xFF):
+            bad = raw.copy()
+            bad[at] = v
+            assert _scan_both(bad) == (blocks if v == raw[at] else None), (at, v)
