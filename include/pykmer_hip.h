@@ -145,10 +145,30 @@ void pk_indexer_destroy(pk_indexer *ix);
  * keeps them alive through the feeds.  They stay set across resets.  1 <= min_count <= max_count <= 255.  One lookup
  * launch serves 16 tables; more are looked up group by group inside the feed.
  * pk_query_results: after pk_indexer_finish.  hits_out / depth_out receive n_recs * N u64 each, row-major [r * N + t];
- * PK_ERR_RECS_CAP if the stream holds more than recs_cap records. */
+ * PK_ERR_RECS_CAP if the stream holds more than recs_cap records; PK_ERR_STATE when bins are on.
+ *
+ * Bins: the same tallies along each record, in bins of W valid windows.  Number the m valid windows of record r in text
+ * order, j = 0 .. m-1; bin b of r holds the windows b*W <= j < min((b+1)*W, m), so r has ceil(m / W) bins, only its last
+ * may hold fewer than W windows, and a record without a valid window has none.  The rows are ordered by record, then by
+ * bin: record r's first row is bin_first[r] = sum of ceil(n_valid / W) over the records before r, r = 0 .. R, and
+ * bin_first[R] is the number of rows.  hits and depth of a row are defined as above over the windows of that bin only.
+ * Bins count valid windows, not bases: in a record without invalid characters window j begins at base j, but the window
+ * numbering skips the gap of a run of N.
+ * pk_query_set_bins: after pk_query_set_tables and before the first feed (PK_ERR_STATE otherwise).  bin_windows = W >= 1;
+ * 0 = one row per record, the default, which a reset restores.  The accumulators are sized before every feed for the rows
+ * the stream can hold by then, bytes_fed / W + the record capacity + 1; where they do not fit the device, the feed returns
+ * an error whose message names W.
+ * pk_query_bin_count: after pk_indexer_finish, the number of rows B.
+ * pk_query_bin_results: after pk_indexer_finish.  hits_out / depth_out receive B * N u64 each, row-major [row * N + t];
+ * bin_first_out receives R + 1 u64.  PK_ERR_RECS_CAP, with the needed numbers in the message, if B > bins_cap or
+ * R > recs_cap; PK_ERR_STATE when bins are off. */
 int pk_query_create(pk_indexer **out, int k, int device);
 int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
 int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);
+int pk_query_set_bins(pk_indexer *q, uint64_t bin_windows);
+int pk_query_bin_count(pk_indexer *q, uint64_t *n_bins_out);
+int pk_query_bin_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t *bin_first_out, uint64_t bins_cap,
+                         uint64_t recs_cap);
 
 /* ---- stats: replaces Header.update_stats (tools.py:246-263) on a host table of n bytes. */
 int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device);

@@ -48,6 +48,9 @@ _SIGNATURES = {
     "pk_query_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     "pk_query_set_tables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "pk_query_results": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_query_set_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_query_bin_count": (ctypes.c_int, [ctypes.c_void_p, _u64p]),
+    "pk_query_bin_results": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -274,6 +277,25 @@ class QueryIndexer(Indexer):
         depth = np.zeros_like(hits)
         _check(load().pk_query_results(self._h, hits.ctypes.data, depth.ctypes.data, n_records))
         return hits[:n_records, :self.n_tables], depth[:n_records, :self.n_tables]
+
+    def set_bins(self, bin_windows: int):
+        """pk_query_set_bins, after set_tables and before the first feed: tally in bins of `bin_windows` valid windows
+        along each record (0: per record, the default a reset restores)."""
+        if not 0 <= int(bin_windows) < 2 ** 64:
+            raise ValueError(f"bin_windows must be an unsigned 64-bit integer, got {bin_windows}")
+        _check(load().pk_query_set_bins(self._h, int(bin_windows)))
+
+    def bin_results(self, n_records: int):
+        """pk_query_bin_results after finish(): (hits, depth, bin_first); hits and depth (B, N) uint64, one row per bin,
+        bin_first (n_records + 1,) uint64 with bin_first[-1] = B."""
+        nb = ctypes.c_uint64(0)
+        _check(load().pk_query_bin_count(self._h, ctypes.byref(nb)))
+        B = int(nb.value)
+        hits = np.zeros((max(B, 1), max(self.n_tables, 1)), dtype=np.uint64)
+        depth = np.zeros_like(hits)
+        bin_first = np.zeros(n_records + 1, dtype=np.uint64)
+        _check(load().pk_query_bin_results(self._h, hits.ctypes.data, depth.ctypes.data, bin_first.ctypes.data, B, n_records))
+        return hits[:B, :self.n_tables], depth[:B, :self.n_tables], bin_first
 
     def timings(self) -> dict:
         t = np.zeros(10, dtype=np.float64)

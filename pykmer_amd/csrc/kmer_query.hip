@@ -25,6 +25,11 @@
 //                   tally.  A wave that lies in one record sums across the wave first; the tallies of a slot meet in an
 //                   LDS accumulator (the slot's first QACC_RECS records, in the spirit of RecAcc, kmer_walk.h) and reach
 //                   HBM as one atomic per record, table and slot.
+// Binned tallies (pk_query_set_bins, W valid windows per bin): the accumulators hold one row per bin instead of one per
+// record, record after record and bin after bin; record r's first row is Bf[r] = sum of ceil(n_valid / W) over the records
+// before r, final once r has opened exactly as P[r] is, and extended by the same k_query_scan.  The window of ordinal o in
+// record r falls in row Bf[r] + (o - P[r]) / W.  From one valid window to the next the row stays or grows by one, so the
+// rows of a slot are as dense as its records are in the per-record case and the tally below serves both.
 // Every kernel returns at once, writing nothing, when it finds flags[0] raised (the squeeze backed out: the slots still
 // hold an earlier text); the host grows the record and accumulator arrays and repeats the feed's squeeze and these kernels.
 #include <type_traits>
@@ -34,7 +39,8 @@
 namespace pk {
 
 constexpr int QNT = 1024;                 // threads per slot, 16 bases each
-constexpr uint32_t QACC_RECS = 128;       // records of a slot tallied in LDS; later ones (reads below ~128 bytes) go to HBM directly
+constexpr uint32_t QACC_RECS = 128;       // rows (records or bins) of a slot tallied in LDS; later ones (reads below ~128 bytes of
+                                          // text, bins of fewer than 128 windows) go to HBM directly
 
 // OR of x << s for s = 0 .. n-1 (n <= 16)
 __device__ __forceinline__ uint32_t q_smear(uint32_t x, uint32_t n) {
@@ -101,10 +107,12 @@ __global__ __launch_bounds__(QNT) void k_query_count(const uint32_t *__restrict_
 
 // One workgroup.  slot_first[c] = windows_before + the window counts of the slots before c.  P[r] for the records this feed
 // opened: p_done entries are final already (the records the stream held before this feed; P[0] = 0), the stream now holds
-// carry->n_recs records.
+// carry->n_recs records.  BINS: Bf[r], the bins of the records before r at W windows per bin, over the same r.
+template <bool BINS>
 __global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__ slot_count, uint32_t n_chunks, unsigned long long windows_before,
                                                     unsigned long long *__restrict__ slot_first, const DevRec *__restrict__ recs,
                                                     const Carry *__restrict__ carry, unsigned long long p_done, unsigned long long *__restrict__ P,
+                                                    unsigned long long *__restrict__ Bf, unsigned long long W,
                                                     const uint32_t *__restrict__ flags) {
     __shared__ unsigned long long wsum[QNT / 64];
     if (flags[0]) return;
@@ -135,10 +143,15 @@ __global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__
     unsigned long long r0 = p_done;
     if (r0 == 0ull) {
         if (n_recs == 0ull) return;
-        if (threadIdx.x == 0) P[0] = 0ull;
+        if (threadIdx.x == 0) {
+            P[0] = 0ull;
+            if constexpr (BINS) Bf[0] = 0ull;
+        }
         r0 = 1ull;
     }
     run = r0 > 1ull ? P[r0 - 1ull] : 0ull;                   // (P[0] = 0 may have been written by thread 0 just now)
+    unsigned long long run_b = 0ull;
+    if constexpr (BINS) run_b = r0 > 1ull ? Bf[r0 - 1ull] : 0ull;
     for (unsigned long long b = r0; b < n_recs; b += QNT) {
         const unsigned long long r = b + threadIdx.x;
         const unsigned long long v = r < n_recs ? recs[r - 1ull].n_valid : 0ull;
@@ -146,6 +159,11 @@ __global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__
         const unsigned long long inc = incl_scan(v, total);
         if (r < n_recs) P[r] = run + inc;
         run += total;
+        if constexpr (BINS) {
+            const unsigned long long inc_b = incl_scan(v ? (v - 1ull) / W + 1ull : 0ull, total);   // ceil(v / W)
+            if (r < n_recs) Bf[r] = run_b + inc_b;
+            run_b += total;
+        }
     }
 }
 
@@ -159,16 +177,18 @@ __device__ __forceinline__ unsigned long long q_find(const unsigned long long *_
     return lo;
 }
 
-template <typename KT>
+// BINS: the accumulators' rows are bins of W windows (Bf, W); otherwise records, and Bf and W are not read.
+template <typename KT, bool BINS>
 __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
                                                       const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state, uint32_t k,
                                                       const unsigned long long *__restrict__ slot_first, const unsigned long long *__restrict__ P,
+                                                      const unsigned long long *__restrict__ Bf, unsigned long long W,
                                                       const Carry *__restrict__ carry, QueryTables tabs, uint32_t n_tab, uint32_t N, uint32_t t0,
                                                       uint32_t min_count, uint32_t max_count, unsigned long long *__restrict__ hits,
                                                       unsigned long long *__restrict__ depth, const uint32_t *__restrict__ flags) {
     __shared__ uint32_t wsum[QNT / 64];
     __shared__ uint32_t acc_h[QACC_RECS * QUERY_MAX_TABLES], acc_d[QACC_RECS * QUERY_MAX_TABLES];
-    __shared__ unsigned long long rec_range[2];
+    __shared__ unsigned long long rec_range[BINS ? 6 : 2];   // BINS: + the slot's first and last row, P and Bf of its first record
     if (flags[0]) return;
     const uint32_t c = blockIdx.x, lane = threadIdx.x & 63u;
     const uint32_t nb = n_bases[c];
@@ -181,12 +201,22 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
     if (threadIdx.x == 0) {
         const unsigned long long n_recs = carry->n_recs;     // >= 1: a window lies in a record
         const unsigned long long lo = q_find(P, 0ull, n_recs - 1ull, first);
+        const unsigned long long hi = q_find(P, lo, n_recs - 1ull, first + total - 1ull);
         rec_range[0] = lo;
-        rec_range[1] = q_find(P, lo, n_recs - 1ull, first + total - 1ull);
+        rec_range[1] = hi;
+        if constexpr (BINS) {
+            const unsigned long long p_lo = P[lo], bf_lo = Bf[lo];
+            rec_range[2] = bf_lo + (first - p_lo) / W;
+            rec_range[3] = Bf[hi] + (first + total - 1ull - P[hi]) / W;
+            rec_range[4] = p_lo;
+            rec_range[5] = bf_lo;
+        }
     }
     for (uint32_t i = threadIdx.x; i < QACC_RECS * n_tab; i += QNT) { acc_h[i] = 0u; acc_d[i] = 0u; }
     __syncthreads();
     const unsigned long long r_lo = rec_range[0], r_hi = rec_range[1];
+    // the accumulators' rows this slot touches: records, or bins
+    const unsigned long long row_lo = BINS ? rec_range[2] : r_lo, row_hi = BINS ? rec_range[3] : r_hi;
 
     // ---- the canonical k-mers of this thread's windows (indexer.py:149-150, 341)
     const KT mask = (KT)((2u * k >= sizeof(KT) * 8u) ? ~(KT)0 : (((KT)1 << (2u * k)) - 1));
@@ -198,12 +228,37 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
         const KT f = (KT)(fwd64 >> (2u * (15u - j))) & mask, rv = (KT)(rev64 >> (2u * j)) & mask;
         a[j] = f < rv ? f : rv;
     }
-    // ---- the record of every window, relative to the slot's first
+    // ---- the row of every window, relative to the slot's first
     uint32_t rr[16];
     uint32_t rr_first = 0, rr_last = 0;
-    if (r_lo == r_hi) {                                      // uniform: the genome case
+    if (row_lo == row_hi) {                                  // uniform: the genome case (with bins: a slot inside one bin)
 #pragma unroll
         for (int j = 0; j < 16; j++) rr[j] = 0u;
+    } else if (BINS && q.ok) {
+        // one division for the first window, then (row, rem) steps with the ordinal: rem windows of the row lie before o
+        unsigned long long o = first + off, r = r_lo, at = o - rec_range[4], row0 = rec_range[5];
+        if (r_lo != r_hi) {                                  // (one record: no thread searches P)
+            r = q_find(P, r_lo, r_hi, o);
+            at = o - P[r];
+            row0 = Bf[r];
+        }
+        unsigned long long next = r < r_hi ? P[r + 1ull] : ~0ull;
+        unsigned long long row = row0 + at / W, rem = at % W;
+        bool seen = false;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            rr[j] = 0u;
+            if ((q.ok >> j) & 1u) {
+                if (o >= next) {
+                    do { r++; next = r < r_hi ? P[r + 1ull] : ~0ull; } while (o >= next);
+                    row = Bf[r]; rem = 0ull;
+                } else if (rem == W) { row++; rem = 0ull; }
+                rr[j] = (uint32_t)(row - row_lo);
+                if (!seen) { rr_first = rr[j]; seen = true; }
+                rr_last = rr[j];
+                o++; rem++;
+            }
+        }
     } else if (q.ok) {
         unsigned long long o = first + off;
         unsigned long long r = q_find(P, r_lo, r_hi, o);
@@ -224,7 +279,7 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
 #pragma unroll
         for (int j = 0; j < 16; j++) rr[j] = 0u;
     }
-    // does the whole wave lie in one record?
+    // does the whole wave lie in one row?
     const bool has = q.ok != 0u;
     const unsigned long long holders = __ballot(has);
     if (holders != 0ull) {                                   // wave-uniform; no barrier inside
@@ -235,7 +290,7 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
                 if (h) atomicAdd(&acc_h[rel * n_tab + tt], h);
                 if (d) atomicAdd(&acc_d[rel * n_tab + tt], d);
             } else {
-                const unsigned long long at = (r_lo + rel) * N + t0 + tt;
+                const unsigned long long at = (row_lo + rel) * N + t0 + tt;
                 if (h) atomicAdd(&hits[at], (unsigned long long)h);
                 if (d) atomicAdd(&depth[at], (unsigned long long)d);
             }
@@ -270,11 +325,11 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
     }
     __syncthreads();
     {
-        const unsigned long long span = r_hi - r_lo + 1ull;
+        const unsigned long long span = row_hi - row_lo + 1ull;
         const uint32_t n_acc = (uint32_t)(span < QACC_RECS ? span : QACC_RECS) * n_tab;
         for (uint32_t i = threadIdx.x; i < n_acc; i += QNT) {
             const uint32_t h = acc_h[i], d = acc_d[i];
-            const unsigned long long at = (r_lo + i / n_tab) * N + t0 + i % n_tab;
+            const unsigned long long at = (row_lo + i / n_tab) * N + t0 + i % n_tab;
             if (h) atomicAdd(&hits[at], (unsigned long long)h);
             if (d) atomicAdd(&depth[at], (unsigned long long)d);
         }
@@ -303,23 +358,28 @@ size_t query_workspace(uint32_t n_chunks, uint8_t *base, PartBuffers *view, Quer
 }
 
 void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,
-                       const Carry *carry, uint64_t p_done, unsigned long long *P, hipStream_t s) {
+                       const Carry *carry, uint64_t p_done, unsigned long long *P, unsigned long long *Bf, uint64_t bin_windows, hipStream_t s) {
     hipLaunchKernelGGL(k_query_count, dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.restarts,
                        (const uint32_t *)b.n_bases, st2, pl.k, qb.slot_count, (const uint32_t *)b.flags);
-    hipLaunchKernelGGL(k_query_scan, dim3(1), dim3(QNT), 0, s, (const uint32_t *)qb.slot_count, pl.n_chunks, (unsigned long long)windows_before,
-                       qb.slot_first, recs, carry, (unsigned long long)p_done, P, (const uint32_t *)b.flags);
+#define PK_QUERY_SCAN(BINS) hipLaunchKernelGGL(k_query_scan<BINS>, dim3(1), dim3(QNT), 0, s, (const uint32_t *)qb.slot_count, pl.n_chunks,                 \
+                                               (unsigned long long)windows_before, qb.slot_first, recs, carry, (unsigned long long)p_done, P, Bf,         \
+                                               (unsigned long long)bin_windows, (const uint32_t *)b.flags)
+    if (bin_windows) PK_QUERY_SCAN(true);
+    else PK_QUERY_SCAN(false);
+#undef PK_QUERY_SCAN
 }
 
-void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P, const Carry *carry,
-                         const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
+void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
+                         const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
                          unsigned long long *hits, unsigned long long *depth, hipStream_t s) {
     QueryTables tabs;
     for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
-#define PK_QUERY_LOOKUP(KT) hipLaunchKernelGGL(k_query_lookup<KT>, dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.restarts, \
-                                               (const uint32_t *)b.n_bases, st2, pl.k, (const unsigned long long *)qb.slot_first, P, carry, tabs, n_tab, N, t0,  \
-                                               min_count, max_count, hits, depth, (const uint32_t *)b.flags)
-    if (pl.k <= 15) PK_QUERY_LOOKUP(uint32_t);
-    else PK_QUERY_LOOKUP(uint64_t);
+#define PK_QUERY_LOOKUP(KT, BINS) hipLaunchKernelGGL((k_query_lookup<KT, BINS>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
+                                                     (const uint32_t *)b.restarts, (const uint32_t *)b.n_bases, st2, pl.k,                                  \
+                                                     (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, carry, tabs, n_tab, \
+                                                     N, t0, min_count, max_count, hits, depth, (const uint32_t *)b.flags)
+    if (pl.k <= 15) { if (bin_windows) PK_QUERY_LOOKUP(uint32_t, true); else PK_QUERY_LOOKUP(uint32_t, false); }
+    else { if (bin_windows) PK_QUERY_LOOKUP(uint64_t, true); else PK_QUERY_LOOKUP(uint64_t, false); }
 #undef PK_QUERY_LOOKUP
 }
 

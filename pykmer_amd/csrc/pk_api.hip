@@ -340,8 +340,15 @@ struct pk_indexer {
     std::vector<const uint8_t *> q_tables;                  // the caller's device tables; they stay across resets
     int q_min = 1, q_max = 255;
     DevBuf<unsigned long long> q_P;                         // P[r]: valid windows of the stream before record r
-    DevBuf<unsigned long long> q_hits, q_depth;             // row-major [record][table]
+    DevBuf<unsigned long long> q_hits, q_depth;             // row-major [record][table]; with bins [bin][table]
     uint64_t q_windows = 0, q_p_done = 0;                   // valid windows / final entries of P before the next feed
+    // bins (pk_query_set_bins): q_bin valid windows per accumulator row, 0 = one row per record.  q_Bf[r]: the rows before
+    // record r, grown with q_P.  The rows a stream of `bytes` bytes and at most `cap` records can hold need no read-back:
+    // every record adds at most one partial bin, and n bytes hold at most n windows.
+    uint64_t q_bin = 0;
+    DevBuf<unsigned long long> q_Bf;
+    uint64_t q_n_bins = 0;                                  // after finish
+    uint64_t query_rows(uint64_t cap, uint64_t bytes) const { return q_bin ? bytes / q_bin + cap + 1 : cap; }
 
     uint64_t recs_cap() const { return recs.bytes / sizeof(DevRec); }
     uint64_t fq_recs_cap() const { return fq_recs.bytes / sizeof(FqRec); }
@@ -361,9 +368,10 @@ static int ix_reset(pk_indexer *ix) {
     HIPCHK(hipMemcpyAsync(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
     ix->tail_on_host = false;
     if (ix->recs.p) HIPCHK(hipMemsetAsync(ix->recs.p, 0, ix->recs.bytes, ix->stream));
-    for (DevBuf<unsigned long long> *b : {&ix->q_P, &ix->q_hits, &ix->q_depth})
+    for (DevBuf<unsigned long long> *b : {&ix->q_P, &ix->q_Bf, &ix->q_hits, &ix->q_depth})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
     ix->q_windows = ix->q_p_done = 0;
+    ix->q_bin = ix->q_n_bins = 0;
     HIPCHK(hipEventRecord(ix->ev.reset_end, ix->stream));
     ix->zero_timed = false;
     ix->t_zero = 0;
@@ -482,6 +490,29 @@ static int ensure_chunks(pk_indexer *ix, uint32_t n_chunks) {
     return ix->t_l2.reserve((n / 1024 + 1) * sizeof(L2));
 }
 
+// Binned query: the accumulators hold the rows that `bytes` bytes of stream and recs_cap() records can make (contents
+// kept, the rest zero).  They grow by half at least, so that a long stream does not move them with every feed.
+static int ensure_bin_rows(pk_indexer *ix, uint64_t bytes) {
+    if (!ix->q_bin) return PK_OK;
+    const uint64_t rows = ix->query_rows(ix->recs_cap(), bytes);
+    const size_t row = ix->q_tables.size() * sizeof(unsigned long long);
+    if (rows > SIZE_MAX / 2 / row)
+        return fail(PK_ERR_ARG, "bins of %llu windows: %llu rows of %zu tables are beyond the address space; take larger bins",
+                    (unsigned long long)ix->q_bin, (unsigned long long)rows, ix->q_tables.size());
+    for (DevBuf<unsigned long long> *b : {&ix->q_hits, &ix->q_depth}) {
+        if (rows * row <= b->bytes) continue;
+        const size_t want = std::max<size_t>(rows * row, b->bytes + b->bytes / 2);
+        const int rc = b->grow_keep(want, ix->stream);
+        if (rc) {
+            (void)hipGetLastError();
+            const std::string why = g_err;
+            return fail(rc, "bins of %llu windows need two accumulators of %zu bytes (%llu rows, %zu tables); take larger bins: %s",
+                        (unsigned long long)ix->q_bin, want, (unsigned long long)rows, ix->q_tables.size(), why.c_str());
+        }
+    }
+    return PK_OK;
+}
+
 // the sizing rules stay with the callers: the capacities the two record arrays reach are part of the retry behaviour
 static int ensure_recs(pk_indexer *ix, uint64_t need) {
     if (need <= ix->recs_cap()) return PK_OK;
@@ -491,6 +522,7 @@ static int ensure_recs(pk_indexer *ix, uint64_t need) {
     // query mode: the window prefix and the accumulators grow with the record array and keep what they hold
     const size_t row = ix->q_tables.size() * sizeof(unsigned long long);
     if ((rc = ix->q_P.grow_keep(cap * sizeof(unsigned long long), ix->stream))) return rc;
+    if (ix->q_bin) return ix->q_Bf.grow_keep(cap * sizeof(unsigned long long), ix->stream);   // the rows: ensure_bin_rows
     if ((rc = ix->q_hits.grow_keep(cap * row, ix->stream))) return rc;
     return ix->q_depth.grow_keep(cap * row, ix->stream);
 }
@@ -610,7 +642,8 @@ static int feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
 
 // One feed of a query indexer: the structure pass and the squeeze as above, then the lookup kernels (kmer_query.hip) where
 // feed_piece runs launch_partitioned.  There is no sampled layout, so the only flag is 2 (the squeeze backed out): the
-// record array, the window prefix and the accumulators grow, and the squeeze and the lookups run again.
+// record array, the window prefix and the accumulators grow, and the squeeze and the lookups run again.  With bins the
+// accumulators are sized before the kernels run for the rows the stream can hold after this feed (ensure_bin_rows).
 static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if (ix->q_tables.empty()) return fail(PK_ERR_STATE, "pk_query_set_tables comes before the first feed");
     const uint32_t n_chunks = (uint32_t)((n_bytes + CHUNK - 1) / CHUNK);
@@ -624,6 +657,7 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
     Carry *carry = &ix->tail.p->carry;
     const Events &ev = ix->ev;
     const uint32_t N = (uint32_t)ix->q_tables.size();
+    if ((rc = ensure_bin_rows(ix, ix->bytes_fed + n_bytes))) return rc;
     HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
     launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
     launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
@@ -639,9 +673,9 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
                        ix->stream);
         HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
         HIPCHK(hipEventRecord(ev.lookup_begin, ix->stream));
-        launch_query_scan(pl, pb, qb, ix->c_l2s.p, ix->q_windows, ix->recs.p, carry, ix->q_p_done, ix->q_P.p, ix->stream);
+        launch_query_scan(pl, pb, qb, ix->c_l2s.p, ix->q_windows, ix->recs.p, carry, ix->q_p_done, ix->q_P.p, ix->q_Bf.p, ix->q_bin, ix->stream);
         for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
-            launch_query_lookup(pl, pb, qb, ix->c_l2s.p, ix->q_P.p, carry, ix->q_tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
+            launch_query_lookup(pl, pb, qb, ix->c_l2s.p, ix->q_P.p, ix->q_Bf.p, ix->q_bin, carry, ix->q_tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
                                 (uint32_t)ix->q_min, (uint32_t)ix->q_max, ix->q_hits.p, ix->q_depth.p, ix->stream);
         HIPCHK(hipEventRecord(ev.lookup_end, ix->stream));
         HIPCHK(hipGetLastError());
@@ -651,6 +685,7 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
         if (!got[0]) break;
         if (got[0] != 2u || attempt >= 3) return fail(PK_ERR_HIP, "the query feed did not settle (internal error, flag %u)", got[0]);
         if ((rc = ensure_recs(ix, ix->pin->tail.carry.n_recs))) return rc;
+        if ((rc = ensure_bin_rows(ix, ix->bytes_fed + n_bytes))) return rc;
     }
     if (ix->pin->tail.carry.n_recs > squeezed_cap)
         return fail(PK_ERR_HIP, "feed looked up without its squeeze: %llu records, %llu slots (internal error)",
@@ -660,6 +695,7 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
     ix->q_windows = ix->pin->tail.carry.num_kmers;
     ix->q_p_done = ix->n_recs;
     if ((rc = ensure_recs(ix, ix->n_recs + 2 * (ix->n_recs - recs_before) + 1024))) return rc;
+    if ((rc = ensure_bin_rows(ix, ix->bytes_fed + n_bytes))) return rc;
     float scan = 0, squeeze_ms = 0, lookup = 0;
     HIPCHK(hipEventElapsedTime(&scan, ev.scan_begin, ev.scan_end));
     HIPCHK(hipEventElapsedTime(&squeeze_ms, ev.squeeze_begin, ev.squeeze_end));
@@ -691,9 +727,65 @@ extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables
     return PK_OK;
 }
 
+extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (ix->q_tables.empty()) return fail(PK_ERR_STATE, "pk_query_set_tables comes before pk_query_set_bins");
+    if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the bins are set before the first feed (reset the indexer first)");
+    HIPCHK(hipSetDevice(ix->device));
+    ix->q_bin = bin_windows;
+    if (!bin_windows) return PK_OK;
+    // Bf beside P; a reset zeroed what was there, a new array is zeroed here
+    const int rc = ix->q_Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
+    return rc ? rc : ensure_bin_rows(ix, 0);
+}
+
+// the rows of a finished binned stream: the last record's bins are not in Bf
+static int query_count_bins(pk_indexer *ix) {
+    ix->q_n_bins = 0;
+    if (!ix->q_bin || !ix->n_recs) return PK_OK;
+    unsigned long long bf = 0;
+    DevRec last;
+    HIPCHK(hipMemcpy(&bf, ix->q_Bf.p + (ix->n_recs - 1), sizeof bf, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&last, ix->recs.p + (ix->n_recs - 1), sizeof last, hipMemcpyDeviceToHost));
+    ix->q_n_bins = bf + (last.n_valid ? (last.n_valid - 1) / ix->q_bin + 1 : 0);
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_count(pk_indexer *ix, uint64_t *n_bins_out) {
+    if (!ix || !n_bins_out) return fail(PK_ERR_ARG, "null argument");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (!ix->q_bin) return fail(PK_ERR_STATE, "the indexer tallies per record (pk_query_set_bins)");
+    if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
+    *n_bins_out = ix->q_n_bins;
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *depth_out, uint64_t *bin_first_out, uint64_t bins_cap,
+                                    uint64_t recs_cap) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (!ix->q_bin) return fail(PK_ERR_STATE, "the indexer tallies per record (pk_query_set_bins); use pk_query_results");
+    if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
+    if (ix->n_recs > recs_cap || ix->q_n_bins > bins_cap)
+        return fail(PK_ERR_RECS_CAP, "%llu bins and %llu records, capacities %llu and %llu", (unsigned long long)ix->q_n_bins,
+                    (unsigned long long)ix->n_recs, (unsigned long long)bins_cap, (unsigned long long)recs_cap);
+    if (!bin_first_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    if (ix->n_recs) HIPCHK(hipMemcpy(bin_first_out, ix->q_Bf.p, ix->n_recs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    bin_first_out[ix->n_recs] = ix->q_n_bins;
+    if (ix->q_n_bins == 0) return PK_OK;
+    if (!hits_out || !depth_out) return fail(PK_ERR_ARG, "null output pointer");
+    const size_t n = ix->q_n_bins * ix->q_tables.size() * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(hits_out, ix->q_hits.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(depth_out, ix->q_depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
 extern "C" int pk_query_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap) {
     if (!ix) return fail(PK_ERR_ARG, "null indexer");
     if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (ix->q_bin) return fail(PK_ERR_STATE, "the indexer tallies per bin (pk_query_set_bins); use pk_query_bin_results");
     if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
     if (ix->n_recs > recs_cap) return fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)ix->n_recs, (unsigned long long)recs_cap);
     if (ix->n_recs == 0) return PK_OK;
@@ -910,6 +1002,10 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
         }
         if (ix->format == PK_FORMAT_FASTQ) {
             int rc = fq_end_check(ix);
+            if (rc) return rc;
+        }
+        if (ix->query) {
+            int rc = query_count_bins(ix);
             if (rc) return rc;
         }
         ix->finished = true;

@@ -112,12 +112,14 @@ struct QueryBuffers {
 // the workspace of a query feed: the squeezed text and the signals (the PartBuffers fields the squeeze uses; the rest stay
 // null) and the per-slot window counts
 size_t query_workspace(uint32_t n_chunks, uint8_t *base = nullptr, PartBuffers *view = nullptr, QueryBuffers *qview = nullptr);
-// per-slot window counts -> slot_first; P[p_done .. carry->n_recs) from recs[].n_valid (P[r] = valid windows before record r)
+// per-slot window counts -> slot_first; P[p_done .. carry->n_recs) from recs[].n_valid (P[r] = valid windows before record r).
+// bin_windows = W > 0: also Bf over the same r (Bf[r] = bins of W windows in the records before r); 0: Bf is not touched.
 void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,
-                       const Carry *carry, uint64_t p_done, unsigned long long *P, hipStream_t s);
-// tables[0 .. n_tab) are columns t0 .. t0 + n_tab of the row-major [record][N] u64 accumulators hits / depth
-void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P, const Carry *carry,
-                         const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
+                       const Carry *carry, uint64_t p_done, unsigned long long *P, unsigned long long *Bf, uint64_t bin_windows, hipStream_t s);
+// tables[0 .. n_tab) are columns t0 .. t0 + n_tab of the row-major [row][N] u64 accumulators hits / depth; a row is a record
+// (bin_windows = 0) or a bin of bin_windows valid windows: row Bf[r] + (o - P[r]) / W for the window of ordinal o in record r
+void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
+                         const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
                          unsigned long long *hits, unsigned long long *depth, hipStream_t s);
 
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record

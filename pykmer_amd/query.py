@@ -9,6 +9,10 @@ it (pk_query_* in include/pykmer_hip.h: the indexer's structure pass and squeeze
 The tables are staged in HBM the way the merger stages them (raw `.kin` mapped, `.kin.bgz` inflated block-parallel).  When
 they do not all fit the HBM budget they are staged in groups and the query is streamed once per group: the columns are
 independent, so the results concatenate.  One device (PK_DEVICE).
+
+With `bin_windows` = W the same tallies are also kept along each record, in bins of W valid windows (pk_query_set_bins):
+record r with m valid windows j = 0 .. m-1 has ceil(m / W) bins, bin b holding the windows b*W <= j < min((b+1)*W, m); the
+rows are ordered by record, then by bin, and bin_first[r] is record r's first row (bin_first[R] = the number of rows).
 """
 import argparse
 import json
@@ -66,6 +70,27 @@ def validate(tables: Sequence, min_count: int, max_count: int) -> int:
     return kmer_len
 
 
+def validate_bins(bin_windows) -> int:
+    """W of `--bin` / `bin_windows`: an integer >= 1 (a bool or a float is none)."""
+    if isinstance(bin_windows, (bool, np.bool_)) or not isinstance(bin_windows, (int, np.integer)):
+        raise ValueError(f"the bin size must be an integer number of windows, got {bin_windows!r}")
+    if not 1 <= int(bin_windows) < 2 ** 64:
+        raise ValueError(f"the bin size must be at least 1 window (and below 2^64), got {int(bin_windows)}")
+    return int(bin_windows)
+
+
+def record_sums(rows: np.ndarray, bin_first: np.ndarray) -> np.ndarray:
+    """(R, N) sums of the (B, N) `rows` over each record's rows [bin_first[r], bin_first[r + 1]); a record without a row
+    sums to zero (np.add.reduceat would give it the next record's first row)."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    first = np.asarray(bin_first, dtype=np.int64)
+    assert rows.ndim == 2 and first.ndim == 1 and first.size >= 1 and first[0] == 0 and first[-1] == rows.shape[0] \
+        and np.all(np.diff(first) >= 0), "bin_first does not describe the rows"
+    cum = np.zeros((rows.shape[0] + 1, rows.shape[1]), dtype=np.uint64)
+    np.cumsum(rows, axis=0, out=cum[1:])
+    return cum[first[1:]] - cum[first[:-1]]
+
+
 def table_groups(n_tables: int, table_bytes: int, budget: int) -> List[Tuple[int, int]]:
     """[lo, hi) index ranges of the tables staged together: as many as fit `budget` bytes, at least one."""
     per = max(1, int(budget) // max(1, int(table_bytes)))
@@ -103,27 +128,37 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
     return Staged([b.ptr for b in bufs], bufs)
 
 
-def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True) -> dict:
+def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
+              bin_windows: int = None) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
-    same query only add columns)."""
+    same query only add columns).  `bin_windows`: tally per bin (bin_hits, bin_depth, bin_first); the per-record arrays
+    are then the sums of each record's rows."""
     src = _Input(query_file, keep=first, quiet=not first)
+    binned = {}
     with _lib.QueryIndexer(kmer_len, device=device, fmt=src.fmt) as q:
         q.set_tables(ptrs, min_count, max_count)
+        if bin_windows is not None:
+            q.set_bins(bin_windows)
         for piece in src.pieces():
             q.feed(piece)
         fin = q.finish()
         recs = q.records(fin["n_records"])
-        hits, depth = q.results(fin["n_records"])
+        if bin_windows is not None:
+            bin_hits, bin_depth, bin_first = q.bin_results(fin["n_records"])
+            hits, depth = record_sums(bin_hits, bin_first), record_sums(bin_depth, bin_first)
+            binned = {"bin_hits": bin_hits.copy(), "bin_depth": bin_depth.copy(), "bin_first": bin_first}
+        else:
+            hits, depth = q.results(fin["n_records"])
         timings = q.timings()
     out = {"seq_len": recs["seq_len"].astype(np.uint64), "n_valid": recs["n_valid_kmers"].astype(np.uint64), "hits": hits.copy(),
-           "depth": depth.copy(), "num_kmers": fin["num_kmers"], "total_bp": fin["total_bp"], "timings": timings}
+           "depth": depth.copy(), "num_kmers": fin["num_kmers"], "total_bp": fin["total_bp"], "timings": timings, **binned}
     if first:
         out["names"] = [nm.decode("utf-8", "replace") for nm in src.names(recs)]
     return out
 
 
 def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
-                  threads: int = DEFAULT_THREADS, stage=None, run=None) -> dict:
+                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None) -> dict:
     """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
     merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
     kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
@@ -131,7 +166,14 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     `hbm_budget` (bytes; default PK_MERGE_HBM_BUDGET, else 80 % of the free HBM less the feed's workspace) bounds the tables
     staged beside each other; more are staged group after group, the query streamed once per group.
     `stage(tables, device)` -> Staged and `run(query_file, kmer_len, ptrs, min_count, max_count, device, first)` -> dict
-    default to stage_tables / run_query (the CPU-only tests substitute both)."""
+    default to stage_tables / run_query (the CPU-only tests substitute both).
+
+    `bin_windows` = W >= 1 adds bin_hits, bin_depth (B, N) and bin_first (R + 1,), uint64: the same tallies per bin of W
+    valid windows along each record (the module's docstring); hits / depth are then the sums over each record's rows, from
+    the same single lookup.  `run` receives bin_windows by keyword, and only when it is set."""
+    if bin_windows is not None:
+        bin_windows = validate_bins(bin_windows)
+    extra = {} if bin_windows is None else {"bin_windows": bin_windows}
     tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
     kmer_len = validate(tables, min_count, max_count)
     stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
@@ -147,7 +189,7 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         staged = stage(tables[lo:hi], device)
         _mark(f"tables {lo}..{hi - 1} staged")
         try:
-            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0)
+            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0, **extra)
         finally:
             staged.free()
         _mark(f"query streamed against tables {lo}..{hi - 1}")
@@ -159,6 +201,12 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
                 "query changed between table groups"
             result["hits"] = np.concatenate([result["hits"], part["hits"]], axis=1)
             result["depth"] = np.concatenate([result["depth"], part["depth"]], axis=1)
+            if bin_windows is not None:
+                assert np.array_equal(part["bin_first"], result["bin_first"]), "bins changed between table groups"
+                result["bin_hits"] = np.concatenate([result["bin_hits"], part["bin_hits"]], axis=1)
+                result["bin_depth"] = np.concatenate([result["bin_depth"], part["bin_depth"]], axis=1)
+    if bin_windows is not None:
+        result["bin_windows"] = bin_windows
     result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
     return result
 
@@ -198,10 +246,56 @@ def write_kmq(project_name: str, result: dict, query_file: str, data: list, colu
     tmp.rename(kmq)
 
 
+def kmb_paths(project_name: str) -> Tuple[Path, Path, Path]:
+    return Path(f"{project_name}.kmb"), Path(f"{project_name}.kmb.json"), Path(f"{project_name}.kmb.tsv")
+
+
+def write_kmb(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
+    """`<project>.kmb` (np.savez_compressed), `.kmb.json` and `.kmb.tsv`: the binned rows, each file through `.tmp` + rename."""
+    kmb, meta, tsv = kmb_paths(project_name)
+    W = int(result["bin_windows"])
+    hits = np.ascontiguousarray(result["bin_hits"], dtype=np.uint64)
+    depth = np.ascontiguousarray(result["bin_depth"], dtype=np.uint64)
+    bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
+    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
+    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
+    names = [n.strip() for n in result["names"]]
+    B = int(bin_first[-1])
+    assert hits.shape == depth.shape == (B, len(columns)) and bin_first.shape == (len(names) + 1,)
+    assert n_valid.shape == seq_len.shape == (len(names),)
+    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
+              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data,
+              "bin_windows": W, "n_bins": B}
+    print(f"saving {meta}")
+    tmp = Path(f"{meta}.tmp")
+    with tmp.open(mode="wt") as fhd:
+        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
+    tmp.rename(meta)
+    print(f"saving {tsv}")
+    tmp = Path(f"{tsv}.tmp")
+    with tmp.open(mode="wt") as fhd:
+        fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + [str(c) for c in columns]) + "\n")
+        for r, name in enumerate(names):
+            m = int(n_valid[r])
+            for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
+                row = hits[int(bin_first[r]) + b]
+                fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + [str(int(v)) for v in row]) + "\n")
+    tmp.rename(tsv)
+    print(f"saving {kmb}")
+    tmp = Path(f"{kmb}.tmp")
+    with tmp.open(mode="wb") as fhd:
+        np.savez_compressed(fhd, hits=hits, depth=depth, bin_first=bin_first, n_valid=n_valid, seq_len=seq_len, bin_windows=np.uint64(W),
+                            kmer_len=np.int64(result["kmer_len"]), min_count=np.int64(result["min_count"]),
+                            max_count=np.int64(result["max_count"]))
+    tmp.rename(kmb)
+
+
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
-          threads: int = DEFAULT_THREADS, hbm_budget: int = None) -> dict:
-    """The CLI's work: validate, query, write the three files; returns query_records' result."""
-    for f in kmq_paths(project_name):
+          threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None) -> dict:
+    """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result."""
+    if bin_windows is not None:
+        bin_windows = validate_bins(bin_windows)
+    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
     if not os.path.exists(query_file):
@@ -218,11 +312,22 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         data.append({"pos": pos, "index_file": Path(kin), "description_file": desc, "header": header})
     validate(headers, min_count, max_count)
     _mark("tables verified")
-    result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads)
+    if bin_windows is None:
+        result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads)
+    else:
+        try:
+            result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
+                                   bin_windows=bin_windows)
+        except _lib.PkError as exc:
+            if exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
+                raise
+            raise ValueError(f"{exc}; the rows of --bin {bin_windows} do not fit the device: use a larger --bin") from exc
     columns = [str(h.project_name) for h in headers]
     for v in data:
         v["header"] = v["header"].to_dict(lean=True)
     write_kmq(project_name, result, query_file, data, columns)
+    if bin_windows is not None:
+        write_kmb(project_name, result, query_file, data, columns)
     _mark("files renamed")
     return result
 
@@ -235,6 +340,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--min-count", type=int, default=1, help="Minimum Kmer Count [1]")
     parser.add_argument("--max-count", type=int, default=255, help="Maximum Kmer Count [255]")
     parser.add_argument("--threads", type=int, default=DEFAULT_THREADS, help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
+    parser.add_argument("--bin", type=int, default=None, metavar="W", dest="bin_windows",
+                        help="Also write <P>.kmb[.json|.tsv]: the hits along each record in bins of W valid windows [off]")
     return parser
 
 
@@ -242,10 +349,10 @@ def main(argv: List[str] = None) -> None:
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     try:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
-                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads)
+                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows)
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)
     hits = result["hits"]
     print(f"{len(result['names'])} records, {int(result['n_valid'].sum()):,d} k-mers, {hits.shape[1]} tables, "
-          f"{result['n_groups']} table group(s)")
+          f"{result['n_groups']} table group(s)" + (f", {int(result['bin_first'][-1]):,d} bins" if args.bin_windows is not None else ""))

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""query.py Project_Name queries.fa|.fq[.gz|.bgz] a.kin[.bgz] b.kin[.bgz] ... [--min-count --max-count --threads]
+"""query.py Project_Name queries.fa|.fq[.gz|.bgz] a.kin[.bgz] b.kin[.bgz] ... [--min-count --max-count --threads --bin W]
 
 Per-record k-mer hits of a FASTA / FASTQ file against N k-mer tables (no counterpart in the reference): writes
 `<project>.kmq` (np.savez_compressed: hits, depth (R,N) uint64; n_valid, seq_len (R,) uint64; kmer_len, min_count, max_count),
 `<project>.kmq.json` (record names and the tables' metadata) and `<project>.kmq.tsv` (one line per record: the hits).  The
 tables are staged in HBM (in groups if they do not fit: PK_MERGE_HBM_BUDGET) and every k-mer of the query is looked up on
-the GPU; one device (PK_DEVICE).
+the GPU; one device (PK_DEVICE).  `--bin W` also writes `<project>.kmb`, `.kmb.json` and `.kmb.tsv`: the same hits along each
+record, one row per bin of W valid windows (README "Binned hits").
 """
 import os
 import sys

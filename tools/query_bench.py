@@ -9,9 +9,14 @@ HIP-event times of the structure pass, the squeeze and the lookup kernels (pk_in
     python tools/query_bench.py [out.json]     both shapes, then one `rocprofv3 --kernel-trace --stats` run of a child
                                                (`--once genome`), whose kernel stats go to profiles/query_genome_kernel_stats.csv
     python tools/query_bench.py --once SHAPE   warm-up + one run of one shape (what the profiled child runs)
+    --bin W        the same inputs tallied in bins of W valid windows (pk_query_set_bins); the rows are fetched with
+                   bin_results instead of results
+    --runs R       timed runs per shape [5]
+    --no-trace     skip the rocprofv3 run
     PK_QUERY_BENCH_BP / PK_QUERY_BENCH_TABLE_BP scale the genome and the table genomes down for a rehearsal.
 
-Writes profiles/query_k15_n13.json (or out.json)."""
+Writes profiles/query_k15_n13.json (or out.json).  `lookup_s_runs` holds the lookup kernels' HIP-event time of every timed
+run; profiles/query_bins_k15_n13.json was put together from such runs of two builds."""
 import csv
 import glob
 import json
@@ -52,27 +57,34 @@ def shapes(genome_bp: int):
     yield "reads", lambda: synth.generate(34, genome_bp // 2, max(1, genome_bp // 2000))
 
 
-def run_shape(make, ptrs, runs: int):
+def run_shape(make, ptrs, runs: int, bin_windows: int = None):
     fa, bp = make()
     text = _lib.DeviceBuffer(len(fa) + 64)
     text.upload(np.asarray(fa))
     try:
         with _lib.QueryIndexer(K) as q:
-            times = []
+            times, lookups = [], []
             for i in range(runs + 1):                                     # the first run warms up: allocations, code load
                 q.reset()
                 q.set_tables(ptrs, 1, 255)
+                if bin_windows is not None:
+                    q.set_bins(bin_windows)
                 t0 = time.perf_counter()
                 q.feed_device(text.ptr, len(fa))
                 fin = q.finish()
-                hits, depth = q.results(fin["n_records"])
+                if bin_windows is not None:
+                    hits, depth, bin_first = q.bin_results(fin["n_records"])
+                else:
+                    hits, depth = q.results(fin["n_records"])
                 if i:
                     times.append(time.perf_counter() - t0)
+                    lookups.append(float(q.timings()["lookup_s"]))         # a reset zeroes the library's timers
             t = q.timings()
         med = statistics.median(times) if times else float("nan")
         front = t["scan_s"] + t["squeeze_s"]
         return {"bp": int(bp), "text_bytes": len(fa), "records": fin["n_records"], "windows": fin["num_kmers"], "tables": len(ptrs),
-                "runs": times, "median_s": med, "best_s": min(times) if times else med, "bp_per_s": bp / med,
+                "bin_windows": bin_windows, "rows": int(hits.shape[0]), "runs": times, "lookup_s_runs": lookups,
+                "lookup_s_median": statistics.median(lookups) if lookups else float("nan"), "median_s": med, "best_s": min(times) if times else med, "bp_per_s": bp / med,
                 "lookups_per_s": fin["num_kmers"] * len(ptrs) / med,
                 "device_s": {"structure_pass": t["scan_s"], "squeeze": t["squeeze_s"], "lookup_kernels": t["lookup_s"]},
                 "lookup_share_of_device_time": t["lookup_s"] / (front + t["lookup_s"]),
@@ -96,24 +108,34 @@ def kernel_stats(argv, dest):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv, args, opts = sys.argv[1:], [], {"--bin": None, "--runs": 5}
+    while argv:
+        a = argv.pop(0)
+        if a in opts:
+            opts[a] = int(argv.pop(0))
+        elif not a.startswith("--"):
+            args.append(a)
+    bin_windows, runs = opts["--bin"], opts["--runs"]
     genome_bp = int(os.environ.get("PK_QUERY_BENCH_BP", 800_000_000))
     table_bp = int(os.environ.get("PK_QUERY_BENCH_TABLE_BP", 40_000_000))
     bufs = stage_tables(table_bp)
     ptrs = [b.ptr for b in bufs]
     if "--once" in sys.argv:
-        run_shape(dict(shapes(genome_bp))[args[0]], ptrs, 1)
+        run_shape(dict(shapes(genome_bp))[args[0]], ptrs, 1, bin_windows)
         return
     out = {"k": K, "n_tables": N, "table_genome_bp": table_bp, "layout": "one 4^k-byte table per sample (not interleaved)",
-           "method": "1 warm-up + median of 5 runs of reset/feed_device/finish/results; device_s from HIP events (pk_indexer_timings)"}
+           "bin_windows": bin_windows,
+           "method": f"1 warm-up + median of {runs} runs of reset/feed_device/finish/results; device_s from HIP events (pk_indexer_timings)"}
     for name, make in shapes(genome_bp):
-        out[name] = run_shape(make, ptrs, 5)
+        out[name] = run_shape(make, ptrs, runs, bin_windows)
         print(name, json.dumps(out[name]), flush=True)
     for b in bufs:
         b.free()
-    rows = kernel_stats([sys.executable, os.path.abspath(__file__), "--once", "genome"], os.path.join(ROOT, "profiles", "query_genome_kernel_stats.csv"))
-    out["genome_kernel_trace_ms_per_call"] = {r["Name"].split("(")[0][:60]: round(float(r["AverageNs"]) / 1e6, 4) for r in rows
-                                               if "k_query" in r["Name"] or "k_squeeze" in r["Name"]}
+    if "--no-trace" not in sys.argv:
+        once = [sys.executable, os.path.abspath(__file__), "--once", "genome"] + (["--bin", str(bin_windows)] if bin_windows is not None else [])
+        rows = kernel_stats(once, os.path.join(ROOT, "profiles", "query_genome_kernel_stats.csv"))
+        out["genome_kernel_trace_ms_per_call"] = {r["Name"].split("(")[0][:60]: round(float(r["AverageNs"]) / 1e6, 4) for r in rows
+                                                   if "k_query" in r["Name"] or "k_squeeze" in r["Name"]}
     path = args[0] if args else os.path.join(ROOT, "profiles", "query_k15_n13.json")
     with open(path + ".tmp", "w") as fh:
         json.dump(out, fh, indent=1)
