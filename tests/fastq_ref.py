@@ -108,3 +108,76 @@ def read_set(n_reads: int, length: int = 150, seed: int = 0, genome_bp: int = 1 
         fq.append(b"@" + name + nl + s + nl + b"+" + nl + qual[i].tobytes() + nl)
         fa.append(b">" + name + nl + s + nl)
     return b"".join(fq), b"".join(fa)
+
+
+SCAN_RUNS = 1024                                 # k_fq_scan: one thread per run of ceil(n_chunks / 1024) consecutive chunks
+
+
+def seam_read_set(n_chunks: int, crlf: bool, seed: int, chunk: int = 16384):
+    """(fastq, fasta, names_at, placed): reads of 30 .. 250 bp whose FASTQ text has exactly `n_chunks` 16 KiB chunks, for the
+    seams between the scan's runs of per = ceil(n_chunks / SCAN_RUNS) chunks (byte offsets B = t * per * chunk).  The
+    varied line lengths put the seams into lines of every role; five seams are hand-placed (`placed`: kind -> B):
+
+      "crlf"         a sequence line's CR at B - 1, its LF at B (this record has CR LF lines whatever `crlf` says);
+      "at_quality"   a quality line that begins with '@' begins at B;
+      "plus_line"    line 3 (the '+') begins at B;
+      "empty_read"   a read without bases: line 1 ends with the byte before B, the empty line 2 begins at B;
+      "name_across"  line 1 begins five bytes before B.
+
+    `fasta` is what fastq_to_fasta makes of the FASTQ, built directly; names_at[i] is where name i lies in the FASTQ."""
+    rng = np.random.default_rng(seed)
+    per = -(-n_chunks // SCAN_RUNS)
+    run, n_runs = per * chunk, -(-n_chunks // per)
+    nl = b"\r\n" if crlf else b"\n"
+    pool = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 1 << 20)]
+    pool[rng.random(pool.size) < 0.002] = ord("N")
+    pool, qpool = pool.tobytes(), rng.integers(33, 74, 1 << 20, dtype=np.uint8).tobytes()
+    fq, fa, names_at, placed = [], [], [], {}
+    pos, n = 0, 0
+
+    def emit(name, seq, qual, eol=nl):
+        nonlocal pos, n
+        rec = b"@" + name + eol + seq + eol + b"+" + eol + qual + eol
+        names_at.append(pos + 1)
+        fq.append(rec)
+        fa.append(b">" + name + eol + seq + eol)
+        pos += len(rec)
+        n += 1
+
+    def random_read():
+        length, at, qat = int(rng.integers(30, 251)), int(rng.integers(0, (1 << 20) - 250)), int(rng.integers(0, (1 << 20) - 250))
+        emit(b"r%d len=%d" % (n, length), pool[at:at + length], qpool[qat:qat + length])
+
+    def advance_to(start):                       # random reads, then one whose name is padded so that it ends at `start`
+        while start - pos > 700:
+            random_read()
+        pad = start - pos - 2 - 2 * 40 - 4 * len(nl)
+        assert pad >= 8, (start, pos)
+        emit((b"pad%d_" % n).ljust(pad, b"p"), pool[:40], qpool[:40])
+        assert pos == start
+
+    seq, qual = pool[1000:1050], qpool[1000:1050]
+    for t, kind in sorted({1: "crlf", n_runs // 3: "at_quality", n_runs // 2: "plus_line", 2 * n_runs // 3: "empty_read", n_runs - 1: "name_across"}.items()):
+        B = t * run
+        placed[kind] = B
+        if kind == "crlf":
+            advance_to(B - 4 - len(b"placed_crlf") - len(seq))
+            emit(b"placed_crlf", seq, qual, b"\r\n")
+        elif kind == "at_quality":
+            advance_to(B - (2 + len(b"placed_at") + len(seq) + 3 * len(nl)))
+            emit(b"placed_at", seq, b"@" + qual[1:])
+        elif kind == "plus_line":
+            advance_to(B - (1 + len(b"placed_plus") + len(seq) + 2 * len(nl)))
+            emit(b"placed_plus", seq, qual)
+        elif kind == "empty_read":
+            advance_to(B - (1 + len(b"placed_empty") + len(nl)))
+            emit(b"placed_empty", b"", b"")
+        else:
+            advance_to(B - 5)
+            emit(b"placed_name_across the seam", seq, qual)
+    assert len(placed) == 5
+    while pos <= (n_chunks - 1) * chunk:
+        random_read()
+    fq, fa = b"".join(fq), b"".join(fa)
+    assert -(-len(fq) // chunk) == n_chunks
+    return fq, fa, np.array(names_at, dtype=np.uint64), placed

@@ -336,6 +336,184 @@ def deep_seam_fasta(k: int, seed: int = 19, pad_to_chunks: int = 0, chunk: int =
     return bytes(out), sites
 
 
+# ------------------------------------------------------------------ scan-tile seams (1024 chunks) -------------------
+# Per-chunk summaries are combined across a feed in tiles of 1024 chunks (SCAN_T, kmer_count.hip; k_query_scan and
+# k_fq_scan walk 1024 at a time too): byte TILE * t of a feed is where a tile seed, not a neighbouring thread, hands the
+# parser state on.
+TILE = 1024 * 16384
+TILE_HEADER = b">tile_seams\n"
+TINY_RECORDS = 400
+TINY_BASES = b"ACGTTGCAAGCTTAGGCTAACGTAT"
+
+
+def tile_site_kinds(k: int) -> list:
+    """Every (kind, d) that tile_seam_fasta writes."""
+    return ([("header_across", d) for d in (1, 2, 63, 64, 65, 20000)] + [("header_at", 0), ("header_ends", 0), ("crlf_split", 0), ("blank_gt", 0)]
+            + [("pending_blanks_base", d) for d in (1, 40)] + [("pending_blanks_eol", d) for d in (1, 40)]
+            + [("N", d) for d in (0, 1, k - 2, k - 1, k, k + 3)] + [("empty_chunks", 0), ("tiny_records", 0)])
+
+
+def _fill_lines(rng, n: int) -> bytes:
+    """Exactly n bytes (n >= 2) of random sequence lines of at most 60 bases, each with its newline."""
+    import numpy as np
+    assert n >= 2, n
+    full, rest = divmod(n, 61)
+    if rest == 1:                                            # no line of a newline alone: 61 + 1 = 31 + 31
+        full, rest = full - 1, 62
+        assert full >= 0
+    short = b""
+    if rest == 62:
+        short = _rand_bases(rng, 30) + b"\n" + _rand_bases(rng, 30) + b"\n"
+    elif rest:
+        short = _rand_bases(rng, rest - 1) + b"\n"
+    seq = np.frombuffer(_rand_bases(rng, full * 60), dtype=np.uint8)
+    return short + _lines(seq, 60)
+
+
+def _with_motif(bases: bytes, at: int) -> bytes:
+    out = bytearray(bases)
+    out[at: at + len(SEAM_MOTIF)] = SEAM_MOTIF
+    assert len(out) == len(bases)
+    return bytes(out)
+
+
+def _tile_site(rng, k: int, kind: str, d: int, B: int):
+    """(pre, post, plan): the bytes that end at B, the bytes that begin there (they end with a newline), and what the site
+    is meant to be: `crossing` valid windows begin in front of B and end at or behind it, the oldest `reach` bases in front;
+    `span`: the bytes the site wrote; `records`: (name_off, name,
+    seq_len or None) of the records the site opens (seq_len where the record also ends inside the site)."""
+    def run_line(n):                                         # n bases and a newline, SEAM_MOTIF first
+        return _with_motif(_rand_bases(rng, n), 0) + b"\n"
+
+    recs, crossing = [], 0
+    if kind == "header_across":                              # '>' d bytes before B, the line ends behind B
+        name = (b"across_d%d_" % d).ljust(d + 11, b"h")
+        pre, post = (b">" + name)[:d], (b">" + name)[d:] + b"\n" + run_line(60)
+        recs.append((B - d + 1, name, None))
+    elif kind == "header_at":                                # a sequence line ends with the tile, '>' opens the next one
+        pre, post = b"", b">at_the_seam\n" + run_line(60)
+        recs.append((B + 1, b"at_the_seam", None))
+    elif kind == "header_ends":                              # the header's newline is the tile's last byte
+        pre, post = b">ends_with_the_tile\n", run_line(60)
+        recs.append((B - len(pre) + 1, b"ends_with_the_tile", None))
+    elif kind == "crlf_split":                               # CR at B - 1, LF at B
+        lines = [_rand_bases(rng, 60) for _ in range(10)]
+        lines[4] = _with_motif(lines[4], 60 - (k - 1))
+        pre = b">crlf_lines\r\n" + b"\r\n".join(lines[:5]) + b"\r"
+        post = b"\n" + b"\r\n".join(lines[5:]) + b"\r\n"
+        recs.append((B - len(pre) + 1, b"crlf_lines", None))
+        crossing = k - 1
+    elif kind == "blank_gt":                                 # the line is still at its start when the seam comes
+        pre, post = b"  \t", b">blank_gt name\n" + run_line(60)
+        recs.append((B + 1, b"blank_gt name", None))
+    elif kind == "pending_blanks_base":                      # interior blanks: they count as sequence and break the run
+        pre, post = _rand_bases(rng, 30) + b" " * d, run_line(40)
+    elif kind == "pending_blanks_eol":                       # trailing blanks: stripped, the run goes on in the next line
+        pre, post = _with_motif(_rand_bases(rng, 30), 30 - (k - 1)) + b" " * d, b"\n" + _rand_bases(rng, 60) + b"\n"
+        crossing = k - 1
+    elif kind == "N":                                        # d valid bases between an N and B, the line goes on
+        run = _with_motif(_rand_bases(rng, d + 40), max(0, d - (k - 1)))
+        pre, post = _rand_bases(rng, 30) + b"N" + run[:d], run[d:] + b"\n"
+        crossing = min(d, k - 1)
+    elif kind == "empty_chunks":                             # the newest bases lie three chunks back
+        pre, post = _with_motif(_rand_bases(rng, 30), 30 - (k - 1)) + b"\n" * (2 * 16384), _rand_bases(rng, 40) + b"\n"
+        crossing = k - 1
+    elif kind == "tiny_records":                             # record number TINY_RECORDS / 2 - 1 lies across B
+        half = TINY_RECORDS // 2
+        texts = []
+        for i in range(TINY_RECORDS):
+            n = k + 1 if i == half - 1 else i % (k + 2)
+            seq = _with_motif(_rand_bases(rng, n), 0) if i == half - 1 else (TINY_BASES * 2)[:n]
+            texts.append((b">t%d\n" % i, seq))
+        pre = b"".join(h + s + b"\n" for h, s in texts[:half - 1]) + texts[half - 1][0] + texts[half - 1][1][:k - 1]
+        post = texts[half - 1][1][k - 1:] + b"\n" + b"".join(h + s + b"\n" for h, s in texts[half:]) + b">behind_the_tiny_records\n"
+        at = B - len(pre)
+        for h, s in texts:
+            recs.append((at + 1, h[1:-1], len(s)))
+            at += len(h) + len(s) + 1
+        recs.append((at + 1, b"behind_the_tiny_records", None))
+        crossing = 2                                         # k + 1 bases, k - 1 of them in front of B: both windows cross
+        assert len(pre) <= 4000 and len(post) <= 4000
+    else:
+        raise KeyError(kind)
+    reach = k - 1 if kind == "tiny_records" else crossing    # bases in front of B of the oldest window across it
+    return pre, post, {"crossing": crossing, "reach": reach, "records": recs, "span": (B - len(pre), B + len(post))}
+
+
+def tile_seam_fasta(k: int, sites_at, seed: int, plan: dict = None, n_bytes: int = None, gap_chunks: int = 16):
+    """(text, sites): ordinary 60-column sequence lines with one site per entry (kind, d, offset) of `sites_at`; `offset`
+    is a byte offset of the text -- the caller puts it on a multiple of TILE of the feed it will lie in.  What the text
+    holds at B = offset (tile_site_kinds lists the kinds):
+
+      "header_across", d     '>' d bytes before B, the header line ends behind B (d = 20000: it fills the tile's last chunk);
+      "header_at"            a line terminator is the last byte before B, '>' the byte at B;
+      "header_ends"          a header's terminator is the last byte before B, bases begin at B;
+      "crlf_split"           CR at B - 1, LF at B, inside a record of CR LF lines;
+      "blank_gt"             a line "  \t>name", its blanks in front of B and '>' at B;
+      "pending_blanks_base", d   d blanks in front of B inside a sequence line, a base at B: the run breaks;
+      "pending_blanks_eol", d    d blanks in front of B, the terminator at B: trailing blanks, the run goes on;
+      "N", d                 exactly d valid bases between an N and B, the run goes on behind B on the same line;
+      "empty_chunks"         the two chunks in front of B are all newlines, the bases behind B continue the run from before;
+      "tiny_records"         TINY_RECORDS records `>tN` of 0 .. k + 1 bases around B, one of them across it, and a header
+                             behind them.
+
+    Where the oldest window that crosses B begins -- or, where none does, the first one behind B -- the text holds
+    SEAM_MOTIF.  The text ends without a newline, 16 chunks behind the last site or, if given, after `n_bytes` bytes.
+    `plan`, if given, receives per site what _tile_site planned; `gap_chunks`: the least run of plain sequence lines between
+    two sites (a text of a prescribed size may not have room for 16 chunks)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    parts, pos, sites = [TILE_HEADER], len(TILE_HEADER), []
+    for kind, d, B in sorted(sites_at, key=lambda s: s[2]):
+        pre, post, p = _tile_site(rng, k, kind, d, B)
+        assert B - len(pre) - pos >= gap_chunks * 16384, "chunks of plain sequence in front of every site"
+        parts.append(_fill_lines(rng, B - len(pre) - pos))
+        parts += [pre, post]
+        pos = B + len(post)
+        sites.append((kind, d, B))
+        if plan is not None:
+            plan[(kind, d, B)] = p
+    end = n_bytes if n_bytes is not None else pos + 16 * 16384 + 57
+    assert end - 57 - pos >= 2 * 16384, "plain sequence behind the last site"
+    parts.append(_fill_lines(rng, end - 57 - pos))
+    parts.append(_rand_bases(rng, 57))                       # no newline at the end
+    return b"".join(parts), sites
+
+
+def tile_cases(k: int) -> list:
+    """tile_site_kinds(k) in cases of at most four sites: case i puts its sites on bytes TILE, 2 TILE, ... of one feed."""
+    kinds = tile_site_kinds(k)
+    return [[(kind, d, TILE * (j + 1)) for j, (kind, d) in enumerate(kinds[i:i + 4])] for i in range(0, len(kinds), 4)]
+
+
+TILE_FEEDS = (TILE + 3 * 16384 + 7, TILE + 5 * 16384)       # two feeds of more than 1024 chunks each
+
+
+def tile_second_feed_cases(k: int) -> list:
+    """Two-site cases for a text fed as TILE_FEEDS: one site of every kind on the second feed's own tile seam (byte
+    TILE_FEEDS[0] + TILE of the text), and one of the remaining (kind, d) on the first feed's."""
+    second = [("header_across", 1), ("header_across", 20000), ("header_at", 0), ("header_ends", 0), ("crlf_split", 0), ("blank_gt", 0),
+              ("pending_blanks_base", 40), ("pending_blanks_eol", 40), ("N", k - 1), ("empty_chunks", 0), ("tiny_records", 0)]
+    first = [s for s in tile_site_kinds(k) if s not in second]
+    assert len(first) == len(second)
+    return [[(*a, TILE), (*b, TILE_FEEDS[0] + TILE)] for a, b in zip(first, second)]
+
+
+def tile_deep_sites(k: int) -> list:
+    """The sites of the deep-window cases (k = 19, 21), each on byte TILE of a text of its own."""
+    return [("N", k - 1, TILE), ("N", k + 3, TILE), ("empty_chunks", 0, TILE)]
+
+
+QUERY_TILE_BYTES = 2 * TILE + 5 * 16384
+QUERY_TILE_CUT = TILE + 2 * 16384 + 7                       # two feeds of more than 1024 chunks each
+
+
+def tile_query_sites(k: int) -> list:
+    """Sites of the query text: chunks 1024 and 2048 of the text, and chunk 1024 of its second feed when it is cut at
+    QUERY_TILE_CUT.  The record that opens the text runs on across chunk 1024 (the N site lies inside it)."""
+    return [("N", k - 1, TILE), ("tiny_records", 0, QUERY_TILE_CUT + TILE), ("header_across", 65, 2 * TILE)]
+
+
 def plain_sequence_fasta(n_bp: int, seed: int = 3, n_at=(), motif_at=()):
     """One record, its `n_bp` bases on ONE line.  `n_at`: byte offsets that hold an N instead; `motif_at`: byte offsets where
     SEAM_MOTIF is written.  Bytes: a 7-byte header line, base i at offset 7 + i."""
