@@ -139,7 +139,8 @@ void pk_indexer_destroy(pk_indexer *ix);
  * otherwise).  set_format, feed, feed_device, finish, records, fastq_stats, reset and destroy work as for any indexer;
  * finish reports num_kmers, total_bp and the record count and zeroes a non-null hist256_out; the table accessors answer
  * PK_ERR_STATE.  pk_indexer_timings: [0] [1] [4] as above, [5] the seconds of the lookup kernels (window counts, ordinal
- * scan, gathers and tallies), [2] [3] as above, the rest 0.
+ * scan, gathers and tallies), [6] the seconds of the coordinate kernels (0 without pk_query_set_coords), [2] [3] as above,
+ * the rest 0.
  * pk_query_set_tables: after create or reset and before the first feed (PK_ERR_STATE otherwise; a feed without tables is
  * PK_ERR_STATE too).  dev_tables are N >= 1 device buffers of 4^k bytes on the indexer's device; the caller owns them and
  * keeps them alive through the feeds.  They stay set across resets.  1 <= min_count <= max_count <= 255.  One lookup
@@ -161,7 +162,22 @@ void pk_indexer_destroy(pk_indexer *ix);
  * pk_query_bin_count: after pk_indexer_finish, the number of rows B.
  * pk_query_bin_results: after pk_indexer_finish.  hits_out / depth_out receive B * N u64 each, row-major [row * N + t];
  * bin_first_out receives R + 1 u64.  PK_ERR_RECS_CAP, with the needed numbers in the message, if B > bins_cap or
- * R > recs_cap; PK_ERR_STATE when bins are off. */
+ * R > recs_cap; PK_ERR_STATE when bins are off.
+ *
+ * Coordinates: where a row lies on its record, in bases.  Positions are counted as seq_len counts them: within a record
+ * every sequence character gets the next position, 0-based, valid base or not; blanks inside a sequence line get theirs once
+ * a non-blank sequence character follows them on the same line; line terminators, the leading and trailing blanks of a line,
+ * header text and text before the first header get none.  A record's positions are [0, seq_len); for FASTQ they are those
+ * within the read (line 2).  A valid window is k consecutive positions.  For the row of record r and bin b,
+ *   bin_start[row] = the position of the first base of window b*W of r
+ *   bin_end[row]   = one past the position of the last base of window min((b+1)*W, m) - 1 of r
+ * so 0 <= bin_start < bin_end <= seq_len[r], bin_end - bin_start >= (windows of the row) + k - 1 with equality exactly when
+ * no invalid character lies inside the span, and bin_start grows strictly along a record.
+ * pk_query_set_coords: after pk_query_set_bins with W > 0 and before the first feed (PK_ERR_STATE otherwise); on != 0 keeps
+ * the coordinates, 0 (the default) does not.  The setting goes with the bins: a reset clears it with them, and so does a
+ * later pk_query_set_bins.  The two arrays are sized with the accumulators (one u64 each per row) and fail the same way.
+ * pk_query_bin_coords: after pk_indexer_finish.  start_out / end_out receive B u64 each, in row order.  PK_ERR_STATE when
+ * coordinates are off; PK_ERR_RECS_CAP, with the needed number in the message, if B > bins_cap. */
 int pk_query_create(pk_indexer **out, int k, int device);
 int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
 int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);
@@ -169,6 +185,8 @@ int pk_query_set_bins(pk_indexer *q, uint64_t bin_windows);
 int pk_query_bin_count(pk_indexer *q, uint64_t *n_bins_out);
 int pk_query_bin_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t *bin_first_out, uint64_t bins_cap,
                          uint64_t recs_cap);
+int pk_query_set_coords(pk_indexer *q, int on);
+int pk_query_bin_coords(pk_indexer *q, uint64_t *start_out, uint64_t *end_out, uint64_t bins_cap);
 
 /* ---- stats: replaces Header.update_stats (tools.py:246-263) on a host table of n bytes. */
 int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device);

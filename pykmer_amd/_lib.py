@@ -51,6 +51,8 @@ _SIGNATURES = {
     "pk_query_set_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "pk_query_bin_count": (ctypes.c_int, [ctypes.c_void_p, _u64p]),
     "pk_query_bin_results": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "pk_query_set_coords": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_query_bin_coords": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -297,10 +299,27 @@ class QueryIndexer(Indexer):
         _check(load().pk_query_bin_results(self._h, hits.ctypes.data, depth.ctypes.data, bin_first.ctypes.data, B, n_records))
         return hits[:B, :self.n_tables], depth[:B, :self.n_tables], bin_first
 
+    def set_coords(self, on: bool = True):
+        """pk_query_set_coords, after set_bins with W > 0 and before the first feed: also keep every row's base coordinates
+        (off by default; a reset clears the setting with the bins)."""
+        _check(load().pk_query_set_coords(self._h, 1 if on else 0))
+
+    def bin_coords(self):
+        """pk_query_bin_coords after finish(): (bin_start, bin_end), each (B,) uint64 in row order: the position of the first
+        base of the row's first window and one past the last base of its last."""
+        nb = ctypes.c_uint64(0)
+        _check(load().pk_query_bin_count(self._h, ctypes.byref(nb)))
+        B = int(nb.value)
+        start = np.zeros(max(B, 1), dtype=np.uint64)
+        end = np.zeros_like(start)
+        _check(load().pk_query_bin_coords(self._h, start.ctypes.data, end.ctypes.data, B))
+        return start[:B], end[:B]
+
     def timings(self) -> dict:
         t = np.zeros(10, dtype=np.float64)
         _check(load().pk_indexer_timings(self._h, t.ctypes.data))
-        return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]), "lookup_s": t[5]}
+        return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]), "lookup_s": t[5],
+                "coords_s": t[6]}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

@@ -1,0 +1,323 @@
+// kmer_coords.hip -- base coordinates of the rows of a binned query (pk_query_set_coords, DESIGN.md 4.10 "Coordinates").
+//
+// The packed stream the lookups read carries no positions, so the text of the feed is walked once more, from the exact
+// parser state the structure pass left for every 64-byte piece (lane_state behind chunk_l2_state, as k_squeeze takes it).
+// Positions are counted as DevRec.seq_len counts them (SeqWalker::step, kmer_walk.h): within a record every sequence
+// character gets the next position, valid base or not; blanks inside a sequence line get theirs once a sequence character
+// follows them on the same line; terminators, stripped blanks and header text get none.  A valid window is k consecutive
+// positions: the one whose last base has position e begins at e - k + 1.  For the window of ordinal o (kmer_query.hip) in
+// record r, with j = o - P[r] and row = Bf[r] + j / W:
+//     j % W == 0                             bin_start[row] = e - k + 1
+//     (j + 1) % W == 0 or j + 1 == n_valid   bin_end[row]   = e + 1      (n_valid as this feed's squeeze left it)
+// The second rule gives a record still open at the end of the feed a provisional end; a later feed that adds windows to
+// that row overwrites it, in stream order.  Every address is written by one lane per feed: plain stores, no atomics, and
+// the arrays are not zeroed between feeds.
+//
+// What a stretch of text does to the position is the pair (opens a record, positions since the last header or since the
+// stretch began); because the state a piece is entered with is exact the pair is concrete (it includes the pending blanks
+// carried in that turn out interior in the piece), and pairs compose associatively: b.hdr ? b : (a.hdr, a.cnt + b.cnt).
+//   k_coords_sum    one workgroup per chunk: the chunk's pair.  Clean pieces (plain sequence text) take their count from
+//                   the structure pass's PiecePack; the text is read only for chunks that hold other pieces
+//   k_coords_scan   one workgroup: the position at every chunk's first byte, from the position at the end of the feed
+//                   before (pos[in]); leaves the position at the end of this feed in pos[out].  The host makes `out` the
+//                   next feed's `in` only once the feed has settled, so that a repeated feed (flags[0] = 2) starts from
+//                   the same position.
+//   k_coords_write  one workgroup per chunk: positions, runs and records of its pieces again, the windows that end in each
+//                   piece prefix-summed behind slot_first[c] (their ordinals), and the two rules above.  Clean pieces by
+//                   masks (piece_scan and the pack's restart bits), the others by the rolled byte loop
+// Like the kernels of kmer_query.hip all three return at once, writing nothing, when flags[0] is raised.
+#include "pk_kernels.h"
+
+namespace pk {
+
+constexpr unsigned long long CP_HDR = 1ull << 63;        // a pair in one word: bit 63 = a record opens, the rest = positions
+
+__device__ __forceinline__ unsigned long long cp_compose(unsigned long long a, unsigned long long b) {   // a first, then b
+    return (b & CP_HDR) ? b : a + b;
+}
+
+// inclusive scan of pairs over a wave
+__device__ __forceinline__ unsigned long long cp_wave_incl(unsigned long long v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long o = __shfl_up(v, d, 64);
+        if (lane >= (uint32_t)d) v = cp_compose(o, v);
+    }
+    return v;
+}
+
+// Exclusive scan of pairs over the workgroup's NW waves (sh: NW words); total = all of them composed.  The pair before
+// lane 0 is the identity (0).
+template <int NW>
+__device__ __forceinline__ unsigned long long cp_block_excl(unsigned long long v, unsigned long long *sh, unsigned long long &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const unsigned long long inc = cp_wave_incl(v, lane);
+    __syncthreads();                                         // sh may still be read from an earlier call
+    if (lane == 63u) sh[w] = inc;
+    __syncthreads();
+    unsigned long long pre = 0ull, tot = 0ull;
+    for (uint32_t i = 0; i < (uint32_t)NW; i++) { if (i < w) pre = cp_compose(pre, sh[i]); tot = cp_compose(tot, sh[i]); }
+    total = tot;
+    const unsigned long long up = __shfl_up(inc, 1, 64);
+    return lane == 0u ? pre : cp_compose(pre, up);
+}
+
+// One piece walked byte by byte from its exact start state, as SeqWalker::step walks it (byte i <-> bit i).
+struct CoordPiece {
+    unsigned long long wend;      // a valid window of a live record ends at this byte (the kmer_acc rule)
+    unsigned long long posm;      // the byte holds a position: a sequence character, or a blank that turned out interior
+    unsigned long long hdrm;      // the byte opens a record
+    unsigned long long carried;   // pending blanks carried into the piece that turned out interior in it
+    __device__ __forceinline__ unsigned long long pair() const {
+        if (!hdrm) return carried + (unsigned long long)__popcll(posm);
+        const uint32_t last = 63u - (uint32_t)__builtin_clzll(hdrm);
+        return CP_HDR | (unsigned long long)__popcll(posm & ~((2ull << last) - 1ull));
+    }
+};
+
+__device__ __forceinline__ CoordPiece coords_walk(const uint8_t *mine, uint32_t nb, uint32_t ls_in, const L2 &st, uint32_t k) {
+    CoordPiece cp; cp.wend = 0; cp.posm = 0; cp.hdrm = 0; cp.carried = 0;
+    uint32_t ls = ls_in, run = l2_len(st);
+    bool live = st.rec != 0u;                                // text before the first header is dropped
+    unsigned long long pend_in = st.p_tail, pendm = 0;       // pending blanks: carried in / of this piece
+    for_each_byte_of(mine, nb, [&](uint32_t i, uint32_t c, bool act) {
+        const bool term = is_term(c), ws = is_ws(c), gt = c == '>';
+        const bool at_start = ls == LS_START, in_seq = ls == LS_SEQ;
+        const bool hdr_start = act && at_start && !ws && gt;
+        const bool seqchar = act && !ws && (in_seq || (at_start && !gt));
+        const bool t = act && term;
+        const unsigned long long bit = 1ull << i;
+        if (hdr_start) { live = true; run = 0u; cp.hdrm |= bit; }
+        if (seqchar && (pend_in | pendm)) {                  // blanks were interior: each holds a position and maps to None
+            cp.posm |= pendm; cp.carried += pend_in; run = 0u; pend_in = 0ull; pendm = 0ull;
+        }
+        if (t) { pend_in = 0ull; pendm = 0ull; }
+        else if (act && ws && in_seq) pendm |= bit;
+        ls = t ? (uint32_t)LS_START : hdr_start ? (uint32_t)LS_HEADER : seqchar ? (uint32_t)LS_SEQ : ls;
+        cp.posm |= seqchar ? bit : 0ull;
+        const bool valid = seqchar && base_code(c) < 4u;
+        run = valid ? (run < k ? run + 1u : run) : (seqchar ? 0u : run);
+        cp.wend |= (valid && run == k && live) ? bit : 0ull;
+    });
+    return cp;
+}
+
+// this lane's exact start state in chunk c
+__device__ __forceinline__ L2 coords_lane_state(const LaneState *__restrict__ lane_state, const L2 *__restrict__ chunk_l2_state, uint32_t c,
+                                                uint32_t km1, uint32_t &ls_in, bool &clean) {
+    const LaneState lst = lane_state[(uint64_t)c * WG + threadIdx.x];
+    ls_in = lane_state_ls(lst);
+    clean = !lane_state_dirty(lst) && !lane_state_header_piece(lst) && ls_in != LS_HEADER;   // the structure pass's definition (k_squeeze)
+    return l2_compose(chunk_l2_state[c], lane_state_l2(lst), km1);
+}
+
+__global__ __launch_bounds__(WG) void k_coords_sum(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
+                                                   const PiecePack *__restrict__ packs, const L2 *__restrict__ chunk_l2_state,
+                                                   const uint32_t *__restrict__ chunk_odd, uint32_t k, unsigned long long *__restrict__ chunk_pos,
+                                                   const uint32_t *__restrict__ flags) {
+    __shared__ __attribute__((aligned(16))) uint8_t text[WG * LDS_STRIDE];
+    __shared__ unsigned long long sh[WG / 64];
+    if (flags[0]) return;
+    const uint32_t c = blockIdx.x;
+    const uint64_t base = (uint64_t)c * CHUNK;
+    uint32_t ls_in;
+    bool clean;
+    const L2 st = coords_lane_state(lane_state, chunk_l2_state, c, k - 1u, ls_in, clean);
+    const uint32_t nb = piece_len(base, n_bytes);
+    // a clean piece (plain sequence text): the structure pass counted its sequence characters; blanks pending from the
+    // piece before are interior if a sequence character comes first (squeeze_apply).  Only a chunk that holds other
+    // pieces (uniform) is read, and only the waves that hold one walk (the walk costs a wave the same for one lane as for 64)
+    const uint32_t meta = packs[(uint64_t)c * WG + threadIdx.x].meta;
+    unsigned long long mine = nb ? ((meta >> 8) & 0xffu) + ((st.p_tail && ((meta >> 16) & 1u)) ? st.p_tail : 0ull) : 0ull;
+    if (chunk_odd[c] != 0u) {
+        stage_chunk(fasta, base, n_bytes, text);
+        __syncthreads();
+        if (__any(!clean)) {
+            const unsigned long long walked = coords_walk(text + threadIdx.x * LDS_STRIDE, nb, ls_in, st, k).pair();
+            if (!clean) mine = walked;
+        }
+    }
+    unsigned long long total;
+    cp_block_excl<WG / 64>(mine, sh, total);
+    if (threadIdx.x == 0) chunk_pos[c] = total;
+}
+
+// One workgroup, in place: chunk_pos[c] = the chunk's pair  ->  the position at the chunk's first byte.
+constexpr int CSNT = 1024;
+__global__ __launch_bounds__(CSNT) void k_coords_scan(unsigned long long *__restrict__ chunk_pos, uint32_t n_chunks,
+                                                      const unsigned long long *__restrict__ pos_in, unsigned long long *__restrict__ pos_out,
+                                                      const uint32_t *__restrict__ flags) {
+    __shared__ unsigned long long sh[CSNT / 64];
+    if (flags[0]) return;
+    unsigned long long run = *pos_in & ~CP_HDR;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += CSNT) {
+        const uint32_t c = c0 + threadIdx.x;
+        const unsigned long long v = c < n_chunks ? chunk_pos[c] : 0ull;
+        unsigned long long total;
+        const unsigned long long ex = cp_block_excl<CSNT / 64>(v, sh, total);
+        if (c < n_chunks) chunk_pos[c] = cp_compose(run, ex) & ~CP_HDR;
+        run = cp_compose(run, total) & ~CP_HDR;
+    }
+    if (threadIdx.x == 0) *pos_out = run;
+}
+
+// exclusive prefix of v over the workgroup (WG threads) and its total; sh: WG / 64 words
+__device__ __forceinline__ uint32_t coords_scan_u32(uint32_t v, uint32_t *sh, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
+    if (lane == 63u) sh[w] = inc;
+    __syncthreads();
+    uint32_t pre = 0;
+    total = 0;
+    for (uint32_t i = 0; i < WG / 64; i++) { if (i < w) pre += sh[i]; total += sh[i]; }
+    return pre + inc - v;
+}
+
+// the byte of the n-th set bit of x, n counted from 0 (n < popcount(x))
+__device__ __forceinline__ uint32_t nth_set(unsigned long long x, uint32_t n) {
+    uint32_t at = 0;
+#pragma unroll
+    for (uint32_t w = 32u; w; w >>= 1) {
+        const uint32_t below = (uint32_t)__popcll(x & ((1ull << w) - 1ull));
+        if (n >= below) { n -= below; x >>= w; at += w; }
+    }
+    return at;
+}
+
+// The valid windows that end at each of a clean piece's nv pushed-together bases (bit j: one ends at base j) from the pack's
+// restart bits and the run carried in: window_ends of kmer_pack.hip, which is local to the squeeze.
+__device__ __forceinline__ unsigned long long coords_window_ends(unsigned long long F, uint32_t nv, uint32_t run, uint32_t km1) {
+    if (run == 0u && nv) F |= 1ull;
+    const unsigned long long keep = nv >= 64u ? ~0ull : ((1ull << nv) - 1ull);
+    unsigned long long X = 0;
+    {
+        const unsigned long long y1 = F | (F << 1), y2 = y1 | (y1 << 2), y3 = y2 | (y2 << 4), y4 = y3 | (y3 << 8);
+        uint32_t off = 0;
+        if (km1 & 16u) { X |= y4; off = 16; }
+        if (km1 & 8u) { X |= y3 << off; off += 8; }
+        if (km1 & 4u) { X |= y2 << off; off += 4; }
+        if (km1 & 2u) { X |= y1 << off; off += 2; }
+        if (km1 & 1u) { X |= F << off; }
+    }
+    const uint32_t short_by = run >= km1 ? 0u : km1 - run;
+    const unsigned long long lead = short_by >= 64u ? ~0ull : ((1ull << short_by) - 1ull);
+    const unsigned long long below_first = F ? ((F & (0ull - F)) - 1ull) : ~0ull;
+    return ~X & ~(lead & below_first) & keep;
+}
+
+__global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
+                                                     const PiecePack *__restrict__ packs, const L2 *__restrict__ chunk_l2_state, uint32_t k,
+                                                     const unsigned long long *__restrict__ chunk_pos,
+                                                     const unsigned long long *__restrict__ slot_first, const unsigned long long *__restrict__ P,
+                                                     const unsigned long long *__restrict__ Bf, unsigned long long W,
+                                                     const DevRec *__restrict__ recs, unsigned long long *__restrict__ bin_start,
+                                                     unsigned long long *__restrict__ bin_end, unsigned long long rows_cap,
+                                                     const uint32_t *__restrict__ flags) {
+    __shared__ __attribute__((aligned(16))) uint8_t text[WG * LDS_STRIDE];
+    __shared__ unsigned long long sh[WG / 64];
+    __shared__ uint32_t sh32[WG / 64];
+    if (flags[0]) return;
+    const uint32_t c = blockIdx.x;
+    const uint64_t base = (uint64_t)c * CHUNK;
+    uint32_t ls_in;
+    bool clean;
+    const L2 st = coords_lane_state(lane_state, chunk_l2_state, c, k - 1u, ls_in, clean);
+    const unsigned long long restart = packs[(uint64_t)c * WG + threadIdx.x].restart;
+    stage_chunk(fasta, base, n_bytes, text);
+    __syncthreads();
+    const uint8_t *mine = text + threadIdx.x * LDS_STRIDE;
+    const uint32_t nb = piece_len(base, n_bytes);
+    // A clean piece (plain sequence text, the usual one) by masks: every byte that is no terminator holds a position, no
+    // record opens, blanks carried in resolve at byte 0 or not at all, and the windows follow from the pack's restart bits
+    // as in squeeze_apply -- over the piece's valid bases pushed together, so cp.wend counts BASES there (valid: which bytes
+    // they are).  The other pieces byte by byte, in the waves that hold one.
+    PieceMasks pm;
+    uint32_t cw[4];
+    piece_scan(mine, nb, pm, cw);
+    const unsigned long long valid = pm.valid;
+    CoordPiece cp;
+    cp.posm = ~pm.term; cp.hdrm = 0ull;
+    cp.carried = (st.p_tail && (cp.posm & 1ull)) ? st.p_tail : 0ull;
+    cp.wend = st.rec != 0u ? coords_window_ends(restart, (uint32_t)__popcll(valid), cp.carried ? 0u : l2_len(st), k - 1u) : 0ull;
+    if (__any(!clean)) {
+        const CoordPiece walked = coords_walk(mine, nb, ls_in, st, k);
+        if (!clean) cp = walked;
+    }
+    // the byte of the n-th window of the mask w of this piece
+    const auto byte_of = [&](unsigned long long w, uint32_t n) -> uint32_t {
+        const uint32_t at = nth_set(w, n);
+        return clean ? nth_set(valid, at) : at;
+    };
+    uint32_t n_win;
+    const uint32_t off = coords_scan_u32((uint32_t)__popcll(cp.wend), sh32, n_win);
+    if (n_win == 0u) return;                                 // uniform: no window ends in the chunk
+    unsigned long long unused;
+    const unsigned long long ex = cp_block_excl<WG / 64>(cp.pair(), sh, unused);
+    if (!cp.wend) return;
+    // positions counted in the record open at the piece's first byte, before that byte (pending blanks not among them)
+    const unsigned long long pos0 = cp_compose(chunk_pos[c], ex) & ~CP_HDR;
+    // the position of the sequence character at byte i
+    const auto pos_of = [&](uint32_t i) -> unsigned long long {
+        const unsigned long long below = (1ull << i) - 1ull, h = cp.hdrm & below;
+        if (!h) return pos0 + cp.carried + (unsigned long long)__popcll(cp.posm & below);   // carried blanks resolve at the piece's first sequence character
+        const uint32_t last = 63u - (uint32_t)__builtin_clzll(h);
+        return (unsigned long long)__popcll(cp.posm & below & ~((2ull << last) - 1ull));
+    };
+    // record by record (a header ends the one before): the windows of ordinals [o, o + nw) end at the bytes `w`
+    unsigned long long o = slot_first[c] + off, left = cp.wend, hdrs = cp.hdrm;
+    unsigned long long rec = st.rec;                         // 1-based
+    for (;;) {
+        const unsigned long long seg = hdrs ? ((hdrs & (0ull - hdrs)) - 1ull) : ~0ull;   // the bytes below the next header
+        const unsigned long long w = left & seg;
+        const uint32_t nw = (uint32_t)__popcll(w);
+        if (nw) {                                            // rec >= 1: a window lies in a record
+            const unsigned long long r = rec - 1ull, j0 = o - P[r], row0 = Bf[r], m = recs[r].n_valid;
+            const unsigned long long q = j0 / W, rem = j0 - q * W;
+            // windows that begin a bin: j % W == 0
+            {
+                const unsigned long long d = rem ? W - rem : 0ull;
+                unsigned long long row = row0 + q + (rem ? 1ull : 0ull);
+                for (unsigned long long idx = d; idx < nw; row++) {
+                    if (row < rows_cap) bin_start[row] = pos_of(byte_of(w, (uint32_t)idx)) + 1ull - k;
+                    if (W >= nw - idx) break;
+                    idx += W;
+                }
+            }
+            // windows that end a bin: (j + 1) % W == 0, and the record's last window so far
+            {
+                unsigned long long row = row0 + q;
+                for (unsigned long long idx = W - 1ull - rem; idx < nw; row++) {
+                    if (row < rows_cap) bin_end[row] = pos_of(byte_of(w, (uint32_t)idx)) + 1ull;
+                    if (W >= nw - idx) break;
+                    idx += W;
+                }
+                if (m > j0 && m - j0 <= nw) {
+                    const unsigned long long last_row = row0 + (m - 1ull) / W;
+                    if (last_row < rows_cap) bin_end[last_row] = pos_of(byte_of(w, (uint32_t)(m - j0 - 1ull))) + 1ull;
+                }
+            }
+        }
+        if (!hdrs) break;
+        o += nw;
+        left &= ~seg;
+        hdrs &= hdrs - 1ull;
+        rec++;
+    }
+}
+
+// ------------------------------------------------------------------ host side -------------------
+void launch_query_coords(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const uint8_t *fasta, uint64_t n, const LaneState *lane_state,
+                         const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, const DevRec *recs, const unsigned long long *P,
+                         const unsigned long long *Bf, uint64_t bin_windows, unsigned long long *chunk_pos, const unsigned long long *pos_in,
+                         unsigned long long *pos_out, unsigned long long *bin_start, unsigned long long *bin_end, uint64_t rows_cap, hipStream_t s) {
+    hipLaunchKernelGGL(k_coords_sum, dim3(pl.n_chunks), dim3(WG), 0, s, fasta, n, lane_state, packs, st2, chunk_odd, pl.k, chunk_pos,
+                       (const uint32_t *)b.flags);
+    hipLaunchKernelGGL(k_coords_scan, dim3(1), dim3(CSNT), 0, s, chunk_pos, pl.n_chunks, pos_in, pos_out, (const uint32_t *)b.flags);
+    hipLaunchKernelGGL(k_coords_write, dim3(pl.n_chunks), dim3(WG), 0, s, fasta, n, lane_state, packs, st2, pl.k, (const unsigned long long *)chunk_pos,
+                       (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, recs, bin_start, bin_end,
+                       (unsigned long long)rows_cap, (const uint32_t *)b.flags);
+}
+
+}  // namespace pk

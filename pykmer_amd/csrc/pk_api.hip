@@ -1,6 +1,6 @@
 // pk_api.hip -- host side of the C-ABI declared in include/pykmer_hip.h.
 // Owns device memory, streams and events (every allocation of the library is made here) and sequences the kernels of the
-// indexer (kmer_count.hip, kmer_pack.hip, kmer_fuse.hip, kmer_part.hip, fastq.hip), of the query path (kmer_query.hip) and of
+// indexer (kmer_count.hip, kmer_pack.hip, kmer_fuse.hip, kmer_part.hip, fastq.hip), of the query path (kmer_query.hip, kmer_coords.hip) and of
 // the merger (gram_scan.hip, gram_spectrum.hip, gram_occ.hip).  No kernel is defined in this file.
 #include <hip/hip_runtime.h>
 
@@ -279,12 +279,13 @@ struct Events {
     hipEvent_t bucket_end = nullptr;
     hipEvent_t final_begin = nullptr, final_end = nullptr;         // pk_indexer_finish
     hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // query mode: the kernels of kmer_query.hip
+    hipEvent_t coords_begin = nullptr, coords_end = nullptr;       // query mode with coordinates: the kernels of kmer_coords.hip
     Events() = default;
     Events(const Events &) = delete;
     ~Events() { for (hipEvent_t *e : all()) if (*e) hipEventDestroy(*e); }
-    std::array<hipEvent_t *, 14> all() {
+    std::array<hipEvent_t *, 16> all() {
         return {&reset_begin, &reset_end, &scan_begin, &scan_end, &squeeze_begin, &squeeze_end, &sort_begin, &sort_end, &part_end, &bucket_end,
-                &final_begin, &final_end, &lookup_begin, &lookup_end};
+                &final_begin, &final_end, &lookup_begin, &lookup_end, &coords_begin, &coords_end};
     }
 };
 }  // namespace
@@ -348,6 +349,13 @@ struct pk_indexer {
     uint64_t q_bin = 0;
     DevBuf<unsigned long long> q_Bf;
     uint64_t q_n_bins = 0;                                  // after finish
+    // coordinates (pk_query_set_coords): per row the position of the first base of its first window and one past the last
+    // base of its last, sized and grown with q_hits.  q_pos: the position in the open record at the start of the next feed
+    // (word q_pos_in) and where the feed's kernels leave the one at its end (the other word); q_cpos: one word per chunk.
+    bool q_coords = false;
+    DevBuf<unsigned long long> q_bin_start, q_bin_end, q_pos, q_cpos;
+    int q_pos_in = 0;
+    double t_coords = 0;
     uint64_t query_rows(uint64_t cap, uint64_t bytes) const { return q_bin ? bytes / q_bin + cap + 1 : cap; }
 
     uint64_t recs_cap() const { return recs.bytes / sizeof(DevRec); }
@@ -368,10 +376,11 @@ static int ix_reset(pk_indexer *ix) {
     HIPCHK(hipMemcpyAsync(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
     ix->tail_on_host = false;
     if (ix->recs.p) HIPCHK(hipMemsetAsync(ix->recs.p, 0, ix->recs.bytes, ix->stream));
-    for (DevBuf<unsigned long long> *b : {&ix->q_P, &ix->q_Bf, &ix->q_hits, &ix->q_depth})
+    for (DevBuf<unsigned long long> *b : {&ix->q_P, &ix->q_Bf, &ix->q_hits, &ix->q_depth, &ix->q_bin_start, &ix->q_bin_end, &ix->q_pos})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
     ix->q_windows = ix->q_p_done = 0;
     ix->q_bin = ix->q_n_bins = 0;
+    ix->q_coords = false; ix->q_pos_in = 0; ix->t_coords = 0;
     HIPCHK(hipEventRecord(ix->ev.reset_end, ix->stream));
     ix->zero_timed = false;
     ix->t_zero = 0;
@@ -508,6 +517,18 @@ static int ensure_bin_rows(pk_indexer *ix, uint64_t bytes) {
             const std::string why = g_err;
             return fail(rc, "bins of %llu windows need two accumulators of %zu bytes (%llu rows, %zu tables); take larger bins: %s",
                         (unsigned long long)ix->q_bin, want, (unsigned long long)rows, ix->q_tables.size(), why.c_str());
+        }
+    }
+    if (!ix->q_coords) return PK_OK;
+    for (DevBuf<unsigned long long> *b : {&ix->q_bin_start, &ix->q_bin_end}) {
+        if (rows * sizeof(unsigned long long) <= b->bytes) continue;
+        const size_t want = std::max<size_t>(rows * sizeof(unsigned long long), b->bytes + b->bytes / 2);
+        const int rc = b->grow_keep(want, ix->stream);
+        if (rc) {
+            (void)hipGetLastError();
+            const std::string why = g_err;
+            return fail(rc, "bins of %llu windows need two coordinate arrays of %zu bytes (%llu rows); take larger bins: %s",
+                        (unsigned long long)ix->q_bin, want, (unsigned long long)rows, why.c_str());
         }
     }
     return PK_OK;
@@ -658,6 +679,7 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
     const Events &ev = ix->ev;
     const uint32_t N = (uint32_t)ix->q_tables.size();
     if ((rc = ensure_bin_rows(ix, ix->bytes_fed + n_bytes))) return rc;
+    if (ix->q_coords && (rc = ix->q_cpos.reserve((size_t)n_chunks * sizeof(unsigned long long)))) return rc;
     HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
     launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
     launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
@@ -678,6 +700,15 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
             launch_query_lookup(pl, pb, qb, ix->c_l2s.p, ix->q_P.p, ix->q_Bf.p, ix->q_bin, carry, ix->q_tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
                                 (uint32_t)ix->q_min, (uint32_t)ix->q_max, ix->q_hits.p, ix->q_depth.p, ix->stream);
         HIPCHK(hipEventRecord(ev.lookup_end, ix->stream));
+        if (ix->q_coords) {
+            // behind launch_query_scan (slot_first, P, Bf) and on the rows ensure_bin_rows sized; a repeated attempt starts
+            // from the same q_pos word: the words change roles only once the feed has settled
+            HIPCHK(hipEventRecord(ev.coords_begin, ix->stream));
+            launch_query_coords(pl, pb, qb, f, n_bytes, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, ix->recs.p, ix->q_P.p, ix->q_Bf.p,
+                                ix->q_bin, ix->q_cpos.p, ix->q_pos.p + ix->q_pos_in, ix->q_pos.p + (ix->q_pos_in ^ 1), ix->q_bin_start.p, ix->q_bin_end.p,
+                                ix->q_bin_start.bytes / sizeof(unsigned long long), ix->stream);
+            HIPCHK(hipEventRecord(ev.coords_end, ix->stream));
+        }
         HIPCHK(hipGetLastError());
         volatile uint32_t *got = ix->pin->flags;
         HIPCHK(hipMemcpyAsync(ix->pin->flags, pb.flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
@@ -701,6 +732,12 @@ static int query_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) 
     HIPCHK(hipEventElapsedTime(&squeeze_ms, ev.squeeze_begin, ev.squeeze_end));
     HIPCHK(hipEventElapsedTime(&lookup, ev.lookup_begin, ev.lookup_end));
     ix->t_scan += scan * 1e-3; ix->t_squeeze += squeeze_ms * 1e-3; ix->t_part += lookup * 1e-3;
+    if (ix->q_coords) {
+        float coords = 0;
+        HIPCHK(hipEventElapsedTime(&coords, ev.coords_begin, ev.coords_end));
+        ix->t_coords += coords * 1e-3;
+        ix->q_pos_in ^= 1;                                   // the position behind this feed is the next feed's start
+    }
     ix->feeds++;
     ix->bytes_fed += n_bytes;
     return PK_OK;
@@ -734,9 +771,23 @@ extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
     if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the bins are set before the first feed (reset the indexer first)");
     HIPCHK(hipSetDevice(ix->device));
     ix->q_bin = bin_windows;
+    ix->q_coords = false;                                    // pk_query_set_coords comes after the bins
     if (!bin_windows) return PK_OK;
     // Bf beside P; a reset zeroed what was there, a new array is zeroed here
     const int rc = ix->q_Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
+    return rc ? rc : ensure_bin_rows(ix, 0);
+}
+
+extern "C" int pk_query_set_coords(pk_indexer *ix, int on) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (!ix->q_bin) return fail(PK_ERR_STATE, "pk_query_set_bins with bins of at least one window comes before pk_query_set_coords");
+    if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the coordinates are set before the first feed (reset the indexer first)");
+    HIPCHK(hipSetDevice(ix->device));
+    ix->q_coords = on != 0;
+    if (!ix->q_coords) return PK_OK;
+    // the two position words; a reset zeroed what was there, a new array is zeroed here
+    const int rc = ix->q_pos.grow_keep(2 * sizeof(unsigned long long), ix->stream);
     return rc ? rc : ensure_bin_rows(ix, 0);
 }
 
@@ -779,6 +830,22 @@ extern "C" int pk_query_bin_results(pk_indexer *ix, uint64_t *hits_out, uint64_t
     const size_t n = ix->q_n_bins * ix->q_tables.size() * sizeof(uint64_t);
     HIPCHK(hipMemcpy(hits_out, ix->q_hits.p, n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(depth_out, ix->q_depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_coords(pk_indexer *ix, uint64_t *start_out, uint64_t *end_out, uint64_t bins_cap) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->query) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (!ix->q_coords) return fail(PK_ERR_STATE, "the indexer keeps no coordinates (pk_query_set_coords)");
+    if (!ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
+    if (ix->q_n_bins > bins_cap)
+        return fail(PK_ERR_RECS_CAP, "%llu bins, capacity %llu", (unsigned long long)ix->q_n_bins, (unsigned long long)bins_cap);
+    if (ix->q_n_bins == 0) return PK_OK;
+    if (!start_out || !end_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const size_t n = ix->q_n_bins * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(start_out, ix->q_bin_start.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(end_out, ix->q_bin_end.p, n, hipMemcpyDeviceToHost));
     return PK_OK;
 }
 
@@ -1081,7 +1148,7 @@ extern "C" int pk_indexer_timings(pk_indexer *ix, double out[10]) {
     if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
     for (int i = 0; i < 10; i++) out[i] = 0;
     out[0] = ix->t_scan; out[1] = ix->t_squeeze; out[2] = ix->t_final; out[3] = ix->t_zero; out[4] = (double)ix->feeds;
-    out[5] = ix->t_part; out[6] = ix->t_bucket; out[7] = ix->t_sort; out[8] = (double)ix->relayouts; out[9] = (double)ix->recounted;
+    out[5] = ix->t_part; out[6] = ix->query ? ix->t_coords : ix->t_bucket; out[7] = ix->t_sort; out[8] = (double)ix->relayouts; out[9] = (double)ix->recounted;
     return PK_OK;
 }
 

@@ -122,6 +122,15 @@ void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBu
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
                          unsigned long long *hits, unsigned long long *depth, hipStream_t s);
 
+// kmer_coords.hip -- base coordinates of a binned query's rows (DESIGN.md 4.10 "Coordinates"), behind launch_query_scan of the
+// same feed (slot_first, P, Bf) and its squeeze (recs[].n_valid).  chunk_pos: n_chunks words of scratch.  pos_in: the position
+// in the open record at the feed's first byte; pos_out receives the one behind its last.  bin_start / bin_end: rows_cap words
+// each; row Bf[r] + j / W takes the first base of its first window and one past the last base of its last.
+void launch_query_coords(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const uint8_t *fasta, uint64_t n, const LaneState *lane_state,
+                         const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, const DevRec *recs, const unsigned long long *P,
+                         const unsigned long long *Bf, uint64_t bin_windows, unsigned long long *chunk_pos, const unsigned long long *pos_in,
+                         unsigned long long *pos_out, unsigned long long *bin_start, unsigned long long *bin_end, uint64_t rows_cap, hipStream_t s);
+
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it
     uint64_t line;           // line terminators seen (the role of the open line is line & 3)

@@ -13,6 +13,10 @@ independent, so the results concatenate.  One device (PK_DEVICE).
 With `bin_windows` = W the same tallies are also kept along each record, in bins of W valid windows (pk_query_set_bins):
 record r with m valid windows j = 0 .. m-1 has ceil(m / W) bins, bin b holding the windows b*W <= j < min((b+1)*W, m); the
 rows are ordered by record, then by bin, and bin_first[r] is record r's first row (bin_first[R] = the number of rows).
+
+With `coords` every row also gets its place on the record in bases (pk_query_set_coords): bin_start = the position of the
+first base of the row's first window, bin_end = one past the last base of its last window, positions counted within the
+record as seq_len counts them (0-based; every sequence character, valid or not, and the blanks inside a sequence line).
 """
 import argparse
 import json
@@ -129,16 +133,20 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
 
 
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
-              bin_windows: int = None) -> dict:
+              bin_windows: int = None, coords: bool = False) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
     same query only add columns).  `bin_windows`: tally per bin (bin_hits, bin_depth, bin_first); the per-record arrays
-    are then the sums of each record's rows."""
+    are then the sums of each record's rows.  `coords`: also bin_start, bin_end -- on the `first` stream only, they do
+    not depend on the tables."""
+    coords = bool(coords) and first
     src = _Input(query_file, keep=first, quiet=not first)
     binned = {}
     with _lib.QueryIndexer(kmer_len, device=device, fmt=src.fmt) as q:
         q.set_tables(ptrs, min_count, max_count)
         if bin_windows is not None:
             q.set_bins(bin_windows)
+            if coords:
+                q.set_coords(True)
         for piece in src.pieces():
             q.feed(piece)
         fin = q.finish()
@@ -147,6 +155,9 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
             bin_hits, bin_depth, bin_first = q.bin_results(fin["n_records"])
             hits, depth = record_sums(bin_hits, bin_first), record_sums(bin_depth, bin_first)
             binned = {"bin_hits": bin_hits.copy(), "bin_depth": bin_depth.copy(), "bin_first": bin_first}
+            if coords:
+                bin_start, bin_end = q.bin_coords()
+                binned.update(bin_start=bin_start.copy(), bin_end=bin_end.copy())
         else:
             hits, depth = q.results(fin["n_records"])
         timings = q.timings()
@@ -158,7 +169,7 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
 
 
 def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
-                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None) -> dict:
+                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False) -> dict:
     """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
     merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
     kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
@@ -170,10 +181,18 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
 
     `bin_windows` = W >= 1 adds bin_hits, bin_depth (B, N) and bin_first (R + 1,), uint64: the same tallies per bin of W
     valid windows along each record (the module's docstring); hits / depth are then the sums over each record's rows, from
-    the same single lookup.  `run` receives bin_windows by keyword, and only when it is set."""
+    the same single lookup.  `run` receives bin_windows by keyword, and only when it is set.
+
+    `coords` = True (with `bin_windows`; ValueError without) adds bin_start and bin_end (B,), uint64: the base positions
+    within its record of the first base of every row's first window and one past the last base of its last (the module's
+    docstring).  They are computed while the first table group is streamed.  `run` receives coords like bin_windows."""
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
+    if coords and bin_windows is None:
+        raise ValueError("coordinates are those of bins: coords needs bin_windows (--coords needs --bin W)")
     extra = {} if bin_windows is None else {"bin_windows": bin_windows}
+    if coords:
+        extra["coords"] = True
     tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
     kmer_len = validate(tables, min_count, max_count)
     stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
@@ -184,7 +203,7 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         budget = hbm_budget or int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or \
             max(0, int(_lib.mem_info(device)[0] * 0.8) - WORKSPACE_RESERVE)
         groups = table_groups(len(tables), 4 ** kmer_len, budget)
-    result, lookup_s = None, 0.0
+    result, lookup_s, coords_s = None, 0.0, 0.0
     for g, (lo, hi) in enumerate(groups):
         staged = stage(tables[lo:hi], device)
         _mark(f"tables {lo}..{hi - 1} staged")
@@ -194,6 +213,9 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
             staged.free()
         _mark(f"query streamed against tables {lo}..{hi - 1}")
         lookup_s += float(part.get("timings", {}).get("lookup_s", 0.0))
+        if coords and g == 0:
+            coords_s = float(part.get("timings", {}).get("coords_s", 0.0))
+            _mark(f"coordinate kernels: {coords_s:.6f} s of HIP-event time (lookup kernels: {lookup_s:.6f} s)")
         if result is None:
             result = part
         else:
@@ -207,6 +229,9 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
                 result["bin_depth"] = np.concatenate([result["bin_depth"], part["bin_depth"]], axis=1)
     if bin_windows is not None:
         result["bin_windows"] = bin_windows
+    if coords:
+        assert result["bin_start"].shape == result["bin_end"].shape == (int(result["bin_first"][-1]),)
+        result["coords_s"] = coords_s
     result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
     return result
 
@@ -251,7 +276,9 @@ def kmb_paths(project_name: str) -> Tuple[Path, Path, Path]:
 
 
 def write_kmb(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
-    """`<project>.kmb` (np.savez_compressed), `.kmb.json` and `.kmb.tsv`: the binned rows, each file through `.tmp` + rename."""
+    """`<project>.kmb` (np.savez_compressed), `.kmb.json` and `.kmb.tsv`: the binned rows, each file through `.tmp` + rename.
+    A result with bin_start / bin_end (coords) adds them to the `.kmb`, `"coords": true` to the json and the columns
+    `start` and `end` to the tsv; without them the files hold none of the three."""
     kmb, meta, tsv = kmb_paths(project_name)
     W = int(result["bin_windows"])
     hits = np.ascontiguousarray(result["bin_hits"], dtype=np.uint64)
@@ -263,9 +290,16 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
     B = int(bin_first[-1])
     assert hits.shape == depth.shape == (B, len(columns)) and bin_first.shape == (len(names) + 1,)
     assert n_valid.shape == seq_len.shape == (len(names),)
+    coords = {}
+    if "bin_start" in result:
+        coords = {"bin_start": np.ascontiguousarray(result["bin_start"], dtype=np.uint64),
+                  "bin_end": np.ascontiguousarray(result["bin_end"], dtype=np.uint64)}
+        assert coords["bin_start"].shape == coords["bin_end"].shape == (B,)
     output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
               "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data,
               "bin_windows": W, "n_bins": B}
+    if coords:
+        output["coords"] = True
     print(f"saving {meta}")
     tmp = Path(f"{meta}.tmp")
     with tmp.open(mode="wt") as fhd:
@@ -274,27 +308,32 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
     print(f"saving {tsv}")
     tmp = Path(f"{tsv}.tmp")
     with tmp.open(mode="wt") as fhd:
-        fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + [str(c) for c in columns]) + "\n")
+        fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) + [str(c) for c in columns]) + "\n")
         for r, name in enumerate(names):
             m = int(n_valid[r])
             for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
-                row = hits[int(bin_first[r]) + b]
-                fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + [str(int(v)) for v in row]) + "\n")
+                at = int(bin_first[r]) + b
+                span = [str(int(coords["bin_start"][at])), str(int(coords["bin_end"][at]))] if coords else []
+                fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + span + [str(int(v)) for v in hits[at]]) + "\n")
     tmp.rename(tsv)
     print(f"saving {kmb}")
     tmp = Path(f"{kmb}.tmp")
     with tmp.open(mode="wb") as fhd:
         np.savez_compressed(fhd, hits=hits, depth=depth, bin_first=bin_first, n_valid=n_valid, seq_len=seq_len, bin_windows=np.uint64(W),
                             kmer_len=np.int64(result["kmer_len"]), min_count=np.int64(result["min_count"]),
-                            max_count=np.int64(result["max_count"]))
+                            max_count=np.int64(result["max_count"]), **coords)
     tmp.rename(kmb)
 
 
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
-          threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None) -> dict:
-    """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result."""
+          threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None, coords: bool = False) -> dict:
+    """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result.
+    `coords` (with `bin_windows`) adds the rows' base coordinates to the `.kmb` files."""
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
+    if coords and bin_windows is None:
+        raise ValueError("--coords gives the coordinates of bins: it needs --bin W")
+    extra = {"coords": True} if coords else {}
     for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
@@ -317,7 +356,7 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
     else:
         try:
             result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
-                                   bin_windows=bin_windows)
+                                   bin_windows=bin_windows, **extra)
         except _lib.PkError as exc:
             if exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
                 raise
@@ -342,6 +381,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--threads", type=int, default=DEFAULT_THREADS, help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
     parser.add_argument("--bin", type=int, default=None, metavar="W", dest="bin_windows",
                         help="Also write <P>.kmb[.json|.tsv]: the hits along each record in bins of W valid windows [off]")
+    parser.add_argument("--coords", action="store_true",
+                        help="With --bin: add every bin's base coordinates within its record (start, end) to the .kmb files [off]")
     return parser
 
 
@@ -349,7 +390,8 @@ def main(argv: List[str] = None) -> None:
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     try:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
-                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows)
+                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows,
+                       **({"coords": True} if args.coords else {}))
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)

@@ -11,12 +11,15 @@ HIP-event times of the structure pass, the squeeze and the lookup kernels (pk_in
     python tools/query_bench.py --once SHAPE   warm-up + one run of one shape (what the profiled child runs)
     --bin W        the same inputs tallied in bins of W valid windows (pk_query_set_bins); the rows are fetched with
                    bin_results instead of results
+    --coords       with --bin: the rows' base coordinates too (pk_query_set_coords, kmer_coords.hip), fetched with
+                   bin_coords; `coords_s_runs` holds the coordinate kernels' HIP-event time of every timed run
     --runs R       timed runs per shape [5]
     --no-trace     skip the rocprofv3 run
     PK_QUERY_BENCH_BP / PK_QUERY_BENCH_TABLE_BP scale the genome and the table genomes down for a rehearsal.
 
 Writes profiles/query_k15_n13.json (or out.json).  `lookup_s_runs` holds the lookup kernels' HIP-event time of every timed
-run; profiles/query_bins_k15_n13.json was put together from such runs of two builds."""
+run, `front_s_runs` that of the structure pass and the squeeze together; profiles/query_bins_k15_n13.json and
+profiles/query_coords_k15_n13.json were put together from such runs of two builds."""
 import csv
 import glob
 import json
@@ -57,36 +60,48 @@ def shapes(genome_bp: int):
     yield "reads", lambda: synth.generate(34, genome_bp // 2, max(1, genome_bp // 2000))
 
 
-def run_shape(make, ptrs, runs: int, bin_windows: int = None):
+def run_shape(make, ptrs, runs: int, bin_windows: int = None, coords: bool = False):
     fa, bp = make()
     text = _lib.DeviceBuffer(len(fa) + 64)
     text.upload(np.asarray(fa))
     try:
         with _lib.QueryIndexer(K) as q:
-            times, lookups = [], []
+            times, lookups, fronts, coord_times = [], [], [], []
             for i in range(runs + 1):                                     # the first run warms up: allocations, code load
                 q.reset()
                 q.set_tables(ptrs, 1, 255)
                 if bin_windows is not None:
                     q.set_bins(bin_windows)
+                    if coords:
+                        q.set_coords(True)
                 t0 = time.perf_counter()
                 q.feed_device(text.ptr, len(fa))
                 fin = q.finish()
                 if bin_windows is not None:
                     hits, depth, bin_first = q.bin_results(fin["n_records"])
+                    if coords:
+                        bin_start, bin_end = q.bin_coords()
                 else:
                     hits, depth = q.results(fin["n_records"])
                 if i:
                     times.append(time.perf_counter() - t0)
-                    lookups.append(float(q.timings()["lookup_s"]))         # a reset zeroes the library's timers
+                    t = q.timings()                                        # a reset zeroes the library's timers
+                    lookups.append(float(t["lookup_s"]))
+                    fronts.append(float(t["scan_s"] + t["squeeze_s"]))
+                    coord_times.append(float(t.get("coords_s", 0.0)))
             t = q.timings()
         med = statistics.median(times) if times else float("nan")
         front = t["scan_s"] + t["squeeze_s"]
         return {"bp": int(bp), "text_bytes": len(fa), "records": fin["n_records"], "windows": fin["num_kmers"], "tables": len(ptrs),
-                "bin_windows": bin_windows, "rows": int(hits.shape[0]), "runs": times, "lookup_s_runs": lookups,
+                "bin_windows": bin_windows, "coords": coords, "rows": int(hits.shape[0]), "runs": times, "lookup_s_runs": lookups,
+                "front_s_runs": fronts, "coords_s_runs": coord_times,
+                "coords_s_median": statistics.median(coord_times) if coord_times else float("nan"),
+                "coords_span_of_row_0": [int(bin_start[0]), int(bin_end[0])] if coords and len(bin_start) else None,
                 "lookup_s_median": statistics.median(lookups) if lookups else float("nan"), "median_s": med, "best_s": min(times) if times else med, "bp_per_s": bp / med,
                 "lookups_per_s": fin["num_kmers"] * len(ptrs) / med,
-                "device_s": {"structure_pass": t["scan_s"], "squeeze": t["squeeze_s"], "lookup_kernels": t["lookup_s"]},
+                "device_s": {"structure_pass": t["scan_s"], "squeeze": t["squeeze_s"], "lookup_kernels": t["lookup_s"],
+                             "coords_kernels": float(t.get("coords_s", 0.0))},
+                "coords_over_structure_plus_squeeze": float(t.get("coords_s", 0.0)) / front,
                 "lookup_share_of_device_time": t["lookup_s"] / (front + t["lookup_s"]),
                 "lookup_over_structure_plus_squeeze": t["lookup_s"] / front,
                 "lookups_per_s_kernels_only": fin["num_kmers"] * len(ptrs) / t["lookup_s"],
@@ -116,27 +131,30 @@ def main():
         elif not a.startswith("--"):
             args.append(a)
     bin_windows, runs = opts["--bin"], opts["--runs"]
+    coords = "--coords" in sys.argv
+    if coords and bin_windows is None:
+        sys.exit("error: --coords needs --bin W")
     genome_bp = int(os.environ.get("PK_QUERY_BENCH_BP", 800_000_000))
     table_bp = int(os.environ.get("PK_QUERY_BENCH_TABLE_BP", 40_000_000))
     bufs = stage_tables(table_bp)
     ptrs = [b.ptr for b in bufs]
     if "--once" in sys.argv:
-        run_shape(dict(shapes(genome_bp))[args[0]], ptrs, 1, bin_windows)
+        run_shape(dict(shapes(genome_bp))[args[0]], ptrs, 1, bin_windows, coords)
         return
     out = {"k": K, "n_tables": N, "table_genome_bp": table_bp, "layout": "one 4^k-byte table per sample (not interleaved)",
-           "bin_windows": bin_windows,
+           "bin_windows": bin_windows, "coords": coords,
            "method": f"1 warm-up + median of {runs} runs of reset/feed_device/finish/results; device_s from HIP events (pk_indexer_timings)"}
     for name, make in shapes(genome_bp):
-        out[name] = run_shape(make, ptrs, runs, bin_windows)
+        out[name] = run_shape(make, ptrs, runs, bin_windows, coords)
         print(name, json.dumps(out[name]), flush=True)
     for b in bufs:
         b.free()
     if "--no-trace" not in sys.argv:
-        once = [sys.executable, os.path.abspath(__file__), "--once", "genome"] + (["--bin", str(bin_windows)] if bin_windows is not None else [])
+        once = [sys.executable, os.path.abspath(__file__), "--once", "genome"] + (["--bin", str(bin_windows)] if bin_windows is not None else []) + (["--coords"] if coords else [])
         rows = kernel_stats(once, os.path.join(ROOT, "profiles", "query_genome_kernel_stats.csv"))
         out["genome_kernel_trace_ms_per_call"] = {r["Name"].split("(")[0][:60]: round(float(r["AverageNs"]) / 1e6, 4) for r in rows
-                                                   if "k_query" in r["Name"] or "k_squeeze" in r["Name"]}
-    path = args[0] if args else os.path.join(ROOT, "profiles", "query_k15_n13.json")
+                                                   if "k_query" in r["Name"] or "k_squeeze" in r["Name"] or "k_coords" in r["Name"]}
+    path = args[0] if args else os.path.join(ROOT, "profiles", "query_coords_k15_n13.json" if coords else "query_k15_n13.json")
     with open(path + ".tmp", "w") as fh:
         json.dump(out, fh, indent=1)
     os.replace(path + ".tmp", path)
