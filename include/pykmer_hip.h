@@ -293,9 +293,16 @@ int pk_bgzf_deflate(const uint8_t *src, uint64_t n_bytes, int level, uint32_t bl
  * 2 k_bucket_count_half_lean, 3 k_scatter2), each at the dynamic LDS size it is launched with; negative = HIP error.
  * pk_diag_plan: the partition plan of ONE feed of n_bytes (0 = the largest piece a feed is cut into) at kmer_len k:
  * out = { largest piece, level-1 record capacity, final-bucket record capacity, level-1 buckets, level-2 digits,
- * address bits per final bucket, 16 KiB chunks, 1 if every record position fits 32 bits }. */
+ * address bits per final bucket, 16 KiB chunks, 1 if every record position fits 32 bits }.
+ * pk_diag_plan_slice: the same feed into ONE of n_slices address slices (what pk_indexer_create_slice accepts, refused
+ * alike), with every choice the launchers make from it; touches no GPU:
+ * out = { addr_bits, fb_bits, b1, b2, sample_stride (16: sampled layout, 1: exact), n_tally (buckets tallied while
+ * sampling), sample2, n_chunks, walk-sort variant (0 narrow, 1 narrow sliced, 2 k15, 3 k17, 4 wide sliced, 5 deep),
+ * bucket-count kernel (0 whole, 1 bytes, 2 half), bucket split, B1, B2, level-1 record capacity, final-bucket record
+ * capacity, 1 if every record position fits 32 bits }. */
 int pk_diag_occupancy(int which);
 int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]);
+int pk_diag_plan_slice(int k, int n_slices, uint64_t n_bytes, uint64_t out[16]);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,7 @@ _SIGNATURES = {
                                         ctypes.c_void_p, _u64p, ctypes.c_int]),
     "pk_diag_occupancy": (ctypes.c_int, [ctypes.c_int]),
     "pk_diag_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_diag_plan_slice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -498,6 +499,23 @@ def diag_plan(k: int, n_bytes: int = 0) -> dict:
     _check(load().pk_diag_plan(k, n_bytes, out.ctypes.data))
     names = ("feed_max", "capacity1", "capacity2", "B1", "B2", "fb_bits", "n_chunks", "fits_u32")
     return {n: int(v) for n, v in zip(names, out)}
+
+
+WS_VARIANTS = ("narrow", "narrow_sliced", "k15", "k17", "wide_sliced", "deep", "wide")
+COUNT_KERNELS = ("whole", "bytes", "half")
+
+
+def diag_plan_slice(k: int, n_slices: int = 1, n_bytes: int = 0) -> dict:
+    """pk_diag_plan_slice: the partition plan of one feed into one of n_slices address slices and what the launchers
+    choose from it (no GPU is touched).  ValueError for what Indexer(k, n_slices=...) refuses."""
+    out = np.zeros(16, dtype=np.uint64)
+    _check(load().pk_diag_plan_slice(k, n_slices, n_bytes, out.ctypes.data))
+    names = ("addr_bits", "fb_bits", "b1", "b2", "sample_stride", "n_tally", "sample2", "n_chunks", "variant", "count_kernel",
+             "split", "B1", "B2", "capacity1", "capacity2", "fits_u32")
+    d = {n: int(v) for n, v in zip(names, out)}
+    d["variant"] = WS_VARIANTS[d["variant"]]
+    d["count_kernel"] = COUNT_KERNELS[d["count_kernel"]]
+    return d
 
 
 def gram_expand(pair: np.ndarray) -> np.ndarray:

@@ -559,18 +559,27 @@ void fuse_set_attributes() {
     set((const void *)PK_WS_DEEP(false), SCATTER_LDS_WIDE); set((const void *)PK_WS_DEEP(true), 65536);
 }
 
+WsVariant walk_sort_variant(const PartPlan &pl) {
+    const bool sliced = pl.slice_bits != 0;
+    if (pl.k > 17) return WS_DEEP;
+    if (pl.k > 15) {
+        if (sliced) return WS_WIDE_SLICED;
+        return pl.k == 17 && pl.b1 == 9 ? WS_K17 : WS_WIDE;
+    }
+    if (sliced) return WS_NARROW_SLICED;
+    return pl.k == 15 && pl.b1 == 7 ? WS_K15 : WS_NARROW;
+}
+
 template <bool COUNT, typename... Args>
 static void launch_ws(const PartPlan &pl, uint32_t grid, size_t lds, hipStream_t s, Args... args) {
-    const bool sliced = pl.slice_bits != 0;
-    if (pl.k > 17) hipLaunchKernelGGL((PK_WS_DEEP(COUNT)), dim3(grid), dim3(1024), lds, s, args...);
-    else if (pl.k > 15) {
-        if (sliced) hipLaunchKernelGGL((PK_WS_WIDE(COUNT, true)), dim3(grid), dim3(1024), lds, s, args...);
-        else if (pl.k == 17 && pl.b1 == 9) hipLaunchKernelGGL((PK_WS_K17(COUNT)), dim3(grid), dim3(1024), lds, s, args...);
-        else hipLaunchKernelGGL((PK_WS_WIDE(COUNT, false)), dim3(grid), dim3(1024), lds, s, args...);
-    } else {
-        if (sliced) hipLaunchKernelGGL((PK_WS_NARROW(COUNT, true)), dim3(grid), dim3(512), lds, s, args...);
-        else if (pl.k == 15 && pl.b1 == 7) hipLaunchKernelGGL((PK_WS_K15(COUNT)), dim3(grid), dim3(512), lds, s, args...);
-        else hipLaunchKernelGGL((PK_WS_NARROW(COUNT, false)), dim3(grid), dim3(512), lds, s, args...);
+    switch (walk_sort_variant(pl)) {
+    case WS_DEEP: hipLaunchKernelGGL((PK_WS_DEEP(COUNT)), dim3(grid), dim3(1024), lds, s, args...); break;
+    case WS_WIDE_SLICED: hipLaunchKernelGGL((PK_WS_WIDE(COUNT, true)), dim3(grid), dim3(1024), lds, s, args...); break;
+    case WS_K17: hipLaunchKernelGGL((PK_WS_K17(COUNT)), dim3(grid), dim3(1024), lds, s, args...); break;
+    case WS_WIDE: hipLaunchKernelGGL((PK_WS_WIDE(COUNT, false)), dim3(grid), dim3(1024), lds, s, args...); break;
+    case WS_NARROW_SLICED: hipLaunchKernelGGL((PK_WS_NARROW(COUNT, true)), dim3(grid), dim3(512), lds, s, args...); break;
+    case WS_K15: hipLaunchKernelGGL((PK_WS_K15(COUNT)), dim3(grid), dim3(512), lds, s, args...); break;
+    case WS_NARROW: hipLaunchKernelGGL((PK_WS_NARROW(COUNT, false)), dim3(grid), dim3(512), lds, s, args...); break;
     }
 }
 

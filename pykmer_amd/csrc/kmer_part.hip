@@ -375,8 +375,8 @@ __device__ __forceinline__ void bucket_count_body(const uint16_t *__restrict__ r
             for (int q = 0; q < 8; q++)                                  // bytes b, b + 1 -> the halves of one counter dword
                 cnt[g * 8 + q] = __builtin_amdgcn_perm(0u, w[q >> 1], (q & 1) ? 0x0c030c02u : 0x0c010c00u);
         }
-    } else {
-        for (uint32_t a = threadIdx.x; a < n_addr / 2; a += T) cnt[a] = slice[2 * a] | ((uint32_t)slice[2 * a + 1] << 16);
+    } else {                                                             // n_addr == 1 (a table of one byte): only the low half exists
+        for (uint32_t a = threadIdx.x; a < max(n_addr / 2, 1u); a += T) cnt[a] = slice[2 * a] | (n_addr > 1u ? (uint32_t)slice[2 * a + 1] << 16 : 0u);
     }
     __syncthreads();
     auto bump = [&](uint32_t a, uint32_t n) {
@@ -499,10 +499,10 @@ __device__ __forceinline__ void bucket_count_body(const uint16_t *__restrict__ r
             reinterpret_cast<uint4 *>(slice)[g] = make_uint4(o[0], o[1], o[2], o[3]);
         }
     } else {
-        for (uint32_t a = threadIdx.x; a < n_addr / 2; a += T) {
+        for (uint32_t a = threadIdx.x; a < max(n_addr / 2, 1u); a += T) {
             uint32_t x = cnt[a], lo = x & 0xffffu, hi = x >> 16;
             slice[2 * a] = (uint8_t)(lo > 255u ? 255u : lo);
-            slice[2 * a + 1] = (uint8_t)(hi > 255u ? 255u : hi);
+            if (n_addr > 1u) slice[2 * a + 1] = (uint8_t)(hi > 255u ? 255u : hi);
         }
     }
     const int d1 = wave_sum_i32(tally.d1), d2 = wave_sum_i32(tally.d2);
@@ -770,8 +770,13 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
 }
 
 // sparse tables (few records per 2^16-address bucket, k = 17): 2^split workgroups per bucket, see k_bucket_count
-static uint32_t bucket_split(const PartPlan &pl, uint64_t n_bytes) {
+uint32_t bucket_split(const PartPlan &pl, uint64_t n_bytes) {
     return pl.fb_bits == 16 && n_bytes / ((uint64_t)pl.B1 * pl.B2) < 8192u ? 1u : 0u;
+}
+// which kernel counts the final buckets (the half-bucket one comes in two forms, by the state of the table)
+CountKernel bucket_count_kernel(const PartPlan &pl, uint64_t n_bytes) {
+    if (pl.fb_bits == 15) return COUNT_HALF;
+    return bucket_split(pl, n_bytes) ? COUNT_BYTES : COUNT_WHOLE;
 }
 
 // What the kernels are built for beyond what make_part_plan promises.  check_k (pk_api.hip) keeps all of it out of reach:
@@ -898,10 +903,14 @@ int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, 
     const auto count = [&](auto kernel, uint32_t grid, size_t lds, auto... geometry) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), lds, s, final_recs, k6_start, k6_end, geometry..., table8, fresh ? 1u : 0u, hist_rep, flags);
     };
-    if (pl.fb_bits == 15 && fresh) count(k_bucket_count_half_lean<1024, true>, n_rows6, lds6, pl.fb_bits, split);   // 64 KiB of counters: two workgroups per CU
-    else if (pl.fb_bits == 15) count(k_bucket_count_half_lean<1024, false>, n_rows6, lds6, pl.fb_bits, split);
-    else if (split) count(k_bucket_count_bytes<1024>, nfb, K6_BYTES_LDS);
-    else count(k_bucket_count<1024>, n_rows6, lds6, pl.fb_bits, split);
+    switch (bucket_count_kernel(pl, n_bytes)) {
+    case COUNT_HALF:                                                     // 64 KiB of counters: two workgroups per CU
+        if (fresh) count(k_bucket_count_half_lean<1024, true>, n_rows6, lds6, pl.fb_bits, split);
+        else count(k_bucket_count_half_lean<1024, false>, n_rows6, lds6, pl.fb_bits, split);
+        break;
+    case COUNT_BYTES: count(k_bucket_count_bytes<1024>, nfb, K6_BYTES_LDS); break;
+    case COUNT_WHOLE: count(k_bucket_count<1024>, n_rows6, lds6, pl.fb_bits, split); break;
+    }
     stage("bucket count");
     hipLaunchKernelGGL(k_apply_side, dim3(AS_WGS), dim3(WG), 0, s, b.side, b.side_n, b.side_cap, table8, hist, hist_rep, flags);
     stage("side list");

@@ -77,6 +77,15 @@ static int check_k(int k, int slice_bits = 0, int slice_index = 0) {
     return PK_OK;
 }
 
+// n_slices as a power of two -> slice_bits, then check_k: what pk_indexer_create_slice and pk_diag_plan_slice accept
+static int check_slices(int k, int n_slices, int slice_index, int *slice_bits_out) {
+    int slice_bits = 0;
+    while (slice_bits < 30 && (1 << slice_bits) < n_slices) slice_bits++;
+    if (n_slices < 1 || (1 << slice_bits) != n_slices) return fail(PK_ERR_ARG, "the number of address slices must be a power of two, got %d", n_slices);
+    *slice_bits_out = slice_bits;
+    return check_k(k, slice_bits, slice_index);
+}
+
 // ================================================================== owned device memory =========
 namespace {
 // "Reserve exactly": nothing at all when the capacity suffices (the steady state of the timed path); otherwise the old
@@ -439,9 +448,7 @@ static int create_indexer(pk_indexer **out, int k, int device, int slice_index, 
     if (!out) return fail(PK_ERR_ARG, "null output pointer");
     *out = nullptr;
     int slice_bits = 0;
-    while (slice_bits < 30 && (1 << slice_bits) < n_slices) slice_bits++;
-    if (n_slices < 1 || (1 << slice_bits) != n_slices) return fail(PK_ERR_ARG, "the number of address slices must be a power of two, got %d", n_slices);
-    int rc = check_k(k, slice_bits, slice_index);
+    int rc = check_slices(k, n_slices, slice_index, &slice_bits);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<pk_indexer> ix(new pk_indexer());        // a failure below destroys what was built so far
@@ -571,6 +578,21 @@ extern "C" int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]) {
     const PartPlan pl = make_part_plan((uint32_t)k, n_bytes, k > 17 ? (uint32_t)(2 * k - 34) : 0u, 0u);
     out[0] = feed_max_for(k); out[1] = pl.capacity1; out[2] = pl.capacity2; out[3] = pl.B1; out[4] = pl.B2; out[5] = pl.fb_bits;
     out[6] = pl.n_chunks; out[7] = plan_fits_u32(pl) ? 1 : 0;
+    return PK_OK;
+}
+
+// the same for one of n_slices address slices, with the choices the launchers make on top of the plan
+extern "C" int pk_diag_plan_slice(int k, int n_slices, uint64_t n_bytes, uint64_t out[16]) {
+    if (!out) return fail(PK_ERR_ARG, "null output");
+    int slice_bits = 0;
+    int rc = check_slices(k, n_slices, 0, &slice_bits);
+    if (rc) return rc;
+    if (n_bytes == 0) n_bytes = feed_max_for(k);
+    const PartPlan pl = make_part_plan((uint32_t)k, n_bytes, (uint32_t)slice_bits, 0u);
+    out[0] = pl.addr_bits; out[1] = pl.fb_bits; out[2] = pl.b1; out[3] = pl.b2; out[4] = pl.sample_stride; out[5] = pl.n_tally;
+    out[6] = pl.sample2; out[7] = pl.n_chunks; out[8] = walk_sort_variant(pl); out[9] = bucket_count_kernel(pl, n_bytes);
+    out[10] = bucket_split(pl, n_bytes); out[11] = pl.B1; out[12] = pl.B2; out[13] = pl.capacity1; out[14] = pl.capacity2;
+    out[15] = plan_fits_u32(pl) ? 1 : 0;
     return PK_OK;
 }
 

@@ -84,6 +84,14 @@ struct PartBuffers {
 };
 struct PartEvents { hipEvent_t sort_begin, sort_end, part_end; };   // recorded by launch_partitioned around the level-1 sort and behind level 2
 PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint32_t slice_index);
+// The two choices the launchers make on top of the plan, as functions: launch_ws / launch_partitioned switch on them and
+// pk_diag_plan_slice reports them (the values are part of that diagnostic: include/pykmer_hip.h).
+enum WsVariant : uint32_t { WS_NARROW = 0, WS_NARROW_SLICED = 1, WS_K15 = 2, WS_K17 = 3, WS_WIDE_SLICED = 4, WS_DEEP = 5,
+                            WS_WIDE = 6 };   // WS_WIDE: 64-bit k-mers, unsliced, not 9 + 9 -- no k that check_k lets through has it
+enum CountKernel : uint32_t { COUNT_WHOLE = 0, COUNT_BYTES = 1, COUNT_HALF = 2 };
+WsVariant walk_sort_variant(const PartPlan &pl);                      // kmer_fuse.hip: the k_walk_sort instantiation
+uint32_t bucket_split(const PartPlan &pl, uint64_t n_bytes);          // kmer_part.hip: 1 = two count workgroups (or byte counters) per final bucket
+CountKernel bucket_count_kernel(const PartPlan &pl, uint64_t n_bytes);   // kmer_part.hip: k_bucket_count, _bytes or _half_lean
 // PK_OK, or PK_ERR_HIP and a message naming the limit of the kernels that the plan exceeds
 int part_plan_check(const PartPlan &pl, uint64_t n_bytes);
 // the bytes of the workspace for the plan; with `view`, also where its regions lie in an allocation starting at `base`
