@@ -33,7 +33,7 @@
 
 namespace pk {
 
-int set_error(int code, const std::string &msg);   // pk_api.hip
+int set_error(int code, const std::string &msg);   // pk_common.hip
 
 // ---- sample2: final-bucket sizes from a sample of the level-1 records (2^15 < final buckets <= 2^18: k = 17, slices of k = 19).
 // One workgroup per level-1 bucket tallies the level-2 digit of every stride2-th group of 256 records in LDS (stride2 = 1:
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(1024) void k_bases2(uint32_t n_blocks, uint32_t n_f
     uint32_t pre = 0, total = 0;
     for (int j = 0; j < 16; j++) { if (j < w) pre += wsum[j]; total += wsum[j]; }
     if (threadIdx.x < n_blocks) block_tot[threadIdx.x] = pre + inc - v;
-    // the sum of all rooms in 64 bits (the 32-bit scan above wraps silently if it ever passed 2^32; feed_piece keeps
+    // the sum of all rooms in 64 bits (the 32-bit scan above wraps silently if it ever passed 2^32; count_feed keeps
     // capacity2 below that, so this can only fire on an internal error -- but then it does fire)
     __shared__ unsigned long long total64;
     if (threadIdx.x == 0) total64 = 0ull;
@@ -779,7 +779,7 @@ CountKernel bucket_count_kernel(const PartPlan &pl, uint64_t n_bytes) {
     return bucket_split(pl, n_bytes) ? COUNT_BYTES : COUNT_WHOLE;
 }
 
-// What the kernels are built for beyond what make_part_plan promises.  check_k (pk_api.hip) keeps all of it out of reach:
+// What the kernels are built for beyond what make_part_plan promises.  check_k (pk_indexer.hip) keeps all of it out of reach:
 // it caps addr_bits at 34, so a two-level plan has bucket_bits <= 18 and B1 >= 16, and its final buckets are either
 // tallied while sampling (addr_bits <= 30: B1 * B2 > B1) or sized from the level-1 records (sample2).
 int part_plan_check(const PartPlan &pl, uint64_t n_bytes) {

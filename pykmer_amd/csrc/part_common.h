@@ -147,7 +147,7 @@ constexpr size_t SCATTER_LDS_WIDE = sizeof(ScatterLds);            // 104 KiB
 // digit and rank of every record in a register until the scan was done: 16 or 32 more live registers and three to
 // four more vector instructions per record, in kernels that are bound by instruction issue.
 // OFF32: every output index of this kernel is below 2^31 (the host cuts feeds of 32-bit k-mers so that both bucket areas
-// stay below that: feed_piece), so byte offsets fit 32 bits and the stores take a scalar base + a 32-bit lane offset
+// stay below that: count_feed), so byte offsets fit 32 bits and the stores take a scalar base + a 32-bit lane offset
 // instead of a 64-bit address per record.
 template <typename RIN, bool WIDE, int NT = SC_T, int PER = SC_PER, int NB = 512, bool FULL = false, int SB = 0, bool OFF32 = false, class Settle>
 __device__ __forceinline__ void scatter_tile(ScatterLdsT<NB> &L, const RIN (&r)[PER], uint32_t okm, uint32_t n_tile,

@@ -1,0 +1,197 @@
+// pk_host.h -- what the files of the host layer share (pk_common.hip, pk_indexer.hip, pk_query.hip, pk_merge.hip): the error
+// helper, owned device memory and the host <-> HBM copy for all of them, struct pk_indexer and the state of a query for
+// pk_indexer.hip (which feeds both kinds of indexer) and pk_query.hip, and the standard headers they use.  Every allocation of
+// the library is made in these files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/pykmer_hip.h"
+#include "pk_kernels.h"
+
+namespace pk {
+extern thread_local std::string g_err;                       // what pk_last_error reports (pk_common.hip)
+int fail(int code, const char *fmt, ...);                    // formats g_err, returns code
+
+#define HIPCHK(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) return pk::fail(PK_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+constexpr int MAX_DEVICES = 64;
+
+// ================================================================== owned device memory =========
+// "Reserve exactly": nothing at all when the capacity suffices (the steady state of the timed path); otherwise the old
+// block is freed FIRST and exactly `need` bytes are allocated.  The k = 17 indexer sits next to a 16 GiB table: these
+// buffers can afford neither geometric growth nor the old and the new block side by side.  The contents are lost.
+int reserve_exact(void **p, size_t *cap, size_t need);
+
+// One device allocation of T and its capacity in bytes.  Move-only; the destructor frees, and leaves g_err alone so that
+// the message of the call that failed survives the clean-up.  Never a member of an object with static storage: the HIP
+// runtime may be gone when static destructors run (Bouncer and GramCtx keep raw pointers for that reason).
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }   // o's destructor frees what this held
+    ~DevBuf() { if (p) hipFree(p); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
+    int reserve(size_t need) { return reserve_exact((void **)&p, &bytes, need); }
+    // "Grow and keep": a larger array with the old contents in front and zeros behind, filled on `s`; the host waits for
+    // it, then the old array is freed.  The new one is released if a step fails.
+    int grow_keep(size_t need, hipStream_t s) {
+        if (need <= bytes) return PK_OK;
+        DevBuf larger;
+        int rc = larger.reserve(need);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(larger.p, 0, need, s));
+        if (bytes) HIPCHK(hipMemcpyAsync(larger.p, p, bytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        swap(larger);
+        return PK_OK;
+    }
+};
+
+// to_device: host -> dev, else dev -> host.  Blocking.  (pk_common.hip)
+int bounce_copy(void *dev, void *host, size_t n, bool to_device, int device);
+
+// the device tallies the values 1 .. 255 only: the zeros are the rest of the n addresses
+inline void hist_with_zeros(const unsigned long long *h, uint64_t n, uint64_t hist256_out[256]) {
+    uint64_t nonzero = 0;
+    for (int v = 1; v < 256; v++) { hist256_out[v] = h[v]; nonzero += h[v]; }
+    hist256_out[0] = n - nonzero;
+}
+
+// ================================================================== indexer and query state ====
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    ~Stream() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+// the device events of a feed, by what they bracket on the stream
+struct Events {
+    hipEvent_t reset_begin = nullptr, reset_end = nullptr;         // ix_reset
+    hipEvent_t scan_begin = nullptr, scan_end = nullptr;           // structure pass: chunk summaries and their scans
+    hipEvent_t squeeze_begin = nullptr, squeeze_end = nullptr;
+    hipEvent_t sort_begin = nullptr, sort_end = nullptr;           // walk + level-1 sort kernel (inside launch_partitioned)
+    hipEvent_t part_end = nullptr;                                 // bucket layout and level 2 end here, the bucket count begins
+    hipEvent_t bucket_end = nullptr;
+    hipEvent_t final_begin = nullptr, final_end = nullptr;         // pk_indexer_finish
+    Events() = default;
+    Events(const Events &) = delete;
+    ~Events() { for (hipEvent_t *e : all()) if (*e) hipEventDestroy(*e); }
+    std::array<hipEvent_t *, 12> all() {
+        return {&reset_begin, &reset_end, &scan_begin, &scan_end, &squeeze_begin, &squeeze_end, &sort_begin, &sort_end, &part_end, &bucket_end,
+                &final_begin, &final_end};
+    }
+};
+
+// What a query indexer (pk_query_create) holds where a counting one holds its table: every valid window is looked up in
+// the caller's tables and tallied per record.  P, hits and depth are sized with the record array and grown with it
+// (grow_with_recs).  The methods queue their work on the indexer's stream `s`.  (pk_query.hip)
+struct QueryState {
+    std::vector<const uint8_t *> tables;                    // the caller's device tables; they stay across resets
+    int min = 1, max = 255;
+    DevBuf<unsigned long long> P;                           // P[r]: valid windows of the stream before record r
+    DevBuf<unsigned long long> hits, depth;                 // row-major [record][table]; with bins [bin][table]
+    uint64_t windows = 0, p_done = 0;                       // valid windows / final entries of P before the next feed
+    // bins (pk_query_set_bins): `bin` valid windows per accumulator row, 0 = one row per record.  Bf[r]: the rows before
+    // record r, grown with P.  The rows a stream of `bytes` bytes and at most `cap` records can hold need no read-back:
+    // every record adds at most one partial bin, and n bytes hold at most n windows.
+    uint64_t bin = 0;
+    DevBuf<unsigned long long> Bf;
+    uint64_t n_bins = 0;                                    // after finish
+    // coordinates (pk_query_set_coords): per row the position of the first base of its first window and one past the last
+    // base of its last, sized and grown with hits.  pos: the position in the open record at the start of the next feed
+    // (word pos_in) and where the feed's kernels leave the one at its end (the other word); cpos: one word per chunk.
+    bool coords = false;
+    DevBuf<unsigned long long> bin_start, bin_end, pos, cpos;
+    int pos_in = 0;
+    hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // the kernels of kmer_query.hip
+    hipEvent_t coords_begin = nullptr, coords_end = nullptr;       // the kernels of kmer_coords.hip
+    double t_coords = 0;
+
+    ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end}) if (e) hipEventDestroy(e); }
+    int create();                                                  // the events, and P for the record array's first capacity
+    int reset(hipStream_t s);                                      // an empty stream; the tables stay, bins and coordinates are off
+    int grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s);   // the record array now holds `cap` records; the rows follow
+    int ensure_rows(uint64_t cap, uint64_t bytes, hipStream_t s);  // binned: the rows `cap` records in `bytes` bytes can make
+};
+
+int create_indexer(pk_indexer **out, int k, int device, int slice_index, int n_slices, bool query);   // pk_indexer.hip
+int query_count_bins(pk_indexer *ix);                          // pk_query.hip: the rows of a finished binned stream
+}  // namespace pk
+
+// One counting stream on one device: the .kin image, the scratch of the structure pass (kmer_count.hip), the squeeze
+// (kmer_pack.hip), the partition passes (kmer_fuse.hip, kmer_part.hip) and the FASTQ front end (fastq.hip), and the stream
+// and events that order and time them.  Everything it holds is released by its destructor.
+struct pk_indexer {
+    int k = 0, device = 0;
+    int slice_bits = 0, slice_index = 0;   // the table holds addresses [slice_index, slice_index + 1) * 4^k / 2^slice_bits
+    uint64_t n = 0;                  // table bytes: 4^k / 2^slice_bits
+    // members are destroyed in reverse order of declaration, behind the destructor's wait: the buffers, then the events,
+    // then the stream
+    pk::Stream stream;
+    pk::Events ev;
+    std::unique_ptr<pk::QueryState> q;       // query mode: no table, hist_rep or partition of its own
+    pk::DevBuf<uint8_t> table8;          // the .kin image
+    // parser state + running totals, and the value histogram, side by side: one copy brings both to the host, one copy resets both
+    struct Tail { pk::Carry carry; unsigned long long hist[256]; pk::FqCarry fq; };
+    pk::DevBuf<Tail> tail, tail0;          // tail0: the state of an empty stream (a reset is a device-to-device copy, no host wait)
+    struct Pinned { Tail tail; uint32_t flags[4]; } *pin = nullptr;   // pinned landing zone of the small read-backs
+    bool tail_on_host = false;         // pin->tail is what the device holds (the last feed brought it along with its flags)
+    bool zero_timed = true;            // t_zero of the last reset has been read from its events
+    pk::DevBuf<unsigned long long> hist_rep;   // HIST_REPLICAS copies of one feed's histogram change (zero between feeds)
+    pk::DevBuf<pk::DevRec> recs;
+    pk::DevBuf<pk::L1> c_l1, c_l1s;
+    pk::DevBuf<pk::L2> c_l2, c_l2s;
+    pk::DevBuf<pk::LaneState> lane_state;      // per 64-byte piece: start state relative to its chunk
+    pk::DevBuf<pk::PiecePack> packs;           // per 64-byte piece: its bases, classified and pushed together (structure pass -> squeeze pass)
+    pk::DevBuf<uint32_t> chunk_odd;        // per chunk: pieces that are not plain sequence text
+    pk::DevBuf<pk::L1> t_l1;                   // scan scratch: one summary per 1024 chunks
+    pk::DevBuf<pk::L2> t_l2;
+    pk::DevBuf<uint8_t> staging[2];        // device copies of host-fed pieces (one counted while the next uploads)
+    uint64_t bytes_fed = 0, n_recs = 0;
+    bool finished = false;
+    double t_scan = 0, t_squeeze = 0, t_sort = 0, t_final = 0, t_zero = 0, t_part = 0, t_bucket = 0;
+    int feeds = 0, relayouts = 0;
+    uint64_t recounted = 0;                                // buckets whose byte counters wrapped and were counted again (k_bucket_count_bytes)
+    bool table_fresh = true;         // no feed has written the u8 table since the last reset
+    pk::DevBuf<uint8_t> ws;              // workspace of the partition passes
+    // FASTQ input (fastq.hip): each feed is turned into FASTA text in fq_out[fq_buf]; that text is counted by the next
+    // feed (or by finish), whose read-back brings this feed's checks and totals along -- no wait of its own
+    int format = PK_FORMAT_FASTA;
+    bool fed = false;                  // bytes were fed since the last reset
+    pk::DevBuf<pk::FqSum> fq_sums;
+    pk::DevBuf<pk::FqState> fq_st;
+    pk::DevBuf<uint8_t> fq_out[2];
+    int fq_buf = 0;
+    uint64_t fq_pending = 0;           // FASTA bytes in fq_out[fq_buf ^ 1] not counted yet
+    pk::DevBuf<pk::FqRec> fq_recs;
+    uint64_t fq_need = 0;
+    bool fq_failed = false;
+    std::string fq_err;
+
+    uint64_t recs_cap() const { return recs.bytes / sizeof(pk::DevRec); }
+    uint64_t fq_recs_cap() const { return fq_recs.bytes / sizeof(pk::FqRec); }
+    ~pk_indexer() {
+        hipSetDevice(device);
+        if (stream) hipStreamSynchronize(stream);
+        if (pin) hipHostFree(pin);
+    }
+};

@@ -1,4 +1,4 @@
-// pk_kernels.h -- device-side structs and kernel launchers shared between the .hip files and pk_api.
+// pk_kernels.h -- device-side structs and kernel launchers shared between the kernel files and the host layer (pk_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,192 @@
+// pk_query.hip -- query mode of the host layer: the state a query indexer holds (QueryState, pk_host.h) and the
+// pk_query_* entry points.  The feeds themselves go through pk_indexer.hip, which queues the kernels of kmer_query.hip and
+// kmer_coords.hip behind the squeeze.
+#include "pk_host.h"
+
+using namespace pk;
+
+int QueryState::create() {
+    for (hipEvent_t *e : {&lookup_begin, &lookup_end, &coords_begin, &coords_end}) HIPCHK(hipEventCreate(e));
+    return P.reserve(4096 * sizeof(unsigned long long));
+}
+
+int QueryState::reset(hipStream_t s) {
+    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos})
+        if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, s));
+    windows = p_done = 0;
+    bin = n_bins = 0;
+    coords = false; pos_in = 0; t_coords = 0;
+    return PK_OK;
+}
+
+// the window prefix and the accumulators grow with the record array and keep what they hold; binned, the rows are sized
+// again for the `bytes` of the stream, the feed under way included
+int QueryState::grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s) {
+    const size_t row = tables.size() * sizeof(unsigned long long);
+    int rc = P.grow_keep(cap * sizeof(unsigned long long), s);
+    if (rc) return rc;
+    if (bin) return (rc = Bf.grow_keep(cap * sizeof(unsigned long long), s)) ? rc : ensure_rows(cap, bytes, s);
+    if ((rc = hits.grow_keep(cap * row, s))) return rc;
+    return depth.grow_keep(cap * row, s);
+}
+
+// Binned query: the accumulators, and with coordinates their two arrays, hold the rows that `bytes` bytes of stream and
+// `cap` records can make (contents kept, the rest zero).  They grow by half at least, so that a long stream does not move
+// them with every feed.
+int QueryState::ensure_rows(uint64_t cap, uint64_t bytes, hipStream_t s) {
+    if (!bin) return PK_OK;
+    const uint64_t rows = bytes / bin + cap + 1;
+    const size_t word = sizeof(unsigned long long), N = tables.size();
+    if (rows > SIZE_MAX / 2 / (N * word))
+        return fail(PK_ERR_ARG, "bins of %llu windows: %llu rows of %zu tables are beyond the address space; take larger bins",
+                    (unsigned long long)bin, (unsigned long long)rows, N);
+    auto grow = [&](DevBuf<unsigned long long> *a, DevBuf<unsigned long long> *b, size_t row, const char *noun, const char *shape) -> int {
+        for (DevBuf<unsigned long long> *buf : {a, b}) {
+            if (rows * row <= buf->bytes) continue;
+            const size_t want = std::max<size_t>(rows * row, buf->bytes + buf->bytes / 2);
+            const int rc = buf->grow_keep(want, s);
+            if (rc) {
+                (void)hipGetLastError();
+                const std::string why = g_err;
+                return fail(rc, "bins of %llu windows need two %s of %zu bytes (%s); take larger bins: %s", (unsigned long long)bin, noun, want, shape,
+                            why.c_str());
+            }
+        }
+        return PK_OK;
+    };
+    char shape[64];                                          // of the arrays, for the refusal
+    snprintf(shape, sizeof shape, "%llu rows, %zu tables", (unsigned long long)rows, N);
+    const int rc = grow(&hits, &depth, N * word, "accumulators", shape);
+    if (rc || !coords) return rc;
+    snprintf(shape, sizeof shape, "%llu rows", (unsigned long long)rows);
+    return grow(&bin_start, &bin_end, word, "coordinate arrays", shape);
+}
+
+// The opening checks of the pk_query_* entry points, in the order that decides which message a caller sees: a query
+// indexer; the entry point's own demand on the tables, bins or coordinates (`met`, null for none; `unmet` says what is
+// missing); then either nothing fed yet (`too_late` is the refusal of a setting) or, without one, a finished stream.
+static int query_check(pk_indexer *ix, bool (*met)(const QueryState &), const char *unmet, const char *too_late) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->q) return fail(PK_ERR_STATE, "not a query indexer (pk_query_create)");
+    if (met && !met(*ix->q)) return fail(PK_ERR_STATE, "%s", unmet);
+    if (too_late && (ix->fed || ix->finished)) return fail(PK_ERR_STATE, "%s", too_late);
+    if (!too_late && !ix->finished) return fail(PK_ERR_STATE, "call pk_indexer_finish first");
+    return PK_OK;
+}
+static bool has_tables(const QueryState &q) { return !q.tables.empty(); }
+static bool binned(const QueryState &q) { return q.bin != 0; }
+static bool per_record(const QueryState &q) { return q.bin == 0; }
+static bool with_coords(const QueryState &q) { return q.coords; }
+
+extern "C" int pk_query_create(pk_indexer **out, int k, int device) {
+    if (k > 17) return fail(PK_ERR_ARG, "a query takes kmer_len <= 17 (one unsliced table), got %d", k);
+    return create_indexer(out, k, device, 0, 1, true);
+}
+
+extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables, int N, int min_count, int max_count) {
+    if (int rc = query_check(ix, nullptr, nullptr, "the tables are set before the first feed (reset the indexer first)")) return rc;
+    if (N < 1 || !dev_tables) return fail(PK_ERR_ARG, "need at least one table");
+    if (min_count < 1 || max_count > 255 || min_count > max_count) return fail(PK_ERR_ARG, "count window must satisfy 1 <= min <= max <= 255, got %d-%d", min_count, max_count);
+    for (int i = 0; i < N; i++)
+        if (!dev_tables[i]) return fail(PK_ERR_ARG, "table %d is a null pointer", i);
+    HIPCHK(hipSetDevice(ix->device));
+    QueryState &q = *ix->q;
+    q.tables.assign((const uint8_t *const *)dev_tables, (const uint8_t *const *)dev_tables + N);
+    q.min = min_count; q.max = max_count;
+    // the accumulators of an empty stream for this many tables (a reset zeroed them, but N may have changed)
+    const size_t need = ix->recs_cap() * (size_t)N * sizeof(unsigned long long);
+    for (DevBuf<unsigned long long> *b : {&q.hits, &q.depth}) {
+        int rc = b->reserve(need);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
+    }
+    return PK_OK;
+}
+
+extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
+    if (int rc = query_check(ix, has_tables, "pk_query_set_tables comes before pk_query_set_bins", "the bins are set before the first feed (reset the indexer first)")) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    QueryState &q = *ix->q;
+    q.bin = bin_windows;
+    q.coords = false;                                        // pk_query_set_coords comes after the bins
+    if (!bin_windows) return PK_OK;
+    // Bf beside P; a reset zeroed what was there, a new array is zeroed here
+    const int rc = q.Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
+    return rc ? rc : q.ensure_rows(ix->recs_cap(), 0, ix->stream);
+}
+
+extern "C" int pk_query_set_coords(pk_indexer *ix, int on) {
+    if (int rc = query_check(ix, binned, "pk_query_set_bins with bins of at least one window comes before pk_query_set_coords", "the coordinates are set before the first feed (reset the indexer first)")) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    QueryState &q = *ix->q;
+    q.coords = on != 0;
+    if (!q.coords) return PK_OK;
+    // the two position words; a reset zeroed what was there, a new array is zeroed here
+    const int rc = q.pos.grow_keep(2 * sizeof(unsigned long long), ix->stream);
+    return rc ? rc : q.ensure_rows(ix->recs_cap(), 0, ix->stream);
+}
+
+// the rows of a finished binned stream: the last record's bins are not in Bf
+int pk::query_count_bins(pk_indexer *ix) {
+    QueryState &q = *ix->q;
+    q.n_bins = 0;
+    if (!q.bin || !ix->n_recs) return PK_OK;
+    unsigned long long bf = 0;
+    DevRec last;
+    HIPCHK(hipMemcpy(&bf, q.Bf.p + (ix->n_recs - 1), sizeof bf, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&last, ix->recs.p + (ix->n_recs - 1), sizeof last, hipMemcpyDeviceToHost));
+    q.n_bins = bf + (last.n_valid ? (last.n_valid - 1) / q.bin + 1 : 0);
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_count(pk_indexer *ix, uint64_t *n_bins_out) {
+    if (!ix || !n_bins_out) return fail(PK_ERR_ARG, "null argument");
+    if (int rc = query_check(ix, binned, "the indexer tallies per record (pk_query_set_bins)", nullptr)) return rc;
+    *n_bins_out = ix->q->n_bins;
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *depth_out, uint64_t *bin_first_out, uint64_t bins_cap,
+                                    uint64_t recs_cap) {
+    if (int rc = query_check(ix, binned, "the indexer tallies per record (pk_query_set_bins); use pk_query_results", nullptr)) return rc;
+    const QueryState &q = *ix->q;
+    if (ix->n_recs > recs_cap || q.n_bins > bins_cap)
+        return fail(PK_ERR_RECS_CAP, "%llu bins and %llu records, capacities %llu and %llu", (unsigned long long)q.n_bins,
+                    (unsigned long long)ix->n_recs, (unsigned long long)bins_cap, (unsigned long long)recs_cap);
+    if (!bin_first_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    if (ix->n_recs) HIPCHK(hipMemcpy(bin_first_out, q.Bf.p, ix->n_recs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    bin_first_out[ix->n_recs] = q.n_bins;
+    if (q.n_bins == 0) return PK_OK;
+    if (!hits_out || !depth_out) return fail(PK_ERR_ARG, "null output pointer");
+    const size_t n = q.n_bins * q.tables.size() * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(hits_out, q.hits.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(depth_out, q.depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_bin_coords(pk_indexer *ix, uint64_t *start_out, uint64_t *end_out, uint64_t bins_cap) {
+    if (int rc = query_check(ix, with_coords, "the indexer keeps no coordinates (pk_query_set_coords)", nullptr)) return rc;
+    const QueryState &q = *ix->q;
+    if (q.n_bins > bins_cap)
+        return fail(PK_ERR_RECS_CAP, "%llu bins, capacity %llu", (unsigned long long)q.n_bins, (unsigned long long)bins_cap);
+    if (q.n_bins == 0) return PK_OK;
+    if (!start_out || !end_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const size_t n = q.n_bins * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(start_out, q.bin_start.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(end_out, q.bin_end.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap) {
+    if (int rc = query_check(ix, per_record, "the indexer tallies per bin (pk_query_set_bins); use pk_query_bin_results", nullptr)) return rc;
+    if (ix->n_recs > recs_cap) return fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)ix->n_recs, (unsigned long long)recs_cap);
+    if (ix->n_recs == 0) return PK_OK;
+    if (!hits_out || !depth_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const size_t n = ix->n_recs * ix->q->tables.size() * sizeof(uint64_t);
+    HIPCHK(hipMemcpy(hits_out, ix->q->hits.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(depth_out, ix->q->depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}

@@ -521,7 +521,7 @@ RECS_INITIAL = 4096                                          # pk_indexer_create
 
 def record_overflows(lengths, record_starts):
     """Which of the feeds (byte lengths, in order; 0 = an empty feed, which never reaches the pipeline) bring more records
-    than the record array holds when they arrive -- the capacity rule of pk_api.hip (ensure_recs, feed_piece: after every
+    than the record array holds when they arrive -- the capacity rule of pk_indexer.hip (ensure_recs, run_feed: after every
     feed room for as many records again as it brought, times two, + 1024).  `record_starts`: offset of every record's '>'."""
     starts = np.sort(np.asarray(record_starts, dtype=np.int64))
     cap, n, end, out = RECS_INITIAL, 0, 0, []

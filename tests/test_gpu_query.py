@@ -220,6 +220,8 @@ def test_feeds_cut_anywhere_and_reset(gpu):
         # a second stream after reset: its own results, nothing carried over
         with _lib().QueryIndexer(k, device=0) as q:
             q.set_tables(dev.ptrs, 2, 255)
+            r = reads[:5000].count(b">")
+            assert 3 * r + 1024 <= 4096 < reads.count(b">")                # the record array grows in the second feed, over the first feed's rows
             _feed(q, reads, [5000])
             first = _collect(q)
             q.reset()

@@ -162,6 +162,23 @@ def test_short_reads_on_a_fresh_indexer_and_again_after_a_reset(gpu):
         _same(halves, want)
 
 
+def test_short_reads_retry_in_the_second_feed(gpu):
+    """The squeeze backs out in a later feed, while the accumulators and the coordinate rows hold the first feed's rows:
+    the first feed ends inside record 100 after 9 bases (5 windows: one full row and an open row with a provisional end)
+    and leaves the record array at its first capacity; the second brings the 5 000 records."""
+    k, W = 5, 3
+    text, want = _want("short", k, W)
+    cut = 1612
+    opened = text[:cut].count(b">")
+    assert opened == 101 and text[cut - 12:cut - 9] == b">r\n"         # 9 bases of record 100: 9 - k + 1 = 5 windows
+    assert int(query_coords_ref.expected(text[:cut], k, _tables(k), 1, 255, W)["n_valid"][100]) == 5
+    assert opened + 2 * opened + 1024 < 4096                 # the first feed does not grow the record array ...
+    assert len(want["records"]) == 5000 > 4096               # ... and the second does not fit in it
+    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+        q.set_tables(dev.ptrs, 1, 255)
+        _same(_coords(q, text, W, cuts=[cut]), want)
+
+
 # ------------------------------------------------------------------ 5. feeds -----------------------
 def _gap_cuts(k: int, W: int):
     text, runs = qci.gapped(k)
