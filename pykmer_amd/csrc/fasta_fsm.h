@@ -121,6 +121,16 @@ __device__ __forceinline__ L2 lane_state_l2(const LaneState &o) {
 __device__ __forceinline__ uint32_t lane_state_ls(const LaneState &o) { return (o.flags >> 16) & 3u; }
 __device__ __forceinline__ bool lane_state_dirty(const LaneState &o) { return (o.flags >> 18) & 1u; }
 __device__ __forceinline__ bool lane_state_header_piece(const LaneState &o) { return (o.flags >> 19) & 1u; }
+// A lane's exact start state: the chunk's state, then the lane's prefix.  clean: plain sequence text that is not entered
+// inside a header line -- the pieces the structure pass does NOT count in chunk_odd, which take the short paths.
+struct LaneStart { L2 st; uint32_t ls_in; bool clean; };
+__device__ __forceinline__ LaneStart lane_start(const LaneState lst, const L2 &chunk_st, uint32_t km1) {
+    LaneStart s;
+    s.st = l2_compose(chunk_st, lane_state_l2(lst), km1);
+    s.ls_in = lane_state_ls(lst);
+    s.clean = !lane_state_dirty(lst) && !lane_state_header_piece(lst) && s.ls_in != LS_HEADER;
+    return s;
+}
 
 // ---- wave / workgroup exclusive scans (64-wide wavefronts, non-commutative operator) ----------
 __device__ __forceinline__ L1 wave_incl_scan_l1(L1 v, int lane) {

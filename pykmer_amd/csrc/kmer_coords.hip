@@ -26,7 +26,9 @@
 //                   piece prefix-summed behind slot_first[c] (their ordinals), and the two rules above.  Clean pieces by
 //                   masks (piece_scan and the pack's restart bits), the others by the rolled byte loop
 // Like the kernels of kmer_query.hip all three return at once, writing nothing, when flags[0] is raised.
+#include "kmer_window.h"
 #include "pk_kernels.h"
+#include "wg_scan.h"
 
 namespace pk {
 
@@ -102,15 +104,6 @@ __device__ __forceinline__ CoordPiece coords_walk(const uint8_t *mine, uint32_t 
     return cp;
 }
 
-// this lane's exact start state in chunk c
-__device__ __forceinline__ L2 coords_lane_state(const LaneState *__restrict__ lane_state, const L2 *__restrict__ chunk_l2_state, uint32_t c,
-                                                uint32_t km1, uint32_t &ls_in, bool &clean) {
-    const LaneState lst = lane_state[(uint64_t)c * WG + threadIdx.x];
-    ls_in = lane_state_ls(lst);
-    clean = !lane_state_dirty(lst) && !lane_state_header_piece(lst) && ls_in != LS_HEADER;   // the structure pass's definition (k_squeeze)
-    return l2_compose(chunk_l2_state[c], lane_state_l2(lst), km1);
-}
-
 __global__ __launch_bounds__(WG) void k_coords_sum(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
                                                    const PiecePack *__restrict__ packs, const L2 *__restrict__ chunk_l2_state,
                                                    const uint32_t *__restrict__ chunk_odd, uint32_t k, unsigned long long *__restrict__ chunk_pos,
@@ -120,9 +113,10 @@ __global__ __launch_bounds__(WG) void k_coords_sum(const uint8_t *__restrict__ f
     if (flags[0]) return;
     const uint32_t c = blockIdx.x;
     const uint64_t base = (uint64_t)c * CHUNK;
-    uint32_t ls_in;
-    bool clean;
-    const L2 st = coords_lane_state(lane_state, chunk_l2_state, c, k - 1u, ls_in, clean);
+    const LaneStart ln = lane_start(lane_state[(uint64_t)c * WG + threadIdx.x], chunk_l2_state[c], k - 1u);
+    const L2 &st = ln.st;
+    const uint32_t ls_in = ln.ls_in;
+    const bool clean = ln.clean;
     const uint32_t nb = piece_len(base, n_bytes);
     // a clean piece (plain sequence text): the structure pass counted its sequence characters; blanks pending from the
     // piece before are interior if a sequence character comes first (squeeze_apply).  Only a chunk that holds other
@@ -161,20 +155,6 @@ __global__ __launch_bounds__(CSNT) void k_coords_scan(unsigned long long *__rest
     if (threadIdx.x == 0) *pos_out = run;
 }
 
-// exclusive prefix of v over the workgroup (WG threads) and its total; sh: WG / 64 words
-__device__ __forceinline__ uint32_t coords_scan_u32(uint32_t v, uint32_t *sh, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    if (lane == 63u) sh[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-    for (uint32_t i = 0; i < WG / 64; i++) { if (i < w) pre += sh[i]; total += sh[i]; }
-    return pre + inc - v;
-}
-
 // the byte of the n-th set bit of x, n counted from 0 (n < popcount(x))
 __device__ __forceinline__ uint32_t nth_set(unsigned long long x, uint32_t n) {
     uint32_t at = 0;
@@ -184,27 +164,6 @@ __device__ __forceinline__ uint32_t nth_set(unsigned long long x, uint32_t n) {
         if (n >= below) { n -= below; x >>= w; at += w; }
     }
     return at;
-}
-
-// The valid windows that end at each of a clean piece's nv pushed-together bases (bit j: one ends at base j) from the pack's
-// restart bits and the run carried in: window_ends of kmer_pack.hip, which is local to the squeeze.
-__device__ __forceinline__ unsigned long long coords_window_ends(unsigned long long F, uint32_t nv, uint32_t run, uint32_t km1) {
-    if (run == 0u && nv) F |= 1ull;
-    const unsigned long long keep = nv >= 64u ? ~0ull : ((1ull << nv) - 1ull);
-    unsigned long long X = 0;
-    {
-        const unsigned long long y1 = F | (F << 1), y2 = y1 | (y1 << 2), y3 = y2 | (y2 << 4), y4 = y3 | (y3 << 8);
-        uint32_t off = 0;
-        if (km1 & 16u) { X |= y4; off = 16; }
-        if (km1 & 8u) { X |= y3 << off; off += 8; }
-        if (km1 & 4u) { X |= y2 << off; off += 4; }
-        if (km1 & 2u) { X |= y1 << off; off += 2; }
-        if (km1 & 1u) { X |= F << off; }
-    }
-    const uint32_t short_by = run >= km1 ? 0u : km1 - run;
-    const unsigned long long lead = short_by >= 64u ? ~0ull : ((1ull << short_by) - 1ull);
-    const unsigned long long below_first = F ? ((F & (0ull - F)) - 1ull) : ~0ull;
-    return ~X & ~(lead & below_first) & keep;
 }
 
 __global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
@@ -221,10 +180,11 @@ __global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__
     if (flags[0]) return;
     const uint32_t c = blockIdx.x;
     const uint64_t base = (uint64_t)c * CHUNK;
-    uint32_t ls_in;
-    bool clean;
-    const L2 st = coords_lane_state(lane_state, chunk_l2_state, c, k - 1u, ls_in, clean);
-    const unsigned long long restart = packs[(uint64_t)c * WG + threadIdx.x].restart;
+    const LaneStart ln = lane_start(lane_state[(uint64_t)c * WG + threadIdx.x], chunk_l2_state[c], k - 1u);
+    const L2 &st = ln.st;
+    const uint32_t ls_in = ln.ls_in;
+    const bool clean = ln.clean;
+    unsigned long long restart = packs[(uint64_t)c * WG + threadIdx.x].restart;   // a copy: window_ends completes base 0's bit in place
     stage_chunk(fasta, base, n_bytes, text);
     __syncthreads();
     const uint8_t *mine = text + threadIdx.x * LDS_STRIDE;
@@ -240,7 +200,7 @@ __global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__
     CoordPiece cp;
     cp.posm = ~pm.term; cp.hdrm = 0ull;
     cp.carried = (st.p_tail && (cp.posm & 1ull)) ? st.p_tail : 0ull;
-    cp.wend = st.rec != 0u ? coords_window_ends(restart, (uint32_t)__popcll(valid), cp.carried ? 0u : l2_len(st), k - 1u) : 0ull;
+    cp.wend = st.rec != 0u ? window_ends(restart, (uint32_t)__popcll(valid), cp.carried ? 0u : l2_len(st), k - 1u) : 0ull;
     if (__any(!clean)) {
         const CoordPiece walked = coords_walk(mine, nb, ls_in, st, k);
         if (!clean) cp = walked;
@@ -251,7 +211,7 @@ __global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__
         return clean ? nth_set(valid, at) : at;
     };
     uint32_t n_win;
-    const uint32_t off = coords_scan_u32((uint32_t)__popcll(cp.wend), sh32, n_win);
+    const uint32_t off = wg_excl_sum<WG / 64, false>((uint32_t)__popcll(cp.wend), sh32, n_win);   // sh32: first use
     if (n_win == 0u) return;                                 // uniform: no window ends in the chunk
     unsigned long long unused;
     const unsigned long long ex = cp_block_excl<WG / 64>(cp.pair(), sh, unused);

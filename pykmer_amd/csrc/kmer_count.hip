@@ -6,6 +6,7 @@
 // starts from.  k_hist is Header.update_stats (tools.py:246-263) for tables that arrive from disk.
 #include "fasta_fsm.h"
 #include "pk_kernels.h"
+#include "wg_scan.h"
 
 namespace pk {
 
@@ -182,31 +183,15 @@ __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__rest
 // Three tiny launches per level instead of one latency-bound workgroup: (1) every 1024-summary tile is
 // reduced by its own workgroup, (2) one workgroup scans the <= a few hundred tile totals behind the
 // carried stream state, (3) every tile is scanned again behind its seed and written out.
+// Each tile is one wg_excl_scan (wg_scan.h); its LDS words are free at every call -- the kernels that loop over tiles
+// end each round with a barrier.
 constexpr int SCAN_T = 1024;
-
-template <typename S, class Compose, class Shfl>
-__device__ __forceinline__ S tile_scan(const S &mine, const S &seed, S *sh, S *total, Compose compose, Shfl shfl_up1) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    S inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        S o = shfl_up1(inc, d);
-        if (lane >= d) inc = compose(o, inc);
-    }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    S pre = seed, tot = seed;
-    for (int j = 0; j < SCAN_T / 64; j++) { if (j == w) pre = tot; tot = compose(tot, sh[j]); }
-    *total = tot;
-    S up = shfl_up1(inc, 1);
-    return lane == 0 ? pre : compose(pre, up);
-}
 
 __global__ __launch_bounds__(SCAN_T) void k_scan_l1_reduce(const L1 *__restrict__ in, uint32_t n, L1 *__restrict__ tile_tot) {
     __shared__ L1 sh[SCAN_T / 64];
     const uint32_t i = blockIdx.x * SCAN_T + threadIdx.x;
     L1 tot;
-    tile_scan<L1>(i < n ? in[i] : 0u, 0u, sh, &tot, [](L1 a, L1 b) { return l1_compose(a, b); }, [](L1 v, int d) { return (L1)__shfl_up(v, d, 64); });
+    wg_excl_scan<SCAN_T / 64, false>(i < n ? in[i] : 0u, 0u, sh, tot, [](L1 a, L1 b) { return l1_compose(a, b); }, [](L1 v, int d) { return (L1)__shfl_up(v, d, 64); });
     if (threadIdx.x == 0) tile_tot[blockIdx.x] = tot;
 }
 // (also zeroes `n_zero` words at `zero_words`: the side-list length and the flags of the feed's partition passes -- one
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l1_tiles(L1 *__restrict__ tile_
     for (uint32_t t0 = 0; t0 < n_tiles; t0 += SCAN_T) {
         const uint32_t i = t0 + threadIdx.x;
         L1 tot;
-        L1 ex = tile_scan<L1>(i < n_tiles ? tile_tot[i] : 0u, run, sh, &tot, [](L1 a, L1 b) { return l1_compose(a, b); },
+        L1 ex = wg_excl_scan<SCAN_T / 64, false>(i < n_tiles ? tile_tot[i] : 0u, run, sh, tot, [](L1 a, L1 b) { return l1_compose(a, b); },
                               [](L1 v, int d) { return (L1)__shfl_up(v, d, 64); });
         if (i < n_tiles) tile_tot[i] = ex;                 // now: the state before the tile
         run = tot;
@@ -232,7 +217,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l1_apply(const L1 *__restrict__
     __shared__ L1 sh[SCAN_T / 64];
     const uint32_t i = blockIdx.x * SCAN_T + threadIdx.x;
     L1 tot;
-    L1 ex = tile_scan<L1>(i < n ? in[i] : 0u, tile_seed[blockIdx.x], sh, &tot, [](L1 a, L1 b) { return l1_compose(a, b); },
+    L1 ex = wg_excl_scan<SCAN_T / 64, false>(i < n ? in[i] : 0u, tile_seed[blockIdx.x], sh, tot, [](L1 a, L1 b) { return l1_compose(a, b); },
                           [](L1 v, int d) { return (L1)__shfl_up(v, d, 64); });
     if (i < n) out_state[i] = ex;
 }
@@ -241,7 +226,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l2_reduce(const L2 *__restrict_
     __shared__ L2 sh[SCAN_T / 64];
     const uint32_t i = blockIdx.x * SCAN_T + threadIdx.x;
     L2 tot;
-    tile_scan<L2>(i < n ? in[i] : l2_identity(), l2_identity(), sh, &tot, [km1](const L2 &a, const L2 &b) { return l2_compose(a, b, km1); },
+    wg_excl_scan<SCAN_T / 64, false>(i < n ? in[i] : l2_identity(), l2_identity(), sh, tot, [km1](const L2 &a, const L2 &b) { return l2_compose(a, b, km1); },
                   [](const L2 &v, int d) { return shfl_up_l2(v, d); });
     if (threadIdx.x == 0) tile_tot[blockIdx.x] = tot;
 }
@@ -251,7 +236,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l2_tiles(L2 *__restrict__ tile_
     for (uint32_t t0 = 0; t0 < n_tiles; t0 += SCAN_T) {
         const uint32_t i = t0 + threadIdx.x;
         L2 tot;
-        L2 ex = tile_scan<L2>(i < n_tiles ? tile_tot[i] : l2_identity(), run, sh, &tot,
+        L2 ex = wg_excl_scan<SCAN_T / 64, false>(i < n_tiles ? tile_tot[i] : l2_identity(), run, sh, tot,
                               [km1](const L2 &a, const L2 &b) { return l2_compose(a, b, km1); }, [](const L2 &v, int d) { return shfl_up_l2(v, d); });
         if (i < n_tiles) tile_tot[i] = ex;
         run = tot;
@@ -265,7 +250,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_l2_apply(const L2 *__restrict__
     __shared__ L2 sh[SCAN_T / 64];
     const uint32_t i = blockIdx.x * SCAN_T + threadIdx.x;
     L2 tot;
-    L2 ex = tile_scan<L2>(i < n ? in[i] : l2_identity(), tile_seed[blockIdx.x], sh, &tot,
+    L2 ex = wg_excl_scan<SCAN_T / 64, false>(i < n ? in[i] : l2_identity(), tile_seed[blockIdx.x], sh, tot,
                           [km1](const L2 &a, const L2 &b) { return l2_compose(a, b, km1); }, [](const L2 &v, int d) { return shfl_up_l2(v, d); });
     if (i < n) out_state[i] = ex;
 }

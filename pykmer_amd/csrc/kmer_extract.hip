@@ -16,6 +16,7 @@
 //   k_extract_text   m addresses -> m lines of k letters + '\n', 16 output bytes per thread
 #include "pk_kernels.h"
 #include "gram_load.h"
+#include "wg_scan.h"
 
 namespace pk {
 
@@ -128,23 +129,14 @@ __global__ __launch_bounds__(XT) void k_extract_write(const uint8_t *const *__re
     unsigned long long rank = wg[blockIdx.x];    // of the workgroup's first selected address
     if (wg[blockIdx.x + 1u] == rank) return; // nothing selected here (wg[n_wg] is the total, so the last workgroup reads it)
     if (threadIdx.x < P) tp[threadIdx.x] = tables[threadIdx.x];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     for (uint32_t s = 0; s < X_STEPS; s++) {
         const uint64_t tile = (uint64_t)blockIdx.x * X_WG + (uint64_t)s * X_TILE;
         if (tile >= n) break;
         const uint64_t off = tile + (uint64_t)threadIdx.x * X_ADDR;
         uint32_t mask = off < n ? masks[off / X_ADDR] : 0u;
-        const uint32_t c = __popc(mask);
-        uint32_t inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-        __syncthreads();                         // the previous step's readers of sel and wsum are done (and tp is written)
-        if (lane == 63u) wsum[w] = inc;
-        __syncthreads();
-        uint32_t pre = 0, S = 0;
-        for (uint32_t i = 0; i < XT / 64; i++) { if (i < w) pre += wsum[i]; S += wsum[i]; }
+        uint32_t S;                              // the barrier in front: the previous step's readers of sel and wsum are done (and tp is written)
+        uint32_t r = wg_excl_sum<XT / 64, true>((uint32_t)__popc(mask), wsum, S);
         if (S == 0u) continue;                   // uniform
-        uint32_t r = pre + inc - c;
         while (mask) {
             const uint32_t j = __ffs(mask) - 1u;
             mask &= mask - 1u;

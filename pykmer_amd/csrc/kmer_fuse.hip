@@ -32,21 +32,11 @@
 // exact sizes.  Inputs below 1024 chunks are counted exactly straight away.  Every kernel here also returns at once
 // when it finds the flag already raised (flags[0] = 2: the squeeze backed out, so codes / restarts / n_bases still
 // hold an earlier text): a raised flag keeps the value it was raised with until the host has read it.
+#include "kmer_window.h"
 #include "part_common.h"
+#include "wg_scan.h"
 
 namespace pk {
-
-// OR of (x << s) for s = 0 .. n-1 (n even, <= 16): which positions have a restart among the n before-or-at them
-__device__ __forceinline__ uint32_t smear_up(uint32_t x, uint32_t n) {
-    const uint32_t y1 = x | (x << 1), y2 = y1 | (y1 << 2), y3 = y2 | (y2 << 4);
-    if (n >= 16u) return y3 | (y3 << 8);
-    uint32_t acc = 0, off = 0;
-    if (n & 8u) { acc |= y3; off = 8; }
-    if (n & 4u) { acc |= y2 << off; off += 4; }
-    if (n & 2u) { acc |= y1 << off; off += 2; }
-    if (n & 1u) { acc |= x << off; }
-    return acc;
-}
 
 // DEEP: the 32 valid bases of the stream in front of slot c, newest at the top (fields 31 .. 0, older bases lower), whatever
 // restarts lie among them -- the run state says how many may be used.  They are the last bases of the slots before c; where
@@ -260,18 +250,8 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
             const uint32_t cnt = n_mine > 16u * w ? min(16u, n_mine - 16u * w) : 0u;
             // window ending at base j of this word is void iff a restart lies among the k-1 bases after its first
             uint32_t has_x;                                                                // bit 16 + j: a restart lies among the k-1 positions before-or-at base j
-            if (DEEP) {
-                const unsigned long long y1 = rb64 | (rb64 << 1), y2 = y1 | (y1 << 2), y3 = y2 | (y2 << 4), y4 = y3 | (y3 << 8);
-                unsigned long long acc = 0;
-                uint32_t off = 0;
-                if (km1 & 16u) { acc |= y4; off = 16; }
-                if (km1 & 8u) { acc |= y3 << off; off += 8; }
-                if (km1 & 4u) { acc |= y2 << off; off += 4; }
-                if (km1 & 2u) { acc |= y1 << off; }
-                has_x = (uint32_t)(acc >> 16);                                              // positions 16 back .. own, like the 32-bit form
-            } else {
-                has_x = smear_up(rbits[w], km1);
-            }
+            if (DEEP) has_x = (uint32_t)(smear<true>(rb64, km1) >> 16);                      // positions 16 back .. own, like the 32-bit form; k - 1 = 18, 20
+            else has_x = smear<false>(rbits[w], km1);
             const uint32_t hasmask = ~(has_x >> 16) & ((1u << cnt) - 1u);
             const uint32_t fprev = revpairs32(prev), fcur = revpairs32(cur[w]);
             const unsigned long long fwd64 = ((unsigned long long)fprev << 32) | fcur;      // first base highest
@@ -393,20 +373,6 @@ __global__ __launch_bounds__(NT, 4) void k_walk_sort(const uint32_t *__restrict_
 // of the level-1 buckets (n_tally = B1).  Room for a bucket of estimated size e: e + e/8 + slack (stride 1: the
 // tally itself, which is exact or an over-count).  With final tallies both levels are laid out: final bucket
 // starts + write cursors + limits, and the level-1 buckets from the sums of their final buckets' estimates.
-__device__ __forceinline__ uint32_t block_excl_scan_1024(uint32_t v, uint32_t *wsum, uint32_t &total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-    __syncthreads();                                       // wsum may still be read from an earlier call
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-    for (int i = 0; i < 16; i++) { if (i < w) pre += wsum[i]; total += wsum[i]; }
-    return pre + inc - v;
-}
-
 // room for a bucket whose sampled tally is h: the scaled estimate + 12.5 % + slack (stride 1: h itself, exact or an over-count)
 __device__ __forceinline__ uint32_t room_for(unsigned long long h, double scale, uint32_t stride, uint32_t slack) {
     if (stride == 1) return (uint32_t)h;
@@ -483,7 +449,7 @@ __global__ __launch_bounds__(1024) void k_provision(const uint32_t *__restrict__
     uint32_t room1 = 0;
     if (threadIdx.x < B1) room1 = (room_for(sum1[threadIdx.x], scale, stride, 4096u) + 3u) & ~3u;   // 16-byte aligned starts
     uint32_t total1;
-    const uint32_t base = block_excl_scan_1024(room1, wsum, total1);
+    const uint32_t base = wg_excl_sum<16, true>(room1, wsum, total1);     // wsum: read above when there are two levels
     if (threadIdx.x < B1) { bucket_base[threadIdx.x] = base; cursor1[threadIdx.x] = base; cap_end[threadIdx.x] = base + room1; }
     if (threadIdx.x == 0) {
         bucket_base[B1] = total1;
@@ -510,7 +476,7 @@ __global__ __launch_bounds__(1024) void k_level1_finish(const uint32_t *__restri
             g2 = (uint32_t)(((uint64_t)size2 + pl.R2 - 1) / pl.R2);
         }
         uint32_t sum_g2;
-        const uint32_t ps = block_excl_scan_1024(g2, wsum, sum_g2);
+        const uint32_t ps = wg_excl_sum<16, true>(g2, wsum, sum_g2);   // SH_BUSY only to keep the generated code: wsum is free here, the barrier in front is not needed
         if (d < B1) wg2_start[d] = ps;
         if (d == 0) wg2_start[B1] = sum_g2;
     }

@@ -19,25 +19,13 @@
 // kmer_fuse.hip assembles the k-mers from the slots with no dependence between its threads.
 #include "fasta_fsm.h"
 #include "kmer_walk.h"
+#include "kmer_window.h"
 #include "pk_kernels.h"
+#include "wg_scan.h"
 
 namespace pk {
 
 constexpr int SQUEEZE_WAVES = 4;   // waves per SIMD the squeeze kernel is compiled for (3, 5, 6 and 8 all give 0.31 ms instead of 0.21)
-
-// exclusive scan of a small count over the 256 lanes of the workgroup (sh: 4 words; one barrier)
-__device__ __forceinline__ uint32_t wg_excl_scan_u32(uint32_t v, uint32_t *sh, uint32_t &total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (int i = 0; i < w; i++) pre += sh[i];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    return pre + inc - v;
-}
 
 // OR `n_bits` bits of (lo, hi) into the LDS bit array `dst` at bit offset `at`
 __device__ __forceinline__ void lds_or_bits(uint32_t *dst, uint32_t at, unsigned long long lo, unsigned long long hi, uint32_t n_bits) {
@@ -51,30 +39,6 @@ __device__ __forceinline__ void lds_or_bits(uint32_t *dst, uint32_t at, unsigned
         carry = sh ? (x[i] >> (32u - sh)) : 0u;
         if (v) atomicOr(&dst[w0 + i], v);                    // words past the lane's bits are all zero and skipped
     }
-}
-
-// The valid windows that END at each of a piece's nv pushed-together bases (bit j: one ends at base j), given the bases'
-// restart bits as the piece alone knows them (F; base 0's is completed here: the run was already broken when the piece
-// began) and the length of the run carried in: no restart among the k-1 positions behind the window's first base, and --
-// where no restart precedes -- enough bases carried in (indexer.py:144).
-__device__ __forceinline__ unsigned long long window_ends(unsigned long long &F, uint32_t nv, uint32_t run, uint32_t km1) {
-    if (run == 0u && nv) F |= 1ull;
-    const unsigned long long keep = nv >= 64u ? ~0ull : ((1ull << nv) - 1ull);
-    unsigned long long X = 0;
-    {
-        const unsigned long long y1 = F | (F << 1), y2 = y1 | (y1 << 2), y3 = y2 | (y2 << 4), y4 = y3 | (y3 << 8);
-        uint32_t off = 0;                                                 // k - 1 <= 20 copies: 16 + 4 at most
-        if (km1 & 16u) { X |= y4; off = 16; }
-        if (km1 & 8u) { X |= y3 << off; off += 8; }
-        if (km1 & 4u) { X |= y2 << off; off += 4; }
-        if (km1 & 2u) { X |= y1 << off; off += 2; }
-        if (km1 & 1u) { X |= F << off; }
-    }
-    const uint32_t short_by = run >= km1 ? 0u : km1 - run;                // leading positions the carried run cannot complete
-    const unsigned long long lead = short_by >= 64u ? ~0ull : ((1ull << short_by) - 1ull);
-    // a restart inside the piece takes over from the carried run: positions at or above the first restart obey X only
-    const unsigned long long below_first = F ? ((F & (0ull - F)) - 1ull) : ~0ull;
-    return ~X & ~(lead & below_first) & keep;
 }
 
 // ------------------------------------------------------------------ clean pieces ----
@@ -285,9 +249,8 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
         // exact parser state at this lane's first byte: chunk state . lane prefix (both from the structure pass)
         const L2 chunk_st = chunk_l2_state[c];
         LaneState lst; lst.flags = me.ls_flags; lst.rec_tail = me.ls_rec_tail;
-        const L2 st2 = l2_compose(chunk_st, lane_state_l2(lst), km1);
-        const uint32_t ls_in = lane_state_ls(lst);
-        wk.begin(ls_in, st2, stream_off + base + (uint64_t)threadIdx.x * PIECE);
+        const LaneStart ln = lane_start(lst, chunk_st, km1);
+        wk.begin(ln.ls_in, ln.st, stream_off + base + (uint64_t)threadIdx.x * PIECE);
         uint8_t *piece = buf + threadIdx.x * PIECE;
         PieceBases pb;
         pb.clear();
@@ -296,7 +259,7 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
         // text byte by byte, which costs the same for one lane as for 64.  They are queued, and the queue is worked off 64
         // pieces per wave pass -- with a header every kilobase (read sets) that is one pass per workgroup instead of one
         // per wave.  A queued piece's result is left in the piece's own 64 bytes of the image.
-        const bool clean = !lane_state_dirty(lst) && !lane_state_header_piece(lst) && ls_in != LS_HEADER;   // the structure pass's definition: chunk_odd counts the rest
+        const bool clean = ln.clean;                       // chunk_odd counts the rest
         {
             PiecePack pk;
             pk.c_lo = ((unsigned long long)me.p0.y << 32) | me.p0.x; pk.c_hi = ((unsigned long long)me.p0.w << 32) | me.p0.z;
@@ -314,7 +277,8 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
                 const LaneState l2s = lane_state[(uint64_t)c * WG + pc];
                 SeqWalker wq;
                 wq.setup(k, recs, recs_cap, &racc);
-                wq.begin(lane_state_ls(l2s), l2_compose(chunk_st, lane_state_l2(l2s), km1), stream_off + base + (uint64_t)pc * PIECE);
+                const LaneStart lq = lane_start(l2s, chunk_st, km1);
+                wq.begin(lq.ls_in, lq.st, stream_off + base + (uint64_t)pc * PIECE);
                 // header pieces by masks (text in front of the first record is dropped: that piece takes the byte-wise walk)
                 const bool by_masks = work && lane_state_header_piece(l2s) && wq.rec != 0u;
                 const uint32_t nbq = (work && !by_masks) ? piece_len_of(pc, base, n_bytes) : 0u;
@@ -346,7 +310,7 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
         wk.flush_rec_wave();
         // where the lane's bases go in the chunk's slot: exclusive prefix of the counts over the workgroup
         uint32_t total;
-        const uint32_t at = wg_excl_scan_u32(pb.n, scan_sh, total);
+        const uint32_t at = wg_excl_sum<WG / 64, false>(pb.n, scan_sh, total);   // scan_sh: last read before the barriers of the chunk before
         lds_or_bits(slot_codes, 2u * at, pb.code_lo, pb.code_hi, 2u * pb.n);
         lds_or_bits(slot_rst, at, pb.restart, 0ull, pb.n);
         __syncthreads();

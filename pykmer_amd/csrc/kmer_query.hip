@@ -34,21 +34,15 @@
 // hold an earlier text); the host grows the record and accumulator arrays and repeats the feed's squeeze and these kernels.
 #include <type_traits>
 
+#include "kmer_window.h"
 #include "pk_kernels.h"
+#include "wg_scan.h"
 
 namespace pk {
 
 constexpr int QNT = 1024;                 // threads per slot, 16 bases each
 constexpr uint32_t QACC_RECS = 128;       // rows (records or bins) of a slot tallied in LDS; later ones (reads below ~128 bytes of
                                           // text, bins of fewer than 128 windows) go to HBM directly
-
-// OR of x << s for s = 0 .. n-1 (n <= 16)
-__device__ __forceinline__ uint32_t q_smear(uint32_t x, uint32_t n) {
-    if (n == 0u) return 0u;
-    uint32_t y = x, have = 1u;                               // y covers s < have
-    while (2u * have <= n) { y |= y << have; have *= 2u; }
-    return y | (y << (n - have));                            // n - have < have: the two stretches overlap or touch
-}
 
 // What thread t of a slot works on: its 16 bases, the 16 before them, and which of its bases end a valid window.
 struct QLane { uint32_t cur, prev, ok; };
@@ -74,23 +68,8 @@ __device__ __forceinline__ QLane q_lane(const uint32_t *__restrict__ codes, cons
         q.prev = cw[t - 1u];
         r = (t & 1u) ? rword : ((rword << 16) | (rw[(t >> 1) - 1u] >> 16));
     }
-    q.ok = ~(q_smear(r, km1) >> 16) & ((1u << cnt) - 1u);
+    q.ok = ~(smear<false>(r, km1) >> 16) & ((1u << cnt) - 1u);
     return q;
-}
-
-// exclusive prefix of v over the workgroup (QNT threads) and its total; wsum: 16 words of LDS
-__device__ __forceinline__ uint32_t q_block_scan(uint32_t v, uint32_t *wsum, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    __syncthreads();                                         // wsum may still be read from an earlier call
-    if (lane == 63u) wsum[w] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-    for (uint32_t i = 0; i < QNT / 64; i++) { if (i < w) pre += wsum[i]; total += wsum[i]; }
-    return pre + inc - v;
 }
 
 __global__ __launch_bounds__(QNT) void k_query_count(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
@@ -101,7 +80,7 @@ __global__ __launch_bounds__(QNT) void k_query_count(const uint32_t *__restrict_
     const uint32_t c = blockIdx.x;
     const QLane q = q_lane(codes, restarts, n_bases[c], chunk_l2_state, c, threadIdx.x, k);
     uint32_t total;
-    q_block_scan((uint32_t)__builtin_popcount(q.ok), wsum, total);
+    wg_excl_sum<QNT / 64, true>((uint32_t)__builtin_popcount(q.ok), wsum, total);   // SH_BUSY only to keep the generated code: wsum is free here, the barrier in front is not needed
     if (threadIdx.x == 0) slot_count[c] = total;
 }
 
@@ -116,27 +95,15 @@ __global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__
                                                     const uint32_t *__restrict__ flags) {
     __shared__ unsigned long long wsum[QNT / 64];
     if (flags[0]) return;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    // inclusive scan of v over the workgroup; total: the sum of all
-    auto incl_scan = [&](unsigned long long v, unsigned long long &total) -> unsigned long long {
-        unsigned long long inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-        __syncthreads();
-        if (lane == 63u) wsum[w] = inc;
-        __syncthreads();
-        unsigned long long pre = 0;
-        total = 0;
-        for (uint32_t i = 0; i < QNT / 64; i++) { if (i < w) pre += wsum[i]; total += wsum[i]; }
-        return pre + inc;
-    };
+    // exclusive prefix of v over the workgroup; wsum may still be read by the round before
+    auto excl_sum = [&](unsigned long long v, unsigned long long &total) { return wg_excl_sum<QNT / 64, true>(v, wsum, total); };
     unsigned long long run = windows_before;
     for (uint32_t c0 = 0; c0 < n_chunks; c0 += QNT) {
         const uint32_t c = c0 + threadIdx.x;
         const unsigned long long v = c < n_chunks ? slot_count[c] : 0ull;
         unsigned long long total;
-        const unsigned long long inc = incl_scan(v, total);
-        if (c < n_chunks) slot_first[c] = run + inc - v;
+        const unsigned long long ex = excl_sum(v, total);
+        if (c < n_chunks) slot_first[c] = run + ex;
         run += total;
     }
     const unsigned long long n_recs = carry->n_recs;
@@ -156,12 +123,13 @@ __global__ __launch_bounds__(QNT) void k_query_scan(const uint32_t *__restrict__
         const unsigned long long r = b + threadIdx.x;
         const unsigned long long v = r < n_recs ? recs[r - 1ull].n_valid : 0ull;
         unsigned long long total;
-        const unsigned long long inc = incl_scan(v, total);
-        if (r < n_recs) P[r] = run + inc;
+        const unsigned long long ex = excl_sum(v, total);
+        if (r < n_recs) P[r] = run + ex + v;                 // inclusive: the windows of the records up to and with r - 1
         run += total;
         if constexpr (BINS) {
-            const unsigned long long inc_b = incl_scan(v ? (v - 1ull) / W + 1ull : 0ull, total);   // ceil(v / W)
-            if (r < n_recs) Bf[r] = run_b + inc_b;
+            const unsigned long long bins = v ? (v - 1ull) / W + 1ull : 0ull;                      // ceil(v / W)
+            const unsigned long long ex_b = excl_sum(bins, total);
+            if (r < n_recs) Bf[r] = run_b + ex_b + bins;
             run_b += total;
         }
     }
@@ -195,7 +163,7 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
     if (nb == 0u) return;
     const QLane q = q_lane(codes, restarts, nb, chunk_l2_state, c, threadIdx.x, k);
     uint32_t total;
-    const uint32_t off = q_block_scan((uint32_t)__builtin_popcount(q.ok), wsum, total);
+    const uint32_t off = wg_excl_sum<QNT / 64, true>((uint32_t)__builtin_popcount(q.ok), wsum, total);   // SH_BUSY only to keep the generated code: wsum is free here, the barrier in front is not needed
     if (total == 0u) return;                                 // uniform
     const unsigned long long first = slot_first[c];
     if (threadIdx.x == 0) {

@@ -379,6 +379,22 @@ def test_full_size_table(gpu):
         counts.free()
 
 
+def test_scan_second_round_of_one_workgroup(gpu):
+    """1025 workgroups: k_extract_scan takes their counts 1024 at a time, the second round holds one, and its rank hangs on
+    the first round's total.  The last workgroup is 17 addresses long; addresses on both sides of the seam are selected."""
+    wg = 4 * extract_ref.TILE                                # addresses per workgroup
+    n = 1024 * wg + 17
+    rng = np.random.default_rng(1025)
+    a, b = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    at = rng.integers(0, n, 40_000)
+    a[at] = rng.integers(1, 256, at.size)
+    a[[0, 1024 * wg - 1, 1024 * wg, n - 1]] = 100
+    b[rng.integers(1, 1024 * wg - 1, 20_000)] = 1
+    want_addr, _ = extract_ref.expected([a], [b], 2, 200)
+    assert want_addr[0] == 0 and (want_addr >= 1024 * wg).sum() >= 2 and want_addr[-1] == n - 1 and 10_000 < want_addr.size < 40_000
+    _check([a], [b], 2, 200)
+
+
 # ------------------------------------------------------------------ 11. CLI ------------------------
 def _cli(*argv, cwd, ok=True):
     r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)

@@ -13,6 +13,7 @@ import pytest
 
 import oracle
 import query_coords_inputs as qci
+import query_bins_ref
 import query_coords_ref
 import query_ref
 import synth
@@ -206,6 +207,38 @@ def test_feeds(gpu, W):
             cut = _coords(q, text, W, cuts=some)
             for key in ("bin_start", "bin_end", "bin_hits", "bin_depth", "bin_first"):
                 assert np.array_equal(cut[key], whole[key]), (key, some)
+
+
+def test_more_than_1024_chunks_in_one_feed(gpu):
+    """1025 chunks in one feed: k_coords_scan takes the chunks' pairs 1024 at a time, and the position at the first byte of
+    chunk 1024 hangs on the first round's total.  One record without a gap runs across chunks 0 .. 1024;
+    short records with a blank, an N and no window follow it in the last chunk.  The byte-wise yardstick would take
+    a minute for 17 MB of text: it walks the text from the second header on (positions begin anew with every record), and
+    the windows of the long record start at 0, 1, 2, ... -- what check_consequences(gap_free=True) states."""
+    k = 5
+    head = b">long\n"
+    n_long = ((1024 * CHUNK + 3000 - len(head)) // (qci.WIDTH + 1)) * qci.WIDTH
+    long_rec = query_ref._record(b"long", query_ref._bases(np.random.default_rng(905), n_long), qci.WIDTH)
+    tail = b">t1\nACGTTGCAAC GTACGGTCAT\nACGNTTGACCA\n>t2\nACG\n>t3\n\n>t4\nTTGACGGTCATTGACCATG\n"
+    text = long_rec + tail
+    assert 1024 * CHUNK < len(long_rec) and -(-len(text) // CHUNK) == 1025      # the scan's second round: one chunk
+    seq_len_t, n_win_t, starts_t = query_coords_ref.window_starts(tail, k)
+    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+        q.set_tables(dev.ptrs, 1, 255)
+        for W in (4099, 10 ** 9):
+            want = query_bins_ref.expected(text, k, _tables(k), 1, 255, W)
+            m = want["n_valid"]
+            assert int(m[0]) == n_long - k + 1 and np.array_equal(m[1:], n_win_t) and np.array_equal(want["seq_len"][1:], seq_len_t)
+            starts = np.concatenate([np.arange(int(m[0]), dtype=np.uint64), starts_t])
+            want["bin_start"], want["bin_end"] = query_coords_ref.bin_coords(m, starts, k, W)
+            query_coords_ref.check_consequences(want, k, W)
+            assert int(want["bin_end"][want["row_record"] == 0][-1]) == n_long
+            q.set_bins(W)
+            q.set_coords(True)
+            _feed(q, text)
+            assert q.timings()["feeds"] == 1, "the text was meant to be one feed of 1025 chunks"
+            q.reset()
+            _same(_coords(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 6. FASTQ -----------------------
