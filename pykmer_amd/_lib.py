@@ -140,6 +140,11 @@ def _hist_out():
     return np.zeros(256, dtype=np.uint64)
 
 
+def _ptr_array(dev_ptrs):
+    """A C array of the device pointers (of one element at least: ctypes gives an empty array no address to pass)."""
+    return (ctypes.c_void_p * max(1, len(dev_ptrs)))(*dev_ptrs)
+
+
 class DeviceBuffer:
     """n bytes of HBM on one device (pk_dev_*)."""
 
@@ -175,15 +180,22 @@ class Indexer:
     """One 4^k count table resident in HBM on one device (pk_indexer_*).  fmt: what the feeds hold, "fasta" or "fastq"
     (pk_indexer_set_format; it stays across resets)."""
 
+    TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "partition_s", "bucket_s", "walk_sort_s", "relayouts",
+               "buckets_recounted")
+    COUNTERS = ("feeds", "relayouts", "buckets_recounted")   # of TIMINGS: integers, not seconds
+
     def __init__(self, k: int, device: int = 0, slice_index: int = 0, n_slices: int = 1, fmt: str = "fasta"):
         if fmt not in FORMATS:
             raise ValueError(f"unknown input format {fmt!r}: expected one of {sorted(FORMATS)}")
         self._h = ctypes.c_void_p()
         self.k, self.device, self.slice_index, self.n_slices, self.fmt = k, device, slice_index, n_slices, fmt
         self.table_bytes = 4 ** k // n_slices
-        _check(load().pk_indexer_create_slice(ctypes.byref(self._h), k, device, slice_index, n_slices))
+        self._create()
         if fmt != "fasta":
             _check(load().pk_indexer_set_format(self._h, FORMATS[fmt]))
+
+    def _create(self):
+        _check(load().pk_indexer_create_slice(ctypes.byref(self._h), self.k, self.device, self.slice_index, self.n_slices))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -245,34 +257,33 @@ class Indexer:
         _check(load().pk_indexer_fastq_stats(self._h, out.ctypes.data))
         return {"records": int(out[0]), "lines": int(out[1]), "bytes_fed": int(out[2]), "bytes_emitted": int(out[3])}
 
-    def timings(self) -> dict:
+    def _timings_raw(self) -> np.ndarray:
         t = np.zeros(10, dtype=np.float64)
         _check(load().pk_indexer_timings(self._h, t.ctypes.data))
-        return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]),
-                "partition_s": t[5], "bucket_s": t[6], "walk_sort_s": t[7], "relayouts": int(t[8]), "buckets_recounted": int(t[9])}
+        return t
+
+    def timings(self) -> dict:
+        """pk_indexer_timings: the first doubles of the library's ten, under the names of this class's TIMINGS."""
+        return {name: int(v) if name in self.COUNTERS else v for name, v in zip(self.TIMINGS, self._timings_raw())}
 
 
 class QueryIndexer(Indexer):
     """An indexer in query mode (pk_query_*): it parses its feeds like an Indexer, holds no table, and tallies per record how
     many windows hit each of N device-resident 4^k-byte tables.  feed / feed_device / finish / records / reset as Indexer."""
 
+    TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "lookup_s", "coords_s")
+
     def __init__(self, k: int, device: int = 0, fmt: str = "fasta"):
-        if fmt not in FORMATS:
-            raise ValueError(f"unknown input format {fmt!r}: expected one of {sorted(FORMATS)}")
-        self._h = ctypes.c_void_p()
-        self.k, self.device, self.slice_index, self.n_slices, self.fmt = k, device, 0, 1, fmt
-        self.table_bytes = 4 ** k if k > 0 else 0
         self.n_tables = 0
-        _check(load().pk_query_create(ctypes.byref(self._h), k, device))
-        if fmt != "fasta":
-            _check(load().pk_indexer_set_format(self._h, FORMATS[fmt]))
+        super().__init__(k, device, fmt=fmt)
+
+    def _create(self):
+        _check(load().pk_query_create(ctypes.byref(self._h), self.k, self.device))
 
     def set_tables(self, dev_ptrs, min_count: int = 1, max_count: int = 255):
         """pk_query_set_tables: device pointers of the 4^k-byte tables (the caller keeps them alive through the feeds)."""
-        N = len(dev_ptrs)
-        ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
-        _check(load().pk_query_set_tables(self._h, ptrs, N, int(min_count), int(max_count)))
-        self.n_tables = N
+        _check(load().pk_query_set_tables(self._h, _ptr_array(dev_ptrs), len(dev_ptrs), int(min_count), int(max_count)))
+        self.n_tables = len(dev_ptrs)
 
     def results(self, n_records: int):
         """pk_query_results after finish(): (hits, depth), each (n_records, N) uint64."""
@@ -288,12 +299,15 @@ class QueryIndexer(Indexer):
             raise ValueError(f"bin_windows must be an unsigned 64-bit integer, got {bin_windows}")
         _check(load().pk_query_set_bins(self._h, int(bin_windows)))
 
+    def _bin_count(self) -> int:
+        nb = ctypes.c_uint64(0)
+        _check(load().pk_query_bin_count(self._h, ctypes.byref(nb)))
+        return int(nb.value)
+
     def bin_results(self, n_records: int):
         """pk_query_bin_results after finish(): (hits, depth, bin_first); hits and depth (B, N) uint64, one row per bin,
         bin_first (n_records + 1,) uint64 with bin_first[-1] = B."""
-        nb = ctypes.c_uint64(0)
-        _check(load().pk_query_bin_count(self._h, ctypes.byref(nb)))
-        B = int(nb.value)
+        B = self._bin_count()
         hits = np.zeros((max(B, 1), max(self.n_tables, 1)), dtype=np.uint64)
         depth = np.zeros_like(hits)
         bin_first = np.zeros(n_records + 1, dtype=np.uint64)
@@ -308,19 +322,11 @@ class QueryIndexer(Indexer):
     def bin_coords(self):
         """pk_query_bin_coords after finish(): (bin_start, bin_end), each (B,) uint64 in row order: the position of the first
         base of the row's first window and one past the last base of its last."""
-        nb = ctypes.c_uint64(0)
-        _check(load().pk_query_bin_count(self._h, ctypes.byref(nb)))
-        B = int(nb.value)
+        B = self._bin_count()
         start = np.zeros(max(B, 1), dtype=np.uint64)
         end = np.zeros_like(start)
         _check(load().pk_query_bin_coords(self._h, start.ctypes.data, end.ctypes.data, B))
         return start[:B], end[:B]
-
-    def timings(self) -> dict:
-        t = np.zeros(10, dtype=np.float64)
-        _check(load().pk_indexer_timings(self._h, t.ctypes.data))
-        return {"scan_s": t[0], "squeeze_s": t[1], "finalize_s": t[2], "zero_s": t[3], "feeds": int(t[4]), "lookup_s": t[5],
-                "coords_s": t[6]}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):
@@ -371,7 +377,7 @@ def gram_device_partial(dev_ptrs, n_slice: int, min_count: int = 1, max_count: i
                         dev_pair_out: int = None):
     """pk_gram_device_partial on device-resident slices -> (pair[N,N] uint64, kernel_seconds)."""
     N = len(dev_ptrs)
-    ptrs = (ctypes.c_void_p * N)(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     pair = np.zeros((N, N), dtype=np.uint64)
     secs = ctypes.c_double(0)
     _check(load().pk_gram_device_partial(ptrs, N, n_slice, min_count, max_count, pair.ctypes.data,
@@ -384,7 +390,7 @@ def gram_device_accumulate(dev_ptrs, n_slice: int, dev_pair_accum: int, min_coun
                            device: int = 0) -> float:
     """pk_gram_device_accumulate: adds one slice's tallies to an N x N u64 accumulator in HBM; returns kernel seconds."""
     N = len(dev_ptrs)
-    ptrs = (ctypes.c_void_p * N)(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     secs = ctypes.c_double(0)
     _check(load().pk_gram_device_accumulate(ptrs, N, n_slice, min_count, max_count, ctypes.c_void_p(dev_pair_accum), device,
                                             ctypes.byref(secs)))
@@ -395,7 +401,7 @@ def gram_device_accumulate_windows(dev_ptrs, n_slice: int, dev_pair_accum: int, 
     """pk_gram_device_accumulate_windows: adds one slice's tallies for every (min_count, max_count) of `windows` to a
     W x N x N u64 accumulator in HBM -- one pass over the slices per group of windows; returns kernel seconds."""
     N, W = len(dev_ptrs), len(windows)
-    ptrs = (ctypes.c_void_p * N)(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     mins = (ctypes.c_int * W)(*[int(w[0]) for w in windows])
     maxs = (ctypes.c_int * W)(*[int(w[1]) for w in windows])
     secs = ctypes.c_double(0)
@@ -413,7 +419,7 @@ def spectrum_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: i
     """pk_spectrum_device_accumulate: adds the value histograms and joint count spectra of N device-resident slices to a
     spectrum_words(N) u64 accumulator in HBM; returns kernel seconds."""
     N = len(dev_ptrs)
-    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     secs = ctypes.c_double(0)
     _check(load().pk_spectrum_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
     return secs.value
@@ -428,7 +434,7 @@ def occgram_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: in
     """pk_occgram_device_accumulate: adds the occupancy-stratified Gram products of N device-resident slices to an
     occgram_words(N) u64 accumulator in HBM; returns kernel seconds."""
     N = len(dev_ptrs)
-    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     secs = ctypes.c_double(0)
     _check(load().pk_occgram_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
     return secs.value
@@ -440,7 +446,7 @@ def extract_device(dev_ptrs, n_present: int, n_slice: int, first_addr: int, min_
     (n_selected, fits, kernel_seconds).  `fits`: the addresses and count rows were written to the two device arrays
     (n_selected <= cap); with cap = 0 and no arrays the call only counts and `fits` is False unless nothing is selected."""
     N = len(dev_ptrs)
-    ptrs = (ctypes.c_void_p * max(1, N))(*dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
     count, secs = ctypes.c_uint64(0), ctypes.c_double(0)
     rc = load().pk_extract_device(ptrs, int(n_present), N - int(n_present), int(n_slice), int(first_addr), int(min_count), int(max_count),
                                   int(min_present), int(max_absent), ctypes.c_void_p(dev_addr_out) if dev_addr_out else None,

@@ -10,12 +10,11 @@ The result is the selected addresses in ascending order and, with each, the P ra
 inside the window or not.  P = 1 and A = 0 is a plain windowed dump of one table.  The reference has no such tool (its
 README stops at the distance matrix); no table is written or changed.
 
-The tables are staged in HBM slice by slice as the merger stages them (merger._staged_pieces); one streaming pass per piece
+The tables are staged in HBM slice by slice as the merger stages them (staging.staged_pieces); one streaming pass per piece
 (pk_extract_device) compacts the selected addresses and their count rows in HBM, and pk_extract_text turns the addresses
 into letters there.  One device (PK_DEVICE).
 """
 import argparse
-import json
 import os
 import sys
 from pathlib import Path
@@ -23,14 +22,14 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, merger
-from .header import Header
+from . import _lib, staging
 from .indexer import _mark
-from .merger import DEFAULT_THREADS, _Encoder
-from .query import load_header, _name_of
+from .merger import DEFAULT_THREADS
+from .output import atomic_write, write_json
+from .query import load_header
+from .tables import MAX_KMER_LEN, common_kmer_len, lean_headers, name_of as _name_of, table_entry   # noqa: F401
 
 MAX_TABLES = 128                    # P + A: what one pk_extract_device call takes
-MAX_KMER_LEN = 17                   # one unsliced 4^k-byte table per sample
 PIECE_ALIGN = 2048                  # addresses: what the cuts of a piece are multiples of (and what always fits the output)
 INITIAL_ROWS = 1 << 22              # output rows the first call has room for (fewer if the output budget holds fewer)
 OUTPUT_SHARE = 8                    # the output arrays get 1 / OUTPUT_SHARE of the HBM budget, the staged slices the rest
@@ -75,17 +74,7 @@ def validate(present: Sequence, absent: Sequence, min_count: int = 1, max_count:
     if not 0 <= int(max_absent) <= A:
         raise ValueError(f"max_absent must lie in 0..{A} (the absent tables), got {max_absent}")
     tables = list(present) + list(absent)
-    kmer_len = None
-    for t in tables:
-        k = _kmer_len_of(t)
-        if k < 1 or k % 2 == 0:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} is not positive and odd")
-        if k > MAX_KMER_LEN:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} is beyond the extract path (at most {MAX_KMER_LEN}: one unsliced table)")
-        if kmer_len is None:
-            kmer_len = k
-        elif k != kmer_len:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} differs from the {kmer_len} of {_name_of(tables[0])}")
+    kmer_len = common_kmer_len(tables, "extract", _kmer_len_of)
     files = [f for f in map(_file_of, tables) if f]
     for f in files:
         if files.count(f) > 1:
@@ -160,6 +149,12 @@ def _extract_range(call, ptrs, off: int, n: int, first_addr: int, state: dict, p
     parts.append(res)
 
 
+def stage_pieces(tables: Sequence, lo: int, hi: int, device: int, threads: int, reserve: int, budget: int):
+    """The staged pieces (ptrs, a, b) of [lo, hi), in ascending order: N slices beside each other in `budget` bytes less the
+    `reserve` of the output arrays (staging.piece_cuts), staged by staging.staged_pieces."""
+    return staging.staged_pieces(tables, staging.piece_cuts(tables, lo, hi, len(tables), device, reserve, budget), device, threads)
+
+
 def extract_kmers(present: Sequence, absent: Sequence = (), min_count: int = 1, max_count: int = 255, min_present: int = None,
                   max_absent: int = 0, device: int = 0, hbm_budget: int = None, threads: int = DEFAULT_THREADS, text: bool = False,
                   initial_rows: int = INITIAL_ROWS, stage=None, call=None) -> dict:
@@ -171,27 +166,28 @@ def extract_kmers(present: Sequence, absent: Sequence = (), min_count: int = 1, 
     arrays: 1 / OUTPUT_SHARE of it is the output's (never less than PIECE_ALIGN rows), the slices are cut to fit the rest.
     A piece that selects more rows than the output holds is taken in halves.
     `stage(tables, lo, hi, device, threads, reserve, budget)` -> iterable of (ptrs, a, b) and `call` (see DeviceCall)
-    default to merger._staged_pieces and a DeviceCall (the CPU-only tests substitute both)."""
+    default to stage_pieces and a DeviceCall (the CPU-only tests substitute both)."""
     present = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in present]
     absent = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in absent]
     kmer_len, min_present = validate(present, absent, min_count, max_count, min_present, max_absent)
     tables, P = present + absent, len(present)
     row_bytes = 8 + P + (kmer_len + 1 if text else 0)
-    budget = int(hbm_budget or 0) or merger.hbm_budget(device)
+    budget = staging.hbm_budget(device, hbm_budget)
     out_budget = max(PIECE_ALIGN * row_bytes, budget // OUTPUT_SHARE)
     state = {"max_rows": out_budget // row_bytes, "calls": 0}
     state["cap"] = max(1, min(state["max_rows"], int(initial_rows)))
     own = None
     if call is None:
         call = own = DeviceCall(P, kmer_len, min_count, max_count, min_present, int(max_absent), device=device, text=text)
-    stage = stage or merger._staged_pieces
+    pieces = (stage or stage_pieces)(tables, 0, 4 ** kmer_len, device, threads, out_budget, budget)
     parts, n_pieces = [], 0
     try:
-        for ptrs, a, b in stage(tables, 0, 4 ** kmer_len, device, threads, out_budget, budget):
+        for ptrs, a, b in pieces:
             _mark(f"addresses {a}..{b - 1} staged")
             n_pieces += 1
             _extract_range(call, ptrs, 0, b - a, a, state, parts)
     finally:
+        getattr(pieces, "close", lambda: None)()             # a generator frees its slice buffers now, not when it is collected
         if own is not None:
             own.free()
     addr = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, dtype=np.uint64)
@@ -219,24 +215,14 @@ def write_kmx(project_name: str, result: dict, data: list) -> None:
     assert counts.shape == (addr.size, int(result["n_present"])) and len(data) == int(result["n_present"]) + int(result["n_absent"])
     output = {"project_name": project_name, "n_selected": int(addr.size), "data": data}
     output.update({key: int(result[key]) for key in SCALARS})
-    print(f"saving {meta}")
-    tmp = Path(f"{meta}.tmp")
-    with tmp.open(mode="wt") as fhd:
-        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    tmp.rename(meta)
+    write_json(meta, output)
     if result.get("text") is not None:
         lines = np.ascontiguousarray(result["text"], dtype=np.uint8)
         assert lines.shape == (addr.size, int(result["kmer_len"]) + 1)
-        print(f"saving {txt}")
-        tmp = Path(f"{txt}.tmp")
-        with tmp.open(mode="wb") as fhd:
+        with atomic_write(txt, "wb") as fhd:
             lines.tofile(fhd)
-        tmp.rename(txt)
-    print(f"saving {kmx}")
-    tmp = Path(f"{kmx}.tmp")
-    with tmp.open(mode="wb") as fhd:
+    with atomic_write(kmx, "wb") as fhd:
         np.savez_compressed(fhd, addr=addr, counts=counts, **{key: np.int64(result[key]) for key in SCALARS})
-    tmp.rename(kmx)
 
 
 def extract(project_name: str, present: List[Path], absent: List[Path] = (), min_count: int = 1, max_count: int = 255, min_present: int = None,
@@ -245,22 +231,16 @@ def extract(project_name: str, present: List[Path], absent: List[Path] = (), min
     for f in kmx_paths(project_name):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
-    data, headers = [], []
+    data = []
     for role, kins in (("present", present), ("absent", absent)):
         for kin in kins:
-            print(f"verifying {kin}")
-            header = load_header(kin, device)
-            name = str(kin)
-            desc = Path((name[:-(len(Header.COMP_EXT) + 1)] if name.endswith("." + Header.COMP_EXT) else name) + "." + Header.DESC_EXT)
-            headers.append(header)
-            data.append({"pos": len(data), "role": role, "index_file": Path(kin), "description_file": desc, "header": header})
-    n_present = len(list(present))
+            data.append(table_entry(len(data), kin, lambda kin: load_header(kin, device), role=role))
+    headers, n_present = [v["header"] for v in data], len(list(present))
     validate(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, project_name=project_name)
     _mark("tables verified")
     result = extract_kmers(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, device=device,
                            hbm_budget=hbm_budget, threads=threads, text=kmers)
-    for v in data:
-        v["header"] = v["header"].to_dict(lean=True)
+    lean_headers(data)
     write_kmx(project_name, result, data)
     _mark("files renamed")
     return result

@@ -32,6 +32,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib
+from .output import atomic_write, write_json
 
 
 def pair_list(N: int) -> np.ndarray:
@@ -111,35 +112,24 @@ def write_matrix(path, m: np.ndarray, ids: List[str]) -> None:
     never over an existing file."""
     path = Path(path)
     assert not path.exists(), f"output file ({path}) already exists. not overwriting."
-    tmp = Path(f"{path}.tmp")
-    print(f"saving {path}")
-    with tmp.open("wt") as fh:
+    with atomic_write(path, "wt") as fh:
         fh.write("\t" + "\t".join(ids) + "\n")
         for name, row in zip(ids, m):
             fh.write(name + "\t" + "\t".join("%.17g" % float(x) for x in row) + "\n")
-    tmp.rename(path)
 
 
 def save(project_name: str, occ_hist, lin, gram, kmer_len: int, data_size: int, data) -> Tuple[Path, Path]:
     """Writes `<project>.kmo` and `.kmo.json` (each through `.tmp` + rename; neither overwrites an existing file)."""
-    from .merger import _Encoder
     kmo, kmo_json = kmo_paths(project_name)[:2]
     for f in (kmo, kmo_json):
         assert not f.exists(), f"kwip output file ({f}) already exists. not overwriting."
     N = lin.shape[0]
     meta = {"project_name": project_name, "kmer_len": int(kmer_len), "data_size": int(data_size), "data": data}
-    tmp = Path(f"{kmo_json}.tmp")
-    print(f"saving {kmo_json}")
-    with tmp.open(mode="wt") as fhd:
-        json.dump(meta, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    tmp.rename(kmo_json)
-    tmp = Path(f"{kmo}.tmp")
-    print(f"saving {kmo}")
-    with tmp.open(mode="wb") as fhd:
+    write_json(kmo_json, meta)
+    with atomic_write(kmo, "wb") as fhd:
         np.savez_compressed(fhd, occ_hist=np.ascontiguousarray(occ_hist, dtype=np.uint64), lin=np.ascontiguousarray(lin, dtype=np.uint64),
                             gram=np.ascontiguousarray(gram, dtype=np.uint64), pairs=pair_list(N), kmer_len=np.int64(kmer_len),
                             data_size=np.int64(data_size))
-    tmp.rename(kmo)
     return kmo, kmo_json
 
 

@@ -10,38 +10,26 @@ mode by itself under a launcher that sets WORLD_SIZE / RANK / LOCAL_RANK (torchr
 starts the N ranks before anything touches a GPU.
 """
 import argparse
-import json
 import os
-import pathlib
 import sys
 from concurrent.futures import ThreadPoolExecutor
-from json import JSONEncoder
+from contextlib import closing
 from pathlib import Path
 from typing import List, Tuple
 
 import numpy as np
 
-from . import _lib, bgzf
+from . import _lib
 from .header import Header
-
-EXTS = ("." + Header.IND_EXT, "." + Header.IND_EXT + "." + Header.COMP_EXT, ".kma", ".kma." + Header.COMP_EXT)
+from .output import _Encoder, atomic_write, write_json             # noqa: F401  (_Encoder: imported from here by older callers)
+from .staging import ResidentTable, hbm_budget, piece_cuts, staged_pieces, sub_slices as _sub_slices   # noqa: F401
+from .tables import EXTS, description_file, lean_headers, table_entry
 
 DEFAULT_MIN_COUNT = Header.DEFAULT_MIN_COUNT
 DEFAULT_MAX_COUNT = Header.DEFAULT_MAX_COUNT
 DEFAULT_BUFFER_SIZE = Header.DEFAULT_BUFFER_SIZE
 DEFAULT_BLOCK_SIZE = Header.DEFAULT_BLOCK_SIZE
 DEFAULT_THREADS = 4
-
-
-class _Encoder(JSONEncoder):
-    """merger.py:23-30 patches JSONEncoder globally so Path objects serialise as strings; same effect, scoped."""
-
-    def default(self, obj):
-        if isinstance(obj, pathlib.PurePath):
-            return str(obj)
-        if hasattr(obj.__class__, "to_dict"):
-            return obj.to_dict()
-        return super().default(obj)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -85,111 +73,37 @@ def address_slice(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, min(n, lo + per)
 
 
-def hbm_budget(device: int, budget: int = None) -> int:
-    """The bytes of HBM a pass may fill with staged slices and what it keeps beside them: `budget` if given, else
-    PK_MERGE_HBM_BUDGET, else 80 % of the free HBM."""
-    return int(budget or 0) or int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or int(_lib.mem_info(device)[0] * 0.8)
-
-
-def _sub_slices(lo: int, hi: int, n_tables: int, device: int, reserve: int = 0, budget: int = None):
-    """[lo, hi) cut so that n_tables slices fit HBM beside each other (the reference streams pairs and takes
-    any N, merger.py:139-153; here a k=17 merge of 32 tables is 512 GiB).  Partials add, so the cuts are free.
-    PK_MERGE_HBM_BUDGET (bytes) overrides the 80 % of free HBM used by default (`budget` overrides both); `reserve` bytes
-    of it are kept for something else (a spectrum accumulator: 41 MB at N = 13, 4.2 GB at N = 128)."""
-    budget = hbm_budget(device, budget)
-    budget -= reserve
-    per_table = max(2048, (budget // max(1, n_tables) - 64) & ~2047)
-    return [(a, min(hi, a + per_table)) for a in range(lo, hi, per_table)]
-
-
-class ResidentTable:
-    """Addresses [first, first + n) of one 4^k-byte table that already lie in HBM on `device` (e.g. the table of an
-    indexer that has just finished: pk_indexer_table_device) -- takes a Header's place in pair_matrix / gpu_partial, which
-    then scan it where it is instead of staging it from a file."""
-
-    def __init__(self, ptr: int, n: int, data_size: int, device: int = 0, first: int = 0):
-        assert ptr % 16 == 0 and first % 32 == 0
-        self.ptr, self.n, self.data_size, self.device, self.first = int(ptr), int(n), int(data_size), device, int(first)
-
-    def device_slice(self, lo: int, hi: int) -> int:
-        assert self.first <= lo <= hi <= self.first + self.n, "address range outside the resident part of the table"
-        return self.ptr + (lo - self.first)
-
-
 def _flat_partial(headers: List[Header], lo: int, hi: int, device: int, threads: int, words: int, accumulate, staged_tables: int,
                   reserve: bool, acc_ptr: int = None, stats: dict = None):
-    """The one staging loop of every merge pass.  Addresses [lo, hi) of every table are staged in HBM on `device`
-    (sub-slice by sub-slice if they do not all fit; only bytes [lo, hi) of each file are read / inflated; ResidentTable
-    entries are scanned where they lie) and `accumulate(ptrs, n, acc_ptr, device=)` runs once per staged piece, adding to a
-    flat u64 accumulator of `words` words: at `acc_ptr` (zeroed by the caller -- the buffer an RCCL all-reduce then sums) or
-    in a buffer of this call, which is then returned as one flat u64 host array.  `accumulate` returns its kernel seconds,
-    which `stats["kernel_seconds"]` accumulates.
+    """The one accumulating loop of every merge pass.  Addresses [lo, hi) of every table are staged in HBM on `device`
+    (staging.staged_pieces: sub-slice by sub-slice if they do not all fit; only bytes [lo, hi) of each file are read /
+    inflated; ResidentTable entries are scanned where they lie) and `accumulate(ptrs, n, acc_ptr, device=)` runs once per
+    staged piece, adding to a flat u64 accumulator of `words` words: at `acc_ptr` (zeroed by the caller -- the buffer an RCCL
+    all-reduce then sums) or in a buffer of this call, which is then returned as one flat u64 host array.  `accumulate`
+    returns its kernel seconds, which `stats["kernel_seconds"]` accumulates.
 
-    `staged_tables` is how many table slices _sub_slices fits into the HBM budget beside each other: N, or more when the
+    `staged_tables` is how many table slices sub_slices fits into the HBM budget beside each other: N, or more when the
     pass keeps scratch per address of its own.  `reserve` keeps room in that budget for the accumulator this call allocates
     (41 MB of spectrum at N = 13, 4.2 GB at N = 128).  The pair tally passes False: its accumulator is a few KB and its cuts
     have never counted it; budgeting it would move the cuts, which is a change of behaviour of its own."""
-    N = len(headers)
-    resident = [hasattr(h, "device_slice") for h in headers]
-    assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one merge"
     own_bytes = words * 8 if acc_ptr is None else 0
-    cuts = [(lo, hi)] if all(resident) else _sub_slices(lo, hi, staged_tables, device, reserve=own_bytes if reserve else 0)
+    cuts = piece_cuts(headers, lo, hi, staged_tables, device, reserve=own_bytes if reserve else 0)
     own = None
     if acc_ptr is None:
-        own = _lib.DeviceBuffer(own_bytes, device)
-        own.zero()
-        acc_ptr = own.ptr
-    bufs = [] if all(resident) else [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
-    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
+        own = _lib.DeviceBuffer(own_bytes, device)           # before the slice buffers, which the first piece allocates
     try:
-        pool = ThreadPoolExecutor(max_workers=max(1, threads)) if bufs else None
-        try:
-            for a, b in cuts:
-                if bufs:
-                    # read / inflate (`threads` tables at a time, each .kin.bgz on its share of the native inflate threads),
-                    # upload as each one lands
-                    list(pool.map(lambda i: bufs[i].upload(headers[i].read_table_slice(a, b, threads=io_threads)), range(N)))
-                    ptrs = [buf.ptr for buf in bufs]
-                else:
-                    ptrs = [h.device_slice(a, b) for h in headers]
+        if own is not None:
+            own.zero()
+            acc_ptr = own.ptr
+        with closing(staged_pieces(headers, cuts, device, threads)) as pieces:
+            for ptrs, a, b in pieces:
                 secs = accumulate(ptrs, b - a, acc_ptr, device=device)
                 if stats is not None:
                     stats["kernel_seconds"] = stats.get("kernel_seconds", 0.0) + secs
-        finally:
-            if pool is not None:
-                pool.shutdown()
-        if own is None:
-            return None
-        return own.download().view(np.uint64)
+        return None if own is None else own.download().view(np.uint64)
     finally:
-        for buf in bufs:
-            buf.free()
         if own is not None:
             own.free()
-
-
-def _staged_pieces(headers: List[Header], lo: int, hi: int, device: int, threads: int, reserve: int = 0, budget: int = None):
-    """_flat_partial's staging for a pass that accumulates nothing: yields (ptrs, a, b) for every staged piece [a, b) of
-    [lo, hi), in ascending order, so the pass learns each piece's first address.  The cuts are _sub_slices' (N slices beside
-    each other, `reserve` bytes of `budget` kept for the caller's own buffers); ResidentTable entries are one piece, where
-    they lie.  The buffers are freed when the generator is exhausted or closed."""
-    N = len(headers)
-    resident = [hasattr(h, "device_slice") for h in headers]
-    assert all(resident) or not any(resident), "resident and file-backed tables cannot be mixed in one pass"
-    if all(resident):
-        yield [h.device_slice(lo, hi) for h in headers], lo, hi
-        return
-    cuts = _sub_slices(lo, hi, N, device, reserve=reserve, budget=budget)
-    bufs = [_lib.DeviceBuffer(max(b - a for a, b in cuts), device) for _ in range(N)]
-    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, N)))
-    try:
-        with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-            for a, b in cuts:
-                list(pool.map(lambda i: bufs[i].upload(headers[i].read_table_slice(a, b, threads=io_threads)), range(N)))
-                yield [buf.ptr for buf in bufs], a, b
-    finally:
-        for buf in bufs:
-            buf.free()
 
 
 def gpu_partial(headers: List[Header], lo: int, hi: int, windows, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
@@ -307,17 +221,9 @@ def write_kma(project_name: str, mn: int, mx: int, data, matrix: np.ndarray) -> 
     `.tmp` + rename."""
     outfile = Path(f"{project_name}.{mn:03d}-{mx:03d}.kma")
     output = {"project_name": project_name, "min_count": mn, "max_count": mx, "data": data}
-    outfile_json = Path(f"{outfile}.json")
-    outfile_json_tmp = Path(f"{outfile_json}.tmp")
-    print(f"saving {outfile_json}")
-    with outfile_json_tmp.open(mode="wt") as fhd:
-        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    outfile_json_tmp.rename(outfile_json)
-    print(f"saving {outfile}")
-    outfile_tmp = Path(f"{outfile}.tmp")
-    with outfile_tmp.open(mode="wb") as fhd:
+    write_json(Path(f"{outfile}.json"), output)
+    with atomic_write(outfile, "wb") as fhd:
         np.savez_compressed(fhd, matrix=matrix)            # merger.py:207: key `matrix`
-    outfile_tmp.rename(outfile)
 
 
 def print_matrix(matrix: np.ndarray) -> None:
@@ -365,20 +271,21 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
     indexes = [Path(p) for p in indexes]
     assert all(i.exists() for i in indexes)
 
-    data, headers, kmer_len = [], [], None
-    for pos, kin in enumerate(indexes):
-        print(f"verifying {kin}")
+    def load(kin):                                             # merger.py:108-117: the reference's checks, in its words
         kins = str(kin)
         assert kins.endswith(EXTS), f"all files must be .{Header.IND_EXT}[.bgz]: {kin}"
-        desc = kins[:-(len(Header.COMP_EXT) + 1)] if kins.endswith("." + Header.COMP_EXT) else kin
-        desc = Path(f"{desc}.{Header.DESC_EXT}")
+        desc = description_file(kin)
         assert desc.exists(), f"all .{Header.IND_EXT}[.{Header.COMP_EXT}] files must have a associated .{Header.IND_EXT}.{Header.DESC_EXT}: {desc}"
-        header = Header(kins, index_file=kins, buffer_size=buffer_size, device=devices[0])
+        return Header(kins, index_file=kins, buffer_size=buffer_size, device=devices[0])
+
+    data, headers, kmer_len = [], [], None
+    for pos, kin in enumerate(indexes):
+        data.append(table_entry(pos, kin, load))
+        header = data[-1]["header"]
         if kmer_len is None:
             kmer_len = header.kmer_len
         assert header.kmer_len == kmer_len, f"kmer_length differs. expected {kmer_len}, got {header.kmer_len}"
         headers.append(header)
-        data.append({"pos": pos, "index_file": kin, "description_file": desc, "header": header})
     print()
 
     if kwip:
@@ -391,8 +298,7 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         pairs = spec.window_pairs(hist, joint, windows)
     else:
         pairs = pair_matrix(headers, windows, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
-    for v in data:
-        v["header"] = v["header"].to_dict(lean=True)          # merger.py:187-188
+    lean_headers(data)
     is_writer = True
     if group is not None:
         import torch.distributed as dist

@@ -19,26 +19,21 @@ first base of the row's first window, bin_end = one past the last base of its la
 record as seq_len counts them (0-based; every sequence character, valid or not, and the blanks inside a sequence line).
 """
 import argparse
-import json
 import os
 import sys
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, bgzf
+from . import _lib, staging
 from .header import Header
 from .indexer import _Input, _mark
-from .merger import DEFAULT_THREADS, EXTS, _Encoder
+from .merger import DEFAULT_THREADS
+from .output import atomic_write, write_json
+from .tables import EXTS, MAX_KMER_LEN, common_kmer_len, lean_headers, name_of as _name_of, table_entry   # noqa: F401
 
-MAX_KMER_LEN = 17                   # one unsliced 4^k-byte table per sample
 WORKSPACE_RESERVE = 4 << 30         # of the free HBM, kept for the feed's workspace when the budget is taken from mem_info
-
-
-def _name_of(table) -> str:
-    return str(getattr(table, "index_file", None) or getattr(table, "project_name", table))
 
 
 def load_header(path, device: int = 0) -> Header:
@@ -60,18 +55,7 @@ def validate(tables: Sequence, min_count: int, max_count: int) -> int:
         raise ValueError(f"the count window must satisfy 1 <= min <= max <= 255, got {min_count}-{max_count}")
     if len(tables) < 1:
         raise ValueError("a query needs at least one table")
-    kmer_len = None
-    for t in tables:
-        k = int(t.kmer_len)
-        if k < 1 or k % 2 == 0:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} is not positive and odd")
-        if k > MAX_KMER_LEN:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} is beyond the query path (at most {MAX_KMER_LEN}: one unsliced table)")
-        if kmer_len is None:
-            kmer_len = k
-        elif k != kmer_len:
-            raise ValueError(f"{_name_of(t)}: kmer_len {k} differs from the {kmer_len} of {_name_of(tables[0])}")
-    return kmer_len
+    return common_kmer_len(tables, "query")
 
 
 def validate_bins(bin_windows) -> int:
@@ -113,23 +97,19 @@ class Staged:
         self.bufs = []
 
 
+class _Piece:
+    """The buffers of the piece a suspended staging.staged_pieces holds: free() closes the generator, which frees them."""
+
+    def __init__(self, pieces):
+        self.free = pieces.close
+
+
 def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) -> Staged:
-    """Whole tables into HBM, `threads` at a time, as merger._flat_partial stages slices; a merger.ResidentTable is used
-    where it lies."""
-    if all(hasattr(t, "device_slice") for t in tables):
-        return Staged([t.device_slice(t.first, t.first + t.n) for t in tables])
-    assert not any(hasattr(t, "device_slice") for t in tables), "resident and file-backed tables cannot be mixed in one group"
-    n = tables[0].data_size
-    bufs = [_lib.DeviceBuffer(n, device) for _ in tables]
-    io_threads = max(1, bgzf.INFLATE_THREADS // max(1, min(threads, len(tables))))
-    try:
-        with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-            list(pool.map(lambda i: bufs[i].upload(tables[i].read_table_slice(0, n, threads=io_threads)), range(len(tables))))
-    except BaseException:
-        for b in bufs:
-            b.free()
-        raise
-    return Staged([b.ptr for b in bufs], bufs)
+    """Whole tables into HBM, `threads` at a time: the one piece [0, 4^k) of staging.staged_pieces, which stays suspended
+    behind the Staged until its free(); a staging.ResidentTable is used where it lies."""
+    pieces = staging.staged_pieces(tables, [(0, tables[0].data_size)], device, threads)
+    ptrs, _, _ = next(pieces)
+    return Staged(ptrs, [_Piece(pieces)])
 
 
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
@@ -200,9 +180,7 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     if all(hasattr(t, "device_slice") for t in tables):
         groups = [(0, len(tables))]                          # resident already: nothing to fit
     else:
-        budget = hbm_budget or int(os.environ.get("PK_MERGE_HBM_BUDGET", "0")) or \
-            max(0, int(_lib.mem_info(device)[0] * 0.8) - WORKSPACE_RESERVE)
-        groups = table_groups(len(tables), 4 ** kmer_len, budget)
+        groups = table_groups(len(tables), 4 ** kmer_len, staging.hbm_budget(device, hbm_budget, workspace=WORKSPACE_RESERVE))
     result, lookup_s, coords_s = None, 0.0, 0.0
     for g, (lo, hi) in enumerate(groups):
         staged = stage(tables[lo:hi], device)
@@ -251,24 +229,14 @@ def write_kmq(project_name: str, result: dict, query_file: str, data: list, colu
     assert hits.shape == depth.shape == (len(names), len(columns)) and n_valid.shape == seq_len.shape == (len(names),)
     output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
               "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data}
-    print(f"saving {meta}")
-    tmp = Path(f"{meta}.tmp")
-    with tmp.open(mode="wt") as fhd:
-        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    tmp.rename(meta)
-    print(f"saving {tsv}")
-    tmp = Path(f"{tsv}.tmp")
-    with tmp.open(mode="wt") as fhd:
+    write_json(meta, output)
+    with atomic_write(tsv, "wt") as fhd:
         fhd.write("\t".join(["record", "seq_len", "n_valid"] + [str(c) for c in columns]) + "\n")
         for r, name in enumerate(names):
             fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in hits[r]]) + "\n")
-    tmp.rename(tsv)
-    print(f"saving {kmq}")
-    tmp = Path(f"{kmq}.tmp")
-    with tmp.open(mode="wb") as fhd:
+    with atomic_write(kmq, "wb") as fhd:
         np.savez_compressed(fhd, hits=hits, depth=depth, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
                             min_count=np.int64(result["min_count"]), max_count=np.int64(result["max_count"]))
-    tmp.rename(kmq)
 
 
 def kmb_paths(project_name: str) -> Tuple[Path, Path, Path]:
@@ -300,14 +268,8 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
               "bin_windows": W, "n_bins": B}
     if coords:
         output["coords"] = True
-    print(f"saving {meta}")
-    tmp = Path(f"{meta}.tmp")
-    with tmp.open(mode="wt") as fhd:
-        json.dump(output, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    tmp.rename(meta)
-    print(f"saving {tsv}")
-    tmp = Path(f"{tsv}.tmp")
-    with tmp.open(mode="wt") as fhd:
+    write_json(meta, output)
+    with atomic_write(tsv, "wt") as fhd:
         fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) + [str(c) for c in columns]) + "\n")
         for r, name in enumerate(names):
             m = int(n_valid[r])
@@ -315,14 +277,10 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
                 at = int(bin_first[r]) + b
                 span = [str(int(coords["bin_start"][at])), str(int(coords["bin_end"][at]))] if coords else []
                 fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + span + [str(int(v)) for v in hits[at]]) + "\n")
-    tmp.rename(tsv)
-    print(f"saving {kmb}")
-    tmp = Path(f"{kmb}.tmp")
-    with tmp.open(mode="wb") as fhd:
+    with atomic_write(kmb, "wb") as fhd:
         np.savez_compressed(fhd, hits=hits, depth=depth, bin_first=bin_first, n_valid=n_valid, seq_len=seq_len, bin_windows=np.uint64(W),
                             kmer_len=np.int64(result["kmer_len"]), min_count=np.int64(result["min_count"]),
                             max_count=np.int64(result["max_count"]), **coords)
-    tmp.rename(kmb)
 
 
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
@@ -333,7 +291,9 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
         raise ValueError("--coords gives the coordinates of bins: it needs --bin W")
-    extra = {"coords": True} if coords else {}
+    extra = {} if bin_windows is None else {"bin_windows": bin_windows}
+    if coords:
+        extra["coords"] = True
     for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
@@ -341,29 +301,19 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         raise ValueError(f"query file does not exist: {query_file}")
     if len(indexes) < 1:
         raise ValueError("a query needs at least one table")
-    data, headers = [], []
-    for pos, kin in enumerate(indexes):
-        print(f"verifying {kin}")
-        header = load_header(kin, device)
-        kins = str(kin)
-        desc = Path((kins[:-(len(Header.COMP_EXT) + 1)] if kins.endswith("." + Header.COMP_EXT) else kins) + "." + Header.DESC_EXT)
-        headers.append(header)
-        data.append({"pos": pos, "index_file": Path(kin), "description_file": desc, "header": header})
+    data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
+    headers = [v["header"] for v in data]
     validate(headers, min_count, max_count)
     _mark("tables verified")
-    if bin_windows is None:
-        result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads)
-    else:
-        try:
-            result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
-                                   bin_windows=bin_windows, **extra)
-        except _lib.PkError as exc:
-            if exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
-                raise
-            raise ValueError(f"{exc}; the rows of --bin {bin_windows} do not fit the device: use a larger --bin") from exc
+    try:
+        result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
+                               **extra)
+    except _lib.PkError as exc:
+        if bin_windows is None or exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
+            raise
+        raise ValueError(f"{exc}; the rows of --bin {bin_windows} do not fit the device: use a larger --bin") from exc
     columns = [str(h.project_name) for h in headers]
-    for v in data:
-        v["header"] = v["header"].to_dict(lean=True)
+    lean_headers(data)
     write_kmq(project_name, result, query_file, data, columns)
     if bin_windows is not None:
         write_kmb(project_name, result, query_file, data, columns)

@@ -22,6 +22,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib
+from .output import atomic_write, write_json
 
 
 def pair_list(N: int) -> np.ndarray:
@@ -85,23 +86,15 @@ def spectrum_paths(project_name: str) -> Tuple[Path, Path]:
 
 def save(project_name: str, hist: np.ndarray, joint: np.ndarray, kmer_len: int, data_size: int, data) -> Tuple[Path, Path]:
     """Writes `<project>.kms` and `.kms.json` (each through `.tmp` + rename; neither overwrites an existing file)."""
-    from .merger import _Encoder
     kms, kms_json = spectrum_paths(project_name)
     for f in (kms, kms_json):
         assert not f.exists(), f"spectrum output file ({f}) already exists. not overwriting."
     N = hist.shape[0]
     meta = {"project_name": project_name, "kmer_len": int(kmer_len), "data_size": int(data_size), "data": data}
-    tmp = Path(f"{kms_json}.tmp")
-    print(f"saving {kms_json}")
-    with tmp.open(mode="wt") as fhd:
-        json.dump(meta, fhd, sort_keys=True, indent=1, cls=_Encoder)
-    tmp.rename(kms_json)
-    tmp = Path(f"{kms}.tmp")
-    print(f"saving {kms}")
-    with tmp.open(mode="wb") as fhd:
+    write_json(kms_json, meta)
+    with atomic_write(kms, "wb") as fhd:
         np.savez_compressed(fhd, hist=np.ascontiguousarray(hist, dtype=np.uint64), joint=np.ascontiguousarray(joint, dtype=np.uint64),
                             pairs=pair_list(N), kmer_len=np.int64(kmer_len), data_size=np.int64(data_size))
-    tmp.rename(kms)
     return kms, kms_json
 
 

@@ -301,6 +301,37 @@ def test_table_counts_and_the_group_loop(gpu):
         _same(got, query_ref.expected(text, k, tables, 1, 254))
 
 
+# ------------------------------------------------------------------ 7b. file-backed table groups --
+def test_file_backed_tables_staged_group_after_group(gpu, tmp_path):
+    """query_records on real files with a budget of two tables: five tables (one of them BGZF) are staged from their files
+    in three groups, the query is streamed once per group, and every byte of a raw table is read exactly once."""
+    from pykmer_amd import bgzf, query
+    from pykmer_amd.header import Header
+    from test_host_layer import _write_index
+    k, N = 9, 5
+    paths, tables, bases = [], [], []
+    for i in range(N):
+        fa, _ = synth.family(i, 60_000)
+        h, got = _write_index(tmp_path, f"q{i}.fa", fa.tobytes(), k)
+        paths.append(h.index_file_root)
+        tables.append(got["table"])
+        bases.append(b"".join(ln for ln in fa.tobytes().split(b"\n") if not ln.startswith(b">")))
+    bgzf.compress_file(paths[2], level=1)
+    headers = [Header(p, index_file=p) for p in paths]
+    assert headers[2].index_file.endswith(".bgz")
+    text = b"".join(b">r%d of sample %d\n" % (i, i % N) + bases[i % N][700 * i:700 * i + 250 + 37 * i] + b"\n" for i in range(6))
+    qf = tmp_path / "q.fa"
+    qf.write_bytes(text)
+    got = query.query_records(str(qf), headers, 2, 254, device=0, hbm_budget=2 * 4 ** k + 100)
+    assert got["n_groups"] == 3
+    want = query_ref.expected(text, k, tables, 2, 254)
+    assert len(got["names"]) == 6 and got["hits"].shape == (6, N) and want["hits"].any(axis=0).all()
+    assert np.array_equal(got["n_valid"], want["n_valid"]) and np.array_equal(got["seq_len"], want["seq_len"])
+    assert np.array_equal(got["hits"], want["hits"]), np.argwhere(got["hits"] != want["hits"])[:5]
+    assert np.array_equal(got["depth"], want["depth"]), np.argwhere(got["depth"] != want["depth"])[:5]
+    assert all(h.bytes_delivered == 4 ** k for i, h in enumerate(headers) if i != 2)
+
+
 # ------------------------------------------------------------------ 8. CLI -------------------------
 def _run(*argv, cwd, env=None):
     r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
