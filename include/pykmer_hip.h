@@ -299,9 +299,13 @@ int pk_bgzf_deflate(const uint8_t *src, uint64_t n_bytes, int level, uint32_t bl
  * out = { addr_bits, fb_bits, b1, b2, sample_stride (16: sampled layout, 1: exact), n_tally (buckets tallied while
  * sampling), sample2, n_chunks, walk-sort variant (0 narrow, 1 narrow sliced, 2 k15, 3 k17, 4 wide sliced, 5 deep),
  * bucket-count kernel (0 whole, 1 bytes, 2 half), bucket split, B1, B2, level-1 record capacity, final-bucket record
- * capacity, 1 if every record position fits 32 bits }. */
+ * capacity, 1 if every record position fits 32 bits }.
+ * pk_diag_settled_chunks: how many 16 KiB chunks of the indexer's last feed the structure pass squeezed itself (full chunks
+ * of plain sequence text that are not entered inside a header line; the squeeze pass only completes those); 0 for a query
+ * indexer and before the first feed.  Copies one small record per chunk from the device. */
 int pk_diag_occupancy(int which);
 int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]);
+int pk_diag_settled_chunks(pk_indexer *ix, uint64_t *out);
 int pk_diag_plan_slice(int k, int n_slices, uint64_t n_bytes, uint64_t out[16]);
 
 #ifdef __cplusplus

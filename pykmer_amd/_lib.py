@@ -79,6 +79,7 @@ _SIGNATURES = {
                                         ctypes.c_void_p, _u64p, ctypes.c_int]),
     "pk_diag_occupancy": (ctypes.c_int, [ctypes.c_int]),
     "pk_diag_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_diag_settled_chunks": (ctypes.c_int, [ctypes.c_void_p, _u64p]),
     "pk_diag_plan_slice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
@@ -256,6 +257,13 @@ class Indexer:
         out = np.zeros(4, dtype=np.uint64)
         _check(load().pk_indexer_fastq_stats(self._h, out.ctypes.data))
         return {"records": int(out[0]), "lines": int(out[1]), "bytes_fed": int(out[2]), "bytes_emitted": int(out[3])}
+
+    def settled_chunks(self) -> int:
+        """pk_diag_settled_chunks: the 16 KiB chunks of the last feed that the structure pass squeezed itself (full chunks of
+        plain sequence text not entered inside a header line); 0 for a query indexer."""
+        n = ctypes.c_uint64(0)
+        _check(load().pk_diag_settled_chunks(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def _timings_raw(self) -> np.ndarray:
         t = np.zeros(10, dtype=np.float64)

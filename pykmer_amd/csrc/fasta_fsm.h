@@ -132,6 +132,21 @@ __device__ __forceinline__ LaneStart lane_start(const LaneState lst, const L2 &c
     return s;
 }
 
+// A SETTLED chunk: a full chunk of clean pieces only.  The structure pass of a counting feed squeezes such a chunk itself --
+// it places the bases in the chunk's slot and counts the windows as if the chunk were entered in a live record with a run of
+// at least k-1 bases and no pending blanks -- and leaves the squeeze pass this record.  The LEADING lanes are the ones whose
+// result still depends on the state the chunk is entered with (lane 0; further lanes while no restart and fewer than k-1
+// valid bases lie between the chunk start and their first byte): only they still get their pack and lane state written.
+struct ChunkFix {
+    uint32_t n_lead;    // leading lanes; 0: the chunk is not settled
+    uint32_t n_seq;     // sequence characters of the chunk
+    uint32_t n_win;     // valid windows under the assumption above
+    uint32_t pad_;
+};
+// the run a lane of a settled chunk starts with under that assumption (its chunk-relative prefix behind a run of k-1)
+__device__ __forceinline__ uint32_t settled_run(const L2 &rel, uint32_t km1) { return (rel.flags & F_BRK) ? l2_len(rel) : km1; }
+__device__ __forceinline__ bool settled_leading(const L2 &rel, uint32_t km1) { return !(rel.flags & F_BRK) && l2_len(rel) < km1; }
+
 // ---- wave / workgroup exclusive scans (64-wide wavefronts, non-commutative operator) ----------
 __device__ __forceinline__ L1 wave_incl_scan_l1(L1 v, int lane) {
     // Short cut for the usual wave: no piece ends inside a header line, and a piece without a terminator ends in

@@ -5,6 +5,8 @@
 // fasta_fsm.h), and every piece gets its exact parser state -- what the squeeze pass (kmer_pack.hip)
 // starts from.  k_hist is Header.update_stats (tools.py:246-263) for tables that arrive from disk.
 #include "fasta_fsm.h"
+#include "kmer_window.h"
+#include "lds_bits.h"
 #include "pk_kernels.h"
 #include "wg_scan.h"
 
@@ -79,10 +81,21 @@ __global__ __launch_bounds__(WG) void k_chunk_l1(const uint8_t *__restrict__ fas
 // too (header_text).  What is left -- a blank or control byte outside header text, a line that begins with one, the partial
 // last piece -- needs the byte-wise machines, which cost a wave the same for one lane as for 64: those pieces are queued
 // and worked off 64 per wave pass.
+//
+// SETTLE (counting feeds): a settled chunk (ChunkFix, fasta_fsm.h) -- the usual chunk of a genome -- is squeezed here, where
+// its packs are in registers: the bases go to the chunk's slot as k_squeeze (kmer_pack.hip) places them, the windows are
+// counted, and only the leading lanes' packs and lane states go to memory for the squeeze pass's fix-up.  The decision is
+// two LDS words behind a barrier that is there anyway; the slot is put together in the LDS of the text, which is used up by
+// then.  Without SETTLE (query feeds: kmer_coords.hip reads the pack and the lane state of every piece) nothing is settled.
+constexpr uint32_t SLOT_RST_AT = SLOT_CODE_WORDS + 8;      // the slot in LDS, in words: codes, slack (lds_or_bits touches up to 5 words), restart bits, slack
+constexpr uint32_t SLOT_LDS_WORDS = SLOT_RST_AT + SLOT_RST_WORDS + 8;
+static_assert(SLOT_LDS_WORDS * 4 <= 2 * WG * 16 && SLOT_LDS_WORDS * 4 <= WG * LDS_STRIDE && SLOT_RST_AT % 4 == 0, "two 16-byte stores per lane zero the slot");
+template <bool SETTLE>
 __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__restrict__ fasta, uint64_t n_bytes,
                                                  const L1 *__restrict__ chunk_l1_state, L2 *__restrict__ chunk_l2,
                                                  LaneState *__restrict__ lane_state, PiecePack *__restrict__ packs,
-                                                 uint32_t *__restrict__ chunk_odd, uint32_t km1) {
+                                                 uint32_t *__restrict__ chunk_odd, uint32_t km1, ChunkFix *__restrict__ chunk_fix,
+                                                 uint32_t *__restrict__ codes, uint32_t *__restrict__ restarts, uint32_t *__restrict__ n_bases) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[WG * LDS_STRIDE];
     __shared__ L1 sh1[WG / 64];
     __shared__ L2 sh2[WG / 64];
@@ -90,9 +103,11 @@ __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__rest
     __shared__ uint32_t n_queued[2], n_header_pieces;
     __shared__ uint32_t res1[WG];                          // queued pieces: L1 summary | dirty << 8
     __shared__ uint8_t ls_of[WG];                          // every piece's incoming line state (for the L2 pass over the queue)
+    __shared__ uint32_t sum_sh[WG / 64], settled_sums[2];  // SETTLE: scan scratch; sequence characters | windows << 16, leading lanes
     const uint64_t base = (uint64_t)blockIdx.x * CHUNK;
     if (threadIdx.x < 2) n_queued[threadIdx.x] = 0;
     if (threadIdx.x == 2) n_header_pieces = 0;
+    if (SETTLE && threadIdx.x >= 4 && threadIdx.x < 6) settled_sums[threadIdx.x - 4] = 0;
     stage_chunk(fasta, base, n_bytes, lds);
     __syncthreads();
     const uint32_t nb = piece_len(base, n_bytes);
@@ -106,10 +121,13 @@ __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__rest
     {
         const unsigned long long S = ~pm.term;                           // the pack of the piece read as plain sequence text
         piece_compact(pm.valid, S & ~pm.valid, cw, plain, (uint32_t)__popcll(S), (S & 1ull) != 0ull, pk);
+    }
+    auto store_pack = [&]() {
         uint4 *dst = reinterpret_cast<uint4 *>(packs + (uint64_t)blockIdx.x * WG + threadIdx.x);
         dst[0] = make_uint4((uint32_t)pk.c_lo, (uint32_t)(pk.c_lo >> 32), (uint32_t)pk.c_hi, (uint32_t)(pk.c_hi >> 32));
         dst[1] = make_uint4((uint32_t)pk.restart, (uint32_t)(pk.restart >> 32), pk.meta, 0u);
-    }
+    };
+    if (!SETTLE) store_pack();
     // ---- L1: line state.  Full pieces whose lines do not begin with a blank from the masks; the rest (and partial pieces)
     // go to the queue
     const bool masks1 = full && lines_start_plain(pm);
@@ -155,6 +173,17 @@ __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__rest
     const unsigned long long hp_wave = __ballot(header_piece);
     if ((threadIdx.x & 63u) == 0u && hp_wave) atomicAdd(&n_header_pieces, (uint32_t)__popcll(hp_wave));
     __syncthreads();
+    // settled: a full chunk with nothing queued and no header piece (uniform).  Its text is used up: the slot takes its place
+    const bool settled = SETTLE && n_queued[1] + n_header_pieces == 0u && base + (uint64_t)CHUNK <= n_bytes;
+    uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
+    if (SETTLE) {
+        if (!settled) {
+            store_pack();
+        } else {
+            reinterpret_cast<uint4 *>(slot)[threadIdx.x] = make_uint4(0, 0, 0, 0);
+            if (threadIdx.x + WG < SLOT_LDS_WORDS / 4) reinterpret_cast<uint4 *>(slot)[threadIdx.x + WG] = make_uint4(0, 0, 0, 0);
+        }
+    }
     for (uint32_t q0 = (threadIdx.x >> 6) * 64u; q0 < n_queued[1]; q0 += WG) {
         const uint32_t qi = q0 + (threadIdx.x & 63u);
         const bool work = qi < n_queued[1];
@@ -170,12 +199,47 @@ __global__ __launch_bounds__(WG, L2_WAVES) void k_chunk_l2(const uint8_t *__rest
         const uint32_t *in = reinterpret_cast<const uint32_t *>(mine);
         my2.flags = in[0]; my2.bits = in[1]; my2.rec = in[2]; my2.p_tail = in[3];
     }
+    // where the lane's bases go in the slot (as k_squeeze, kmer_pack.hip); the codes are placed before the L2 scan, which
+    // then has four registers fewer to carry.  The barrier inside the sum stands between the zeroing and the first OR.
+    uint32_t at = 0, n_slot = 0;
+    if (settled) {
+        at = wg_excl_sum<WG / 64, false>(pack_n_valid(pk), sum_sh, n_slot);
+        lds_or_bits(slot, 2u * at, pk.c_lo, pk.c_hi, 2u * pack_n_valid(pk));
+    }
     L2 total;
     const L2 rel = wg_excl_scan_l2(my2, l2_identity(), sh2, &total, km1);     // prefix relative to the chunk start
-    lane_state[(uint64_t)blockIdx.x * WG + threadIdx.x] = lane_state_pack(rel, ls_in, q2, header_piece);
+    const bool leading = settled && (threadIdx.x == 0u || settled_leading(rel, km1));
+    if (!settled || leading) lane_state[(uint64_t)blockIdx.x * WG + threadIdx.x] = lane_state_pack(rel, ls_in, q2, header_piece);
     if (threadIdx.x == 0) {
         chunk_l2[blockIdx.x] = total;
         chunk_odd[blockIdx.x] = n_queued[1] + n_header_pieces;   // pieces whose text the squeeze pass has to see
+        if (SETTLE && !settled) chunk_fix[blockIdx.x].n_lead = 0u;
+    }
+    if (!settled) return;                                                // uniform
+    if (leading) store_pack();
+    const uint32_t nv = pack_n_valid(pk);
+    unsigned long long F = pk.restart;
+    const unsigned long long has = window_ends(F, nv, settled_run(rel, km1), km1);
+    lds_or_bits(slot + SLOT_RST_AT, at, F, 0ull, nv);
+    uint32_t sums = pack_n_seq(pk) | ((uint32_t)__popcll(has) << 16);    // <= 16384 each over the chunk
+    for (int d = 32; d; d >>= 1) sums += __shfl_down(sums, d, 64);
+    const unsigned long long lead_wave = __ballot(leading);
+    if ((threadIdx.x & 63u) == 0u) {
+        atomicAdd(&settled_sums[0], sums);
+        if (lead_wave) atomicAdd(&settled_sums[1], (uint32_t)__popcll(lead_wave));
+    }
+    __syncthreads();
+    // slot -> HBM, 16 bytes per lane, only the words that hold bases
+    const uint32_t code_q = (n_slot + 63u) / 64u, rst_q = (n_slot + 127u) / 128u;
+    if (threadIdx.x < code_q)
+        reinterpret_cast<uint4 *>(codes + (uint64_t)blockIdx.x * SLOT_CODE_WORDS)[threadIdx.x] = reinterpret_cast<const uint4 *>(slot)[threadIdx.x];
+    if (threadIdx.x < rst_q)
+        reinterpret_cast<uint4 *>(restarts + (uint64_t)blockIdx.x * SLOT_RST_WORDS)[threadIdx.x] = reinterpret_cast<const uint4 *>(slot + SLOT_RST_AT)[threadIdx.x];
+    if (threadIdx.x == 0) {
+        n_bases[blockIdx.x] = n_slot;
+        ChunkFix fx;
+        fx.n_lead = settled_sums[1]; fx.n_seq = settled_sums[0] & 0xffffu; fx.n_win = settled_sums[0] >> 16; fx.pad_ = 0u;
+        chunk_fix[blockIdx.x] = fx;
     }
 }
 
@@ -306,9 +370,16 @@ void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *
     hipLaunchKernelGGL(k_scan_l1_tiles, dim3(1), dim3(SCAN_T), 0, s, tile_ws, n_tiles, carry, (uint32_t *)zeroed, (uint32_t)(sizeof(PartSignals) / 4));
     hipLaunchKernelGGL(k_scan_l1_apply, dim3(n_tiles), dim3(SCAN_T), 0, s, in, n_chunks, (const L1 *)tile_ws, out);
 }
-void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd, uint32_t n_chunks,
-                     uint32_t k, hipStream_t s) {
-    hipLaunchKernelGGL(k_chunk_l2, dim3(n_chunks), dim3(WG), 0, s, fasta, n, st1, chunk_l2, lane_state, packs, chunk_odd, k - 1);
+// chunk_fix: one record per chunk, and the slots in `b` are written for the settled chunks (a counting feed); null: nothing is
+// settled, and every piece's pack and lane state is written (a query feed)
+void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd,
+                     ChunkFix *chunk_fix, const PartBuffers &b, uint32_t n_chunks, uint32_t k, hipStream_t s) {
+    if (chunk_fix)
+        hipLaunchKernelGGL(k_chunk_l2<true>, dim3(n_chunks), dim3(WG), 0, s, fasta, n, st1, chunk_l2, lane_state, packs, chunk_odd, k - 1, chunk_fix, b.codes,
+                           b.restarts, b.n_bases);
+    else
+        hipLaunchKernelGGL(k_chunk_l2<false>, dim3(n_chunks), dim3(WG), 0, s, fasta, n, st1, chunk_l2, lane_state, packs, chunk_odd, k - 1, chunk_fix,
+                           (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
 }
 void launch_scan_l2(const L2 *in, uint32_t n_chunks, Carry *carry, L2 *out, L2 *tile_ws, uint32_t k, hipStream_t s) {
     const uint32_t n_tiles = (n_chunks + SCAN_T - 1) / SCAN_T;

@@ -20,26 +20,13 @@
 #include "fasta_fsm.h"
 #include "kmer_walk.h"
 #include "kmer_window.h"
+#include "lds_bits.h"
 #include "pk_kernels.h"
 #include "wg_scan.h"
 
 namespace pk {
 
 constexpr int SQUEEZE_WAVES = 4;   // waves per SIMD the squeeze kernel is compiled for (3, 5, 6 and 8 all give 0.31 ms instead of 0.21)
-
-// OR `n_bits` bits of (lo, hi) into the LDS bit array `dst` at bit offset `at`
-__device__ __forceinline__ void lds_or_bits(uint32_t *dst, uint32_t at, unsigned long long lo, unsigned long long hi, uint32_t n_bits) {
-    if (n_bits == 0) return;
-    const uint32_t w0 = at >> 5, sh = at & 31u;
-    const uint32_t x[5] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), 0u};
-    uint32_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const uint32_t v = sh ? ((x[i] << sh) | carry) : x[i];
-        carry = sh ? (x[i] >> (32u - sh)) : 0u;
-        if (v) atomicOr(&dst[w0 + i], v);                    // words past the lane's bits are all zero and skipped
-    }
-}
 
 // ------------------------------------------------------------------ clean pieces ----
 // A CLEAN piece holds nothing but sequence characters and line terminators and does not start inside a header line
@@ -175,7 +162,8 @@ template <uint32_t KC>                   // k as a literal (0: the argument)
 __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__restrict__ fasta, uint64_t n_bytes, uint64_t stream_off,
                                                 const LaneState *__restrict__ lane_state, const PiecePack *__restrict__ packs,
                                                 const L2 *__restrict__ chunk_l2_state,
-                                                const uint32_t *__restrict__ chunk_odd, uint32_t k_arg, uint32_t n_chunks, uint32_t chunks_per_wg,
+                                                const uint32_t *__restrict__ chunk_odd, const ChunkFix *__restrict__ chunk_fix, uint32_t k_arg,
+                                                uint32_t n_chunks, uint32_t chunks_per_wg,
                                                 uint32_t *__restrict__ codes,
                                                 uint32_t *__restrict__ restarts, uint32_t *__restrict__ n_bases,
                                                 DevRec *__restrict__ recs, uint64_t recs_cap, Carry *carry, uint32_t *__restrict__ flags) {
@@ -195,6 +183,7 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
     __shared__ uint16_t queue[WG];                         // pieces that need their text
     __shared__ uint32_t n_queued;
     __shared__ RecAcc racc;
+    __shared__ uint32_t todo[SQUEEZE_G_MAX / 32];          // of the workgroup's chunks: the ones that are not settled
     const uint32_t k = KC ? KC : k_arg, km1 = k - 1;
     if (threadIdx.x == 0) n_queued = 0;
     for (uint32_t i = threadIdx.x; i < SLOT_CODE_WORDS + 8; i += WG) slot_codes[i] = 0;
@@ -220,15 +209,85 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
         asm volatile("" : "+v"(nxt.ls_flags), "+v"(nxt.ls_rec_tail), "+v"(nxt.p0.x), "+v"(nxt.p0.y), "+v"(nxt.p0.z), "+v"(nxt.p0.w),
                           "+v"(nxt.p1.x), "+v"(nxt.p1.y), "+v"(nxt.p1.z), "+v"(nxt.p1.w));
     };
-    if (c_lo < c_hi) {
-        if (chunk_odd[c_lo]) stage_image(fasta, (uint64_t)c_lo * CHUNK, n_bytes, image[0]);
-        fetch(c_lo, nxt);
+    // the first chunk at or behind c that is not settled (c_hi: none).  Uniform.
+    auto next_todo = [&](uint32_t c) -> uint32_t {
+        for (uint32_t i = c - c_lo; i < SQUEEZE_G_MAX; i = (i | 31u) + 1u) {
+            const uint32_t m = todo[i >> 5] & (~0u << (i & 31u));
+            if (m) return min(c_lo + (i & ~31u) + (uint32_t)__builtin_ctz(m), c_hi);
+        }
+        return c_hi;
+    };
+    __syncthreads();                                       // racc is set up
+    // ---- settled chunks (ChunkFix, fasta_fsm.h): the structure pass has placed their bases and counted their windows as if
+    // they were entered in a live record behind a run of k-1 bases.  What is left depends on the state the chunk is really
+    // entered with, and only the leading lanes see it: they go through lane_start + squeeze_apply like every clean piece, in
+    // order, and give the base-0 restart bit, the windows the carried run is too short for and the pending blanks that turn
+    // out interior.  What goes to the slots (a restart bit OR-ed in, a base count of 0) is the same however often this runs.
+    // One thread per chunk (the plan gives a workgroup at most SQUEEZE_G_MAX); the chunks that are not settled are marked in
+    // `todo` and take the loop below.
+    static_assert(SQUEEZE_G_MAX <= WG && SQUEEZE_G_MAX % 32 == 0, "one thread per chunk of the workgroup");
+    if (threadIdx.x < SQUEEZE_G_MAX / 32) todo[threadIdx.x] = 0u;
+    if (threadIdx.x == 0 && c_lo < c_hi) racc.rec0 = chunk_l2_state[c_lo].rec;   // nothing is gathered yet: the record window starts where the chunks do
+    __syncthreads();
+    {
+        const uint32_t c = c_lo + threadIdx.x;
+        const bool have = c < c_hi;
+        ChunkFix fx; fx.n_lead = 0u; fx.n_seq = 0u; fx.n_win = 0u; fx.pad_ = 0u;
+        L2 chunk_st = l2_identity();
+        LaneState lst; lst.flags = 0u; lst.rec_tail = 0u;
+        uint4 p1 = make_uint4(0, 0, 0, 0);
+        if (have) {
+            if (chunk_fix) fx = chunk_fix[c];
+            chunk_st = chunk_l2_state[c];
+            lst = lane_state[(uint64_t)c * WG];            // lane 0 leads every settled chunk: asked for along with the record
+            p1 = reinterpret_cast<const uint4 *>(packs + (uint64_t)c * WG)[1];
+        }
+        const bool is_settled = fx.n_lead != 0u;
+        if (have && !is_settled) atomicOr(&todo[threadIdx.x >> 5], 1u << (threadIdx.x & 31u));
+        wk.begin(LS_SEQ, chunk_st, 0ull);
+        // lanes without a chunk go along in the record of the wave's first chunk, so that the wave's sums can be taken as one
+        if (!have) wk.rec = (uint32_t)__builtin_amdgcn_readfirstlane((int)wk.rec);
+        if (is_settled && chunk_st.rec == 0u) {            // text in front of the first header is dropped
+            n_bases[c] = 0u;
+        } else if (is_settled) {
+            uint64_t seq = fx.n_seq, win = fx.n_win;               // less the leading lanes' share, which is added as it really is
+            for (uint32_t j = 0; j < fx.n_lead; j++) {
+                if (j) {
+                    lst = lane_state[(uint64_t)c * WG + j];
+                    p1 = reinterpret_cast<const uint4 *>(packs + (uint64_t)c * WG + j)[1];
+                }
+                PiecePack pk;
+                pk.c_lo = 0ull; pk.c_hi = 0ull; pk.restart = ((unsigned long long)p1.y << 32) | p1.x; pk.meta = p1.z; pk.pad_ = 0u;
+                const LaneStart ln = lane_start(lst, chunk_st, km1);
+                unsigned long long assumed_F = pk.restart;
+                const unsigned long long assumed = window_ends(assumed_F, pack_n_valid(pk), settled_run(lane_state_l2(lst), km1), km1);
+                seq -= pack_n_seq(pk);
+                win -= (uint64_t)__popcll(assumed);
+                wk.ls = ln.ls_in; wk.pend = ln.st.p_tail; wk.run = l2_len(ln.st);
+                PieceBases pb;
+                squeeze_apply(pk, wk, pb, true);                 // adds the lane's exact tallies to wk's
+                // base 0 of the lane restarts the run after all: it lies l2_len(prefix) bases into the slot
+                if (pb.restart & ~assumed_F & 1ull) {
+                    const uint32_t at = l2_len(lane_state_l2(lst));
+                    atomicOr(&restarts[(uint64_t)c * SLOT_RST_WORDS + (at >> 5)], 1u << (at & 31u));
+                }
+            }
+            wk.seq_acc += seq; wk.kmer_acc += win;
+        }
+        wk.flush_rec_wave();
+    }
+    __syncthreads();
+    uint32_t c = next_todo(c_lo), c_next = c_hi;
+    if (c < c_hi) {
+        if (chunk_odd[c]) stage_image(fasta, (uint64_t)c * CHUNK, n_bytes, image[0]);
+        fetch(c, nxt);
+        c_next = next_todo(c + 1u);
     }
     settle();
     __syncthreads();
-    for (uint32_t c = c_lo; c < c_hi; c++) {
+    for (uint32_t n_done = 0; c < c_hi; c = c_next, c_next = next_todo(min(c_next + 1u, c_hi)), n_done++) {
         const uint64_t base = (uint64_t)c * CHUNK;
-        uint8_t *buf = image[(c - c_lo) & 1u];
+        uint8_t *buf = image[n_done & 1u];
         const bool all_clean = chunk_odd[c] == 0u;         // uniform over the workgroup; the usual chunk
         if (!all_clean) __syncthreads();                   // every wave's share of the image has landed (each waited for its own in settle)
         // the record tallies of a chunk count up from the record it starts in; when that moves on, what was gathered
@@ -241,10 +300,10 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
             __syncthreads();
         }
         const Fetched me = nxt;
-        if (c + 1 < c_hi) {
+        if (c_next < c_hi) {
             // the other image is free: its readers passed the barriers of the chunk before this one
-            if (chunk_odd[c + 1]) stage_image(fasta, base + CHUNK, n_bytes, image[(c - c_lo + 1) & 1u]);
-            fetch(c + 1, nxt);
+            if (chunk_odd[c_next]) stage_image(fasta, (uint64_t)c_next * CHUNK, n_bytes, image[(n_done + 1u) & 1u]);
+            fetch(c_next, nxt);
         }
         // exact parser state at this lane's first byte: chunk state . lane prefix (both from the structure pass)
         const L2 chunk_st = chunk_l2_state[c];
@@ -338,9 +397,11 @@ __global__ __launch_bounds__(WG, SQUEEZE_WAVES) void k_squeeze(const uint8_t *__
     recacc_finish(racc, recs, recs_cap, carry);
 }
 
+// chunk_fix: what launch_chunk_l2 was given for this feed
 void launch_squeeze(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state,
-                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, DevRec *recs, uint64_t recs_cap, Carry *carry, hipStream_t s) {
-#define PK_SQUEEZE(KC) hipLaunchKernelGGL(k_squeeze<KC>, dim3(pl.n_wg0), dim3(WG), 0, s, fasta, n, stream_off, lane_state, packs, st2, chunk_odd, pl.k, \
+                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, const ChunkFix *chunk_fix, DevRec *recs, uint64_t recs_cap, Carry *carry,
+                    hipStream_t s) {
+#define PK_SQUEEZE(KC) hipLaunchKernelGGL(k_squeeze<KC>, dim3(pl.n_wg0), dim3(WG), 0, s, fasta, n, stream_off, lane_state, packs, st2, chunk_odd, chunk_fix, pl.k, \
                                           pl.n_chunks, pl.G, b.codes, b.restarts, b.n_bases, recs, recs_cap, carry, b.flags)
     if (pl.k == 15) PK_SQUEEZE(15);
     else if (pl.k == 17) PK_SQUEEZE(17);

@@ -750,6 +750,7 @@ PartPlan make_part_plan(uint32_t k, uint64_t n_bytes, uint32_t slice_bits, uint3
     if (pl.n_wg0 == 0) pl.n_wg0 = 1;
     pl.G = (pl.n_chunks + pl.n_wg0 - 1) / pl.n_wg0;
     if (pl.G == 0) pl.G = 1;
+    if (pl.G > SQUEEZE_G_MAX) { pl.G = SQUEEZE_G_MAX; pl.n_wg0 = (pl.n_chunks + pl.G - 1) / pl.G; }   // a 2 GiB feed, the largest: 128
     const uint32_t wg1 = 4096u;                            // shorter stretches per workgroup even out the last round (1024: 1.42 ms, 4096: 1.39)
     pl.n_wg1 = pl.n_chunks < wg1 ? pl.n_chunks : wg1;
     if (pl.n_wg1 == 0) pl.n_wg1 = 1;

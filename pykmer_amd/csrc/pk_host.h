@@ -163,6 +163,8 @@ struct pk_indexer {
     pk::DevBuf<pk::LaneState> lane_state;      // per 64-byte piece: start state relative to its chunk
     pk::DevBuf<pk::PiecePack> packs;           // per 64-byte piece: its bases, classified and pushed together (structure pass -> squeeze pass)
     pk::DevBuf<uint32_t> chunk_odd;        // per chunk: pieces that are not plain sequence text
+    pk::DevBuf<pk::ChunkFix> chunk_fix;    // per chunk of a counting feed: what the structure pass leaves of a chunk it squeezed itself
+    uint32_t fix_chunks = 0;               // chunks of the last feed that chunk_fix describes (0: a query feed, or none yet)
     pk::DevBuf<pk::L1> t_l1;                   // scan scratch: one summary per 1024 chunks
     pk::DevBuf<pk::L2> t_l2;
     pk::DevBuf<uint8_t> staging[2];        // device copies of host-fed pieces (one counted while the next uploads)

@@ -50,6 +50,7 @@ static int ix_reset(pk_indexer *ix) {
     ix->feeds = ix->relayouts = 0; ix->recounted = 0;
     ix->fed = false;
     ix->fq_pending = 0; ix->fq_need = 0; ix->fq_failed = false; ix->fq_err.clear();
+    ix->fix_chunks = 0;
     return PK_OK;
 }
 
@@ -138,6 +139,7 @@ static int ensure_chunks(pk_indexer *ix, uint32_t n_chunks) {
     if ((rc = ix->lane_state.reserve(n * WG * sizeof(LaneState)))) return rc;
     if ((rc = ix->packs.reserve(n * WG * sizeof(PiecePack)))) return rc;
     if ((rc = ix->chunk_odd.reserve(n * sizeof(uint32_t)))) return rc;
+    if (!ix->q && (rc = ix->chunk_fix.reserve(n * sizeof(ChunkFix)))) return rc;
     if ((rc = ix->t_l1.reserve((n / 1024 + 1) * sizeof(L1)))) return rc;
     return ix->t_l2.reserve((n / 1024 + 1) * sizeof(L2));
 }
@@ -185,6 +187,18 @@ extern "C" int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]) {
     return PK_OK;
 }
 
+// diagnostics: the chunks of the last feed that the structure pass squeezed itself, counted from its per-chunk records
+extern "C" int pk_diag_settled_chunks(pk_indexer *ix, uint64_t *out) {
+    if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
+    *out = 0;
+    if (!ix->fix_chunks) return PK_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    std::vector<ChunkFix> fix(ix->fix_chunks);
+    HIPCHK(hipMemcpy(fix.data(), ix->chunk_fix.p, fix.size() * sizeof(ChunkFix), hipMemcpyDeviceToHost));   // every feed ends with a wait
+    for (const ChunkFix &f : fix) *out += f.n_lead != 0u;
+    return PK_OK;
+}
+
 // the same for one of n_slices address slices, with the choices the launchers make on top of the plan
 extern "C" int pk_diag_plan_slice(int k, int n_slices, uint64_t n_bytes, uint64_t out[16]) {
     if (!out) return fail(PK_ERR_ARG, "null output");
@@ -213,6 +227,10 @@ static int run_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes, const Pa
     if (rc) return rc;
     Carry *carry = &ix->tail.p->carry;
     const Events &ev = ix->ev;
+    // a counting feed: the structure pass squeezes the settled chunks into pb's slots itself (ChunkFix, fasta_fsm.h); a query
+    // feed keeps every piece's pack and lane state for the coordinate kernels
+    ChunkFix *fix = ix->q ? nullptr : ix->chunk_fix.p;
+    ix->fix_chunks = 0;
     // Nothing between here and the last kernel of the feed waits for the device: the record array was sized from what the
     // feeds so far held (ensure_recs below, after the feed), the squeeze pass checks that against the count the structure
     // pass leaves in `carry` and backs out if it does not fit (flags[0] = 2), the sorts back out if a sampled bucket
@@ -222,7 +240,7 @@ static int run_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes, const Pa
     HIPCHK(hipEventRecord(ev.scan_begin, ix->stream));
     launch_chunk_l1(f, n_bytes, ix->c_l1.p, n_chunks, ix->stream);
     launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
-    launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, n_chunks, (uint32_t)ix->k, ix->stream);
+    launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, fix, pb, n_chunks, (uint32_t)ix->k, ix->stream);
     launch_scan_l2(ix->c_l2.p, n_chunks, carry, ix->c_l2s.p, ix->t_l2.p, (uint32_t)ix->k, ix->stream);
     HIPCHK(hipEventRecord(ev.scan_end, ix->stream));
     uint32_t raised = 0;
@@ -232,8 +250,8 @@ static int run_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes, const Pa
         if (!raised || raised == 2u) {
             squeezed_cap = ix->recs_cap();
             HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream));
-            launch_squeeze(pl, pb, f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, ix->recs.p, squeezed_cap, carry,
-                           ix->stream);
+            launch_squeeze(pl, pb, f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, fix, ix->recs.p, squeezed_cap,
+                           carry, ix->stream);
             if (ix->k > 17) launch_deep_tail(pl, pb, carry, ix->stream);
             HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
         }
@@ -261,6 +279,7 @@ static int run_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes, const Pa
     if ((rc = add_elapsed(&ix->t_squeeze, ev.squeeze_begin, ev.squeeze_end))) return rc;
     ix->feeds++;
     ix->bytes_fed += n_bytes;
+    if (fix) ix->fix_chunks = n_chunks;
     return PK_OK;
 }
 

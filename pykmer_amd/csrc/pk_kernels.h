@@ -39,14 +39,13 @@ struct PartSignals {
 
 void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_chunks, hipStream_t s);
 void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, PartSignals *zeroed, hipStream_t s);
-void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd, uint32_t n_chunks,
-                     uint32_t k, hipStream_t s);
 void launch_scan_l2(const L2 *in, uint32_t n_chunks, Carry *carry, L2 *out, L2 *tile_ws, uint32_t k, hipStream_t s);
 void launch_hist8(const uint8_t *table8, uint64_t n, unsigned long long *hist, hipStream_t s);
 
 // kmer_pack.hip -- the packed stream: one slot per 16 KiB text chunk
 constexpr uint32_t SLOT_CODE_WORDS = 1024;   // 16384 bases x 2 bits
 constexpr uint32_t SLOT_RST_WORDS = 512;     // 16384 restart bits
+constexpr uint32_t SQUEEZE_G_MAX = 256;      // chunks per workgroup of k_squeeze at most (make_part_plan): it looks at them one thread each
 
 // kmer_fuse.hip / kmer_part.hip -- partitioned table update
 struct PartPlan {
@@ -100,8 +99,13 @@ void part_set_attributes();
 void fuse_set_attributes();
 // The launchers take the plan, the view and what lives outside the workspace.  `carry`: its deep_in / deep_out words are
 // touched by k = 19, 21 only.
+// chunk_fix (one record per chunk) non-null: a counting feed -- the structure pass squeezes the settled chunks (ChunkFix,
+// fasta_fsm.h) into the slots of `b` itself, and the squeeze pass only completes them.  Null: a query feed, nothing is settled.
+void launch_chunk_l2(const uint8_t *fasta, uint64_t n, const L1 *st1, L2 *chunk_l2, LaneState *lane_state, PiecePack *packs, uint32_t *chunk_odd,
+                     ChunkFix *chunk_fix, const PartBuffers &b, uint32_t n_chunks, uint32_t k, hipStream_t s);
 void launch_squeeze(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, uint64_t stream_off, const LaneState *lane_state,
-                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, DevRec *recs, uint64_t recs_cap, Carry *carry, hipStream_t s);
+                    const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, const ChunkFix *chunk_fix, DevRec *recs, uint64_t recs_cap, Carry *carry,
+                    hipStream_t s);
 void launch_deep_tail(const PartPlan &pl, const PartBuffers &b, Carry *carry, hipStream_t s);
 void launch_provision(const PartPlan &pl, const PartBuffers &b, const L2 *st2, uint32_t stride, const Carry *carry, hipStream_t s);
 void launch_walk_sort(const PartPlan &pl, const PartBuffers &b, const L2 *st2, const Carry *carry, hipStream_t s);
