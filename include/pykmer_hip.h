@@ -270,6 +270,29 @@ int pk_extract_device(const void *const *dev_tables, int n_present, int n_absent
                       int device, double *kernel_seconds_out);
 int pk_extract_text(const void *dev_addr, uint64_t m, int k, void *dev_text_out, int device);
 
+/* ---- extract, as a table: the same selection over the same slices, handed back dense -- one byte per address, which is
+ * what a `.kin` holds, so the result can be fed to every tool that reads one (the `kmc_tools simple` / `jellyfish merge`
+ * family: pooled, intersected, united and subtracted samples, occupancy).  Arguments and refusals as pk_extract_device;
+ * with V(x) = { i present : min_count <= T_i[x] <= max_count }, so that p(x) = |V(x)|,
+ *   out[x] = 0                               if x is not selected
+ *   out[x] = min(255, sum_{i in V(x)} T_i[x])   op = PK_TABLE_SUM
+ *            min_{i in V(x)} T_i[x]              op = PK_TABLE_MIN
+ *            max_{i in V(x)} T_i[x]              op = PK_TABLE_MAX
+ *            |V(x)|                              op = PK_TABLE_COUNT   (<= 128)
+ * Only bytes inside the window take part (the count rows of pk_extract_device are raw bytes; these are not).  A selected
+ * address has p >= min_present >= 1 and every byte of V is >= 1, so out[x] >= 1 exactly on the selected addresses, for
+ * every op.  The saturating sum over the window 1-255 with min_present = 1 is the table of the pooled inputs, byte for
+ * byte: min(255, sum min(255, c_i)) = min(255, sum c_i).
+ * dev_table_out (device, n_slice bytes, 16-byte aligned, overlapping no input) receives out; no byte at or beyond n_slice
+ * is written.  dev_hist_accum (device, 256 u64, required, zeroed by the caller before the first slice) has the number of
+ * addresses with out[x] = v ADDED to word v for v = 1..255; word 0 is left alone (the zeros are the addresses less the
+ * other 255 words, as pk_table_stats derives them), so the slices of a table sum.  A bad op, a null or misaligned output
+ * and an output that overlaps an input are PK_ERR_ARG before anything is queued; n_slice = 0 is PK_OK and touches nothing. */
+enum { PK_TABLE_SUM = 0, PK_TABLE_MIN = 1, PK_TABLE_MAX = 2, PK_TABLE_COUNT = 3 };
+int pk_extract_table_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice,
+                            int min_count, int max_count, int min_present, int max_absent, int op,
+                            void *dev_table_out, void *dev_hist_accum, int device, double *kernel_seconds_out);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

@@ -72,6 +72,9 @@ _SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_double)]),
     "pk_extract_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    "pk_extract_table_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_double)]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -168,6 +171,11 @@ class DeviceBuffer:
         out = np.empty(n, dtype=np.uint8)
         _check(load().pk_dev_download(out.ctypes.data, ctypes.c_void_p(self.ptr + offset), n, self.device))
         return out
+
+    def download_into(self, out: np.ndarray, offset: int = 0) -> None:
+        """Bytes [offset, offset + out.size) into `out`, a writable contiguous uint8 array (e.g. a slice of a memmap)."""
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and offset + out.size <= self.n
+        _check(load().pk_dev_download(out.ctypes.data, ctypes.c_void_p(self.ptr + offset), out.size, self.device))
 
     def free(self):
         if getattr(self, "ptr", None):
@@ -463,6 +471,24 @@ def extract_device(dev_ptrs, n_present: int, n_slice: int, first_addr: int, min_
     if rc != PK_ERR_RECS_CAP:
         _check(rc)
     return int(count.value), rc == PK_OK and int(count.value) <= int(cap), secs.value
+
+
+TABLE_OPS = ("sum", "min", "max", "count")                  # PK_TABLE_SUM .. PK_TABLE_COUNT
+
+
+def extract_table_device(dev_ptrs, n_present: int, n_slice: int, min_count: int, max_count: int, min_present: int, max_absent: int, op,
+                         dev_table_out: int, dev_hist_accum: int, device: int = 0) -> float:
+    """pk_extract_table_device on device-resident slices (`n_present` present tables first, then the absent ones): the
+    selection as n_slice bytes at dev_table_out, reduced by `op` (a name of TABLE_OPS, or its number), and the counts of
+    the values 1..255 among them added to the 256 u64 at dev_hist_accum; returns kernel seconds."""
+    N = len(dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
+    secs = ctypes.c_double(0)
+    _check(load().pk_extract_table_device(ptrs, int(n_present), N - int(n_present), int(n_slice), int(min_count), int(max_count), int(min_present),
+                                          int(max_absent), TABLE_OPS.index(op) if isinstance(op, str) else int(op),
+                                          ctypes.c_void_p(dev_table_out) if dev_table_out else None,
+                                          ctypes.c_void_p(dev_hist_accum) if dev_hist_accum else None, device, ctypes.byref(secs)))
+    return secs.value
 
 
 def extract_text(dev_addr: int, m: int, k: int, dev_text_out: int, device: int = 0) -> None:

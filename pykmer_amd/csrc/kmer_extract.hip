@@ -14,6 +14,10 @@
 //                    aligned dword of it, gathering its four bytes T_i[x] from the tables, so the rows leave as dword
 //                    stores whatever P is (the range's unaligned ends, at most 3 bytes each, are byte stores)
 //   k_extract_text   m addresses -> m lines of k letters + '\n', 16 output bytes per thread
+// And the same selection as a dense table, one byte per address (a `.kin` made from `.kin`s):
+//   k_extract_table  a streaming map with k_extract_count's geometry: beside p and q a thread reduces the present bytes that
+//                    lie in the window (sum, min, max; the count is p itself) in 16-bit lanes, blanks the addresses that
+//                    are not selected and stores its 16 result bytes at once
 #include "pk_kernels.h"
 #include "gram_load.h"
 #include "wg_scan.h"
@@ -49,9 +53,29 @@ __device__ __forceinline__ uint32_t x_valid(uint32_t x, const ExtractParams &p) 
 // 1 in every byte of x that is not zero
 __device__ __forceinline__ uint32_t x_held(uint32_t x) { return ((((x & L4) + L4) | x) & H4) >> 7; }
 
-// The selection mask of addresses [off, off + 16): bit j for address off + j.  p and q are byte counters: with up to 128
-// tables a counter reaches 0x80, so the thresholds are compared on the extracted byte, not on a byte's high bit.  Bytes at
-// or beyond n read as 0: p = 0 < min_present, never selected.
+// The threshold test on the byte counters p and q of 16 addresses: bit j for address j.  With up to 128 tables a counter
+// reaches 0x80, so the thresholds are compared on the extracted byte, not on a byte's high bit.
+__device__ __forceinline__ uint32_t x_select16(const uint32_t (&p)[4], const uint32_t (&q)[4], const ExtractParams &ep) {
+    uint32_t mask = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < X_ADDR; j++) {
+        const uint32_t pj = (p[j >> 2] >> (8u * (j & 3u))) & 0xffu, qj = (q[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+        mask |= (uint32_t)(pj >= ep.min_present && qj <= ep.max_absent) << j;
+    }
+    return mask;
+}
+// q of addresses [off, off + 16) over the absent tables, added to the byte counters
+__device__ __forceinline__ void x_count_absent(const uint8_t *const *__restrict__ tables, uint32_t P, uint32_t A, uint64_t off, uint64_t n,
+                                               uint32_t (&q)[4]) {
+#pragma unroll 4
+    for (uint32_t t = P; t < P + A; t++) {
+        const uint4 x = load_half(tables[t], off, n);
+        q[0] += x_held(x.x); q[1] += x_held(x.y); q[2] += x_held(x.z); q[3] += x_held(x.w);
+    }
+}
+
+// The selection mask of addresses [off, off + 16): bit j for address off + j.  p and q are byte counters.  Bytes at or
+// beyond n read as 0: p = 0 < min_present, never selected.
 __device__ __forceinline__ uint32_t x_mask16(const uint8_t *const *__restrict__ tables, uint32_t P, uint32_t A, uint64_t off, uint64_t n,
                                              const ExtractParams &ep) {
     uint32_t p[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
@@ -60,18 +84,8 @@ __device__ __forceinline__ uint32_t x_mask16(const uint8_t *const *__restrict__ 
         const uint4 x = load_half(tables[t], off, n);
         p[0] += x_valid(x.x, ep); p[1] += x_valid(x.y, ep); p[2] += x_valid(x.z, ep); p[3] += x_valid(x.w, ep);
     }
-#pragma unroll 4
-    for (uint32_t t = P; t < P + A; t++) {
-        const uint4 x = load_half(tables[t], off, n);
-        q[0] += x_held(x.x); q[1] += x_held(x.y); q[2] += x_held(x.z); q[3] += x_held(x.w);
-    }
-    uint32_t mask = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < X_ADDR; j++) {
-        const uint32_t pj = (p[j >> 2] >> (8u * (j & 3u))) & 0xffu, qj = (q[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-        mask |= (uint32_t)(pj >= ep.min_present && qj <= ep.max_absent) << j;
-    }
-    return mask;
+    x_count_absent(tables, P, A, off, n, q);
+    return x_select16(p, q, ep);
 }
 
 // masks (nullable: the caller wants the count alone): one u16 per 16 addresses; wg_count[b] = selected addresses of workgroup b
@@ -163,6 +177,63 @@ __global__ __launch_bounds__(XT) void k_extract_write(const uint8_t *const *__re
     }
 }
 
+// ---- the selection as a table ----
+// Two 16-bit lanes per dword: the even bytes of a table dword in one accumulator, the odd bytes in another.  A sum over 128
+// tables reaches 128 * 255 = 32 640 < 2^16, so a lane never carries into its neighbour; min and max are the packed u16
+// instructions on the same lanes, and so is the clamp of the sum to 255.
+constexpr uint32_t LANES = 0x00ff00ffu;
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+// one table dword x, v = x_valid(x), into the accumulators of its even and odd bytes.  Bytes outside the window take no
+// part: they enter as the operation's identity, 0 for sum and max, 255 for min.
+template <int OP> __device__ __forceinline__ void x_reduce(uint32_t x, uint32_t v, uint32_t &even, uint32_t &odd) {
+    const uint32_t in = v * 0xffu;               // 0xff in every byte inside the window (v holds 0 or 1 per byte: no carries)
+    if (OP == TABLE_SUM) { x &= in; even += x & LANES; odd += (x >> 8) & LANES; }
+    if (OP == TABLE_MIN) { x |= ~in; even = pk_min_u16(even, x & LANES); odd = pk_min_u16(odd, (x >> 8) & LANES); }
+    if (OP == TABLE_MAX) { x &= in; even = pk_max_u16(even, x & LANES); odd = pk_max_u16(odd, (x >> 8) & LANES); }
+}
+
+// out[off .. off + 16) for off < n, cut at n.  Bytes at or beyond n read as 0 and are not stored.
+template <int OP> __global__ __launch_bounds__(XT) void k_extract_table(const uint8_t *const *__restrict__ tables, uint32_t P, uint32_t A, uint64_t n,
+                                                                        ExtractParams ep, uint8_t *__restrict__ out) {
+    constexpr uint32_t ID = OP == TABLE_MIN ? LANES : 0u;
+    for (uint32_t s = 0; s < X_STEPS; s++) {
+        const uint64_t off = (uint64_t)blockIdx.x * X_WG + (uint64_t)s * X_TILE + (uint64_t)threadIdx.x * X_ADDR;
+        if (off >= n) break;
+        uint32_t p[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+        uint32_t even[4] = {ID, ID, ID, ID}, odd[4] = {ID, ID, ID, ID};
+#pragma unroll 4
+        for (uint32_t t = 0; t < P; t++) {
+            const uint4 x = load_half(tables[t], off, n);
+            const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                const uint32_t v = x_valid(xs[d], ep);
+                p[d] += v;
+                x_reduce<OP>(xs[d], v, even[d], odd[d]);
+            }
+        }
+        x_count_absent(tables, P, A, off, n, q);
+        const uint32_t mask = x_select16(p, q, ep);
+        uint32_t r[4];
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const uint32_t m4 = (mask >> (4 * d)) & 0xfu;                                        // the dword's four selection bits ...
+            const uint32_t sel = ((m4 & 1u) | ((m4 & 2u) << 7) | ((m4 & 4u) << 14) | ((m4 & 8u) << 21)) * 0xffu;   // ... as 0xff bytes
+            if (OP == TABLE_COUNT) r[d] = p[d] & sel;                                             // p <= 128 fits its byte
+            else if (OP == TABLE_SUM) r[d] = (pk_min_u16(even[d], LANES) | (pk_min_u16(odd[d], LANES) << 8)) & sel;
+            else r[d] = (even[d] | (odd[d] << 8)) & sel;   // a selected address has a byte in the window: no identity is left
+        }
+        if (off + X_ADDR <= n) *(uint4 *)(out + off) = make_uint4(r[0], r[1], r[2], r[3]);
+        else for (uint64_t i = off; i < n; i++) out[i] = (uint8_t)(r[(i - off) >> 2] >> (8u * ((i - off) & 3u)));
+    }
+}
+
 // text bytes [0, m * (k + 1)): line r holds the k letters of addr[r], first base in the highest bits, then '\n'
 __global__ __launch_bounds__(XT) void k_extract_text(const unsigned long long *__restrict__ addr, uint64_t m, uint32_t k, uint8_t *__restrict__ text) {
     const uint64_t total = m * (k + 1u);
@@ -185,9 +256,7 @@ __global__ __launch_bounds__(XT) void k_extract_text(const unsigned long long *_
 uint32_t extract_workgroups(uint64_t n_slice) { return (uint32_t)((n_slice + X_WG - 1) / X_WG); }
 uint64_t extract_mask_words(uint64_t n_slice) { return (n_slice + X_ADDR - 1) / X_ADDR; }
 
-int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, uint64_t first_addr, int min_count, int max_count, int min_present,
-                   int max_absent, uint16_t *masks, unsigned long long *wg, unsigned long long *addr_out, uint8_t *counts_out, uint64_t cap,
-                   hipStream_t s) {
+static ExtractParams extract_params(int min_count, int max_count, int min_present, int max_absent) {
     ExtractParams ep;
     ep.lo_rep = (uint32_t)(min_count & 0x7f) * 0x01010101u;
     ep.lo_hi = min_count >= 128;
@@ -196,6 +265,13 @@ int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_sl
     ep.has_up = max_count < 255;
     ep.min_present = (uint32_t)min_present;
     ep.max_absent = (uint32_t)max_absent;
+    return ep;
+}
+
+int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, uint64_t first_addr, int min_count, int max_count, int min_present,
+                   int max_absent, uint16_t *masks, unsigned long long *wg, unsigned long long *addr_out, uint8_t *counts_out, uint64_t cap,
+                   hipStream_t s) {
+    const ExtractParams ep = extract_params(min_count, max_count, min_present, max_absent);
     const uint32_t n_wg = extract_workgroups(n_slice);
     const bool write = cap > 0;
     hipLaunchKernelGGL(k_extract_count, dim3(n_wg), dim3(XT), 0, s, dev_tables, (uint32_t)P, (uint32_t)A, n_slice, ep, write ? masks : nullptr, wg);
@@ -203,6 +279,24 @@ int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_sl
     if (write)
         hipLaunchKernelGGL(k_extract_write, dim3(n_wg), dim3(XT), 0, s, dev_tables, (uint32_t)P, n_slice, first_addr, (const uint16_t *)masks,
                            (const unsigned long long *)wg, n_wg, cap, addr_out, counts_out);
+    return hipGetLastError() != hipSuccess;
+}
+
+template <int OP> static void launch_table_op(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, const ExtractParams &ep, uint8_t *out,
+                                              hipStream_t s) {
+    hipLaunchKernelGGL(k_extract_table<OP>, dim3(extract_workgroups(n_slice)), dim3(XT), 0, s, dev_tables, (uint32_t)P, (uint32_t)A, n_slice, ep, out);
+}
+
+int launch_extract_table(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, int min_count, int max_count, int min_present,
+                         int max_absent, int op, uint8_t *table_out, hipStream_t s) {
+    const ExtractParams ep = extract_params(min_count, max_count, min_present, max_absent);
+    switch (op) {
+    case TABLE_SUM: launch_table_op<TABLE_SUM>(dev_tables, P, A, n_slice, ep, table_out, s); break;
+    case TABLE_MIN: launch_table_op<TABLE_MIN>(dev_tables, P, A, n_slice, ep, table_out, s); break;
+    case TABLE_MAX: launch_table_op<TABLE_MAX>(dev_tables, P, A, n_slice, ep, table_out, s); break;
+    case TABLE_COUNT: launch_table_op<TABLE_COUNT>(dev_tables, P, A, n_slice, ep, table_out, s); break;
+    default: return 1;
+    }
     return hipGetLastError() != hipSuccess;
 }
 

@@ -215,6 +215,12 @@ uint64_t extract_mask_words(uint64_t n_slice);
 int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, uint64_t first_addr, int min_count, int max_count, int min_present,
                    int max_absent, uint16_t *masks, unsigned long long *wg, unsigned long long *addr_out, uint8_t *counts_out, uint64_t cap,
                    hipStream_t s);
+// The same selection as a dense table: out[x] (n_slice bytes, 16-byte aligned, no input) = 0 where x is not selected, else
+// the reduction `op` (TABLE_SUM .. TABLE_COUNT) over the present bytes inside the window; nothing at or beyond n_slice is
+// written.  One launch, no scratch.
+enum TableOp : int { TABLE_SUM = 0, TABLE_MIN = 1, TABLE_MAX = 2, TABLE_COUNT = 3 };
+int launch_extract_table(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, int min_count, int max_count, int min_present,
+                         int max_absent, int op, uint8_t *table_out, hipStream_t s);
 // m addresses -> m lines of k letters + '\n' (text 16-byte aligned)
 int launch_extract_text(const unsigned long long *addr, uint64_t m, int k, uint8_t *text, hipStream_t s);
 

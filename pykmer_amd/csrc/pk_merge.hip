@@ -197,19 +197,27 @@ extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N
     });
 }
 
-// The k-mers behind a presence / absence condition (kmer_extract.hip): count, scan and -- when the caller's arrays hold
-// the total -- write, all queued behind each other; the host only reads the total back.
-extern "C" int pk_extract_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice, uint64_t first_addr,
-                                 int min_count, int max_count, int min_present, int max_absent, void *dev_addr_out, void *dev_counts_out,
-                                 uint64_t cap, uint64_t *n_selected_out, int device, double *kernel_seconds_out) {
+// what pk_extract_device and pk_extract_table_device refuse alike
+static int check_extract(int n_present, int n_absent, uint64_t n_slice, int min_count, int max_count, int min_present, int max_absent) {
     if (n_present < 1 || n_absent < 0 || n_present > 128 || n_absent > 128 || n_present + n_absent > 128)
         return fail(PK_ERR_ARG, "an extraction takes 1 to 128 tables, at least one of them present (got %d present, %d absent)", n_present, n_absent);
     if (min_count < 1 || max_count > 255 || min_count > max_count)
         return fail(PK_ERR_ARG, "the count window must satisfy 1 <= min <= max <= 255 (got %d-%d)", min_count, max_count);
     if (min_present < 1 || min_present > n_present) return fail(PK_ERR_ARG, "min_present must lie in 1..%d (got %d)", n_present, min_present);
     if (max_absent < 0 || max_absent > n_absent) return fail(PK_ERR_ARG, "max_absent must lie in 0..%d (got %d)", n_absent, max_absent);
+    if (n_slice > (1ull << 40)) return fail(PK_ERR_ARG, "slice of %llu addresses is out of range", (unsigned long long)n_slice);
+    return PK_OK;
+}
+
+// The k-mers behind a presence / absence condition (kmer_extract.hip): count, scan and -- when the caller's arrays hold
+// the total -- write, all queued behind each other; the host only reads the total back.
+extern "C" int pk_extract_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice, uint64_t first_addr,
+                                 int min_count, int max_count, int min_present, int max_absent, void *dev_addr_out, void *dev_counts_out,
+                                 uint64_t cap, uint64_t *n_selected_out, int device, double *kernel_seconds_out) {
+    int rc = check_extract(n_present, n_absent, n_slice, min_count, max_count, min_present, max_absent);
+    if (rc) return rc;
     if (!n_selected_out) return fail(PK_ERR_ARG, "null n_selected_out");
-    if (n_slice > (1ull << 40) || first_addr + n_slice < first_addr) return fail(PK_ERR_ARG, "slice of %llu addresses is out of range", (unsigned long long)n_slice);
+    if (first_addr + n_slice < first_addr) return fail(PK_ERR_ARG, "slice of %llu addresses is out of range", (unsigned long long)n_slice);
     if (cap && (!dev_addr_out || !dev_counts_out || ((uintptr_t)dev_addr_out & 15u) || ((uintptr_t)dev_counts_out & 15u)))
         return fail(PK_ERR_ARG, "a capacity needs both output arrays, 16-byte aligned");
     if (cap > (1ull << 40)) return fail(PK_ERR_ARG, "capacity out of range");
@@ -223,7 +231,7 @@ extern "C" int pk_extract_device(const void *const *dev_tables, int n_present, i
         *n_selected_out = 0;
         return PK_OK;
     }
-    int rc = timed_pass(
+    rc = timed_pass(
         "extract", dev_tables, N, device, kernel_seconds_out,
         [&](GramCtx &c) -> int {
             int r = upload_pointers(dev_tables, N)(c);
@@ -244,6 +252,31 @@ extern "C" int pk_extract_device(const void *const *dev_tables, int n_present, i
     if (total > cap && (cap || dev_addr_out || dev_counts_out))
         return fail(PK_ERR_RECS_CAP, "%llu addresses selected, room for %llu", total, (unsigned long long)cap);
     return PK_OK;
+}
+
+// The same selection as a dense table (k_extract_table), and the table's value histogram behind it on the same stream.
+extern "C" int pk_extract_table_device(const void *const *dev_tables, int n_present, int n_absent, uint64_t n_slice, int min_count, int max_count,
+                                       int min_present, int max_absent, int op, void *dev_table_out, void *dev_hist_accum, int device,
+                                       double *kernel_seconds_out) {
+    int rc = check_extract(n_present, n_absent, n_slice, min_count, max_count, min_present, max_absent);
+    if (rc) return rc;
+    if (op < PK_TABLE_SUM || op > PK_TABLE_COUNT) return fail(PK_ERR_ARG, "op must be 0..3 = sum, min, max, count (got %d)", op);
+    if (!dev_table_out || ((uintptr_t)dev_table_out & 15u)) return fail(PK_ERR_ARG, "the output table must not be null and must be 16-byte aligned");
+    if (!dev_hist_accum || ((uintptr_t)dev_hist_accum & 7u)) return fail(PK_ERR_ARG, "the histogram accumulator must not be null and must be 8-byte aligned");
+    if (!dev_tables) return fail(PK_ERR_ARG, "null table list");
+    const int N = n_present + n_absent;
+    const uintptr_t o0 = (uintptr_t)dev_table_out, o1 = o0 + n_slice;
+    for (int i = 0; i < N; i++)
+        if (dev_tables[i] && (uintptr_t)dev_tables[i] < o1 && o0 < (uintptr_t)dev_tables[i] + n_slice)
+            return fail(PK_ERR_ARG, "the output table overlaps table %d", i);
+    if (n_slice == 0) return PK_OK;
+    return timed_pass("extract table", dev_tables, N, device, kernel_seconds_out, upload_pointers(dev_tables, N), [&](GramCtx &c) {
+        if (launch_extract_table(c.d_ptrs, n_present, n_absent, n_slice, min_count, max_count, min_present, max_absent, op, (uint8_t *)dev_table_out,
+                                 c.stream))
+            return 1;
+        launch_hist8((const uint8_t *)dev_table_out, n_slice, (unsigned long long *)dev_hist_accum, c.stream);
+        return (int)(hipGetLastError() != hipSuccess);
+    });
 }
 
 extern "C" int pk_extract_text(const void *dev_addr, uint64_t m, int k, void *dev_text_out, int device) {

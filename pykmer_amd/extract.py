@@ -13,8 +13,15 @@ README stops at the distance matrix); no table is written or changed.
 The tables are staged in HBM slice by slice as the merger stages them (staging.staged_pieces); one streaming pass per piece
 (pk_extract_device) compacts the selected addresses and their count rows in HBM, and pk_extract_text turns the addresses
 into letters there.  One device (PK_DEVICE).
+
+The same selection as a table (combine_tables, `--table OP`): one byte per address, 0 where x is not selected, else the
+reduction OP over V(x) = { i present : min <= T_i[x] <= max } -- the bytes inside the window, not the raw rows --
+    sum: min(255, sum of T_i[x])    min / max: the smallest / largest T_i[x]    count: |V(x)| = p(x)
+written as a `.kin` + `.kin.json` that every tool reads (pk_extract_table_device, one streaming map per piece).  out[x] >= 1
+exactly on the selected addresses.
 """
 import argparse
+import hashlib
 import os
 import sys
 from pathlib import Path
@@ -24,6 +31,7 @@ import numpy as np
 
 from . import _lib, staging
 from .indexer import _mark
+from .header import Header
 from .merger import DEFAULT_THREADS
 from .output import atomic_write, write_json
 from .query import load_header
@@ -33,6 +41,8 @@ MAX_TABLES = 128                    # P + A: what one pk_extract_device call tak
 PIECE_ALIGN = 2048                  # addresses: what the cuts of a piece are multiples of (and what always fits the output)
 INITIAL_ROWS = 1 << 22              # output rows the first call has room for (fewer if the output budget holds fewer)
 OUTPUT_SHARE = 8                    # the output arrays get 1 / OUTPUT_SHARE of the HBM budget, the staged slices the rest
+OPS = _lib.TABLE_OPS                # ("sum", "min", "max", "count"): what combine_tables / --table reduce the present bytes with
+HIST_BYTES = 256 * 8                # the value histogram of a combined table, kept in HBM across the pieces
 
 
 def _kmer_len_of(table) -> int:
@@ -54,6 +64,12 @@ def _file_of(table):
 
 def kmx_paths(project_name: str) -> Tuple[Path, Path, Path]:
     return Path(f"{project_name}.kmx"), Path(f"{project_name}.kmx.json"), Path(f"{project_name}.kmx.txt")
+
+
+def _refuse_existing(files) -> None:
+    for f in files:
+        if Path(f).exists():
+            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
 
 
 def validate(present: Sequence, absent: Sequence, min_count: int = 1, max_count: int = 255, min_present: int = None, max_absent: int = 0,
@@ -80,9 +96,7 @@ def validate(present: Sequence, absent: Sequence, min_count: int = 1, max_count:
         if files.count(f) > 1:
             raise ValueError(f"{f} is named twice: a table is present or absent, and listed once")
     if project_name is not None:
-        for f in kmx_paths(project_name):
-            if f.exists():
-                raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+        _refuse_existing(kmx_paths(project_name))
     return kmer_len, min_present
 
 
@@ -202,7 +216,100 @@ def extract_kmers(present: Sequence, absent: Sequence = (), min_count: int = 1, 
     return result
 
 
+class TableCall:
+    """pk_extract_table_device on one staged piece, with the piece's output slice and the table's value histogram in HBM.
+    call(ptrs, a, b, out) fills out[a:b] (downloaded straight into it); call.hist256() is the histogram of everything
+    written so far, zeros included.  combine_tables' `call=` substitutes anything of this shape."""
+
+    def __init__(self, n_present: int, op: str, min_count: int, max_count: int, min_present: int, max_absent: int, device: int = 0):
+        self.P, self.op, self.device = n_present, op, device
+        self.params = (min_count, max_count, min_present, max_absent)
+        self.slice, self.hist, self.addresses, self.kernel_seconds = None, None, 0, 0.0
+
+    def free(self):
+        for b in (self.slice, self.hist):
+            if b is not None:
+                b.free()
+        self.slice = self.hist = None
+
+    def __call__(self, ptrs, a: int, b: int, out: np.ndarray) -> None:
+        n = b - a
+        if self.hist is None:
+            self.hist = _lib.DeviceBuffer(HIST_BYTES, self.device)
+            self.hist.zero()
+        if self.slice is None or self.slice.n < n:
+            if self.slice is not None:
+                self.slice.free()                            # first: the old and the new slice need not fit beside each other
+            self.slice = _lib.DeviceBuffer((n + 15) & ~15, self.device)
+        self.kernel_seconds += _lib.extract_table_device(ptrs, self.P, n, *self.params, self.op, self.slice.ptr, self.hist.ptr, device=self.device)
+        self.slice.download_into(out[a:b])
+        self.addresses += n
+        _mark(f"addresses {a}..{b - 1}: table bytes downloaded")
+
+    def hist256(self) -> np.ndarray:
+        hist = np.zeros(256, dtype=np.uint64) if self.hist is None else self.hist.download().view(np.uint64).copy()
+        hist[0] = self.addresses - int(hist[1:].sum())       # the device tallies the values 1 .. 255
+        return hist
+
+
+def stage_table_pieces(tables: Sequence, lo: int, hi: int, device: int, threads: int, reserve: int, budget: int):
+    """stage_pieces with room for one more slice beside the N staged ones: the output's."""
+    return staging.staged_pieces(tables, staging.piece_cuts(tables, lo, hi, len(tables) + 1, device, reserve, budget), device, threads)
+
+
+def combine_tables(present: Sequence, absent: Sequence = (), op: str = "sum", min_count: int = 1, max_count: int = 255, min_present: int = None,
+                   max_absent: int = 0, out: np.ndarray = None, device: int = 0, hbm_budget: int = None, threads: int = DEFAULT_THREADS,
+                   stage=None, call=None) -> dict:
+    """The selection of `present` / `absent` (as extract_kmers takes them) as a table of 4^k bytes: 0 where an address is
+    not selected, else `op` (one of OPS) over the present bytes inside the window.  Returns dict(table -- `out`, a writable
+    uint8 array or memmap of 4^k bytes, or a fresh array --, hist256 (256,) uint64, n_selected (its non-zero bytes), op,
+    kmer_len, min_count, max_count, min_present, max_absent, n_present, n_absent, n_pieces, kernel_seconds).
+
+    The pieces are cut so that the P + A slices and one output slice fit `hbm_budget` (as extract_kmers reads it) beside
+    each other; every piece is one device call and one download into out[a:b], and the histogram stays in HBM until the
+    last.  `stage(tables, lo, hi, device, threads, reserve, budget)` and `call` (see TableCall) default to
+    stage_table_pieces and a TableCall."""
+    if op not in OPS:
+        raise ValueError(f"unknown table operation {op!r}: expected one of {', '.join(OPS)}")
+    present = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in present]
+    absent = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in absent]
+    kmer_len, min_present = validate(present, absent, min_count, max_count, min_present, max_absent)
+    size = 4 ** kmer_len
+    if out is None:
+        out = np.empty(size, dtype=np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == (size,) and out.flags.c_contiguous and out.flags.writeable):
+        raise ValueError(f"out must be a writable contiguous uint8 array of 4^{kmer_len} = {size} bytes")
+    tables, P = present + absent, len(present)
+    own = None
+    if call is None:
+        call = own = TableCall(P, op, min_count, max_count, min_present, int(max_absent), device=device)
+    pieces = (stage or stage_table_pieces)(tables, 0, size, device, threads, HIST_BYTES, hbm_budget)
+    n_pieces = 0
+    try:
+        for ptrs, a, b in pieces:
+            _mark(f"addresses {a}..{b - 1} staged")
+            n_pieces += 1
+            call(ptrs, a, b, out)
+        hist = np.ascontiguousarray(call.hist256(), dtype=np.uint64)
+    finally:
+        getattr(pieces, "close", lambda: None)()             # a generator frees its slice buffers now, not when it is collected
+        if own is not None:
+            own.free()
+    assert hist.shape == (256,) and int(hist.sum()) == size, "the histogram does not cover the table"
+    return {"table": out, "hist256": hist, "n_selected": size - int(hist[0]), "op": op, "kmer_len": kmer_len, "min_count": int(min_count),
+            "max_count": int(max_count), "min_present": min_present, "max_absent": int(max_absent), "n_present": P, "n_absent": len(absent),
+            "n_pieces": n_pieces, "kernel_seconds": own.kernel_seconds if own is not None else 0.0}
+
+
 SCALARS = ("kmer_len", "min_count", "max_count", "min_present", "max_absent", "n_present", "n_absent")
+
+
+def write_kmx_json(project_name: str, result: dict, data: list, **more) -> None:
+    """`<project>.kmx.json`: the scalars, n_selected, the tables' metadata (present tables first) and whatever `more` holds."""
+    assert len(data) == int(result["n_present"]) + int(result["n_absent"])
+    output = {"project_name": project_name, "n_selected": int(result["n_selected"]), "data": data, **more}
+    output.update({key: int(result[key]) for key in SCALARS})
+    write_json(kmx_paths(project_name)[1], output)
 
 
 def write_kmx(project_name: str, result: dict, data: list) -> None:
@@ -212,10 +319,8 @@ def write_kmx(project_name: str, result: dict, data: list) -> None:
     kmx, meta, txt = kmx_paths(project_name)
     addr = np.ascontiguousarray(result["addr"], dtype=np.uint64)
     counts = np.ascontiguousarray(result["counts"], dtype=np.uint8)
-    assert counts.shape == (addr.size, int(result["n_present"])) and len(data) == int(result["n_present"]) + int(result["n_absent"])
-    output = {"project_name": project_name, "n_selected": int(addr.size), "data": data}
-    output.update({key: int(result[key]) for key in SCALARS})
-    write_json(meta, output)
+    assert counts.shape == (addr.size, int(result["n_present"]))
+    write_kmx_json(project_name, dict(result, n_selected=addr.size), data)
     if result.get("text") is not None:
         lines = np.ascontiguousarray(result["text"], dtype=np.uint8)
         assert lines.shape == (addr.size, int(result["kmer_len"]) + 1)
@@ -225,19 +330,72 @@ def write_kmx(project_name: str, result: dict, data: list) -> None:
         np.savez_compressed(fhd, addr=addr, counts=counts, **{key: np.int64(result[key]) for key in SCALARS})
 
 
+def table_paths(project_name: str, kmer_len: int) -> Tuple[Path, Path, Path]:
+    """What `--table` writes: `<project>.<KK>.kin`, its `.kin.json` and `<project>.kmx.json`."""
+    kin = f"{project_name}.{kmer_len:02d}.{Header.IND_EXT}"
+    return Path(kin), Path(f"{kin}.{Header.DESC_EXT}"), kmx_paths(project_name)[1]
+
+
+def write_table(project_name: str, op: str, data: list, device: int, **combine) -> dict:
+    """combine_tables straight into `<project>.<KK>.kin.tmp`, renamed once it is complete, then its `.kin.json`
+    (Header.write_derived_metadata_file) and `<project>.kmx.json`.  `data`: the table entries, Headers still in them.  An
+    empty selection is an error (a `.kin.json` asserts a non-zero num_kmers); no file is left behind when the pass fails."""
+    headers = [v["header"] for v in data]
+    n_present = sum(v["role"] == "present" for v in data)
+    kmer_len = int(headers[0].kmer_len)
+    kin = table_paths(project_name, kmer_len)[0]
+    _refuse_existing(table_paths(project_name, kmer_len) + (Path(f"{kin}.{Header.COMP_EXT}"),))   # a .kin.bgz would be read in the .kin's place
+    header = Header(os.path.basename(project_name), input_file=project_name, kmer_len=kmer_len, device=device)
+    tmp = Path(f"{kin}.{Header.TMP}")
+    print(f"saving {kin}")
+    table = None
+    try:
+        table = np.memmap(tmp, dtype=np.uint8, mode="w+", shape=(4 ** kmer_len,))
+        result = combine_tables(headers[:n_present], headers[n_present:], op=op, out=table, device=device, **combine)
+        if result["n_selected"] == 0:
+            raise ValueError(f"no k-mer is selected (count window {result['min_count']}-{result['max_count']}, min_present {result['min_present']} "
+                             f"of {result['n_present']}, max_absent {result['max_absent']} of {result['n_absent']}): no table is written")
+        table.flush()
+        sha = hashlib.sha256()
+        for at in range(0, table.size, 1 << 24):
+            sha.update(table[at:at + (1 << 24)])
+        del result["table"]                                  # the mapping goes before the file is renamed
+        table = None
+        tmp.rename(kin)
+    except BaseException:
+        table = None
+        tmp.unlink(missing_ok=True)
+        raise
+    _mark("table written")
+    sources = [(f"{v['role']}:{v['header'].project_name}", v["header"].num_kmers) for v in data]
+    header.write_derived_metadata_file(str(kin), result["hist256"], sources, checksum=sha.hexdigest())
+    lean_headers(data)
+    write_kmx_json(project_name, result, data, table=op, table_file=kin)
+    result["table_file"] = str(kin)
+    return result
+
+
 def extract(project_name: str, present: List[Path], absent: List[Path] = (), min_count: int = 1, max_count: int = 255, min_present: int = None,
-            max_absent: int = 0, kmers: bool = False, device: int = 0, threads: int = DEFAULT_THREADS, hbm_budget: int = None) -> dict:
-    """The CLI's work: validate, extract, write the files; returns extract_kmers' result."""
-    for f in kmx_paths(project_name):
-        if f.exists():
-            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+            max_absent: int = 0, kmers: bool = False, device: int = 0, threads: int = DEFAULT_THREADS, hbm_budget: int = None, table: str = None) -> dict:
+    """The CLI's work: validate, extract, write the files; returns extract_kmers' result -- or, with `table` (one of OPS),
+    write_table's: the selection as `<project>.<KK>.kin` instead of the `.kmx` list."""
+    if table is not None and table not in OPS:
+        raise ValueError(f"unknown table operation {table!r}: expected one of {', '.join(OPS)}")
+    if table is not None and kmers:
+        raise ValueError("--table writes a table and no k-mer list: it cannot be combined with --kmers")
+    _refuse_existing(kmx_paths(project_name)[1:2] if table else kmx_paths(project_name))
     data = []
     for role, kins in (("present", present), ("absent", absent)):
         for kin in kins:
             data.append(table_entry(len(data), kin, lambda kin: load_header(kin, device), role=role))
     headers, n_present = [v["header"] for v in data], len(list(present))
-    validate(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, project_name=project_name)
+    validate(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, project_name=None if table else project_name)
     _mark("tables verified")
+    if table is not None:
+        result = write_table(project_name, table, data, device, min_count=min_count, max_count=max_count, min_present=min_present,
+                             max_absent=max_absent, hbm_budget=hbm_budget, threads=threads)
+        _mark("files renamed")
+        return result
     result = extract_kmers(headers[:n_present], headers[n_present:], min_count, max_count, min_present, max_absent, device=device,
                            hbm_budget=hbm_budget, threads=threads, text=kmers)
     lean_headers(data)
@@ -256,6 +414,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--min-present", type=int, default=None, help="present tables that must hold the k-mer [all of them]")
     parser.add_argument("--max-absent", type=int, default=0, help="absent tables that may hold it all the same [0]")
     parser.add_argument("--kmers", action="store_true", help="also write <P>.kmx.txt: the k-mers as letters, one per line")
+    parser.add_argument("--table", choices=OPS, default=None,
+                        help="write the selection as a table, <P>.<KK>.kin + .kin.json, instead of the .kmx list: per selected k-mer the sum "
+                             "(saturating at 255), min or max of the present counts inside the window, or the number of such tables")
     parser.add_argument("--threads", type=int, default=DEFAULT_THREADS, help=f"Host threads reading / inflating the tables [{DEFAULT_THREADS}]")
     return parser
 
@@ -265,12 +426,12 @@ def main(argv: List[str] = None) -> None:
     try:
         result = extract(args.Project_Name, args.present, args.absent, min_count=args.min_count, max_count=args.max_count,
                          min_present=args.min_present, max_absent=args.max_absent, kmers=args.kmers,
-                         device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads)
+                         device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, table=args.table)
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)
     print(f"{result['n_selected']:,d} k-mers selected, {result['n_present']} present + {result['n_absent']} absent tables, "
-          f"{result['n_pieces']} staged piece(s)")
+          f"{result['n_pieces']} staged piece(s)" + (f", table {result['table_file']} ({result['op']})" if args.table else ""))
 
 
 if __name__ == "__main__":

@@ -267,9 +267,13 @@ class Header(HeaderVars):
         self.input_file_size = os.path.getsize(self.input_file_path)
         self.input_file_ctime = os.path.getctime(self.input_file_path)
         self.input_file_cheksum = checksums.get("input") or gen_checksum(self.input_file_path)
+        self._stamp_output(index_file, checksums.get("output"))
+
+    def _stamp_output(self, index_file: str, checksum: str = None) -> None:
+        """The fields of update_metadata that describe the table file, this machine and the run (tools.py:279-291)."""
         self.output_file_size = os.path.getsize(index_file)
         self.output_file_ctime = os.path.getctime(index_file)
-        self.output_file_cheksum = checksums.get("output") or gen_checksum(index_file)
+        self.output_file_cheksum = checksum or gen_checksum(index_file)
         self.hostname = socket.gethostname()
         # the reference hashes `tools.py` found in the cwd (tools.py:285); this build hashes its own format module
         self.checksum_script = gen_checksum(os.path.abspath(__file__))
@@ -373,6 +377,24 @@ class Header(HeaderVars):
         else:
             for fhd in self.open_file(index_file):
                 self.update_stats(fhd)
+        with open(self.metadata_file, "wt") as fhm:
+            json.dump(self.to_dict(), fhm, indent=1, sort_keys=1)
+
+    def write_derived_metadata_file(self, index_file: str, hist256, sources, checksum: str = None) -> None:
+        """The `.kin.json` of a table computed from other tables (extract.py --table) instead of counted from a sequence
+        file: all 33 keys, so that Header(index_file=...) here and in the reference loads it.  There is no input file: its
+        name and path are what the table's file name parses to, its size, ctime and checksum are null.  `hist256`: the
+        table's value histogram; num_kmers = the sum of the table's bytes (vals_sum).  `sources`: (name, num_kmers) of every
+        table it was computed from, in order: the `chromosomes` list.  `checksum`: the sha256 of the table's bytes if the
+        caller has it."""
+        self.update_stats_from_hist256(hist256)
+        self.num_kmers = self.vals_sum
+        self.chromosomes = [[str(name), int(num_kmers)] for name, num_kmers in sources]
+        assert self.num_kmers
+        assert self.chromosomes
+        self.input_file_size = self.input_file_ctime = self.input_file_cheksum = None
+        self.timer.update(self.data_size)                     # creation_speed: addresses per second
+        self._stamp_output(index_file, checksum)
         with open(self.metadata_file, "wt") as fhm:
             json.dump(self.to_dict(), fhm, indent=1, sort_keys=1)
 
