@@ -97,6 +97,15 @@ int pk_indexer_reset(pk_indexer *ix);                       /* zero the table, f
 int pk_indexer_set_format(pk_indexer *ix, int format);
 /* FASTQ indexers: out = { records, lines, FASTQ bytes fed, FASTA bytes emitted to the counting pipeline }. */
 int pk_indexer_fastq_stats(pk_indexer *ix, uint64_t out[4]);
+/* Base qualities of a FASTQ indexer or query (README "Base quality"): threshold_byte T = Q + offset, 1 .. 255; 0 (the
+ * default) is off.  Byte i of a record's line 2 counts as 'N' when byte i of its line 4 is < T as an unsigned byte, unless it
+ * is one of the ten str.strip() blanks; nothing else of the stream changes (lengths, names, positions, the malformed-file
+ * rules).  After pk_indexer_set_format(FASTQ) and before the first feed (PK_ERR_STATE otherwise; PK_ERR_ARG outside
+ * 0 .. 255); it persists across resets, and setting the format back to FASTA turns it off.  The result does not depend on
+ * how the stream is cut into feeds: the text of a record is held back on the device until its line 4 has gone by. */
+int pk_indexer_set_min_qual(pk_indexer *ix, int threshold_byte);
+/* FASTQ indexers: the line-2 bytes replaced so far (a low-quality 'N' counts too); 0 with the threshold off. */
+int pk_indexer_fastq_masked(pk_indexer *ix, uint64_t *out);
 /* Feed the next n_bytes of the FASTA text.  Chunks may split lines, records and k-mers anywhere.   */
 int pk_indexer_feed(pk_indexer *ix, const uint8_t *host_fasta, uint64_t n_bytes);
 /* Same, but the bytes already sit in device memory on the indexer's device (16-byte aligned).  Work runs on

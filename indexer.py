@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """indexer.py <input.fa[.gz|.bgz]> <sample_name> <kmer_len>   (also: indexer.py <input.fa> <kmer_len>)
+                                       [--min-qual Q] [--qual-offset 33|64]   (FASTQ input: README "Base quality")
 
 Drop-in for the reference's indexer.py CLI (indexer.py:475-495): writes `<abs input>.<kk>.kin` and
 `<abs input>.<kk>.kin.json` next to the input.  The k-mer counting runs on an MI355X through

@@ -35,6 +35,8 @@ _SIGNATURES = {
     "pk_indexer_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "pk_indexer_set_format": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pk_indexer_fastq_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_indexer_set_min_qual": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_indexer_fastq_masked": (ctypes.c_int, [ctypes.c_void_p, _u64p]),
     "pk_indexer_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_indexer_feed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_indexer_finish": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, ctypes.c_void_p, _u64p]),
@@ -187,21 +189,26 @@ class DeviceBuffer:
 
 class Indexer:
     """One 4^k count table resident in HBM on one device (pk_indexer_*).  fmt: what the feeds hold, "fasta" or "fastq"
-    (pk_indexer_set_format; it stays across resets)."""
+    (pk_indexer_set_format; it stays across resets).  min_qual_byte: FASTQ only, the threshold byte Q + offset below which a
+    base counts as N (pk_indexer_set_min_qual; 0 = off; it stays across resets too)."""
 
     TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "partition_s", "bucket_s", "walk_sort_s", "relayouts",
                "buckets_recounted")
     COUNTERS = ("feeds", "relayouts", "buckets_recounted")   # of TIMINGS: integers, not seconds
 
-    def __init__(self, k: int, device: int = 0, slice_index: int = 0, n_slices: int = 1, fmt: str = "fasta"):
+    def __init__(self, k: int, device: int = 0, slice_index: int = 0, n_slices: int = 1, fmt: str = "fasta", min_qual_byte: int = 0):
         if fmt not in FORMATS:
             raise ValueError(f"unknown input format {fmt!r}: expected one of {sorted(FORMATS)}")
+        if min_qual_byte and fmt != "fastq":
+            raise ValueError("min_qual_byte needs fmt=\"fastq\": only FASTQ records carry base qualities")
         self._h = ctypes.c_void_p()
         self.k, self.device, self.slice_index, self.n_slices, self.fmt = k, device, slice_index, n_slices, fmt
         self.table_bytes = 4 ** k // n_slices
         self._create()
         if fmt != "fasta":
             _check(load().pk_indexer_set_format(self._h, FORMATS[fmt]))
+        if min_qual_byte:
+            _check(load().pk_indexer_set_min_qual(self._h, int(min_qual_byte)))
 
     def _create(self):
         _check(load().pk_indexer_create_slice(ctypes.byref(self._h), self.k, self.device, self.slice_index, self.n_slices))
@@ -266,6 +273,12 @@ class Indexer:
         _check(load().pk_indexer_fastq_stats(self._h, out.ctypes.data))
         return {"records": int(out[0]), "lines": int(out[1]), "bytes_fed": int(out[2]), "bytes_emitted": int(out[3])}
 
+    def fastq_masked(self) -> int:
+        """pk_indexer_fastq_masked of a FASTQ indexer: the line-2 bytes replaced by N so far (0 with min_qual_byte = 0)."""
+        n = ctypes.c_uint64(0)
+        _check(load().pk_indexer_fastq_masked(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def settled_chunks(self) -> int:
         """pk_diag_settled_chunks: the 16 KiB chunks of the last feed that the structure pass squeezed itself (full chunks of
         plain sequence text not entered inside a header line); 0 for a query indexer."""
@@ -289,9 +302,9 @@ class QueryIndexer(Indexer):
 
     TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "lookup_s", "coords_s")
 
-    def __init__(self, k: int, device: int = 0, fmt: str = "fasta"):
+    def __init__(self, k: int, device: int = 0, fmt: str = "fasta", min_qual_byte: int = 0):
         self.n_tables = 0
-        super().__init__(k, device, fmt=fmt)
+        super().__init__(k, device, fmt=fmt, min_qual_byte=min_qual_byte)
 
     def _create(self):
         _check(load().pk_query_create(ctypes.byref(self._h), self.k, self.device))

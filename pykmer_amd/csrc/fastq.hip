@@ -13,6 +13,9 @@
 //   k_fq_write  every lane re-derives its own state, copies its kept bytes (compacted in LDS, written as dwords), checks
 //               the bytes at its line starts and writes the per-record header offsets and line 2 / line 4 lengths
 //   k_fq_check  line 2 against line 4 of every record whose line 4 ended in this feed
+//   k_fq_write_held  k_fq_write for base qualities: behind text held back from earlier feeds, and noting where line 2 went
+//   k_fq_mask   base qualities only (threshold byte tq > 0): every line-4 byte below tq turns its line-2 byte in the emitted
+//               text into 'N'; the text of a record whose line 4 is still open stays at the front of out[] (`held` bytes)
 // Nothing waits for the host: errors, the need for a larger record array and the new totals sit in FqCarry, which the
 // host reads with the feed's own read-back.
 #include "fasta_fsm.h"
@@ -213,7 +216,7 @@ __global__ __launch_bounds__(WG) void k_fq_count(const uint8_t *__restrict__ f, 
 // run again from its exact state.  The carry moves to the end of the feed; the state at its start stays in `in`.
 constexpr uint32_t SCAN_T = 1024;
 __global__ __launch_bounds__(SCAN_T) void k_fq_scan(const uint8_t *__restrict__ f, uint64_t n, const FqSum *__restrict__ sums,
-                                                    uint32_t n_chunks, FqState *__restrict__ st, FqCarry *__restrict__ carry) {
+                                                    uint32_t n_chunks, FqState *__restrict__ st, uint32_t tq, FqCarry *__restrict__ carry) {
     __shared__ FqSum sh[2 * SCAN_T];
     const uint32_t t = threadIdx.x;
     const uint32_t per = (n_chunks + SCAN_T - 1) / SCAN_T;
@@ -250,6 +253,7 @@ __global__ __launch_bounds__(SCAN_T) void k_fq_scan(const uint8_t *__restrict__ 
         cy.bytes_fed += n;
         const uint64_t need = s.line / 4u + 1u;                          // records that may get a slot (the open one too)
         if (need > cy.need) cy.need = need;
+        if (tq) cy.masked_in = cy.masked;
     }
 }
 
@@ -257,9 +261,13 @@ __device__ __forceinline__ void fq_error(FqCarry *carry, uint64_t rec, uint32_t 
     atomicMin((unsigned long long *)&carry->err, (unsigned long long)((rec << 3) | rule));
 }
 
-__global__ __launch_bounds__(WG) void k_fq_write(const uint8_t *__restrict__ f, uint64_t n, const FqState *__restrict__ st,
-                                                 uint8_t *__restrict__ out, FqRec *__restrict__ recs, uint64_t recs_cap,
-                                                 FqCarry *__restrict__ carry) {
+// The body of k_fq_write.  MASK (base qualities, k_fq_write_held): out[] begins with `held` bytes of earlier text, out2[] takes
+// per record the bytes emitted before its line 2, and the count of k_fq_mask restarts.  Without it held = 0 and out2 is not
+// touched: the kernel is the one it was before base qualities.
+template <bool MASK>
+__device__ __forceinline__ void fq_write_body(const uint8_t *__restrict__ f, uint64_t n, const FqState *__restrict__ st,
+                                              uint8_t *__restrict__ out, uint64_t held, FqRec *__restrict__ recs,
+                                              uint64_t *__restrict__ out2, uint64_t recs_cap, FqCarry *__restrict__ carry) {
     __shared__ __align__(16) uint8_t lds[WG * LDS_STRIDE];
     __shared__ __align__(16) uint8_t obuf[CHUNK + 16];
     __shared__ FqSum sh[2 * WG];
@@ -277,7 +285,8 @@ __global__ __launch_bounds__(WG) void k_fq_write(const uint8_t *__restrict__ f, 
     const FqSum ex = fq_wg_scan(fq_sum_of(m), sh, &tot);
     const FqState c0 = st[chunk];
     const FqState s = fq_apply(c0, ex);
-    const uint64_t out0 = carry->in.out;                                // emitted before this feed: out[] starts there
+    const uint64_t out0 = carry->in.out - held;                         // out[] starts there: `held` bytes before this feed's text
+    if (MASK && chunk == 0u && threadIdx.x == 0) carry->masked = carry->masked_in;   // k_fq_mask counts this feed from there, each time it runs
     const uint32_t r = (uint32_t)(s.line & 3u);
     const uint64_t g0 = carry->in_bytes + base + (uint64_t)threadIdx.x * PIECE;   // stream offset of the piece
 
@@ -323,6 +332,8 @@ __global__ __launch_bounds__(WG) void k_fq_write(const uint8_t *__restrict__ f, 
                         }
                     } else if (role == 2u && c != '+') {
                         fq_error(carry, rec, FQ_RULE_PLUS);
+                    } else if (MASK && role == 1u && rec < recs_cap) {
+                        out2[rec] = s.out + (uint32_t)__popcll(keep & ((1ull << a) - 1ull));
                     }
                 }
             }
@@ -366,6 +377,17 @@ __global__ __launch_bounds__(WG) void k_fq_write(const uint8_t *__restrict__ f, 
     }
 }
 
+__global__ __launch_bounds__(WG) void k_fq_write(const uint8_t *__restrict__ f, uint64_t n, const FqState *__restrict__ st,
+                                                 uint8_t *__restrict__ out, FqRec *__restrict__ recs, uint64_t recs_cap,
+                                                 FqCarry *__restrict__ carry) {
+    fq_write_body<false>(f, n, st, out, 0u, recs, nullptr, recs_cap, carry);
+}
+__global__ __launch_bounds__(WG) void k_fq_write_held(const uint8_t *__restrict__ f, uint64_t n, const FqState *__restrict__ st,
+                                                      uint8_t *__restrict__ out, uint64_t held, FqRec *__restrict__ recs,
+                                                      uint64_t *__restrict__ out2, uint64_t recs_cap, FqCarry *__restrict__ carry) {
+    fq_write_body<true>(f, n, st, out, held, recs, out2, recs_cap, carry);
+}
+
 // line 2 against line 4 of the records whose line 4 ended in this feed
 __global__ __launch_bounds__(WG) void k_fq_check(const FqRec *__restrict__ recs, uint64_t recs_cap, FqCarry *__restrict__ carry) {
     const uint64_t lo = carry->in.line / 4u, hi = carry->st.line / 4u;
@@ -373,21 +395,155 @@ __global__ __launch_bounds__(WG) void k_fq_check(const FqRec *__restrict__ recs,
         if (recs[rec].len2 != recs[rec].len4) fq_error(carry, rec, FQ_RULE_LEN);
 }
 
-}  // namespace
-
-void launch_fq_front(const uint8_t *f, uint64_t n, FqSum *sums, FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap,
-                     FqCarry *carry, hipStream_t s) {
-    const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
-    hipLaunchKernelGGL(k_fq_count, dim3(n_chunks), dim3(WG), 0, s, f, n, (const FqCarry *)carry, sums);
-    hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(SCAN_T), 0, s, f, n, (const FqSum *)sums, n_chunks, st, carry);
-    launch_fq_write(f, n, st, out, recs, recs_cap, carry, s);
+// str.strip() whitespace (9 .. 13, 28 .. 31, 32) among the bytes of a word -> 0x80 flags
+__device__ __forceinline__ uint32_t swar_ws(uint32_t w) {
+    return (swar_less(w, 0x0e0e0e0eu) & ~swar_less(w, 0x09090909u)) | (swar_less(w, 0x20202020u) & ~swar_less(w, 0x1c1c1c1cu)) |
+           swar_eq(w, 0x20202020u);
 }
 
-void launch_fq_write(const uint8_t *f, uint64_t n, const FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap, FqCarry *carry,
-                     hipStream_t s) {
+// bytes of a word below tq (1 .. 255) as unsigned bytes -> 0x80 flags
+__device__ __forceinline__ uint32_t swar_below(uint32_t w, uint32_t tq) {
+    const uint32_t n7 = (tq > 0x80u ? tq - 0x80u : tq) * 0x01010101u;    // compared with the low 7 bits, 1 .. 0x80
+    const uint32_t lt7 = ~(((w & 0x7f7f7f7fu) | 0x80808080u) - n7) & 0x80808080u;
+    return tq > 0x80u ? ((~w & 0x80808080u) | (lt7 & w)) : (lt7 & ~w);
+}
+
+// Base qualities (README "Base quality"), behind k_fq_write of the same feed: byte o of record r's line 4 below tq turns
+// byte o of r's line 2 in the emitted text into 'N', unless o >= len2[r] (a malformed record: k_fq_check reports it), the
+// record has no slot (the front end runs again) or the text byte is a str.strip() blank.  out[] holds the emitted bytes
+// [in.out - held, st.out): `held` bytes of records whose line 4 was still open, then this feed's text; out2[r] and
+// len2[r] were written when line 2 went by, in this feed or an earlier one.  Every text byte has one quality byte, so no
+// two lanes meet (a lane patches the text dwords that lie wholly under its bytes as words, the rest byte by byte), and a
+// second run over the same feed finds the same bytes: the count restarts from masked_in (k_fq_write_held).
+// The first thread also leaves the offset up to which the text is settled: the start of line 2 of the open record.
+__global__ __launch_bounds__(WG) void k_fq_mask(const uint8_t *__restrict__ f, uint64_t n, const FqState *__restrict__ st,
+                                                uint8_t *__restrict__ out, uint64_t held, const FqRec *__restrict__ recs,
+                                                const uint64_t *__restrict__ out2, uint64_t recs_cap, uint32_t tq, FqCarry *__restrict__ carry) {
+    __shared__ __align__(16) uint8_t lds[WG * LDS_STRIDE];
+    __shared__ FqSum sh[2 * WG];
+    __shared__ uint32_t wg_masked;
+    const uint32_t chunk = blockIdx.x;
+    const uint64_t base = (uint64_t)chunk * CHUNK;
+    if (threadIdx.x == 0) wg_masked = 0;
+    stage_chunk(f, base, n, lds);
+    __syncthreads();
+    const uint8_t *mine = lds + threadIdx.x * LDS_STRIDE;
+    FqMasks m;
+    const uint32_t nb = piece_len(base, n);
+    fq_masks(mine, nb, fq_prev4(f, chunk, lds, carry->prev4_in), m);
+    FqSum tot;
+    const FqSum ex = fq_wg_scan(fq_sum_of(m), sh, &tot);
+    const FqState s = fq_apply(st[chunk], ex);
+    const uint64_t out_lo = carry->in.out - held, out_hi = carry->st.out;   // the emitted bytes out[] holds
+
+    unsigned long long low = 0;                                          // bytes below tq
+    {
+        const uint4 *quads = reinterpret_cast<const uint4 *>(mine);
+        uint32_t lo32[2] = {0, 0};
+#pragma unroll
+        for (int q = 0; q < PIECE / 16; q++) {
+            const uint4 v = quads[q];
+            const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int d = q * 4 + j;
+                lo32[d >> 3] |= movemask4(swar_below(w4[j], tq)) << (4 * (d & 7));
+            }
+        }
+        low = ((((unsigned long long)lo32[1]) << 32) | lo32[0]) & (nb >= 64u ? ~0ull : ((1ull << nb) - 1ull));
+    }
+
+    uint32_t masked = 0;
+    {   // the lines of the piece as k_fq_write walks them
+        unsigned long long t = m.ts;
+        uint64_t line = s.line;
+        uint32_t a = (uint32_t)(m.cont & 1ull);
+        uint64_t len0 = ((m.ls >> a) & 1ull) ? 0u : s.curlen;            // bytes of the segment's line before the piece
+        for (;;) {
+            const bool term = t != 0ull;
+            const uint32_t p = term ? (uint32_t)__builtin_ctzll(t) : nb;   // the segment is bytes [a, p)
+            const uint64_t rec = line >> 2;
+            unsigned long long x = (p >= 64u ? ~0ull : ((1ull << p) - 1ull)) & ~((1ull << a) - 1ull) & low;
+            if ((line & 3u) == 3u && x && rec < recs_cap) {
+                const uint64_t len2 = recs[rec].len2, at = out2[rec] + len0;   // `at`: where the text byte of piece byte a lies
+                const uint64_t room = len2 > len0 ? len2 - len0 : 0u;           // line-2 bytes from there on
+                const uint32_t pe = (uint64_t)(p - a) <= room ? p : a + (uint32_t)room;   // piece bytes [a, pe) have a text byte
+                x &= pe >= 64u ? ~0ull : ((1ull << pe) - 1ull);
+                if (x && at >= out_lo && at + (pe - a) <= out_hi) {
+                    const uint64_t t0 = at - out_lo - a;                        // out[t0 + i] is the text byte of piece byte i (t0 + a >= 0)
+                    // the text dwords that lie inside [a, pe) are this lane's alone: read together, patched, written back
+                    const uint32_t i_lo = a + (uint32_t)((0u - (t0 + a)) & 3u);
+                    const uint32_t n_words = i_lo < pe ? (pe - i_lo) >> 2 : 0u;
+                    uint32_t wv[PIECE / 4];
+#pragma unroll
+                    for (int j = 0; j < PIECE / 4; j++) {
+                        const uint32_t i = i_lo + 4u * j;
+                        const uint32_t bits = (uint32_t)j < n_words ? (uint32_t)(x >> (i & 63u)) & 15u : 0u;
+                        wv[j] = bits ? *reinterpret_cast<const uint32_t *>(out + (t0 + i)) : 0u;
+                    }
+#pragma unroll
+                    for (int j = 0; j < PIECE / 4; j++) {
+                        const uint32_t i = i_lo + 4u * j;
+                        const uint32_t bits = (uint32_t)j < n_words ? (uint32_t)(x >> (i & 63u)) & 15u : 0u;
+                        if (bits) {
+                            const uint32_t hit = ((bits * 0x00204081u) & 0x01010101u) & ~(swar_ws(wv[j]) >> 7);   // 0x01 per byte to replace
+                            const uint32_t bytes = hit * 0xffu;
+                            if (hit) *reinterpret_cast<uint32_t *>(out + (t0 + i)) = (wv[j] & ~bytes) | (0x4e4e4e4eu & bytes);
+                            masked += (uint32_t)__popc(hit);
+                        }
+                    }
+                    // the bytes in front of and behind those words share theirs with other lanes: byte by byte
+                    const uint32_t i_hi = i_lo + 4u * n_words;
+                    if (n_words) x &= ((1ull << i_lo) - 1ull) | (i_hi >= 64u ? 0ull : ~((1ull << i_hi) - 1ull));
+                    while (x) {
+                        const uint32_t i = (uint32_t)__builtin_ctzll(x);
+                        x &= x - 1ull;
+                        if (!is_ws(out[t0 + i])) {
+                            out[t0 + i] = (uint8_t)'N';
+                            masked++;
+                        }
+                    }
+                }
+            }
+            if (!term) break;
+            t &= t - 1ull;
+            line++;
+            a = p + 1u + (p < 63u ? (uint32_t)((m.cont >> (p + 1u)) & 1ull) : 0u);
+            if (a >= 64u) break;
+            len0 = 0;
+        }
+    }
+    if (masked) atomicAdd(&wg_masked, masked);
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_masked) atomicAdd((unsigned long long *)&carry->masked, (unsigned long long)wg_masked);
+
+    if (chunk == 0u && threadIdx.x == 0) {
+        const FqState e = carry->st;
+        const uint32_t role = (uint32_t)(e.line & 3u);
+        const uint64_t rec = e.line >> 2;
+        uint64_t settled = e.out;                                        // no line 2 is waiting for its line 4
+        if (role >= 2u || (role == 1u && e.curlen > 0u)) settled = rec < recs_cap ? out2[rec] : out_lo;
+        carry->settled = settled;
+    }
+}
+
+}  // namespace
+
+void launch_fq_front(const uint8_t *f, uint64_t n, FqSum *sums, FqState *st, uint8_t *out, uint64_t held, FqRec *recs, uint64_t *out2,
+                     uint64_t recs_cap, uint32_t tq, FqCarry *carry, hipStream_t s) {
     const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
-    hipLaunchKernelGGL(k_fq_write, dim3(n_chunks), dim3(WG), 0, s, f, n, st, out, recs, recs_cap, carry);
+    hipLaunchKernelGGL(k_fq_count, dim3(n_chunks), dim3(WG), 0, s, f, n, (const FqCarry *)carry, sums);
+    hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(SCAN_T), 0, s, f, n, (const FqSum *)sums, n_chunks, st, tq, carry);
+    launch_fq_write(f, n, st, out, held, recs, out2, recs_cap, tq, carry, s);
+}
+
+void launch_fq_write(const uint8_t *f, uint64_t n, const FqState *st, uint8_t *out, uint64_t held, FqRec *recs, uint64_t *out2,
+                     uint64_t recs_cap, uint32_t tq, FqCarry *carry, hipStream_t s) {
+    const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
+    if (tq) hipLaunchKernelGGL(k_fq_write_held, dim3(n_chunks), dim3(WG), 0, s, f, n, st, out, held, recs, out2, recs_cap, carry);
+    else hipLaunchKernelGGL(k_fq_write, dim3(n_chunks), dim3(WG), 0, s, f, n, st, out, recs, recs_cap, carry);
     hipLaunchKernelGGL(k_fq_check, dim3(256), dim3(WG), 0, s, (const FqRec *)recs, recs_cap, carry);
+    if (tq) hipLaunchKernelGGL(k_fq_mask, dim3(n_chunks), dim3(WG), 0, s, f, n, st, out, held, (const FqRec *)recs, (const uint64_t *)out2, recs_cap, tq, carry);
 }
 
 }  // namespace pk

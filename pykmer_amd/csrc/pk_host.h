@@ -184,6 +184,12 @@ struct pk_indexer {
     pk::DevBuf<uint8_t> fq_out[2];
     int fq_buf = 0;
     uint64_t fq_pending = 0;           // FASTA bytes in fq_out[fq_buf ^ 1] not counted yet
+    // base qualities (pk_indexer_set_min_qual): line-4 bytes below fq_tq turn their line-2 bytes into 'N'.  The text of a
+    // record whose line 4 is still open is held back: fq_tail bytes behind the pending ones, copied to the front of the
+    // next feed's buffer, where that feed's line 4 bytes can still reach them.  The threshold stays across resets.
+    int fq_tq = 0;
+    uint64_t fq_tail = 0;
+    pk::DevBuf<uint64_t> fq_out2;      // per record slot of fq_recs: the bytes emitted before its line 2 (allocated with a threshold only)
     pk::DevBuf<pk::FqRec> fq_recs;
     uint64_t fq_need = 0;
     bool fq_failed = false;

@@ -49,7 +49,7 @@ static int ix_reset(pk_indexer *ix) {
     ix->t_scan = ix->t_squeeze = ix->t_sort = ix->t_final = ix->t_part = ix->t_bucket = 0;
     ix->feeds = ix->relayouts = 0; ix->recounted = 0;
     ix->fed = false;
-    ix->fq_pending = 0; ix->fq_need = 0; ix->fq_failed = false; ix->fq_err.clear();
+    ix->fq_pending = 0; ix->fq_tail = 0; ix->fq_need = 0; ix->fq_failed = false; ix->fq_err.clear();
     ix->fix_chunks = 0;
     return PK_OK;
 }
@@ -406,46 +406,58 @@ static int fq_verdict(pk_indexer *ix) {
 }
 
 static int fq_ensure_recs(pk_indexer *ix, uint64_t need) {
-    if (need <= ix->fq_recs_cap()) return PK_OK;
-    return ix->fq_recs.grow_keep(std::max<uint64_t>(need, 2 * ix->fq_recs_cap()) * sizeof(FqRec), ix->stream);
+    if (need > ix->fq_recs_cap()) {
+        int rc = ix->fq_recs.grow_keep(std::max<uint64_t>(need, 2 * ix->fq_recs_cap()) * sizeof(FqRec), ix->stream);
+        if (rc) return rc;
+    }
+    return ix->fq_tq ? ix->fq_out2.grow_keep(ix->fq_recs_cap() * sizeof(uint64_t), ix->stream) : PK_OK;   // slot for slot
 }
 
-// the FASTA text of the previous FASTQ feed, if any, into the pipeline; ends with the read-back of the carry
+// the FASTA text of the previous FASTQ feed, if any, into the pipeline; ends with the read-back of the carry.  With a
+// held-back record in front of it the text can be longer than a piece: it goes in pieces (a multiple of 16: they stay aligned).
 static int fq_flush(pk_indexer *ix) {
-    if (ix->fq_pending) {
-        const uint64_t n = ix->fq_pending;
-        ix->fq_pending = 0;
-        return feed_piece(ix, ix->fq_out[ix->fq_buf ^ 1].p, n);
-    }
-    return read_tail(ix);
+    if (!ix->fq_pending) return read_tail(ix);
+    const uint64_t n = ix->fq_pending, piece_max = feed_max_for(ix->k);
+    ix->fq_pending = 0;
+    for (uint64_t off = 0; off < n; off += piece_max)
+        if (int rc = feed_piece(ix, ix->fq_out[ix->fq_buf ^ 1].p + off, std::min(piece_max, n - off))) return rc;
+    return PK_OK;
 }
 
 // one FASTQ piece of at most feed_max_for(k) bytes: the front end turns it into FASTA text in fq_out[fq_buf] while the
-// text of the piece before goes through the FASTA pipeline
+// text of the piece before goes through the FASTA pipeline.  With base qualities the buffer begins with the text held back
+// from the piece before (behind its pending bytes), which this piece's line 4 bytes may still change; what is settled
+// after this piece becomes the pending text, the rest is held back in turn.
 static int fq_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n) {
     const uint32_t n_chunks = (uint32_t)((n + CHUNK - 1) / CHUNK);
     const int b = ix->fq_buf;
+    const uint32_t tq = (uint32_t)ix->fq_tq;
+    const uint64_t held = ix->fq_tail;
     int rc;
     if ((rc = ix->fq_sums.reserve((size_t)n_chunks * sizeof(FqSum)))) return rc;
     if ((rc = ix->fq_st.reserve((size_t)n_chunks * sizeof(FqState)))) return rc;
-    if ((rc = ix->fq_out[b].reserve(n + 64))) return rc;
+    if ((rc = ix->fq_out[b].reserve(held + n + 64))) return rc;
     // record slots for what the stream needed so far and one record per 256 bytes of this piece; a piece that needs
     // more writes its text again once the array has grown
     if ((rc = fq_ensure_recs(ix, ix->fq_need + n / 256 + 1024))) return rc;
     FqCarry *carry = &ix->tail.p->fq;
-    launch_fq_front(f, n, ix->fq_sums.p, ix->fq_st.p, ix->fq_out[b].p, ix->fq_recs.p, ix->fq_recs_cap(), carry, ix->stream);
+    if (held) HIPCHK(hipMemcpyAsync(ix->fq_out[b].p, ix->fq_out[b ^ 1].p + ix->fq_pending, held, hipMemcpyDeviceToDevice, ix->stream));
+    launch_fq_front(f, n, ix->fq_sums.p, ix->fq_st.p, ix->fq_out[b].p, held, ix->fq_recs.p, ix->fq_out2.p, ix->fq_recs_cap(), tq, carry, ix->stream);
     HIPCHK(hipGetLastError());
     if ((rc = fq_flush(ix))) return rc;
     if (ix->pin->tail.fq.need > ix->fq_recs_cap()) {
         if ((rc = fq_ensure_recs(ix, ix->pin->tail.fq.need + n / 256 + 1024))) return rc;
-        launch_fq_write(f, n, ix->fq_st.p, ix->fq_out[b].p, ix->fq_recs.p, ix->fq_recs_cap(), carry, ix->stream);
+        launch_fq_write(f, n, ix->fq_st.p, ix->fq_out[b].p, held, ix->fq_recs.p, ix->fq_out2.p, ix->fq_recs_cap(), tq, carry, ix->stream);
         HIPCHK(hipGetLastError());
         if ((rc = fq_flush(ix))) return rc;
     }
     const FqCarry &q = ix->pin->tail.fq;
     ix->fq_need = q.need;
     if ((rc = fq_verdict(ix))) return rc;
-    ix->fq_pending = q.st.out - q.in.out;
+    const uint64_t out_lo = q.in.out - held;                 // the emitted bytes fq_out[b] begins with
+    const uint64_t settled = tq ? std::min(std::max(q.settled, out_lo), q.st.out) : q.st.out;
+    ix->fq_pending = settled - out_lo;
+    ix->fq_tail = q.st.out - settled;
     ix->fq_buf = b ^ 1;
     return PK_OK;
 }
@@ -471,6 +483,23 @@ extern "C" int pk_indexer_set_format(pk_indexer *ix, int format) {
     if (format != PK_FORMAT_FASTA && format != PK_FORMAT_FASTQ) return fail(PK_ERR_ARG, "unknown input format %d", format);
     if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the input format is set before the first feed (reset the indexer first)");
     ix->format = format;
+    if (format != PK_FORMAT_FASTQ) ix->fq_tq = 0;            // base qualities belong to FASTQ
+    return PK_OK;
+}
+
+extern "C" int pk_indexer_set_min_qual(pk_indexer *ix, int threshold_byte) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (threshold_byte < 0 || threshold_byte > 255) return fail(PK_ERR_ARG, "quality threshold byte %d outside 0..255", threshold_byte);
+    if (ix->format != PK_FORMAT_FASTQ) return fail(PK_ERR_STATE, "base qualities need a FASTQ indexer (pk_indexer_set_format first)");
+    if (ix->fed || ix->finished) return fail(PK_ERR_STATE, "the quality threshold is set before the first feed (reset the indexer first)");
+    ix->fq_tq = threshold_byte;
+    return PK_OK;
+}
+
+extern "C" int pk_indexer_fastq_masked(pk_indexer *ix, uint64_t *out) {
+    if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
+    if (ix->format != PK_FORMAT_FASTQ) return fail(PK_ERR_STATE, "not a FASTQ indexer");
+    *out = ix->fed && ix->fq_tq ? ix->pin->tail.fq.masked : 0;   // every feed ends with its read-back
     return PK_OK;
 }
 
@@ -549,7 +578,9 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
     HIPCHK(hipSetDevice(ix->device));
     if (!ix->finished && ix->format == PK_FORMAT_FASTQ) {
         if (ix->fq_failed) return fail(PK_ERR_FORMAT, "%s", ix->fq_err.c_str());
-        if (ix->fq_pending) {                                // the last feed's text
+        if (ix->fq_pending || ix->fq_tail) {                 // the last feed's text, with what it held back: no line 4 is left to come
+            ix->fq_pending += ix->fq_tail;
+            ix->fq_tail = 0;
             int rc = fq_flush(ix);
             if (rc) return rc;
         }

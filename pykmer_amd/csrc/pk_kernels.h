@@ -170,13 +170,20 @@ struct FqCarry {
     uint64_t full;           // 1 + the last line with a byte that is no terminator
     uint64_t need;           // record slots the stream needs
     uint32_t prev4, prev4_in;   // the last 4 bytes of the stream (before the last feed), newest highest
+    // base qualities (tq > 0) only
+    uint64_t masked, masked_in;   // line-2 bytes turned into 'N' (before the last feed)
+    uint64_t settled;        // emitted bytes before this offset belong to records whose whole line 4 has been seen
 };
-// k_fq_count + k_fq_scan + launch_fq_write.  out: n + 64 bytes; record slots at or beyond recs_cap are not written
-// (carry->need says how many are needed, and launch_fq_write can be repeated with a larger array).
-void launch_fq_front(const uint8_t *fastq, uint64_t n, FqSum *sums, FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap,
-                     FqCarry *carry, hipStream_t s);
-void launch_fq_write(const uint8_t *fastq, uint64_t n, const FqState *st, uint8_t *out, FqRec *recs, uint64_t recs_cap, FqCarry *carry,
-                     hipStream_t s);
+// k_fq_count + k_fq_scan + launch_fq_write.  out: held + n + 64 bytes, 16-byte aligned; record slots at or beyond recs_cap are
+// not written (carry->need says how many are needed, and launch_fq_write can be repeated with a larger array).
+// tq = 0: base qualities are not looked at, held = 0 and out2 is null.  tq = 1 .. 255: k_fq_write_held stands in for
+// k_fq_write and k_fq_mask runs behind k_fq_check; out2 (recs_cap words, a record's slot like recs) receives per record the
+// bytes emitted before its line 2; the first `held` bytes of out are emitted text from before this feed that line 4 bytes of
+// this feed may still change (the text behind carry->settled of the feed before), and this feed's text goes behind them.
+void launch_fq_front(const uint8_t *fastq, uint64_t n, FqSum *sums, FqState *st, uint8_t *out, uint64_t held, FqRec *recs, uint64_t *out2,
+                     uint64_t recs_cap, uint32_t tq, FqCarry *carry, hipStream_t s);
+void launch_fq_write(const uint8_t *fastq, uint64_t n, const FqState *st, uint8_t *out, uint64_t held, FqRec *recs, uint64_t *out2,
+                     uint64_t recs_cap, uint32_t tq, FqCarry *carry, hipStream_t s);
 
 // gram_scan.hip
 // tables: device array of N device pointers, each n_slice bytes (16-byte aligned).  pair: device N*N u64,

@@ -36,6 +36,31 @@ def input_format(input_file: str) -> str:
     return "fastq" if input_file.endswith(FASTQ_SUFFIXES) else "fasta"
 
 
+QUAL_OFFSETS = (33, 64)
+
+
+def qual_threshold(input_file: str, min_qual, qual_offset=None) -> int:
+    """The threshold byte T = Q + offset of `--min-qual Q [--qual-offset 33|64]` (README "Base quality"): bases whose quality
+    byte is below T count as N.  0: off (no option, or Q = 0).  ValueError for what the CLIs refuse: an offset without a
+    quality, an offset other than 33 or 64, Q < 0, T > 255, and a quality on an input that is not FASTQ by its name."""
+    if min_qual is None:
+        if qual_offset is not None:
+            raise ValueError("--qual-offset belongs to --min-qual: give --min-qual Q too")
+        return 0
+    if isinstance(min_qual, (bool, np.bool_)) or not isinstance(min_qual, (int, np.integer)):
+        raise ValueError(f"--min-qual must be an integer, got {min_qual!r}")
+    offset = 33 if qual_offset is None else qual_offset
+    if offset not in QUAL_OFFSETS:
+        raise ValueError(f"--qual-offset must be 33 or 64, got {offset!r}")
+    if min_qual < 0:
+        raise ValueError(f"--min-qual must not be negative, got {min_qual}")
+    if min_qual + offset > 255:
+        raise ValueError(f"--min-qual {min_qual} with offset {offset} is beyond the largest quality byte (255)")
+    if input_format(input_file) != "fastq":
+        raise ValueError(f"--min-qual needs FASTQ input (.fq / .fastq[.gz|.bgz]): {input_file} has no base qualities")
+    return int(min_qual) + int(offset) if min_qual else 0
+
+
 def _open_input(input_file: str):
     """indexer.py:101-128: .gz / .bgz through gzip, anything else as is (bytes here, text there)."""
     label = input_format(input_file).upper()
@@ -190,8 +215,10 @@ def n_address_slices(kmer_len: int) -> int:
     return forced or max(1, 4 ** kmer_len >> 34)
 
 
-def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str = None, devices=None):
-    """Streams one FASTA or FASTQ file (input_format: by its name) through the GPU indexer.
+def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str = None, devices=None, min_qual: int = 0,
+               qual_offset: int = 33):
+    """Streams one FASTA or FASTQ file (input_format: by its name) through the GPU indexer.  `min_qual` = Q > 0 (FASTQ only):
+    bases whose quality byte is below Q + qual_offset count as N (qual_threshold); summary["masked"] is their number.
 
     Returns (table, summary dict, all_records [(name, seq_len, n_valid)]).  With `table_file` the 4^k-byte
     table is written straight into that file (tools.py:333-341: exactly 4^k bytes, no header) piece by piece as
@@ -206,6 +233,7 @@ def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str 
     import threading
     from concurrent.futures import ThreadPoolExecutor
     devices = tuple(devices) if devices else (device,)
+    tq = qual_threshold(input_file, min_qual, qual_offset) if min_qual else 0
     n = 4 ** kmer_len
     n_slices = n_address_slices(kmer_len)
     size = n // n_slices
@@ -231,7 +259,8 @@ def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str 
         as they land, later slices are hashed whole once it is their turn (the file is hashed in address order)."""
         src = source if s == 0 else _Input(input_file, keep=False, quiet=True)   # only slice 0's names and messages are used
         _mark("creating the indexer (library load, HIP start-up, table and workspace allocation)")
-        with _lib.Indexer(kmer_len, device=devices[s % len(devices)], slice_index=s, n_slices=n_slices, fmt=src.fmt) as ix:
+        with _lib.Indexer(kmer_len, device=devices[s % len(devices)], slice_index=s, n_slices=n_slices, fmt=src.fmt,
+                           min_qual_byte=tq) as ix:
             _mark("indexer ready")
             for piece in src.pieces():
                 ix.feed(piece)
@@ -239,6 +268,8 @@ def count_file(input_file: str, kmer_len: int, device: int = 0, table_file: str 
             _mark("text counted")
             fin["records"] = ix.records(fin["n_records"]) if s == 0 else None
             fin["timings"] = ix.timings()
+            if tq:
+                fin["masked"] = ix.fastq_masked()
             for off in range(0, size, TABLE_SLICE):
                 part = table[s * size + off: s * size + min(size, off + TABLE_SLICE)]
                 ix.table_slice_to_host(part, off)
@@ -287,9 +318,14 @@ def create_fasta_index(
         max_frag_size: int = Header.DEFAULT_MAX_FRAG_SIZE,
         buffer_size: int = Header.DEFAULT_BUFFER_SIZE,
         debug: bool = False,
-        device: int = 0) -> Header:
+        device: int = 0,
+        min_qual: int = 0,
+        qual_offset: int = 33) -> Header:
     """indexer.py:299-414.  flush_every / frag sizes only travel into the .kin.json (the table is
-    independent of batching, indexer.py:262); the 4^k table is resident in HBM instead."""
+    independent of batching, indexer.py:262); the 4^k table is resident in HBM instead.  min_qual / qual_offset: as
+    count_file; the .kin.json keeps the reference's keys, so the threshold is not recorded in it."""
+    if min_qual:
+        qual_threshold(input_file, min_qual, qual_offset)      # refused before any file is touched
     header = Header(project_name, sample_name=sample_name, input_file=input_file, kmer_len=kmer_len,
                     flush_every=flush_every, min_frag_size=min_frag_size, max_frag_size=max_frag_size,
                     buffer_size=buffer_size, device=device)
@@ -304,8 +340,11 @@ def create_fasta_index(
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     input_sum = pool.submit(gen_checksum, header.input_file_path, 1 << 22)
     devices = tuple(int(d) for d in os.environ.get("PK_DEVICES", str(device)).split(",") if d != "")
-    table, fin, everything = count_file(input_file, kmer_len, device=device, table_file=header.index_tmp_file, devices=devices)
+    table, fin, everything = count_file(input_file, kmer_len, device=device, table_file=header.index_tmp_file, devices=devices,
+                                             min_qual=min_qual, qual_offset=qual_offset)
     del table
+    if min_qual:
+        print(f"MASKED {fin['masked']} bases below quality {min_qual} (offset {qual_offset})")
     for num, (name, seq_len, n_valid) in enumerate(everything):
         print(f"{num + 1:03d} {name} {seq_len:15,d}")           # indexer.py:136
     header.timer.update(fin["total_bp"])
@@ -338,15 +377,39 @@ def read_fasta_index(project_name: str, input_file: Union[str, None] = None, kme
 
 
 def main(argv: List[str] = None) -> None:
-    """indexer.py:475-495: `indexer.py <fasta[.gz|.bgz]> <sample_name> <k>`; also the README's `indexer.py <fasta> <k>`."""
+    """indexer.py:475-495: `indexer.py <fasta[.gz|.bgz]> <sample_name> <k>`; also the README's `indexer.py <fasta> <k>`.
+    `--min-qual Q` and `--qual-offset 33|64` (README "Base quality") may stand anywhere among the positionals."""
     argv = list(sys.argv[1:] if argv is None else argv)
+    usage = "usage: indexer.py <input.fa[.gz|.bgz]> <sample_name> <kmer_len> [--min-qual Q] [--qual-offset 33|64]"
+    opts, rest, i = {}, [], 0
+    while i < len(argv):
+        name, eq, value = argv[i].partition("=")
+        if name in ("--min-qual", "--qual-offset"):
+            if not eq:
+                i += 1
+                value = argv[i] if i < len(argv) else ""
+            try:
+                opts[name] = int(value)
+            except ValueError:
+                print(f"error: {name} needs an integer, got {value!r}", file=sys.stderr)
+                sys.exit(1)
+        else:
+            rest.append(argv[i])
+        i += 1
+    argv = rest
     if len(argv) == 2 and argv[1].isdigit():                   # README.md:22
         argv = [argv[0], os.path.basename(argv[0]), argv[1]]
     if len(argv) != 3:
-        print("usage: indexer.py <input.fa[.gz|.bgz]> <sample_name> <kmer_len>")
+        print(usage)
         sys.exit(1)
     input_file, sample_name, kmer_len = argv[0], argv[1], int(argv[2])
+    min_qual, qual_offset = opts.get("--min-qual"), opts.get("--qual-offset")
+    try:
+        qual_threshold(input_file, min_qual, qual_offset)
+    except ValueError as exc:
+        print(f"error: {exc}", file=sys.stderr)
+        sys.exit(1)
     print(f"project_name {input_file:s} input_file {input_file:s} sample_name {sample_name:s} kmer_len {kmer_len:15,d}")
     create_fasta_index(input_file, sample_name, input_file, kmer_len, buffer_size=2 ** 16, overwrite=True, debug=False,
-                       device=int(os.environ.get("PK_DEVICE", "0")))
+                       device=int(os.environ.get("PK_DEVICE", "0")), min_qual=min_qual or 0, qual_offset=33 if qual_offset is None else qual_offset)
     print()

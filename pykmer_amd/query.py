@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib, staging
 from .header import Header
-from .indexer import _Input, _mark
+from .indexer import _Input, _mark, qual_threshold
 from .merger import DEFAULT_THREADS
 from .output import atomic_write, write_json
 from .tables import EXTS, MAX_KMER_LEN, common_kmer_len, lean_headers, name_of as _name_of, table_entry   # noqa: F401
@@ -113,15 +113,15 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
 
 
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
-              bin_windows: int = None, coords: bool = False) -> dict:
+              bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
     same query only add columns).  `bin_windows`: tally per bin (bin_hits, bin_depth, bin_first); the per-record arrays
     are then the sums of each record's rows.  `coords`: also bin_start, bin_end -- on the `first` stream only, they do
-    not depend on the tables."""
+    not depend on the tables.  `min_qual_byte`: a FASTQ query's bases below this quality byte count as N (qual_threshold)."""
     coords = bool(coords) and first
     src = _Input(query_file, keep=first, quiet=not first)
     binned = {}
-    with _lib.QueryIndexer(kmer_len, device=device, fmt=src.fmt) as q:
+    with _lib.QueryIndexer(kmer_len, device=device, fmt=src.fmt, min_qual_byte=min_qual_byte) as q:
         q.set_tables(ptrs, min_count, max_count)
         if bin_windows is not None:
             q.set_bins(bin_windows)
@@ -141,15 +141,16 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
         else:
             hits, depth = q.results(fin["n_records"])
         timings = q.timings()
+        masked = {"masked": q.fastq_masked()} if min_qual_byte else {}
     out = {"seq_len": recs["seq_len"].astype(np.uint64), "n_valid": recs["n_valid_kmers"].astype(np.uint64), "hits": hits.copy(),
-           "depth": depth.copy(), "num_kmers": fin["num_kmers"], "total_bp": fin["total_bp"], "timings": timings, **binned}
+           "depth": depth.copy(), "num_kmers": fin["num_kmers"], "total_bp": fin["total_bp"], "timings": timings, **binned, **masked}
     if first:
         out["names"] = [nm.decode("utf-8", "replace") for nm in src.names(recs)]
     return out
 
 
 def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
-                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False) -> dict:
+                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False, min_qual: int = 0, qual_offset: int = 33) -> dict:
     """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
     merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
     kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
@@ -165,7 +166,11 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
 
     `coords` = True (with `bin_windows`; ValueError without) adds bin_start and bin_end (B,), uint64: the base positions
     within its record of the first base of every row's first window and one past the last base of its last (the module's
-    docstring).  They are computed while the first table group is streamed.  `run` receives coords like bin_windows."""
+    docstring).  They are computed while the first table group is streamed.  `run` receives coords like bin_windows.
+
+    `min_qual` = Q > 0 (a FASTQ query only; ValueError otherwise): bases whose quality byte is below Q + qual_offset count
+    as N (README "Base quality"); the result gains `masked`, their number.  `run` receives min_qual_byte by keyword, and
+    only when it is set."""
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
@@ -173,6 +178,8 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     extra = {} if bin_windows is None else {"bin_windows": bin_windows}
     if coords:
         extra["coords"] = True
+    if min_qual:
+        extra["min_qual_byte"] = qual_threshold(str(query_file), min_qual, qual_offset)
     tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
     kmer_len = validate(tables, min_count, max_count)
     stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
@@ -211,7 +218,14 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         assert result["bin_start"].shape == result["bin_end"].shape == (int(result["bin_first"][-1]),)
         result["coords_s"] = coords_s
     result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
+    if min_qual:
+        result.update(min_qual=int(min_qual), qual_offset=int(qual_offset))
     return result
+
+
+def _qual_keys(result: dict) -> dict:
+    """min_qual and qual_offset of the `.kmq.json` / `.kmb.json`: only when the query ran with --min-qual."""
+    return {"min_qual": int(result["min_qual"]), "qual_offset": int(result["qual_offset"])} if result.get("min_qual") else {}
 
 
 def kmq_paths(project_name: str) -> Tuple[Path, Path, Path]:
@@ -229,6 +243,7 @@ def write_kmq(project_name: str, result: dict, query_file: str, data: list, colu
     assert hits.shape == depth.shape == (len(names), len(columns)) and n_valid.shape == seq_len.shape == (len(names),)
     output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
               "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data}
+    output.update(_qual_keys(result))
     write_json(meta, output)
     with atomic_write(tsv, "wt") as fhd:
         fhd.write("\t".join(["record", "seq_len", "n_valid"] + [str(c) for c in columns]) + "\n")
@@ -268,6 +283,7 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
               "bin_windows": W, "n_bins": B}
     if coords:
         output["coords"] = True
+    output.update(_qual_keys(result))
     write_json(meta, output)
     with atomic_write(tsv, "wt") as fhd:
         fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) + [str(c) for c in columns]) + "\n")
@@ -284,9 +300,12 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
 
 
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
-          threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None, coords: bool = False) -> dict:
+          threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None, coords: bool = False, min_qual: int = None,
+          qual_offset: int = None) -> dict:
     """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result.
-    `coords` (with `bin_windows`) adds the rows' base coordinates to the `.kmb` files."""
+    `coords` (with `bin_windows`) adds the rows' base coordinates to the `.kmb` files.  `min_qual` / `qual_offset`
+    (--min-qual, --qual-offset; None: not given) mask a FASTQ query's low-quality bases and are recorded in the json files."""
+    qual_threshold(str(query_file), min_qual, qual_offset)
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
@@ -294,6 +313,8 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
     extra = {} if bin_windows is None else {"bin_windows": bin_windows}
     if coords:
         extra["coords"] = True
+    if min_qual:
+        extra.update(min_qual=min_qual, qual_offset=33 if qual_offset is None else qual_offset)
     for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
@@ -333,6 +354,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Also write <P>.kmb[.json|.tsv]: the hits along each record in bins of W valid windows [off]")
     parser.add_argument("--coords", action="store_true",
                         help="With --bin: add every bin's base coordinates within its record (start, end) to the .kmb files [off]")
+    parser.add_argument("--min-qual", type=int, default=None, metavar="Q",
+                        help="FASTQ query: bases with a quality below Q count as N [off]")
+    parser.add_argument("--qual-offset", type=int, default=None, metavar="O", help="With --min-qual: the quality encoding, 33 or 64 [33]")
     return parser
 
 
@@ -341,7 +365,8 @@ def main(argv: List[str] = None) -> None:
     try:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
                        device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows,
-                       **({"coords": True} if args.coords else {}))
+                       **({"coords": True} if args.coords else {}),
+                       **({"min_qual": args.min_qual, "qual_offset": args.qual_offset} if args.min_qual is not None or args.qual_offset is not None else {}))
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)

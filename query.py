@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""query.py Project_Name queries.fa|.fq[.gz|.bgz] a.kin[.bgz] b.kin[.bgz] ... [--min-count --max-count --threads --bin W [--coords]]
+"""query.py Project_Name queries.fa|.fq[.gz|.bgz] a.kin[.bgz] b.kin[.bgz] ... [--min-count --max-count --threads --bin W [--coords] --min-qual Q [--qual-offset 33|64]]
 
 Per-record k-mer hits of a FASTA / FASTQ file against N k-mer tables (no counterpart in the reference): writes
 `<project>.kmq` (np.savez_compressed: hits, depth (R,N) uint64; n_valid, seq_len (R,) uint64; kmer_len, min_count, max_count),
