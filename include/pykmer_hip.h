@@ -186,7 +186,19 @@ void pk_indexer_destroy(pk_indexer *ix);
  * the coordinates, 0 (the default) does not.  The setting goes with the bins: a reset clears it with them, and so does a
  * later pk_query_set_bins.  The two arrays are sized with the accumulators (one u64 each per row) and fail the same way.
  * pk_query_bin_coords: after pk_indexer_finish.  start_out / end_out receive B u64 each, in row order.  PK_ERR_STATE when
- * coordinates are off; PK_ERR_RECS_CAP, with the needed number in the message, if B > bins_cap. */
+ * coordinates are off; PK_ERR_RECS_CAP, with the needed number in the message, if B > bins_cap.
+ *
+ * Count spectra: per row (a record, or a bin when bins are on) and table, how many of the row's valid windows have each
+ * table count,  spectrum[row][t][c] = #{ j : T_t[a_j] == c },  c = 0 .. 255, exact u64.  Absent k-mers are c = 0 and the
+ * count window plays no part, so spectrum[row][t] sums to the row's windows, and hits and depth of ANY window [A, B] are
+ * the sums of spectrum[c] and of c * spectrum[c] over c = A .. B.  The tally rides on the gathers of the lookup.
+ * pk_query_set_spectrum: after pk_query_set_tables and before the first feed (PK_ERR_STATE otherwise), before or after
+ * pk_query_set_bins; on != 0 keeps the spectra, 0 (the default, which a reset restores) does not.  The array takes
+ * rows * N * 2 KiB of device memory beside hits and depth and is sized with them; where it does not fit, the call or the
+ * feed returns an error whose message names the size and what reduces it.
+ * pk_query_spectrum: after pk_indexer_finish.  out receives rows * N * 256 u64, [row][t][c]; rows are the records, or the
+ * B bins in row order when bins are on.  PK_ERR_STATE when spectra are off; PK_ERR_RECS_CAP, with the needed number in the
+ * message, if there are more rows than rows_cap. */
 int pk_query_create(pk_indexer **out, int k, int device);
 int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
 int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);
@@ -196,6 +208,8 @@ int pk_query_bin_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out,
                          uint64_t recs_cap);
 int pk_query_set_coords(pk_indexer *q, int on);
 int pk_query_bin_coords(pk_indexer *q, uint64_t *start_out, uint64_t *end_out, uint64_t bins_cap);
+int pk_query_set_spectrum(pk_indexer *q, int on);
+int pk_query_spectrum(pk_indexer *q, uint64_t *out, uint64_t rows_cap);
 
 /* ---- stats: replaces Header.update_stats (tools.py:246-263) on a host table of n bytes. */
 int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device);

@@ -55,6 +55,8 @@ _SIGNATURES = {
     "pk_query_bin_results": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
     "pk_query_set_coords": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pk_query_bin_coords": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_query_set_spectrum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_query_spectrum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -356,6 +358,18 @@ class QueryIndexer(Indexer):
         end = np.zeros_like(start)
         _check(load().pk_query_bin_coords(self._h, start.ctypes.data, end.ctypes.data, B))
         return start[:B], end[:B]
+
+    def set_spectrum(self, on: bool = True):
+        """pk_query_set_spectrum, after set_tables and before the first feed (before or after set_bins): also tally the
+        table count of every valid window per row and table (off by default; a reset clears the setting)."""
+        _check(load().pk_query_set_spectrum(self._h, 1 if on else 0))
+
+    def spectrum(self, n_rows: int):
+        """pk_query_spectrum after finish(): (n_rows, N, 256) uint64, spectrum[row][t][c] = the windows of the row whose count
+        in table t is c; the rows are the records, or the bins (n_rows = bin_first[-1]) when bins are on."""
+        out = np.zeros((max(n_rows, 1), max(self.n_tables, 1), 256), dtype=np.uint64)
+        _check(load().pk_query_spectrum(self._h, out.ctypes.data, n_rows))
+        return out[:n_rows, :self.n_tables]
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

@@ -30,6 +30,12 @@
 // before r, final once r has opened exactly as P[r] is, and extended by the same k_query_scan.  The window of ordinal o in
 // record r falls in row Bf[r] + (o - P[r]) / W.  From one valid window to the next the row stays or grows by one, so the
 // rows of a slot are as dense as its records are in the per-record case and the tally below serves both.
+// Count spectra (pk_query_set_spectrum): the lookup also tallies every gathered byte, the zeros included, per row and table:
+// spectrum[row][t][c] = #{ j : T_t[a_j] == c }, u64 in HBM.  The tables of a launch are taken one after the other; a
+// slot's first QSPEC_ROWS rows meet in one LDS histogram that is flushed (non-zero entries, one HBM atomic each) and zeroed
+// between two tables, later rows go to HBM directly.  One count usually dominates a table, so equal counts are joined
+// before they reach a counter: a wave that lies in one row first sums the windows that hold the count of its first window
+// across the wave (one LDS atomic for all of them), and every thread joins equal consecutive counts of a row.
 // Every kernel returns at once, writing nothing, when it finds flags[0] raised (the squeeze backed out: the slots still
 // hold an earlier text); the host grows the record and accumulator arrays and repeats the feed's squeeze and these kernels.
 #include <type_traits>
@@ -43,6 +49,7 @@ namespace pk {
 constexpr int QNT = 1024;                 // threads per slot, 16 bases each
 constexpr uint32_t QACC_RECS = 128;       // rows (records or bins) of a slot tallied in LDS; later ones (reads below ~128 bytes of
                                           // text, bins of fewer than 128 windows) go to HBM directly
+constexpr uint32_t QSPEC_ROWS = 32;       // rows of a slot whose count spectrum of one table is tallied in LDS (256 u32 each)
 
 // What thread t of a slot works on: its 16 bases, the 16 before them, and which of its bases end a valid window.
 struct QLane { uint32_t cur, prev, ok; };
@@ -146,16 +153,19 @@ __device__ __forceinline__ unsigned long long q_find(const unsigned long long *_
 }
 
 // BINS: the accumulators' rows are bins of W windows (Bf, W); otherwise records, and Bf and W are not read.
-template <typename KT, bool BINS>
+// SPEC: also spectrum[row][table][256], the tally of every valid window's table count; otherwise `spectrum` is not touched.
+template <typename KT, bool BINS, bool SPEC>
 __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
                                                       const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state, uint32_t k,
                                                       const unsigned long long *__restrict__ slot_first, const unsigned long long *__restrict__ P,
                                                       const unsigned long long *__restrict__ Bf, unsigned long long W,
                                                       const Carry *__restrict__ carry, QueryTables tabs, uint32_t n_tab, uint32_t N, uint32_t t0,
                                                       uint32_t min_count, uint32_t max_count, unsigned long long *__restrict__ hits,
-                                                      unsigned long long *__restrict__ depth, const uint32_t *__restrict__ flags) {
+                                                      unsigned long long *__restrict__ depth, unsigned long long *__restrict__ spectrum,
+                                                      const uint32_t *__restrict__ flags) {
     __shared__ uint32_t wsum[QNT / 64];
     __shared__ uint32_t acc_h[QACC_RECS * QUERY_MAX_TABLES], acc_d[QACC_RECS * QUERY_MAX_TABLES];
+    __shared__ uint32_t acc_s[SPEC ? QSPEC_ROWS * 256u : 1u];   // one table at a time; a slot has at most 16384 windows
     __shared__ unsigned long long rec_range[BINS ? 6 : 2];   // BINS: + the slot's first and last row, P and Bf of its first record
     if (flags[0]) return;
     const uint32_t c = blockIdx.x, lane = threadIdx.x & 63u;
@@ -181,6 +191,8 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
         }
     }
     for (uint32_t i = threadIdx.x; i < QACC_RECS * n_tab; i += QNT) { acc_h[i] = 0u; acc_d[i] = 0u; }
+    if constexpr (SPEC)
+        for (uint32_t i = threadIdx.x; i < QSPEC_ROWS * 256u; i += QNT) acc_s[i] = 0u;
     __syncthreads();
     const unsigned long long r_lo = rec_range[0], r_hi = rec_range[1];
     // the accumulators' rows this slot touches: records, or bins
@@ -250,46 +262,98 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
     // does the whole wave lie in one row?
     const bool has = q.ok != 0u;
     const unsigned long long holders = __ballot(has);
-    if (holders != 0ull) {                                   // wave-uniform; no barrier inside
-        const uint32_t ref = (uint32_t)__shfl((int)rr_first, (int)__builtin_ctzll(holders), 64);
-        const bool wave_one = __all(!has || (rr_first == ref && rr_last == ref));
-        auto add = [&](uint32_t rel, uint32_t tt, uint32_t h, uint32_t d) {
-            if (rel < QACC_RECS) {
-                if (h) atomicAdd(&acc_h[rel * n_tab + tt], h);
-                if (d) atomicAdd(&acc_d[rel * n_tab + tt], d);
-            } else {
-                const unsigned long long at = (row_lo + rel) * N + t0 + tt;
-                if (h) atomicAdd(&hits[at], (unsigned long long)h);
-                if (d) atomicAdd(&depth[at], (unsigned long long)d);
+    // for a wave with a window (holders != 0): the row of its first window, and whether all its windows lie in that row
+    auto wave_ref = [&]() { return (uint32_t)__shfl((int)rr_first, (int)__builtin_ctzll(holders), 64); };
+    auto wave_in = [&](uint32_t ref) { return (bool)__all(!has || (rr_first == ref && rr_last == ref)); };
+    auto add = [&](uint32_t rel, uint32_t tt, uint32_t h, uint32_t d) {
+        if (rel < QACC_RECS) {
+            if (h) atomicAdd(&acc_h[rel * n_tab + tt], h);
+            if (d) atomicAdd(&acc_d[rel * n_tab + tt], d);
+        } else {
+            const unsigned long long at = (row_lo + rel) * N + t0 + tt;
+            if (h) atomicAdd(&hits[at], (unsigned long long)h);
+            if (d) atomicAdd(&depth[at], (unsigned long long)d);
+        }
+    };
+    // n windows of row `rel` (relative to the slot's first) with the count cnt in table tt
+    auto add_spec = [&](uint32_t rel, uint32_t tt, uint32_t cnt, uint32_t n) {
+        if (rel < QSPEC_ROWS) atomicAdd(&acc_s[rel * 256u + cnt], n);
+        else atomicAdd(&spectrum[((row_lo + rel) * N + t0 + tt) * 256ull + cnt], (unsigned long long)n);
+    };
+    // one table for this thread's windows; wave-uniform where it matters, no barrier inside
+    auto tally = [&](uint32_t tt, const uint32_t ref, const bool wave_one) {
+        const uint8_t *__restrict__ T = tabs.t[tt];
+        uint32_t cv[16];                                     // all gathers of a table in flight before the first is used
+#pragma unroll
+        for (int j = 0; j < 16; j++) cv[j] = ((q.ok >> j) & 1u) ? (uint32_t)T[a[j]] : 0u;   // a count of 0 lies in no window (min >= 1)
+        if (wave_one) {
+            uint32_t h = 0, d = 0;
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const bool in = cv[j] >= min_count && cv[j] <= max_count;
+                h += in ? 1u : 0u; d += in ? cv[j] : 0u;
             }
-        };
-        for (uint32_t tt = 0; tt < n_tab; tt++) {
-            const uint8_t *__restrict__ T = tabs.t[tt];
-            uint32_t cv[16];                                 // all gathers of a table in flight before the first is used
+            for (int s = 32; s; s >>= 1) { h += __shfl_down(h, s, 64); d += __shfl_down(d, s, 64); }
+            if (lane == 0u) add(ref, tt, h, d);
+        } else if (has) {
+            uint32_t cur = rr_first, h = 0, d = 0;
 #pragma unroll
-            for (int j = 0; j < 16; j++) cv[j] = ((q.ok >> j) & 1u) ? (uint32_t)T[a[j]] : 0u;   // a count of 0 lies in no window (min >= 1)
-            if (wave_one) {
-                uint32_t h = 0, d = 0;
-#pragma unroll
-                for (int j = 0; j < 16; j++) {
+            for (int j = 0; j < 16; j++) {
+                if ((q.ok >> j) & 1u) {
+                    if (rr[j] != cur) { add(cur, tt, h, d); h = 0; d = 0; cur = rr[j]; }
                     const bool in = cv[j] >= min_count && cv[j] <= max_count;
                     h += in ? 1u : 0u; d += in ? cv[j] : 0u;
                 }
-                for (int s = 32; s; s >>= 1) { h += __shfl_down(h, s, 64); d += __shfl_down(d, s, 64); }
-                if (lane == 0u) add(ref, tt, h, d);
-            } else if (has) {
-                uint32_t cur = rr_first, h = 0, d = 0;
-#pragma unroll
-                for (int j = 0; j < 16; j++) {
-                    if ((q.ok >> j) & 1u) {
-                        if (rr[j] != cur) { add(cur, tt, h, d); h = 0; d = 0; cur = rr[j]; }
-                        const bool in = cv[j] >= min_count && cv[j] <= max_count;
-                        h += in ? 1u : 0u; d += in ? cv[j] : 0u;
-                    }
-                }
-                add(cur, tt, h, d);
             }
+            add(cur, tt, h, d);
         }
+        if constexpr (SPEC) {
+            // peel: the count of the wave's first window, summed over the wave (the dominant count, more often than not);
+            // 256 is no count and peels nothing
+            uint32_t peel = 256u;
+            if (wave_one) {
+                uint32_t mine = 0u, n0 = 0u;
+#pragma unroll
+                for (int j = 15; j >= 0; j--) mine = ((q.ok >> j) & 1u) ? cv[j] : mine;
+                peel = (uint32_t)__shfl((int)mine, (int)__builtin_ctzll(holders), 64);
+#pragma unroll
+                for (int j = 0; j < 16; j++) n0 += (((q.ok >> j) & 1u) && cv[j] == peel) ? 1u : 0u;
+                for (int s = 32; s; s >>= 1) n0 += __shfl_down(n0, s, 64);
+                if (lane == 0u) add_spec(ref, tt, peel, n0);
+            }
+            // the rest: runs of equal (row, count)
+            uint32_t cur_r = 0u, cur_c = 0u, n = 0u;
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                if (((q.ok >> j) & 1u) && cv[j] != peel) {
+                    if (n && (rr[j] != cur_r || cv[j] != cur_c)) { add_spec(cur_r, tt, cur_c, n); n = 0u; }
+                    cur_r = rr[j]; cur_c = cv[j]; n++;
+                }
+            }
+            if (n) add_spec(cur_r, tt, cur_c, n);
+        }
+    };
+    if constexpr (SPEC) {
+        const unsigned long long span = row_hi - row_lo + 1ull;
+        const uint32_t n_spec = (uint32_t)(span < QSPEC_ROWS ? span : QSPEC_ROWS) * 256u;
+        const uint32_t ref = holders != 0ull ? wave_ref() : 0u;
+        const bool wave_one = holders != 0ull && wave_in(ref);
+        for (uint32_t tt = 0; tt < n_tab; tt++) {            // uniform: the barriers are met by every thread
+            if (holders != 0ull) tally(tt, ref, wave_one);
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < n_spec; i += QNT) {
+                const uint32_t v = acc_s[i];
+                if (v) {
+                    atomicAdd(&spectrum[((row_lo + i / 256u) * N + t0 + tt) * 256ull + i % 256u], (unsigned long long)v);
+                    acc_s[i] = 0u;
+                }
+            }
+            __syncthreads();
+        }
+    } else if (holders != 0ull) {                            // wave-uniform
+        const uint32_t ref = wave_ref();
+        const bool wave_one = wave_in(ref);
+        for (uint32_t tt = 0; tt < n_tab; tt++) tally(tt, ref, wave_one);
     }
     __syncthreads();
     {
@@ -339,15 +403,17 @@ void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuff
 
 void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
-                         unsigned long long *hits, unsigned long long *depth, hipStream_t s) {
+                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, hipStream_t s) {
     QueryTables tabs;
     for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
-#define PK_QUERY_LOOKUP(KT, BINS) hipLaunchKernelGGL((k_query_lookup<KT, BINS>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
+#define PK_QUERY_LOOKUP(KT, BINS, SPEC) hipLaunchKernelGGL((k_query_lookup<KT, BINS, SPEC>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
                                                      (const uint32_t *)b.restarts, (const uint32_t *)b.n_bases, st2, pl.k,                                  \
                                                      (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, carry, tabs, n_tab, \
-                                                     N, t0, min_count, max_count, hits, depth, (const uint32_t *)b.flags)
-    if (pl.k <= 15) { if (bin_windows) PK_QUERY_LOOKUP(uint32_t, true); else PK_QUERY_LOOKUP(uint32_t, false); }
-    else { if (bin_windows) PK_QUERY_LOOKUP(uint64_t, true); else PK_QUERY_LOOKUP(uint64_t, false); }
+                                                     N, t0, min_count, max_count, hits, depth, spectrum, (const uint32_t *)b.flags)
+#define PK_QUERY_LOOKUP_K(BINS, SPEC) do { if (pl.k <= 15) PK_QUERY_LOOKUP(uint32_t, BINS, SPEC); else PK_QUERY_LOOKUP(uint64_t, BINS, SPEC); } while (0)
+    if (spectrum) { if (bin_windows) PK_QUERY_LOOKUP_K(true, true); else PK_QUERY_LOOKUP_K(false, true); }
+    else { if (bin_windows) PK_QUERY_LOOKUP_K(true, false); else PK_QUERY_LOOKUP_K(false, false); }
+#undef PK_QUERY_LOOKUP_K
 #undef PK_QUERY_LOOKUP
 }
 

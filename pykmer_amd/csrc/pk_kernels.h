@@ -129,10 +129,11 @@ size_t query_workspace(uint32_t n_chunks, uint8_t *base = nullptr, PartBuffers *
 void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,
                        const Carry *carry, uint64_t p_done, unsigned long long *P, unsigned long long *Bf, uint64_t bin_windows, hipStream_t s);
 // tables[0 .. n_tab) are columns t0 .. t0 + n_tab of the row-major [row][N] u64 accumulators hits / depth; a row is a record
-// (bin_windows = 0) or a bin of bin_windows valid windows: row Bf[r] + (o - P[r]) / W for the window of ordinal o in record r
+// (bin_windows = 0) or a bin of bin_windows valid windows: row Bf[r] + (o - P[r]) / W for the window of ordinal o in record r.
+// spectrum: null, or the [row][N][256] u64 tally of the table counts of every valid window (the same rows), added to
 void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
-                         unsigned long long *hits, unsigned long long *depth, hipStream_t s);
+                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, hipStream_t s);
 
 // kmer_coords.hip -- base coordinates of a binned query's rows (DESIGN.md 4.10 "Coordinates"), behind launch_query_scan of the
 // same feed (slot_first, P, Bf) and its squeeze (recs[].n_valid).  chunk_pos: n_chunks words of scratch.  pos_in: the position

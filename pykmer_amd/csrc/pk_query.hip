@@ -11,10 +11,11 @@ int QueryState::create() {
 }
 
 int QueryState::reset(hipStream_t s) {
-    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos})
+    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos, &spec})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, s));
     windows = p_done = 0;
     bin = n_bins = 0;
+    spectrum = false;
     coords = false; pos_in = 0; t_coords = 0;
     return PK_OK;
 }
@@ -25,9 +26,36 @@ int QueryState::grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s) {
     const size_t row = tables.size() * sizeof(unsigned long long);
     int rc = P.grow_keep(cap * sizeof(unsigned long long), s);
     if (rc) return rc;
-    if (bin) return (rc = Bf.grow_keep(cap * sizeof(unsigned long long), s)) ? rc : ensure_rows(cap, bytes, s);
-    if ((rc = hits.grow_keep(cap * row, s))) return rc;
-    return depth.grow_keep(cap * row, s);
+    if (bin) {
+        if ((rc = Bf.grow_keep(cap * sizeof(unsigned long long), s))) return rc;
+        if ((rc = ensure_rows(cap, bytes, s))) return rc;
+    } else {
+        if ((rc = hits.grow_keep(cap * row, s))) return rc;
+        if ((rc = depth.grow_keep(cap * row, s))) return rc;
+    }
+    return ensure_spectrum(cap, bytes, s);
+}
+
+// Count spectra: 256 u64 per table for every row hits and depth have (per record: `cap` rows; binned: those of ensure_rows),
+// contents kept, the rest zero.  They grow to exactly what is needed: 256 times the size of hits, the old and the new array
+// side by side are what the device has to hold, and a copy at HBM speed per feed is cheap beside the lookups.  An array that
+// does not fit is an error that names its size and what makes it smaller.
+int QueryState::ensure_spectrum(uint64_t cap, uint64_t bytes, hipStream_t s) {
+    if (!spectrum) return PK_OK;
+    const uint64_t rows = bin ? bytes / bin + cap + 1 : cap;
+    const size_t N = tables.size(), per_row = N * 256 * sizeof(unsigned long long);
+    const char *helps = "take fewer tables per run, larger bins or a smaller query";
+    if (rows > SIZE_MAX / 2 / per_row)
+        return fail(PK_ERR_ARG, "count spectra of %llu rows and %zu tables (2 KiB each) are beyond the address space; %s", (unsigned long long)rows, N,
+                    helps);
+    if (rows * per_row <= spec.bytes) return PK_OK;
+    const size_t want = rows * per_row;
+    const int rc = spec.grow_keep(want, s);
+    if (!rc) return PK_OK;
+    (void)hipGetLastError();
+    const std::string why = g_err;
+    return fail(rc, "count spectra need an accumulator of %zu bytes (%llu rows, %zu tables, 2 KiB each); %s: %s", want, (unsigned long long)rows, N, helps,
+                why.c_str());
 }
 
 // Binned query: the accumulators, and with coordinates their two arrays, hold the rows that `bytes` bytes of stream and
@@ -77,6 +105,7 @@ static bool has_tables(const QueryState &q) { return !q.tables.empty(); }
 static bool binned(const QueryState &q) { return q.bin != 0; }
 static bool per_record(const QueryState &q) { return q.bin == 0; }
 static bool with_coords(const QueryState &q) { return q.coords; }
+static bool with_spectrum(const QueryState &q) { return q.spectrum; }
 
 extern "C" int pk_query_create(pk_indexer **out, int k, int device) {
     if (k > 17) return fail(PK_ERR_ARG, "a query takes kmer_len <= 17 (one unsliced table), got %d", k);
@@ -100,7 +129,7 @@ extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
     }
-    return PK_OK;
+    return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);   // (all zero before the first feed, whatever N was)
 }
 
 extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
@@ -109,10 +138,22 @@ extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
     QueryState &q = *ix->q;
     q.bin = bin_windows;
     q.coords = false;                                        // pk_query_set_coords comes after the bins
-    if (!bin_windows) return PK_OK;
+    if (!bin_windows) return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
     // Bf beside P; a reset zeroed what was there, a new array is zeroed here
-    const int rc = q.Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
-    return rc ? rc : q.ensure_rows(ix->recs_cap(), 0, ix->stream);
+    int rc = q.Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
+    if (rc || (rc = q.ensure_rows(ix->recs_cap(), 0, ix->stream))) return rc;
+    return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
+}
+
+extern "C" int pk_query_set_spectrum(pk_indexer *ix, int on) {
+    if (int rc = query_check(ix, has_tables, "pk_query_set_tables comes before pk_query_set_spectrum", "the spectra are set before the first feed (reset the indexer first)")) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    QueryState &q = *ix->q;
+    q.spectrum = on != 0;
+    // a reset zeroed what was there, a new array is zeroed here; per record or for the bins set so far
+    const int rc = q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
+    if (rc) q.spectrum = false;                              // an array that did not fit: the setting did not take
+    return rc;
 }
 
 extern "C" int pk_query_set_coords(pk_indexer *ix, int on) {
@@ -188,5 +229,17 @@ extern "C" int pk_query_results(pk_indexer *ix, uint64_t *hits_out, uint64_t *de
     const size_t n = ix->n_recs * ix->q->tables.size() * sizeof(uint64_t);
     HIPCHK(hipMemcpy(hits_out, ix->q->hits.p, n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(depth_out, ix->q->depth.p, n, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_spectrum(pk_indexer *ix, uint64_t *out, uint64_t rows_cap) {
+    if (int rc = query_check(ix, with_spectrum, "the indexer keeps no count spectra (pk_query_set_spectrum)", nullptr)) return rc;
+    const QueryState &q = *ix->q;
+    const uint64_t rows = q.bin ? q.n_bins : ix->n_recs;
+    if (rows > rows_cap) return fail(PK_ERR_RECS_CAP, "%llu rows, capacity %llu", (unsigned long long)rows, (unsigned long long)rows_cap);
+    if (rows == 0) return PK_OK;
+    if (!out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipMemcpy(out, q.spec.p, rows * q.tables.size() * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PK_OK;
 }

@@ -17,6 +17,11 @@ rows are ordered by record, then by bin, and bin_first[r] is record r's first ro
 With `coords` every row also gets its place on the record in bases (pk_query_set_coords): bin_start = the position of the
 first base of the row's first window, bin_end = one past the last base of its last window, positions counted within the
 record as seq_len counts them (0-based; every sequence character, valid or not, and the blanks inside a sequence line).
+
+With `spectrum` the same lookup also tallies, per row (record, or bin) and table, how many valid windows have each table
+count (pk_query_set_spectrum): spectrum[row][t][c], c = 0 .. 255, zeros (absent k-mers) included and independent of the
+count window.  Hits and depth of any window, the median and every quantile of a row's k-mer counts follow from it
+(pykmer_amd.qspectrum re-windows a written `.kmh` without tables or a GPU).
 """
 import argparse
 import os
@@ -79,6 +84,14 @@ def record_sums(rows: np.ndarray, bin_first: np.ndarray) -> np.ndarray:
     return cum[first[1:]] - cum[first[:-1]]
 
 
+def spectrum_record_sums(rows: np.ndarray, bin_first: np.ndarray) -> np.ndarray:
+    """record_sums for (B, N, 256) spectra: the (R, N, 256) sums over each record's rows."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    assert rows.ndim == 3
+    width = rows.shape[1] * rows.shape[2]                   # (spelled out: a query without a window has no row to infer it from)
+    return record_sums(rows.reshape(rows.shape[0], width), bin_first).reshape((len(bin_first) - 1,) + rows.shape[1:])
+
+
 def table_groups(n_tables: int, table_bytes: int, budget: int) -> List[Tuple[int, int]]:
     """[lo, hi) index ranges of the tables staged together: as many as fit `budget` bytes, at least one."""
     per = max(1, int(budget) // max(1, int(table_bytes)))
@@ -113,11 +126,12 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
 
 
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
-              bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0) -> dict:
+              bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0, spectrum: bool = False) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
     same query only add columns).  `bin_windows`: tally per bin (bin_hits, bin_depth, bin_first); the per-record arrays
     are then the sums of each record's rows.  `coords`: also bin_start, bin_end -- on the `first` stream only, they do
-    not depend on the tables.  `min_qual_byte`: a FASTQ query's bases below this quality byte count as N (qual_threshold)."""
+    not depend on the tables.  `min_qual_byte`: a FASTQ query's bases below this quality byte count as N (qual_threshold).
+    `spectrum`: also the count spectra, `spectrum` (R, N, 256) and, binned, `bin_spectrum` (B, N, 256)."""
     coords = bool(coords) and first
     src = _Input(query_file, keep=first, quiet=not first)
     binned = {}
@@ -127,6 +141,8 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
             q.set_bins(bin_windows)
             if coords:
                 q.set_coords(True)
+        if spectrum:
+            q.set_spectrum(True)
         for piece in src.pieces():
             q.feed(piece)
         fin = q.finish()
@@ -138,8 +154,13 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
             if coords:
                 bin_start, bin_end = q.bin_coords()
                 binned.update(bin_start=bin_start.copy(), bin_end=bin_end.copy())
+            if spectrum:
+                binned["bin_spectrum"] = q.spectrum(int(bin_first[-1]))
+                binned["spectrum"] = spectrum_record_sums(binned["bin_spectrum"], bin_first)
         else:
             hits, depth = q.results(fin["n_records"])
+            if spectrum:
+                binned["spectrum"] = q.spectrum(fin["n_records"])
         timings = q.timings()
         masked = {"masked": q.fastq_masked()} if min_qual_byte else {}
     out = {"seq_len": recs["seq_len"].astype(np.uint64), "n_valid": recs["n_valid_kmers"].astype(np.uint64), "hits": hits.copy(),
@@ -150,7 +171,8 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
 
 
 def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
-                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False, min_qual: int = 0, qual_offset: int = 33) -> dict:
+                  threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False, min_qual: int = 0, qual_offset: int = 33,
+                  spectrum: bool = False) -> dict:
     """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
     merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
     kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
@@ -170,7 +192,12 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
 
     `min_qual` = Q > 0 (a FASTQ query only; ValueError otherwise): bases whose quality byte is below Q + qual_offset count
     as N (README "Base quality"); the result gains `masked`, their number.  `run` receives min_qual_byte by keyword, and
-    only when it is set."""
+    only when it is set.
+
+    `spectrum` = True adds `spectrum` (R, N, 256) uint64, spectrum[r][t][c] = the valid windows of record r whose count in
+    table t is c (0 = absent; the count window plays no part), and `median` (R, N) uint8, the lower median of those counts
+    (qspectrum.median_from_spectrum).  With `bin_windows` also `bin_spectrum` (B, N, 256) and `bin_median` (B, N), and
+    `spectrum` is the sum over each record's rows.  `run` receives spectrum=True by keyword, and only when it is set."""
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
@@ -178,6 +205,8 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     extra = {} if bin_windows is None else {"bin_windows": bin_windows}
     if coords:
         extra["coords"] = True
+    if spectrum:
+        extra["spectrum"] = True
     if min_qual:
         extra["min_qual_byte"] = qual_threshold(str(query_file), min_qual, qual_offset)
     tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
@@ -212,8 +241,16 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
                 assert np.array_equal(part["bin_first"], result["bin_first"]), "bins changed between table groups"
                 result["bin_hits"] = np.concatenate([result["bin_hits"], part["bin_hits"]], axis=1)
                 result["bin_depth"] = np.concatenate([result["bin_depth"], part["bin_depth"]], axis=1)
+            for key in ("spectrum", "bin_spectrum") if spectrum else ():
+                if key in result:
+                    result[key] = np.concatenate([result[key], part[key]], axis=1)
     if bin_windows is not None:
         result["bin_windows"] = bin_windows
+    if spectrum:
+        from .qspectrum import median_from_spectrum
+        result["median"] = median_from_spectrum(result["spectrum"])
+        if bin_windows is not None:
+            result["bin_median"] = median_from_spectrum(result["bin_spectrum"])
     if coords:
         assert result["bin_start"].shape == result["bin_end"].shape == (int(result["bin_first"][-1]),)
         result["coords_s"] = coords_s
@@ -299,12 +336,61 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
                             max_count=np.int64(result["max_count"]), **coords)
 
 
+def kmh_paths(project_name: str) -> Tuple[Path, Path, Path]:
+    return Path(f"{project_name}.kmh"), Path(f"{project_name}.kmh.json"), Path(f"{project_name}.kmh.tsv")
+
+
+def write_kmh(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
+    """`<project>.kmh` (np.savez_compressed), `.kmh.json` and `.kmh.tsv`: the count spectra of a result with `spectrum`, each
+    file through `.tmp` + rename.  The rows are the records; those of a binned result (bin_spectrum) are its bins, and the
+    `.kmh` then holds bin_first and bin_windows and the json bin_windows and n_bins.  The json has the keys of the
+    `.kmq.json` but the count window, which the spectra do not depend on; the tsv has the leading columns of the `.kmq.tsv`
+    (binned: of the `.kmb.tsv`, without coordinates) and every table's median count."""
+    from .qspectrum import median_from_spectrum
+    kmh, meta, tsv = kmh_paths(project_name)
+    binned = "bin_spectrum" in result
+    spec = np.ascontiguousarray(result["bin_spectrum" if binned else "spectrum"], dtype=np.uint64)
+    key = "bin_median" if binned else "median"
+    median = np.ascontiguousarray(result[key], dtype=np.uint8) if key in result else median_from_spectrum(spec)
+    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
+    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
+    names = [n.strip() for n in result["names"]]
+    assert n_valid.shape == seq_len.shape == (len(names),)
+    arrays, more = {}, {}
+    if binned:
+        W = int(result["bin_windows"])
+        bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
+        assert bin_first.shape == (len(names) + 1,)
+        rows = int(bin_first[-1])
+        arrays = {"bin_first": bin_first, "bin_windows": np.uint64(W)}
+        more = {"bin_windows": W, "n_bins": rows}
+    else:
+        rows = len(names)
+    assert spec.shape == (rows, len(columns), 256) and median.shape == (rows, len(columns))
+    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "query_file": str(query_file), "records": names, "data": data, **more}
+    output.update(_qual_keys(result))
+    write_json(meta, output)
+    with atomic_write(tsv, "wt") as fhd:
+        fhd.write("\t".join((["record", "bin", "first_window", "n_windows"] if binned else ["record", "seq_len", "n_valid"]) + [str(c) for c in columns]) + "\n")
+        for r, name in enumerate(names):
+            if binned:
+                m = int(n_valid[r])
+                for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
+                    at = int(bin_first[r]) + b
+                    fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + [str(int(v)) for v in median[at]]) + "\n")
+            else:
+                fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in median[r]]) + "\n")
+    with atomic_write(kmh, "wb") as fhd:
+        np.savez_compressed(fhd, spectrum=spec, median=median, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]), **arrays)
+
+
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
           threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None, coords: bool = False, min_qual: int = None,
-          qual_offset: int = None) -> dict:
+          qual_offset: int = None, spectrum: bool = False) -> dict:
     """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result.
     `coords` (with `bin_windows`) adds the rows' base coordinates to the `.kmb` files.  `min_qual` / `qual_offset`
-    (--min-qual, --qual-offset; None: not given) mask a FASTQ query's low-quality bases and are recorded in the json files."""
+    (--min-qual, --qual-offset; None: not given) mask a FASTQ query's low-quality bases and are recorded in the json files.
+    `spectrum` (--spectrum) also writes the three `.kmh` files: the count spectra of the rows (write_kmh)."""
     qual_threshold(str(query_file), min_qual, qual_offset)
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
@@ -315,7 +401,9 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         extra["coords"] = True
     if min_qual:
         extra.update(min_qual=min_qual, qual_offset=33 if qual_offset is None else qual_offset)
-    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()):
+    if spectrum:
+        extra["spectrum"] = True
+    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()) + (kmh_paths(project_name) if spectrum else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
     if not os.path.exists(query_file):
@@ -330,6 +418,8 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
                                **extra)
     except _lib.PkError as exc:
+        if spectrum and exc.code == _lib.PK_ERR_HIP and "count spectra need" in str(exc):
+            raise ValueError(f"{exc}; the spectra of --spectrum do not fit the device") from exc
         if bin_windows is None or exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
             raise
         raise ValueError(f"{exc}; the rows of --bin {bin_windows} do not fit the device: use a larger --bin") from exc
@@ -338,6 +428,8 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
     write_kmq(project_name, result, query_file, data, columns)
     if bin_windows is not None:
         write_kmb(project_name, result, query_file, data, columns)
+    if spectrum:
+        write_kmh(project_name, result, query_file, data, columns)
     _mark("files renamed")
     return result
 
@@ -354,6 +446,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Also write <P>.kmb[.json|.tsv]: the hits along each record in bins of W valid windows [off]")
     parser.add_argument("--coords", action="store_true",
                         help="With --bin: add every bin's base coordinates within its record (start, end) to the .kmb files [off]")
+    parser.add_argument("--spectrum", action="store_true",
+                        help="Also write <P>.kmh[.json|.tsv]: per record (with --bin: per bin) and table the count spectrum of its "
+                             "k-mers and their median count; python -m pykmer_amd.qspectrum re-windows it [off]")
     parser.add_argument("--min-qual", type=int, default=None, metavar="Q",
                         help="FASTQ query: bases with a quality below Q count as N [off]")
     parser.add_argument("--qual-offset", type=int, default=None, metavar="O", help="With --min-qual: the quality encoding, 33 or 64 [33]")
@@ -365,7 +460,7 @@ def main(argv: List[str] = None) -> None:
     try:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
                        device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows,
-                       **({"coords": True} if args.coords else {}),
+                       **({"coords": True} if args.coords else {}), **({"spectrum": True} if args.spectrum else {}),
                        **({"min_qual": args.min_qual, "qual_offset": args.qual_offset} if args.min_qual is not None or args.qual_offset is not None else {}))
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)

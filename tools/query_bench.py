@@ -13,6 +13,13 @@ HIP-event times of the structure pass, the squeeze and the lookup kernels (pk_in
                    bin_results instead of results
     --coords       with --bin: the rows' base coordinates too (pk_query_set_coords, kmer_coords.hip), fetched with
                    bin_coords; `coords_s_runs` holds the coordinate kernels' HIP-event time of every timed run
+    --spectrum     count spectra (pk_query_set_spectrum, DESIGN.md 4.10 "Count spectra"): per shape and kind of table the
+                   lookup with the option off and on, per record and in bins of 10 000 and of 100 windows (with --bin W:
+                   in bins of W only), the text uploaded and the tables staged once for all of them.  The kinds of table are
+                   the 13 genome tables and 13 tables that are all zero (one count dominates).  The wall clock of a run
+                   with the option on includes the download of the spectra (skipped, and said so, above
+                   PK_QUERY_BENCH_MAX_DOWNLOAD bytes [16 GiB]); a configuration whose spectra do not fit the device is
+                   recorded with the library's refusal.  Writes profiles/query_spectrum_k15_n13.json.
     --runs R       timed runs per shape [5]
     --no-trace     skip the rocprofv3 run
     PK_QUERY_BENCH_BP / PK_QUERY_BENCH_TABLE_BP scale the genome and the table genomes down for a rehearsal.
@@ -41,13 +48,14 @@ from pykmer_amd import _lib  # noqa: E402
 K, N = 15, 13
 
 
-def stage_tables(table_bp: int):
+def stage_tables(table_bp: int, zero: bool = False):
+    """13 tables counted from the members of synth.family; zero: counted from nothing, so every count is 0."""
     bufs = []
     with _lib.Indexer(K) as ix:
         for i in range(N):
-            fa, _ = synth.family(i, table_bp)
             ix.reset()
-            ix.feed(fa)
+            if not zero:
+                ix.feed(synth.family(i, table_bp)[0])
             ix.finish()
             b = _lib.DeviceBuffer(4 ** K)
             ix.table_slice_to_device(b.ptr, 0, 4 ** K)
@@ -110,6 +118,82 @@ def run_shape(make, ptrs, runs: int, bin_windows: int = None, coords: bool = Fal
         text.free()
 
 
+def time_config(q, text, n_bytes: int, ptrs, runs: int, bin_windows, spectrum: bool, max_download: int) -> dict:
+    """1 warm-up + `runs` timed runs of one configuration on an indexer that other configurations have used before."""
+    walls, lookups, rows, download = [], [], 0, None
+    try:
+        for i in range(runs + 1):
+            q.reset()
+            q.set_tables(ptrs, 1, 255)
+            if bin_windows is not None:
+                q.set_bins(bin_windows)
+            if spectrum:
+                q.set_spectrum(True)
+            t0 = time.perf_counter()
+            q.feed_device(text.ptr, n_bytes)
+            fin = q.finish()
+            if bin_windows is not None:
+                hits, depth, bin_first = q.bin_results(fin["n_records"])
+            else:
+                hits, depth = q.results(fin["n_records"])
+            rows = int(hits.shape[0])
+            spec_bytes = rows * len(ptrs) * 2048
+            if spectrum:
+                download = spec_bytes <= max_download
+                if download:
+                    spec = q.spectrum(rows)
+                    if i == 0:                               # once per configuration: the identities of the definition
+                        sums = spec.sum(axis=2, dtype=np.uint64)
+                        assert (sums == sums[:, :1]).all() and int(sums[:, 0].sum()) == fin["num_kmers"], "spectra do not sum to the windows"
+                        assert np.array_equal(spec[:, :, 1:].sum(axis=2, dtype=np.uint64), hits), "window 1-255 of the spectra is not the hits"
+                    del spec
+            if i:
+                walls.append(time.perf_counter() - t0)
+                lookups.append(float(q.timings()["lookup_s"]))
+    except _lib.PkError as exc:
+        return {"bin_windows": bin_windows, "spectrum": spectrum, "refused": str(exc)}
+    return {"bin_windows": bin_windows, "spectrum": spectrum, "rows": rows, "spectrum_bytes": rows * len(ptrs) * 2048 if spectrum else 0,
+            "downloaded": download, "lookup_s_runs": lookups, "lookup_s_median": statistics.median(lookups), "lookup_s_min": min(lookups),
+            "lookup_s_max": max(lookups), "wall_s_runs": walls, "wall_s_median": statistics.median(walls)}
+
+
+def run_spectrum_matrix(genome_bp: int, table_bp: int, runs: int, bins, path: str) -> dict:
+    max_download = int(os.environ.get("PK_QUERY_BENCH_MAX_DOWNLOAD", 16 << 30))
+    out = {"k": K, "n_tables": N, "table_genome_bp": table_bp, "runs": runs,
+           "method": f"per configuration 1 warm-up + {runs} runs of reset/set_*/feed_device/finish/results[/spectrum]; lookup_s from HIP events "
+                     "(pk_indexer_timings), wall_s around the blocking calls, the download of the spectra included where `downloaded`",
+           "on_over_off": "lookup_s_median with the option on over the one with it off, same bins, same tables, same build"}
+    texts = {}
+    for name, make in shapes(genome_bp):
+        fa, bp = make()
+        buf = _lib.DeviceBuffer(len(fa) + 64)
+        buf.upload(np.asarray(fa))
+        texts[name] = (buf, len(fa), int(bp))
+        del fa
+    for kind in ("genome_tables", "zero_tables"):
+        bufs = stage_tables(table_bp, zero=kind == "zero_tables")
+        ptrs = [b.ptr for b in bufs]
+        out[kind] = {}
+        for name, (buf, n_bytes, bp) in texts.items():
+            res = out[kind][name] = {"bp": bp, "text_bytes": n_bytes, "configs": []}
+            with _lib.QueryIndexer(K) as q:
+                for W in bins:
+                    off = time_config(q, buf, n_bytes, ptrs, runs, W, False, max_download)
+                    on = time_config(q, buf, n_bytes, ptrs, runs, W, True, max_download)
+                    if "refused" not in on and "refused" not in off:
+                        on["on_over_off"] = on["lookup_s_median"] / off["lookup_s_median"]
+                    res["configs"] += [off, on]
+                    print(kind, name, json.dumps(off), json.dumps(on), flush=True)
+            with open(path + ".tmp", "w") as fh:             # what is measured so far survives a run that is cut short
+                json.dump(out, fh, indent=1)
+            os.replace(path + ".tmp", path)
+        for b in bufs:
+            b.free()
+    for buf, _, _ in texts.values():
+        buf.free()
+    return out
+
+
 def kernel_stats(argv, dest):
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     d = tempfile.mkdtemp(prefix="qprof")
@@ -136,6 +220,10 @@ def main():
         sys.exit("error: --coords needs --bin W")
     genome_bp = int(os.environ.get("PK_QUERY_BENCH_BP", 800_000_000))
     table_bp = int(os.environ.get("PK_QUERY_BENCH_TABLE_BP", 40_000_000))
+    if "--spectrum" in sys.argv:
+        path = args[0] if args else os.path.join(ROOT, "profiles", "query_spectrum_k15_n13.json")
+        run_spectrum_matrix(genome_bp, table_bp, runs, [bin_windows] if bin_windows is not None else [None, 10_000, 100], path)
+        return
     bufs = stage_tables(table_bp)
     ptrs = [b.ptr for b in bufs]
     if "--once" in sys.argv:
