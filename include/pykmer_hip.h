@@ -198,7 +198,20 @@ void pk_indexer_destroy(pk_indexer *ix);
  * feed returns an error whose message names the size and what reduces it.
  * pk_query_spectrum: after pk_indexer_finish.  out receives rows * N * 256 u64, [row][t][c]; rows are the records, or the
  * B bins in row order when bins are on.  PK_ERR_STATE when spectra are off; PK_ERR_RECS_CAP, with the needed number in the
- * message, if there are more rows than rows_cap. */
+ * message, if there are more rows than rows_cap.
+ *
+ * Shared windows: per row (a record, or a bin when bins are on) and pair of tables i < j, how many of the row's valid windows
+ * lie in the count window of both,  shared[row][p] = #{ j : min <= T_i[a_j] <= max and min <= T_j[a_j] <= max },  exact u64;
+ * p numbers the P = N (N - 1) / 2 pairs in row-major order: (0,1) (0,2) .. (0,N-1) (1,2) ..  The diagonal is hits[row][t].
+ * The tally rides on the gathers of the lookup, which needs the tables of a pair in one launch: at most 16 tables.
+ * pk_query_set_pairs: after pk_query_set_tables and before the first feed (PK_ERR_STATE otherwise), before or after
+ * pk_query_set_bins; on != 0 keeps the shared windows, 0 (the default, which a reset restores) does not.  PK_ERR_ARG with
+ * more than 16 tables, or while count spectra are on (the two are tallied in separate streams).  The array takes
+ * rows * P * 8 bytes of device memory beside hits and depth and is sized with them; where it does not fit, the call or the
+ * feed returns an error whose message names the size and what reduces it.
+ * pk_query_pairs: after pk_indexer_finish.  out receives rows * P u64, [row][p]; rows are the records, or the B bins in row
+ * order when bins are on.  PK_ERR_STATE when pairs are off; PK_ERR_RECS_CAP, with the needed number in the message, if
+ * there are more rows than rows_cap. */
 int pk_query_create(pk_indexer **out, int k, int device);
 int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
 int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);
@@ -210,6 +223,8 @@ int pk_query_set_coords(pk_indexer *q, int on);
 int pk_query_bin_coords(pk_indexer *q, uint64_t *start_out, uint64_t *end_out, uint64_t bins_cap);
 int pk_query_set_spectrum(pk_indexer *q, int on);
 int pk_query_spectrum(pk_indexer *q, uint64_t *out, uint64_t rows_cap);
+int pk_query_set_pairs(pk_indexer *q, int on);
+int pk_query_pairs(pk_indexer *q, uint64_t *out, uint64_t rows_cap);
 
 /* ---- stats: replaces Header.update_stats (tools.py:246-263) on a host table of n bytes. */
 int pk_table_stats(const uint8_t *table, uint64_t n, uint64_t hist256_out[256], int device);

@@ -57,6 +57,8 @@ _SIGNATURES = {
     "pk_query_bin_coords": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_query_set_spectrum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pk_query_spectrum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_query_set_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_query_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -370,6 +372,19 @@ class QueryIndexer(Indexer):
         out = np.zeros((max(n_rows, 1), max(self.n_tables, 1), 256), dtype=np.uint64)
         _check(load().pk_query_spectrum(self._h, out.ctypes.data, n_rows))
         return out[:n_rows, :self.n_tables]
+
+    def set_pairs(self, on: bool = True):
+        """pk_query_set_pairs, after set_tables (at most 16) and before the first feed (before or after set_bins): also tally,
+        per row and pair of tables, the windows valid in both (off by default; a reset clears the setting)."""
+        _check(load().pk_query_set_pairs(self._h, 1 if on else 0))
+
+    def pairs(self, n_rows: int):
+        """pk_query_pairs after finish(): (n_rows, P) uint64, P = N (N - 1) / 2, shared[row][p] = the windows of the row valid
+        in both tables of pair p (spectrum.pair_list(N)[p]); the rows are the records, or the bins when bins are on."""
+        P = self.n_tables * (self.n_tables - 1) // 2
+        out = np.zeros((max(n_rows, 1), max(P, 1)), dtype=np.uint64)
+        _check(load().pk_query_pairs(self._h, out.ctypes.data, n_rows))
+        return out[:n_rows, :P]
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

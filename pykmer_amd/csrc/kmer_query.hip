@@ -36,6 +36,11 @@
 // between two tables, later rows go to HBM directly.  One count usually dominates a table, so equal counts are joined
 // before they reach a counter: a wave that lies in one row first sums the windows that hold the count of its first window
 // across the wave (one LDS atomic for all of them), and every thread joins equal consecutive counts of a row.
+// Shared windows (pk_query_set_pairs; all tables in one launch): the lookup also keeps, per thread and table, which of the
+// thread's 16 windows passed the count window -- one 16-bit plane per table, two planes to a register -- and after the
+// table loop tallies, per row and pair of tables i < j,  shared[row][p] = #{ j : V_i(j) and V_j(j) }  as popcount(v_i & v_j):
+// the merger's and + bit count (gram_occ.hip) over windows instead of addresses.  The levels are those of hits: a wave in
+// one row sums across the wave, a thread masks its planes by row segment, a slot's first QPAIR_ROWS rows meet in LDS.
 // Every kernel returns at once, writing nothing, when it finds flags[0] raised (the squeeze backed out: the slots still
 // hold an earlier text); the host grows the record and accumulator arrays and repeats the feed's squeeze and these kernels.
 #include <type_traits>
@@ -50,6 +55,8 @@ constexpr int QNT = 1024;                 // threads per slot, 16 bases each
 constexpr uint32_t QACC_RECS = 128;       // rows (records or bins) of a slot tallied in LDS; later ones (reads below ~128 bytes of
                                           // text, bins of fewer than 128 windows) go to HBM directly
 constexpr uint32_t QSPEC_ROWS = 32;       // rows of a slot whose count spectrum of one table is tallied in LDS (256 u32 each)
+constexpr uint32_t QPAIR_ROWS = 64;       // rows of a slot whose shared windows are tallied in LDS (one u32 per pair of tables)
+constexpr uint32_t QPAIR_MAX = QUERY_MAX_TABLES * (QUERY_MAX_TABLES - 1u) / 2u;   // pairs of one launch
 
 // What thread t of a slot works on: its 16 bases, the 16 before them, and which of its bases end a valid window.
 struct QLane { uint32_t cur, prev, ok; };
@@ -154,7 +161,9 @@ __device__ __forceinline__ unsigned long long q_find(const unsigned long long *_
 
 // BINS: the accumulators' rows are bins of W windows (Bf, W); otherwise records, and Bf and W are not read.
 // SPEC: also spectrum[row][table][256], the tally of every valid window's table count; otherwise `spectrum` is not touched.
-template <typename KT, bool BINS, bool SPEC>
+// PAIRS (never with SPEC, whose table loop has barriers; t0 = 0 and n_tab = N): also shared[row][pair], the windows valid in
+// both tables of every pair i < j < N, pairs in row-major order; otherwise `shared` is not touched.
+template <typename KT, bool BINS, bool SPEC, bool PAIRS>
 __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ restarts,
                                                       const uint32_t *__restrict__ n_bases, const L2 *__restrict__ chunk_l2_state, uint32_t k,
                                                       const unsigned long long *__restrict__ slot_first, const unsigned long long *__restrict__ P,
@@ -162,10 +171,12 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
                                                       const Carry *__restrict__ carry, QueryTables tabs, uint32_t n_tab, uint32_t N, uint32_t t0,
                                                       uint32_t min_count, uint32_t max_count, unsigned long long *__restrict__ hits,
                                                       unsigned long long *__restrict__ depth, unsigned long long *__restrict__ spectrum,
-                                                      const uint32_t *__restrict__ flags) {
+                                                      unsigned long long *__restrict__ shared, const uint32_t *__restrict__ flags) {
+    static_assert(!(SPEC && PAIRS), "the spectrum's table loop has barriers; pairs are tallied without");
     __shared__ uint32_t wsum[QNT / 64];
     __shared__ uint32_t acc_h[QACC_RECS * QUERY_MAX_TABLES], acc_d[QACC_RECS * QUERY_MAX_TABLES];
     __shared__ uint32_t acc_s[SPEC ? QSPEC_ROWS * 256u : 1u];   // one table at a time; a slot has at most 16384 windows
+    __shared__ uint32_t acc_p[PAIRS ? QPAIR_ROWS * QPAIR_MAX : 1u];   // [row][pair]; a slot has at most 16384 windows
     __shared__ unsigned long long rec_range[BINS ? 6 : 2];   // BINS: + the slot's first and last row, P and Bf of its first record
     if (flags[0]) return;
     const uint32_t c = blockIdx.x, lane = threadIdx.x & 63u;
@@ -193,6 +204,9 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
     for (uint32_t i = threadIdx.x; i < QACC_RECS * n_tab; i += QNT) { acc_h[i] = 0u; acc_d[i] = 0u; }
     if constexpr (SPEC)
         for (uint32_t i = threadIdx.x; i < QSPEC_ROWS * 256u; i += QNT) acc_s[i] = 0u;
+    const uint32_t n_pairs = PAIRS ? n_tab * (n_tab - 1u) / 2u : 0u;
+    if constexpr (PAIRS)
+        for (uint32_t i = threadIdx.x; i < QPAIR_ROWS * n_pairs; i += QNT) acc_p[i] = 0u;
     __syncthreads();
     const unsigned long long r_lo = rec_range[0], r_hi = rec_range[1];
     // the accumulators' rows this slot touches: records, or bins
@@ -280,6 +294,13 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
         if (rel < QSPEC_ROWS) atomicAdd(&acc_s[rel * 256u + cnt], n);
         else atomicAdd(&spectrum[((row_lo + rel) * N + t0 + tt) * 256ull + cnt], (unsigned long long)n);
     };
+    // PAIRS: the planes of this thread, table 2i in the low half of pl[i] and table 2i + 1 in the high half; bit j of a
+    // plane: window j is valid and its count lies in the count window
+    uint32_t pl[PAIRS ? QUERY_MAX_TABLES / 2u : 1u];
+    if constexpr (PAIRS) {
+#pragma unroll
+        for (uint32_t i = 0; i < QUERY_MAX_TABLES / 2u; i++) pl[i] = 0u;
+    }
     // one table for this thread's windows; wave-uniform where it matters, no barrier inside
     auto tally = [&](uint32_t tt, const uint32_t ref, const bool wave_one) {
         const uint8_t *__restrict__ T = tabs.t[tt];
@@ -307,6 +328,14 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
             }
             add(cur, tt, h, d);
         }
+        if constexpr (PAIRS) {
+            uint32_t bits = 0u;
+#pragma unroll
+            for (int j = 0; j < 16; j++) bits |= (cv[j] >= min_count && cv[j] <= max_count) ? 1u << j : 0u;
+            bits <<= 16u * (tt & 1u);
+#pragma unroll
+            for (uint32_t i = 0; i < QUERY_MAX_TABLES / 2u; i++) pl[i] |= (i == (tt >> 1)) ? bits : 0u;   // (tt is uniform: selects, no indexed register)
+        }
         if constexpr (SPEC) {
             // peel: the count of the wave's first window, summed over the wave (the dominant count, more often than not);
             // 256 is no count and peels nothing
@@ -333,6 +362,57 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
             if (n) add_spec(cur_r, tt, cur_c, n);
         }
     };
+    // PAIRS, after the table loop: the pairs of this thread's planes.  The loops over the tables are unrolled over all
+    // QUERY_MAX_TABLES and cut short by the uniform n_tab, so that every plane is a fixed half of a fixed register.
+    auto plane = [&](uint32_t t) { return (pl[t >> 1] >> (16u * (t & 1u))) & 0xffffu; };
+    auto add_pair = [&](uint32_t rel, uint32_t p, uint32_t n) {
+        if (rel < QPAIR_ROWS) atomicAdd(&acc_p[rel * n_pairs + p], n);
+        else atomicAdd(&shared[(row_lo + rel) * n_pairs + p], (unsigned long long)n);
+    };
+    auto tally_pairs = [&](const uint32_t ref, const bool wave_one) {
+        if (wave_one) {                                      // one add per pair and wave
+#pragma unroll
+            for (uint32_t i = 0; i + 1u < QUERY_MAX_TABLES; i++) {
+                if (i + 1u < n_tab) {
+                    const uint32_t vi = plane(i), p0 = i * (2u * n_tab - i - 1u) / 2u;
+#pragma unroll
+                    for (uint32_t j = i + 1u; j < QUERY_MAX_TABLES; j++) {
+                        if (j < n_tab) {
+                            uint32_t n = (uint32_t)__builtin_popcount(vi & plane(j));
+                            for (int s = 32; s; s >>= 1) n += __shfl_down(n, s, 64);
+                            if (lane == 0u && n) add_pair(ref, p0 + j - i - 1u, n);
+                        }
+                    }
+                }
+            }
+        } else if (has) {
+            // row segment after row segment: `m`, the windows of the first row among those left
+            uint32_t rest = q.ok;
+            while (rest) {
+                const uint32_t j0 = (uint32_t)__builtin_ctz(rest);
+                uint32_t row = 0u, m = 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 16u; j++) row = j == j0 ? rr[j] : row;
+#pragma unroll
+                for (uint32_t j = 0; j < 16u; j++) m |= rr[j] == row ? 1u << j : 0u;
+                m &= rest;
+                rest &= ~m;
+#pragma unroll
+                for (uint32_t i = 0; i + 1u < QUERY_MAX_TABLES; i++) {
+                    const uint32_t vi = plane(i) & m, p0 = i * (2u * n_tab - i - 1u) / 2u;
+                    if (i + 1u < n_tab && vi) {
+#pragma unroll
+                        for (uint32_t j = i + 1u; j < QUERY_MAX_TABLES; j++) {
+                            if (j < n_tab) {
+                                const uint32_t n = (uint32_t)__builtin_popcount(vi & plane(j));
+                                if (n) add_pair(row, p0 + j - i - 1u, n);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    };
     if constexpr (SPEC) {
         const unsigned long long span = row_hi - row_lo + 1ull;
         const uint32_t n_spec = (uint32_t)(span < QSPEC_ROWS ? span : QSPEC_ROWS) * 256u;
@@ -354,8 +434,17 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
         const uint32_t ref = wave_ref();
         const bool wave_one = wave_in(ref);
         for (uint32_t tt = 0; tt < n_tab; tt++) tally(tt, ref, wave_one);
+        if constexpr (PAIRS) tally_pairs(ref, wave_one);
     }
     __syncthreads();
+    if constexpr (PAIRS) {
+        const unsigned long long span = row_hi - row_lo + 1ull;
+        const uint32_t n_acc = (uint32_t)(span < QPAIR_ROWS ? span : QPAIR_ROWS) * n_pairs;
+        for (uint32_t i = threadIdx.x; i < n_acc; i += QNT) {
+            const uint32_t v = acc_p[i];
+            if (v) atomicAdd(&shared[row_lo * n_pairs + i], (unsigned long long)v);
+        }
+    }
     {
         const unsigned long long span = row_hi - row_lo + 1ull;
         const uint32_t n_acc = (uint32_t)(span < QACC_RECS ? span : QACC_RECS) * n_tab;
@@ -403,16 +492,17 @@ void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuff
 
 void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
-                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, hipStream_t s) {
+                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, unsigned long long *shared, hipStream_t s) {
     QueryTables tabs;
     for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
-#define PK_QUERY_LOOKUP(KT, BINS, SPEC) hipLaunchKernelGGL((k_query_lookup<KT, BINS, SPEC>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
+#define PK_QUERY_LOOKUP(KT, BINS, SPEC, PAIRS) hipLaunchKernelGGL((k_query_lookup<KT, BINS, SPEC, PAIRS>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
                                                      (const uint32_t *)b.restarts, (const uint32_t *)b.n_bases, st2, pl.k,                                  \
                                                      (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, carry, tabs, n_tab, \
-                                                     N, t0, min_count, max_count, hits, depth, spectrum, (const uint32_t *)b.flags)
-#define PK_QUERY_LOOKUP_K(BINS, SPEC) do { if (pl.k <= 15) PK_QUERY_LOOKUP(uint32_t, BINS, SPEC); else PK_QUERY_LOOKUP(uint64_t, BINS, SPEC); } while (0)
-    if (spectrum) { if (bin_windows) PK_QUERY_LOOKUP_K(true, true); else PK_QUERY_LOOKUP_K(false, true); }
-    else { if (bin_windows) PK_QUERY_LOOKUP_K(true, false); else PK_QUERY_LOOKUP_K(false, false); }
+                                                     N, t0, min_count, max_count, hits, depth, spectrum, shared, (const uint32_t *)b.flags)
+#define PK_QUERY_LOOKUP_K(BINS, SPEC, PAIRS) do { if (pl.k <= 15) PK_QUERY_LOOKUP(uint32_t, BINS, SPEC, PAIRS); else PK_QUERY_LOOKUP(uint64_t, BINS, SPEC, PAIRS); } while (0)
+    if (spectrum) { if (bin_windows) PK_QUERY_LOOKUP_K(true, true, false); else PK_QUERY_LOOKUP_K(false, true, false); }
+    else if (shared) { if (bin_windows) PK_QUERY_LOOKUP_K(true, false, true); else PK_QUERY_LOOKUP_K(false, false, true); }
+    else { if (bin_windows) PK_QUERY_LOOKUP_K(true, false, false); else PK_QUERY_LOOKUP_K(false, false, false); }
 #undef PK_QUERY_LOOKUP_K
 #undef PK_QUERY_LOOKUP
 }

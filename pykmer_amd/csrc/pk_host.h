@@ -126,16 +126,22 @@ struct QueryState {
     // row, sized, grown and zeroed with hits (ensure_spectrum); 2 KiB per row and table
     bool spectrum = false;
     DevBuf<unsigned long long> spec;
+    // shared windows (pk_query_set_pairs; at most QUERY_MAX_TABLES tables): [row][pair], the windows of a row valid in both
+    // tables of a pair i < j, sized, grown and zeroed with hits (ensure_pairs); one table has no pair and no array
+    bool pairs = false;
+    DevBuf<unsigned long long> shared;
     hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // the kernels of kmer_query.hip
     hipEvent_t coords_begin = nullptr, coords_end = nullptr;       // the kernels of kmer_coords.hip
     double t_coords = 0;
 
     ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end}) if (e) hipEventDestroy(e); }
     int create();                                                  // the events, and P for the record array's first capacity
-    int reset(hipStream_t s);                                      // an empty stream; the tables stay, bins, coordinates and spectra are off
+    int reset(hipStream_t s);                                      // an empty stream; the tables stay; bins, coordinates, spectra and pairs are off
     int grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s);   // the record array now holds `cap` records; the rows follow
     int ensure_rows(uint64_t cap, uint64_t bytes, hipStream_t s);  // binned: the rows `cap` records in `bytes` bytes can make
     int ensure_spectrum(uint64_t cap, uint64_t bytes, hipStream_t s);   // spectra: the same rows, per record or binned
+    int ensure_pairs(uint64_t cap, uint64_t bytes, hipStream_t s);      // shared windows: the same rows, per record or binned
+    size_t n_pairs() const { return tables.size() * (tables.size() - 1) / 2; }
 };
 
 int create_indexer(pk_indexer **out, int k, int device, int slice_index, int n_slices, bool query);   // pk_indexer.hip

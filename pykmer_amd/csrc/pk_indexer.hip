@@ -335,6 +335,7 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     const uint32_t N = (uint32_t)q.tables.size();
     if ((rc = q.ensure_rows(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
     if ((rc = q.ensure_spectrum(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
+    if ((rc = q.ensure_pairs(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
     if (q.coords && (rc = q.cpos.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
     auto queue = [&](uint32_t raised) -> int {
         if (raised && raised != 2u) return fail(PK_ERR_HIP, "the query feed did not settle (internal error, flag %u)", raised);
@@ -342,7 +343,8 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         launch_query_scan(pl, pb, qb, ix->c_l2s.p, q.windows, ix->recs.p, carry, q.p_done, q.P.p, q.Bf.p, q.bin, ix->stream);
         for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
             launch_query_lookup(pl, pb, qb, ix->c_l2s.p, q.P.p, q.Bf.p, q.bin, carry, q.tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
-                                (uint32_t)q.min, (uint32_t)q.max, q.hits.p, q.depth.p, q.spectrum ? q.spec.p : nullptr, ix->stream);
+                                (uint32_t)q.min, (uint32_t)q.max, q.hits.p, q.depth.p, q.spectrum ? q.spec.p : nullptr, q.pairs ? q.shared.p : nullptr,
+                                ix->stream);
         HIPCHK(hipEventRecord(q.lookup_end, ix->stream));
         if (q.coords) {
             // behind launch_query_scan (slot_first, P, Bf) and on the rows ensure_rows sized; a repeated attempt starts

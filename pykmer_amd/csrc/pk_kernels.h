@@ -131,9 +131,11 @@ void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuff
 // tables[0 .. n_tab) are columns t0 .. t0 + n_tab of the row-major [row][N] u64 accumulators hits / depth; a row is a record
 // (bin_windows = 0) or a bin of bin_windows valid windows: row Bf[r] + (o - P[r]) / W for the window of ordinal o in record r.
 // spectrum: null, or the [row][N][256] u64 tally of the table counts of every valid window (the same rows), added to
+// shared: null, or (without spectrum; t0 = 0 and n_tab = N) the [row][N (N - 1) / 2] u64 tally of the windows valid in both
+// tables of a pair i < j, pairs in row-major order (the same rows), added to
 void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
-                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, hipStream_t s);
+                         unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, unsigned long long *shared, hipStream_t s);
 
 // kmer_coords.hip -- base coordinates of a binned query's rows (DESIGN.md 4.10 "Coordinates"), behind launch_query_scan of the
 // same feed (slot_first, P, Bf) and its squeeze (recs[].n_valid).  chunk_pos: n_chunks words of scratch.  pos_in: the position

@@ -11,11 +11,12 @@ int QueryState::create() {
 }
 
 int QueryState::reset(hipStream_t s) {
-    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos, &spec})
+    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos, &spec, &shared})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, s));
     windows = p_done = 0;
     bin = n_bins = 0;
     spectrum = false;
+    pairs = false;
     coords = false; pos_in = 0; t_coords = 0;
     return PK_OK;
 }
@@ -33,7 +34,29 @@ int QueryState::grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s) {
         if ((rc = hits.grow_keep(cap * row, s))) return rc;
         if ((rc = depth.grow_keep(cap * row, s))) return rc;
     }
-    return ensure_spectrum(cap, bytes, s);
+    if ((rc = ensure_spectrum(cap, bytes, s))) return rc;
+    return ensure_pairs(cap, bytes, s);
+}
+
+// Shared windows: one u64 per pair of tables for every row hits and depth have (per record: `cap` rows; binned: those of
+// ensure_rows), contents kept, the rest zero.  Binned they grow by half at least, as the rows of hits do.  An array that does
+// not fit is an error that names its size and what makes it smaller.
+int QueryState::ensure_pairs(uint64_t cap, uint64_t bytes, hipStream_t s) {
+    if (!pairs || n_pairs() == 0) return PK_OK;
+    const uint64_t rows = bin ? bytes / bin + cap + 1 : cap;
+    const size_t N = tables.size(), per_row = n_pairs() * sizeof(unsigned long long);
+    const char *helps = "take fewer tables per run, larger bins or a smaller query";
+    if (rows > SIZE_MAX / 2 / per_row)
+        return fail(PK_ERR_ARG, "shared windows of %llu rows and %zu pairs of tables are beyond the address space; %s", (unsigned long long)rows,
+                    n_pairs(), helps);
+    if (rows * per_row <= shared.bytes) return PK_OK;
+    const size_t want = bin ? std::max<size_t>(rows * per_row, shared.bytes + shared.bytes / 2) : rows * per_row;
+    const int rc = shared.grow_keep(want, s);
+    if (!rc) return PK_OK;
+    (void)hipGetLastError();
+    const std::string why = g_err;
+    return fail(rc, "shared windows need an accumulator of %zu bytes (%llu rows, %zu tables, %zu pairs of 8 bytes each); %s: %s", want,
+                (unsigned long long)rows, N, n_pairs(), helps, why.c_str());
 }
 
 // Count spectra: 256 u64 per table for every row hits and depth have (per record: `cap` rows; binned: those of ensure_rows),
@@ -106,6 +129,7 @@ static bool binned(const QueryState &q) { return q.bin != 0; }
 static bool per_record(const QueryState &q) { return q.bin == 0; }
 static bool with_coords(const QueryState &q) { return q.coords; }
 static bool with_spectrum(const QueryState &q) { return q.spectrum; }
+static bool with_pairs(const QueryState &q) { return q.pairs; }
 
 extern "C" int pk_query_create(pk_indexer **out, int k, int device) {
     if (k > 17) return fail(PK_ERR_ARG, "a query takes kmer_len <= 17 (one unsliced table), got %d", k);
@@ -118,6 +142,8 @@ extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables
     if (min_count < 1 || max_count > 255 || min_count > max_count) return fail(PK_ERR_ARG, "count window must satisfy 1 <= min <= max <= 255, got %d-%d", min_count, max_count);
     for (int i = 0; i < N; i++)
         if (!dev_tables[i]) return fail(PK_ERR_ARG, "table %d is a null pointer", i);
+    if (ix->q->pairs && N > (int)QUERY_MAX_TABLES)
+        return fail(PK_ERR_ARG, "shared windows (pk_query_set_pairs) take at most %u tables, all in one lookup; got %d", QUERY_MAX_TABLES, N);
     HIPCHK(hipSetDevice(ix->device));
     QueryState &q = *ix->q;
     q.tables.assign((const uint8_t *const *)dev_tables, (const uint8_t *const *)dev_tables + N);
@@ -129,7 +155,8 @@ extern "C" int pk_query_set_tables(pk_indexer *ix, const void *const *dev_tables
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, ix->stream));
     }
-    return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);   // (all zero before the first feed, whatever N was)
+    if (int rc = q.ensure_spectrum(ix->recs_cap(), 0, ix->stream)) return rc;   // (all zero before the first feed, whatever N was)
+    return q.ensure_pairs(ix->recs_cap(), 0, ix->stream);
 }
 
 extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
@@ -138,21 +165,39 @@ extern "C" int pk_query_set_bins(pk_indexer *ix, uint64_t bin_windows) {
     QueryState &q = *ix->q;
     q.bin = bin_windows;
     q.coords = false;                                        // pk_query_set_coords comes after the bins
-    if (!bin_windows) return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
-    // Bf beside P; a reset zeroed what was there, a new array is zeroed here
-    int rc = q.Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
-    if (rc || (rc = q.ensure_rows(ix->recs_cap(), 0, ix->stream))) return rc;
-    return q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
+    int rc = PK_OK;
+    if (bin_windows) {
+        // Bf beside P; a reset zeroed what was there, a new array is zeroed here
+        rc = q.Bf.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream);
+        if (rc || (rc = q.ensure_rows(ix->recs_cap(), 0, ix->stream))) return rc;
+    }
+    if ((rc = q.ensure_spectrum(ix->recs_cap(), 0, ix->stream))) return rc;
+    return q.ensure_pairs(ix->recs_cap(), 0, ix->stream);
 }
 
 extern "C" int pk_query_set_spectrum(pk_indexer *ix, int on) {
     if (int rc = query_check(ix, has_tables, "pk_query_set_tables comes before pk_query_set_spectrum", "the spectra are set before the first feed (reset the indexer first)")) return rc;
     HIPCHK(hipSetDevice(ix->device));
     QueryState &q = *ix->q;
+    if (on && q.pairs) return fail(PK_ERR_ARG, "count spectra and shared windows (pk_query_set_pairs) are tallied in separate streams");
     q.spectrum = on != 0;
     // a reset zeroed what was there, a new array is zeroed here; per record or for the bins set so far
     const int rc = q.ensure_spectrum(ix->recs_cap(), 0, ix->stream);
     if (rc) q.spectrum = false;                              // an array that did not fit: the setting did not take
+    return rc;
+}
+
+extern "C" int pk_query_set_pairs(pk_indexer *ix, int on) {
+    if (int rc = query_check(ix, has_tables, "pk_query_set_tables comes before pk_query_set_pairs", "the pairs are set before the first feed (reset the indexer first)")) return rc;
+    QueryState &q = *ix->q;
+    if (on && q.tables.size() > QUERY_MAX_TABLES)
+        return fail(PK_ERR_ARG, "shared windows take at most %u tables, all in one lookup; the indexer has %zu", QUERY_MAX_TABLES, q.tables.size());
+    if (on && q.spectrum) return fail(PK_ERR_ARG, "shared windows and count spectra (pk_query_set_spectrum) are tallied in separate streams");
+    HIPCHK(hipSetDevice(ix->device));
+    q.pairs = on != 0;
+    // a reset zeroed what was there, a new array is zeroed here; per record or for the bins set so far
+    const int rc = q.ensure_pairs(ix->recs_cap(), 0, ix->stream);
+    if (rc) q.pairs = false;                                 // an array that did not fit: the setting did not take
     return rc;
 }
 
@@ -241,5 +286,17 @@ extern "C" int pk_query_spectrum(pk_indexer *ix, uint64_t *out, uint64_t rows_ca
     if (!out) return fail(PK_ERR_ARG, "null output pointer");
     HIPCHK(hipSetDevice(ix->device));
     HIPCHK(hipMemcpy(out, q.spec.p, rows * q.tables.size() * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_pairs(pk_indexer *ix, uint64_t *out, uint64_t rows_cap) {
+    if (int rc = query_check(ix, with_pairs, "the indexer keeps no shared windows (pk_query_set_pairs)", nullptr)) return rc;
+    const QueryState &q = *ix->q;
+    const uint64_t rows = q.bin ? q.n_bins : ix->n_recs;
+    if (rows > rows_cap) return fail(PK_ERR_RECS_CAP, "%llu rows, capacity %llu", (unsigned long long)rows, (unsigned long long)rows_cap);
+    if (rows == 0 || q.n_pairs() == 0) return PK_OK;
+    if (!out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipMemcpy(out, q.shared.p, rows * q.n_pairs() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PK_OK;
 }

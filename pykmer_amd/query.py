@@ -22,6 +22,11 @@ With `spectrum` the same lookup also tallies, per row (record, or bin) and table
 count (pk_query_set_spectrum): spectrum[row][t][c], c = 0 .. 255, zeros (absent k-mers) included and independent of the
 count window.  Hits and depth of any window, the median and every quantile of a row's k-mer counts follow from it
 (pykmer_amd.qspectrum re-windows a written `.kmh` without tables or a GPU).
+
+With `pairs` the same lookup also tallies, per row and pair of tables i < j, the valid windows that lie in the count window
+of both (pk_query_set_pairs): shared[row][p], p the index of (i, j) in spectrum.pair_list(N).  With hits as the diagonal a
+row is a `.kma`-shaped matrix of its own: local Jaccard distances and trees along a record (pykmer_amd.qpairs).  A pair
+needs both tables in one lookup: at most 16 tables, staged as one group.
 """
 import argparse
 import os
@@ -35,9 +40,11 @@ from . import _lib, staging
 from .header import Header
 from .indexer import _Input, _mark, qual_threshold
 from .merger import DEFAULT_THREADS
+from .spectrum import pair_list
 from .output import atomic_write, write_json
 from .tables import EXTS, MAX_KMER_LEN, common_kmer_len, lean_headers, name_of as _name_of, table_entry   # noqa: F401
 
+MAX_PAIR_TABLES = 16                # pk_query_set_pairs: the tables of a pair meet in one lookup launch (QUERY_MAX_TABLES)
 WORKSPACE_RESERVE = 4 << 30         # of the free HBM, kept for the feed's workspace when the budget is taken from mem_info
 
 
@@ -126,12 +133,13 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
 
 
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
-              bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0, spectrum: bool = False) -> dict:
+              bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0, spectrum: bool = False, pairs: bool = False) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
     same query only add columns).  `bin_windows`: tally per bin (bin_hits, bin_depth, bin_first); the per-record arrays
     are then the sums of each record's rows.  `coords`: also bin_start, bin_end -- on the `first` stream only, they do
     not depend on the tables.  `min_qual_byte`: a FASTQ query's bases below this quality byte count as N (qual_threshold).
-    `spectrum`: also the count spectra, `spectrum` (R, N, 256) and, binned, `bin_spectrum` (B, N, 256)."""
+    `spectrum`: also the count spectra, `spectrum` (R, N, 256) and, binned, `bin_spectrum` (B, N, 256).
+    `pairs`: also the shared windows of every pair of tables, `shared` (R, P) and, binned, `bin_shared` (B, P)."""
     coords = bool(coords) and first
     src = _Input(query_file, keep=first, quiet=not first)
     binned = {}
@@ -143,6 +151,8 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
                 q.set_coords(True)
         if spectrum:
             q.set_spectrum(True)
+        if pairs:
+            q.set_pairs(True)
         for piece in src.pieces():
             q.feed(piece)
         fin = q.finish()
@@ -157,10 +167,15 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
             if spectrum:
                 binned["bin_spectrum"] = q.spectrum(int(bin_first[-1]))
                 binned["spectrum"] = spectrum_record_sums(binned["bin_spectrum"], bin_first)
+            if pairs:
+                binned["bin_shared"] = q.pairs(int(bin_first[-1])).copy()
+                binned["shared"] = record_sums(binned["bin_shared"], bin_first)
         else:
             hits, depth = q.results(fin["n_records"])
             if spectrum:
                 binned["spectrum"] = q.spectrum(fin["n_records"])
+            if pairs:
+                binned["shared"] = q.pairs(fin["n_records"]).copy()
         timings = q.timings()
         masked = {"masked": q.fastq_masked()} if min_qual_byte else {}
     out = {"seq_len": recs["seq_len"].astype(np.uint64), "n_valid": recs["n_valid_kmers"].astype(np.uint64), "hits": hits.copy(),
@@ -172,7 +187,7 @@ def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
 
 def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
                   threads: int = DEFAULT_THREADS, stage=None, run=None, bin_windows: int = None, coords: bool = False, min_qual: int = 0, qual_offset: int = 33,
-                  spectrum: bool = False) -> dict:
+                  spectrum: bool = False, pairs: bool = False) -> dict:
     """Per-record hits of `query_file` (FASTA or FASTQ by its name; plain, gzip or BGZF) against `tables`: Headers,
     merger.ResidentTables or `.kin[.bgz]` paths.  Returns dict(names, seq_len (R,), n_valid (R,), hits (R, N), depth (R, N),
     kmer_len, ...), all integer arrays uint64, rows in file order, columns in the order of `tables`.
@@ -197,7 +212,16 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     `spectrum` = True adds `spectrum` (R, N, 256) uint64, spectrum[r][t][c] = the valid windows of record r whose count in
     table t is c (0 = absent; the count window plays no part), and `median` (R, N) uint8, the lower median of those counts
     (qspectrum.median_from_spectrum).  With `bin_windows` also `bin_spectrum` (B, N, 256) and `bin_median` (B, N), and
-    `spectrum` is the sum over each record's rows.  `run` receives spectrum=True by keyword, and only when it is set."""
+    `spectrum` is the sum over each record's rows.  `run` receives spectrum=True by keyword, and only when it is set.
+
+    `pairs` = True adds `shared` (R, P) uint64, P = N (N - 1) / 2, shared[r][p] = the valid windows of record r whose count
+    lies in the count window in both tables of pair p, and `pairs` (P, 2) int32, the tables (i, j), i < j, of every p in
+    row-major order (spectrum.pair_list).  With `bin_windows` also `bin_shared` (B, P), and `shared` is the sum over each
+    record's rows.  The tables of a pair meet in one lookup: ValueError for more than 16 tables, for tables that do not fit
+    the budget as one group, and together with `spectrum`.  `run` receives pairs=True by keyword, and only when it is set."""
+    if pairs and spectrum:
+        raise ValueError("pairs and spectrum are tallied in separate runs (the spectrum takes the tables one after the other): "
+                         "--pairs and --spectrum do not go together")
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
@@ -207,16 +231,23 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         extra["coords"] = True
     if spectrum:
         extra["spectrum"] = True
+    if pairs:
+        extra["pairs"] = True
     if min_qual:
         extra["min_qual_byte"] = qual_threshold(str(query_file), min_qual, qual_offset)
     tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
     kmer_len = validate(tables, min_count, max_count)
+    if pairs and len(tables) > MAX_PAIR_TABLES:
+        raise ValueError(f"pairs take at most {MAX_PAIR_TABLES} tables, all in one lookup; got {len(tables)}")
     stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
     run = run or run_query
     if all(hasattr(t, "device_slice") for t in tables):
         groups = [(0, len(tables))]                          # resident already: nothing to fit
     else:
         groups = table_groups(len(tables), 4 ** kmer_len, staging.hbm_budget(device, hbm_budget, workspace=WORKSPACE_RESERVE))
+    if pairs and len(groups) > 1:
+        raise ValueError(f"pairs need all {len(tables)} tables of {4 ** kmer_len:,d} bytes staged together, and the HBM budget holds "
+                         f"{groups[0][1]} at a time: take fewer tables or a larger budget (PK_MERGE_HBM_BUDGET)")
     result, lookup_s, coords_s = None, 0.0, 0.0
     for g, (lo, hi) in enumerate(groups):
         staged = stage(tables[lo:hi], device)
@@ -251,6 +282,9 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         result["median"] = median_from_spectrum(result["spectrum"])
         if bin_windows is not None:
             result["bin_median"] = median_from_spectrum(result["bin_spectrum"])
+    if pairs:
+        result["pairs"] = pair_list(len(tables))
+        assert result["shared"].shape == (len(result["n_valid"]), len(result["pairs"]))
     if coords:
         assert result["bin_start"].shape == result["bin_end"].shape == (int(result["bin_first"][-1]),)
         result["coords_s"] = coords_s
@@ -384,13 +418,76 @@ def write_kmh(project_name: str, result: dict, query_file: str, data: list, colu
         np.savez_compressed(fhd, spectrum=spec, median=median, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]), **arrays)
 
 
+def kmp_paths(project_name: str) -> Tuple[Path, Path, Path]:
+    return Path(f"{project_name}.kmp"), Path(f"{project_name}.kmp.json"), Path(f"{project_name}.kmp.tsv")
+
+
+def write_kmp(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
+    """`<project>.kmp` (np.savez_compressed), `.kmp.json` and `.kmp.tsv`: the shared windows of a result with `pairs`, each
+    file through `.tmp` + rename.  The rows are the records; those of a binned result (bin_shared) are its bins, and the
+    files then hold what the `.kmb` files hold besides (bin_first, bin_windows, n_bins; with coordinates bin_start, bin_end,
+    "coords", the columns start and end).  The `.kmp` holds the rows' hits next to `shared`: a row's matrix needs no other
+    file (pykmer_amd.qpairs).  The json has the keys of the `.kmq.json` and n_pairs; the tsv has the leading columns of the
+    `.kmq.tsv` (binned: of the `.kmb.tsv`), then one column `<name_i>|<name_j>` per pair."""
+    kmp, meta, tsv = kmp_paths(project_name)
+    binned = "bin_shared" in result
+    shared = np.ascontiguousarray(result["bin_shared" if binned else "shared"], dtype=np.uint64)
+    hits = np.ascontiguousarray(result["bin_hits" if binned else "hits"], dtype=np.uint64)
+    pairs = np.ascontiguousarray(result["pairs"], dtype=np.int32).reshape(-1, 2)
+    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
+    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
+    names = [n.strip() for n in result["names"]]
+    assert n_valid.shape == seq_len.shape == (len(names),)
+    arrays, more, coords = {}, {}, {}
+    if binned:
+        W = int(result["bin_windows"])
+        bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
+        assert bin_first.shape == (len(names) + 1,)
+        rows = int(bin_first[-1])
+        arrays = {"bin_first": bin_first, "bin_windows": np.uint64(W)}
+        more = {"bin_windows": W, "n_bins": rows}
+        if "bin_start" in result:
+            coords = {"bin_start": np.ascontiguousarray(result["bin_start"], dtype=np.uint64),
+                      "bin_end": np.ascontiguousarray(result["bin_end"], dtype=np.uint64)}
+            assert coords["bin_start"].shape == coords["bin_end"].shape == (rows,)
+            more["coords"] = True
+    else:
+        rows = len(names)
+    N = len(columns)
+    assert hits.shape == (rows, N) and pairs.shape == (N * (N - 1) // 2, 2) and shared.shape == (rows, len(pairs))
+    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
+              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data, "n_pairs": len(pairs), **more}
+    output.update(_qual_keys(result))
+    write_json(meta, output)
+    heads = [f"{columns[i]}|{columns[j]}" for i, j in pairs]
+    with atomic_write(tsv, "wt") as fhd:
+        lead = ["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) if binned else ["record", "seq_len", "n_valid"]
+        fhd.write("\t".join(lead + heads) + "\n")
+        for r, name in enumerate(names):
+            if binned:
+                m = int(n_valid[r])
+                for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
+                    at = int(bin_first[r]) + b
+                    span = [str(int(coords["bin_start"][at])), str(int(coords["bin_end"][at]))] if coords else []
+                    fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + span + [str(int(v)) for v in shared[at]]) + "\n")
+            else:
+                fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in shared[r]]) + "\n")
+    with atomic_write(kmp, "wb") as fhd:
+        np.savez_compressed(fhd, shared=shared, hits=hits, pairs=pairs, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
+                            min_count=np.int64(result["min_count"]), max_count=np.int64(result["max_count"]), **arrays, **coords)
+
+
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
           threads: int = DEFAULT_THREADS, hbm_budget: int = None, bin_windows: int = None, coords: bool = False, min_qual: int = None,
-          qual_offset: int = None, spectrum: bool = False) -> dict:
+          qual_offset: int = None, spectrum: bool = False, pairs: bool = False) -> dict:
     """The CLI's work: validate, query, write the three files (six with `bin_windows`); returns query_records' result.
     `coords` (with `bin_windows`) adds the rows' base coordinates to the `.kmb` files.  `min_qual` / `qual_offset`
     (--min-qual, --qual-offset; None: not given) mask a FASTQ query's low-quality bases and are recorded in the json files.
-    `spectrum` (--spectrum) also writes the three `.kmh` files: the count spectra of the rows (write_kmh)."""
+    `spectrum` (--spectrum) also writes the three `.kmh` files: the count spectra of the rows (write_kmh).
+    `pairs` (--pairs; not with `spectrum`, at most 16 tables in one staged group) also writes the three `.kmp` files: the
+    shared windows of every pair of tables per row (write_kmp)."""
+    if pairs and spectrum:
+        raise ValueError("--pairs and --spectrum do not go together (the spectrum takes the tables one after the other): run them separately")
     qual_threshold(str(query_file), min_qual, qual_offset)
     if bin_windows is not None:
         bin_windows = validate_bins(bin_windows)
@@ -403,13 +500,18 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         extra.update(min_qual=min_qual, qual_offset=33 if qual_offset is None else qual_offset)
     if spectrum:
         extra["spectrum"] = True
-    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()) + (kmh_paths(project_name) if spectrum else ()):
+    if pairs:
+        extra["pairs"] = True
+    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()) + (kmh_paths(project_name) if spectrum else ()) \
+            + (kmp_paths(project_name) if pairs else ()):
         if f.exists():
             raise ValueError(f"project output file ({f}) already exists. not overwriting.")
     if not os.path.exists(query_file):
         raise ValueError(f"query file does not exist: {query_file}")
     if len(indexes) < 1:
         raise ValueError("a query needs at least one table")
+    if pairs and len(indexes) > MAX_PAIR_TABLES:
+        raise ValueError(f"--pairs takes at most {MAX_PAIR_TABLES} tables, all in one lookup; got {len(indexes)}")
     data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
     headers = [v["header"] for v in data]
     validate(headers, min_count, max_count)
@@ -420,6 +522,8 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
     except _lib.PkError as exc:
         if spectrum and exc.code == _lib.PK_ERR_HIP and "count spectra need" in str(exc):
             raise ValueError(f"{exc}; the spectra of --spectrum do not fit the device") from exc
+        if pairs and exc.code == _lib.PK_ERR_HIP and "shared windows need" in str(exc):
+            raise ValueError(f"{exc}; the shared windows of --pairs do not fit the device") from exc
         if bin_windows is None or exc.code != _lib.PK_ERR_HIP or "bins of" not in str(exc):
             raise
         raise ValueError(f"{exc}; the rows of --bin {bin_windows} do not fit the device: use a larger --bin") from exc
@@ -430,6 +534,8 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         write_kmb(project_name, result, query_file, data, columns)
     if spectrum:
         write_kmh(project_name, result, query_file, data, columns)
+    if pairs:
+        write_kmp(project_name, result, query_file, data, columns)
     _mark("files renamed")
     return result
 
@@ -449,6 +555,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--spectrum", action="store_true",
                         help="Also write <P>.kmh[.json|.tsv]: per record (with --bin: per bin) and table the count spectrum of its "
                              "k-mers and their median count; python -m pykmer_amd.qspectrum re-windows it [off]")
+    parser.add_argument("--pairs", action="store_true",
+                        help="Also write <P>.kmp[.json|.tsv]: per record (with --bin: per bin) and pair of tables the k-mers found in "
+                             "both; at most 16 tables, not with --spectrum; python -m pykmer_amd.qpairs makes a row's .kma [off]")
     parser.add_argument("--min-qual", type=int, default=None, metavar="Q",
                         help="FASTQ query: bases with a quality below Q count as N [off]")
     parser.add_argument("--qual-offset", type=int, default=None, metavar="O", help="With --min-qual: the quality encoding, 33 or 64 [33]")
@@ -461,10 +570,12 @@ def main(argv: List[str] = None) -> None:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
                        device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows,
                        **({"coords": True} if args.coords else {}), **({"spectrum": True} if args.spectrum else {}),
+                       **({"pairs": True} if args.pairs else {}),
                        **({"min_qual": args.min_qual, "qual_offset": args.qual_offset} if args.min_qual is not None or args.qual_offset is not None else {}))
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)
     hits = result["hits"]
     print(f"{len(result['names'])} records, {int(result['n_valid'].sum()):,d} k-mers, {hits.shape[1]} tables, "
-          f"{result['n_groups']} table group(s)" + (f", {int(result['bin_first'][-1]):,d} bins" if args.bin_windows is not None else ""))
+          f"{result['n_groups']} table group(s)" + (f", {int(result['bin_first'][-1]):,d} bins" if args.bin_windows is not None else "")
+          + (f", {len(result['pairs'])} pairs" if args.pairs else ""))

@@ -20,6 +20,9 @@ HIP-event times of the structure pass, the squeeze and the lookup kernels (pk_in
                    with the option on includes the download of the spectra (skipped, and said so, above
                    PK_QUERY_BENCH_MAX_DOWNLOAD bytes [16 GiB]); a configuration whose spectra do not fit the device is
                    recorded with the library's refusal.  Writes profiles/query_spectrum_k15_n13.json.
+    --pairs        shared windows per pair of tables (pk_query_set_pairs, DESIGN.md 4.10 "Shared windows"): the matrix of
+                   --spectrum with that option off and on, against the 13 genome tables only; the wall clock of a run with the
+                   option on includes the download of the rows x 78 u64.  Writes profiles/query_pairs_k15_n13.json.
     --runs R       timed runs per shape [5]
     --no-trace     skip the rocprofv3 run
     PK_QUERY_BENCH_BP / PK_QUERY_BENCH_TABLE_BP scale the genome and the table genomes down for a rehearsal.
@@ -118,7 +121,7 @@ def run_shape(make, ptrs, runs: int, bin_windows: int = None, coords: bool = Fal
         text.free()
 
 
-def time_config(q, text, n_bytes: int, ptrs, runs: int, bin_windows, spectrum: bool, max_download: int) -> dict:
+def time_config(q, text, n_bytes: int, ptrs, runs: int, bin_windows, spectrum: bool, max_download: int, pairs: bool = False) -> dict:
     """1 warm-up + `runs` timed runs of one configuration on an indexer that other configurations have used before."""
     walls, lookups, rows, download = [], [], 0, None
     try:
@@ -129,6 +132,8 @@ def time_config(q, text, n_bytes: int, ptrs, runs: int, bin_windows, spectrum: b
                 q.set_bins(bin_windows)
             if spectrum:
                 q.set_spectrum(True)
+            if pairs:
+                q.set_pairs(True)
             t0 = time.perf_counter()
             q.feed_device(text.ptr, n_bytes)
             fin = q.finish()
@@ -147,21 +152,41 @@ def time_config(q, text, n_bytes: int, ptrs, runs: int, bin_windows, spectrum: b
                         assert (sums == sums[:, :1]).all() and int(sums[:, 0].sum()) == fin["num_kmers"], "spectra do not sum to the windows"
                         assert np.array_equal(spec[:, :, 1:].sum(axis=2, dtype=np.uint64), hits), "window 1-255 of the spectra is not the hits"
                     del spec
+            if pairs:
+                n_pairs = len(ptrs) * (len(ptrs) - 1) // 2
+                download = rows * n_pairs * 8 <= max_download
+                if download:
+                    shared = q.pairs(rows)
+                    if i == 0:                               # once per configuration: the bound of the definition
+                        at = 0
+                        for a in range(len(ptrs)):
+                            for b in range(a + 1, len(ptrs)):
+                                assert (shared[:, at] <= np.minimum(hits[:, a], hits[:, b])).all(), "a pair shares more than its tables hit"
+                                at += 1
+                        pair_sum = int(shared.sum(dtype=np.uint64))
+                    del shared
             if i:
                 walls.append(time.perf_counter() - t0)
                 lookups.append(float(q.timings()["lookup_s"]))
     except _lib.PkError as exc:
-        return {"bin_windows": bin_windows, "spectrum": spectrum, "refused": str(exc)}
+        return {"bin_windows": bin_windows, "spectrum": spectrum, "pairs": pairs, "refused": str(exc)}
+    if pairs:
+        return {"bin_windows": bin_windows, "pairs": True, "rows": rows, "pairs_bytes": rows * len(ptrs) * (len(ptrs) - 1) // 2 * 8,
+                "downloaded": download, "shared_sum": pair_sum if download else None, "lookup_s_runs": lookups,
+                "lookup_s_median": statistics.median(lookups), "lookup_s_min": min(lookups), "lookup_s_max": max(lookups), "wall_s_runs": walls,
+                "wall_s_median": statistics.median(walls)}
     return {"bin_windows": bin_windows, "spectrum": spectrum, "rows": rows, "spectrum_bytes": rows * len(ptrs) * 2048 if spectrum else 0,
             "downloaded": download, "lookup_s_runs": lookups, "lookup_s_median": statistics.median(lookups), "lookup_s_min": min(lookups),
             "lookup_s_max": max(lookups), "wall_s_runs": walls, "wall_s_median": statistics.median(walls)}
 
 
-def run_spectrum_matrix(genome_bp: int, table_bp: int, runs: int, bins, path: str) -> dict:
+def run_spectrum_matrix(genome_bp: int, table_bp: int, runs: int, bins, path: str, pairs: bool = False) -> dict:
+    """The option (count spectra; pairs: shared windows) off and on, per kind of table, shape and bin size."""
     max_download = int(os.environ.get("PK_QUERY_BENCH_MAX_DOWNLOAD", 16 << 30))
     out = {"k": K, "n_tables": N, "table_genome_bp": table_bp, "runs": runs,
-           "method": f"per configuration 1 warm-up + {runs} runs of reset/set_*/feed_device/finish/results[/spectrum]; lookup_s from HIP events "
-                     "(pk_indexer_timings), wall_s around the blocking calls, the download of the spectra included where `downloaded`",
+           "option": "pairs" if pairs else "spectrum",
+           "method": f"per configuration 1 warm-up + {runs} runs of reset/set_*/feed_device/finish/results[/spectrum|pairs]; lookup_s from HIP events "
+                     "(pk_indexer_timings), wall_s around the blocking calls, the download of the option's array included where `downloaded`",
            "on_over_off": "lookup_s_median with the option on over the one with it off, same bins, same tables, same build"}
     texts = {}
     for name, make in shapes(genome_bp):
@@ -170,7 +195,7 @@ def run_spectrum_matrix(genome_bp: int, table_bp: int, runs: int, bins, path: st
         buf.upload(np.asarray(fa))
         texts[name] = (buf, len(fa), int(bp))
         del fa
-    for kind in ("genome_tables", "zero_tables"):
+    for kind in ("genome_tables",) if pairs else ("genome_tables", "zero_tables"):
         bufs = stage_tables(table_bp, zero=kind == "zero_tables")
         ptrs = [b.ptr for b in bufs]
         out[kind] = {}
@@ -179,7 +204,7 @@ def run_spectrum_matrix(genome_bp: int, table_bp: int, runs: int, bins, path: st
             with _lib.QueryIndexer(K) as q:
                 for W in bins:
                     off = time_config(q, buf, n_bytes, ptrs, runs, W, False, max_download)
-                    on = time_config(q, buf, n_bytes, ptrs, runs, W, True, max_download)
+                    on = time_config(q, buf, n_bytes, ptrs, runs, W, not pairs, max_download, pairs=pairs)
                     if "refused" not in on and "refused" not in off:
                         on["on_over_off"] = on["lookup_s_median"] / off["lookup_s_median"]
                     res["configs"] += [off, on]
@@ -220,9 +245,10 @@ def main():
         sys.exit("error: --coords needs --bin W")
     genome_bp = int(os.environ.get("PK_QUERY_BENCH_BP", 800_000_000))
     table_bp = int(os.environ.get("PK_QUERY_BENCH_TABLE_BP", 40_000_000))
-    if "--spectrum" in sys.argv:
-        path = args[0] if args else os.path.join(ROOT, "profiles", "query_spectrum_k15_n13.json")
-        run_spectrum_matrix(genome_bp, table_bp, runs, [bin_windows] if bin_windows is not None else [None, 10_000, 100], path)
+    if "--spectrum" in sys.argv or "--pairs" in sys.argv:
+        pairs = "--pairs" in sys.argv
+        path = args[0] if args else os.path.join(ROOT, "profiles", "query_pairs_k15_n13.json" if pairs else "query_spectrum_k15_n13.json")
+        run_spectrum_matrix(genome_bp, table_bp, runs, [bin_windows] if bin_windows is not None else [None, 10_000, 100], path, pairs=pairs)
         return
     bufs = stage_tables(table_bp)
     ptrs = [b.ptr for b in bufs]
