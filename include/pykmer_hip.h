@@ -331,6 +331,38 @@ int pk_extract_table_device(const void *const *dev_tables, int n_present, int n_
                             int min_count, int max_count, int min_present, int max_absent, int op,
                             void *dev_table_out, void *dev_hist_accum, int device, double *kernel_seconds_out);
 
+/* ---- select: the bytes of a chosen subset of the records of a byte stream (no reference counterpart: the `bbduk` /
+ * `kat filter seq` step behind a query).  No parser runs: the stream is cut into records by offsets the caller has, for a FASTA
+ * or FASTQ file pk_record.name_off - 1 of every record and the length of the stream, so both formats are the same to it.
+ * pk_select_create touches no device; the first pk_select_set_records with records brings it up.
+ * pk_select_set_records: starts holds n_records + 1 non-decreasing stream offsets, counted from the first byte ever fed; record
+ * r is the bytes [starts[r], starts[r + 1]), and keep[r] != 0 keeps it.  Bytes below starts[0] and at or beyond starts[R]
+ * belong to no record and are never emitted; equal offsets make an empty record.  A decreasing list, or a null pointer with
+ * n_records > 0, is PK_ERR_ARG; n_records = 0 is legal (starts and keep may then be null) and every feed emits nothing.
+ * Before the first feed; after one it is PK_ERR_STATE, and so is a feed without records.  Both arrays are copied (to the
+ * device, and the offsets with a prefix sum of the kept bytes on the host): the caller may free them.
+ * pk_select_feed: the next n_bytes >= 0 of the stream, cut anywhere.  The feed that covers the stream offsets [a, a + n) writes
+ * to host_out exactly the bytes at the offsets o of that range whose record is kept, in order, and their number to *n_out: the
+ * outputs of the feeds, concatenated, are the kept records however the stream is cut.  out_cap >= n_bytes always suffices.
+ * If the feed keeps more than out_cap bytes the call returns PK_ERR_RECS_CAP, *n_out holds the number needed, nothing is
+ * written to the output and the stream does not move: the same feed may be sent again.  (The number follows from the
+ * offsets alone, so the refusal costs no device work.)
+ * pk_select_feed_device: the same with the text in device memory on the selector's device, 16-byte aligned as for
+ * pk_indexer_feed_device, and the output in device memory at any alignment, overlapping no input (PK_ERR_ARG otherwise).
+ * Both forms cut large feeds into pieces themselves.
+ * pk_select_finish: totals_out = { bytes fed, bytes kept, records kept }; a kept record counts, once, when
+ * starts[r] < min(bytes fed, starts[R]).  Feeds after it are PK_ERR_STATE.
+ * pk_select_timings: out = { seconds of the select kernels so far, measured with HIP events on the selector's stream (the
+ * copies of the host form are outside them), feeds (as a double) }. */
+typedef struct pk_select pk_select;
+int pk_select_create(pk_select **out, int device);
+int pk_select_set_records(pk_select *s, const uint64_t *starts, const uint8_t *keep, uint64_t n_records);
+int pk_select_feed(pk_select *s, const uint8_t *host_text, uint64_t n_bytes, uint8_t *host_out, uint64_t out_cap, uint64_t *n_out);
+int pk_select_feed_device(pk_select *s, const void *dev_text, uint64_t n_bytes, void *dev_out, uint64_t out_cap, uint64_t *n_out);
+int pk_select_finish(pk_select *s, uint64_t totals_out[3]);
+int pk_select_timings(pk_select *s, double out[2]);
+void pk_select_destroy(pk_select *s);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

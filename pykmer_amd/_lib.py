@@ -81,6 +81,13 @@ _SIGNATURES = {
     "pk_extract_table_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_double)]),
+    "pk_select_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    "pk_select_set_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_select_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
+    "pk_select_feed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
+    "pk_select_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_select_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_select_destroy": (None, [ctypes.c_void_p]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -385,6 +392,80 @@ class QueryIndexer(Indexer):
         out = np.zeros((max(n_rows, 1), max(P, 1)), dtype=np.uint64)
         _check(load().pk_query_pairs(self._h, out.ctypes.data, n_rows))
         return out[:n_rows, :P]
+
+
+class Selector:
+    """The bytes of a chosen subset of the records of a byte stream (pk_select_*): set_records once, then feed the stream in
+    consecutive pieces cut anywhere; every feed hands back the bytes of its piece that lie in kept records.  Creating one
+    touches no device; set_records with at least one record brings it up."""
+
+    def __init__(self, device: int = 0):
+        self._h = ctypes.c_void_p()
+        self.device = device
+        _check(load().pk_select_create(ctypes.byref(self._h), device))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            load().pk_select_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_records(self, starts, keep):
+        """pk_select_set_records: `starts` (R + 1,) non-decreasing stream offsets, `keep` (R,) flags (non-zero keeps record r,
+        the bytes [starts[r], starts[r + 1])).  Both are copied.  ValueError for a decreasing list or lengths that differ."""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if starts.ndim != 1 or keep.ndim != 1 or starts.size != keep.size + 1:
+            raise ValueError(f"{keep.size} records need {keep.size + 1} offsets, got {starts.size}")
+        _check(load().pk_select_set_records(self._h, starts.ctypes.data, keep.ctypes.data if keep.size else None, keep.size))
+
+    def _fed(self, rc, n_out):
+        if rc == PK_ERR_RECS_CAP:
+            exc = PkError(rc, f"the feed keeps {int(n_out.value)} bytes: the output is too small")
+            exc.needed = int(n_out.value)
+            raise exc
+        _check(rc)
+        return int(n_out.value)
+
+    def feed(self, data, out: np.ndarray = None) -> np.ndarray:
+        """pk_select_feed: the next piece of the stream (anything with the buffer protocol) -> its kept bytes, a uint8 array
+        (a view of `out`, a writable contiguous uint8 array, when one is given; a PkError with `.needed` and the code
+        PK_ERR_RECS_CAP if it is too small -- nothing was written and the same piece may be fed again)."""
+        buf = _as_u8(data)
+        if out is None:
+            out = np.empty(buf.size, dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
+        n_out = ctypes.c_uint64(0)
+        rc = load().pk_select_feed(self._h, buf.ctypes.data if buf.size else None, buf.size, out.ctypes.data if out.size else None, out.size,
+                                   ctypes.byref(n_out))
+        return out[:self._fed(rc, n_out)]
+
+    def feed_device(self, dev_ptr: int, n_bytes: int, dev_out: int, out_cap: int) -> int:
+        """pk_select_feed_device: the next n_bytes of the stream at dev_ptr (HBM, 16-byte aligned) -> the number of kept bytes
+        written to dev_out (HBM, any alignment, out_cap bytes of room); PkError with `.needed` as feed."""
+        n_out = ctypes.c_uint64(0)
+        rc = load().pk_select_feed_device(self._h, ctypes.c_void_p(dev_ptr) if dev_ptr else None, int(n_bytes),
+                                          ctypes.c_void_p(dev_out) if dev_out else None, int(out_cap), ctypes.byref(n_out))
+        return self._fed(rc, n_out)
+
+    def finish(self) -> dict:
+        """pk_select_finish: bytes_fed, bytes_kept, records_kept (kept records whose first byte was fed)."""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(load().pk_select_finish(self._h, out.ctypes.data))
+        return {"bytes_fed": int(out[0]), "bytes_kept": int(out[1]), "records_kept": int(out[2])}
+
+    def timings(self) -> dict:
+        """pk_select_timings: the HIP-event seconds of the select kernels so far, and the feeds."""
+        out = np.zeros(2, dtype=np.float64)
+        _check(load().pk_select_timings(self._h, out.ctypes.data))
+        return {"select_s": float(out[0]), "feeds": int(out[1])}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

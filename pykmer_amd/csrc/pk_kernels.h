@@ -234,4 +234,13 @@ int launch_extract_table(const uint8_t *const *dev_tables, int P, int A, uint64_
 // m addresses -> m lines of k letters + '\n' (text 16-byte aligned)
 int launch_extract_text(const unsigned long long *addr, uint64_t m, int k, uint8_t *text, hipStream_t s);
 
+// kmer_select.hip -- the bytes of the kept records of a stream.  starts: R + 1 non-decreasing stream offsets,
+// keep: R flags (device).  text[0 .. n) (16-byte aligned) is the stream from offset pos on; its bytes that lie in kept records
+// go to out[0 .. expected), in order (any alignment) -- if they are exactly `expected` bytes, which the caller derives from the
+// same two arrays; otherwise nothing is written.  masks: select_chunks(n) * 256 u64; sums: select_chunks(n) + 1 u64, whose
+// last word receives the number of kept bytes, which is also added to *grand.  R = 0 or n = 0: nothing is launched.
+uint32_t select_chunks(uint64_t n);
+int launch_select(const unsigned long long *starts, const uint8_t *keep, uint64_t R, const uint8_t *text, uint64_t pos, uint64_t n,
+                  unsigned long long *masks, unsigned long long *sums, unsigned long long *grand, uint8_t *out, uint64_t expected, hipStream_t s);
+
 }  // namespace pk
