@@ -212,3 +212,54 @@ def test_cli(gpu, tables, tmp_path):
     assert again.returncode == 1 and [ln for ln in again.stderr.split("\n") if ln.startswith("error: ") and "already exists" in ln]
     bad = subprocess.run(argv[:4] + kins + ["--min-tables", "3"], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
     assert bad.returncode == 1 and "min-tables" in bad.stderr
+
+
+# ------------------------------------------------------------------ the product's size: reads at k = 15
+@pytest.fixture(scope="module")
+def tables15(gpu, tmp_path_factory):
+    """([a.kin, b.kin], SparseTables) at k = 15: two 1 GiB tables of query_ref.counted_sources, written side by side."""
+    from concurrent.futures import ThreadPoolExecutor
+    from test_host_layer import _write_index
+    d = tmp_path_factory.mktemp("filter_tables15")
+    sources, sparse = query_ref.counted_case(15)
+    with ThreadPoolExecutor(2) as pool:
+        got = list(pool.map(lambda i: _write_index(d, f"t{i}.fa", sources[i], 15), range(2)))
+    return [h.index_file_root for h, _ in got], sparse[:2]
+
+
+@pytest.mark.parametrize("form", ["plain", "gzip", "bgzf"])
+def test_reads_at_k15_in_feeds_of_20011_bytes(gpu, tables15, tmp_path, monkeypatch, form):
+    """5000 FASTQ reads of 0 .. 150 bases (tests/test_query_host.py checks the set) against two tables at k = 15, with the
+    feeds of all three passes -- the query, record_starts and the selector -- cut every 20 011 bytes: inside headers, reads
+    and quality lines, and more records than the record array first holds."""
+    from pykmer_amd import filter as kfilter
+    from pykmer_amd import indexer
+    k = 15
+    kins, tabs = tables15
+    text = query_ref.reads_case(k, 5000, True)
+    monkeypatch.setattr(indexer, "FEED_BYTES", 20_011)
+    monkeypatch.setattr(indexer, "GZ_PIECE", 20_011)
+    path = _forms(tmp_path, "reads.fq", text)[("plain", "gzip", "bgzf").index(form)]
+    runs = [(False, 0), (True, 0)] + ([(False, 20)] if form == "plain" else [])
+    for invert, Q in runs:
+        exp, matched, starts = _want(text, "fastq", k, tabs, H=3, P=40, T=33 + Q if Q else 0)
+        assert matched.any() and not matched.all() and (exp["n_valid"] == 0).any() and matched.size == 5000 > 4096
+        proj = str(tmp_path / f"p{int(invert)}{Q}")
+        res = kfilter.filter(proj, path, kins, min_hits=3, min_percent=40, invert=invert, rest=True, **({"min_qual": Q} if Q else {}))
+        keep = matched != invert
+        assert np.array_equal(res["keep"], keep.astype(np.uint8)) and np.array_equal(res["starts"], starts)
+        assert np.array_equal(res["hits"], exp["hits"]) and np.array_equal(res["n_valid"], exp["n_valid"])
+        kept, rest = open(f"{proj}.kept.fq", "rb").read(), open(f"{proj}.rest.fq", "rb").read()
+        assert kept == filter_ref.select_bytes(text, starts, keep) and rest == filter_ref.select_bytes(text, starts, ~keep)
+        pieces, ik, ir = [], 0, 0                            # kept and rest interleave back to the input
+        for r in range(len(keep)):
+            ln = int(starts[r + 1] - starts[r])
+            if keep[r]:
+                pieces.append(kept[ik:ik + ln])
+                ik += ln
+            else:
+                pieces.append(rest[ir:ir + ln])
+                ir += ln
+        assert b"".join(pieces) == text and ik == len(kept) and ir == len(rest)
+    if form == "plain":                                      # the masked run decides otherwise than the unmasked one
+        assert not np.array_equal(matched, _want(text, "fastq", k, tabs, H=3, P=40)[1])

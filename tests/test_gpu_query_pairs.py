@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 16384
 K = 9
+QPAIR_ROWS = 64                                              # kmer_query.hip: the rows of a slot whose pairs are tallied in LDS
 
 
 def _lib():
@@ -131,6 +132,28 @@ def test_one_record_across_three_slots(gpu, W):
                     per_record = _stream(q, text)
                     assert np.array_equal(ref.record_sums(got["shared"], got["bin_first"]), per_record["shared"])
     assert sums[16, (1, 255)].size == 120 and sums[16, (1, 255)].all()
+
+
+# ------------------------------------------------------------------ 1b. the LDS-resident rows ------
+@pytest.mark.parametrize("ragged", [False, True])
+@pytest.mark.parametrize("s", [QPAIR_ROWS - 1, QPAIR_ROWS, QPAIR_ROWS + 1, 129, 200])
+def test_long_record_behind_short_ones(gpu, s, ragged):
+    """The 12 000-base record is row s of its slot (tests/test_query_host.py checks the layout): whole waves of it lie in
+    one row, so their pairs are summed across the wave and added by one lane -- to the last row tallied in LDS, and to
+    HBM directly for the first row beyond and for later ones; from 129 on the hits of the same wave go to HBM as well.
+    N = 2, 3, 16: an even and an odd number of planes, and all sixteen (every plane register full).  W = 1000: the record has twelve rows."""
+    text, index = query_ref.long_after_short(s, seed=980 + s, ragged=ragged, tail_len=4000)
+    tables = _tables(K, 16, 901)
+    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+        for N in (2, 3, 16):
+            for window in ((1, 255), (255, 255)):
+                q.set_tables(dev.ptrs[:N], *window)
+                for W in (None, 1000):
+                    want = ref.expected(text, K, tables[:N], *window, W=W)
+                    rows = slice(index, index + 1) if W is None else slice(int(want["bin_first"][index]), int(want["bin_first"][index + 1]))
+                    assert want["n_valid"][index] == 12_000 - K + 1 and want["shared"][rows].all()
+                    assert W is None or rows.stop - rows.start == 12 and (ragged or rows.start == s)
+                    _checked(q, text, want, W=W)
 
 
 # ------------------------------------------------------------------ 2. many rows per slot ----------
