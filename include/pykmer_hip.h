@@ -211,7 +211,36 @@ void pk_indexer_destroy(pk_indexer *ix);
  * feed returns an error whose message names the size and what reduces it.
  * pk_query_pairs: after pk_indexer_finish.  out receives rows * P u64, [row][p]; rows are the records, or the B bins in row
  * order when bins are on.  PK_ERR_STATE when pairs are off; PK_ERR_RECS_CAP, with the needed number in the message, if
- * there are more rows than rows_cap. */
+ * there are more rows than rows_cap.
+ *
+ * Covered bases: which bases of the text the tables explain, and the text with those bases marked (the `bbduk kmask` step).
+ * A VALID BASE is a byte of ACGTacgt that is a sequence character of a record (text before the first header has none);
+ * the valid bases of the stream are numbered g = 0, 1, .. in text order over all records and feeds.  A valid window MATCHES
+ * iff min_count <= T_t[a] <= max_count in at least one table t, and a valid base is COVERED iff it lies in at least one
+ * matching window.  Two phases, because a base at the end of a feed may be covered only by a window that ends in the next.
+ * pk_query_set_cover: after pk_query_set_tables and before the first feed (PK_ERR_STATE otherwise); on != 0 keeps one cover
+ * bit per valid base, 0 (the default, which a reset restores) does not.  With the bits on the feeds run the cover kernels
+ * where they run the lookup: hits and depth stay zero, and bins, spectra and pairs do not go with it (PK_ERR_ARG).  The
+ * bitmap takes one bit per byte fed and is sized before every feed.  pk_indexer_timings [5] holds the cover kernels' seconds.
+ * pk_query_cover: after pk_indexer_finish.  *n_bases_out = the valid bases of the stream, B; bits_out receives
+ * ceil(B / 8) bytes, bit g at byte g / 8, bit g % 8 (np.unpackbits(bitorder="little")).  PK_ERR_RECS_CAP, with
+ * *n_bases_out set, if B > n_bits_cap; PK_ERR_STATE when the bits are off.
+ * pk_query_set_mask: after create or reset and before the first feed (PK_ERR_STATE otherwise); it needs no tables.  bits
+ * are n_bases cover bits in the layout above, from pk_query_cover or from anywhere; they are copied.  The SELECTED bases
+ * are the valid bases whose bit is set, with PK_MASK_INVERT those whose bit is clear.  Every feed (FASTA only; at most one
+ * piece, PK_FEED_PIECE bytes from the host and 1 GiB from the device, PK_ERR_ARG beyond) then leaves its text, byte for
+ * byte and at the same length, with only the selected bytes changed: byte | 0x20 (lower case), with PK_MASK_HARD 'N'.
+ * A reset ends the mode.  pk_indexer_timings [7] holds the apply kernel's seconds.
+ * pk_query_mask_text: the last feed's patched bytes; *n_out = their number; PK_ERR_RECS_CAP if it exceeds cap.
+ * pk_query_mask_counts: after pk_indexer_finish.  masked_out receives R u64, masked[r] = the selected bases of record r (a
+ * base counts whether or not its byte changed); *n_bases_seen_out = the valid bases the stream held.  PK_ERR_STATE if that
+ * is not the n_bases the mask was made for (the text changed between the phases); PK_ERR_RECS_CAP if R > recs_cap. */
+enum { PK_MASK_HARD = 1, PK_MASK_INVERT = 2 };
+int pk_query_set_cover(pk_indexer *q, int on);
+int pk_query_cover(pk_indexer *q, uint8_t *bits_out, uint64_t n_bits_cap, uint64_t *n_bases_out);
+int pk_query_set_mask(pk_indexer *q, const uint8_t *bits, uint64_t n_bases, int mode);
+int pk_query_mask_text(pk_indexer *q, uint8_t *host_out, uint64_t cap, uint64_t *n_out);
+int pk_query_mask_counts(pk_indexer *q, uint64_t *masked_out, uint64_t recs_cap, uint64_t *n_bases_seen_out);
 int pk_query_create(pk_indexer **out, int k, int device);
 int pk_query_set_tables(pk_indexer *q, const void *const *dev_tables, int N, int min_count, int max_count);
 int pk_query_results(pk_indexer *q, uint64_t *hits_out, uint64_t *depth_out, uint64_t recs_cap);

@@ -13,6 +13,7 @@ from ._rt import LIB_PATH, open_library
 PK_OK, PK_ERR_ARG, PK_ERR_HIP, PK_ERR_RECS_CAP, PK_ERR_STATE, PK_ERR_FORMAT = 0, -1, -2, -3, -4, -5
 PK_FORMAT_FASTA, PK_FORMAT_FASTQ = 0, 1
 FORMATS = {"fasta": PK_FORMAT_FASTA, "fastq": PK_FORMAT_FASTQ}
+MASK_HARD, MASK_INVERT = 1, 2                                # the mode bits of pk_query_set_mask
 
 RECORD_DTYPE = np.dtype([("name_off", "<u8"), ("name_len", "<u8"), ("seq_len", "<u8"), ("n_valid_kmers", "<u8")])
 
@@ -59,6 +60,11 @@ _SIGNATURES = {
     "pk_query_spectrum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_query_set_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "pk_query_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_query_set_cover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_query_cover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
+    "pk_query_set_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]),
+    "pk_query_mask_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
+    "pk_query_mask_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -311,7 +317,7 @@ class QueryIndexer(Indexer):
     """An indexer in query mode (pk_query_*): it parses its feeds like an Indexer, holds no table, and tallies per record how
     many windows hit each of N device-resident 4^k-byte tables.  feed / feed_device / finish / records / reset as Indexer."""
 
-    TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "lookup_s", "coords_s")
+    TIMINGS = ("scan_s", "squeeze_s", "finalize_s", "zero_s", "feeds", "lookup_s", "coords_s", "mask_s")
 
     def __init__(self, k: int, device: int = 0, fmt: str = "fasta", min_qual_byte: int = 0):
         self.n_tables = 0
@@ -392,6 +398,45 @@ class QueryIndexer(Indexer):
         out = np.zeros((max(n_rows, 1), max(P, 1)), dtype=np.uint64)
         _check(load().pk_query_pairs(self._h, out.ctypes.data, n_rows))
         return out[:n_rows, :P]
+
+    def set_cover(self, on: bool = True):
+        """pk_query_set_cover, after set_tables and before the first feed: keep one bit per valid base of the stream, set iff
+        the base lies in a valid window that matches at least one table; the feeds then run no lookup (hits stay zero).  Off by
+        default; a reset clears the setting."""
+        _check(load().pk_query_set_cover(self._h, 1 if on else 0))
+
+    def cover(self, n_bits_cap: int):
+        """pk_query_cover after finish(): (cover, n_bases), the packed bits (ceil(n_bases / 8),) uint8, bit g of the stream at
+        byte g // 8, bit g % 8 (np.unpackbits(bitorder="little")).  n_bits_cap: an upper bound of n_bases, the bytes fed for one."""
+        out = np.zeros((int(n_bits_cap) + 7) // 8 + 1, dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        _check(load().pk_query_cover(self._h, out.ctypes.data, int(n_bits_cap), ctypes.byref(n)))
+        return out[:(int(n.value) + 7) // 8], int(n.value)
+
+    def set_mask(self, cover, n_bases: int, hard: bool = False, invert: bool = False):
+        """pk_query_set_mask, before the first feed and without tables: every feed then leaves its text with the selected valid
+        bases marked (mask_text) -- those whose bit in `cover` (packed as cover() returns it, for n_bases bases) is set, with
+        `invert` the others; lower case, with `hard` N.  A reset ends the mode."""
+        bits = np.ascontiguousarray(cover, dtype=np.uint8)
+        if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
+            raise ValueError(f"{int(n_bases)} bases take {(int(n_bases) + 7) // 8} bytes of cover bits, got an array of shape {bits.shape}")
+        mode = (MASK_HARD if hard else 0) | (MASK_INVERT if invert else 0)
+        _check(load().pk_query_set_mask(self._h, bits.ctypes.data if bits.size else None, int(n_bases), mode))
+
+    def mask_text(self, out: np.ndarray) -> np.ndarray:
+        """pk_query_mask_text: the last feed's patched bytes into `out` (uint8, at least as long as the feed); returns the view of them."""
+        assert out.dtype == np.uint8 and out.flags.c_contiguous
+        n = ctypes.c_uint64(0)
+        _check(load().pk_query_mask_text(self._h, out.ctypes.data if out.size else None, out.size, ctypes.byref(n)))
+        return out[:int(n.value)]
+
+    def mask_counts(self, n_records: int):
+        """pk_query_mask_counts after finish(): (masked (n_records,) uint64, n_bases_seen); PkError if the stream's valid bases do
+        not number what the mask was made for."""
+        masked = np.zeros(max(n_records, 1), dtype=np.uint64)
+        n = ctypes.c_uint64(0)
+        _check(load().pk_query_mask_counts(self._h, masked.ctypes.data, n_records, ctypes.byref(n)))
+        return masked[:n_records], int(n.value)
 
 
 class Selector:

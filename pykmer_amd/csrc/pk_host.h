@@ -130,11 +130,28 @@ struct QueryState {
     // tables of a pair i < j, sized, grown and zeroed with hits (ensure_pairs); one table has no pair and no array
     bool pairs = false;
     DevBuf<unsigned long long> shared;
-    hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // the kernels of kmer_query.hip
+    // covered bases (kmer_cover.hip).  nb: the valid bases of the stream at the start of the next feed (word nb_in) and where
+    // the feed's scan leaves the number at its end (the other word); base_first: one word per chunk.
+    // cover (pk_query_set_cover): the feeds run k_query_cover where they run the lookup; cover_bits holds one bit per valid
+    // base, sized before every feed for the bytes fed by then (ensure_cover).
+    // apply (pk_query_set_mask; no tables): the feeds patch the caller's bits (mask_bits, for mask_n_bases bases) into the
+    // text; mask_out holds the last feed's patched text (mask_out_n bytes), masked[r] the selected bases of record r, sized
+    // and grown with the record array.
+    bool cover = false, apply = false;
+    DevBuf<unsigned long long> nb, base_first, masked;
+    int nb_in = 0;
+    DevBuf<uint32_t> cover_bits, mask_bits;
+    DevBuf<uint8_t> mask_out;
+    uint64_t mask_n_bases = 0, mask_out_n = 0;
+    uint32_t mask_mode = 0;
+    hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // the kernels of kmer_query.hip, or k_cover_scan + k_query_cover
     hipEvent_t coords_begin = nullptr, coords_end = nullptr;       // the kernels of kmer_coords.hip
-    double t_coords = 0;
+    hipEvent_t mask_begin = nullptr, mask_end = nullptr;           // k_mask_apply
+    double t_coords = 0, t_mask = 0;
 
-    ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end}) if (e) hipEventDestroy(e); }
+    ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end, mask_begin, mask_end}) if (e) hipEventDestroy(e); }
+    int ensure_cover(uint64_t bytes, hipStream_t s);               // cover: a bit for every byte of a stream of `bytes` bytes
+    uint64_t cover_words() const { return cover_bits.bytes / sizeof(uint32_t); }
     int create();                                                  // the events, and P for the record array's first capacity
     int reset(hipStream_t s);                                      // an empty stream; the tables stay; bins, coordinates, spectra and pairs are off
     int grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s);   // the record array now holds `cap` records; the rows follow

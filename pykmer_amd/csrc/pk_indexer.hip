@@ -317,6 +317,39 @@ static int count_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     return add_elapsed(&ix->t_sort, ev.sort_begin, ev.sort_end);
 }
 
+// The feed of a query indexer that applies a mask (pk_query_set_mask): behind the squeeze (for n_bases[]) the base scan and
+// k_mask_apply, which leaves the feed's patched text in a buffer of its own -- the squeeze of a repeated attempt (flag 2)
+// reads the text it read before.  No tables, no lookups.
+static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
+    QueryState &q = *ix->q;
+    if (ix->format != PK_FORMAT_FASTA) return fail(PK_ERR_STATE, "a mask is applied to FASTA text only");
+    const PartPlan pl = make_part_plan((uint32_t)ix->k, n_bytes, 0u, 0u);   // the squeeze's launch shape; nothing is partitioned
+    int rc = ix->ws.reserve(query_workspace(pl.n_chunks));
+    if (rc) return rc;
+    PartBuffers pb;
+    QueryBuffers qb;
+    query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb);
+    if ((rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
+    if ((rc = q.mask_out.reserve(n_bytes + 64))) return rc;
+    q.mask_out_n = 0;
+    auto queue = [&](uint32_t raised) -> int {
+        if (raised && raised != 2u) return fail(PK_ERR_HIP, "the mask feed did not settle (internal error, flag %u)", raised);
+        // a repeated attempt starts from the same base count (the words change roles once the feed has settled) and finds
+        // masked[] as the feed before left it: the attempt that backed out added nothing
+        launch_cover_scan(pl, pb, q.nb.p + q.nb_in, q.nb.p + (q.nb_in ^ 1), q.base_first.p, ix->stream);
+        HIPCHK(hipEventRecord(q.mask_begin, ix->stream));
+        launch_mask_apply(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, q.mask_bits.bytes / sizeof(uint32_t),
+                          q.mask_mode, q.mask_out.p, q.masked.p, q.masked.bytes / sizeof(unsigned long long), ix->stream);
+        HIPCHK(hipEventRecord(q.mask_end, ix->stream));
+        HIPCHK(hipGetLastError());
+        return PK_OK;
+    };
+    if ((rc = run_feed(ix, f, n_bytes, pl, pb, "the mask feed", "masked", queue))) return rc;
+    q.nb_in ^= 1;                                            // the base count behind this feed is the next feed's start
+    q.mask_out_n = n_bytes;
+    return add_elapsed(&q.t_mask, q.mask_begin, q.mask_end);
+}
+
 // A query indexer's feed: the lookup kernels (kmer_query.hip), and with coordinates those of kmer_coords.hip, where
 // count_feed runs launch_partitioned.  There is no sampled layout, so the only flag is 2 (the squeeze backed out): the
 // record array, the window prefix and the accumulators grow (ensure_recs), and the squeeze and the lookups run again.  With
@@ -324,6 +357,7 @@ static int count_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
 // again, for the same stream, whenever the record array grows (ensure_recs).
 static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     QueryState &q = *ix->q;
+    if (q.apply) return mask_feed(ix, f, n_bytes);
     if (q.tables.empty()) return fail(PK_ERR_STATE, "pk_query_set_tables comes before the first feed");
     const PartPlan pl = make_part_plan((uint32_t)ix->k, n_bytes, 0u, 0u);   // the squeeze's launch shape; nothing is partitioned
     int rc = ix->ws.reserve(query_workspace(pl.n_chunks));
@@ -337,9 +371,24 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if ((rc = q.ensure_spectrum(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
     if ((rc = q.ensure_pairs(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
     if (q.coords && (rc = q.cpos.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
+    if (q.cover) {
+        if ((rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
+        if ((rc = q.ensure_cover(ix->bytes_fed + n_bytes, ix->stream))) return rc;
+    }
     auto queue = [&](uint32_t raised) -> int {
         if (raised && raised != 2u) return fail(PK_ERR_HIP, "the query feed did not settle (internal error, flag %u)", raised);
         HIPCHK(hipEventRecord(q.lookup_begin, ix->stream));
+        if (q.cover) {
+            // the cover kernels where the lookup runs: no row tallies are needed.  A repeated attempt starts from the same
+            // base count: the two words change roles only once the feed has settled
+            launch_cover_scan(pl, pb, q.nb.p + q.nb_in, q.nb.p + (q.nb_in ^ 1), q.base_first.p, ix->stream);
+            for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
+                launch_query_cover(pl, pb, ix->c_l2s.p, q.base_first.p, q.tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), (uint32_t)q.min,
+                                   (uint32_t)q.max, q.cover_bits.p, q.cover_words(), ix->stream);
+            HIPCHK(hipEventRecord(q.lookup_end, ix->stream));
+            HIPCHK(hipGetLastError());
+            return PK_OK;
+        }
         launch_query_scan(pl, pb, qb, ix->c_l2s.p, q.windows, ix->recs.p, carry, q.p_done, q.P.p, q.Bf.p, q.bin, ix->stream);
         for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
             launch_query_lookup(pl, pb, qb, ix->c_l2s.p, q.P.p, q.Bf.p, q.bin, carry, q.tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), N, t0,
@@ -362,6 +411,7 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     q.windows = ix->pin->tail.carry.num_kmers;
     q.p_done = ix->n_recs;
     if ((rc = add_elapsed(&ix->t_part, q.lookup_begin, q.lookup_end))) return rc;
+    if (q.cover) q.nb_in ^= 1;                               // the base count behind this feed is the next feed's start
     if (!q.coords) return PK_OK;
     if ((rc = add_elapsed(&q.t_coords, q.coords_begin, q.coords_end))) return rc;
     q.pos_in ^= 1;                                           // the position behind this feed is the next feed's start
@@ -531,6 +581,10 @@ extern "C" int pk_indexer_feed_device(pk_indexer *ix, const void *dev_fasta, uin
     const uint64_t piece_max = feed_max_for(ix->k);                 // a multiple of 16: pieces stay aligned
     const bool fastq = ix->format == PK_FORMAT_FASTQ;
     if (fastq && ix->fq_failed) return fail(PK_ERR_FORMAT, "%s", ix->fq_err.c_str());
+    // pk_query_mask_text hands back one piece: the caller cuts a longer text itself
+    if (ix->q && ix->q->apply && n_bytes > piece_max)
+        return fail(PK_ERR_ARG, "a mask feed takes at most %llu bytes, got %llu; feed the text in smaller pieces", (unsigned long long)piece_max,
+                    (unsigned long long)n_bytes);
     ix->fed = true;
     for (uint64_t off = 0; off < n_bytes; off += piece_max) {
         const uint64_t len = std::min(piece_max, n_bytes - off);
@@ -551,6 +605,9 @@ extern "C" int pk_indexer_feed(pk_indexer *ix, const uint8_t *host_fasta, uint64
     uint64_t piece = env ? strtoull(env, nullptr, 10) : (256ULL << 20);
     piece = std::max<uint64_t>(1 << 20, std::min<uint64_t>(piece, 1ULL << 30)) & ~15ULL;
     const uint64_t n_pieces = (n_bytes + piece - 1) / piece;
+    if (ix->q && ix->q->apply && n_pieces > 1)               // pk_query_mask_text hands back one piece
+        return fail(PK_ERR_ARG, "a mask feed takes at most %llu bytes, got %llu; feed the text in smaller pieces", (unsigned long long)piece,
+                    (unsigned long long)n_bytes);
     const uint64_t buf_bytes = std::min(piece, n_bytes) + 64;
     const int n_bufs = n_pieces > 1 ? 2 : 1;
     int rc = PK_OK;
@@ -686,7 +743,7 @@ extern "C" int pk_indexer_timings(pk_indexer *ix, double out[10]) {
     if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
     for (int i = 0; i < 10; i++) out[i] = 0;
     out[0] = ix->t_scan; out[1] = ix->t_squeeze; out[2] = ix->t_final; out[3] = ix->t_zero; out[4] = (double)ix->feeds;
-    out[5] = ix->t_part; out[6] = ix->q ? ix->q->t_coords : ix->t_bucket; out[7] = ix->t_sort; out[8] = (double)ix->relayouts; out[9] = (double)ix->recounted;
+    out[5] = ix->t_part; out[6] = ix->q ? ix->q->t_coords : ix->t_bucket; out[7] = ix->q ? ix->q->t_mask : ix->t_sort; out[8] = (double)ix->relayouts; out[9] = (double)ix->recounted;
     return PK_OK;
 }
 

@@ -146,6 +146,22 @@ void launch_query_coords(const PartPlan &pl, const PartBuffers &b, const QueryBu
                          const unsigned long long *Bf, uint64_t bin_windows, unsigned long long *chunk_pos, const unsigned long long *pos_in,
                          unsigned long long *pos_out, unsigned long long *bin_start, unsigned long long *bin_end, uint64_t rows_cap, hipStream_t s);
 
+// kmer_cover.hip -- the bases of the stream that the tables cover, one bit per valid base, and the text with them marked
+// (DESIGN.md 4.14).  All three run behind the squeeze of the same feed (n_bases[]).
+// nb_in: the valid bases of the stream before the feed; nb_out receives the number behind it; base_first: n_chunks words.
+void launch_cover_scan(const PartPlan &pl, const PartBuffers &b, const unsigned long long *nb_in, unsigned long long *nb_out,
+                       unsigned long long *base_first, hipStream_t s);
+// ORs into bitmap (n_words u32, bit g at word g / 32, bit g % 32) the bases that lie in a valid window with min <= T[a] <= max
+// in one of tables[0 .. n_tab), n_tab <= QUERY_MAX_TABLES
+void launch_query_cover(const PartPlan &pl, const PartBuffers &b, const L2 *st2, const unsigned long long *base_first, const uint8_t *const *tables,
+                        uint32_t n_tab, uint32_t min_count, uint32_t max_count, uint32_t *bitmap, uint64_t n_words, hipStream_t s);
+// out (n + 64 bytes, 16-byte aligned) = the feed's text with the selected valid bases marked: those whose bit in `bits` is set,
+// with mode bit 1 (invert) the others; lower case, with mode bit 0 (hard) 'N'.  masked[r] (recs_cap words) += the selected
+// bases of record r.
+void launch_mask_apply(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state, const L2 *st2,
+                       const unsigned long long *base_first, const uint32_t *bits, uint64_t n_words, uint32_t mode, uint8_t *out,
+                       unsigned long long *masked, uint64_t recs_cap, hipStream_t s);
+
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it
     uint64_t line;           // line terminators seen (the role of the open line is line & 3)

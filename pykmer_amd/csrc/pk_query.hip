@@ -6,19 +6,32 @@
 using namespace pk;
 
 int QueryState::create() {
-    for (hipEvent_t *e : {&lookup_begin, &lookup_end, &coords_begin, &coords_end}) HIPCHK(hipEventCreate(e));
+    for (hipEvent_t *e : {&lookup_begin, &lookup_end, &coords_begin, &coords_end, &mask_begin, &mask_end}) HIPCHK(hipEventCreate(e));
     return P.reserve(4096 * sizeof(unsigned long long));
 }
 
 int QueryState::reset(hipStream_t s) {
-    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos, &spec, &shared})
+    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos, &spec, &shared, &nb, &masked})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, s));
+    if (cover_bits.p) HIPCHK(hipMemsetAsync(cover_bits.p, 0, cover_bits.bytes, s));
     windows = p_done = 0;
     bin = n_bins = 0;
     spectrum = false;
     pairs = false;
     coords = false; pos_in = 0; t_coords = 0;
+    cover = apply = false; nb_in = 0; t_mask = 0;
+    mask_n_bases = mask_out_n = 0; mask_mode = 0;
     return PK_OK;
+}
+
+// Covered bases: one bit per valid base, and a stream of `bytes` bytes holds at most as many; one word in front of the
+// first base's is never written, one behind the last takes the read of a lane's third word.  Contents kept, the rest zero;
+// it grows by half at least, so that a long stream does not move it with every feed.
+int QueryState::ensure_cover(uint64_t bytes, hipStream_t s) {
+    if (!cover) return PK_OK;
+    const size_t need = (bytes / 32 + 2) * sizeof(uint32_t);
+    if (need <= cover_bits.bytes) return PK_OK;
+    return cover_bits.grow_keep(std::max<size_t>(need, cover_bits.bytes + cover_bits.bytes / 2), s);
 }
 
 // the window prefix and the accumulators grow with the record array and keep what they hold; binned, the rows are sized
@@ -35,6 +48,7 @@ int QueryState::grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s) {
         if ((rc = depth.grow_keep(cap * row, s))) return rc;
     }
     if ((rc = ensure_spectrum(cap, bytes, s))) return rc;
+    if (apply && (rc = masked.grow_keep(cap * sizeof(unsigned long long), s))) return rc;
     return ensure_pairs(cap, bytes, s);
 }
 
@@ -210,6 +224,104 @@ extern "C" int pk_query_set_coords(pk_indexer *ix, int on) {
     // the two position words; a reset zeroed what was there, a new array is zeroed here
     const int rc = q.pos.grow_keep(2 * sizeof(unsigned long long), ix->stream);
     return rc ? rc : q.ensure_rows(ix->recs_cap(), 0, ix->stream);
+}
+
+// the two base-count words; a reset zeroed what was there, a new array is zeroed here
+static int cover_words_ready(pk_indexer *ix) { return ix->q->nb.grow_keep(2 * sizeof(unsigned long long), ix->stream); }
+
+extern "C" int pk_query_set_cover(pk_indexer *ix, int on) {
+    if (int rc = query_check(ix, has_tables, "pk_query_set_tables comes before pk_query_set_cover", "the cover bits are set before the first feed (reset the indexer first)")) return rc;
+    QueryState &q = *ix->q;
+    if (on && (q.bin || q.spectrum || q.pairs))
+        return fail(PK_ERR_ARG, "the cover bits take the place of the tallies: bins, count spectra and shared windows belong to a stream of their own");
+    if (on && q.apply) return fail(PK_ERR_ARG, "the indexer applies a mask (pk_query_set_mask); the cover bits come from a stream of their own");
+    HIPCHK(hipSetDevice(ix->device));
+    q.cover = on != 0;
+    if (!q.cover) return PK_OK;
+    int rc = cover_words_ready(ix);
+    if (!rc) rc = q.ensure_cover(0, ix->stream);
+    if (rc) q.cover = false;                                 // an array that did not fit: the setting did not take
+    return rc;
+}
+
+// the valid bases of the stream so far, as the last settled feed left them (after a wait on the stream)
+static int bases_seen(pk_indexer *ix, uint64_t *out) {
+    *out = 0;
+    if (!ix->q->nb.p) return PK_OK;
+    unsigned long long n = 0;
+    HIPCHK(hipMemcpy(&n, ix->q->nb.p + ix->q->nb_in, sizeof n, hipMemcpyDeviceToHost));
+    *out = n;
+    return PK_OK;
+}
+
+static bool with_cover(const QueryState &q) { return q.cover; }
+static bool applying(const QueryState &q) { return q.apply; }
+
+extern "C" int pk_query_cover(pk_indexer *ix, uint8_t *bits_out, uint64_t n_bits_cap, uint64_t *n_bases_out) {
+    if (int rc = query_check(ix, with_cover, "the indexer keeps no cover bits (pk_query_set_cover)", nullptr)) return rc;
+    if (!n_bases_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const QueryState &q = *ix->q;
+    if (int rc = bases_seen(ix, n_bases_out)) return rc;
+    const uint64_t n = *n_bases_out;
+    if (n > n_bits_cap) return fail(PK_ERR_RECS_CAP, "%llu valid bases, capacity %llu bits", (unsigned long long)n, (unsigned long long)n_bits_cap);
+    if (n == 0) return PK_OK;
+    if (!bits_out) return fail(PK_ERR_ARG, "null output pointer");
+    if ((n + 7) / 8 > q.cover_bits.bytes) return fail(PK_ERR_HIP, "cover bitmap smaller than the stream (internal error)");
+    HIPCHK(hipMemcpy(bits_out, q.cover_bits.p, (n + 7) / 8, hipMemcpyDeviceToHost));
+    return PK_OK;
+}
+
+extern "C" int pk_query_set_mask(pk_indexer *ix, const uint8_t *bits, uint64_t n_bases, int mode) {
+    if (int rc = query_check(ix, nullptr, nullptr, "the mask is set before the first feed (reset the indexer first)")) return rc;
+    if (mode < 0 || mode > (PK_MASK_HARD | PK_MASK_INVERT)) return fail(PK_ERR_ARG, "unknown mask mode %d", mode);
+    if (n_bases && !bits) return fail(PK_ERR_ARG, "null bitmap for %llu bases", (unsigned long long)n_bases);
+    QueryState &q = *ix->q;
+    if (q.cover) return fail(PK_ERR_ARG, "the indexer keeps cover bits (pk_query_set_cover); a mask is applied in a stream of its own");
+    if (ix->format != PK_FORMAT_FASTA) return fail(PK_ERR_ARG, "a mask is applied to FASTA text only");
+    HIPCHK(hipSetDevice(ix->device));
+    int rc = cover_words_ready(ix);
+    if (rc) return rc;
+    // whole words, zero behind the last base; one more for the read of a lane's third word
+    const size_t words = n_bases / 32 + 2;
+    if ((rc = q.mask_bits.reserve(words * sizeof(uint32_t)))) return rc;
+    HIPCHK(hipMemsetAsync(q.mask_bits.p, 0, q.mask_bits.bytes, ix->stream));
+    if (n_bases) HIPCHK(hipMemcpyAsync(q.mask_bits.p, bits, (n_bases + 7) / 8, hipMemcpyHostToDevice, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));                // the caller may free its bits
+    if ((rc = q.masked.grow_keep(ix->recs_cap() * sizeof(unsigned long long), ix->stream))) return rc;
+    q.mask_n_bases = n_bases;
+    q.mask_mode = (uint32_t)mode;
+    q.mask_out_n = 0;
+    q.apply = true;
+    return PK_OK;
+}
+
+extern "C" int pk_query_mask_text(pk_indexer *ix, uint8_t *host_out, uint64_t cap, uint64_t *n_out) {
+    if (!ix) return fail(PK_ERR_ARG, "null indexer");
+    if (!ix->q || !ix->q->apply) return fail(PK_ERR_STATE, "the indexer applies no mask (pk_query_set_mask)");
+    if (!n_out) return fail(PK_ERR_ARG, "null output pointer");
+    const QueryState &q = *ix->q;
+    *n_out = q.mask_out_n;
+    if (q.mask_out_n > cap) return fail(PK_ERR_RECS_CAP, "%llu bytes of text, capacity %llu", (unsigned long long)q.mask_out_n, (unsigned long long)cap);
+    if (q.mask_out_n == 0) return PK_OK;
+    if (!host_out) return fail(PK_ERR_ARG, "null output pointer");
+    return bounce_copy(q.mask_out.p, host_out, q.mask_out_n, false, ix->device);   // every feed ends with a wait
+}
+
+extern "C" int pk_query_mask_counts(pk_indexer *ix, uint64_t *masked_out, uint64_t recs_cap, uint64_t *n_bases_seen_out) {
+    if (int rc = query_check(ix, applying, "the indexer applies no mask (pk_query_set_mask)", nullptr)) return rc;
+    if (!n_bases_seen_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipSetDevice(ix->device));
+    const QueryState &q = *ix->q;
+    if (int rc = bases_seen(ix, n_bases_seen_out)) return rc;
+    if (*n_bases_seen_out != q.mask_n_bases)
+        return fail(PK_ERR_STATE, "the stream holds %llu valid bases and the mask was made for %llu: the text changed between the phases",
+                    (unsigned long long)*n_bases_seen_out, (unsigned long long)q.mask_n_bases);
+    if (ix->n_recs > recs_cap) return fail(PK_ERR_RECS_CAP, "%llu records, capacity %llu", (unsigned long long)ix->n_recs, (unsigned long long)recs_cap);
+    if (ix->n_recs == 0) return PK_OK;
+    if (!masked_out) return fail(PK_ERR_ARG, "null output pointer");
+    HIPCHK(hipMemcpy(masked_out, q.masked.p, ix->n_recs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PK_OK;
 }
 
 // the rows of a finished binned stream: the last record's bins are not in Bf
