@@ -331,12 +331,18 @@ class QueryIndexer(Indexer):
         _check(load().pk_query_set_tables(self._h, _ptr_array(dev_ptrs), len(dev_ptrs), int(min_count), int(max_count)))
         self.n_tables = len(dev_ptrs)
 
+    @staticmethod
+    def _room(*shape):
+        """(array, view): uint64 zeros with room for `shape` and no empty dimension, so that the library always gets a
+        pointer, and the `shape` corner of them that the getter hands back."""
+        full = np.zeros([max(int(n), 1) for n in shape], dtype=np.uint64)
+        return full, full[tuple(slice(0, int(n)) for n in shape)]
+
     def results(self, n_records: int):
         """pk_query_results after finish(): (hits, depth), each (n_records, N) uint64."""
-        hits = np.zeros((max(n_records, 1), max(self.n_tables, 1)), dtype=np.uint64)
-        depth = np.zeros_like(hits)
+        (hits, h), (depth, d) = self._room(n_records, self.n_tables), self._room(n_records, self.n_tables)
         _check(load().pk_query_results(self._h, hits.ctypes.data, depth.ctypes.data, n_records))
-        return hits[:n_records, :self.n_tables], depth[:n_records, :self.n_tables]
+        return h, d
 
     def set_bins(self, bin_windows: int):
         """pk_query_set_bins, after set_tables and before the first feed: tally in bins of `bin_windows` valid windows
@@ -354,11 +360,10 @@ class QueryIndexer(Indexer):
         """pk_query_bin_results after finish(): (hits, depth, bin_first); hits and depth (B, N) uint64, one row per bin,
         bin_first (n_records + 1,) uint64 with bin_first[-1] = B."""
         B = self._bin_count()
-        hits = np.zeros((max(B, 1), max(self.n_tables, 1)), dtype=np.uint64)
-        depth = np.zeros_like(hits)
+        (hits, h), (depth, d) = self._room(B, self.n_tables), self._room(B, self.n_tables)
         bin_first = np.zeros(n_records + 1, dtype=np.uint64)
         _check(load().pk_query_bin_results(self._h, hits.ctypes.data, depth.ctypes.data, bin_first.ctypes.data, B, n_records))
-        return hits[:B, :self.n_tables], depth[:B, :self.n_tables], bin_first
+        return h, d, bin_first
 
     def set_coords(self, on: bool = True):
         """pk_query_set_coords, after set_bins with W > 0 and before the first feed: also keep every row's base coordinates
@@ -369,10 +374,9 @@ class QueryIndexer(Indexer):
         """pk_query_bin_coords after finish(): (bin_start, bin_end), each (B,) uint64 in row order: the position of the first
         base of the row's first window and one past the last base of its last."""
         B = self._bin_count()
-        start = np.zeros(max(B, 1), dtype=np.uint64)
-        end = np.zeros_like(start)
+        (start, s), (end, e) = self._room(B), self._room(B)
         _check(load().pk_query_bin_coords(self._h, start.ctypes.data, end.ctypes.data, B))
-        return start[:B], end[:B]
+        return s, e
 
     def set_spectrum(self, on: bool = True):
         """pk_query_set_spectrum, after set_tables and before the first feed (before or after set_bins): also tally the
@@ -382,9 +386,9 @@ class QueryIndexer(Indexer):
     def spectrum(self, n_rows: int):
         """pk_query_spectrum after finish(): (n_rows, N, 256) uint64, spectrum[row][t][c] = the windows of the row whose count
         in table t is c; the rows are the records, or the bins (n_rows = bin_first[-1]) when bins are on."""
-        out = np.zeros((max(n_rows, 1), max(self.n_tables, 1), 256), dtype=np.uint64)
+        out, view = self._room(n_rows, self.n_tables, 256)
         _check(load().pk_query_spectrum(self._h, out.ctypes.data, n_rows))
-        return out[:n_rows, :self.n_tables]
+        return view
 
     def set_pairs(self, on: bool = True):
         """pk_query_set_pairs, after set_tables (at most 16) and before the first feed (before or after set_bins): also tally,
@@ -394,10 +398,9 @@ class QueryIndexer(Indexer):
     def pairs(self, n_rows: int):
         """pk_query_pairs after finish(): (n_rows, P) uint64, P = N (N - 1) / 2, shared[row][p] = the windows of the row valid
         in both tables of pair p (spectrum.pair_list(N)[p]); the rows are the records, or the bins when bins are on."""
-        P = self.n_tables * (self.n_tables - 1) // 2
-        out = np.zeros((max(n_rows, 1), max(P, 1)), dtype=np.uint64)
+        out, view = self._room(n_rows, self.n_tables * (self.n_tables - 1) // 2)
         _check(load().pk_query_pairs(self._h, out.ctypes.data, n_rows))
-        return out[:n_rows, :P]
+        return view
 
     def set_cover(self, on: bool = True):
         """pk_query_set_cover, after set_tables and before the first feed: keep one bit per valid base of the stream, set iff
@@ -433,10 +436,10 @@ class QueryIndexer(Indexer):
     def mask_counts(self, n_records: int):
         """pk_query_mask_counts after finish(): (masked (n_records,) uint64, n_bases_seen); PkError if the stream's valid bases do
         not number what the mask was made for."""
-        masked = np.zeros(max(n_records, 1), dtype=np.uint64)
+        masked, view = self._room(n_records)
         n = ctypes.c_uint64(0)
         _check(load().pk_query_mask_counts(self._h, masked.ctypes.data, n_records, ctypes.byref(n)))
-        return masked[:n_records], int(n.value)
+        return view, int(n.value)
 
 
 class Selector:

@@ -233,8 +233,7 @@ void launch_cover_scan(const PartPlan &pl, const PartBuffers &b, const unsigned 
 
 void launch_query_cover(const PartPlan &pl, const PartBuffers &b, const L2 *st2, const unsigned long long *base_first, const uint8_t *const *tables,
                         uint32_t n_tab, uint32_t min_count, uint32_t max_count, uint32_t *bitmap, uint64_t n_words, hipStream_t s) {
-    QueryTables tabs;
-    for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
+    const QueryTables tabs = query_tables(tables, n_tab);
 #define PK_QUERY_COVER(KT) hipLaunchKernelGGL(k_query_cover<KT>, dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes, (const uint32_t *)b.restarts, \
                                               (const uint32_t *)b.n_bases, st2, pl.k, base_first, tabs, n_tab, min_count, max_count, bitmap,                 \
                                               (unsigned long long)n_words, (const uint32_t *)b.flags)

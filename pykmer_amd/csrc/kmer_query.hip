@@ -456,8 +456,7 @@ void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuff
 void launch_query_lookup(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, const Carry *carry, const uint8_t *const *tables, uint32_t n_tab, uint32_t N, uint32_t t0, uint32_t min_count, uint32_t max_count,
                          unsigned long long *hits, unsigned long long *depth, unsigned long long *spectrum, unsigned long long *shared, hipStream_t s) {
-    QueryTables tabs;
-    for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
+    const QueryTables tabs = query_tables(tables, n_tab);
 #define PK_QUERY_LOOKUP(KT, BINS, SPEC, PAIRS) hipLaunchKernelGGL((k_query_lookup<KT, BINS, SPEC, PAIRS>), dim3(pl.n_chunks), dim3(QNT), 0, s, (const uint32_t *)b.codes,               \
                                                      (const uint32_t *)b.restarts, (const uint32_t *)b.n_bases, st2, pl.k,                                  \
                                                      (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, carry, tabs, n_tab, \

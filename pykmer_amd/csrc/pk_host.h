@@ -1,6 +1,7 @@
 // pk_host.h -- what the files of the host layer share (pk_common.hip, pk_indexer.hip, pk_query.hip, pk_merge.hip, pk_select.hip): the error
-// helper, owned device memory and the host <-> HBM copy for all of them, struct pk_indexer and the state of a query for
-// pk_indexer.hip (which feeds both kinds of indexer) and pk_query.hip, and the standard headers they use.  Every allocation of
+// helper, owned device memory and the host <-> HBM copy for all of them, struct pk_indexer and the state of a query (with
+// the value it carries from feed to feed, Carried) for pk_indexer.hip (which feeds both kinds of indexer) and pk_query.hip,
+// and the standard headers they use.  Every allocation of
 // the library is made in these files.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -101,9 +102,22 @@ struct Events {
     }
 };
 
+// A value carried from one feed to the next in two device words: the feed's kernels read the value at its start from
+// start() and leave the one at its end in end().  A repeated attempt of a feed starts from the same word: the two change
+// roles only once the feed has settled (settle()).
+struct Carried {
+    DevBuf<unsigned long long> words;
+    int in = 0;                                                 // the word that holds the value at the start of the next feed
+    // the two words; a reset zeroed what was there, a new array is zeroed here
+    int ready(hipStream_t s) { return words.grow_keep(2 * sizeof(unsigned long long), s); }
+    const unsigned long long *start() const { return words.p + in; }
+    unsigned long long *end() { return words.p + (in ^ 1); }
+    void settle() { in ^= 1; }
+};
+
 // What a query indexer (pk_query_create) holds where a counting one holds its table: every valid window is looked up in
-// the caller's tables and tallied per record.  P, hits and depth are sized with the record array and grown with it
-// (grow_with_recs).  The methods queue their work on the indexer's stream `s`.  (pk_query.hip)
+// the caller's tables and tallied per record.  Every array keyed by the records or by the rows of the tallies is sized in
+// one place (size_rows).  The methods queue their work on the indexer's stream `s`.  (pk_query.hip)
 struct QueryState {
     std::vector<const uint8_t *> tables;                    // the caller's device tables; they stay across resets
     int min = 1, max = 255;
@@ -117,29 +131,29 @@ struct QueryState {
     DevBuf<unsigned long long> Bf;
     uint64_t n_bins = 0;                                    // after finish
     // coordinates (pk_query_set_coords): per row the position of the first base of its first window and one past the last
-    // base of its last, sized and grown with hits.  pos: the position in the open record at the start of the next feed
-    // (word pos_in) and where the feed's kernels leave the one at its end (the other word); cpos: one word per chunk.
+    // base of its last, sized and grown with hits.  pos: the position in the open record, carried from feed to feed; cpos:
+    // one word per chunk.
     bool coords = false;
-    DevBuf<unsigned long long> bin_start, bin_end, pos, cpos;
-    int pos_in = 0;
+    DevBuf<unsigned long long> bin_start, bin_end, cpos;
+    Carried pos;
     // count spectra (pk_query_set_spectrum): [row][table][256], the tally of the table counts of every valid window of a
-    // row, sized, grown and zeroed with hits (ensure_spectrum); 2 KiB per row and table
+    // row, sized, grown and zeroed with hits; 2 KiB per row and table
     bool spectrum = false;
     DevBuf<unsigned long long> spec;
     // shared windows (pk_query_set_pairs; at most QUERY_MAX_TABLES tables): [row][pair], the windows of a row valid in both
-    // tables of a pair i < j, sized, grown and zeroed with hits (ensure_pairs); one table has no pair and no array
+    // tables of a pair i < j, sized, grown and zeroed with hits; one table has no pair and no array
     bool pairs = false;
     DevBuf<unsigned long long> shared;
-    // covered bases (kmer_cover.hip).  nb: the valid bases of the stream at the start of the next feed (word nb_in) and where
-    // the feed's scan leaves the number at its end (the other word); base_first: one word per chunk.
+    // covered bases (kmer_cover.hip).  nb: the valid bases of the stream, carried from feed to feed; base_first: one word per
+    // chunk.
     // cover (pk_query_set_cover): the feeds run k_query_cover where they run the lookup; cover_bits holds one bit per valid
-    // base, sized before every feed for the bytes fed by then (ensure_cover).
+    // base, sized before every feed for the bytes fed by then.
     // apply (pk_query_set_mask; no tables): the feeds patch the caller's bits (mask_bits, for mask_n_bases bases) into the
     // text; mask_out holds the last feed's patched text (mask_out_n bytes), masked[r] the selected bases of record r, sized
     // and grown with the record array.
     bool cover = false, apply = false;
-    DevBuf<unsigned long long> nb, base_first, masked;
-    int nb_in = 0;
+    DevBuf<unsigned long long> base_first, masked;
+    Carried nb;
     DevBuf<uint32_t> cover_bits, mask_bits;
     DevBuf<uint8_t> mask_out;
     uint64_t mask_n_bases = 0, mask_out_n = 0;
@@ -150,14 +164,12 @@ struct QueryState {
     double t_coords = 0, t_mask = 0;
 
     ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end, mask_begin, mask_end}) if (e) hipEventDestroy(e); }
-    int ensure_cover(uint64_t bytes, hipStream_t s);               // cover: a bit for every byte of a stream of `bytes` bytes
     uint64_t cover_words() const { return cover_bits.bytes / sizeof(uint32_t); }
     int create();                                                  // the events, and P for the record array's first capacity
     int reset(hipStream_t s);                                      // an empty stream; the tables stay; bins, coordinates, spectra and pairs are off
-    int grow_with_recs(uint64_t cap, uint64_t bytes, hipStream_t s);   // the record array now holds `cap` records; the rows follow
-    int ensure_rows(uint64_t cap, uint64_t bytes, hipStream_t s);  // binned: the rows `cap` records in `bytes` bytes can make
-    int ensure_spectrum(uint64_t cap, uint64_t bytes, hipStream_t s);   // spectra: the same rows, per record or binned
-    int ensure_pairs(uint64_t cap, uint64_t bytes, hipStream_t s);      // shared windows: the same rows, per record or binned
+    // every array of the options that are on, for a record array of `cap` records and a stream of `bytes` bytes (the feed
+    // under way included): contents kept, the rest zero; nothing but comparisons where the capacities suffice
+    int size_rows(uint64_t cap, uint64_t bytes, hipStream_t s);
     size_t n_pairs() const { return tables.size() * (tables.size() - 1) / 2; }
 };
 

@@ -158,7 +158,7 @@ static int ensure_recs(pk_indexer *ix, uint64_t need, uint64_t bytes) {
     if (need <= ix->recs_cap()) return PK_OK;
     const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, ix->recs_cap() * 2));
     int rc = ix->recs.grow_keep(cap * sizeof(DevRec), ix->stream);
-    return rc || !ix->q ? rc : ix->q->grow_with_recs(cap, bytes, ix->stream);
+    return rc || !ix->q ? rc : ix->q->size_rows(cap, bytes, ix->stream);   // what a query keys by records or rows follows
 }
 
 // one feed of at most FEED_MAX bytes: structure pass -> squeeze -> bucket layout -> fused k-mer assembly + level-1
@@ -334,9 +334,9 @@ static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     q.mask_out_n = 0;
     auto queue = [&](uint32_t raised) -> int {
         if (raised && raised != 2u) return fail(PK_ERR_HIP, "the mask feed did not settle (internal error, flag %u)", raised);
-        // a repeated attempt starts from the same base count (the words change roles once the feed has settled) and finds
-        // masked[] as the feed before left it: the attempt that backed out added nothing
-        launch_cover_scan(pl, pb, q.nb.p + q.nb_in, q.nb.p + (q.nb_in ^ 1), q.base_first.p, ix->stream);
+        // a repeated attempt starts from the same base count (Carried) and finds masked[] as the feed before left it: the
+        // attempt that backed out added nothing
+        launch_cover_scan(pl, pb, q.nb.start(), q.nb.end(), q.base_first.p, ix->stream);
         HIPCHK(hipEventRecord(q.mask_begin, ix->stream));
         launch_mask_apply(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, q.mask_bits.bytes / sizeof(uint32_t),
                           q.mask_mode, q.mask_out.p, q.masked.p, q.masked.bytes / sizeof(unsigned long long), ix->stream);
@@ -345,16 +345,16 @@ static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         return PK_OK;
     };
     if ((rc = run_feed(ix, f, n_bytes, pl, pb, "the mask feed", "masked", queue))) return rc;
-    q.nb_in ^= 1;                                            // the base count behind this feed is the next feed's start
+    q.nb.settle();                                           // the base count behind this feed is the next feed's start
     q.mask_out_n = n_bytes;
     return add_elapsed(&q.t_mask, q.mask_begin, q.mask_end);
 }
 
 // A query indexer's feed: the lookup kernels (kmer_query.hip), and with coordinates those of kmer_coords.hip, where
 // count_feed runs launch_partitioned.  There is no sampled layout, so the only flag is 2 (the squeeze backed out): the
-// record array, the window prefix and the accumulators grow (ensure_recs), and the squeeze and the lookups run again.  With
-// bins the accumulators are sized before the kernels run for the rows the stream can hold after this feed (ensure_rows), and
-// again, for the same stream, whenever the record array grows (ensure_recs).
+// record array, the window prefix and the accumulators grow (ensure_recs), and the squeeze and the lookups run again.  The
+// arrays of every option are sized before the kernels run, with bins for the rows the stream can hold after this feed, and
+// again, for the same stream, whenever the record array grows (QueryState::size_rows both times).
 static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     QueryState &q = *ix->q;
     if (q.apply) return mask_feed(ix, f, n_bytes);
@@ -367,21 +367,16 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb);
     Carry *carry = &ix->tail.p->carry;
     const uint32_t N = (uint32_t)q.tables.size();
-    if ((rc = q.ensure_rows(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
-    if ((rc = q.ensure_spectrum(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
-    if ((rc = q.ensure_pairs(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
+    if ((rc = q.size_rows(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
     if (q.coords && (rc = q.cpos.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
-    if (q.cover) {
-        if ((rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
-        if ((rc = q.ensure_cover(ix->bytes_fed + n_bytes, ix->stream))) return rc;
-    }
+    if (q.cover && (rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
     auto queue = [&](uint32_t raised) -> int {
         if (raised && raised != 2u) return fail(PK_ERR_HIP, "the query feed did not settle (internal error, flag %u)", raised);
         HIPCHK(hipEventRecord(q.lookup_begin, ix->stream));
         if (q.cover) {
             // the cover kernels where the lookup runs: no row tallies are needed.  A repeated attempt starts from the same
-            // base count: the two words change roles only once the feed has settled
-            launch_cover_scan(pl, pb, q.nb.p + q.nb_in, q.nb.p + (q.nb_in ^ 1), q.base_first.p, ix->stream);
+            // base count (Carried)
+            launch_cover_scan(pl, pb, q.nb.start(), q.nb.end(), q.base_first.p, ix->stream);
             for (uint32_t t0 = 0; t0 < N; t0 += QUERY_MAX_TABLES)
                 launch_query_cover(pl, pb, ix->c_l2s.p, q.base_first.p, q.tables.data() + t0, std::min(QUERY_MAX_TABLES, N - t0), (uint32_t)q.min,
                                    (uint32_t)q.max, q.cover_bits.p, q.cover_words(), ix->stream);
@@ -396,11 +391,11 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
                                 ix->stream);
         HIPCHK(hipEventRecord(q.lookup_end, ix->stream));
         if (q.coords) {
-            // behind launch_query_scan (slot_first, P, Bf) and on the rows ensure_rows sized; a repeated attempt starts
-            // from the same pos word: the words change roles only once the feed has settled
+            // behind launch_query_scan (slot_first, P, Bf) and on the rows size_rows sized; a repeated attempt starts
+            // from the same position (Carried)
             HIPCHK(hipEventRecord(q.coords_begin, ix->stream));
             launch_query_coords(pl, pb, qb, f, n_bytes, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, ix->recs.p, q.P.p, q.Bf.p, q.bin,
-                                q.cpos.p, q.pos.p + q.pos_in, q.pos.p + (q.pos_in ^ 1), q.bin_start.p, q.bin_end.p,
+                                q.cpos.p, q.pos.start(), q.pos.end(), q.bin_start.p, q.bin_end.p,
                                 q.bin_start.bytes / sizeof(unsigned long long), ix->stream);
             HIPCHK(hipEventRecord(q.coords_end, ix->stream));
         }
@@ -411,10 +406,10 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     q.windows = ix->pin->tail.carry.num_kmers;
     q.p_done = ix->n_recs;
     if ((rc = add_elapsed(&ix->t_part, q.lookup_begin, q.lookup_end))) return rc;
-    if (q.cover) q.nb_in ^= 1;                               // the base count behind this feed is the next feed's start
+    if (q.cover) q.nb.settle();                              // the base count behind this feed is the next feed's start
     if (!q.coords) return PK_OK;
     if ((rc = add_elapsed(&q.t_coords, q.coords_begin, q.coords_end))) return rc;
-    q.pos_in ^= 1;                                           // the position behind this feed is the next feed's start
+    q.pos.settle();                                          // the position behind this feed is the next feed's start
     return PK_OK;
 }
 

@@ -117,6 +117,12 @@ int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, 
 // like the indexer and then runs these where the indexer runs launch_partitioned.
 constexpr uint32_t QUERY_MAX_TABLES = 16;                   // tables per lookup launch; more are looked up group by group
 struct QueryTables { const uint8_t *t[QUERY_MAX_TABLES]; };
+// tables[0 .. n_tab) as a launch takes them; the slots behind them repeat the first table, so that every slot can be read
+inline QueryTables query_tables(const uint8_t *const *tables, uint32_t n_tab) {
+    QueryTables tabs;
+    for (uint32_t i = 0; i < QUERY_MAX_TABLES; i++) tabs.t[i] = tables[i < n_tab ? i : 0];
+    return tabs;
+}
 struct QueryBuffers {
     uint32_t *slot_count;                                   // valid windows per slot
     unsigned long long *slot_first;                         // stream ordinal of a slot's first valid window

@@ -25,8 +25,8 @@ from . import _lib
 from .indexer import _Input, _mark, input_format, qual_threshold
 from .merger import DEFAULT_THREADS
 from .output import atomic_write, write_json
-from .query import _qual_keys, load_header, query_records, validate
-from .tables import lean_headers, table_entry
+from .query import _qual_keys, as_headers, query_records, refuse_files, verified_tables
+from .tables import lean_headers
 
 PAIR_RULES = ("any", "both")
 
@@ -143,7 +143,7 @@ def filter_records(query_file: str, tables: Sequence, min_count: int = 1, max_co
     if mate is not None and input_format(str(mate)) != input_format(str(query_file)):
         raise ValueError(f"the two files of a pair must have one format: {query_file} and {mate}")
     select = select or select_records
-    tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
+    tables = as_headers(tables, device)
     qual = {"min_qual": min_qual, "qual_offset": qual_offset} if min_qual else {}
 
     def phase1(path):
@@ -197,16 +197,8 @@ def filter(project_name: str, query_file: str, indexes: List[Path], min_count: i
     validate_rule(min_hits, min_percent, min_tables, len(indexes))
     kmf, meta = kmf_paths(project_name)
     seq_paths = output_paths(project_name, query_file, mate, rest)
-    for f in [kmf, meta] + list(seq_paths.values()):
-        if f.exists():
-            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
-    for f in [query_file] + ([mate] if mate is not None else []):
-        if not os.path.exists(f):
-            raise ValueError(f"query file does not exist: {f}")
-    data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
-    headers = [v["header"] for v in data]
-    validate(headers, min_count, max_count)
-    _mark("tables verified")
+    refuse_files([kmf, meta] + list(seq_paths.values()), [query_file] + ([mate] if mate is not None else []))
+    data, headers = verified_tables(indexes, min_count, max_count, device)
     extra = {"min_qual": min_qual, "qual_offset": 33 if qual_offset is None else qual_offset} if min_qual else {}
     result = filter_records(query_file, headers, min_count, max_count, min_hits, min_percent, min_tables, invert=invert, mate=mate,
                             pair_rule=pair_rule, project_name=project_name, rest=rest, device=device, hbm_budget=hbm_budget, threads=threads,

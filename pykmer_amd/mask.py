@@ -20,12 +20,12 @@ from typing import List, Sequence
 
 import numpy as np
 
-from . import _lib, staging
+from . import _lib
 from .indexer import _Input, _mark, input_format
 from .merger import DEFAULT_THREADS
 from .output import atomic_write, write_json
-from .query import WORKSPACE_RESERVE, load_header, stage_tables, table_groups, validate
-from .tables import lean_headers, table_entry
+from .query import as_headers, plan_groups, refuse_files, stage_tables, stream_groups, validate, verified_tables
+from .tables import lean_headers
 
 APPLY_FEED = 64 << 20               # phase 2 feeds at most this much at a time: one piece of the library's, handed back whole
 
@@ -66,33 +66,21 @@ def cover_bits(query_file: str, tables: Sequence, min_count: int = 1, max_count:
     one.  `stage(tables, device)` and `run(query_file, kmer_len, ptrs, min_count, max_count, device, first)` default to
     query.stage_tables and run_cover (the CPU-only tests substitute both)."""
     check_fasta(query_file)
-    tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
+    tables = as_headers(tables, device)
     kmer_len = validate(tables, min_count, max_count)
-    stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
-    run = run or run_cover
-    if all(hasattr(t, "device_slice") for t in tables):
-        groups = [(0, len(tables))]                          # resident already: nothing to fit
-    else:
-        groups = table_groups(len(tables), 4 ** kmer_len, staging.hbm_budget(device, hbm_budget, workspace=WORKSPACE_RESERVE))
-    result, lookup_s = None, 0.0
-    for g, (lo, hi) in enumerate(groups):
-        staged = stage(tables[lo:hi], device)
-        _mark(f"tables {lo}..{hi - 1} staged")
-        try:
-            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0)
-        finally:
-            staged.free()
-        _mark(f"query streamed against tables {lo}..{hi - 1}")
-        lookup_s += float(part.get("timings", {}).get("lookup_s", 0.0))
+
+    def join(result, part):
+        """A later group's bits OR-ed into those of the groups before; the first group's part, its bits copied, is the result."""
         if result is None:
-            result = part
-            result["cover"] = np.array(part["cover"], dtype=np.uint8)
-        else:
-            assert part["n_bases"] == result["n_bases"] and np.array_equal(part["n_valid"], result["n_valid"]) \
-                and np.array_equal(part["seq_len"], result["seq_len"]), "query changed between table groups"
-            result["cover"] |= np.asarray(part["cover"], dtype=np.uint8)
+            part["cover"] = np.array(part["cover"], dtype=np.uint8)
+            return part
+        assert part["n_bases"] == result["n_bases"], "query changed between table groups"
+        result["cover"] |= np.asarray(part["cover"], dtype=np.uint8)
+        return result
+
+    result = stream_groups(query_file, tables, kmer_len, plan_groups(tables, kmer_len, device, hbm_budget), min_count, max_count, run or run_cover,
+                           join, device, threads, stage or (lambda group, dev: stage_tables(group, dev, threads)))
     assert result["cover"].shape == ((result["n_bases"] + 7) // 8,)
-    result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
     return result
 
 
@@ -165,15 +153,8 @@ def mask(project_name: str, query_file: str, indexes: List[Path], min_count: int
     if len(indexes) < 1:
         raise ValueError("a mask needs at least one table")
     out_file, kmm, meta = kmm_paths(project_name)
-    for f in (out_file, kmm, meta):
-        if f.exists():
-            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
-    if not os.path.exists(query_file):
-        raise ValueError(f"query file does not exist: {query_file}")
-    data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
-    headers = [v["header"] for v in data]
-    validate(headers, min_count, max_count)
-    _mark("tables verified")
+    refuse_files((out_file, kmm, meta), [query_file])
+    data, headers = verified_tables(indexes, min_count, max_count, device)
     result = mask_records(query_file, headers, min_count, max_count, hard=hard, invert=invert, project_name=project_name, device=device,
                           hbm_budget=hbm_budget, threads=threads, stage=stage, run=run, apply=apply)
     lean_headers(data)

@@ -132,6 +132,51 @@ def stage_tables(tables: Sequence, device: int, threads: int = DEFAULT_THREADS) 
     return Staged(ptrs, [_Piece(pieces)])
 
 
+def as_headers(tables: Sequence, device: int = 0) -> list:
+    """`tables` with every `.kin[.bgz]` path turned into its Header; Headers and resident tables stay as they are."""
+    return [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
+
+
+def set_options(bin_windows=None, coords=False, spectrum=False, pairs=False, **more) -> dict:
+    """The option keywords that query, query_records and `run` hand on: only those that are set (`more`: the caller's own)."""
+    given = {} if bin_windows is None else {"bin_windows": bin_windows}
+    given.update({name: True for name, on in (("coords", coords), ("spectrum", spectrum), ("pairs", pairs)) if on})
+    return {**given, **more}
+
+
+def plan_groups(tables: Sequence, kmer_len: int, device: int = 0, hbm_budget: int = None) -> List[Tuple[int, int]]:
+    """The [lo, hi) ranges of `tables` staged together: one group when they are resident, else what the HBM budget holds
+    beside the feed's workspace (table_groups)."""
+    if all(hasattr(t, "device_slice") for t in tables):
+        return [(0, len(tables))]                            # resident already: nothing to fit
+    return table_groups(len(tables), 4 ** kmer_len, staging.hbm_budget(device, hbm_budget, workspace=WORKSPACE_RESERVE))
+
+
+def stream_groups(query_file: str, tables: Sequence, kmer_len: int, groups, min_count: int, max_count: int, run, join, device: int = 0,
+                  threads: int = DEFAULT_THREADS, stage=None, **extra) -> dict:
+    """The group loop of every tool that streams a query against staged tables: per group of `groups` (plan_groups) stage,
+    `run(query_file, kmer_len, ptrs, min_count, max_count, device, first, **extra)`, free.  `join(result, part)` -> result says
+    how a group's part joins the result of the groups before (None for the first group); the records of a later part must be
+    those of the first.  The result gains kmer_len, min_count, max_count, n_groups and lookup_s, the sum over the groups.
+    `stage(tables, device)` -> Staged defaults to stage_tables."""
+    stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
+    result, lookup_s = None, 0.0
+    for g, (lo, hi) in enumerate(groups):
+        staged = stage(tables[lo:hi], device)
+        _mark(f"tables {lo}..{hi - 1} staged")
+        try:
+            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0, **extra)
+        finally:
+            staged.free()
+        _mark(f"query streamed against tables {lo}..{hi - 1}")
+        lookup_s += float(part.get("timings", {}).get("lookup_s", 0.0))
+        assert result is None or (np.array_equal(part["n_valid"], result["n_valid"]) and np.array_equal(part["seq_len"], result["seq_len"])), \
+            "query changed between table groups"
+        result = join(result, part)
+    result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
+    return result
+
+
 def run_query(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: int, device: int = 0, first: bool = True,
               bin_windows: int = None, coords: bool = False, min_qual_byte: int = 0, spectrum: bool = False, pairs: bool = False) -> dict:
     """Streams the query once against the staged tables `ptrs`.  `first`: also fetch the record names (later groups of the
@@ -226,55 +271,35 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
         raise ValueError("coordinates are those of bins: coords needs bin_windows (--coords needs --bin W)")
-    extra = {} if bin_windows is None else {"bin_windows": bin_windows}
-    if coords:
-        extra["coords"] = True
-    if spectrum:
-        extra["spectrum"] = True
-    if pairs:
-        extra["pairs"] = True
-    if min_qual:
-        extra["min_qual_byte"] = qual_threshold(str(query_file), min_qual, qual_offset)
-    tables = [load_header(t, device) if isinstance(t, (str, os.PathLike)) else t for t in tables]
+    extra = set_options(bin_windows, coords, spectrum, pairs,
+                        **({"min_qual_byte": qual_threshold(str(query_file), min_qual, qual_offset)} if min_qual else {}))
+    tables = as_headers(tables, device)
     kmer_len = validate(tables, min_count, max_count)
     if pairs and len(tables) > MAX_PAIR_TABLES:
         raise ValueError(f"pairs take at most {MAX_PAIR_TABLES} tables, all in one lookup; got {len(tables)}")
-    stage = stage or (lambda group, dev: stage_tables(group, dev, threads))
-    run = run or run_query
-    if all(hasattr(t, "device_slice") for t in tables):
-        groups = [(0, len(tables))]                          # resident already: nothing to fit
-    else:
-        groups = table_groups(len(tables), 4 ** kmer_len, staging.hbm_budget(device, hbm_budget, workspace=WORKSPACE_RESERVE))
+    groups = plan_groups(tables, kmer_len, device, hbm_budget)
     if pairs and len(groups) > 1:
         raise ValueError(f"pairs need all {len(tables)} tables of {4 ** kmer_len:,d} bytes staged together, and the HBM budget holds "
                          f"{groups[0][1]} at a time: take fewer tables or a larger budget (PK_MERGE_HBM_BUDGET)")
-    result, lookup_s, coords_s = None, 0.0, 0.0
-    for g, (lo, hi) in enumerate(groups):
-        staged = stage(tables[lo:hi], device)
-        _mark(f"tables {lo}..{hi - 1} staged")
-        try:
-            part = run(query_file, kmer_len, staged.ptrs, min_count, max_count, device, g == 0, **extra)
-        finally:
-            staged.free()
-        _mark(f"query streamed against tables {lo}..{hi - 1}")
-        lookup_s += float(part.get("timings", {}).get("lookup_s", 0.0))
-        if coords and g == 0:
-            coords_s = float(part.get("timings", {}).get("coords_s", 0.0))
-            _mark(f"coordinate kernels: {coords_s:.6f} s of HIP-event time (lookup kernels: {lookup_s:.6f} s)")
+    binned = bin_windows is not None
+    columns = ["hits", "depth"] + (["bin_hits", "bin_depth"] if binned else []) + ((["spectrum", "bin_spectrum"] if binned else ["spectrum"]) if spectrum else [])
+    coords_s = 0.0
+
+    def join(result, part):
+        """A later group's columns behind those of the groups before; the first group's part is the result."""
+        nonlocal coords_s
         if result is None:
-            result = part
-        else:
-            assert np.array_equal(part["n_valid"], result["n_valid"]) and np.array_equal(part["seq_len"], result["seq_len"]), \
-                "query changed between table groups"
-            result["hits"] = np.concatenate([result["hits"], part["hits"]], axis=1)
-            result["depth"] = np.concatenate([result["depth"], part["depth"]], axis=1)
-            if bin_windows is not None:
-                assert np.array_equal(part["bin_first"], result["bin_first"]), "bins changed between table groups"
-                result["bin_hits"] = np.concatenate([result["bin_hits"], part["bin_hits"]], axis=1)
-                result["bin_depth"] = np.concatenate([result["bin_depth"], part["bin_depth"]], axis=1)
-            for key in ("spectrum", "bin_spectrum") if spectrum else ():
-                if key in result:
-                    result[key] = np.concatenate([result[key], part[key]], axis=1)
+            if coords:
+                coords_s, lookup_s = (float(part.get("timings", {}).get(key, 0.0)) for key in ("coords_s", "lookup_s"))
+                _mark(f"coordinate kernels: {coords_s:.6f} s of HIP-event time (lookup kernels: {lookup_s:.6f} s)")
+            return part
+        if binned:
+            assert np.array_equal(part["bin_first"], result["bin_first"]), "bins changed between table groups"
+        for key in columns:
+            result[key] = np.concatenate([result[key], part[key]], axis=1)
+        return result
+
+    result = stream_groups(query_file, tables, kmer_len, groups, min_count, max_count, run or run_query, join, device, threads, stage, **extra)
     if bin_windows is not None:
         result["bin_windows"] = bin_windows
     if spectrum:
@@ -288,7 +313,6 @@ def query_records(query_file: str, tables: Sequence, min_count: int = 1, max_cou
     if coords:
         assert result["bin_start"].shape == result["bin_end"].shape == (int(result["bin_first"][-1]),)
         result["coords_s"] = coords_s
-    result.update(kmer_len=kmer_len, min_count=min_count, max_count=max_count, n_groups=len(groups), lookup_s=lookup_s)
     if min_qual:
         result.update(min_qual=int(min_qual), qual_offset=int(qual_offset))
     return result
@@ -299,30 +323,70 @@ def _qual_keys(result: dict) -> dict:
     return {"min_qual": int(result["min_qual"]), "qual_offset": int(result["qual_offset"])} if result.get("min_qual") else {}
 
 
+def _write_rows(paths, project_name: str, result: dict, query_file: str, data: list, heads: List[str], cells: str, values: dict,
+                binned: bool, coords: bool = False, window: bool = True, json_more: dict = None, npz_more: dict = None) -> None:
+    """The three files of one kind of row values, `paths` = (npz, json, tsv), each through `.tmp` + rename, in that order
+    json, tsv, npz.  `values`: npz name -> (array, dtype, shape of one row); the rows are the records, `binned` the bins of
+    result["bin_first"].  The tsv has the leading columns record, seq_len, n_valid (binned: record, bin, first_window,
+    n_windows, and with `coords` and a result that holds them start, end), then under `heads` the row of values[cells].
+    The json has the common keys (`window`: the count window among them), binned bin_windows and n_bins, "coords" with the
+    coordinates, `json_more` and _qual_keys; the npz the values, n_valid, seq_len, kmer_len, the count window, binned
+    bin_first and bin_windows, the coordinates, and `npz_more`."""
+    npz, meta, tsv = paths
+    n_valid, seq_len = (np.ascontiguousarray(result[key], dtype=np.uint64) for key in ("n_valid", "seq_len"))
+    names = [n.strip() for n in result["names"]]
+    assert n_valid.shape == seq_len.shape == (len(names),)
+    counts = {"min_count": int(result["min_count"]), "max_count": int(result["max_count"])} if window else {}
+    arrays, more, span, rows = {}, {}, {}, len(names)
+    if binned:
+        W = int(result["bin_windows"])
+        bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
+        assert bin_first.shape == (len(names) + 1,)
+        rows = int(bin_first[-1])
+        arrays = {"bin_first": bin_first, "bin_windows": np.uint64(W)}
+        more = {"bin_windows": W, "n_bins": rows}
+        if coords and "bin_start" in result:
+            span = {key: np.ascontiguousarray(result[key], dtype=np.uint64) for key in ("bin_start", "bin_end")}
+            assert span["bin_start"].shape == span["bin_end"].shape == (rows,)
+            more["coords"] = True
+    shapes = {name: (rows,) + tuple(shape) for name, (_, _, shape) in values.items()}
+    values = {name: np.ascontiguousarray(a, dtype=dtype) for name, (a, dtype, _) in values.items()}
+    assert all(values[name].shape == shapes[name] for name in values)
+
+    def leads():
+        """(row, its leading columns), in row order"""
+        for r, name in enumerate(names):
+            if not binned:
+                yield r, [name, str(int(seq_len[r])), str(int(n_valid[r]))]
+                continue
+            m = int(n_valid[r])
+            for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
+                at = int(bin_first[r]) + b
+                yield at, [name, str(b), str(b * W), str(min(W, m - b * W))] + [str(int(span[key][at])) for key in span]
+
+    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), **counts, "query_file": str(query_file), "records": names,
+              "data": data, **more, **(json_more or {})}
+    output.update(_qual_keys(result))
+    write_json(meta, output)
+    with atomic_write(tsv, "wt") as fhd:
+        lead = ["record", "bin", "first_window", "n_windows"] + (["start", "end"] if span else []) if binned else ["record", "seq_len", "n_valid"]
+        fhd.write("\t".join(lead + [str(h) for h in heads]) + "\n")
+        for at, lead in leads():
+            fhd.write("\t".join(lead + [str(int(v)) for v in values[cells][at]]) + "\n")
+    with atomic_write(npz, "wb") as fhd:
+        np.savez_compressed(fhd, **values, **(npz_more or {}), n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
+                            **{key: np.int64(v) for key, v in counts.items()}, **arrays, **span)
+
+
 def kmq_paths(project_name: str) -> Tuple[Path, Path, Path]:
     return Path(f"{project_name}.kmq"), Path(f"{project_name}.kmq.json"), Path(f"{project_name}.kmq.tsv")
 
 
 def write_kmq(project_name: str, result: dict, query_file: str, data: list, columns: List[str]) -> None:
     """`<project>.kmq` (np.savez_compressed), `.kmq.json` and `.kmq.tsv`, each through `.tmp` + rename."""
-    kmq, meta, tsv = kmq_paths(project_name)
-    hits = np.ascontiguousarray(result["hits"], dtype=np.uint64)
-    depth = np.ascontiguousarray(result["depth"], dtype=np.uint64)
-    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
-    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
-    names = [n.strip() for n in result["names"]]
-    assert hits.shape == depth.shape == (len(names), len(columns)) and n_valid.shape == seq_len.shape == (len(names),)
-    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
-              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data}
-    output.update(_qual_keys(result))
-    write_json(meta, output)
-    with atomic_write(tsv, "wt") as fhd:
-        fhd.write("\t".join(["record", "seq_len", "n_valid"] + [str(c) for c in columns]) + "\n")
-        for r, name in enumerate(names):
-            fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in hits[r]]) + "\n")
-    with atomic_write(kmq, "wb") as fhd:
-        np.savez_compressed(fhd, hits=hits, depth=depth, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
-                            min_count=np.int64(result["min_count"]), max_count=np.int64(result["max_count"]))
+    row = (len(columns),)
+    _write_rows(kmq_paths(project_name), project_name, result, query_file, data, columns, "hits",
+                {"hits": (result["hits"], np.uint64, row), "depth": (result["depth"], np.uint64, row)}, binned=False)
 
 
 def kmb_paths(project_name: str) -> Tuple[Path, Path, Path]:
@@ -333,41 +397,9 @@ def write_kmb(project_name: str, result: dict, query_file: str, data: list, colu
     """`<project>.kmb` (np.savez_compressed), `.kmb.json` and `.kmb.tsv`: the binned rows, each file through `.tmp` + rename.
     A result with bin_start / bin_end (coords) adds them to the `.kmb`, `"coords": true` to the json and the columns
     `start` and `end` to the tsv; without them the files hold none of the three."""
-    kmb, meta, tsv = kmb_paths(project_name)
-    W = int(result["bin_windows"])
-    hits = np.ascontiguousarray(result["bin_hits"], dtype=np.uint64)
-    depth = np.ascontiguousarray(result["bin_depth"], dtype=np.uint64)
-    bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
-    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
-    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
-    names = [n.strip() for n in result["names"]]
-    B = int(bin_first[-1])
-    assert hits.shape == depth.shape == (B, len(columns)) and bin_first.shape == (len(names) + 1,)
-    assert n_valid.shape == seq_len.shape == (len(names),)
-    coords = {}
-    if "bin_start" in result:
-        coords = {"bin_start": np.ascontiguousarray(result["bin_start"], dtype=np.uint64),
-                  "bin_end": np.ascontiguousarray(result["bin_end"], dtype=np.uint64)}
-        assert coords["bin_start"].shape == coords["bin_end"].shape == (B,)
-    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
-              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data,
-              "bin_windows": W, "n_bins": B}
-    if coords:
-        output["coords"] = True
-    output.update(_qual_keys(result))
-    write_json(meta, output)
-    with atomic_write(tsv, "wt") as fhd:
-        fhd.write("\t".join(["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) + [str(c) for c in columns]) + "\n")
-        for r, name in enumerate(names):
-            m = int(n_valid[r])
-            for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
-                at = int(bin_first[r]) + b
-                span = [str(int(coords["bin_start"][at])), str(int(coords["bin_end"][at]))] if coords else []
-                fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + span + [str(int(v)) for v in hits[at]]) + "\n")
-    with atomic_write(kmb, "wb") as fhd:
-        np.savez_compressed(fhd, hits=hits, depth=depth, bin_first=bin_first, n_valid=n_valid, seq_len=seq_len, bin_windows=np.uint64(W),
-                            kmer_len=np.int64(result["kmer_len"]), min_count=np.int64(result["min_count"]),
-                            max_count=np.int64(result["max_count"]), **coords)
+    row = (len(columns),)
+    _write_rows(kmb_paths(project_name), project_name, result, query_file, data, columns, "hits",
+                {"hits": (result["bin_hits"], np.uint64, row), "depth": (result["bin_depth"], np.uint64, row)}, binned=True, coords=True)
 
 
 def kmh_paths(project_name: str) -> Tuple[Path, Path, Path]:
@@ -381,41 +413,13 @@ def write_kmh(project_name: str, result: dict, query_file: str, data: list, colu
     `.kmq.json` but the count window, which the spectra do not depend on; the tsv has the leading columns of the `.kmq.tsv`
     (binned: of the `.kmb.tsv`, without coordinates) and every table's median count."""
     from .qspectrum import median_from_spectrum
-    kmh, meta, tsv = kmh_paths(project_name)
     binned = "bin_spectrum" in result
     spec = np.ascontiguousarray(result["bin_spectrum" if binned else "spectrum"], dtype=np.uint64)
     key = "bin_median" if binned else "median"
-    median = np.ascontiguousarray(result[key], dtype=np.uint8) if key in result else median_from_spectrum(spec)
-    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
-    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
-    names = [n.strip() for n in result["names"]]
-    assert n_valid.shape == seq_len.shape == (len(names),)
-    arrays, more = {}, {}
-    if binned:
-        W = int(result["bin_windows"])
-        bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
-        assert bin_first.shape == (len(names) + 1,)
-        rows = int(bin_first[-1])
-        arrays = {"bin_first": bin_first, "bin_windows": np.uint64(W)}
-        more = {"bin_windows": W, "n_bins": rows}
-    else:
-        rows = len(names)
-    assert spec.shape == (rows, len(columns), 256) and median.shape == (rows, len(columns))
-    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "query_file": str(query_file), "records": names, "data": data, **more}
-    output.update(_qual_keys(result))
-    write_json(meta, output)
-    with atomic_write(tsv, "wt") as fhd:
-        fhd.write("\t".join((["record", "bin", "first_window", "n_windows"] if binned else ["record", "seq_len", "n_valid"]) + [str(c) for c in columns]) + "\n")
-        for r, name in enumerate(names):
-            if binned:
-                m = int(n_valid[r])
-                for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
-                    at = int(bin_first[r]) + b
-                    fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + [str(int(v)) for v in median[at]]) + "\n")
-            else:
-                fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in median[r]]) + "\n")
-    with atomic_write(kmh, "wb") as fhd:
-        np.savez_compressed(fhd, spectrum=spec, median=median, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]), **arrays)
+    median = result[key] if key in result else median_from_spectrum(spec)
+    N = len(columns)
+    _write_rows(kmh_paths(project_name), project_name, result, query_file, data, columns, "median",
+                {"spectrum": (spec, np.uint64, (N, 256)), "median": (median, np.uint8, (N,))}, binned=binned, window=False)
 
 
 def kmp_paths(project_name: str) -> Tuple[Path, Path, Path]:
@@ -429,52 +433,33 @@ def write_kmp(project_name: str, result: dict, query_file: str, data: list, colu
     "coords", the columns start and end).  The `.kmp` holds the rows' hits next to `shared`: a row's matrix needs no other
     file (pykmer_amd.qpairs).  The json has the keys of the `.kmq.json` and n_pairs; the tsv has the leading columns of the
     `.kmq.tsv` (binned: of the `.kmb.tsv`), then one column `<name_i>|<name_j>` per pair."""
-    kmp, meta, tsv = kmp_paths(project_name)
     binned = "bin_shared" in result
-    shared = np.ascontiguousarray(result["bin_shared" if binned else "shared"], dtype=np.uint64)
-    hits = np.ascontiguousarray(result["bin_hits" if binned else "hits"], dtype=np.uint64)
     pairs = np.ascontiguousarray(result["pairs"], dtype=np.int32).reshape(-1, 2)
-    n_valid = np.ascontiguousarray(result["n_valid"], dtype=np.uint64)
-    seq_len = np.ascontiguousarray(result["seq_len"], dtype=np.uint64)
-    names = [n.strip() for n in result["names"]]
-    assert n_valid.shape == seq_len.shape == (len(names),)
-    arrays, more, coords = {}, {}, {}
-    if binned:
-        W = int(result["bin_windows"])
-        bin_first = np.ascontiguousarray(result["bin_first"], dtype=np.uint64)
-        assert bin_first.shape == (len(names) + 1,)
-        rows = int(bin_first[-1])
-        arrays = {"bin_first": bin_first, "bin_windows": np.uint64(W)}
-        more = {"bin_windows": W, "n_bins": rows}
-        if "bin_start" in result:
-            coords = {"bin_start": np.ascontiguousarray(result["bin_start"], dtype=np.uint64),
-                      "bin_end": np.ascontiguousarray(result["bin_end"], dtype=np.uint64)}
-            assert coords["bin_start"].shape == coords["bin_end"].shape == (rows,)
-            more["coords"] = True
-    else:
-        rows = len(names)
     N = len(columns)
-    assert hits.shape == (rows, N) and pairs.shape == (N * (N - 1) // 2, 2) and shared.shape == (rows, len(pairs))
-    output = {"project_name": project_name, "kmer_len": int(result["kmer_len"]), "min_count": int(result["min_count"]),
-              "max_count": int(result["max_count"]), "query_file": str(query_file), "records": names, "data": data, "n_pairs": len(pairs), **more}
-    output.update(_qual_keys(result))
-    write_json(meta, output)
-    heads = [f"{columns[i]}|{columns[j]}" for i, j in pairs]
-    with atomic_write(tsv, "wt") as fhd:
-        lead = ["record", "bin", "first_window", "n_windows"] + (["start", "end"] if coords else []) if binned else ["record", "seq_len", "n_valid"]
-        fhd.write("\t".join(lead + heads) + "\n")
-        for r, name in enumerate(names):
-            if binned:
-                m = int(n_valid[r])
-                for b in range(int(bin_first[r + 1]) - int(bin_first[r])):
-                    at = int(bin_first[r]) + b
-                    span = [str(int(coords["bin_start"][at])), str(int(coords["bin_end"][at]))] if coords else []
-                    fhd.write("\t".join([name, str(b), str(b * W), str(min(W, m - b * W))] + span + [str(int(v)) for v in shared[at]]) + "\n")
-            else:
-                fhd.write("\t".join([name, str(int(seq_len[r])), str(int(n_valid[r]))] + [str(int(v)) for v in shared[r]]) + "\n")
-    with atomic_write(kmp, "wb") as fhd:
-        np.savez_compressed(fhd, shared=shared, hits=hits, pairs=pairs, n_valid=n_valid, seq_len=seq_len, kmer_len=np.int64(result["kmer_len"]),
-                            min_count=np.int64(result["min_count"]), max_count=np.int64(result["max_count"]), **arrays, **coords)
+    assert pairs.shape == (N * (N - 1) // 2, 2)
+    _write_rows(kmp_paths(project_name), project_name, result, query_file, data, [f"{columns[i]}|{columns[j]}" for i, j in pairs], "shared",
+                {"shared": (result["bin_shared" if binned else "shared"], np.uint64, (len(pairs),)),
+                 "hits": (result["bin_hits" if binned else "hits"], np.uint64, (N,))},
+                binned=binned, coords=True, json_more={"n_pairs": len(pairs)}, npz_more={"pairs": pairs})
+
+
+def refuse_files(outputs: Sequence[Path], inputs: Sequence) -> None:
+    """How query, filter and mask open, behind their own checks: no output is overwritten, and every input is there."""
+    for f in outputs:
+        if f.exists():
+            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
+    for f in inputs:
+        if not os.path.exists(f):
+            raise ValueError(f"query file does not exist: {f}")
+
+
+def verified_tables(indexes: Sequence, min_count: int, max_count: int, device: int = 0) -> Tuple[list, list]:
+    """... and then: the `data` entries of the tables `indexes` (tables.table_entry) and their Headers, validated."""
+    data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
+    headers = [v["header"] for v in data]
+    validate(headers, min_count, max_count)
+    _mark("tables verified")
+    return data, headers
 
 
 def query(project_name: str, query_file: str, indexes: List[Path], min_count: int = 1, max_count: int = 255, device: int = 0,
@@ -493,29 +478,15 @@ def query(project_name: str, query_file: str, indexes: List[Path], min_count: in
         bin_windows = validate_bins(bin_windows)
     if coords and bin_windows is None:
         raise ValueError("--coords gives the coordinates of bins: it needs --bin W")
-    extra = {} if bin_windows is None else {"bin_windows": bin_windows}
-    if coords:
-        extra["coords"] = True
-    if min_qual:
-        extra.update(min_qual=min_qual, qual_offset=33 if qual_offset is None else qual_offset)
-    if spectrum:
-        extra["spectrum"] = True
-    if pairs:
-        extra["pairs"] = True
-    for f in kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()) + (kmh_paths(project_name) if spectrum else ()) \
-            + (kmp_paths(project_name) if pairs else ()):
-        if f.exists():
-            raise ValueError(f"project output file ({f}) already exists. not overwriting.")
-    if not os.path.exists(query_file):
-        raise ValueError(f"query file does not exist: {query_file}")
+    extra = set_options(bin_windows, coords, spectrum, pairs,
+                        **({"min_qual": min_qual, "qual_offset": 33 if qual_offset is None else qual_offset} if min_qual else {}))
+    refuse_files(kmq_paths(project_name) + (kmb_paths(project_name) if bin_windows is not None else ()) + (kmh_paths(project_name) if spectrum else ())
+                 + (kmp_paths(project_name) if pairs else ()), [query_file])
     if len(indexes) < 1:
         raise ValueError("a query needs at least one table")
     if pairs and len(indexes) > MAX_PAIR_TABLES:
         raise ValueError(f"--pairs takes at most {MAX_PAIR_TABLES} tables, all in one lookup; got {len(indexes)}")
-    data = [table_entry(pos, kin, lambda kin: load_header(kin, device)) for pos, kin in enumerate(indexes)]
-    headers = [v["header"] for v in data]
-    validate(headers, min_count, max_count)
-    _mark("tables verified")
+    data, headers = verified_tables(indexes, min_count, max_count, device)
     try:
         result = query_records(query_file, headers, min_count, max_count, device=device, hbm_budget=hbm_budget, threads=threads,
                                **extra)
@@ -568,10 +539,10 @@ def main(argv: List[str] = None) -> None:
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     try:
         result = query(args.Project_Name, args.Query, args.Kmer_N, min_count=args.min_count, max_count=args.max_count,
-                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads, bin_windows=args.bin_windows,
-                       **({"coords": True} if args.coords else {}), **({"spectrum": True} if args.spectrum else {}),
-                       **({"pairs": True} if args.pairs else {}),
-                       **({"min_qual": args.min_qual, "qual_offset": args.qual_offset} if args.min_qual is not None or args.qual_offset is not None else {}))
+                       device=int(os.environ.get("PK_DEVICE", "0")), threads=args.threads,
+                       **set_options(args.bin_windows, args.coords, args.spectrum, args.pairs,
+                                     **({"min_qual": args.min_qual, "qual_offset": args.qual_offset}
+                                        if args.min_qual is not None or args.qual_offset is not None else {})))
     except ValueError as exc:
         print(f"error: {exc}", file=sys.stderr)
         sys.exit(1)

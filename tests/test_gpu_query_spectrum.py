@@ -229,6 +229,20 @@ def test_feeds_cut_anywhere_and_reset(gpu):
         assert np.array_equal(hits, ref.window(want_seams["spectrum"], 2, 255)[0])
 
 
+def test_binned_feeds_grow_the_records_and_the_rows_over_live_spectra(gpu):
+    """Bins of 4 windows with the spectra on, in two feeds: cut at byte 5000 the record array grows inside the second feed,
+    cut at record 5000 inside both, and every time the rows of hits, depth and the spectra move with live contents."""
+    reads, tables = _reads_text(K), _tables(K, 3, 843)
+    want = ref.expected(reads, K, tables, 4)
+    at = reads.index(b">r5000\n")
+    assert 3 * reads[:5000].count(b">") + 1024 <= 4096 < reads[:at].count(b">") == 5000
+    assert int(want["bin_first"][-1]) > 5000 // 4 + 4096 + 1                 # more rows than the first feed was sized for
+    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+        q.set_tables(dev.ptrs, 2, 255)
+        for cut in (5000, at):
+            _checked(q, reads, (2, 255), want, W=4, cuts=[cut], bins_last=cut == at)
+
+
 # ------------------------------------------------------------------ 7. one table, seventeen --------
 def test_one_table_and_seventeen(gpu):
     """N = 17: the lookup runs once for 16 tables and once for the last; column t is the run against table t alone."""
