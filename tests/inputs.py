@@ -565,3 +565,37 @@ def deep_k21_fasta(seed: int = 2121, body_bp: int = 300_000):
 
 def sha256(data) -> str:
     return hashlib.sha256(data).hexdigest()
+
+
+# ------------------------------------------------------------------ feeds that overflow the record array
+RECS_INITIAL = 4096                                          # pk_indexer_create_slice: record slots of a fresh indexer
+
+
+def record_overflows(lengths, record_starts):
+    """Which of the feeds (byte lengths, in order; 0 = an empty feed, which never reaches the pipeline) bring more records
+    than the record array holds when they arrive -- the capacity rule of pk_indexer.hip (ensure_recs, run_feed: after every
+    feed room for as many records again as it brought, times two, + 1024).  `record_starts`: offset of every record's '>'."""
+    import numpy as np
+    starts = np.sort(np.asarray(record_starts, dtype=np.int64))
+    cap, n, end, out = RECS_INITIAL, 0, 0, []
+
+    def grown(cap, need):
+        return cap if need <= cap else max(need, max(1024, 2 * cap))
+
+    for length in lengths:
+        if length == 0:
+            out.append(False)
+            continue
+        end += length
+        n_after = int(np.searchsorted(starts, end))
+        out.append(n_after > cap)
+        cap = grown(cap, n_after)
+        cap = grown(cap, n_after + 2 * (n_after - n) + 1024)
+        n = n_after
+    return out
+
+
+def record_starts(records):
+    """The offset of every record's '>' from the records of a count."""
+    import numpy as np
+    return records["name_off"].astype(np.int64) - 1

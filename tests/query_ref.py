@@ -136,6 +136,33 @@ COUNT_WINDOWS = ((1, 255), (2, 254), (255, 255))
 TANDEM_COPIES = 260                                          # > 255: every k-mer inside a tandem repeat is counted to the clip
 
 
+def seam_text(k: int) -> bytes:
+    """One record of 100 000 bases, line width 60 (seven 16 KiB chunks), an N within k-1 bases on either side of two chunk
+    boundaries."""
+    rng = np.random.default_rng(200 + k)
+    seq = bytearray(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 100_000)].tobytes())
+    head = b">seams one record\n"
+    def base_at(byte):                                       # index of the base at (or just before) a byte offset of the text
+        body = byte - len(head)
+        return body - body // 61                             # 60 bases + '\n' per line
+    for boundary, delta in ((2 * CHUNK, -(k - 2)), (2 * CHUNK, 1), (5 * CHUNK, -1), (5 * CHUNK, k - 2)):
+        seq[base_at(boundary) + delta] = ord("N")
+    body = b"".join(bytes(seq[i:i + 60]) + b"\n" for i in range(0, len(seq), 60))
+    return head + body
+
+
+def reads_text(k: int, n_reads: int = 6000, seed: int = 31) -> bytes:
+    """`>rN\\n<bases>\\n` per read, lengths 0, 1, k-1, k, k+1, 40 ... mixed: many records per 64-byte piece and per chunk."""
+    rng = np.random.default_rng(seed)
+    lens = np.array([0, 1, k - 1, k, k + 1, 40, 2, 13, 64, 150])[rng.integers(0, 10, n_reads)]
+    lens[:12] = [0, 0, 1, k - 1, k, k + 1, 40, 0, k, 0, 0, 1]
+    alphabet = np.frombuffer(b"ACGTACGTACGTACGTN", dtype=np.uint8)
+    out = []
+    for i, n in enumerate(lens):
+        out.append(b">r%d\n" % i + alphabet[rng.integers(0, alphabet.size, int(n))].tobytes() + b"\n")
+    return b"".join(out)
+
+
 def sequence(fasta: bytes) -> bytes:
     """The bases of a FASTA text whose lines end in `\\n`, record after record, headers and line ends left out."""
     return b"".join(ln for ln in fasta.split(b"\n") if not ln.startswith(b">"))

@@ -101,3 +101,13 @@ def cover(need: dict) -> dict:
         for case in tally[best]:
             del left[case]
     return out
+
+
+N_SLICES = {17: 2, 19: 16, 21: 256}                      # slices of 2^33 (the 64-bit control) and 2^34 addresses
+
+
+def seam_slice(exp, cut):
+    """The slice of the window that crosses byte `cut` of the text and reaches furthest back (first_window_at)."""
+    i = first_window_at(exp.data, exp.k, cut)
+    assert i < exp.kmers.size, ("no window crosses byte", cut)
+    return exp.slice_of(exp.kmers[i])

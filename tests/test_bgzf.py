@@ -80,8 +80,8 @@ def test_corrupt_block_detected(tmp_path):
 
 def test_header_reads_bgzf_table_and_cli(tmp_path, manifest):
     from pykmer_amd.header import Header
-    from test_host_layer import _family_indexes
-    path = _family_indexes(tmp_path, manifest, n=1)[0]
+    from host_support import family_indexes
+    path = family_indexes(tmp_path, manifest, n=1)[0]
     want = np.fromfile(path, dtype=np.uint8)
     bgzf.main([path])                                                # the README step: compress + remove the .kin
     assert not os.path.exists(path) and os.path.exists(path + ".bgz") and os.path.exists(path + ".bgz.gzi")

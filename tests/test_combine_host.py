@@ -5,7 +5,6 @@ import json
 import os
 import re
 import subprocess
-import types
 
 import numpy as np
 import pytest
@@ -13,16 +12,13 @@ import pytest
 import combine_ref
 import extract_ref
 import oracle
+from host_support import stub_header, write_kin
 from pykmer_amd import _lib, extract
 from pykmer_amd.header import Header, HeaderVars, gen_checksum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K = 7
 PARAMS = dict(min_count=2, max_count=200, min_present=1, max_absent=0)
-
-
-def _stub(k, name, table=None):
-    return types.SimpleNamespace(kmer_len=k, index_file=name, data_size=4 ** k, table=table)
 
 
 class _NumpyCall:
@@ -68,7 +64,7 @@ def small():
     dense = extract_ref.mixed_tables(4 ** K, 4, seed=7, zero=0.3)
     prof = combine_ref.profile(dense[:3], dense[3:], **PARAMS)
     assert prof["saturated"] > 100 and prof["unsaturated"] > 1000 and prof["mixed"] > 500 and prof["occupancies"] == {1, 2, 3}
-    return [_stub(K, f"t{i}.kin", t) for i, t in enumerate(dense)], dense
+    return [stub_header(K, f"t{i}.kin", t) for i, t in enumerate(dense)], dense
 
 
 # ------------------------------------------------------------------ the reference itself ----------
@@ -163,21 +159,6 @@ def test_combine_refuses_bad_arguments(small):
 
 
 # ------------------------------------------------------------------ files -------------------------
-def _write_index(tmp_path, name, data, k):
-    """<name>.<kk>.kin + .json as the indexer writes them, with the oracle standing in for the GPU."""
-    fa = tmp_path / name
-    fa.write_bytes(data)
-    got = oracle.count_fasta(data, k)
-    h = Header(name, input_file=str(fa), kmer_len=k)
-    h.timer.update(got["total_bp"])
-    h.num_kmers = got["num_kmers"]
-    h.chromosomes = oracle.chromosomes(data, got["records"])
-    got["table"].tofile(h.index_tmp_file)
-    h.write_metadata_index_tmp_file(hist256=np.bincount(got["table"], minlength=256))
-    os.rename(h.index_tmp_file, h.index_file_root)
-    return h.index_file_root, got["table"]
-
-
 def _fasta(seed, n=3000):
     rng = np.random.default_rng(seed)
     letters = np.frombuffer(b"ACGT", np.uint8)
@@ -188,7 +169,8 @@ def _fasta(seed, n=3000):
 
 @pytest.fixture()
 def project(tmp_path):
-    kins, tables = zip(*[_write_index(tmp_path, f"s{i}.fa", _fasta(i), K) for i in range(3)])
+    written = [write_kin(tmp_path, f"s{i}.fa", _fasta(i), K, project=f"s{i}.fa") for i in range(3)]
+    kins, tables = [w.path for w in written], [w.table for w in written]
     data = []
     for i, kin in enumerate(kins):
         data.append({"pos": i, "role": "present" if i < 2 else "absent", "index_file": kin, "description_file": kin + ".json",
@@ -315,7 +297,7 @@ def test_saturating_sum_is_the_table_of_the_pooled_files():
     pooled = combine_ref.expected([tx, ty], [], "sum", 1, 255, 1, 0)
     assert np.array_equal(pooled, oracle.count_fasta(x + y, k)["table"])
     assert np.array_equal(pooled, np.minimum(255, raw).astype(np.uint8))
-    tabs = [_stub(k, "x.kin", tx), _stub(k, "y.kin", ty)]      # the pooling recipe: --present x y --min-present 1 --table sum
+    tabs = [stub_header(k, "x.kin", tx), stub_header(k, "y.kin", ty)]      # the pooling recipe: --present x y --min-present 1 --table sum
     got = extract.combine_tables(tabs, op="sum", min_present=1, stage=_Stage(4 ** k), call=_NumpyCall(2, "sum", dict(min_present=1)))
     assert np.array_equal(got["table"], pooled) and got["n_selected"] == np.count_nonzero(raw)
 

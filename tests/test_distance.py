@@ -47,10 +47,11 @@ def test_neighbor_joining_worked_example():
 
 
 def test_outputs_from_a_kma(tmp_path, manifest):
-    from test_host_layer import _family_indexes, _oracle_partial
-    paths = sorted(_family_indexes(tmp_path, manifest, n=6))
+    from host_support import family_indexes
+    from merge_ref import oracle_partial
+    paths = sorted(family_indexes(tmp_path, manifest, n=6))
     proj = str(tmp_path / "proj")
-    merger.merge(proj, paths, partial_fn=_oracle_partial)
+    merger.merge(proj, paths, partial_fn=oracle_partial)
     kma = proj + ".001-255.kma"
     (tmp_path / "proj.001-255.kma.names.tsv").write_text("s00.fa\tancestor\ns03.fa\tthird\n")
     d = distance.load(kma)

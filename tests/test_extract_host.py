@@ -4,34 +4,30 @@ import json
 import os
 import re
 import subprocess
-import types
 
 import numpy as np
 import pytest
 
 import extract_ref
 from oracle import pyoracle
+from host_support import stub_header
 from pykmer_amd import _lib, extract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _stub(k, name, table=None):
-    return types.SimpleNamespace(kmer_len=k, index_file=name, data_size=4 ** k, table=table)
-
-
 # ------------------------------------------------------------------ validate ----------------------
 def test_validate_refuses_bad_arguments(tmp_path):
-    a, b, c = _stub(9, "a.kin"), _stub(9, "b.kin"), _stub(9, "c.kin")
+    a, b, c = stub_header(9, "a.kin"), stub_header(9, "b.kin"), stub_header(9, "c.kin")
     assert extract.validate([a, b], [c]) == (9, 2)
     assert extract.validate([a, b], [c], 2, 200, 1, 1) == (9, 1)
     with pytest.raises(ValueError, match="even.kin"):
-        extract.validate([_stub(8, "even.kin")], [])
+        extract.validate([stub_header(8, "even.kin")], [])
     with pytest.raises(ValueError, match="d.kin.*differs"):
-        extract.validate([a], [_stub(11, "d.kin")])
+        extract.validate([a], [stub_header(11, "d.kin")])
     with pytest.raises(ValueError, match="at least one present"):
         extract.validate([], [a])
-    many = [_stub(9, f"t{i}.kin") for i in range(129)]
+    many = [stub_header(9, f"t{i}.kin") for i in range(129)]
     assert extract.validate(many[:64], many[64:128]) == (9, 64)
     with pytest.raises(ValueError, match="at most 128"):
         extract.validate(many[:100], many[100:])
@@ -46,9 +42,9 @@ def test_validate_refuses_bad_arguments(tmp_path):
         with pytest.raises(ValueError, match="count window"):
             extract.validate([a], [], mn, mx)
     with pytest.raises(ValueError, match="named twice"):
-        extract.validate([a, b], [_stub(9, "a.kin")])
+        extract.validate([a, b], [stub_header(9, "a.kin")])
     with pytest.raises(ValueError, match="named twice"):
-        extract.validate([a, _stub(9, "./a.kin")], [])
+        extract.validate([a, stub_header(9, "./a.kin")], [])
     proj = str(tmp_path / "proj")
     assert extract.validate([a], [], project_name=proj) == (9, 1)
     for f in extract.kmx_paths(proj):
@@ -92,7 +88,7 @@ def _stage(piece):
 @pytest.fixture(scope="module")
 def small():
     dense = extract_ref.mixed_tables(4 ** K, 5, seed=7)
-    tables = [_stub(K, f"t{i}.kin", t) for i, t in enumerate(dense)]
+    tables = [stub_header(K, f"t{i}.kin", t) for i, t in enumerate(dense)]
     want = extract_ref.expected(dense[:3], dense[3:], PARAMS["min_count"], PARAMS["max_count"], PARAMS["min_present"], PARAMS["max_absent"])
     assert 2000 < want[0].size < 4 ** K // 2
     return tables, want
@@ -137,7 +133,7 @@ def test_pieces_halve_when_the_output_budget_is_small(small):
 
 def test_everything_selected_in_one_minimal_piece():
     """2048 addresses always fit: a piece of 2048 addresses that selects all of them is never halved."""
-    t = _stub(K, "full.kin", np.full(4 ** K, 9, dtype=np.uint8))
+    t = stub_header(K, "full.kin", np.full(4 ** K, 9, dtype=np.uint8))
     params = dict(min_count=2, max_count=200, min_present=1, max_absent=0)
     call = _NumpyCall(1, params=params)
     got = extract.extract_kmers([t], [], **params, hbm_budget=1, initial_rows=1, stage=_stage(2048), call=call)

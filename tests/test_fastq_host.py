@@ -5,48 +5,9 @@ import re
 import pytest
 
 import fastq_ref
-from fastq_ref import FastqError, fastq_to_fasta
+from fastq_ref import CASES, MALFORMED, FastqError, fastq_to_fasta
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# (name, FASTQ, the FASTA text it stands for)
-CASES = [
-    ("plain", b"@r1 first\nACGTACGTAC\n+\nIIIIIIIIII\n@r2\nGGGTTT\n+r2\n!!!!!!\n",
-     b">r1 first\nACGTACGTAC\n>r2\nGGGTTT\n"),
-    ("crlf", b"@r1\r\nACGTTGCA\r\n+\r\nIIIIIIII\r\n@r2\r\nTTTT\r\n+\r\nIIII\r\n", b">r1\r\nACGTTGCA\r\n>r2\r\nTTTT\r\n"),
-    ("lone_cr", b"@r1\rACGTTGCA\r+\rIIIIIIII\r@r2\rAC\r+\rII", b">r1\rACGTTGCA\r>r2\rAC\r"),
-    ("mixed_terminators", b"@a\r\nACGT\n+\rIIII\r\n@b\rCC\r\n+\nII\n", b">a\r\nACGT\n>b\rCC\r\n"),
-    ("empty_reads", b"@e1\n\n+\n\n@r\nACG\n+\nIII\n@e2\n\n+\n\n", b">e1\n\n>r\nACG\n>e2\n\n"),
-    ("quality_starts_with_at_plus_gt", b"@r1\nACGT\n+\n@III\n@r2\nACGT\n+\n+III\n@r3\nACGT\n+\n>III\n",
-     b">r1\nACGT\n>r2\nACGT\n>r3\nACGT\n"),
-    ("quality_all_acgt", b"@q\nACGTACGT\n+\nACGTACGT\n@q2\nTTTT\n+q2\nGGGG\n", b">q\nACGTACGT\n>q2\nTTTT\n"),
-    ("no_final_newline", b"@r1\nACGTA\n+\nIIIII\n@r2\nCCCC\n+\nIIII", b">r1\nACGTA\n>r2\nCCCC\n"),
-    ("trailing_blank_lines", b"@r1\nACGTA\n+\nIIIII\n\n\n\r\n\r\n\n\n\n", b">r1\nACGTA\n"),
-    ("name_with_blanks_and_tabs", b"@r1 a\tb  \nAC GT\n+\nIIIII\n", b">r1 a\tb  \nAC GT\n"),
-    ("lower_case_and_n", b"@x\nacgtNNacgt\n+\nIIIIIIIIII\n", b">x\nacgtNNacgt\n"),
-    ("seq_with_leading_blank", b"@x\n  ACGT\n+\nIIIIII\n", b">x\n  ACGT\n"),
-    ("empty_stream", b"", b""),
-    ("only_blank_lines", b"\n\n\r\n", b""),
-]
-
-# (name, FASTQ, 1-based record, rule)
-MALFORMED = [
-    ("no_at", b"@r1\nAC\n+\nII\nr2\nAC\n+\nII\n", 2, 1),
-    ("fasta_given_as_fastq", b">r1\nACGT\nACGT\n>r2\nAC\n", 1, 1),
-    ("seq_begins_with_gt", b"@r1\nAC\n+\nII\n@r2\n>AC\n+\nIII\n", 2, 2),
-    ("seq_begins_with_gt_after_blanks", b"@r1\n \t>AC\n+\nIIIII\n", 1, 2),
-    ("no_plus", b"@r1\nAC\n+\nII\n@r2\nAC\n-\nII\n", 2, 3),
-    ("empty_line_3", b"@r1\nAC\n\nII\n", 1, 3),
-    ("quality_too_short", b"@r1\nACGT\n+\nIII\n@r2\nAC\n+\nII\n", 1, 4),
-    ("quality_too_long_last", b"@r1\nAC\n+\nII\n@r2\nACGT\n+\nIIIII", 2, 4),
-    ("wrapped", b"@r1\nACGT\nACGT\n+\nIIII\nIIII\n", 1, 3),
-    ("ends_after_line_2", b"@r1\nAC\n+\nII\n@r2\nACGT\n", 2, 5),
-    ("ends_inside_line_1", b"@r1\nAC\n+\nII\n@r2", 2, 5),
-    ("ends_before_line_4", b"@r1\nAC\n+\nII\n@r2\n\n+\n", 2, 5),
-    ("blank_line_then_record", b"@r1\nAC\n+\nII\n\n@r2\nAC\n+\nII\n", 2, 1),
-    ("text_after_blank_lines", b"@r1\nAC\n+\nII\n\n\n\nx", 2, 1),
-]
-
 
 @pytest.mark.parametrize("name,fq,fa", CASES, ids=[c[0] for c in CASES])
 def test_restatement_cases(name, fq, fa):

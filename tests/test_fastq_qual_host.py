@@ -6,8 +6,7 @@ import pytest
 
 import fastq_ref
 from fastq_qual_ref import biased_qualities, hand_qualities, mask_fastq_to_fasta
-from fastq_ref import fastq_to_fasta
-from test_fastq_host import CASES, MALFORMED
+from fastq_ref import CASES, MALFORMED, fastq_to_fasta
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WELL_FORMED = [fq for _, fq, _ in CASES]

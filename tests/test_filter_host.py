@@ -10,12 +10,10 @@ import numpy as np
 import pytest
 
 import filter_ref
-import inputs
-import oracle
 import query_ref
 from fastq_qual_ref import mask_fastq_to_fasta
-from pykmer_amd import _lib, filter as kfilter, query
-from pykmer_amd.header import Header
+from host_support import stage_host, write_kin
+from pykmer_amd import _lib, filter as kfilter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SELECT_SYMBOLS = ("pk_select_create", "pk_select_set_records", "pk_select_feed", "pk_select_feed_device", "pk_select_finish",
@@ -92,26 +90,6 @@ def _fastq(n=6, seed=3, crlf=False):
     return b"".join(recs)
 
 
-def _write_kin(tmp_path, name, data, k):
-    """<name>.<kk>.kin + .json as pykmer_amd.indexer writes them, the oracle standing in for the GPU."""
-    fa = tmp_path / name
-    fa.write_bytes(data)
-    got = oracle.count_fasta(data, k)
-    h = Header(str(fa), sample_name=name, input_file=str(fa), kmer_len=k)
-    h._init_clean(overwrite=True)
-    h.timer.update(got["total_bp"])
-    h.num_kmers = got["num_kmers"]
-    h.chromosomes = oracle.chromosomes(data, got["records"])
-    got["table"].tofile(h.index_tmp_file)
-    h.write_metadata_index_tmp_file(hist256=np.bincount(got["table"], minlength=256))
-    os.rename(h.index_tmp_file, h.index_file_root)
-    return h.index_file_root
-
-
-def _stage(group, device):
-    return query.Staged([g.read_table_slice(0, g.data_size) for g in group])
-
-
 def _run(query_file, kmer_len, ptrs, mn, mx, device, first, min_qual_byte=0):
     text = open(query_file, "rb").read()
     fmt = "fastq" if query_file.endswith(".fq") else "fasta"
@@ -134,13 +112,13 @@ def _select(input_file, keep, out_file, starts=None, device=0):
     return {"n_records": len(keep), "n_kept": int(np.count_nonzero(keep)), "bytes_in": len(text), "bytes_kept": len(kept)}
 
 
-FAKES = dict(run=_run, stage=_stage, select=_select, hbm_budget=1 << 40)
+FAKES = dict(run=_run, stage=stage_host, select=_select, hbm_budget=1 << 40)
 
 
 @pytest.fixture()
 def project(tmp_path):
     k = 5
-    kins = [_write_kin(tmp_path, "donor.fa", b">d\nTTGACCAGGTAACGTACGTTAGCACGT\n", k), _write_kin(tmp_path, "other.fa", b">o\nGATTACAGATTACAGGTACC\n", k)]
+    kins = [write_kin(tmp_path, "donor.fa", b">d\nTTGACCAGGTAACGTACGTTAGCACGT\n", k).path, write_kin(tmp_path, "other.fa", b">o\nGATTACAGATTACAGGTACC\n", k).path]
     q = tmp_path / "reads.fa"
     q.write_bytes(FASTA)
     return tmp_path, kins, str(q)
@@ -199,7 +177,7 @@ def test_mates_share_their_flags(project):
     fq1, fq2 = _fastq(6, seed=3), _fastq(6, seed=4, crlf=True)
     (tmp_path / "r_1.fq").write_bytes(fq1)
     (tmp_path / "r_2.fq").write_bytes(fq2)
-    table = _write_kin(tmp_path, "bait.fa", b">b\n" + fq1.split(b"\n")[1] + b"\n" + fq2.split(b"\r\n")[9] + b"\n", 7)
+    table = write_kin(tmp_path, "bait.fa", b">b\n" + fq1.split(b"\n")[1] + b"\n" + fq2.split(b"\r\n")[9] + b"\n", 7).path
     t = np.fromfile(table, dtype=np.uint8)
     m1 = np.array(filter_ref.decide(*[query_ref.expected(fq1, 7, [t], 1, 255, "fastq")[key] for key in ("hits", "n_valid")])[0])
     m2 = np.array(filter_ref.decide(*[query_ref.expected(fq2, 7, [t], 1, 255, "fastq")[key] for key in ("hits", "n_valid")])[0])
@@ -223,7 +201,7 @@ def test_min_qual_changes_the_flags_and_is_recorded(project):
     tmp_path, kins, _ = project
     fq = _fastq(6, seed=3)
     (tmp_path / "r.fq").write_bytes(fq)
-    table = _write_kin(tmp_path, "bait.fa", b">b\n" + fq.split(b"\n")[1] + b"\n", 7)
+    table = write_kin(tmp_path, "bait.fa", b">b\n" + fq.split(b"\n")[1] + b"\n", 7).path
     plain = kfilter.filter(str(tmp_path / "plain"), str(tmp_path / "r.fq"), [table], **FAKES)
     masked = kfilter.filter(str(tmp_path / "masked"), str(tmp_path / "r.fq"), [table], min_qual=41, **FAKES)
     assert plain["keep"][0] == 1 and masked["keep"][0] == 0                # every quality byte is below 33 + 41

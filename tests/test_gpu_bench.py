@@ -2,24 +2,20 @@
 --dump-outputs writes the same arrays either way."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from gpu_support import run_py
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--bp", "2000000", "--k", "11", "--steps", "2", "--warmup", "1", "--merge-n", "3", "--merge-bp", "1000000",
          "--no-merge32", "--cpu-bp", "1000000"]
 FULL_ONLY = {"merge", "merge_n32", "cpu_baseline", "e2e"}
 
 
 def _bench(*flags, cwd):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *flags], cwd=cwd, capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return json.loads(run_py("bench.py", *SMALL, *flags, cwd=cwd).stdout.strip().splitlines()[-1])
 
 
 def _dump(d):

@@ -16,9 +16,7 @@ import byte_inputs
 import oracle
 import parse_ref
 import query_ref
-from test_gpu_fastq import _check_against_oracle as _check_fastq, _count as _count_fastq
-from test_gpu_indexer import _check_against_oracle
-from test_gpu_query import _Device, _query, _same
+from gpu_support import Device, check_against_oracle, check_fastq_against_oracle, count_fastq, query, same
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,20 +28,20 @@ def test_every_byte_value_at_piece_and_chunk_edges(gpu, dense):
     """k = 3 keeps windows alive between foreign bytes; k = 15 is the literal instantiation, 14 carried bases at a seam."""
     for text in byte_inputs.placement_fasta(dense):
         for k in (3, 15):
-            _check_against_oracle(gpu, text, k)
+            check_against_oracle(gpu, text, k)
 
 
 def test_every_byte_value_at_line_starts(gpu):
     text = byte_inputs.line_start_fasta()
-    got = _check_against_oracle(gpu, text, 5)
+    got = check_against_oracle(gpu, text, 5)
     assert len(got["records"]) == 1 + 256 + 3                 # only '>' opened records: not 0xBE, 0x1E, 0x3C, 0x3F, 0x7E
     for t in byte_inputs.stream_start_fastas():
-        _check_against_oracle(gpu, t, 5)
+        check_against_oracle(gpu, t, 5)
 
 
 def test_every_byte_value_in_header_text(gpu):
     text = byte_inputs.header_bytes_fasta()
-    got = _check_against_oracle(gpu, text, 5)
+    got = check_against_oracle(gpu, text, 5)
     want, _ = parse_ref.parse(text, 5)
     assert parse_ref.names(text, got["records"]) == parse_ref.names(text, want)
 
@@ -62,15 +60,15 @@ def test_full_alphabet_soup(gpu):
     for seed, n in byte_inputs.SOUP_CASES:
         data = byte_inputs.soup(seed, n)
         for k in (3, 9):
-            _check_against_oracle(gpu, data, k)
+            check_against_oracle(gpu, data, k)
     first = byte_inputs.soup(*byte_inputs.SOUP_CASES[0])
     for m in byte_inputs.SOUP_PREFIXES:
-        _check_against_oracle(gpu, first[:m], 3)
+        check_against_oracle(gpu, first[:m], 3)
     # the same bytes through the streaming interface: cuts immediately before and behind bytes >= 0x80 and bytes < 0x21,
     # each of those also as a feed of one byte
     cuts = byte_inputs.cuts_around_odd_bytes(first, seed=5)
     for k in (3, 9):
-        whole = _check_against_oracle(gpu, first, k)
+        whole = check_against_oracle(gpu, first, k)
         want = oracle.count_fasta(first, k)
         fin = _streamed(gpu, first, k, cuts)
         assert fin["num_kmers"] == want["num_kmers"] == whole["num_kmers"] and fin["total_bp"] == want["total_bp"]
@@ -87,21 +85,21 @@ def test_full_alphabet_soup(gpu):
 def test_fastq_every_byte_value_in_every_line_role(gpu, crlf):
     fq = byte_inputs.placement_fastq(crlf)
     for k in (3, 15):
-        _check_fastq(_count_fastq(gpu, fq, k), fq, k)
+        check_fastq_against_oracle(count_fastq(fq, k), fq, k)
     rng = np.random.default_rng(40 + crlf)
     cuts = sorted(set(int(c) for c in rng.integers(1, len(fq), size=40)))
-    _check_fastq(_count_fastq(gpu, fq, 3, cuts=cuts), fq, 3)
+    check_fastq_against_oracle(count_fastq(fq, 3, cuts=cuts), fq, 3)
 
 
 def test_query_over_full_alphabet_text(gpu):
     k = 9
     tables = query_ref.random_tables(k, 2, seed=61)
     texts = [byte_inputs.soup(*byte_inputs.SOUP_CASES[0]), *byte_inputs.placement_fasta(False)]   # all three placement texts
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for text in texts:
             want = query_ref.expected(text, k, tables, 1, 255)
             assert want["hits"].any(axis=0).all() and int(want["n_valid"].sum()) >= 500   # not a vacuous comparison
-            _same(_query(text, k, dev.ptrs, 1, 255), want)
+            same(query(text, k, dev.ptrs, 1, 255), want)
 
 
 def test_cli_names_that_are_not_utf8(gpu, tmp_path):

@@ -2,22 +2,14 @@
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import inputs
+from gpu_support import env_without_ranks, family_kins, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _run(*argv, cwd):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
 
 
 @pytest.mark.parametrize("name", ["G2_c1_k7", "G3_edge_k9", "G3_edge_gz_k7", "G3_edge_k15"])
@@ -26,7 +18,7 @@ def test_indexer_cli_writes_reference_files(gpu, tmp_path, manifest, small_table
     fa = tmp_path / case["input_file"]
     data = inputs.make_input(case["input"])
     fa.write_bytes(data)
-    _run(os.path.join(ROOT, "indexer.py"), str(fa), "sample", str(case["k"]), cwd=str(tmp_path))
+    run_py("indexer.py", str(fa), "sample", str(case["k"]), cwd=str(tmp_path))
     kin = f"{fa}.{case['k']:02d}.kin"
     assert os.path.getsize(kin) == 4 ** case["k"] and not os.path.exists(kin + ".tmp")
     with open(kin + ".json") as fh:
@@ -44,12 +36,12 @@ def test_indexer_cli_writes_reference_files(gpu, tmp_path, manifest, small_table
 def test_indexer_cli_readme_form_and_refusal(gpu, tmp_path):
     fa = tmp_path / "r.fa"
     fa.write_bytes(inputs.edge_fasta())
-    _run(os.path.join(ROOT, "indexer.py"), str(fa), "7", cwd=str(tmp_path))          # README.md:22: indexer.py <file> <K>
+    run_py("indexer.py", str(fa), "7", cwd=str(tmp_path))          # README.md:22: indexer.py <file> <K>
     assert os.path.exists(f"{fa}.07.kin.json")
     empty = tmp_path / "n.fa"
     empty.write_bytes(b">all_n\nNNNNNNNNNNNNNNNN\n")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "indexer.py"), str(empty), "s", "7"], capture_output=True, text=True)
-    assert r.returncode != 0 and "AssertionError" in r.stderr                        # tools.py:367: no k-mers -> assert
+    r = run_py("indexer.py", str(empty), "s", "7", status=1)
+    assert "AssertionError" in r.stderr                                             # tools.py:367: no k-mers -> assert
 
 
 def test_merger_cli_matches_reference_matrix(gpu, tmp_path, manifest):
@@ -58,12 +50,12 @@ def test_merger_cli_matches_reference_matrix(gpu, tmp_path, manifest):
     for i, spec in enumerate(case["inputs"]):
         fa = tmp_path / f"s{i:02d}.fa"
         fa.write_bytes(inputs.make_input(spec))
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), f"s{i}", "7", cwd=str(tmp_path))
+        run_py("indexer.py", str(fa), f"s{i}", "7", cwd=str(tmp_path))
         kins.append(f"{fa}.07.kin")
     with open(kins[4], "rb") as fh, gzip.open(kins[4] + ".bgz", "wb") as out:        # Header.index_file then prefers the .bgz
         out.write(fh.read())
     proj = str(tmp_path / "proj")
-    _run(os.path.join(ROOT, "merger.py"), proj, *reversed(kins), "--max-count", "3", "--threads", "3", cwd=str(tmp_path))
+    run_py("merger.py", proj, *reversed(kins), "--max-count", "3", "--threads", "3", cwd=str(tmp_path))
     m = np.load(proj + ".001-003.kma")["matrix"]
     assert m.dtype == np.uint64 and np.array_equal(m, np.array(case["matrix"], dtype=np.uint64))
     with open(proj + ".001-003.kma.json") as fh:
@@ -73,7 +65,7 @@ def test_merger_cli_matches_reference_matrix(gpu, tmp_path, manifest):
     assert [os.path.basename(d["index_file"]) for d in meta["data"]] == case["order"]  # sorted, whatever the argv order
     # a sweep stages the tables once and writes one .kma per window
     sw = str(tmp_path / "sweep")
-    _run(os.path.join(ROOT, "merger.py"), sw, *kins, "--sweep", "1-3,2-255", cwd=str(tmp_path))
+    run_py("merger.py", sw, *kins, "--sweep", "1-3,2-255", cwd=str(tmp_path))
     assert np.array_equal(np.load(sw + ".001-003.kma")["matrix"], m)
     assert np.array_equal(np.load(sw + ".002-255.kma")["matrix"], np.array(manifest["merger"]["G7_k7_n13_min2"]["matrix"], dtype=np.uint64))
     # the pair API the reference's pool workers call (merger.py:62-78)
@@ -92,9 +84,7 @@ def test_indexer_cli_counts_in_address_slices(gpu, tmp_path, manifest):
     fa = tmp_path / case["input_file"]
     fa.write_bytes(inputs.make_input(case["input"]))
     env = dict(os.environ, PK_SLICES="4", PK_DEVICES="0,0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "indexer.py"), str(fa), "sample", "9"], cwd=str(tmp_path), capture_output=True,
-                       text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    run_py("indexer.py", str(fa), "sample", "9", cwd=str(tmp_path), env=env)
     kin = f"{fa}.09.kin"
     with open(kin + ".json") as fh:
         meta = json.load(fh)
@@ -102,31 +92,16 @@ def test_indexer_cli_counts_in_address_slices(gpu, tmp_path, manifest):
         assert meta[f] == v, f
 
 
-def _family_kins(tmp_path, manifest, tag="G7_k7_n13_default"):
-    case = manifest["merger"][tag]
-    kins = []
-    for i, spec in enumerate(case["inputs"]):
-        fa = tmp_path / f"s{i:02d}.fa"
-        fa.write_bytes(inputs.make_input(spec))
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), f"s{i}", "7", cwd=str(tmp_path))
-        kins.append(f"{fa}.07.kin")
-    return kins
-
-
 def test_merger_cli_one_process_per_gpu(gpu, tmp_path, manifest):
     """merger.py:213-239 with the reference's pool (merger.py:137-178) replaced by ranks: `--gpus 2` starts two ranks (here both
     on the one GPU, so the rehearsal backend gloo: RCCL refuses two ranks on one device), each scans its half of the k-mer
     address range, one all-reduce sums the partials, rank 0 writes.  Then the RCCL form of the same entry: a launcher's
     environment (WORLD_SIZE=1, as torchrun sets it) makes the CLI join an nccl group."""
-    kins = _family_kins(tmp_path, manifest)
+    kins = family_kins(tmp_path, manifest)
     want = np.array(manifest["merger"]["G7_k7_n13_min2"]["matrix"], dtype=np.uint64)
-    env = dict(os.environ, PK_DIST_BACKEND="gloo")
-    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(v, None)
+    env = env_without_ranks(PK_DIST_BACKEND="gloo")
     proj = str(tmp_path / "two")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "merger.py"), proj, *kins, "--min-count", "2", "--gpus", "2"], cwd=str(tmp_path),
-                       capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = run_py("merger.py", proj, *kins, "--min-count", "2", "--gpus", "2", cwd=str(tmp_path), env=env)
     assert np.array_equal(np.load(proj + ".002-255.kma")["matrix"], want)
     assert r.stdout.count("saving") == 2                                             # rank 0 alone prints and writes
     with open(proj + ".002-255.kma.json") as fh:
@@ -135,9 +110,7 @@ def test_merger_cli_one_process_per_gpu(gpu, tmp_path, manifest):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29617")
     env.pop("PK_DIST_BACKEND", None)
     proj = str(tmp_path / "one")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "merger.py"), proj, *kins, "--sweep", "2-255,1-3"], cwd=str(tmp_path),
-                       capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    run_py("merger.py", proj, *kins, "--sweep", "2-255,1-3", cwd=str(tmp_path), env=env)
     assert np.array_equal(np.load(proj + ".002-255.kma")["matrix"], want)
     assert np.array_equal(np.load(proj + ".001-003.kma")["matrix"], np.array(manifest["merger"]["G7_k7_n13_max3"]["matrix"], dtype=np.uint64))
 
@@ -162,7 +135,7 @@ def test_indexer_cli_on_bgzipped_fasta(gpu, tmp_path, manifest, small_tables, pi
         monkeypatch.setattr(indexer, "GZ_PIECE", piece)
         indexer.main([str(fa), "sample", "7"])
     else:
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), "sample", "7", cwd=str(tmp_path))
+        run_py("indexer.py", str(fa), "sample", "7", cwd=str(tmp_path))
     kin = f"{fa}.07.kin"
     with open(kin + ".json") as fh:
         meta = json.load(fh)

@@ -3,59 +3,33 @@
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import combine_ref
 import extract_ref
 import inputs
 import oracle
 import query_ref
 import synth
+from gpu_support import ROOT, SENTINEL, Device, HostTable, SentinelOut, lib, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0xA5
 OPS = combine_ref.OPS
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(max(16, t.size), 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-class _Out:
+class _Out(SentinelOut):
     """A sentinel-filled output table of `size` bytes and a zeroed histogram accumulator in HBM."""
 
     def __init__(self, size):
-        lib = _lib()
-        self.table = lib.DeviceBuffer((max(16, size) + 15) & ~15, 0)
-        self.table.upload(np.full(self.table.n, SENTINEL, dtype=np.uint8))
-        self.hist = lib.DeviceBuffer(256 * 8, 0)
+        super().__init__(table=(max(16, size) + 15) & ~15)
+        self.hist = lib().DeviceBuffer(256 * 8, 0)
         self.hist.zero()
 
     def untouched(self):
-        return bool((self.table.download() == SENTINEL).all()) and not self.hist.download().any()
+        return super().untouched() and not self.hist.download().any()
 
     def hist256(self, addresses):
         """The accumulator with the zeros filled in: the device tallies the values 1 .. 255."""
@@ -65,7 +39,7 @@ class _Out:
         return h
 
     def free(self):
-        self.table.free()
+        super().free()
         self.hist.free()
 
 
@@ -79,10 +53,10 @@ def _check(present, absent, op, mn=1, mx=255, min_present=None, max_absent=0, n=
     out = _Out(n + 64)
     try:
         if ptrs is None:
-            with _Device(list(present) + list(absent)) as dev:
-                secs = _lib().extract_table_device(dev.ptrs, P, n, mn, mx, min_present, max_absent, op, out.table.ptr, out.hist.ptr)
+            with Device(list(present) + list(absent), min_bytes=16) as dev:
+                secs = lib().extract_table_device(dev.ptrs, P, n, mn, mx, min_present, max_absent, op, out.table.ptr, out.hist.ptr)
         else:
-            secs = _lib().extract_table_device(ptrs, P, n, mn, mx, min_present, max_absent, op, out.table.ptr, out.hist.ptr)
+            secs = lib().extract_table_device(ptrs, P, n, mn, mx, min_present, max_absent, op, out.table.ptr, out.hist.ptr)
         got = out.table.download()
         assert secs > 0
         assert np.array_equal(got[:n], want), (op, np.flatnonzero(got[:n] != want)[:5], got[:n][got[:n] != want][:5], want[got[:n] != want][:5])
@@ -105,7 +79,7 @@ def test_slice_sizes(gpu, n):
     if n >= 4 ** 7:
         prof = combine_ref.profile([t[:n] for t in tables[:3]], [t[:n] for t in tables[3:]], 2, 200, 1, 0)
         assert prof["saturated"] > 100 and prof["unsaturated"] > 1000 and prof["mixed"] > 500 and prof["occupancies"] == {1, 2, 3}, prof
-    with _Device(tables) as dev:
+    with Device(tables, min_bytes=16) as dev:
         for op in OPS:
             want = _check(tables[:3], tables[3:], op, 2, 200, 1, 0, n=n, ptrs=dev.ptrs)
             assert n < 64 or 0 < np.count_nonzero(want) < n
@@ -120,7 +94,7 @@ def test_window_edges(gpu, mn, mx):
     absent = np.zeros(a.size, dtype=np.uint8)
     absent[2::5] = 1                                         # count 1 is held, whatever the window
     absent[1::7] = 255
-    with _Device([a, b, c, absent]) as dev:
+    with Device([a, b, c, absent], min_bytes=16) as dev:
         for op in OPS:
             for min_present in (1, 3):
                 want = _check([a, b, c], [absent], op, mn, mx, min_present, 0, ptrs=dev.ptrs)
@@ -132,13 +106,13 @@ def test_counters_and_sums_at_128_tables(gpu):
     n = 4100
     for value, want_sum in ((1, 128), (2, 255), (255, 255)):  # 128, 256 clamped, 32 640 clamped: a wrap in 8 or 15 bits shows
         full = [np.full(n, value, dtype=np.uint8)] * 128
-        with _Device(full[:1]) as dev:                        # the same slice 128 times: the kernel reads 128 pointers
+        with Device(full[:1], min_bytes=16) as dev:                        # the same slice 128 times: the kernel reads 128 pointers
             ptrs = dev.ptrs * 128
             assert (_check(full, [], "sum", ptrs=ptrs) == want_sum).all()
             assert (_check(full, [], "count", ptrs=ptrs) == 128).all()
             assert (_check(full, [], "min", ptrs=ptrs) == value).all() and (_check(full, [], "max", ptrs=ptrs) == value).all()
     tables = extract_ref.mixed_tables(n, 128, seed=3, zero=0.5)
-    with _Device(tables) as dev:
+    with Device(tables, min_bytes=16) as dev:
         for op in OPS:
             want = _check(tables[:127], tables[127:], op, 2, 200, 40, 0, ptrs=dev.ptrs)
             assert 0 < np.count_nonzero(want) < n
@@ -166,8 +140,8 @@ def test_histogram_accumulates_over_the_slices_of_a_table(gpu):
     tables = extract_ref.mixed_tables(n, 3, seed=5, zero=0.3)
     want = combine_ref.expected(tables[:2], tables[2:], "sum", 2, 200, 1, 0)
     out = _Out(n)
-    with _Device(tables) as dev:
-        lib = _lib()
+    with Device(tables, min_bytes=16) as dev:
+        lib = gs.lib()
         lib.extract_table_device(dev.ptrs, 2, cut, 2, 200, 1, 0, "sum", out.table.ptr, out.hist.ptr)
         first = out.hist256(cut)
         assert np.array_equal(first, combine_ref.hist256(want[:cut]))
@@ -184,7 +158,7 @@ def test_nonzero_addresses_are_the_extracted_list(gpu, params):
     k = 7
     tables = extract_ref.mixed_tables(4 ** k, 4, seed=6, zero=0.3)
     mn, mx, min_present, max_absent = params
-    with _Device(tables) as dev:
+    with Device(tables, min_bytes=16) as dev:
         resident = [merger.ResidentTable(p, 4 ** k, 4 ** k) for p in dev.ptrs]
         listed = extract.extract_kmers(resident[:2], resident[2:], mn, mx, min_present, max_absent)
         assert 100 < listed["n_selected"] < 4 ** k
@@ -208,10 +182,10 @@ def test_thousands_of_workgroups(gpu):
 
 # ------------------------------------------------------------------ 8. arguments -------------------
 def test_bad_arguments_are_refused(gpu):
-    lib = _lib()
+    lib = gs.lib()
     n = 4096
     t = np.full(n, 3, dtype=np.uint8)
-    with _Device([t]) as dev:
+    with Device([t], min_bytes=16) as dev:
         p = dev.ptrs[0]
         out = _Out(n)
 
@@ -246,24 +220,14 @@ def test_bad_arguments_are_refused(gpu):
 
 
 # ------------------------------------------------------------------ 9. the whole path, small -------
-class _HostTable:
-    """What the staging loop needs of a Header, backed by a host array."""
-
-    def __init__(self, k, name, table):
-        self.kmer_len, self.index_file, self.data_size, self.table = k, name, 4 ** k, table
-
-    def read_table_slice(self, lo, hi, threads=None):
-        return self.table[lo:hi]
-
-
 def test_whole_path_under_a_small_budget(gpu, monkeypatch):
     from pykmer_amd import extract
     k = 9
     x, y = inputs.record_dense_fasta(27 + 61 * 1000, 9, seed=3), inputs.record_dense_fasta(27 + 61 * 500, 9, seed=4)
     texts = [inputs.edge_fasta() + x, x + y + inputs.byte_soup(20_000, 5), y]
-    counted = [_lib().count_fasta(t, k, device=0)["table"].copy() for t in texts]
+    counted = [lib().count_fasta(t, k, device=0)["table"].copy() for t in texts]
     want_tables = [oracle.count_fasta(t, k)["table"] for t in texts]
-    tables = [_HostTable(k, f"t{i}.kin", t) for i, t in enumerate(counted)]
+    tables = [HostTable(k, f"t{i}.kin", t) for i, t in enumerate(counted)]
     for op in OPS:
         want = combine_ref.expected(want_tables[:2], want_tables[2:], op, 1, 255, 1, 0)
         assert np.count_nonzero(want) > 100
@@ -281,12 +245,6 @@ def test_whole_path_under_a_small_budget(gpu, monkeypatch):
 
 
 # ------------------------------------------------------------------ 10. CLI, and the loop closed ---
-def _cli(*argv, cwd, ok=True):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert (r.returncode == 0) == ok, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_cli_end_to_end_and_back_in(gpu, tmp_path):
     from pykmer_amd.header import Header
     k = 9
@@ -300,7 +258,7 @@ def test_cli_end_to_end_and_back_in(gpu, tmp_path):
         if i < 2:
             data += b">repeat\n" + unit * 150 + b"\n"                           # 150 + 150: the pooled count saturates, neither file's does
         fa.write_bytes(data)
-        _cli(os.path.join(ROOT, "indexer.py"), str(fa), f"s{i}", str(k), cwd=str(tmp_path))
+        run_py("indexer.py", str(fa), f"s{i}", str(k), cwd=str(tmp_path))
         kins.append(f"{fa}.{k:02d}.kin")
         tables.append(oracle.count_fasta(data, k)["table"])
         texts.append(data)
@@ -309,8 +267,8 @@ def test_cli_end_to_end_and_back_in(gpu, tmp_path):
     pooled = np.minimum(255, raw).astype(np.uint8)
     # ---- the pooled table
     proj = str(tmp_path / "proj")
-    argv = [os.path.join(ROOT, "extract.py"), proj, "--present", kins[0], kins[1], "--min-present", "1", "--table", "sum"]
-    r = _cli(*argv, cwd=str(tmp_path))
+    argv = ["extract.py", proj, "--present", kins[0], kins[1], "--min-present", "1", "--table", "sum"]
+    r = run_py(*argv, cwd=str(tmp_path))
     kin = f"{proj}.{k:02d}.kin"
     assert f"{np.count_nonzero(pooled):,d} k-mers selected" in r.stdout and r.stdout.rstrip().endswith(f"table {kin} (sum)")
     got = np.fromfile(kin, dtype=np.uint8)
@@ -327,26 +285,26 @@ def test_cli_end_to_end_and_back_in(gpu, tmp_path):
     sources = [Header(f, index_file=f) for f in kins[:2]]
     assert header.chromosomes == [[f"present:{h.project_name}", h.num_kmers] for h in sources] and sources[0].num_kmers > 0
     # ---- and back in: merged, queried against, extracted from
-    _cli(os.path.join(ROOT, "merger.py"), str(tmp_path / "m"), kin, kins[2], cwd=str(tmp_path))
+    run_py("merger.py", str(tmp_path / "m"), kin, kins[2], cwd=str(tmp_path))
     assert np.array_equal(np.load(str(tmp_path / "m.001-255.kma"))["matrix"], oracle.gram([pooled, tables[2]]))
-    _cli(os.path.join(ROOT, "query.py"), str(tmp_path / "q"), str(tmp_path / "s2.fa"), kin, cwd=str(tmp_path))
+    run_py("query.py", str(tmp_path / "q"), str(tmp_path / "s2.fa"), kin, cwd=str(tmp_path))
     want = query_ref.expected(texts[2], k, [pooled], 1, 255)
     z = np.load(str(tmp_path / "q.kmq"))
     assert np.array_equal(z["hits"], want["hits"]) and np.array_equal(z["depth"], want["depth"]) and want["hits"].sum() > 0
-    _cli(os.path.join(ROOT, "extract.py"), str(tmp_path / "again"), "--present", kin, "--absent", kins[2], cwd=str(tmp_path))
+    run_py("extract.py", str(tmp_path / "again"), "--present", kin, "--absent", kins[2], cwd=str(tmp_path))
     want_addr, want_counts = extract_ref.expected([pooled], [tables[2]], 1, 255)
     z = np.load(str(tmp_path / "again.kmx"))
     assert np.array_equal(z["addr"], want_addr) and np.array_equal(z["counts"], want_counts) and want_addr.size > 100
     # ---- refusals
     files = [kin, kin + ".json", proj + ".kmx.json"]
     before = [open(f, "rb").read() for f in files]
-    r = _cli(*argv, cwd=str(tmp_path), ok=False)              # a second run refuses to overwrite
+    r = run_py(*argv, cwd=str(tmp_path), status=1)              # a second run refuses to overwrite
     assert r.returncode == 1 and "error:" in r.stderr and "already exists" in r.stderr
     assert before == [open(f, "rb").read() for f in files]
-    r = _cli("-m", "pykmer_amd.extract", str(tmp_path / "twice"), "--present", kins[0], "--absent", kins[0], "--table", "max", cwd=ROOT, ok=False)
+    r = run_py("-m", "pykmer_amd.extract", str(tmp_path / "twice"), "--present", kins[0], "--absent", kins[0], "--table", "max", cwd=ROOT, status=1)
     assert r.returncode == 1 and "named twice" in r.stderr
     listing = sorted(p.name for p in tmp_path.iterdir())
-    r = _cli(os.path.join(ROOT, "extract.py"), str(tmp_path / "none"), "--present", kins[0], "--min-count", "255", "--max-count", "255", "--table", "max",
-             cwd=str(tmp_path), ok=False)
+    r = run_py("extract.py", str(tmp_path / "none"), "--present", kins[0], "--min-count", "255", "--max-count", "255", "--table", "max",
+             cwd=str(tmp_path), status=1)
     assert r.returncode == 1 and "error:" in r.stderr and "no k-mer is selected" in r.stderr and "255-255" in r.stderr
     assert sorted(p.name for p in tmp_path.iterdir()) == listing

@@ -8,55 +8,26 @@ import tempfile
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import mask_inputs as mi
 import mask_ref
 import oracle
 import query_coords_inputs as qci
 import query_ref
 import synth
+from gpu_support import Device, feed, lib, stream
 
 pytestmark = pytest.mark.gpu
 CHUNK = mi.CHUNK
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-@contextlib.contextmanager
-def _device(tables):
-    """Host tables staged in HBM for the length of a test: their device pointers."""
-    bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-    try:
-        for b, t in zip(bufs, tables):
-            b.upload(t)
-        yield [b.ptr for b in bufs]
-    finally:
-        for b in bufs:
-            b.free()
-
-
-def _feed(q, text: bytes, cuts=None):
-    buf = np.frombuffer(text, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(text)]:
-        if c > pos:
-            q.feed(buf[pos:c])
-            pos = c
-
-
 def _cover(q, text: bytes, cuts=None):
-    """One stream through an indexer whose tables are set: (bits, n_bases, finish())."""
-    q.set_cover(True)
-    _feed(q, text, cuts)
-    fin = q.finish()
-    bits, n_bases = q.cover(len(text))
-    return bits.copy(), n_bases, fin
+    """One stream through an indexer whose tables are set; no reset behind it."""
+    return stream(q, text, cover=True, cuts=cuts, reset=False)
 
 
 def _same(got, want):
-    bits, n_bases, fin = got
+    bits, n_bases, fin = got["bits"], got["n_bases"], got["fin"]
     assert n_bases == want["n_bases"] and fin["n_records"] == want["n_records"] and fin["num_kmers"] == want["win_end"].size
     assert bits.dtype == np.uint8 and bits.shape == want["bits"].shape
     cover = mask_ref.unpack(bits, n_bases)
@@ -72,13 +43,13 @@ def staged(gpu, request):
     with contextlib.ExitStack() as stack:
         bufs = []
         for t in tabs:
-            b = _lib().DeviceBuffer(4 ** k, 0)
+            b = lib().DeviceBuffer(4 ** k, 0)
             stack.callback(b.free)
             dense = t.dense()
             b.upload(dense)
             del dense
             bufs.append(b)
-        q = stack.enter_context(_lib().QueryIndexer(k, device=0))
+        q = stack.enter_context(lib().QueryIndexer(k, device=0))
         yield k, tabs, [b.ptr for b in bufs], q
 
 
@@ -104,7 +75,7 @@ def test_k17(gpu):
     text = qci.k17_text()
     genome = qci.k17_genomes()[0]
     sparse = [query_ref.SparseTable(oracle.kmer_list(genome, k))]
-    lib = _lib()
+    lib = gs.lib()
     with lib.Indexer(k, device=0) as ix:
         ix.feed(genome)
         ix.finish()
@@ -124,8 +95,8 @@ def test_seams(gpu, which):
     table = mi.seam_tables()[0 if which == "around" else 1]
     want = mask_ref.expected(text, k, [table], 1, 255)
     assert 0 < want["cover"].sum() < want["n_bases"]
-    with _device([table]) as ptrs, _lib().QueryIndexer(k, device=0) as q:
-        q.set_tables(ptrs, 1, 255)
+    with Device([table]) as dev, lib().QueryIndexer(k, device=0) as q:
+        q.set_tables(dev.ptrs, 1, 255)
         _same(_cover(q, text), want)
         for cut in mi.seam_cuts():
             q.reset()
@@ -136,7 +107,7 @@ def test_seams(gpu, which):
         _same(_cover(q, text, [CHUNK - 3, CHUNK + 2, 2 * CHUNK - 1, 2 * CHUNK + 1]), want)
         if which == "around":                                # counts of 2 around the even boundary only
             q.reset()
-            q.set_tables(ptrs, 2, 254)
+            q.set_tables(dev.ptrs, 2, 254)
             two = mask_ref.expected(text, k, [table], 2, 254)
             assert 0 < two["cover"].sum() < want["cover"].sum()
             _same(_cover(q, text, [2 * CHUNK - 4]), two)
@@ -148,8 +119,8 @@ def test_run_across_a_chunk_with_three_bases(gpu):
     k = mi.SEAM_K
     text, table = mi.hollow()
     want = mask_ref.expected(text, k, [table], 1, 255)
-    with _device([table]) as ptrs, _lib().QueryIndexer(k, device=0) as q:
-        q.set_tables(ptrs, 1, 255)
+    with Device([table]) as dev, lib().QueryIndexer(k, device=0) as q:
+        q.set_tables(dev.ptrs, 1, 255)
         _same(_cover(q, text), want)
         for cuts in ([CHUNK], [CHUNK + 2, 2 * CHUNK], [CHUNK - 1, CHUNK + 1, 2 * CHUNK - 5, 2 * CHUNK + 3]):
             q.reset()
@@ -160,8 +131,8 @@ def test_more_chunks_than_the_scan_tile(gpu):
     k = mi.SEAM_K
     text, table = mi.long_text()
     want = mask_ref.expected(text, k, [table], 1, 255, fast=True)
-    with _device([table]) as ptrs, _lib().QueryIndexer(k, device=0) as q:
-        q.set_tables(ptrs, 1, 255)
+    with Device([table]) as dev, lib().QueryIndexer(k, device=0) as q:
+        q.set_tables(dev.ptrs, 1, 255)
         got = _cover(q, text)
         assert q.timings()["feeds"] == 1, "the text was meant to be one feed of 1026 chunks"
         _same(got, want)
@@ -177,9 +148,9 @@ def test_retry_in_the_second_feed_and_reset(gpu):
     dense = [t.dense() for t in tabs]
     want = mask_ref.expected(text, k, tabs, 1, 255)
     assert want["n_records"] == 5000 > 4096 and 0 < want["cover"].sum() < want["n_bases"]
-    with _device(dense) as ptrs:
-        with _lib().QueryIndexer(k, device=0) as q:
-            q.set_tables(ptrs, 1, 255)
+    with Device(dense) as dev:
+        with lib().QueryIndexer(k, device=0) as q:
+            q.set_tables(dev.ptrs, 1, 255)
             _same(_cover(q, text, [200]), want)
             q.reset()
             _same(_cover(q, text, [200]), want)
@@ -187,12 +158,12 @@ def test_retry_in_the_second_feed_and_reset(gpu):
             other = qci.many_records(127)
             _same(_cover(q, other), mask_ref.expected(other, k, tabs, 1, 255))
             q.reset()
-            with pytest.raises(_lib().PkError):              # the bits are off after a reset
-                _feed(q, text)
+            with pytest.raises(lib().PkError):              # the bits are off after a reset
+                feed(q, text)
                 q.finish()
                 q.cover(len(text))
-        with _lib().QueryIndexer(k, device=0) as q:
-            q.set_tables(ptrs, 1, 255)
+        with lib().QueryIndexer(k, device=0) as q:
+            q.set_tables(dev.ptrs, 1, 255)
             _same(_cover(q, text), want)
 
 
@@ -212,11 +183,11 @@ def test_seventeen_tables_and_three_staging_groups(gpu):
     want = mask_ref.expected(text, k, tables, 1, 255)
     last = mask_ref.expected(text, k, tables[:16], 1, 255)
     assert 0 < last["cover"].sum() < want["cover"].sum() < want["n_bases"]          # the seventeenth table adds bases
-    with tempfile.TemporaryDirectory() as d, _device(tables) as ptrs:
+    with tempfile.TemporaryDirectory() as d, Device(tables) as dev:
         path = os.path.join(d, "q.fa")
         with open(path, "wb") as fh:
             fh.write(text)
-        resident = [merger.ResidentTable(p, 4 ** k, 4 ** k, device=0) for p in ptrs]
+        resident = [merger.ResidentTable(p, 4 ** k, 4 ** k, device=0) for p in dev.ptrs]
         for t in resident:
             t.kmer_len = k
         got = mask.cover_bits(path, resident, 1, 255, device=0)
@@ -226,7 +197,7 @@ def test_seventeen_tables_and_three_staging_groups(gpu):
             def __init__(self, i):
                 self.i, self.kmer_len = i, k
 
-        def stage(group, dev):
-            return query.Staged([ptrs[t.i] for t in group])
+        def stage(group, device):
+            return query.Staged([dev.ptrs[t.i] for t in group])
         three = mask.cover_bits(path, [_Host(i) for i in range(17)], 1, 255, device=0, hbm_budget=6 * 4 ** k + 100, stage=stage)
         assert three["n_groups"] == 3 and np.array_equal(three["cover"], want["bits"]) and three["lookup_s"] > 0

@@ -12,12 +12,11 @@ import pytest
 
 import fastq_ref
 import inputs
-import oracle
 import slice_ref
 
 pytestmark = pytest.mark.gpu
 
-N_SLICES = {17: 2, 19: 16, 21: 256}                      # slices of 2^33 (control) and 2^34 addresses
+N_SLICES = slice_ref.N_SLICES
 CHUNK = 16384
 
 
@@ -31,13 +30,6 @@ def _run(ix, exp, s, feeds, tag, full_table=False, name_off=None):
 def _cut(data, cuts):
     cuts = [0] + sorted(cuts) + [len(data)]
     return [data[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-
-
-def _seam_slice(exp, cut):
-    """The slice of the window that crosses byte `cut` of the text and reaches furthest back (slice_ref.first_window_at)."""
-    i = slice_ref.first_window_at(exp.data, exp.k, cut)
-    assert i < exp.kmers.size, cut
-    return exp.slice_of(exp.kmers[i])
 
 
 # ------------------------------------------------------------------ 1. k = 21, real slices ---------------------------
@@ -102,7 +94,7 @@ def _check_sites(exp, sites):
     need = {}
     for kind, d, off in sites:
         assert slice_ref.crossing_windows(exp.data, exp.k, off) == _site_crossing(kind, d, exp.k), (kind, d, off)
-        need[(kind, d, off)] = {_seam_slice(exp, off)}
+        need[(kind, d, off)] = {slice_ref.seam_slice(exp, off)}
     return need
 
 
@@ -173,18 +165,18 @@ def test_feed_seams(gpu, k, monkeypatch):
             assert set(seam_text[off - CHUNK:off]) <= set(b"\n ")
             add(("seam text", kind, "alone"), seam, _cut(seam_text, [off - CHUNK, off]), slices)
     deep_site = next(off for kind, d, off in sites if kind == "N" and d == k - 1)
-    add(("seam text", "bytewise"), seam, _cut(seam_text, range(deep_site - 32, deep_site + 33)), {_seam_slice(seam, deep_site)})
+    add(("seam text", "bytewise"), seam, _cut(seam_text, range(deep_site - 32, deep_site + 33)), {slice_ref.seam_slice(seam, deep_site)})
     rng = np.random.default_rng(40 + k)
     random_cuts = sorted(set(rng.integers(1, len(seam_text), size=40).tolist()))
-    add(("seam text", "random"), seam, _cut(seam_text, random_cuts), {_seam_slice(seam, c) for c in random_cuts})
+    add(("seam text", "random"), seam, _cut(seam_text, random_cuts), {slice_ref.seam_slice(seam, c) for c in random_cuts})
     for d, cut in n_cuts.items():
         assert plain_text[cut - d - 1] == ord("N") and slice_ref.crossing_windows(plain_text, k, cut) == min(d, k - 1)
-        add(("plain", "N", d), plain, _cut(plain_text, [cut]), {_seam_slice(plain, cut)})
+        add(("plain", "N", d), plain, _cut(plain_text, [cut]), {slice_ref.seam_slice(plain, cut)})
     for m, cut in mid.items():                               # the window that ends behind the short feed begins two feeds back
         assert slice_ref.crossing_windows(plain_text, k, cut) == k - 1
-        add(("plain", "middle feed", m), plain, _cut(plain_text, [cut - m, cut]), {_seam_slice(plain, cut)})
-    add(("plain", "empty feed"), plain, [plain_text[:empty_cut], b"", plain_text[empty_cut:]], {_seam_slice(plain, empty_cut)})
-    add(("plain", "library pieces"), plain, [plain_text], {_seam_slice(plain, pieces[0])}, piece=_PIECE)
+        add(("plain", "middle feed", m), plain, _cut(plain_text, [cut - m, cut]), {slice_ref.seam_slice(plain, cut)})
+    add(("plain", "empty feed"), plain, [plain_text[:empty_cut], b"", plain_text[empty_cut:]], {slice_ref.seam_slice(plain, empty_cut)})
+    add(("plain", "library pieces"), plain, [plain_text], {slice_ref.seam_slice(plain, pieces[0])}, piece=_PIECE)
     by_slice = slice_ref.cover(need)
     for s in sorted(by_slice):
         with gpu.Indexer(k, slice_index=s, n_slices=n) as ix:
@@ -230,7 +222,7 @@ def test_fastq_feed_seams(gpu, k):
     need = {}
     for d in cut_fq:
         assert slice_ref.crossing_windows(fa, k, cut_fa[d]) == min(d, k - 1)
-        need[d] = {_seam_slice(exp, cut_fa[d])}
+        need[d] = {slice_ref.seam_slice(exp, cut_fa[d])}
     for s, cuts in sorted(slice_ref.cover(need).items()):
         with gpu.Indexer(k, slice_index=s, n_slices=n, fmt="fastq") as ix:
             _run(ix, exp, s, [fq], (k, s, "one shot"), name_off=names_at)

@@ -2,73 +2,35 @@
 numpy restatement (extract_ref); exact equality everywhere."""
 import ctypes
 import json
-import os
-import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import extract_ref
 import inputs
 import oracle
-import synth
+from gpu_support import ROOT, SENTINEL, Device, HostTable, SentinelOut, index_cli, lib, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0xA5
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(max(16, t.size), 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-class _Out:
+class _Out(SentinelOut):
     """Output arrays of `cap` rows in HBM, filled with a sentinel."""
 
     def __init__(self, cap, P):
-        lib = _lib()
         self.cap, self.P = cap, P
-        self.addr = lib.DeviceBuffer(max(16, cap * 8), 0)
-        self.counts = lib.DeviceBuffer(max(16, cap * P), 0)
-        for b in (self.addr, self.counts):
-            b.upload(np.full(b.n, SENTINEL, dtype=np.uint8))
-
-    def untouched(self):
-        return all((b.download() == SENTINEL).all() for b in (self.addr, self.counts))
+        super().__init__(addr=max(16, cap * 8), counts=max(16, cap * P))
 
     def rows(self, m):
         return self.addr.download(m * 8).view(np.uint64), self.counts.download(m * self.P).reshape(m, self.P)
-
-    def free(self):
-        self.addr.free()
-        self.counts.free()
 
 
 def _run(ptrs, P, n, mn, mx, min_present, max_absent, cap, first_addr=0):
     """One pk_extract_device call into fresh sentinel-filled arrays of `cap` rows -> (n_selected, fits, addr, counts, untouched)."""
     out = _Out(cap, P)
     try:
-        m, fits, _ = _lib().extract_device(ptrs, P, n, first_addr, mn, mx, min_present, max_absent, out.addr.ptr, out.counts.ptr, cap)
+        m, fits, _ = lib().extract_device(ptrs, P, n, first_addr, mn, mx, min_present, max_absent, out.addr.ptr, out.counts.ptr, cap)
         if not fits:
             return m, False, None, None, out.untouched()
         addr, counts = out.rows(m)
@@ -83,7 +45,7 @@ def _check(present, absent, mn, mx, min_present=None, max_absent=0, first_addr=0
     n = present[0].size if n is None else n
     min_present = P if min_present is None else min_present
     want_addr, want_counts = extract_ref.expected([t[:n] for t in present], [t[:n] for t in absent], mn, mx, min_present, max_absent, first_addr)
-    with _Device(present + absent) as dev:
+    with Device(present + absent, min_bytes=16) as dev:
         m, fits, addr, counts, tail_ok = _run(dev.ptrs, P, n, mn, mx, min_present, max_absent, want_addr.size + 3, first_addr)
     assert m == want_addr.size and fits and tail_ok
     assert np.array_equal(addr, want_addr), np.flatnonzero(addr != want_addr)[:5]
@@ -108,7 +70,7 @@ def test_slice_sizes(gpu, n):
 def test_selection_density(gpu):
     n = 4 ** 7 + 17
     hold, none = np.full(n, 5, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-    with _Device([hold, none, hold]) as dev:
+    with Device([hold, none, hold], min_bytes=16) as dev:
         m, fits, addr, counts, untouched = _run(dev.ptrs, 2, n, 1, 255, 2, 0, 64)      # present: hold, none -> nothing selected
         assert (m, fits) == (0, True) and addr.size == 0 and untouched
         m, fits, addr, counts, untouched = _run([dev.ptrs[0], dev.ptrs[2]], 1, n, 1, 255, 1, 0, 64)   # absent holds everything
@@ -119,7 +81,7 @@ def test_selection_density(gpu):
         one[at] = 200
         rng = np.random.default_rng(at)
         other = rng.integers(1, 256, n).astype(np.uint8)
-        with _Device([one, other, none]) as dev:
+        with Device([one, other, none], min_bytes=16) as dev:
             m, fits, addr, counts, tail_ok = _run(dev.ptrs, 2, n, 1, 255, 2, 0, 1)
         assert (m, fits, tail_ok) == (1, True, True) and addr.tolist() == [at] and counts.tolist() == [[200, int(other[at])]]
 
@@ -221,12 +183,12 @@ def test_window_edges(gpu, mn, mx):
 
 # ------------------------------------------------------------------ 6. capacity --------------------
 def test_capacity(gpu):
-    lib = _lib()
+    lib = gs.lib()
     tables = extract_ref.mixed_tables(4 ** 7 + 17, 3, seed=6)
     want_addr, want_counts = extract_ref.expected(tables[:2], tables[2:], 2, 200, 1, 0)
     M = want_addr.size
     assert M > 100
-    with _Device(tables) as dev:
+    with Device(tables, min_bytes=16) as dev:
         m, fits, _, _, untouched = _run(dev.ptrs, 2, tables[0].size, 2, 200, 1, 0, M - 1)
         assert (m, fits, untouched) == (M, False, True)
         out = _Out(M - 1, 2)
@@ -245,10 +207,10 @@ def test_capacity(gpu):
 
 # ------------------------------------------------------------------ 7. arguments -------------------
 def test_bad_arguments_are_refused(gpu):
-    lib = _lib()
+    lib = gs.lib()
     n = 4096
     t = np.full(n, 3, dtype=np.uint8)
-    with _Device([t]) as dev:
+    with Device([t], min_bytes=16) as dev:
         p = dev.ptrs[0]
         out = _Out(16, 1)
         count = ctypes.c_uint64(0)
@@ -284,7 +246,7 @@ def test_text(gpu, k):
     """Every odd k and the largest one: a thread writes 16 bytes and a line is k + 1, so where lines end inside a thread's
     bytes differs with (k + 1) mod 16; from k = 18 on the addresses need more than 35 bits.  1000 lines are two
     workgroups or more from k = 5 on."""
-    lib = _lib()
+    lib = gs.lib()
     rng = np.random.default_rng(k)
     for m in (1, 2, 7, 1000):
         addr = rng.integers(0, 4 ** k, m, dtype=np.uint64)
@@ -308,24 +270,14 @@ def test_text(gpu, k):
 
 
 # ------------------------------------------------------------------ 9. the whole path, small -------
-class _HostTable:
-    """What the staging loop needs of a Header, backed by a host array."""
-
-    def __init__(self, k, name, table):
-        self.kmer_len, self.index_file, self.data_size, self.table = k, name, 4 ** k, table
-
-    def read_table_slice(self, lo, hi, threads=None):
-        return self.table[lo:hi]
-
-
 def test_whole_path_under_a_small_budget(gpu, monkeypatch):
     from pykmer_amd import extract
     k = 9
     x, y = inputs.record_dense_fasta(27 + 61 * 1000, 9, seed=3), inputs.record_dense_fasta(27 + 61 * 500, 9, seed=4)
     texts = [inputs.edge_fasta() + x, x + y + inputs.byte_soup(20_000, 5), y]
-    counted = [_lib().count_fasta(t, k, device=0)["table"].copy() for t in texts]
+    counted = [lib().count_fasta(t, k, device=0)["table"].copy() for t in texts]
     want_tables = [oracle.count_fasta(t, k)["table"] for t in texts]
-    tables = [_HostTable(k, f"t{i}.kin", t) for i, t in enumerate(counted)]
+    tables = [HostTable(k, f"t{i}.kin", t) for i, t in enumerate(counted)]
     want = extract_ref.expected(want_tables[:2], want_tables[2:], 1, 255, 2, 0)
     assert want[0].size > 100
     monkeypatch.delenv("PK_MERGE_HBM_BUDGET", raising=False)
@@ -346,7 +298,7 @@ def test_whole_path_under_a_small_budget(gpu, monkeypatch):
 # ------------------------------------------------------------------ 10. one full-size case ---------
 def test_full_size_table(gpu):
     """k = 15: 2^30 addresses, 65536 workgroups (64 rounds of the scan), ranks far beyond one workgroup's."""
-    lib = _lib()
+    lib = gs.lib()
     k, n = 15, 4 ** 15
     pool_a = np.zeros(64, dtype=np.uint8)
     pool_a[[3, 17, 18, 40, 63]] = [2, 200, 201, 1, 77]
@@ -360,7 +312,7 @@ def test_full_size_table(gpu):
     M = int(np.count_nonzero(mask))
     want_addr = np.flatnonzero(mask).astype(np.uint64)
     assert 2 ** 25 < M < 2 ** 26
-    with _Device([a, b]) as dev:
+    with Device([a, b], min_bytes=16) as dev:
         addr, counts = lib.DeviceBuffer(M * 8, 0), lib.DeviceBuffer((M + 15) // 16 * 16, 0)
         m, fits, secs = lib.extract_device(dev.ptrs, 1, n, 0, 2, 200, 1, 0, addr.ptr, counts.ptr, M)
         assert (m, fits) == (M, True) and secs > 0
@@ -396,27 +348,14 @@ def test_scan_second_round_of_one_workgroup(gpu):
 
 
 # ------------------------------------------------------------------ 11. CLI ------------------------
-def _cli(*argv, cwd, ok=True):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert (r.returncode == 0) == ok, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_cli_end_to_end(gpu, tmp_path):
     k = 9
-    kins, tables = [], []
-    for i in range(3):
-        fa = tmp_path / f"s{i}.fa"
-        data = bytes(synth.family(i, 20_000)[0])
-        fa.write_bytes(data)
-        _cli(os.path.join(ROOT, "indexer.py"), str(fa), f"s{i}", str(k), cwd=str(tmp_path))
-        kins.append(f"{fa}.{k:02d}.kin")
-        tables.append(oracle.count_fasta(data, k)["table"])
+    kins, tables = index_cli(tmp_path, ("s0", "s1", "s2"), k)
     want = extract_ref.expected(tables[:2], tables[2:], 1, 250, 1, 0)
     proj = str(tmp_path / "proj")
-    argv = [os.path.join(ROOT, "extract.py"), proj, "--present", kins[0], kins[1], "--absent", kins[2], "--max-count", "250", "--min-present", "1",
+    argv = ["extract.py", proj, "--present", kins[0], kins[1], "--absent", kins[2], "--max-count", "250", "--min-present", "1",
             "--kmers"]
-    r = _cli(*argv, cwd=str(tmp_path))
+    r = run_py(*argv, cwd=str(tmp_path))
     assert f"{want[0].size:,d} k-mers selected" in r.stdout
     z = np.load(proj + ".kmx")
     assert np.array_equal(z["addr"], want[0]) and np.array_equal(z["counts"], want[1]) and z["addr"].dtype == np.uint64
@@ -429,9 +368,9 @@ def test_cli_end_to_end(gpu, tmp_path):
     assert len(lines) == want[0].size + 1 and lines[-1] == b"" and all(len(ln) == k and set(ln) <= set(b"ACGT") for ln in lines[:-1])
     assert b"\n".join(lines) == extract_ref.decode(want[0], k).tobytes()
     before = [open(proj + ext, "rb").read() for ext in (".kmx", ".kmx.json", ".kmx.txt")]
-    r = _cli(*argv, cwd=str(tmp_path), ok=False)              # a second run refuses to overwrite
+    r = run_py(*argv, cwd=str(tmp_path), status=1)              # a second run refuses to overwrite
     assert r.returncode == 1 and "error:" in r.stderr and "already exists" in r.stderr
     assert before == [open(proj + ext, "rb").read() for ext in (".kmx", ".kmx.json", ".kmx.txt")]
-    r = _cli("-m", "pykmer_amd.extract", str(tmp_path / "twice"), "--present", kins[0], "--absent", kins[0], cwd=ROOT, ok=False)
+    r = run_py("-m", "pykmer_amd.extract", str(tmp_path / "twice"), "--present", kins[0], "--absent", kins[0], cwd=ROOT, status=1)
     assert "named twice" in r.stderr
 

@@ -1,20 +1,17 @@
 """GPU: FASTQ input (fastq.hip) counted exactly like the FASTA text it stands for (fastq_ref.fastq_to_fasta)."""
 import gzip
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import fastq_ref
 import oracle
-from fastq_ref import fastq_to_fasta
-from test_fastq_host import CASES, MALFORMED
+from fastq_ref import CASES, MALFORMED, fastq_to_fasta
+from gpu_support import check_fastq_against_oracle, count_fastq, env_without_ranks, lib, record_names, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _adversarial() -> bytes:
@@ -24,62 +21,22 @@ def _adversarial() -> bytes:
     return fq + b"@last\r\nACGTTTGACCA\r\n+\r\n@>+ACGTIIII"
 
 
-def _count(lib, fq: bytes, k: int, cuts=None, n_slices: int = 1, slice_index: int = 0):
-    """FASTQ through one indexer, fed whole or in the given pieces; table, totals, records, stats."""
-    with lib.Indexer(k, device=0, fmt="fastq", slice_index=slice_index, n_slices=n_slices) as ix:
-        if cuts is None:
-            ix.feed(fq)
-        else:
-            pos = 0
-            for c in list(cuts) + [len(fq)]:
-                if c > pos:
-                    ix.feed(np.frombuffer(fq, dtype=np.uint8)[pos:c])
-                    pos = c
-        fin = ix.finish()
-        fin["records"] = ix.records(fin["n_records"])
-        fin["stats"] = ix.fastq_stats()
-        fin["table"] = ix.table_to_host() if k <= 15 else None
-        return fin
-
-
-def _names(fq: bytes, recs):
-    return [(fq[int(r["name_off"]):int(r["name_off"]) + int(r["name_len"])], int(r["seq_len"]), int(r["n_valid_kmers"])) for r in recs]
-
-
-def _check_against_oracle(got, fq: bytes, k: int):
-    fa = fastq_to_fasta(fq)
-    want = oracle.count_fasta(fa, k)
-    assert got["num_kmers"] == want["num_kmers"] and got["total_bp"] == want["total_bp"]
-    assert np.array_equal(got["table"], want["table"])
-    hist, _ = oracle.table_stats(want["table"])
-    assert np.array_equal(got["hist256"][1:], hist)
-    w = want["records"]
-    assert got["n_records"] == len(w)
-    assert _names(fq, got["records"]) == _names(fa, w)       # names sliced from the FASTQ equal those of the FASTA
-    assert got["stats"] == fastq_ref.stats(fq)
-
-
 @pytest.mark.parametrize("k", [3, 7, 15])
 def test_adversarial_cases(gpu, k):
     fq = _adversarial()
-    _check_against_oracle(_count(_lib(), fq, k), fq, k)
-
-
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
+    check_fastq_against_oracle(count_fastq(fq, k), fq, k)
 
 
 @pytest.mark.parametrize("name,fq,fa", CASES, ids=[c[0] for c in CASES])
 def test_each_case_alone(gpu, name, fq, fa):
-    got = _count(_lib(), fq, 7)
+    got = count_fastq(fq, 7)
     assert got["stats"]["bytes_emitted"] == len(fa)
-    _check_against_oracle(got, fq, 7)
+    check_fastq_against_oracle(got, fq, 7)
 
 
 def test_k17_matches_fasta_path(gpu):
     """k = 17 (a 16 GiB table): the FASTQ path and the FASTA path on the converted text agree byte for byte."""
-    lib = _lib()
+    lib = gs.lib()
     fq, fa = fastq_ref.read_set(20_000, length=150, seed=17, genome_bp=200_000)
     fq = _adversarial() + b"\r\n" + fq
     fa = fastq_to_fasta(fq)
@@ -91,7 +48,7 @@ def test_k17_matches_fasta_path(gpu):
         for key in ("num_kmers", "total_bp", "n_records"):
             assert fa_[key] == fb_[key], key
         assert np.array_equal(fa_["hist256"], fb_["hist256"])
-        assert _names(fq, a.records(fa_["n_records"])) == _names(fa, b.records(fb_["n_records"]))
+        assert record_names(fq, a.records(fa_["n_records"])) == record_names(fa, b.records(fb_["n_records"]))
         ta, tb = np.empty(step, dtype=np.uint8), np.empty(step, dtype=np.uint8)
         for off in range(0, 4 ** k, step):
             a.table_slice_to_host(ta, off)
@@ -109,12 +66,12 @@ def test_long_single_line_read(gpu):
     fq = b"@long read\n" + seq.tobytes() + b"\n+\n" + bytes(rng.integers(33, 74, seq.size, dtype=np.uint8)) + b"\n"
     fq += b"@short\nACGTACGTAAAC\n+\nIIIIIIIIIIII\n"
     for cuts in (None, [7, 1 << 20, (1 << 20) + 1, 2_500_020, 2_500_021, 4_000_000]):
-        _check_against_oracle(_count(_lib(), fq, 15, cuts=cuts), fq, 15)
+        check_fastq_against_oracle(count_fastq(fq, 15, cuts=cuts), fq, 15)
 
 
 def test_million_short_reads_grow_the_record_array(gpu):
     fq, fa = fastq_ref.read_set(1_100_000, length=24, seed=11, genome_bp=1 << 16, n_rate=0.01)
-    got = _count(_lib(), fq, 7)
+    got = count_fastq(fq, 7)
     want = oracle.count_fasta(fa, 7)
     assert got["num_kmers"] == want["num_kmers"] and got["total_bp"] == want["total_bp"]
     assert np.array_equal(got["table"], want["table"])
@@ -123,7 +80,7 @@ def test_million_short_reads_grow_the_record_array(gpu):
     assert np.array_equal(got["records"]["n_valid_kmers"], want["records"]["n_valid_kmers"])
     assert np.array_equal(got["records"]["name_len"], want["records"]["name_len"])
     i = np.array([0, 1, 777, 500_000, 1_099_999])
-    assert _names(fq, got["records"][i]) == _names(fa, want["records"][i])
+    assert record_names(fq, got["records"][i]) == record_names(fa, want["records"][i])
     assert got["stats"] == {"records": 1_100_000, "lines": 4_400_000, "bytes_fed": len(fq), "bytes_emitted": len(fa)}
 
 
@@ -149,9 +106,9 @@ def test_random_cuts_give_identical_results(gpu, crlf):
     rng = np.random.default_rng(21 + crlf)
     fq, _ = fastq_ref.read_set(40_000, length=150, seed=4 + crlf, genome_bp=1 << 18, crlf=crlf)
     fq = _adversarial() + b"\r\n" + fq
-    whole = _count(_lib(), fq, 15)
-    _check_against_oracle(whole, fq, 15)
-    cut = _count(_lib(), fq, 15, cuts=_cuts(fq, rng, 100))
+    whole = count_fastq(fq, 15)
+    check_fastq_against_oracle(whole, fq, 15)
+    cut = count_fastq(fq, 15, cuts=_cuts(fq, rng, 100))
     for key in ("num_kmers", "total_bp", "n_records", "stats"):
         assert cut[key] == whole[key], key
     assert np.array_equal(cut["table"], whole["table"]) and np.array_equal(cut["hist256"], whole["hist256"])
@@ -160,7 +117,7 @@ def test_random_cuts_give_identical_results(gpu, crlf):
 
 def test_read_set_200mbp_matches_gpu_fasta_path(gpu):
     """~200 Mbp of 150 bp reads at k = 15 through feed_device: the FASTQ table is byte-identical to the FASTA path's."""
-    lib = _lib()
+    lib = gs.lib()
     fq, fa = fastq_ref.read_set(1_350_000, length=150, seed=9, genome_bp=50_000_000)
     tables, fins = [], []
     for data, fmt in ((fq, "fastq"), (fa, "fasta")):
@@ -181,14 +138,14 @@ def test_read_set_200mbp_matches_gpu_fasta_path(gpu):
     for f in ("name_len", "seq_len", "n_valid_kmers"):
         assert np.array_equal(fins[0]["records"][f], fins[1]["records"][f])
     i = np.array([0, 12345, 1_349_999])
-    assert _names(fq, fins[0]["records"][i]) == _names(fa, fins[1]["records"][i])
+    assert record_names(fq, fins[0]["records"][i]) == record_names(fa, fins[1]["records"][i])
 
 
 def test_address_slices_concatenate(gpu):
     fq, _ = fastq_ref.read_set(30_000, length=150, seed=8, genome_bp=1 << 18)
     fq = _adversarial() + b"\r\n" + fq
-    whole = _count(_lib(), fq, 15)
-    parts = [_count(_lib(), fq, 15, n_slices=4, slice_index=s) for s in range(4)]
+    whole = count_fastq(fq, 15)
+    parts = [count_fastq(fq, 15, n_slices=4, slice_index=s) for s in range(4)]
     assert np.array_equal(np.concatenate([p["table"] for p in parts]), whole["table"])
     assert sum(p["hist256"][1:].sum() for p in parts) == whole["hist256"][1:].sum()
     for p in parts:
@@ -197,7 +154,7 @@ def test_address_slices_concatenate(gpu):
 
 @pytest.mark.parametrize("name,fq,rec,rule", MALFORMED, ids=[c[0] for c in MALFORMED])
 def test_malformed_then_reset(gpu, name, fq, rec, rule):
-    lib = _lib()
+    lib = gs.lib()
     good, _ = fastq_ref.read_set(300, length=60, seed=2, genome_bp=5000)
     for cuts in (None, list(range(1, len(fq)))):                    # whole, and one byte per feed
         with lib.Indexer(7, fmt="fastq") as ix:
@@ -218,11 +175,11 @@ def test_malformed_then_reset(gpu, name, fq, rec, rule):
             ix.feed(good)
             fin = ix.finish()
             fin["records"], fin["stats"], fin["table"] = ix.records(fin["n_records"]), ix.fastq_stats(), ix.table_to_host()
-            _check_against_oracle(fin, good, 7)
+            check_fastq_against_oracle(fin, good, 7)
 
 
 def test_format_is_set_before_the_first_feed(gpu):
-    lib = _lib()
+    lib = gs.lib()
     fq, _ = fastq_ref.read_set(10, length=30, seed=1, genome_bp=1000)
     with lib.Indexer(7) as ix:
         ix.feed(fq[:0])
@@ -238,18 +195,6 @@ def test_format_is_set_before_the_first_feed(gpu):
         assert lib.load().pk_indexer_set_format(ix._h, 7) == lib.PK_ERR_ARG
 
 
-def _run(*argv, cwd, env=None):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=900, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
-# .kin.json fields that depend on the counts alone (not on the input file, the clock or the host)
-DETERMINISTIC = ("chromosomes", "data_size", "file_ver", "flush_every", "frag_size", "hist", "hist_count", "hist_max", "hist_min",
-                 "hist_sum", "kmer_len", "kmer_size", "max_size", "num_kmers", "output_file_cheksum", "output_file_size",
-                 "vals_count", "vals_max", "vals_min", "vals_sum")
-
-
 def test_indexer_cli_fastq_plain_gz_bgz(gpu, tmp_path):
     from pykmer_amd import bgzf
     fq, fa = fastq_ref.read_set(5000, length=100, seed=6, genome_bp=100_000)
@@ -261,18 +206,18 @@ def test_indexer_cli_fastq_plain_gz_bgz(gpu, tmp_path):
         fh.write(fq)
     bgzf.compress_file(str(tmp_path / "reads.fq"), str(tmp_path / "reads.fq.bgz"))
     assert bgzf.is_bgzf(str(tmp_path / "reads.fq.bgz"))
-    out = _run(os.path.join(ROOT, "indexer.py"), str(tmp_path / "reads.fa"), "s", "9", cwd=str(tmp_path))
+    out = run_py("indexer.py", str(tmp_path / "reads.fa"), "s", "9", cwd=str(tmp_path), timeout=900).stdout
     assert "READING FASTA FROM" in out
     with open(tmp_path / "reads.fa.09.kin.json") as fh:
         want = json.load(fh)
     kin_fa = (tmp_path / "reads.fa.09.kin").read_bytes()
     for name in ("reads.fq", "reads.fq.gz", "reads.fq.bgz"):
-        out = _run(os.path.join(ROOT, "indexer.py"), str(tmp_path / name), "s", "9", cwd=str(tmp_path))
+        out = run_py("indexer.py", str(tmp_path / name), "s", "9", cwd=str(tmp_path), timeout=900).stdout
         assert "READING FASTQ FROM" in out and "READING FASTA" not in out
         with open(tmp_path / f"{name}.09.kin.json") as fh:
             got = json.load(fh)
         assert sorted(got) == sorted(want)                            # same schema, no new key
-        for key in DETERMINISTIC:
+        for key in fastq_ref.DETERMINISTIC:
             assert got[key] == want[key], (name, key)
         assert (tmp_path / f"{name}.09.kin").read_bytes() == kin_fa
         assert len(got["chromosomes"]) == len(want["chromosomes"]) > 5000
@@ -286,17 +231,14 @@ def test_merger_kwip_over_fastq_tables(gpu, tmp_path):
         fq, _ = fastq_ref.read_set(1000 + 500 * i, length=150, seed=30 + i, genome=genome)
         p = tmp_path / f"s{i}.fastq"
         p.write_bytes(fq)
-        _run(os.path.join(ROOT, "indexer.py"), str(p), f"s{i}", "11", cwd=str(tmp_path))
+        run_py("indexer.py", str(p), f"s{i}", "11", cwd=str(tmp_path), timeout=900)
         kins.append(f"{p}.11.kin")
-    env = dict(os.environ)
-    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(v, None)
-    _run(os.path.join(ROOT, "merger.py"), str(tmp_path / "kw"), *kins, "--kwip", cwd=str(tmp_path), env=env)
+    run_py("merger.py", str(tmp_path / "kw"), *kins, "--kwip", cwd=str(tmp_path), timeout=900, env=env_without_ranks())
     k = np.loadtxt(tmp_path / "kw.kern", skiprows=1, usecols=range(1, 4))
     d = np.loadtxt(tmp_path / "kw.dist", skiprows=1, usecols=range(1, 4))
     assert k.shape == d.shape == (3, 3) and np.all(np.isfinite(k)) and np.all(np.isfinite(d)) and np.allclose(d, d.T)
     assert np.all(k > 0) and np.all(np.diag(d) == 0) and np.all(d[~np.eye(3, dtype=bool)] > 0)
-    from test_kwip_host import direct_kernel
+    from merge_ref import direct_kernel
     from pykmer_amd import merger
     tabs = [merger.Header(x, index_file=x).read_table_slice(0, 4 ** 11) for x in sorted(kins)]
     assert np.allclose(k, direct_kernel(tabs), rtol=1e-12, atol=0)
@@ -329,7 +271,7 @@ def test_record_overflow_after_a_relayout_feed(gpu):
     text is counted one call late: the first text's relayout happens in the second feed call, the second text's record
     retry inside finish."""
     import inputs
-    from test_gpu_indexer import _record_starts, record_overflows
+    from inputs import record_overflows, record_starts
     k = 15
     fa1 = inputs.skewed_fasta(20_000_000, 61, seed=72, width=None)
     head, seq = fa1.split(b"\n")[:2]
@@ -337,19 +279,19 @@ def test_record_overflow_after_a_relayout_feed(gpu):
     assert fastq_to_fasta(fq1) == fa1
     fq2, fa2 = _padded_reads(len(fa1), 120_000, 100, seed=73)
     fq, fa = fq1 + fq2, fa1 + fa2
-    with _lib().Indexer(k, fmt="fastq") as ix:
+    with lib().Indexer(k, fmt="fastq") as ix:
         ix.feed(fq1)
         ix.feed(fq2)
         assert ix.timings()["relayouts"] >= 1, "the long read was meant to overflow the sampled layout"
         fin = ix.finish()
         got = dict(fin, records=ix.records(fin["n_records"]), stats=ix.fastq_stats(), table=ix.table_to_host())
     want = oracle.count_fasta(fa, k)
-    assert record_overflows([len(fa1), len(fa2)], _record_starts(want["records"])) == [False, True]
+    assert record_overflows([len(fa1), len(fa2)], record_starts(want["records"])) == [False, True]
     assert got["num_kmers"] == want["num_kmers"] and got["total_bp"] == want["total_bp"]
     assert got["n_records"] == len(want["records"]) == 120_001
     for f in ("name_len", "seq_len", "n_valid_kmers"):
         assert np.array_equal(got["records"][f], want["records"][f]), f
-    assert _names(fq, got["records"]) == _names(fa, want["records"])        # name_off: the same names, sliced from the FASTQ
+    assert record_names(fq, got["records"]) == record_names(fa, want["records"])        # name_off: the same names, sliced from the FASTQ
     assert np.array_equal(got["hist256"][1:], oracle.table_stats(want["table"])[0])
     assert np.array_equal(got["table"], want["table"])
     assert got["stats"] == fastq_ref.stats(fq)

@@ -4,37 +4,21 @@ path -- however the stream is cut into feeds; every comparison is exact."""
 import functools
 import gzip
 import json
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import fastq_ref
 import oracle
 import query_ref
 from fastq_qual_ref import biased_qualities, hand_qualities, mask_fastq_to_fasta
-from test_fastq_host import CASES
+from fastq_ref import CASES
+from gpu_support import Device, feed, lib, record_names, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THRESHOLDS = [1, 34, 53, 255]
-
-
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-def _feed(ix, data: bytes, cuts=None):
-    buf = np.frombuffer(data, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(data)]:
-        if c > pos:
-            ix.feed(buf[pos:c])
-            pos = c
 
 
 def _finish(ix, fastq: bool = True):
@@ -49,17 +33,13 @@ def _finish(ix, fastq: bool = True):
 def _count(fq: bytes, k: int, T: int, cuts=None, ix=None):
     """FASTQ under threshold byte T, fed whole or in pieces; through `ix` (which is reset behind it) or an indexer of its own."""
     if ix is not None:
-        _feed(ix, fq, cuts)
+        feed(ix, fq, cuts)
         fin = _finish(ix)
         ix.reset()
         return fin
-    with _lib().Indexer(k, device=0, fmt="fastq", min_qual_byte=T) as own:
-        _feed(own, fq, cuts)
+    with lib().Indexer(k, device=0, fmt="fastq", min_qual_byte=T) as own:
+        feed(own, fq, cuts)
         return _finish(own)
-
-
-def _names(text: bytes, recs):
-    return [(text[int(r["name_off"]):int(r["name_off"]) + int(r["name_len"])], int(r["seq_len"]), int(r["n_valid_kmers"])) for r in recs]
 
 
 def _check(got, fq: bytes, k: int, T: int, want=None):
@@ -72,7 +52,7 @@ def _check(got, fq: bytes, k: int, T: int, want=None):
     hist = want["hist256"][1:] if "hist256" in want else oracle.table_stats(want["table"])[0]
     assert np.array_equal(got["hist256"][1:], hist)
     assert got["n_records"] == len(want["records"])
-    assert _names(fq, got["records"]) == _names(fa, want["records"])
+    assert record_names(fq, got["records"]) == record_names(fa, want["records"])
     assert got["stats"] == fastq_ref.stats(fq)
 
 
@@ -100,7 +80,7 @@ def _stream(eol: bytes) -> bytes:
 
 @pytest.mark.parametrize("T", THRESHOLDS)
 def test_each_hand_case_alone(gpu, T):
-    with _lib().Indexer(7, device=0, fmt="fastq", min_qual_byte=T) as ix:
+    with lib().Indexer(7, device=0, fmt="fastq", min_qual_byte=T) as ix:
         for i, (name, fq) in enumerate(ALONE):
             fq = hand_qualities(fq, T, seed=100 * T + i)
             _check(_count(fq, 7, T, ix=ix), fq, 7, T)
@@ -122,7 +102,7 @@ def test_cuts_give_identical_results(gpu, T):
     fq = hand_qualities(_stream(b"\r\n"), T, seed=7)
     assert 300 < len(fq) < 1000
     rng = np.random.default_rng(T)
-    with _lib().Indexer(7, device=0, fmt="fastq", min_qual_byte=T) as ix:
+    with lib().Indexer(7, device=0, fmt="fastq", min_qual_byte=T) as ix:
         whole = _count(fq, 7, T, ix=ix)
         _check(whole, fq, 7, T)
         _same(_count(fq, 7, T, cuts=range(1, len(fq)), ix=ix), whole)          # one byte per feed
@@ -142,11 +122,11 @@ def test_long_read_quality_many_feeds_behind_its_bases(gpu):
     fq = biased_qualities(fq, T, 0.3, seed=41)
     fa, n_masked = mask_fastq_to_fasta(fq, T)
     assert 10_000 < n_masked < 14_000
-    with _lib().Indexer(k, device=0) as ref:                               # the GPU FASTA path on the masked text
+    with lib().Indexer(k, device=0) as ref:                               # the GPU FASTA path on the masked text
         ref.feed(fa)
         want = _finish(ref, fastq=False)
     edges = sorted({c for s, e, t in fastq_ref.lines(fq) for x in (s, e, t) for c in (x - 1, x, x + 1) if 0 < c < len(fq)})
-    with _lib().Indexer(k, device=0, fmt="fastq", min_qual_byte=T) as ix:
+    with lib().Indexer(k, device=0, fmt="fastq", min_qual_byte=T) as ix:
         for cuts in (None, range(4096, len(fq), 4096), edges):
             _check(_count(fq, k, T, cuts=cuts, ix=ix), fq, k, T, want=want)
 
@@ -182,7 +162,7 @@ def test_only_the_valid_windows_change(gpu, T):
     assert plain["masked"] == 0 and plain["stats"] == masked["stats"]
     for f in ("name_off", "name_len", "seq_len"):
         assert np.array_equal(masked["records"][f], plain["records"][f]), f
-    assert [n for n, _, _ in _names(fq, masked["records"])] == [n for n, _, _ in _names(fq, plain["records"])]
+    assert [n for n, _, _ in record_names(fq, masked["records"])] == [n for n, _, _ in record_names(fq, plain["records"])]
     assert np.all(masked["records"]["n_valid_kmers"] <= plain["records"]["n_valid_kmers"])
     assert masked["num_kmers"] < plain["num_kmers"] and masked["total_bp"] == plain["total_bp"]
 
@@ -209,7 +189,7 @@ def test_the_count_stays_exact_when_the_front_end_runs_twice(gpu):
 def test_a_quality_line_longer_than_its_bases(gpu, surplus):
     """Line 4 of record 2 is longer than line 2, all of it low: the same error as without masking, and the surplus bytes
     reach no text -- after a reset a good file counts right on the same buffers."""
-    lib = _lib()
+    lib = gs.lib()
     T = 53
     fq = b"@r1\nACGTACGTACGT\n+\n!!!!!!!!!!!!\n@r2\nACGTAC\n+\n" + b"!" * (6 + surplus) + b"\n@r3\nACGTACGTAA\n+\n!!!!!!!!!!\n"
     want = fastq_ref.FastqError(2, fq.index(b"@r2"), 4)
@@ -219,7 +199,7 @@ def test_a_quality_line_longer_than_its_bases(gpu, surplus):
         for bytewise in (False, True):
             with lib.Indexer(7, device=0, fmt="fastq", min_qual_byte=T if masked else 0) as ix:
                 with pytest.raises(lib.PkError) as e:
-                    _feed(ix, fq, range(1, len(fq)) if bytewise else None)
+                    feed(ix, fq, range(1, len(fq)) if bytewise else None)
                     ix.finish()
                 assert e.value.code == lib.PK_ERR_FORMAT and str(want) in str(e.value), str(e.value)
                 messages.append(str(e.value))
@@ -230,10 +210,10 @@ def test_a_quality_line_longer_than_its_bases(gpu, surplus):
 
 # ------------------------------------------------------------------ off is off, state rules --------
 def test_off_is_off(gpu):
-    lib = _lib()
+    lib = gs.lib()
     fq = _seam_set(0)
     with lib.Indexer(9, device=0, fmt="fastq") as never:
-        _feed(never, fq)
+        feed(never, fq)
         want = _finish(never)
     got = _count(fq, 9, 0)
     with lib.Indexer(9, device=0, fmt="fastq", min_qual_byte=53) as ix:     # set, then set back before the first feed
@@ -245,7 +225,7 @@ def test_off_is_off(gpu):
 
 
 def test_state_rules(gpu):
-    lib = _lib()
+    lib = gs.lib()
     set_min_qual = lib.load().pk_indexer_set_min_qual
     fq = biased_qualities(fastq_ref.read_set(10, length=30, seed=1, genome_bp=1000)[0], 53, 0.3, seed=6)
     with lib.Indexer(7, device=0) as ix:                                     # a FASTA indexer
@@ -273,16 +253,6 @@ def test_state_rules(gpu):
 
 
 # ------------------------------------------------------------------ query --------------------------
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-
 def test_query_masks_like_the_indexer(gpu, tmp_path):
     from pykmer_amd import query
     k, W, Q = 7, 5, 20
@@ -294,7 +264,7 @@ def test_query_masks_like_the_indexer(gpu, tmp_path):
     tables = [types.SimpleNamespace(kmer_len=k, index_file=f"t{i}.kin", data_size=4 ** k, table=t) for i, t in enumerate(dense)]
 
     def stage(group, device):
-        dev = _Device([g.table for g in group])
+        dev = Device([g.table for g in group])
         return query.Staged(dev.ptrs, dev.bufs)
 
     got = query.query_records(str(tmp_path / "q.fq"), tables, 1, 255, device=0, stage=stage, min_qual=Q, bin_windows=W, coords=True)
@@ -311,14 +281,7 @@ def test_query_masks_like_the_indexer(gpu, tmp_path):
 
 
 # ------------------------------------------------------------------ CLI ----------------------------
-def _run(*argv, cwd, status=0):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == status, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_indexer_cli(gpu, tmp_path):
-    from test_gpu_fastq import DETERMINISTIC
     Q = 20
     fq = biased_qualities(fastq_ref.read_set(200, length=100, seed=6, genome_bp=5000)[0], Q + 33, 0.3, seed=11)
     fa, n_masked = mask_fastq_to_fasta(fq, Q + 33)
@@ -326,19 +289,18 @@ def test_indexer_cli(gpu, tmp_path):
     (tmp_path / "reads.fq").write_bytes(fq)
     with gzip.open(tmp_path / "reads.fq.gz", "wb") as fh:
         fh.write(fq)
-    indexer_py = os.path.join(ROOT, "indexer.py")
-    out = _run(indexer_py, "masked.fa", "s", "7", cwd=str(tmp_path)).stdout
+    out = run_py("indexer.py", "masked.fa", "s", "7", cwd=str(tmp_path)).stdout
     assert "MASKED" not in out
     want = json.loads((tmp_path / "masked.fa.07.kin.json").read_text())
     kin = (tmp_path / "masked.fa.07.kin").read_bytes()
     for name, argv in (("reads.fq", ["reads.fq", "s", "7", "--min-qual", str(Q)]), ("reads.fq.gz", ["--min-qual", str(Q), "reads.fq.gz", "--qual-offset=33", "7"])):
-        out = _run(indexer_py, *argv, cwd=str(tmp_path)).stdout
+        out = run_py("indexer.py", *argv, cwd=str(tmp_path)).stdout
         assert f"MASKED {n_masked} bases below quality {Q} (offset 33)\n" in out
         got = json.loads((tmp_path / f"{name}.07.kin.json").read_text())
         assert sorted(got) == sorted(want)                                 # the reference's keys, no new one
-        for key in DETERMINISTIC:
+        for key in fastq_ref.DETERMINISTIC:
             assert got[key] == want[key], (name, key)
         assert (tmp_path / f"{name}.07.kin").read_bytes() == kin
     before = sorted(p.name for p in tmp_path.iterdir())
-    r = _run(indexer_py, "masked.fa", "t", "9", "--min-qual", str(Q), cwd=str(tmp_path), status=1)
+    r = run_py("indexer.py", "masked.fa", "t", "9", "--min-qual", str(Q), cwd=str(tmp_path), status=1)
     assert any(line.startswith("error: ") for line in r.stderr.splitlines()) and sorted(p.name for p in tmp_path.iterdir()) == before

@@ -4,8 +4,6 @@ written file is compared byte for byte."""
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,9 +11,10 @@ import pytest
 import filter_ref
 import query_ref
 from fastq_qual_ref import mask_fastq_to_fasta
+from gpu_support import run_py
+from host_support import write_kin
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DONOR = b"TTGACCAGGTAACGTACGTTAGCACGTGGATCCAATTGGCACTGA"
 HOST = b"GATTACAGATTACAGGTACCTTAGGCATCGATCGGATATCCGGA"
@@ -44,12 +43,11 @@ FASTQ_BLANKS = FASTQ + b"\n\r\n\n"                            # blank lines behi
 @pytest.fixture(scope="module")
 def tables(gpu, tmp_path_factory):
     """{k: ([donor.kin, host.kin], [donor table, host table])} at k = 5 and 7, indexed here."""
-    from test_host_layer import _write_index
     d = tmp_path_factory.mktemp("filter_tables")
     out = {}
     for k in (5, 7):
-        got = [_write_index(d, f"{name}{k}.fa", b">" + name.encode() + b"\n" + seq + b"\n", k) for name, seq in (("donor", DONOR), ("host", HOST))]
-        out[k] = ([h.index_file_root for h, _ in got], [g["table"] for _, g in got])
+        got = [write_kin(d, f"{name}{k}.fa", b">" + name.encode() + b"\n" + seq + b"\n", k) for name, seq in (("donor", DONOR), ("host", HOST))]
+        out[k] = ([w.path for w in got], [w.table for w in got])
     return out
 
 
@@ -199,19 +197,18 @@ def test_cli(gpu, tables, tmp_path):
     with gzip.open(path, "wb") as fh:
         fh.write(FASTQ_BLANKS)
     proj = str(tmp_path / "cli")
-    argv = [sys.executable, os.path.join(ROOT, "filter.py"), proj, str(path)] + kins + ["--min-hits", "4", "--min-percent", "30", "--invert", "--rest"]
-    r = subprocess.run(argv, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    argv = ["filter.py", proj, str(path)] + kins + ["--min-hits", "4", "--min-percent", "30", "--invert", "--rest"]
+    r = run_py(*argv, cwd=str(tmp_path))
     exp, matched, starts = _want(FASTQ_BLANKS, "fastq", k, tabs, H=4, P=30)
     assert matched.any() and not matched.all()
     kept = filter_ref.select_bytes(FASTQ_BLANKS, starts, ~matched)
     assert open(proj + ".kept.fq", "rb").read() == kept and open(proj + ".rest.fq", "rb").read() == filter_ref.select_bytes(FASTQ_BLANKS, starts, matched)
     last = r.stdout.strip().split("\n")[-1]
     assert last == f"{int((~matched).sum())} of {matched.size} records kept, {len(kept):,d} of {len(FASTQ_BLANKS):,d} bytes, {proj}.kept.fq {proj}.rest.fq"
-    again = subprocess.run(argv, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert again.returncode == 1 and [ln for ln in again.stderr.split("\n") if ln.startswith("error: ") and "already exists" in ln]
-    bad = subprocess.run(argv[:4] + kins + ["--min-tables", "3"], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert bad.returncode == 1 and "min-tables" in bad.stderr
+    again = run_py(*argv, cwd=str(tmp_path), status=1)
+    assert [ln for ln in again.stderr.split("\n") if ln.startswith("error: ") and "already exists" in ln]
+    bad = run_py(*argv[:3], *kins, "--min-tables", "3", cwd=str(tmp_path), status=1)
+    assert "min-tables" in bad.stderr
 
 
 # ------------------------------------------------------------------ the product's size: reads at k = 15
@@ -219,12 +216,11 @@ def test_cli(gpu, tables, tmp_path):
 def tables15(gpu, tmp_path_factory):
     """([a.kin, b.kin], SparseTables) at k = 15: two 1 GiB tables of query_ref.counted_sources, written side by side."""
     from concurrent.futures import ThreadPoolExecutor
-    from test_host_layer import _write_index
     d = tmp_path_factory.mktemp("filter_tables15")
     sources, sparse = query_ref.counted_case(15)
     with ThreadPoolExecutor(2) as pool:
-        got = list(pool.map(lambda i: _write_index(d, f"t{i}.fa", sources[i], 15), range(2)))
-    return [h.index_file_root for h, _ in got], sparse[:2]
+        got = list(pool.map(lambda i: write_kin(d, f"t{i}.fa", sources[i], 15), range(2)))
+    return [w.path for w in got], sparse[:2]
 
 
 @pytest.mark.parametrize("form", ["plain", "gzip", "bgzf"])

@@ -9,23 +9,10 @@ import pytest
 import inputs
 import oracle
 import slice_ref
+from gpu_support import check_against_oracle
+from inputs import record_overflows, record_starts
 
 pytestmark = pytest.mark.gpu
-
-
-def _check_against_oracle(gpu, data, k):
-    got = gpu.count_fasta(data, k)
-    want = oracle.count_fasta(data, k)
-    assert got["num_kmers"] == want["num_kmers"]
-    assert got["total_bp"] == want["total_bp"]
-    assert len(got["records"]) == len(want["records"])
-    for f in ("name_off", "name_len", "seq_len", "n_valid_kmers"):
-        assert np.array_equal(got["records"][f], want["records"][f]), f
-    assert np.array_equal(got["table"], want["table"])
-    hist, vals = oracle.table_stats(want["table"])
-    assert np.array_equal(got["hist256"][1:], hist)
-    assert int(got["hist256"].sum()) == 4 ** k
-    return got
 
 
 def _expect_fields(got, data, case):
@@ -44,7 +31,7 @@ def _expect_fields(got, data, case):
 
 @pytest.mark.parametrize("k", [1, 3, 5, 7, 9, 11, 13])
 def test_edge_fasta_vs_oracle(gpu, k):
-    _check_against_oracle(gpu, inputs.edge_fasta(), k)
+    check_against_oracle(gpu, inputs.edge_fasta(), k)
 
 
 @pytest.mark.parametrize("name", ["G1_kat_k3", "G1_kat_k5", "G1_kat_k7", "G2_c1_k7", "G3_edge_k3", "G3_edge_k7",
@@ -261,7 +248,7 @@ def test_many_runs_of_invalid_characters_per_piece(gpu, k):
         width = (61, 7, 64, 0, 130)[i]
         body = seq.tobytes() if width == 0 else b"\n".join(seq[j: j + width].tobytes() for j in range(0, n, width))
         parts.append(b">r%d\n" % i + body + b"\n")
-    _check_against_oracle(gpu, np.frombuffer(b"".join(parts), dtype=np.uint8), k)
+    check_against_oracle(gpu, np.frombuffer(b"".join(parts), dtype=np.uint8), k)
 
 
 def test_control_bytes_inside_sequence_lines(gpu):
@@ -279,7 +266,7 @@ def test_control_bytes_inside_sequence_lines(gpu):
         lines.append(body[i:i + 61].tobytes())
     data = np.frombuffer(b"\n".join(lines), dtype=np.uint8)           # no trailing newline
     for k in (5, 9, 15):
-        _check_against_oracle(gpu, data, k)
+        check_against_oracle(gpu, data, k)
 
 
 def test_indexer_reuse_after_reset(gpu):
@@ -315,7 +302,7 @@ def test_random_structure_fuzz(gpu):
         w = rng.random(alphabet.size) ** 3
         data = alphabet[rng.choice(alphabet.size, size=n, p=w / w.sum())].tobytes()
         for k in (3, 9):
-            _check_against_oracle(gpu, data, k)
+            check_against_oracle(gpu, data, k)
 
 
 def test_read_set_headers_fuzz(gpu):
@@ -345,7 +332,7 @@ def test_read_set_headers_fuzz(gpu):
             parts.append(bytes(body) + ends[int(rng.integers(len(ends)))])
         data = b"".join(parts)
         for k in ((3, 15) if trial < 2 else (9,)):
-            _check_against_oracle(gpu, data, k)
+            check_against_oracle(gpu, data, k)
         if trial in (1, 2):
             # the same bytes through the streaming interface, cut at random places (inside header lines, between CR and
             # LF, one-byte feeds): the carried parser state meets header pieces at every offset
@@ -368,7 +355,7 @@ def test_unwrapped_long_lines_and_empty(gpu):
     rng = np.random.default_rng(3)
     seq = "".join("ACGT"[i] for i in rng.integers(0, 4, size=300_000))
     data = (">one_line_record\n" + seq + "\n>second\n" + seq[:100_000]).encode()      # 300 kbp on one line
-    _check_against_oracle(gpu, data, 11)
+    check_against_oracle(gpu, data, 11)
     for blob in (b"", b"\n\n", b">only_header", b"ACGTACGTACGT\n", b">x\n" + b"A" * 20):
         got = gpu.count_fasta(blob, 5)
         want = oracle.count_fasta(blob, 5)
@@ -421,7 +408,7 @@ def test_structure_across_chunk_boundaries(gpu):
     data = b"".join(parts)
     assert len(data) > 10 * 16384
     for k in (5, 15):
-        _check_against_oracle(gpu, data, k)
+        check_against_oracle(gpu, data, k)
     # the same bytes through the streaming interface with cuts on and around the seams
     want = oracle.count_fasta(data, 11)
     cuts = sorted(set([0, len(data)] + [c for b in (64, 16384, 40000, 65536) for c in (b - 1, b, b + 1, 3 * b, 3 * b + 1) if c < len(data)]))
@@ -453,7 +440,7 @@ def test_many_distinct_tandem_repeats(gpu):
     data = b"".join(parts)
     assert len(data) > 2_000_000
     for k in (9, 15):
-        _check_against_oracle(gpu, data, k)
+        check_against_oracle(gpu, data, k)
 
 
 @pytest.mark.parametrize("k,unit_len", [(13, 61), (15, 61), (15, 997), (17, 61)])
@@ -516,36 +503,6 @@ def test_byte_counters_wrap_and_are_recounted(gpu, k):
 # A feed is retried in place when its records do not fit the record array (the squeeze backs out, flags[0] = 2: grow it,
 # squeeze again) or when a sampled bucket room overflows (flags[0] = 1: lay out again with exact sizes, no new squeeze).
 # The tests below make both happen on neighbouring feeds and in one feed, and check every output against the oracle.
-RECS_INITIAL = 4096                                          # pk_indexer_create_slice: record slots of a fresh indexer
-
-
-def record_overflows(lengths, record_starts):
-    """Which of the feeds (byte lengths, in order; 0 = an empty feed, which never reaches the pipeline) bring more records
-    than the record array holds when they arrive -- the capacity rule of pk_indexer.hip (ensure_recs, run_feed: after every
-    feed room for as many records again as it brought, times two, + 1024).  `record_starts`: offset of every record's '>'."""
-    starts = np.sort(np.asarray(record_starts, dtype=np.int64))
-    cap, n, end, out = RECS_INITIAL, 0, 0, []
-
-    def grown(cap, need):
-        return cap if need <= cap else max(need, max(1024, 2 * cap))
-
-    for length in lengths:
-        if length == 0:
-            out.append(False)
-            continue
-        end += length
-        n_after = int(np.searchsorted(starts, end))
-        out.append(n_after > cap)
-        cap = grown(cap, n_after)
-        cap = grown(cap, n_after + 2 * (n_after - n) + 1024)
-        n = n_after
-    return out
-
-
-def _record_starts(records):
-    return records["name_off"].astype(np.int64) - 1
-
-
 _RETRY_BP = 20_000_220                                       # skewed text of 20.3 MB, a multiple of 16 bytes
 
 
@@ -603,7 +560,7 @@ def test_record_overflow_after_a_relayout_feed(gpu, k, n_slices):
         ix.feed(dense)
         want = _check_retried(ix, data, k, n_slices, slice_index)
     assert len(want["records"]) >= 100_000
-    assert record_overflows([len(skewed), len(dense)], _record_starts(want["records"])) == [False, True]
+    assert record_overflows([len(skewed), len(dense)], record_starts(want["records"])) == [False, True]
 
 
 def test_record_overflow_after_a_relayout_piece_of_one_host_feed(gpu, monkeypatch):
@@ -616,7 +573,7 @@ def test_record_overflow_after_a_relayout_piece_of_one_host_feed(gpu, monkeypatc
         t = ix.timings()
         assert t["feeds"] == 2 and t["relayouts"] >= 1
         want = _check_retried(ix, skewed + dense, k)
-    assert record_overflows([len(skewed), len(dense)], _record_starts(want["records"])) == [False, True]
+    assert record_overflows([len(skewed), len(dense)], record_starts(want["records"])) == [False, True]
 
 
 @functools.lru_cache(maxsize=None)
@@ -634,7 +591,7 @@ def test_both_retries_in_one_feed(gpu):
         assert ix.timings()["relayouts"] == 1, "the feed was meant to overflow the sampled layout"
         want = _check_retried(ix, data, k)
     assert len(want["records"]) >= 10_000
-    assert record_overflows([len(data)], _record_starts(want["records"])) == [True]
+    assert record_overflows([len(data)], record_starts(want["records"])) == [True]
 
 
 def test_retry_schedule_on_one_indexer(gpu):
@@ -662,7 +619,7 @@ def test_retry_schedule_on_one_indexer(gpu):
             relayouts.append(ix.timings()["relayouts"])
         assert relayouts[0] >= 1 and relayouts[-1] > relayouts[-2], relayouts
         want = _check_retried(ix, data, k)
-        assert record_overflows([len(f) for f in feeds], _record_starts(want["records"])) == \
+        assert record_overflows([len(f) for f in feeds], record_starts(want["records"])) == \
             [False, True, False, False, True, False, True]
         ix.reset()
         plain, _ = synth.c2(3_000_000, seed=71)

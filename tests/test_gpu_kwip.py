@@ -1,18 +1,15 @@
 """GPU: k_occgram (pk_occgram_device_accumulate) against numpy on mixed and adversarial tables, its accumulation over
 sub-slices, the no-wrap case, the full-size N = 13 pass against float64 matmuls and a k_spectrum pass, and the
 `merger.py --kwip` command line."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from pykmer_amd import kwip, merger, spectrum
-from test_kwip_host import direct_kernel, numpy_occgram
+from gpu_support import env_without_ranks, family_kins, run_py
+from merge_ref import direct_kernel, numpy_occgram
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _device_occgram(gpu, tabs, cuts=None):
@@ -185,23 +182,14 @@ def test_occgram_full_size_n13(gpu):
     print(f"occgram N=13 k=15 kernel {secs * 1e3:.3f} ms")
 
 
-def _run(*argv, cwd, env=None):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_kwip_command_lines(gpu, tmp_path, manifest, monkeypatch):
     """indexer.py -> merger.py --kwip on the G7 FASTA inputs: the .kmo equals numpy over the tables, the .kern the direct
     restatement; the same files from .kin.bgz inputs in forced sub-slices and from two ranks (gloo on the one GPU)."""
     import gzip
-    from test_gpu_cli import _family_kins
-    kins = _family_kins(tmp_path, manifest)
-    env = dict(os.environ)
-    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(v, None)
+    kins = family_kins(tmp_path, manifest)
+    env = env_without_ranks()
     proj = str(tmp_path / "kw")
-    r = _run(os.path.join(ROOT, "merger.py"), proj, *kins, "--kwip", cwd=str(tmp_path), env=env)
+    r = run_py("merger.py", proj, *kins, "--kwip", cwd=str(tmp_path), env=env)
     assert r.stdout.count("saving") == 4 and not list(tmp_path.glob("kw*.kma"))
     tabs = [merger.Header(k, index_file=k).read_table_slice(0, 4 ** 7) for k in sorted(kins)]
     occ = kwip.load(proj + ".kmo")
@@ -220,7 +208,7 @@ def test_kwip_command_lines(gpu, tmp_path, manifest, monkeypatch):
     monkeypatch.delenv("PK_MERGE_HBM_BUDGET")
     assert (tmp_path / "sub.kern").read_bytes() == (tmp_path / "kw.kern").read_bytes()
 
-    _run(os.path.join(ROOT, "merger.py"), str(tmp_path / "two"), *kins, "--kwip", "--gpus", "2", cwd=str(tmp_path),
+    run_py("merger.py", str(tmp_path / "two"), *kins, "--kwip", "--gpus", "2", cwd=str(tmp_path),
          env=dict(env, PK_DIST_BACKEND="gloo"))
     for ext in ("kern", "dist"):
         assert (tmp_path / f"two.{ext}").read_bytes() == (tmp_path / f"kw.{ext}").read_bytes()

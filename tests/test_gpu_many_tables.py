@@ -7,20 +7,17 @@ products on the device."""
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 from pykmer_amd import merger, spectrum
-from test_gpu_merger import SWEEP9, _accumulate_windows, _random_tables, _torch_tables
-from test_gpu_spectrum import _device_bincount
-from test_host_layer import _write_index
+from gpu_support import accumulate_windows, env_without_ranks, run_py
+from host_support import write_kin
+from merge_ref import SWEEP9, device_bincount, mixed_tables, torch_tables
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THREADS = max(1, min(16, len(os.sched_getaffinity(0))))
 
 # launch_gram (gram_scan.hip): tables per block, pair blocks per launch, workgroup cap, tiles per workgroup of packed tallies
@@ -72,9 +69,9 @@ def test_gram_many_tables_vs_oracle(gpu, N):
     assert (N, NB, len(launches)) == (1, 1, 1) or (9 <= NB <= 16 and len(launches) >= 2)
     rng = np.random.default_rng(500 + N)
     for n, windows in ((4 ** 7, SWEEP9), (300_001, [(1, 255), (129, 254)])):
-        tables = _random_tables(rng, N, n)
+        tables = mixed_tables(rng, N, n)
         assert _distinct(tables)
-        acc = _accumulate_windows(gpu, tables, windows)
+        acc = accumulate_windows(gpu, tables, windows)
         for w, (mn, mx) in enumerate(windows):
             want = oracle.gram_mt(tables, mn, mx, threads=THREADS)
             assert np.array_equal(gpu.gram(tables, mn, mx), want), (N, n, mn, mx)
@@ -84,7 +81,7 @@ def test_gram_many_tables_vs_oracle(gpu, N):
             totals = [int(((t >= mn) & (t <= mx)).sum()) for t in tables]
             assert np.diagonal(acc[w]).tolist() == totals, (N, n, mn, mx)
             if N == 1:                                               # one window per call: k_gram_blk, not the multi-window pass
-                assert _accumulate_windows(gpu, tables, [(mn, mx)])[0].tolist() == [totals], (n, mn, mx)
+                assert accumulate_windows(gpu, tables, [(mn, mx)])[0].tolist() == [totals], (n, mn, mx)
 
 
 def test_gram_100_tables_several_tiles_per_workgroup(gpu):
@@ -97,7 +94,7 @@ def test_gram_100_tables_several_tiles_per_workgroup(gpu):
     NB, launches = _gram_launches(N)
     tiles, grid, per_wg = _gram_grid(n)
     assert NB == 13 and len(launches) == 4 and tiles > GRID_CAP and grid == GRID_CAP and per_wg > 1
-    tabs = _torch_tables(n, N, seed=900)
+    tabs = torch_tables(n, N, seed=900)
     ptrs = [t.data_ptr() for t in tabs]
     windows = [(1, 255), (130, 250)]
     acc = torch.zeros((len(windows), N, N), dtype=torch.int64, device="cuda")
@@ -241,21 +238,13 @@ def test_spectrum_47_tables_several_chunks_per_lane(gpu):
         assert np.array_equal(got, want[w]), wins[w]
     for i, j in ((0, 1), (0, 46), (7, 8), (15, 40), (39, 40), (40, 46), (45, 46)):
         p = i * N - i * (i + 1) // 2 + (j - i - 1)
-        b = _device_bincount(tabs[i].to(torch.int32) * 256 + tabs[j].to(torch.int32), 65536)
+        b = device_bincount(tabs[i].to(torch.int32) * 256 + tabs[j].to(torch.int32), 65536)
         assert np.array_equal(joint[p], b.reshape(256, 256)), (i, j)
     del tabs, dev
     torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------ merger.py on 100 tables, and 129 refused --------------
-def _cli(*argv, cwd):
-    env = dict(os.environ)
-    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(v, None)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "merger.py")] + list(argv), cwd=cwd, capture_output=True,
-                          text=True, timeout=600, env=env)
-
-
 def test_merger_cli_100_tables_and_refuses_129(gpu, tmp_path):
     """100 distinct .kin files at k = 7 (the oracle stands in for the indexer): a four-window sweep writes four .kma, each
     equal to the oracle's pair loop, and .kma.json lists the 100 inputs in order.  129 files: the pair path and --spectrum
@@ -265,13 +254,12 @@ def test_merger_cli_100_tables_and_refuses_129(gpu, tmp_path):
     kins, tables = [], []
     for i in range(129):
         fa, _ = synth.family(i, 20_000)
-        h, got = _write_index(tmp_path, f"m{i:03d}.fa", fa.tobytes(), k)
-        kins.append(h.index_file_root)
-        tables.append(got["table"])
+        w = write_kin(tmp_path, f"m{i:03d}.fa", fa.tobytes(), k)
+        kins.append(w.path)
+        tables.append(w.table)
     assert _distinct(tables)
     proj = str(tmp_path / "p100")
-    r = _cli(proj, *kins[:100], "--sweep", "1-255,2-255,1-3,2-5", cwd=str(tmp_path))
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    run_py("merger.py", proj, *kins[:100], "--sweep", "1-255,2-255,1-3,2-5", cwd=str(tmp_path), env=env_without_ranks())
     for mn, mx in ((1, 255), (2, 255), (1, 3), (2, 5)):
         name = f"{proj}.{mn:03d}-{mx:03d}.kma"
         assert np.array_equal(np.load(name)["matrix"], oracle.gram_mt(tables[:100], mn, mx, threads=THREADS)), (mn, mx)
@@ -281,8 +269,8 @@ def test_merger_cli_100_tables_and_refuses_129(gpu, tmp_path):
 
     for extra, msg in (((), "a pair tally takes 1 to 128 tables"), (("--spectrum",), "a spectrum takes 2 to 128 tables")):
         proj = str(tmp_path / ("p129" + "".join(extra).replace("-", "_")))
-        r = _cli(proj, *kins, *extra, cwd=str(tmp_path))
-        assert r.returncode != 0 and msg in r.stderr, (extra, r.stdout[-1000:], r.stderr[-2000:])
+        r = run_py("merger.py", proj, *kins, *extra, cwd=str(tmp_path), status=1, env=env_without_ranks())
+        assert msg in r.stderr, (extra, r.stdout[-1000:], r.stderr[-2000:])
         assert "verifying" in r.stdout and "saving" not in r.stdout
         assert not [f for f in os.listdir(tmp_path) if f.startswith(os.path.basename(proj))], extra
 

@@ -4,32 +4,26 @@ exactly."""
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import byte_inputs
 import mask_inputs as mi
 import mask_ref
 import query_coords_inputs as qci
 import query_ref
+from gpu_support import lib, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = mi.CHUNK
 MODES = ((False, False), (True, False), (False, True), (True, True))          # (hard, invert)
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
 def _apply(text: bytes, bits, n_bases: int, hard=False, invert=False, cuts=None, q=None):
     """The text through one applying indexer, fed in the pieces `cuts` make: (masked text, masked (R,), bases seen)."""
-    lib = _lib()
+    lib = gs.lib()
     own = q is None
     q = lib.QueryIndexer(1, device=0) if own else q
     try:
@@ -105,7 +99,7 @@ def test_feeds_cut_anywhere(gpu):
     k = mi.SEAM_K
     text = mi.seam_text()
     want = mask_ref.expected(text, k, [mi.seam_tables()[0]], 1, 255)
-    with _lib().QueryIndexer(1, device=0) as q:
+    with lib().QueryIndexer(1, device=0) as q:
         for cut in list(range(CHUNK - 11, CHUNK + 12)) + [1, 3, text.index(b"\n"), text.index(b"\n") + 1]:
             _check(text, want, _apply(text, want["bits"], want["n_bases"], True, False, [cut], q=q), True, False)
             q.reset()
@@ -121,7 +115,7 @@ def test_feeds_cut_anywhere(gpu):
 
 
 def test_bits_of_the_wrong_length_and_all_ones(gpu):
-    lib = _lib()
+    lib = gs.lib()
     text = qci.blanks()
     want = mask_ref.expected(text, 5, mi.band_tables(5), 1, 255)
     n = want["n_bases"]
@@ -153,8 +147,7 @@ def kins(gpu, tmp_path_factory):
     for name, seq in (("donor", mi.DONOR), ("host", mi.HOST)):
         fa, data = d / f"{name}.fa", b">" + name.encode() + b"\n" + seq + b"\n"
         fa.write_bytes(data)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "indexer.py"), str(fa), name, "5"], cwd=str(d), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        run_py("indexer.py", str(fa), name, "5", cwd=str(d))
         paths.append(f"{fa}.05.kin")
         tabs.append(oracle.count_fasta(data, 5)["table"])
     return paths, tabs
@@ -199,9 +192,8 @@ def test_cli(gpu, kins, tmp_path, form):
         with gzip.open(src, "wb") as fh:
             fh.write(text)
     proj = str(tmp_path / "cli")
-    argv = [sys.executable, os.path.join(ROOT, "mask.py"), proj, str(src)] + paths + ["--min-count", "1", "--max-count", "254", "--hard"]
-    r = subprocess.run(argv, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    argv = ["mask.py", proj, str(src)] + paths + ["--min-count", "1", "--max-count", "254", "--hard"]
+    r = run_py(*argv, cwd=str(tmp_path))
     want = mask_ref.expected(text, 5, tabs, 1, 254)
     assert 0 < want["cover"].sum() < want["n_bases"]
     assert open(proj + ".masked.fa", "rb").read() == mask_ref.masked_text(text, want, True, False)
@@ -218,5 +210,5 @@ def test_cli(gpu, kins, tmp_path, form):
     last = r.stdout.strip().split("\n")[-1]
     assert last == f"{int(want['cover'].sum())} of {want['n_bases']} valid bases masked in {want['n_records']} records, {proj}.masked.fa"
     assert not [f for f in os.listdir(tmp_path) if f.endswith(".tmp")]
-    again = subprocess.run(argv, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
-    assert again.returncode == 1 and [ln for ln in again.stderr.split("\n") if ln.startswith("error: ") and "already exists" in ln]
+    again = run_py(*argv, cwd=str(tmp_path), status=1)
+    assert [ln for ln in again.stderr.split("\n") if ln.startswith("error: ") and "already exists" in ln]

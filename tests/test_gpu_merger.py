@@ -5,26 +5,19 @@ import pytest
 
 import inputs
 import oracle
+from gpu_support import accumulate_windows
+from host_support import family_indexes, write_kin
+from merge_ref import SWEEP9, mixed_tables, torch_tables
 from oracle import pyoracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _random_tables(rng, N, n, density=0.4):
-    out = []
-    for _ in range(N):
-        t = rng.integers(1, 256, size=n, dtype=np.uint8)
-        t[rng.random(n) > density] = 0
-        t[rng.random(n) < 0.05] = rng.integers(1, 6)          # plenty of small counts for min/max windows
-        out.append(t)
-    return out
 
 
 @pytest.mark.parametrize("N", [2, 3, 5, 8, 9, 13, 16, 17, 24, 25, 32, 33, 40, 41, 48, 49, 64])
 def test_gram_vs_oracle(gpu, N):
     rng = np.random.default_rng(100 + N)
     n = 4 ** 7
-    tables = _random_tables(rng, N, n)
+    tables = mixed_tables(rng, N, n)
     for mn, mx in ((1, 255), (2, 255), (1, 3), (2, 5), (128, 255), (100, 200), (1, 127), (129, 254), (255, 255)):
         got = gpu.gram(tables, mn, mx)
         want = oracle.gram(tables, mn, mx)
@@ -34,7 +27,7 @@ def test_gram_vs_oracle(gpu, N):
 
 def test_gram_matches_numpy_restatement(gpu):
     rng = np.random.default_rng(7)
-    tables = _random_tables(rng, 6, 4 ** 5)
+    tables = mixed_tables(rng, 6, 4 ** 5)
     assert np.array_equal(gpu.gram(tables, 2, 9), pyoracle.gram(tables, 2, 9))
 
 
@@ -43,7 +36,7 @@ def test_gram_ragged_sizes(gpu, n):
     """Table sizes that are not multiples of the 32-address word / 256-word tile."""
     rng = np.random.default_rng(n)
     for N in (3, 20):
-        tables = _random_tables(rng, N, n, density=0.7)
+        tables = mixed_tables(rng, N, n, density=0.7)
         assert np.array_equal(gpu.gram(tables), oracle.gram(tables))
 
 
@@ -107,18 +100,6 @@ def test_gram_full_size_properties(gpu):
     print(f"gram N=13 k=15 kernel {secs * 1e3:.3f} ms -> {N * n / secs / 1e12:.2f} TB/s")
 
 
-def _torch_tables(n, N, seed):
-    import torch
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    tabs = []
-    for i in range(N):
-        t = torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda", generator=g)
-        keep = torch.rand(n, device="cuda", generator=g) < (0.1 + 0.8 * ((i * 7) % N) / N)
-        tabs.append(t * keep)
-    torch.cuda.synchronize()
-    return tabs
-
-
 @pytest.mark.parametrize("N", [13, 32])
 def test_gram_full_size_every_pair(gpu, N):
     """configs 3 and 5 at full size (4^15-byte tables resident in HBM): EVERY total and EVERY shared tally
@@ -126,7 +107,7 @@ def test_gram_full_size_every_pair(gpu, N):
     import torch
     torch.cuda.empty_cache()
     n = 4 ** 15
-    tabs = _torch_tables(n, N, seed=40 + N)
+    tabs = torch_tables(n, N, seed=40 + N)
     ptrs = [t.data_ptr() for t in tabs]
     for mn, mx in ((1, 255), (3, 200)):
         pair, secs = gpu.gram_device_partial(ptrs, n, mn, mx)
@@ -175,15 +156,14 @@ def test_merge_host_path_sub_slices_and_threads(gpu, tmp_path, monkeypatch):
     table arrives as BGZF with a .gzi -- and only the bytes of each slice are read."""
     from pykmer_amd import bgzf, merger
     from pykmer_amd.header import Header
-    from test_host_layer import _write_index
     import synth
     k, N = 9, 5
     paths, tables = [], []
     for i in range(N):
         fa, _ = synth.family(i, 60_000)
-        h, got = _write_index(tmp_path, f"m{i}.fa", fa.tobytes(), k)
-        paths.append(h.index_file_root)
-        tables.append(got["table"])
+        w = write_kin(tmp_path, f"m{i}.fa", fa.tobytes(), k)
+        paths.append(w.path)
+        tables.append(w.table)
     bgzf.compress_file(paths[2], level=1)
     headers = [Header(p, index_file=p) for p in paths]
     assert headers[2].index_file.endswith(".bgz")
@@ -199,34 +179,15 @@ def test_merge_host_path_sub_slices_and_threads(gpu, tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------ several windows in one pass ------------
-SWEEP9 = [(1, 255), (2, 255), (1, 3), (2, 5), (128, 255), (100, 200), (1, 127), (129, 254), (255, 255)]
-
-
-def _accumulate_windows(gpu, tables, windows):
-    """Host tables -> device buffers -> ONE pk_gram_device_accumulate_windows call -> W x N x N."""
-    N, n = len(tables), tables[0].size
-    bufs = [gpu.DeviceBuffer(n, 0) for _ in range(N)]
-    acc = gpu.DeviceBuffer(len(windows) * N * N * 8, 0)
-    try:
-        for b, t in zip(bufs, tables):
-            b.upload(t)
-        acc.zero()
-        gpu.gram_device_accumulate_windows([b.ptr for b in bufs], n, acc.ptr, windows)
-        return acc.download().view(np.uint64).reshape(len(windows), N, N)
-    finally:
-        for b in bufs + [acc]:
-            b.free()
-
-
 @pytest.mark.parametrize("N", [2, 5, 8, 9, 13, 16, 17, 24, 25, 32, 33, 49])
 def test_window_sweep_in_one_pass_vs_oracle(gpu, N):
     """Every window of a sweep from one call (k_gram_mw: bit planes + ripple comparators; N > 32: one scan per window)
     against the oracle's pair loop (tools.py:473-482), for window lists that do and do not fill a pass, sorted and not."""
     rng = np.random.default_rng(300 + N)
     for n in (4 ** 7, 300_001):
-        tables = _random_tables(rng, N, n)
+        tables = mixed_tables(rng, N, n)
         for windows in (SWEEP9, SWEEP9[:2], [(5, 9)], [(7, 255), (1, 255), (3, 255), (3, 20), (2, 255), (1, 1)]):
-            got = _accumulate_windows(gpu, tables, windows)
+            got = accumulate_windows(gpu, tables, windows)
             for w, (mn, mx) in enumerate(windows):
                 assert np.array_equal(gpu.gram_expand(got[w]), oracle.gram(tables, mn, mx)), (N, n, mn, mx)
         if N > 9:
@@ -235,7 +196,7 @@ def test_window_sweep_in_one_pass_vs_oracle(gpu, N):
 
 def test_window_sweep_accumulates_and_rejects(gpu):
     rng = np.random.default_rng(5)
-    tables = _random_tables(rng, 4, 4 ** 6)
+    tables = mixed_tables(rng, 4, 4 ** 6)
     N, n = 4, tables[0].size
     bufs = [gpu.DeviceBuffer(n, 0) for _ in range(N)]
     acc = gpu.DeviceBuffer(2 * N * N * 8, 0)
@@ -261,7 +222,7 @@ def test_window_sweep_full_size(gpu, N):
     import torch
     torch.cuda.empty_cache()
     n = 4 ** 15
-    tabs = _torch_tables(n, N, seed=70 + N)
+    tabs = torch_tables(n, N, seed=70 + N)
     ptrs = [t.data_ptr() for t in tabs]
     windows = [(1, 255), (2, 255), (3, 255), (4, 255), (5, 200), (8, 255), (1, 50), (2, 20)]
     acc = torch.zeros((len(windows), N, N), dtype=torch.int64, device="cuda")
@@ -293,8 +254,7 @@ def test_merge_through_rccl_group_of_one(gpu, tmp_path, manifest):
     import torch
     import torch.distributed as dist
     from pykmer_amd import merger
-    from test_host_layer import _family_indexes
-    paths = sorted(_family_indexes(tmp_path, manifest))
+    paths = sorted(family_indexes(tmp_path, manifest))
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]

@@ -2,77 +2,21 @@
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import inputs
 import oracle
 import query_ref
 import synth
+from gpu_support import Device, index_cli, lib, query, run_py, same, stream
+from host_support import write_kin
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 16384
 WINDOWS = ((1, 255), (2, 254), (255, 255), (1, 1))
-
-
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-def _collect(q):
-    fin = q.finish()
-    recs = q.records(fin["n_records"])
-    hits, depth = q.results(fin["n_records"])
-    assert np.array_equal(fin["hist256"], np.zeros(256, dtype=np.uint64))
-    return {"fin": fin, "records": recs, "hits": hits.copy(), "depth": depth.copy()}
-
-
-def _feed(q, text: bytes, cuts=None):
-    buf = np.frombuffer(text, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(text)]:
-        if c > pos:
-            q.feed(buf[pos:c])
-            pos = c
-
-
-def _query(text: bytes, k: int, ptrs, mn=1, mx=255, fmt="fasta", cuts=None):
-    with _lib().QueryIndexer(k, device=0, fmt=fmt) as q:
-        q.set_tables(ptrs, mn, mx)
-        _feed(q, text, cuts)
-        return _collect(q)
-
-
-def _same(got, want):
-    assert got["fin"]["n_records"] == len(want["records"])
-    assert got["fin"]["num_kmers"] == int(want["n_valid"].sum())
-    assert np.array_equal(got["records"]["n_valid_kmers"], want["n_valid"]) and np.array_equal(got["records"]["seq_len"], want["seq_len"])
-    assert got["hits"].dtype == np.uint64 and got["hits"].shape == want["hits"].shape
-    assert np.array_equal(got["hits"], want["hits"]), np.argwhere(got["hits"] != want["hits"])[:5]
-    assert np.array_equal(got["depth"], want["depth"]), np.argwhere(got["depth"] != want["depth"])[:5]
-    assert (got["hits"] <= want["n_valid"][:, None]).all()
 
 
 # ------------------------------------------------------------------ 1. edge grammar ----------------
@@ -80,36 +24,21 @@ def _same(got, want):
 def test_edge_grammar(gpu, k):
     tables = query_ref.random_tables(k, 3, seed=k)
     texts = [inputs.edge_fasta(), inputs.byte_soup(40_000, 11), inputs.byte_soup(40_000, 12)]
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for text in texts:
             for mn, mx in WINDOWS:
                 want = query_ref.expected(text, k, tables, mn, mx)
-                _same(_query(text, k, dev.ptrs, mn, mx), want)
+                same(query(text, k, dev.ptrs, mn, mx), want)
     want = query_ref.expected(texts[0], k, tables, 1, 255)
     assert (want["n_valid"] == 0).any() and want["hits"].any()           # records with no window are listed, others hit
 
 
 # ------------------------------------------------------------------ 2. slot seams ------------------
-def _seam_text(k: int) -> bytes:
-    """One record of 100 000 bases, line width 60 (seven 16 KiB chunks), an N within k-1 bases on either side of two chunk
-    boundaries."""
-    rng = np.random.default_rng(200 + k)
-    seq = bytearray(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 100_000)].tobytes())
-    head = b">seams one record\n"
-    def base_at(byte):                                       # index of the base at (or just before) a byte offset of the text
-        body = byte - len(head)
-        return body - body // 61                             # 60 bases + '\n' per line
-    for boundary, delta in ((2 * CHUNK, -(k - 2)), (2 * CHUNK, 1), (5 * CHUNK, -1), (5 * CHUNK, k - 2)):
-        seq[base_at(boundary) + delta] = ord("N")
-    body = b"".join(bytes(seq[i:i + 60]) + b"\n" for i in range(0, len(seq), 60))
-    return head + body
-
-
 @pytest.mark.parametrize("k", [1, 9, 13, 15, 17])
 def test_slot_seams(gpu, k):
     if k == 17:
         return _slot_seams_k17()
-    text = _seam_text(k)
+    text = query_ref.seam_text(k)
     assert len(text) > 6 * CHUNK
     if k <= 9:
         tables = query_ref.random_tables(k, 2, seed=21)
@@ -117,9 +46,9 @@ def test_slot_seams(gpu, k):
         pool = np.array([0, 1, 254, 255, 7, 0, 1, 255], dtype=np.uint8)
         tables = [np.tile(np.roll(pool, i), 4 ** k // 8) for i in range(2)]
         tables[1] = np.roll(tables[1], 3)
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for mn, mx in ((1, 255), (2, 254)):
-            _same(_query(text, k, dev.ptrs, mn, mx), query_ref.expected(text, k, tables, mn, mx))
+            same(query(text, k, dev.ptrs, mn, mx), query_ref.expected(text, k, tables, mn, mx))
 
 
 def _slot_seams_k17():
@@ -127,9 +56,9 @@ def _slot_seams_k17():
     windows of every slot.  The table is counted on the GPU from stretches of the seam text around every chunk boundary:
     windows across the boundaries without an N hit, and so do the windows next to the two seams.  Feeds cut 3 bytes before
     and behind the seams' chunk boundaries give the same result."""
-    lib = _lib()
+    lib = gs.lib()
     k = 17
-    text = _seam_text(k)
+    text = query_ref.seam_text(k)
     counted = query_ref.counted_text_for(text, k, seed=1700)
     sparse = [query_ref.SparseTable(oracle.kmer_list(counted, k))]
     kmers = oracle.kmer_list(text, k)
@@ -151,10 +80,10 @@ def _slot_seams_k17():
         for mn, mx in ((1, 255), (2, 254)):
             want = query_ref.expected(text, k, sparse, mn, mx)
             assert want["hits"][0, 0] > 0
-            whole = _query(text, k, ptrs, mn, mx)
-            _same(whole, want)
+            whole = query(text, k, ptrs, mn, mx)
+            same(whole, want)
             for sign in (-3, 3):
-                cut = _query(text, k, ptrs, mn, mx, cuts=[2 * CHUNK + sign, 5 * CHUNK + sign])
+                cut = query(text, k, ptrs, mn, mx, cuts=[2 * CHUNK + sign, 5 * CHUNK + sign])
                 assert np.array_equal(cut["hits"], whole["hits"]) and np.array_equal(cut["depth"], whole["depth"]), sign
                 assert np.array_equal(cut["records"], whole["records"])
 
@@ -168,35 +97,23 @@ def test_long_record_behind_short_ones(gpu, s, ragged):
     k = 9
     text, index = query_ref.long_after_short(s, seed=300 + s, ragged=ragged)
     tables = query_ref.random_tables(k, 2, seed=22)
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for mn, mx in ((1, 255), (2, 254)):
             want = query_ref.expected(text, k, tables, mn, mx)
             assert want["n_valid"][index] == 12_000 - k + 1 and want["hits"][index].all()
-            _same(_query(text, k, dev.ptrs, mn, mx), want)
+            same(query(text, k, dev.ptrs, mn, mx), want)
 
 
 # ------------------------------------------------------------------ 3. many records ----------------
-def _reads_text(k: int, n_reads: int = 6000, seed: int = 31) -> bytes:
-    """`>rN\\n<bases>\\n` per read, lengths 0, 1, k-1, k, k+1, 40 ... mixed: many records per 64-byte piece and per chunk."""
-    rng = np.random.default_rng(seed)
-    lens = np.array([0, 1, k - 1, k, k + 1, 40, 2, 13, 64, 150])[rng.integers(0, 10, n_reads)]
-    lens[:12] = [0, 0, 1, k - 1, k, k + 1, 40, 0, k, 0, 0, 1]
-    alphabet = np.frombuffer(b"ACGTACGTACGTACGTN", dtype=np.uint8)
-    out = []
-    for i, n in enumerate(lens):
-        out.append(b">r%d\n" % i + alphabet[rng.integers(0, alphabet.size, int(n))].tobytes() + b"\n")
-    return b"".join(out)
-
-
 def test_many_records_per_piece_and_chunk(gpu):
     k = 9
-    text = _reads_text(k)
+    text = query_ref.reads_text(k)
     tables = query_ref.random_tables(k, 2, seed=32)
     want = query_ref.expected(text, k, tables, 1, 254)
     assert len(want["records"]) == 6000 > 4096               # beyond the record array's first capacity: the squeeze backs out once
-    with _Device(tables) as dev:
-        got = _query(text, k, dev.ptrs, 1, 254)
-    _same(got, want)
+    with Device(tables) as dev:
+        got = query(text, k, dev.ptrs, 1, 254)
+    same(got, want)
     empty = want["n_valid"] == 0
     assert empty.sum() > 1000 and got["hits"].shape[0] == 6000 and not got["hits"][empty].any() and not got["depth"][empty].any()
 
@@ -204,36 +121,32 @@ def test_many_records_per_piece_and_chunk(gpu):
 # ------------------------------------------------------------------ 4. feeds -----------------------
 def test_feeds_cut_anywhere_and_reset(gpu):
     k = 9
-    reads, seams = _reads_text(k), _seam_text(k)
+    reads, seams = query_ref.reads_text(k), query_ref.seam_text(k)
     tables = query_ref.random_tables(k, 2, seed=41)
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for text in (reads, seams):
-            whole = _query(text, k, dev.ptrs, 2, 255)
-            _same(whole, query_ref.expected(text, k, tables, 2, 255))
+            whole = query(text, k, dev.ptrs, 2, 255)
+            same(whole, query_ref.expected(text, k, tables, 2, 255))
             at = text.find(b">", 3 * CHUNK + 100)
             hdr = at + 2 if at >= 0 else 3 * CHUNK + 100     # inside a header (reads); the one-record text has none there
             cuts = sorted({7, 8, CHUNK, CHUNK + 5, 2 * CHUNK - 3, 3 * CHUNK, hdr, 4 * CHUNK + 61 * 3 + 4, len(text) - 1})
-            cut = _query(text, k, dev.ptrs, 2, 255, cuts=cuts)   # 7..8: one byte; CHUNK, 3 * CHUNK: ends at a chunk multiple; the rest inside k-mers
+            cut = query(text, k, dev.ptrs, 2, 255, cuts=cuts)   # 7..8: one byte; CHUNK, 3 * CHUNK: ends at a chunk multiple; the rest inside k-mers
             for key in ("hits", "depth"):
                 assert np.array_equal(cut[key], whole[key]), key
             assert np.array_equal(cut["records"], whole["records"])
         # a second stream after reset: its own results, nothing carried over
-        with _lib().QueryIndexer(k, device=0) as q:
+        with lib().QueryIndexer(k, device=0) as q:
             q.set_tables(dev.ptrs, 2, 255)
             r = reads[:5000].count(b">")
             assert 3 * r + 1024 <= 4096 < reads.count(b">")                # the record array grows in the second feed, over the first feed's rows
-            _feed(q, reads, [5000])
-            first = _collect(q)
-            q.reset()
-            _feed(q, seams, [CHUNK + 1])
-            second = _collect(q)
-            q.reset()
+            first = stream(q, reads, cuts=[5000])
+            second = stream(q, seams, cuts=[CHUNK + 1])
             q.set_tables(dev.ptrs[:1], 1, 1)                  # and other tables / another window after a reset
-            _feed(q, reads)
-            third = _collect(q)
-        _same(first, query_ref.expected(reads, k, tables, 2, 255))
-        _same(second, query_ref.expected(seams, k, tables, 2, 255))
-        _same(third, query_ref.expected(reads, k, tables[:1], 1, 1))
+            third = stream(q, reads)
+        assert not any(got["fin"]["hist256"].any() for got in (first, second, third))
+        same(first, query_ref.expected(reads, k, tables, 2, 255))
+        same(second, query_ref.expected(seams, k, tables, 2, 255))
+        same(third, query_ref.expected(reads, k, tables[:1], 1, 1))
 
 
 # ------------------------------------------------------------------ 5. FASTQ -----------------------
@@ -249,16 +162,16 @@ def test_fastq_reads(gpu):
     tables = query_ref.random_tables(k, 2, seed=52)
     want = query_ref.expected(fq, k, tables, 1, 255, fmt="fastq")
     assert len(want["records"]) == 3000
-    with _Device(tables) as dev:
-        _same(_query(fq, k, dev.ptrs, fmt="fastq"), want)
-        _same(_query(fq, k, dev.ptrs, fmt="fastq", cuts=[1, 100_003, 2 * CHUNK]), want)
+    with Device(tables) as dev:
+        same(query(fq, k, dev.ptrs, fmt="fastq"), want)
+        same(query(fq, k, dev.ptrs, fmt="fastq", cuts=[1, 100_003, 2 * CHUNK]), want)
 
 
 # ------------------------------------------------------------------ 6. full-size tables ------------
 @pytest.mark.parametrize("k,n_tables", [(15, 2), (17, 1)])
 def test_full_size_tables_counted_on_the_gpu(gpu, k, n_tables):
     """32-bit (k = 15) and 64-bit (k = 17) k-mers against tables that were counted on the GPU and never left HBM."""
-    lib = _lib()
+    lib = gs.lib()
     genomes = [synth.family(i, 200_000)[0] for i in range(n_tables + 1)]
     text = bytes(genomes[n_tables]) + bytes(genomes[0])      # another family member, then one of the indexed genomes itself
     sparse = [query_ref.SparseTable(oracle.kmer_list(g, k)) for g in genomes[:n_tables]]
@@ -272,8 +185,8 @@ def test_full_size_tables_counted_on_the_gpu(gpu, k, n_tables):
         ptrs = [ix.table_device_ptr() for ix in indexers]
         for mn, mx in ((1, 255), (2, 255)):
             want = query_ref.expected(text, k, sparse, mn, mx)
-            got = _query(text, k, ptrs, mn, mx)
-            _same(got, want)
+            got = query(text, k, ptrs, mn, mx)
+            same(got, want)
             if (mn, mx) == (1, 255):
                 n_self = len(oracle.kmer_list(genomes[0], k, records=True)[1]["records"])
                 assert n_self >= 1 and np.array_equal(got["hits"][-n_self:, 0], want["n_valid"][-n_self:])
@@ -287,18 +200,18 @@ def test_full_size_tables_counted_on_the_gpu(gpu, k, n_tables):
 def test_table_counts_and_the_group_loop(gpu):
     """N = 1, 13 and 17 (one launch takes 16 tables, so 17 runs the group loop): column t equals the 1-table run on table t."""
     k = 9
-    text = _reads_text(k, n_reads=1500, seed=71) + inputs.byte_soup(30_000, 72)
+    text = query_ref.reads_text(k, n_reads=1500, seed=71) + inputs.byte_soup(30_000, 72)
     tables = query_ref.random_tables(k, 17, seed=73)
-    with _Device(tables) as dev:
-        single = [_query(text, k, dev.ptrs[t:t + 1], 1, 254) for t in range(17)]
-        _same(single[0], query_ref.expected(text, k, tables[:1], 1, 254))
+    with Device(tables) as dev:
+        single = [query(text, k, dev.ptrs[t:t + 1], 1, 254) for t in range(17)]
+        same(single[0], query_ref.expected(text, k, tables[:1], 1, 254))
         for n in (13, 17):
-            got = _query(text, k, dev.ptrs[:n], 1, 254)
+            got = query(text, k, dev.ptrs[:n], 1, 254)
             assert got["hits"].shape[1] == n
             for t in range(n):
                 assert np.array_equal(got["hits"][:, t], single[t]["hits"][:, 0]), (n, t)
                 assert np.array_equal(got["depth"][:, t], single[t]["depth"][:, 0]), (n, t)
-        _same(got, query_ref.expected(text, k, tables, 1, 254))
+        same(got, query_ref.expected(text, k, tables, 1, 254))
 
 
 # ------------------------------------------------------------------ 7b. file-backed table groups --
@@ -307,14 +220,13 @@ def test_file_backed_tables_staged_group_after_group(gpu, tmp_path):
     in three groups, the query is streamed once per group, and every byte of a raw table is read exactly once."""
     from pykmer_amd import bgzf, query
     from pykmer_amd.header import Header
-    from test_host_layer import _write_index
     k, N = 9, 5
     paths, tables, bases = [], [], []
     for i in range(N):
         fa, _ = synth.family(i, 60_000)
-        h, got = _write_index(tmp_path, f"q{i}.fa", fa.tobytes(), k)
-        paths.append(h.index_file_root)
-        tables.append(got["table"])
+        w = write_kin(tmp_path, f"q{i}.fa", fa.tobytes(), k)
+        paths.append(w.path)
+        tables.append(w.table)
         bases.append(b"".join(ln for ln in fa.tobytes().split(b"\n") if not ln.startswith(b">")))
     bgzf.compress_file(paths[2], level=1)
     headers = [Header(p, index_file=p) for p in paths]
@@ -333,29 +245,16 @@ def test_file_backed_tables_staged_group_after_group(gpu, tmp_path):
 
 
 # ------------------------------------------------------------------ 8. CLI -------------------------
-def _run(*argv, cwd, env=None):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_end_to_end(gpu, tmp_path):
     k = 9
-    kins, tables = [], []
-    for i in range(3):
-        fa = tmp_path / f"s{i}.fa"
-        data = bytes(synth.family(i, 20_000)[0])
-        fa.write_bytes(data)
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), f"s{i}", str(k), cwd=str(tmp_path))
-        kins.append(f"{fa}.{k:02d}.kin")
-        tables.append(oracle.count_fasta(data, k)["table"])
+    kins, tables = index_cli(tmp_path, ("s0", "s1", "s2"), k)
     with open(kins[1], "rb") as fh:
         raw = fh.read()
     with gzip.open(kins[1] + ".bgz", "wb") as out:
         out.write(raw)
     os.remove(kins[1])
     kins[1] += ".bgz"
-    text = _reads_text(k, n_reads=800, seed=81) + bytes(synth.family(1, 20_000)[0])
+    text = query_ref.reads_text(k, n_reads=800, seed=81) + bytes(synth.family(1, 20_000)[0])
     qf = tmp_path / "queries.fa.gz"
     with gzip.open(qf, "wb") as out:
         out.write(text)
@@ -379,11 +278,11 @@ def test_cli_end_to_end(gpu, tmp_path):
         return [open(proj + ext, "rb").read() for ext in (".kmq", ".kmq.json", ".kmq.tsv")]
 
     a = str(tmp_path / "proj")
-    _run(os.path.join(ROOT, "query.py"), a, str(qf), *kins, "--min-count", "2", "--max-count", "250", cwd=str(tmp_path))
+    run_py("query.py", a, str(qf), *kins, "--min-count", "2", "--max-count", "250", cwd=str(tmp_path))
     files_a = check(a)
     b = str(tmp_path / "grouped")
-    out = _run(os.path.join(ROOT, "query.py"), b, str(qf), *kins, "--min-count", "2", "--max-count", "250", cwd=str(tmp_path),
-               env=dict(os.environ, PK_MERGE_HBM_BUDGET=str(2 * 4 ** k + 1000)))
+    out = run_py("query.py", b, str(qf), *kins, "--min-count", "2", "--max-count", "250", cwd=str(tmp_path),
+                 env=dict(os.environ, PK_MERGE_HBM_BUDGET=str(2 * 4 ** k + 1000))).stdout
     assert "2 table group(s)" in out
     files_b = check(b)
     assert files_a[0] == files_b[0] and files_a[2] == files_b[2]
@@ -392,11 +291,11 @@ def test_cli_end_to_end(gpu, tmp_path):
 
 # ------------------------------------------------------------------ 9. state errors ----------------
 def test_state_errors(gpu):
-    lib = _lib()
+    lib = gs.lib()
     k = 9
     tables = query_ref.random_tables(k, 1, seed=91)
     text = inputs.edge_fasta()
-    with _Device(tables) as dev, lib.QueryIndexer(k, device=0) as q:
+    with Device(tables) as dev, lib.QueryIndexer(k, device=0) as q:
         with pytest.raises(lib.PkError) as e:
             q.feed(text)                                     # no tables yet
         assert e.value.code == lib.PK_ERR_STATE

@@ -5,8 +5,6 @@ import ctypes
 import functools
 import json
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -14,93 +12,14 @@ import pytest
 
 import oracle
 import query_bins_ref
+import gpu_support as gs
 import query_ref
 import synth
+from gpu_support import Device, binned, feed, index_cli, lib, run_py, same_bins
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 16384
 K = 9
-
-
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-def _feed(q, text: bytes, cuts=None):
-    buf = np.frombuffer(text, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(text)]:
-        if c > pos:
-            q.feed(buf[pos:c])
-            pos = c
-
-
-def _collect_bins(q):
-    fin = q.finish()
-    recs = q.records(fin["n_records"])
-    hits, depth, first = q.bin_results(fin["n_records"])
-    return {"fin": fin, "records": recs, "bin_hits": hits.copy(), "bin_depth": depth.copy(), "bin_first": first.copy()}
-
-
-def _sums(rows, first):
-    """Per-record sums of the rows, by a loop (not the function under test)."""
-    out = np.zeros((first.size - 1, rows.shape[1]), dtype=np.uint64)
-    for r in range(first.size - 1):
-        out[r] = rows[int(first[r]):int(first[r + 1])].sum(axis=0, dtype=np.uint64)
-    return out
-
-
-def _binned(q, text: bytes, W: int, cuts=None):
-    """One binned stream through `q` (tables set), then, after a reset, the same text unbinned through the same indexer; the
-    two invariants of every case are asserted here."""
-    q.set_bins(W)
-    _feed(q, text, cuts)
-    got = _collect_bins(q)
-    q.reset()                                                # bins are off again
-    _feed(q, text)
-    fin = q.finish()
-    hits, depth = q.results(fin["n_records"])
-    q.reset()
-    assert fin["n_records"] == got["fin"]["n_records"] and fin["num_kmers"] == got["fin"]["num_kmers"]
-    first = got["bin_first"]
-    assert first.dtype == np.uint64 and first.shape == (fin["n_records"] + 1,) and int(first[0]) == 0
-    assert int(first[-1]) == got["bin_hits"].shape[0] == got["bin_depth"].shape[0]
-    assert np.array_equal(_sums(got["bin_hits"], first), hits) and np.array_equal(_sums(got["bin_depth"], first), depth)
-    got["hits"], got["depth"] = hits.copy(), depth.copy()
-    return got
-
-
-def _same(got, want):
-    assert got["fin"]["n_records"] == len(want["records"]) and got["fin"]["num_kmers"] == int(want["n_valid"].sum())
-    assert np.array_equal(got["records"]["n_valid_kmers"], want["n_valid"]) and np.array_equal(got["records"]["seq_len"], want["seq_len"])
-    assert np.array_equal(got["bin_first"], want["bin_first"]), np.flatnonzero(got["bin_first"] != want["bin_first"])[:5]
-    for key in ("bin_hits", "bin_depth", "hits", "depth"):
-        assert got[key].dtype == np.uint64 and got[key].shape == want[key].shape, key
-        assert np.array_equal(got[key], want[key]), (key, np.argwhere(got[key] != want[key])[:5])
-
-
-@functools.lru_cache(maxsize=None)
-def _tables(k: int, n: int, seed: int):
-    return tuple(query_ref.random_tables(k, n, seed))
 
 
 # ------------------------------------------------------------------ 1. one record across slots -----
@@ -116,13 +35,13 @@ def _one_record() -> bytes:
 def test_one_record_across_slots(gpu, W):
     """W = 1 .. 127: more than 128 rows per slot (rows beyond the LDS accumulator go to HBM); 128 .. 1024: rows inside waves
     and across them; 16384: rows across slots; 10^9: one row for the record."""
-    text, tables = _one_record(), _tables(K, 3, 401)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    text, tables = _one_record(), gs.tables(K, 3, 401)
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         for mn, mx in ((1, 255), (2, 254)):
             q.set_tables(dev.ptrs, mn, mx)
             want = query_bins_ref.expected(text, K, tables, mn, mx, W)
             assert int(want["bin_first"][-1]) == -(-(40_000 - K + 1) // W)
-            _same(_binned(q, text, W), want)
+            same_bins(binned(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 2. gaps ------------------------
@@ -163,12 +82,12 @@ def _gap_bin_sizes():
 def test_gaps(gpu, W):
     """Bins count valid windows: they continue across a run of N, and no window that holds an N is counted."""
     text, start, _ = _gapped()
-    tables = _tables(K, 3, 401)
+    tables = gs.tables(K, 3, 401)
     want = query_bins_ref.expected(text, K, tables, 1, 255, W)
     assert int(want["n_valid"][0]) == start.size and int(want["bin_first"][-1]) == -(-start.size // W)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
-        _same(_binned(q, text, W), want)
+        same_bins(binned(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 3. many records ----------------
@@ -177,51 +96,51 @@ def test_many_records(gpu, s):
     """Reads of 12 bases have four windows: W = 4 fills one bin exactly, 3 gives two bins, 5 and 1000 a partial one; records
     without a window get no row; the long record lies behind more than 128 short ones."""
     text, index = query_ref.long_after_short(s, seed=500 + s, ragged=True)
-    tables = _tables(K, 2, 402)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    tables = gs.tables(K, 2, 402)
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 2, 255)
         for W in (1, 3, 4, 5, 1000):
             want = query_bins_ref.expected(text, K, tables, 2, 255, W)
             empty = want["n_valid"] == 0
             assert empty.sum() > 40 and np.array_equal(np.diff(want["bin_first"].astype(np.int64))[empty], np.zeros(empty.sum(), dtype=np.int64))
             assert int(want["bin_first"][index]) == (want["n_valid"][:index] > 0).sum() * (2 if W == 3 else 4 if W == 1 else 1) >= 84
-            _same(_binned(q, text, W), want)
+            same_bins(binned(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 4. feeds -----------------------
 def test_feeds_cut_anywhere_and_reset(gpu):
     text, _, _ = _gapped()
-    tables = _tables(K, 3, 401)
+    tables = gs.tables(K, 3, 401)
     rng = np.random.default_rng(403)
     # a cut inside the header, a 1-byte piece, cuts at random offsets (all of them inside a bin of 97 windows or more)
     cuts = sorted({3, 4, 2 * CHUNK, *(int(c) for c in rng.integers(12, len(text) - 1, 6))})
     assert text.index(b"\n") > 4 and 4 - 3 == 1
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
-        whole = _binned(q, text, 97)
-        _same(whole, query_bins_ref.expected(text, K, tables, 1, 255, 97))
-        cut = _binned(q, text, 97, cuts=cuts)
+        whole = binned(q, text, 97)
+        same_bins(whole, query_bins_ref.expected(text, K, tables, 1, 255, 97))
+        cut = binned(q, text, 97, cuts=cuts)
         for key in ("bin_hits", "bin_depth", "bin_first", "records"):
             assert np.array_equal(cut[key], whole[key]), key
         # another W after the reset, fed in other pieces
-        _same(_binned(q, text, 4099, cuts=[CHUNK + 1, len(text) - 1]), query_bins_ref.expected(text, K, tables, 1, 255, 4099))
+        same_bins(binned(q, text, 4099, cuts=[CHUNK + 1, len(text) - 1]), query_bins_ref.expected(text, K, tables, 1, 255, 4099))
         # and no bins after a reset: the per-record call answers as before, the binned one refuses
-        _feed(q, text, cuts)
+        feed(q, text, cuts)
         fin = q.finish()
         hits, depth = q.results(fin["n_records"])
         plain = query_ref.expected(text, K, tables, 1, 255)
         assert np.array_equal(hits, plain["hits"]) and np.array_equal(depth, plain["depth"])
-        with pytest.raises(_lib().PkError) as e:
+        with pytest.raises(lib().PkError) as e:
             q.bin_results(fin["n_records"])
-        assert e.value.code == _lib().PK_ERR_STATE
+        assert e.value.code == lib().PK_ERR_STATE
         # with bins on, the per-record call refuses
         q.reset()
         q.set_bins(97)
-        _feed(q, text)
+        feed(q, text)
         fin = q.finish()
-        with pytest.raises(_lib().PkError) as e:
+        with pytest.raises(lib().PkError) as e:
             q.results(fin["n_records"])
-        assert e.value.code == _lib().PK_ERR_STATE
+        assert e.value.code == lib().PK_ERR_STATE
 
 
 # ------------------------------------------------------------------ 5. more than 16 tables ---------
@@ -232,12 +151,12 @@ def test_more_than_sixteen_tables_in_two_staging_groups(gpu, tmp_path):
     text, _ = query_ref.long_after_short(129, seed=629, ragged=True)
     qf = tmp_path / "q.fa"
     qf.write_bytes(text)
-    dense = _tables(K, 20, 404)
+    dense = gs.tables(K, 20, 404)
     tables = [types.SimpleNamespace(kmer_len=K, index_file=f"t{i}.kin", data_size=4 ** K, table=t) for i, t in enumerate(dense)]
     staged = []
 
     def stage(group, device):
-        dev = _Device([g.table for g in group])
+        dev = Device([g.table for g in group])
         staged.append(len(group))
         return query.Staged(dev.ptrs, dev.bufs)
 
@@ -262,29 +181,29 @@ def test_fastq_reads(gpu):
         nl = b"\r\n" if i % 3 == 0 else b"\n"                  # CRLF in part of the set
         out.append(b"@read%d extra" % i + nl + seq + nl + b"+" + nl + bytes(rng.integers(33, 74, n, dtype=np.uint8)) + nl)
     fq = b"".join(out)
-    tables = _tables(K, 2, 406)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0, fmt="fastq") as q:
+    tables = gs.tables(K, 2, 406)
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0, fmt="fastq") as q:
         q.set_tables(dev.ptrs, 1, 255)
         for W in (2, 50):
             want = query_bins_ref.expected(fq, K, tables, 1, 255, W, fmt="fastq")
             assert len(want["records"]) == 400 and (want["n_valid"] == 0).any() and (want["n_valid"] > 50).any()
-            _same(_binned(q, fq, W), want)
-            _same(_binned(q, fq, W, cuts=[1, 20_003, CHUNK]), want)
+            same_bins(binned(q, fq, W), want)
+            same_bins(binned(q, fq, W, cuts=[1, 20_003, CHUNK]), want)
 
 
 # ------------------------------------------------------------------ 7. k = 13 and k = 17 -----------
 def test_k13(gpu):
     k, W, text = 13, 1000, _one_record()
-    tables = _tables(k, 1, 407)
-    with _Device(tables) as dev, _lib().QueryIndexer(k, device=0) as q:
+    tables = gs.tables(k, 1, 407)
+    with Device(tables) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 254)
-        _same(_binned(q, text, W), query_bins_ref.expected(text, k, tables, 1, 254, W))
+        same_bins(binned(q, text, W), query_bins_ref.expected(text, k, tables, 1, 254, W))
 
 
 def test_k17_table_counted_on_the_gpu(gpu):
     """The 64-bit instantiation of the lookup, against a table that was counted on the GPU and never left HBM."""
     k, W = 17, 1000
-    lib = _lib()
+    lib = gs.lib()
     genomes = [synth.family(i, 200_000)[0] for i in range(2)]
     text = bytes(genomes[1]) + bytes(genomes[0])             # another family member, then the indexed genome itself
     sparse = [query_ref.SparseTable(oracle.kmer_list(genomes[0], k))]
@@ -294,8 +213,8 @@ def test_k17_table_counted_on_the_gpu(gpu):
         ix.finish()
         with lib.QueryIndexer(k, device=0) as q:
             q.set_tables([ix.table_device_ptr()], 1, 255)
-            got = _binned(q, text, W)
-    _same(got, want)
+            got = binned(q, text, W)
+    same_bins(got, want)
     n_self = len(oracle.kmer_list(genomes[0], k, records=True)[1]["records"])
     self_rows = got["bin_hits"][int(got["bin_first"][-1 - n_self]):, 0]
     assert n_self >= 1 and np.array_equal(self_rows, want["row_windows"][-self_rows.size:].astype(np.uint64))   # every window of itself hits
@@ -303,31 +222,18 @@ def test_k17_table_counted_on_the_gpu(gpu):
 
 
 # ------------------------------------------------------------------ 8. CLI -------------------------
-def _run(*argv, cwd, status=0):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == status, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_cli_end_to_end(gpu, tmp_path):
     k, W = 9, 500
-    kins, tables = [], []
-    for name in ("a", "b"):
-        fa = tmp_path / f"{name}.fa"
-        data = bytes(synth.family(len(kins), 20_000)[0])
-        fa.write_bytes(data)
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), name, str(k), cwd=str(tmp_path))
-        kins.append(f"{name}.fa.{k:02d}.kin")
-        tables.append(oracle.count_fasta(data, k)["table"])
+    kins, tables = index_cli(tmp_path, ("a", "b"), k)
+    kins = [os.path.basename(kin) for kin in kins]
     text = query_ref.long_after_short(50, seed=650, ragged=True)[0] + bytes(synth.family(1, 20_000)[0])
     (tmp_path / "q.fa").write_bytes(text)
     want = query_bins_ref.expected(text, k, tables, 2, 255, W)
     names = [n.strip() for n in query_ref.names(text, want["records"])]
-    query_py = os.path.join(ROOT, "query.py")
 
-    out = _run(query_py, "P", "q.fa", *kins, "--bin", str(W), "--min-count", "2", cwd=str(tmp_path)).stdout
+    out = run_py("query.py", "P", "q.fa", *kins, "--bin", str(W), "--min-count", "2", cwd=str(tmp_path)).stdout
     assert f"{int(want['bin_first'][-1]):,d} bins" in out
-    _run(query_py, "plain", "q.fa", *kins, "--min-count", "2", cwd=str(tmp_path))
+    run_py("query.py", "plain", "q.fa", *kins, "--min-count", "2", cwd=str(tmp_path))
     made = sorted(p.name for p in tmp_path.iterdir() if p.name.startswith(("P.", "plain.")))
     assert made == ["P.kmb", "P.kmb.json", "P.kmb.tsv", "P.kmq", "P.kmq.json", "P.kmq.tsv", "plain.kmq", "plain.kmq.json", "plain.kmq.tsv"]
     # the .kmq trio is the one of a run without --bin
@@ -360,22 +266,22 @@ def test_cli_end_to_end(gpu, tmp_path):
     assert np.array_equal(np.array([[int(v) for v in r[4:]] for r in rows], dtype=np.uint64), want["bin_hits"])
     # nothing is overwritten, and a bin size below 1 is refused
     before = {p.name: p.read_bytes() for p in tmp_path.iterdir()}
-    r = _run(query_py, "P", "q.fa", *kins, "--bin", str(W), "--min-count", "2", cwd=str(tmp_path), status=1)
+    r = run_py("query.py", "P", "q.fa", *kins, "--bin", str(W), "--min-count", "2", cwd=str(tmp_path), status=1)
     assert r.stderr.splitlines()[-1].startswith("error: ") and "already exists" in r.stderr
-    r = _run(query_py, "Z", "q.fa", *kins, "--bin", "0", cwd=str(tmp_path), status=1)
+    r = run_py("query.py", "Z", "q.fa", *kins, "--bin", "0", cwd=str(tmp_path), status=1)
     assert r.stderr.splitlines()[-1].startswith("error: ") and "bin size" in r.stderr
     assert {p.name: p.read_bytes() for p in tmp_path.iterdir()} == before
 
 
 # ------------------------------------------------------------------ 9. state errors ----------------
 def test_state_errors(gpu):
-    lib = _lib()
+    lib = gs.lib()
     raw = lib.load()
     text, _ = query_ref.long_after_short(20, seed=720, ragged=True)
-    tables = _tables(K, 2, 408)
+    tables = gs.tables(K, 2, 408)
     with lib.Indexer(K, device=0) as ix:                     # not a query indexer
         assert raw.pk_query_set_bins(ix._h, 5) == lib.PK_ERR_STATE
-    with _Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
         with pytest.raises(lib.PkError) as e:
             q.set_bins(5)                                    # before the tables
         assert e.value.code == lib.PK_ERR_STATE

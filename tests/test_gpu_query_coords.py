@@ -4,50 +4,25 @@ bin_end and all binned arrays.  Coordinates do not depend on the tables: these a
 import functools
 import json
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle
 import query_coords_inputs as qci
 import query_bins_ref
 import query_coords_ref
 import query_ref
-import synth
+from gpu_support import Device, feed, index_cli, lib, run_py, same_coords
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = qci.CHUNK
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-@functools.lru_cache(maxsize=None)
 def _tables(k: int, n: int = 2, seed: int = 910):
-    return tuple(query_ref.random_tables(k, n, seed))
+    return gs.tables(k, n, seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,37 +33,9 @@ def _want(name: str, k: int, W: int, fmt: str = "fasta"):
     return text, query_coords_ref.expected(text, k, _tables(k), 1, 255, W, fmt)
 
 
-def _feed(q, text: bytes, cuts=None):
-    buf = np.frombuffer(text, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(text)]:
-        if c > pos:
-            q.feed(buf[pos:c])
-            pos = c
-
-
 def _coords(q, text: bytes, W: int, cuts=None):
     """One binned stream with coordinates through `q` (tables set); the indexer is reset behind it."""
-    q.set_bins(W)
-    q.set_coords(True)
-    _feed(q, text, cuts)
-    fin = q.finish()
-    recs = q.records(fin["n_records"])
-    hits, depth, first = q.bin_results(fin["n_records"])
-    start, end = q.bin_coords()
-    got = {"fin": fin, "records": recs, "bin_hits": hits.copy(), "bin_depth": depth.copy(), "bin_first": first.copy(),
-           "bin_start": start.copy(), "bin_end": end.copy(), "coords_s": q.timings()["coords_s"]}
-    q.reset()
-    return got
-
-
-def _same(got, want):
-    assert got["fin"]["n_records"] == len(want["records"]) and got["fin"]["num_kmers"] == int(want["n_valid"].sum())
-    assert np.array_equal(got["records"]["n_valid_kmers"], want["n_valid"]) and np.array_equal(got["records"]["seq_len"], want["seq_len"])
-    for key in ("bin_first", "bin_hits", "bin_depth", "bin_start", "bin_end"):
-        assert got[key].dtype == np.uint64 and got[key].shape == want[key].shape, key
-        assert np.array_equal(got[key], want[key]), (key, np.argwhere(got[key] != want[key])[:5], got[key][:8], want[key][:8])
-    assert got["coords_s"] > 0 or want["bin_first"][-1] == 0
+    return gs.stream(q, text, bins=W, coords=True, cuts=cuts)
 
 
 # ------------------------------------------------------------------ 1. one gap-free record ---------
@@ -97,10 +44,10 @@ def test_one_gap_free_record(gpu, W):
     k = 9
     text, want = _want("one", k, W)
     query_coords_ref.check_consequences(want, k, W, gap_free=True)
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         got = _coords(q, text, W)
-    _same(got, want)
+    same_coords(got, want)
     b = np.arange(got["bin_start"].size, dtype=np.uint64)
     m = np.uint64(40_000 - k + 1)
     Wc = np.uint64(min(W, 1 << 40))
@@ -112,13 +59,13 @@ def test_one_gap_free_record(gpu, W):
 def test_gaps(gpu, k):
     """Runs of N of length 1, k-1, k, 63, 64, 65 and 300 inside a piece, across piece and chunk seams, over a whole chunk,
     and at both ends of the record (query_coords_inputs.gapped)."""
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         for W in (1, 5, 100, 5000):
             text, want = _want("gapped", k, W)
             query_coords_ref.check_consequences(want, k, W)
             assert int(want["bin_start"][0]) == 64 and int(want["bin_end"][-1]) == int(want["seq_len"][0]) - 65
-            _same(_coords(q, text, W), want)
+            same_coords(_coords(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 3. blanks and line ends --------
@@ -127,10 +74,10 @@ def test_blanks_and_line_ends(gpu, W):
     k = 5
     text, want = _want("blanks", k, W)
     assert len(want["records"]) == 6 and int(want["n_valid"][4]) == 0
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
-        _same(_coords(q, text, W), want)
-        _same(_coords(q, text, W, cuts=[5, 20 * qci.PIECE - 1, CHUNK - 2, CHUNK, 2 * CHUNK - 1, 3 * CHUNK - 1]), want)   # cuts inside the pending blanks
+        same_coords(_coords(q, text, W), want)
+        same_coords(_coords(q, text, W, cuts=[5, 20 * qci.PIECE - 1, CHUNK - 2, CHUNK, 2 * CHUNK - 1, 3 * CHUNK - 1]), want)   # cuts inside the pending blanks
 
 
 # ------------------------------------------------------------------ 4. many records ----------------
@@ -138,13 +85,13 @@ def test_blanks_and_line_ends(gpu, W):
 def test_many_records(gpu, s):
     """More than 64 records in a chunk, empty and shorter-than-k records between them, the long record behind them."""
     k = 5
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         for W in (1, 3, 8, 1000):
             text, want = _want(f"many{s}", k, W)
             assert (want["n_valid"] == 0).sum() > 40
             query_coords_ref.check_consequences(want, k, W, gap_free=True)
-            _same(_coords(q, text, W), want)
+            same_coords(_coords(q, text, W), want)
 
 
 def test_short_reads_on_a_fresh_indexer_and_again_after_a_reset(gpu):
@@ -153,14 +100,14 @@ def test_short_reads_on_a_fresh_indexer_and_again_after_a_reset(gpu):
     k, W = 5, 3
     text, want = _want("short", k, W)
     assert len(want["records"]) == 5000 > 4096
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         first = _coords(q, text, W)
-        _same(first, want)
+        same_coords(first, want)
         again = _coords(q, text, W)
-        _same(again, want)
+        same_coords(again, want)
         halves = _coords(q, text, W, cuts=[len(text) // 2 + 1])
-        _same(halves, want)
+        same_coords(halves, want)
 
 
 def test_short_reads_retry_in_the_second_feed(gpu):
@@ -175,9 +122,9 @@ def test_short_reads_retry_in_the_second_feed(gpu):
     assert int(query_coords_ref.expected(text[:cut], k, _tables(k), 1, 255, W)["n_valid"][100]) == 5
     assert opened + 2 * opened + 1024 < 4096                 # the first feed does not grow the record array ...
     assert len(want["records"]) == 5000 > 4096               # ... and the second does not fit in it
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
-        _same(_coords(q, text, W, cuts=[cut]), want)
+        same_coords(_coords(q, text, W, cuts=[cut]), want)
 
 
 # ------------------------------------------------------------------ 5. feeds -----------------------
@@ -199,10 +146,10 @@ def test_feeds(gpu, W):
     """The provisional end of the row that is open when a feed ends is overwritten by the feed that adds windows to it."""
     k = 9
     text, want, cuts = _gap_cuts(k, W)
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         whole = _coords(q, text, W)
-        _same(whole, want)
+        same_coords(whole, want)
         for some in (cuts, cuts[1:2], cuts[2:3], [CHUNK, 2 * CHUNK + 1, 9 * CHUNK + 5000, 10 * CHUNK]):
             cut = _coords(q, text, W, cuts=some)
             for key in ("bin_start", "bin_end", "bin_hits", "bin_depth", "bin_first"):
@@ -223,7 +170,7 @@ def test_more_than_1024_chunks_in_one_feed(gpu):
     text = long_rec + tail
     assert 1024 * CHUNK < len(long_rec) and -(-len(text) // CHUNK) == 1025      # the scan's second round: one chunk
     seq_len_t, n_win_t, starts_t = query_coords_ref.window_starts(tail, k)
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         for W in (4099, 10 ** 9):
             want = query_bins_ref.expected(text, k, _tables(k), 1, 255, W)
@@ -235,29 +182,29 @@ def test_more_than_1024_chunks_in_one_feed(gpu):
             assert int(want["bin_end"][want["row_record"] == 0][-1]) == n_long
             q.set_bins(W)
             q.set_coords(True)
-            _feed(q, text)
+            feed(q, text)
             assert q.timings()["feeds"] == 1, "the text was meant to be one feed of 1025 chunks"
             q.reset()
-            _same(_coords(q, text, W), want)
+            same_coords(_coords(q, text, W), want)
 
 
 # ------------------------------------------------------------------ 6. FASTQ -----------------------
 def test_fastq_reads(gpu):
     k = 9
-    with _Device(_tables(k)) as dev, _lib().QueryIndexer(k, device=0, fmt="fastq") as q:
+    with Device(_tables(k)) as dev, lib().QueryIndexer(k, device=0, fmt="fastq") as q:
         q.set_tables(dev.ptrs, 1, 255)
         for W in (2, 50):
             fq, want = _want("fastq", k, W, "fastq")
             assert len(want["records"]) == 300 and (want["n_valid"] == 0).any() and (want["n_valid"] > 50).any()
             query_coords_ref.check_consequences(want, k, W)
-            _same(_coords(q, fq, W), want)
-            _same(_coords(q, fq, W, cuts=[1, 10_003, CHUNK]), want)
+            same_coords(_coords(q, fq, W), want)
+            same_coords(_coords(q, fq, W, cuts=[1, 10_003, CHUNK]), want)
 
 
 # ------------------------------------------------------------------ 7. k = 17, more than 16 tables -
 def test_k17_table_counted_on_the_gpu(gpu):
     k, W = 17, 1000
-    lib = _lib()
+    lib = gs.lib()
     genomes = qci.k17_genomes()
     text = qci.k17_text()
     sparse = [query_ref.SparseTable(oracle.kmer_list(genomes[0], k))]
@@ -268,7 +215,7 @@ def test_k17_table_counted_on_the_gpu(gpu):
         with lib.QueryIndexer(k, device=0) as q:
             q.set_tables([ix.table_device_ptr()], 1, 255)
             got = _coords(q, text, W)
-    _same(got, want)
+    same_coords(got, want)
 
 
 def test_seventeen_tables_in_two_staging_groups(gpu, tmp_path):
@@ -284,7 +231,7 @@ def test_seventeen_tables_in_two_staging_groups(gpu, tmp_path):
     staged, with_coords = [], []
 
     def stage(group, device):
-        dev = _Device([g.table for g in group])
+        dev = Device([g.table for g in group])
         staged.append(len(group))
         return query.Staged(dev.ptrs, dev.bufs)
 
@@ -302,28 +249,15 @@ def test_seventeen_tables_in_two_staging_groups(gpu, tmp_path):
 
 
 # ------------------------------------------------------------------ 8. CLI -------------------------
-def _run(*argv, cwd, status=0):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == status, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def test_cli_end_to_end(gpu, tmp_path):
     k, W = 9, 50
-    kins, tables = [], []
-    for name in ("a", "b"):
-        fa = tmp_path / f"{name}.fa"
-        data = bytes(synth.family(len(kins), 20_000)[0])
-        fa.write_bytes(data)
-        _run(os.path.join(ROOT, "indexer.py"), str(fa), name, str(k), cwd=str(tmp_path))
-        kins.append(f"{name}.fa.{k:02d}.kin")
-        tables.append(oracle.count_fasta(data, k)["table"])
+    kins, tables = index_cli(tmp_path, ("a", "b"), k)
+    kins = [os.path.basename(kin) for kin in kins]
     text = qci.blanks() + qci.gapped(k)[0][:30_000] + b"\n"
     (tmp_path / "q.fa").write_bytes(text)
     want = query_coords_ref.expected(text, k, tables, 1, 255, W)
-    query_py = os.path.join(ROOT, "query.py")
-    _run(query_py, "C", "q.fa", *kins, "--bin", str(W), "--coords", cwd=str(tmp_path))
-    _run(query_py, "P", "q.fa", *kins, "--bin", str(W), cwd=str(tmp_path))
+    run_py("query.py", "C", "q.fa", *kins, "--bin", str(W), "--coords", cwd=str(tmp_path))
+    run_py("query.py", "P", "q.fa", *kins, "--bin", str(W), cwd=str(tmp_path))
     made = sorted(p.name for p in tmp_path.iterdir() if p.name.startswith(("C.", "P.")))
     assert made == [f"{p}.{e}" for p in "CP" for e in ("kmb", "kmb.json", "kmb.tsv", "kmq", "kmq.json", "kmq.tsv")]
     zc, zp = np.load(tmp_path / "C.kmb"), np.load(tmp_path / "P.kmb")
@@ -350,7 +284,7 @@ def test_cli_end_to_end(gpu, tmp_path):
     assert np.array_equal(np.array([int(r[5]) for r in rows_c], dtype=np.uint64), zc["bin_end"])
     assert (tmp_path / "C.kmq.tsv").read_bytes() == (tmp_path / "P.kmq.tsv").read_bytes()
     assert np.array_equal(np.load(tmp_path / "C.kmq")["hits"], np.load(tmp_path / "P.kmq")["hits"])
-    r = _run(query_py, "Z", "q.fa", *kins, "--coords", cwd=str(tmp_path), status=1)
+    r = run_py("query.py", "Z", "q.fa", *kins, "--coords", cwd=str(tmp_path), status=1)
     # (the device warms up on a thread of its own beside the argument checks: its chatter may follow the message)
     assert [ln for ln in r.stderr.splitlines() if ln.startswith("error: ") and "--bin" in ln]
     assert not [p for p in tmp_path.iterdir() if p.name.startswith("Z.")]
@@ -358,14 +292,14 @@ def test_cli_end_to_end(gpu, tmp_path):
 
 # ------------------------------------------------------------------ 9. state errors ----------------
 def test_state_errors(gpu):
-    lib = _lib()
+    lib = gs.lib()
     raw = lib.load()
     k, W = 5, 3
     text, want = _want("many127", k, W)
     one = np.zeros(1, dtype=np.uint64)
     with lib.Indexer(k, device=0) as ix:                     # not a query indexer
         assert raw.pk_query_set_coords(ix._h, 1) == lib.PK_ERR_STATE
-    with _Device(_tables(k)) as dev, lib.QueryIndexer(k, device=0) as q:
+    with Device(_tables(k)) as dev, lib.QueryIndexer(k, device=0) as q:
         q.set_tables(dev.ptrs, 1, 255)
         with pytest.raises(lib.PkError) as e:
             q.set_coords(True)                               # before the bins
@@ -375,7 +309,7 @@ def test_state_errors(gpu):
         q.set_bins(W)
         q.set_coords(True)
         q.set_coords(False)                                  # any number of times before the first feed
-        _feed(q, text)
+        feed(q, text)
         with pytest.raises(lib.PkError) as e:
             q.set_coords(True)                               # after the first feed
         assert e.value.code == lib.PK_ERR_STATE
@@ -389,13 +323,13 @@ def test_state_errors(gpu):
         # a reset clears the setting with the bins; set again, the same indexer delivers
         q.reset()
         q.set_bins(W)
-        _feed(q, text)
+        feed(q, text)
         q.finish()
         assert raw.pk_query_bin_coords(q._h, one.ctypes.data, one.ctypes.data, 1 << 40) == lib.PK_ERR_STATE
         q.reset()
         q.set_bins(W)
         q.set_coords(True)
-        _feed(q, text)
+        feed(q, text)
         with pytest.raises(lib.PkError) as e:
             q.bin_coords()                                   # before finish
         assert e.value.code == lib.PK_ERR_STATE

@@ -5,103 +5,22 @@ text with the option off, and no pair shares more windows than either of its tab
 import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle
 import query_pairs_ref as ref
 import query_ref
 import synth
 from fastq_qual_ref import mask_fastq_to_fasta
-from test_gpu_query import _reads_text
+from gpu_support import Device, checked_pairs, feed, index_cli, lib, run_py
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 16384
 K = 9
 QPAIR_ROWS = 64                                              # kmer_query.hip: the rows of a slot whose pairs are tallied in LDS
-
-
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
-class _Device:
-    """Host tables staged in HBM for the length of a test."""
-
-    def __init__(self, tables):
-        self.bufs = [_lib().DeviceBuffer(t.size, 0) for t in tables]
-        for b, t in zip(self.bufs, tables):
-            b.upload(t)
-        self.ptrs = [b.ptr for b in self.bufs]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
-
-
-def _feed(q, text: bytes, cuts=None):
-    buf = np.frombuffer(text, dtype=np.uint8)
-    pos = 0
-    for c in list(cuts or []) + [len(text)]:
-        if c > pos:
-            q.feed(buf[pos:c])
-            pos = c
-
-
-def _stream(q, text: bytes, W=None, pairs=True, cuts=None, bins_last=False):
-    """One stream through `q` (tables set), then a reset.  bins_last: pk_query_set_pairs before pk_query_set_bins."""
-    if W is not None and not bins_last:
-        q.set_bins(W)
-    if pairs:
-        q.set_pairs(True)
-    if W is not None and bins_last:
-        q.set_bins(W)
-    _feed(q, text, cuts)
-    fin = q.finish()
-    n = fin["n_records"]
-    out = {"fin": fin, "n_valid": q.records(n)["n_valid_kmers"].astype(np.uint64)}
-    if W is None:
-        hits, depth = q.results(n)
-        rows = n
-    else:
-        hits, depth, first = q.bin_results(n)
-        rows = int(first[-1])
-        out["bin_first"] = first.copy()
-    out.update(hits=hits.copy(), depth=depth.copy())
-    if pairs:
-        out["shared"] = q.pairs(rows).copy()
-    q.reset()
-    return out
-
-
-def _checked(q, text: bytes, want: dict, W=None, cuts=None, bins_last=False):
-    """A stream with the option on and one with it off through `q` (tables set with the window of `want`): the unchanged
-    tallies, the bound, and hits and shared against the yardstick."""
-    got = _stream(q, text, W, True, cuts, bins_last)
-    plain = _stream(q, text, W, False)
-    for key in ("hits", "depth", "n_valid") + (("bin_first",) if W is not None else ()):
-        assert np.array_equal(got[key], plain[key]), key
-    assert np.array_equal(got["n_valid"], want["n_valid"]) and got["fin"]["num_kmers"] == int(want["n_valid"].sum())
-    if W is not None:
-        assert np.array_equal(got["bin_first"], want["bin_first"])
-    assert np.array_equal(got["hits"], want["hits"])
-    assert got["shared"].dtype == np.uint64 and got["shared"].shape == want["shared"].shape, (got["shared"].shape, want["shared"].shape)
-    assert np.array_equal(got["shared"], want["shared"]), np.argwhere(got["shared"] != want["shared"])[:5]
-    ref.check_identities(got["shared"], got["hits"])
-    return got
-
-
-@functools.lru_cache(maxsize=None)
-def _tables(k: int, n: int, seed: int):
-    return tuple(query_ref.random_tables(k, n, seed))
 
 
 # ------------------------------------------------------------------ 1. one record across three slots
@@ -118,18 +37,18 @@ def test_one_record_across_three_slots(gpu, W):
     N = 1 has no pair (an empty second axis), 16 fills every plane."""
     text = _long_text()
     assert 2 * CHUNK < len(text) < 3 * CHUNK
-    tables = _tables(K, 16, 901)
+    tables = gs.tables(K, 16, 901)
     sums = {}
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         for N in (1, 2, 3, 16):
             for window in ((1, 255), (2, 5), (255, 255)):
                 want = ref.expected(text, K, tables[:N], *window, W=W)
                 assert want["shared"].shape[1] == N * (N - 1) // 2 and (N == 1 or want["shared"].any())
                 q.set_tables(dev.ptrs[:N], *window)
-                got = _checked(q, text, want, W=W, bins_last=N == 3)
+                got = checked_pairs(q, text, want, W=W, bins_last=N == 3)
                 sums[N, window] = got["shared"].sum(axis=0, dtype=np.uint64)
                 if W is not None:                            # each record's rows sum to the unbinned run
-                    per_record = _stream(q, text)
+                    per_record = gs.stream(q, text, pairs=True)
                     assert np.array_equal(ref.record_sums(got["shared"], got["bin_first"]), per_record["shared"])
     assert sums[16, (1, 255)].size == 120 and sums[16, (1, 255)].all()
 
@@ -143,8 +62,8 @@ def test_long_record_behind_short_ones(gpu, s, ragged):
     HBM directly for the first row beyond and for later ones; from 129 on the hits of the same wave go to HBM as well.
     N = 2, 3, 16: an even and an odd number of planes, and all sixteen (every plane register full).  W = 1000: the record has twelve rows."""
     text, index = query_ref.long_after_short(s, seed=980 + s, ragged=ragged, tail_len=4000)
-    tables = _tables(K, 16, 901)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    tables = gs.tables(K, 16, 901)
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         for N in (2, 3, 16):
             for window in ((1, 255), (255, 255)):
                 q.set_tables(dev.ptrs[:N], *window)
@@ -153,7 +72,7 @@ def test_long_record_behind_short_ones(gpu, s, ragged):
                     rows = slice(index, index + 1) if W is None else slice(int(want["bin_first"][index]), int(want["bin_first"][index + 1]))
                     assert want["n_valid"][index] == 12_000 - K + 1 and want["shared"][rows].all()
                     assert W is None or rows.stop - rows.start == 12 and (ragged or rows.start == s)
-                    _checked(q, text, want, W=W)
+                    checked_pairs(q, text, want, W=W)
 
 
 # ------------------------------------------------------------------ 2. many rows per slot ----------
@@ -172,12 +91,12 @@ def _reads(n_reads: int, seed: int) -> bytes:
 @pytest.mark.parametrize("W", [None, 16])
 def test_many_reads_per_slot(gpu, W):
     text = _reads(5000, 910)
-    tables = _tables(K, 5, 911)
+    tables = gs.tables(K, 5, 911)
     want = ref.expected(text, K, tables, 1, 254, W=W)
     assert len(want["records"]) == 5000 and (want["n_valid"] == 0).sum() > 400
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 1, 254)
-        got = _checked(q, text, want, W=W)
+        got = checked_pairs(q, text, want, W=W)
     if W is None:
         assert not got["shared"][want["n_valid"] == 0].any()
 
@@ -191,53 +110,53 @@ def test_fastq_reads_masked_and_not(gpu):
         nl = b"\r\n" if i % 3 == 0 else b"\n"
         out.append(b"@read%d extra" % i + nl + seq + nl + b"+" + nl + bytes(rng.integers(33, 74, n, dtype=np.uint8)) + nl)
     fq = b"".join(out)
-    tables = _tables(K, 3, 921)
-    with _Device(tables) as dev:
-        with _lib().QueryIndexer(K, device=0, fmt="fastq") as q:
+    tables = gs.tables(K, 3, 921)
+    with Device(tables) as dev:
+        with lib().QueryIndexer(K, device=0, fmt="fastq") as q:
             q.set_tables(dev.ptrs, 1, 255)
             want = ref.expected(fq, K, tables, 1, 255, fmt="fastq")
             assert len(want["records"]) == 3000 and (want["n_valid"] == 0).any()
-            _checked(q, fq, want)
-            _checked(q, fq, ref.expected(fq, K, tables, 1, 255, W=16, fmt="fastq"), W=16, cuts=[20_003])
+            checked_pairs(q, fq, want)
+            checked_pairs(q, fq, ref.expected(fq, K, tables, 1, 255, W=16, fmt="fastq"), W=16, cuts=[20_003])
         T = 33 + 3
         fasta, masked = mask_fastq_to_fasta(fq, T)
-        with _lib().QueryIndexer(K, device=0, fmt="fastq", min_qual_byte=T) as q:
+        with lib().QueryIndexer(K, device=0, fmt="fastq", min_qual_byte=T) as q:
             q.set_tables(dev.ptrs, 1, 255)
             low = ref.expected(fasta, K, tables, 1, 255)
             assert masked > 1000 and 0 < int(low["n_valid"].sum()) < int(want["n_valid"].sum())
-            _checked(q, fq, low)
-            _checked(q, fq, ref.expected(fasta, K, tables, 1, 255, W=16), W=16)
+            checked_pairs(q, fq, low)
+            checked_pairs(q, fq, ref.expected(fasta, K, tables, 1, 255, W=16), W=16)
 
 
 # ------------------------------------------------------------------ 3. feeds, retries, state -------
 def test_feeds_cut_inside_a_record_and_a_window(gpu):
     text = _long_text() + _reads(800, 930)
-    tables = _tables(K, 4, 931)
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    tables = gs.tables(K, 4, 931)
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 2, 254)
         for W in (None, 100):
             want = ref.expected(text, K, tables, 2, 254, W=W)
-            uncut = _checked(q, text, want, W=W)
-            cut = _checked(q, text, want, W=W, cuts=[7, 8, 5000, 5003, CHUNK, CHUNK + 5, 2 * CHUNK - 3, len(text) - 40, len(text) - 1])
+            uncut = checked_pairs(q, text, want, W=W)
+            cut = checked_pairs(q, text, want, W=W, cuts=[7, 8, 5000, 5003, CHUNK, CHUNK + 5, 2 * CHUNK - 3, len(text) - 40, len(text) - 1])
             assert np.array_equal(cut["shared"], uncut["shared"])
 
 
 def test_retried_feeds_count_nothing_twice(gpu):
     """A fresh indexer whose first feed opens more records than the record array holds: the squeeze backs out, the arrays
     grow and the feed runs again; the second feed does the same."""
-    lib = _lib()
-    text = _reads_text(K, n_reads=24_000, seed=941)
+    lib = gs.lib()
+    text = query_ref.reads_text(K, n_reads=24_000, seed=941)
     at = text.index(b">r5000\n")
     assert text[:at].count(b">") == 5000 > 4096
-    tables = _tables(K, 3, 942)
+    tables = gs.tables(K, 3, 942)
     for W in (None, 5):
         want = ref.expected(text, K, tables, 1, 255, W=W)
-        with _Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
+        with Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
             q.set_tables(dev.ptrs, 1, 255)
             if W is not None:
                 q.set_bins(W)
             q.set_pairs(True)
-            _feed(q, text, [at])                             # 5000 records, then 19 000 more: both feeds outgrow the array
+            feed(q, text, [at])                             # 5000 records, then 19 000 more: both feeds outgrow the array
             fin = q.finish()
             assert fin["n_records"] == 24_000
             rows = fin["n_records"] if W is None else int(q.bin_results(fin["n_records"])[2][-1])
@@ -245,15 +164,15 @@ def test_retried_feeds_count_nothing_twice(gpu):
 
 
 def test_state_errors_and_reset(gpu):
-    lib = _lib()
+    lib = gs.lib()
     raw = lib.load()
     text, _ = query_ref.long_after_short(20, seed=950, ragged=True)
-    tables = _tables(K, 3, 951)
+    tables = gs.tables(K, 3, 951)
     one = np.zeros(1, dtype=np.uint64)
     with lib.Indexer(K, device=0) as ix:                     # not a query indexer
         assert raw.pk_query_set_pairs(ix._h, 1) == lib.PK_ERR_STATE
         assert raw.pk_query_pairs(ix._h, one.ctypes.data, 1) == lib.PK_ERR_STATE
-    with _Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib.QueryIndexer(K, device=0) as q:
         with pytest.raises(lib.PkError) as e:
             q.set_pairs(True)                                # before the tables
         assert e.value.code == lib.PK_ERR_STATE and "pk_query_set_tables" in str(e.value)
@@ -300,12 +219,12 @@ def test_state_errors_and_reset(gpu):
 
 def test_two_equal_tables_share_their_hits(gpu):
     text = _long_text() + _reads(500, 960)
-    a, b = _tables(K, 2, 961)
+    a, b = gs.tables(K, 2, 961)
     tables = (a, b, a.copy())
-    with _Device(tables) as dev, _lib().QueryIndexer(K, device=0) as q:
+    with Device(tables) as dev, lib().QueryIndexer(K, device=0) as q:
         q.set_tables(dev.ptrs, 2, 254)
         for W in (None, 50):
-            got = _checked(q, text, ref.expected(text, K, tables, 2, 254, W=W), W=W)
+            got = checked_pairs(q, text, ref.expected(text, K, tables, 2, 254, W=W), W=W)
             assert np.array_equal(got["shared"][:, 1], got["hits"][:, 0]) and got["hits"][:, 0].any()       # pair (0, 2)
             assert np.array_equal(got["shared"][:, 0], got["shared"][:, 2])                                 # (0, 1) and (1, 2)
 
@@ -315,7 +234,7 @@ def test_two_equal_tables_share_their_hits(gpu):
 def test_tables_counted_on_the_gpu(gpu, k):
     """The 32-bit (k = 15) and the 64-bit (k = 17) instantiation, against tables that were counted on the GPU and never left
     HBM; the reference reads them as SparseTables."""
-    lib = _lib()
+    lib = gs.lib()
     genomes = [bytes(synth.family(i, 60_000)[0]) for i in range(2)]
     text = genomes[1] + genomes[0]
     sparse = [query_ref.SparseTable(oracle.kmer_list(g, k)) for g in genomes]
@@ -325,35 +244,26 @@ def test_tables_counted_on_the_gpu(gpu, k):
             ix.finish()
         with lib.QueryIndexer(k, device=0) as q:
             q.set_tables([ix.table_device_ptr() for ix in (a, b)], 1, 255)
-            got = _checked(q, text, ref.expected(text, k, sparse, 1, 255))
-            _checked(q, text, ref.expected(text, k, sparse, 1, 255, W=1000), W=1000)
+            got = checked_pairs(q, text, ref.expected(text, k, sparse, 1, 255))
+            checked_pairs(q, text, ref.expected(text, k, sparse, 1, 255, W=1000), W=1000)
     assert got["shared"].any()
 
 
 # ------------------------------------------------------------------ 5. CLI -------------------------
 def _run(*argv, cwd, status=0):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == status, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
+    return run_py(*argv, cwd=cwd, status=status, env=gs.env_with_root())
 
 
 def test_cli_end_to_end(gpu, tmp_path):
-    kins, tables = [], []
-    for name in ("a", "b", "c"):
-        data = bytes(synth.family(len(kins), 20_000)[0])
-        (tmp_path / f"{name}.fa").write_bytes(data)
-        _run(os.path.join(ROOT, "indexer.py"), f"{name}.fa", name, str(K), cwd=str(tmp_path))
-        kins.append(f"{name}.fa.{K:02d}.kin")
-        tables.append(oracle.count_fasta(data, K)["table"])
+    kins, tables = index_cli(tmp_path, ("a", "b", "c"), K)
+    kins = [os.path.basename(kin) for kin in kins]
     text = query_ref.long_after_short(30, seed=970, ragged=True)[0] + bytes(synth.family(1, 20_000)[0])
     (tmp_path / "q.fa").write_bytes(text)
-    query_py = os.path.join(ROOT, "query.py")
     before = {p.name for p in tmp_path.iterdir()}
-    r = _run(query_py, "P", "q.fa", *kins, "--pairs", cwd=str(tmp_path))
+    r = _run("query.py", "P", "q.fa", *kins, "--pairs", cwd=str(tmp_path))
     assert r.stdout.strip().splitlines()[-1].endswith(", 3 pairs")
-    _run(query_py, "B", "q.fa", *kins, "--bin", "50", "--coords", "--pairs", cwd=str(tmp_path))
-    _run(query_py, "D", "q.fa", *kins, "--bin", "50", "--coords", cwd=str(tmp_path))        # without the option: the files as before
+    _run("query.py", "B", "q.fa", *kins, "--bin", "50", "--coords", "--pairs", cwd=str(tmp_path))
+    _run("query.py", "D", "q.fa", *kins, "--bin", "50", "--coords", cwd=str(tmp_path))        # without the option: the files as before
     trio, kmb = ["kmq", "kmq.json", "kmq.tsv"], ["kmb", "kmb.json", "kmb.tsv"]
     kmp = ["kmp", "kmp.json", "kmp.tsv"]
     made = sorted(p.name for p in tmp_path.iterdir() if p.name not in before)
@@ -404,10 +314,10 @@ def test_cli_end_to_end(gpu, tmp_path):
     assert np.array_equal(np.load(tmp_path / "S.001-255.kma")["matrix"], qpairs.row_matrix(binned["hits"][at], binned["shared"][at]))
     # refusals: nothing written
     listing = sorted(p.name for p in tmp_path.iterdir())
-    r = _run(query_py, "X", "q.fa", *kins, "--pairs", "--spectrum", cwd=str(tmp_path), status=1)
+    r = _run("query.py", "X", "q.fa", *kins, "--pairs", "--spectrum", cwd=str(tmp_path), status=1)
     assert [ln for ln in r.stderr.splitlines() if ln.startswith("error: ")]
     (tmp_path / "only.kmp.tsv").write_bytes(b"")
-    r = _run(query_py, "only", "q.fa", *kins, "--pairs", cwd=str(tmp_path), status=1)
+    r = _run("query.py", "only", "q.fa", *kins, "--pairs", cwd=str(tmp_path), status=1)
     assert [ln for ln in r.stderr.splitlines() if ln.startswith("error: ") and "already exists" in ln]
     (tmp_path / "only.kmp.tsv").unlink()
     assert sorted(p.name for p in tmp_path.iterdir()) == listing

@@ -12,16 +12,14 @@ import types
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import query_bins_ref
 import query_coords_ref
 import query_pairs_ref
 import query_ref
 import query_spectrum_ref
-import test_gpu_query_bins as t_bins
-import test_gpu_query_coords as t_coords
-import test_gpu_query_pairs as t_pairs
-import test_gpu_query_spectrum as t_spec
 from fastq_qual_ref import mask_fastq_to_fasta
+from gpu_support import binned, checked_pairs, checked_spectrum, lib, same, same_bins, same_coords, stream
 
 pytestmark = pytest.mark.gpu
 CHUNK = query_ref.CHUNK
@@ -29,16 +27,11 @@ WINDOWS = ((1, 255), (2, 254))
 QACC_RECS, QSPEC_ROWS, QPAIR_ROWS = 128, 32, 64              # kmer_query.hip: the rows of a slot that are tallied in LDS
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
 @contextlib.contextmanager
 def _counted(k):
     """The counted tables of k (three, at k = 17 two of 16 GiB) in their indexers, and one QueryIndexer that every case
     streams through, with a reset between two streams."""
-    lib = _lib()
+    lib = gs.lib()
     sources, sparse = query_ref.counted_case(k)
     with contextlib.ExitStack() as stack:
         ptrs = []
@@ -79,18 +72,6 @@ def only(*ks):
     return pytest.mark.parametrize("k", ks)
 
 
-def _plain(q, text, cuts=None):
-    return t_pairs._stream(q, text, None, False, cuts)
-
-
-def _same_plain(got, want):
-    assert got["fin"]["n_records"] == len(want["records"]) and got["fin"]["num_kmers"] == int(want["n_valid"].sum())
-    assert np.array_equal(got["n_valid"], want["n_valid"])
-    for key in ("hits", "depth"):
-        assert got[key].dtype == np.uint64 and got[key].shape == want[key].shape, key
-        assert np.array_equal(got[key], want[key]), (key, np.argwhere(got[key] != want[key])[:5])
-
-
 def _same_as_plain(got, plain, keys=("hits", "depth", "n_valid")):
     for key in keys:
         assert np.array_equal(got[key], plain[key]), key
@@ -112,30 +93,30 @@ def test_reads_with_every_option(at_k, option):
     text = query_ref.reads_case(k)
     for window in WINDOWS:
         q.set_tables(at_k.ptrs, *window)
-        plain = _plain(q, text)
-        _same_plain(plain, query_ref.expected(text, k, tables, *window))
+        plain = stream(q, text)
+        same(plain, query_ref.expected(text, k, tables, *window))
         assert plain["hits"].any(axis=0).all() and (plain["n_valid"] == 0).sum() > 3000 // 4
         if option == "bins":
             for W in (1, 3, 1000):
                 want = query_bins_ref.expected(text, k, tables, *window, W)
-                got = t_bins._binned(q, text, W)             # (its record sums equal the unbinned run through the same indexer)
-                t_bins._same(got, want)
+                got = binned(q, text, W)             # (its record sums equal the unbinned run through the same indexer)
+                same_bins(got, want)
                 _same_as_plain(got, plain, ("hits", "depth"))
         elif option == "coords":
             want = query_coords_ref.expected(text, k, tables, *window, 3)
-            got = t_coords._coords(q, text, 3)
-            t_coords._same(got, want)
-            off = t_bins._binned(q, text, 3)
+            got = stream(q, text, bins=3, coords=True)
+            same_coords(got, want)
+            off = binned(q, text, 3)
             _same_as_plain(got, off, ("bin_hits", "bin_depth", "bin_first"))
             assert np.array_equal(got["records"], off["records"])
         elif option == "spectrum":
             for W in (None, 3):
-                got = t_spec._checked(q, text, window, _spectrum_want(k, W), W=W)      # (against the same stream with the option off)
+                got = checked_spectrum(q, text, window, _spectrum_want(k, W), W=W)      # (against the same stream with the option off)
                 if W is None:
                     _same_as_plain(got, plain)
         else:
             for W in (None, 3):
-                got = t_pairs._checked(q, text, query_pairs_ref.expected(text, k, tables, *window, W=W), W=W)
+                got = checked_pairs(q, text, query_pairs_ref.expected(text, k, tables, *window, W=W), W=W)
                 assert got["shared"].any(axis=0).all()
                 if W is None:
                     _same_as_plain(got, plain)
@@ -150,14 +131,14 @@ def test_reads_cut_into_feeds(at_k):
     assert text[hdr - 2:hdr] == b">r" and text[hdr:hdr + 1].isdigit()
     cuts = sorted({7, 8, hdr, CHUNK, CHUNK + 5, 2 * CHUNK - 3, len(text) - 1})
     q.set_tables(at_k.ptrs, 1, 255)
-    whole, cut = _plain(q, text), _plain(q, text, cuts)
-    _same_plain(whole, query_ref.expected(text, k, tables, 1, 255))
+    whole, cut = stream(q, text), stream(q, text, cuts=cuts)
+    same(whole, query_ref.expected(text, k, tables, 1, 255))
     _same_as_plain(cut, whole)
     want = query_pairs_ref.expected(text, k, tables, 1, 255)
-    whole, cut = t_pairs._checked(q, text, want), t_pairs._checked(q, text, want, cuts=cuts)
+    whole, cut = checked_pairs(q, text, want), checked_pairs(q, text, want, cuts=cuts)
     assert np.array_equal(cut["shared"], whole["shared"])
     want = _spectrum_want(k)
-    whole, cut = t_spec._checked(q, text, (1, 255), want), t_spec._checked(q, text, (1, 255), want, cuts=cuts)
+    whole, cut = checked_spectrum(q, text, (1, 255), want), checked_spectrum(q, text, (1, 255), want, cuts=cuts)
     assert np.array_equal(cut["spectrum"], whole["spectrum"])
 
 
@@ -170,7 +151,7 @@ def test_retried_feed_counts_nothing_twice(at_k, option):
     k, tables = at_k.k, at_k.sparse
     text = query_ref.reads_case(k, 5000)
     assert text.count(b">") == 5000 > 4096
-    with _lib().QueryIndexer(k, device=0) as q:
+    with lib().QueryIndexer(k, device=0) as q:
         q.set_tables(at_k.ptrs, 1, 255)
         if option == "pairs":
             want = query_pairs_ref.expected(text, k, tables, 1, 255)
@@ -197,18 +178,18 @@ def test_fastq_reads_masked_and_not(at_k):
     fq = query_ref.reads_case(k, 3000, True)
     T = 33 + 20
     fasta, n_masked = mask_fastq_to_fasta(fq, T)
-    with _lib().QueryIndexer(k, device=0, fmt="fastq") as q:
+    with lib().QueryIndexer(k, device=0, fmt="fastq") as q:
         q.set_tables(at_k.ptrs, 1, 255)
         want = query_ref.expected(fq, k, tables, 1, 255, fmt="fastq")          # (through fastq_ref.fastq_to_fasta)
         assert len(want["records"]) == 3000 and (want["n_valid"] == 0).any()
-        _same_plain(_plain(q, fq), want)
-        t_pairs._checked(q, fq, query_pairs_ref.expected(fq, k, tables, 1, 255, fmt="fastq"))
-    with _lib().QueryIndexer(k, device=0, fmt="fastq", min_qual_byte=T) as q:
+        same(stream(q, fq), want)
+        checked_pairs(q, fq, query_pairs_ref.expected(fq, k, tables, 1, 255, fmt="fastq"))
+    with lib().QueryIndexer(k, device=0, fmt="fastq", min_qual_byte=T) as q:
         q.set_tables(at_k.ptrs, 1, 255)
         low = query_ref.expected(fasta, k, tables, 1, 255)
         assert n_masked > 1000 and 0 < int(low["n_valid"].sum()) < int(want["n_valid"].sum())     # some windows go, not all
-        _same_plain(_plain(q, fq), low)
-        got = t_pairs._checked(q, fq, query_pairs_ref.expected(fasta, k, tables, 1, 255))
+        same(stream(q, fq), low)
+        got = checked_pairs(q, fq, query_pairs_ref.expected(fasta, k, tables, 1, 255))
         assert got["shared"].any(axis=0).all()
 
 
@@ -231,9 +212,9 @@ def test_long_record_at_the_last_lds_row_of_the_hits(at_k, s, ragged, W):
         if W is None:
             want = query_ref.expected(text, at_k.k, at_k.sparse, *window)
             assert want["hits"][index].all()
-            _same_plain(_plain(q, text), want)
+            same(stream(q, text), want)
         else:
-            t_bins._same(t_bins._binned(q, text, W), query_bins_ref.expected(text, at_k.k, at_k.sparse, *window, W))
+            same_bins(binned(q, text, W), query_bins_ref.expected(text, at_k.k, at_k.sparse, *window, W))
     _rows(at_k, s, ragged, W, run)
 
 
@@ -243,7 +224,7 @@ def test_long_record_at_the_last_lds_row_of_the_hits(at_k, s, ragged, W):
 @pytest.mark.parametrize("s", [QSPEC_ROWS - 1, QSPEC_ROWS, QSPEC_ROWS + 1])
 def test_long_record_at_the_last_lds_row_of_the_spectrum(at_k, s, ragged, W):
     def run(q, text, index, window, W):
-        t_spec._checked(q, text, window, query_spectrum_ref.expected(text, at_k.k, at_k.sparse, W), W=W)
+        checked_spectrum(q, text, window, query_spectrum_ref.expected(text, at_k.k, at_k.sparse, W), W=W)
     _rows(at_k, s, ragged, W, run)
 
 
@@ -255,7 +236,7 @@ def test_long_record_at_the_last_lds_row_of_the_pairs(at_k, s, ragged, W):
     def run(q, text, index, window, W):
         want = query_pairs_ref.expected(text, at_k.k, at_k.sparse, *window, W=W)
         assert want["shared"][-5:].any()                     # the long records share windows (their last rows, binned or not)
-        t_pairs._checked(q, text, want, W=W)
+        checked_pairs(q, text, want, W=W)
     _rows(at_k, s, ragged, W, run)
 
 
@@ -271,14 +252,14 @@ def test_record_break_around_a_slot_boundary(at_k):
         text = query_ref.break_case(k, d)
         want = query_ref.expected(text, k, tables, 1, 255)
         assert len(want["records"]) == 2 and want["hits"].all()
-        whole, cut = _plain(q, text), _plain(q, text, [CHUNK])
-        _same_plain(whole, want)
+        whole, cut = stream(q, text), stream(q, text, cuts=[CHUNK])
+        same(whole, want)
         _same_as_plain(cut, whole)
         if d in (-1, 0, 1, k - 1):
             pairs = query_pairs_ref.expected(text, k, tables, 1, 255)
             assert pairs["shared"].all()
-            t_pairs._checked(q, text, pairs)
-            t_pairs._checked(q, text, pairs, cuts=[CHUNK])
-            binned = query_bins_ref.expected(text, k, tables, 1, 255, 7)
-            t_bins._same(t_bins._binned(q, text, 7), binned)
-            t_bins._same(t_bins._binned(q, text, 7, cuts=[CHUNK]), binned)
+            checked_pairs(q, text, pairs)
+            checked_pairs(q, text, pairs, cuts=[CHUNK])
+            want7 = query_bins_ref.expected(text, k, tables, 1, 255, 7)
+            same_bins(binned(q, text, 7), want7)
+            same_bins(binned(q, text, 7, cuts=[CHUNK]), want7)

@@ -11,7 +11,7 @@ import pytest
 
 import oracle
 import slice_ref
-from test_gpu_indexer import _record_starts, record_overflows
+from inputs import record_overflows, record_starts
 
 pytestmark = pytest.mark.gpu
 
@@ -232,7 +232,7 @@ def test_record_array_retry(gpu):
     text = first + second
     _run(gpu, text, k, cuts=(len(first),), tag="retry")
     assert settled_chunks(text, len(first), len(text)) >= 3
-    starts = _record_starts(_oracle(text, k)["records"])
+    starts = record_starts(_oracle(text, k)["records"])
     assert record_overflows([len(first), len(second)], starts) == [False, True]
 
 

@@ -3,17 +3,15 @@ accumulation over sub-slices, the full-size N = 13 pass against the single-windo
 `merger.py --spectrum` / `python -m pykmer_amd.spectrum` command lines."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from pykmer_amd import merger, spectrum
-from test_spectrum_host import numpy_spectrum
+from gpu_support import ROOT, env_without_ranks, family_kins, run_py
+from merge_ref import device_bincount, numpy_spectrum
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _device_spectrum(gpu, tabs, cuts=None):
@@ -102,15 +100,6 @@ def test_spectrum_refuses_more_than_128_tables(gpu):
         buf.free()
 
 
-def _device_bincount(x, bins):
-    """torch.bincount's result, by a sort on the device (one hot bin of 10^9 adds would serialise bincount's atomics)."""
-    import torch
-    vals, counts = torch.unique(x, sorted=True, return_counts=True)
-    out = np.zeros(bins, dtype=np.uint64)
-    out[vals.cpu().numpy()] = counts.cpu().numpy().astype(np.uint64)
-    return out
-
-
 def test_spectrum_full_size_n13(gpu):
     """4^15-byte tables resident in HBM: histograms against pk_table_stats and torch, the marginal invariants, 16 windows
     against pk_gram_device_accumulate_windows (every entry) and four pairs against torch.bincount on the device."""
@@ -134,7 +123,7 @@ def test_spectrum_full_size_n13(gpu):
     for i in (0, 12):
         assert np.array_equal(hist[i], gpu.table_stats(tabs[i].cpu().numpy()))
     for i in range(N):
-        assert np.array_equal(hist[i], _device_bincount(tabs[i].to(torch.int32), 256)), i
+        assert np.array_equal(hist[i], device_bincount(tabs[i].to(torch.int32), 256)), i
     for p, (i, j) in enumerate(spectrum.pair_list(N)):
         assert int(joint[p].sum()) == n
         assert np.array_equal(joint[p].sum(axis=1), hist[i]) and np.array_equal(joint[p].sum(axis=0), hist[j])
@@ -148,7 +137,7 @@ def test_spectrum_full_size_n13(gpu):
         assert np.array_equal(got, want[w]), wins[w]
     for i, j in ((0, 1), (3, 11), (5, 12), (11, 12)):
         p = i * N - i * (i + 1) // 2 + (j - i - 1)
-        b = _device_bincount(tabs[i].to(torch.int32) * 256 + tabs[j].to(torch.int32), 65536)
+        b = device_bincount(tabs[i].to(torch.int32) * 256 + tabs[j].to(torch.int32), 65536)
         assert np.array_equal(joint[p], b.reshape(256, 256)), (i, j)
     print(f"spectrum N=13 k=15 kernel {secs * 1e3:.3f} ms")
 
@@ -170,12 +159,6 @@ def test_spectrum_counters_do_not_wrap(gpu):
     torch.cuda.empty_cache()
 
 
-def _run(*argv, cwd, env=None):
-    r = subprocess.run([sys.executable] + list(argv), cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
-
-
 def _same_kms(a, b):
     x, y = spectrum.load(a), spectrum.load(b)
     return np.array_equal(x["hist"], y["hist"]) and np.array_equal(x["joint"], y["joint"])
@@ -185,14 +168,11 @@ def test_spectrum_command_lines(gpu, tmp_path, manifest, monkeypatch):
     """merger.py --spectrum on the G7 family against the goldens; the same .kms from .kin.bgz inputs in forced sub-slices,
     from two ranks (gloo) and from ResidentTable inputs; the spectrum CLI re-derives the windows with the .kin files gone."""
     import gzip
-    from test_gpu_cli import _family_kins
-    kins = _family_kins(tmp_path, manifest)
+    kins = family_kins(tmp_path, manifest)
     want = {tag: np.array(manifest["merger"][f"G7_k7_n13_{tag}"]["matrix"], dtype=np.uint64) for tag in ("min2", "max3", "default")}
-    env = dict(os.environ)
-    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        env.pop(v, None)
+    env = env_without_ranks()
     proj = str(tmp_path / "sp")
-    r = _run(os.path.join(ROOT, "merger.py"), proj, *kins, "--spectrum", "--sweep", "2-255,1-3", cwd=str(tmp_path), env=env)
+    r = run_py("merger.py", proj, *kins, "--spectrum", "--sweep", "2-255,1-3", cwd=str(tmp_path), env=env)
     assert r.stdout.count("saving") == 6
     assert np.array_equal(np.load(proj + ".002-255.kma")["matrix"], want["min2"])
     assert np.array_equal(np.load(proj + ".001-003.kma")["matrix"], want["max3"])
@@ -209,7 +189,7 @@ def test_spectrum_command_lines(gpu, tmp_path, manifest, monkeypatch):
     assert _same_kms(proj + ".kms", str(tmp_path / "sub.kms"))
 
     # two ranks on the one GPU (gloo: RCCL refuses two ranks on one device)
-    r = _run(os.path.join(ROOT, "merger.py"), str(tmp_path / "two"), *kins, "--spectrum", "--gpus", "2", cwd=str(tmp_path),
+    r = run_py("merger.py", str(tmp_path / "two"), *kins, "--spectrum", "--gpus", "2", cwd=str(tmp_path),
              env=dict(env, PK_DIST_BACKEND="gloo"))
     assert _same_kms(proj + ".kms", str(tmp_path / "two.kms"))
     assert np.array_equal(np.load(str(tmp_path / "two.001-255.kma"))["matrix"], want["default"])
@@ -234,7 +214,7 @@ def test_spectrum_command_lines(gpu, tmp_path, manifest, monkeypatch):
     for k in kins + bgz:
         os.remove(k)
     (tmp_path / "d").mkdir()
-    _run("-m", "pykmer_amd.spectrum", proj + ".kms", "sp", "--sweep", "2-255,1-3", cwd=str(tmp_path / "d"),
+    run_py("-m", "pykmer_amd.spectrum", proj + ".kms", "sp", "--sweep", "2-255,1-3", cwd=str(tmp_path / "d"),
          env=dict(env, PYTHONPATH=ROOT))
     for name, tag in (("sp.002-255.kma", "min2"), ("sp.001-003.kma", "max3")):
         assert np.array_equal(np.load(str(tmp_path / "d" / name))["matrix"], want[tag])

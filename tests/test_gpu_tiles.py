@@ -18,9 +18,8 @@ import oracle
 import query_bins_ref
 import query_ref
 import slice_ref
-from test_gpu_deep import N_SLICES, _seam_slice
-from test_gpu_query import _Device, _query, _same
-from test_gpu_query_bins import _binned, _same as _same_bins
+from gpu_support import Device, binned, lib, query, same, same_bins
+from slice_ref import N_SLICES, seam_slice
 
 pytestmark = pytest.mark.gpu
 
@@ -34,14 +33,9 @@ def _chunks(n_bytes: int) -> int:
     return -(-n_bytes // CHUNK)
 
 
-def _lib():
-    from pykmer_amd import _lib as lib
-    return lib
-
-
 def _check_indexer(ix, data: bytes, k: int, tag):
     """finish() of a whole-table indexer that was fed `data` against oracle.count_fasta: totals, every record field, the
-    table and the value histogram (test_gpu_indexer._check_against_oracle for feeds of our own cutting)."""
+    table and the value histogram (gpu_support.check_against_oracle for feeds of our own cutting)."""
     fin = ix.finish()
     want = oracle.count_fasta(data, k)
     assert fin["num_kmers"] == want["num_kmers"], tag
@@ -106,7 +100,7 @@ def test_deep_tile_seam(gpu, k, site):
     assert B == TILE and _chunks(len(text)) > SCAN_T
     exp = slice_ref.Expect(text, k, n)
     assert slice_ref.crossing_windows(text, k, B) == k - 1
-    s = _seam_slice(exp, B)
+    s = seam_slice(exp, B)
     i = slice_ref.first_window_at(text, k, B)
     assert exp.slice_of(exp.kmers[i]) == s and exp.distinct_per_slice()[s] > 0
     with gpu.Indexer(k, slice_index=s, n_slices=n) as ix:
@@ -138,20 +132,20 @@ def test_query_more_than_1024_slots(gpu):
     than 1024 slots each (the second with windows and records before it); per record, and binned (W = 1 would take more
     than 1 GB of rows)."""
     k, text, cut, tables = _query_text_checked()
-    with _Device(tables) as dev:
+    with Device(tables) as dev:
         for mn, mx in ((1, 255), (2, 254)):
             want = query_ref.expected(text, k, tables, mn, mx)
             assert int(want["records"]["name_off"][0]) == 1 and int(want["records"]["name_off"][1]) > TILE  # a record across slot 1024
             assert len(want["records"]) > inputs.TINY_RECORDS and (want["n_valid"] == 0).any() and want["hits"].all(axis=1).any()
-            _same(_query(text, k, dev.ptrs, mn, mx), want)
-            _same(_query(text, k, dev.ptrs, mn, mx, cuts=[cut]), want)
-        with _lib().QueryIndexer(k, device=0) as q:
+            same(query(text, k, dev.ptrs, mn, mx), want)
+            same(query(text, k, dev.ptrs, mn, mx, cuts=[cut]), want)
+        with lib().QueryIndexer(k, device=0) as q:
             q.set_tables(dev.ptrs, 1, 255)
             for W in (64, 4099):
                 want = query_bins_ref.expected(text, k, tables, 1, 255, W)
                 assert int(want["bin_first"][-1]) > len(text) // (2 * W)
-                _same_bins(_binned(q, text, W), want)
-                _same_bins(_binned(q, text, W, cuts=[cut]), want)
+                same_bins(binned(q, text, W), want)
+                same_bins(binned(q, text, W, cuts=[cut]), want)
 
 
 # ------------------------------------------------------------------ 5. FASTQ -----------------------------------------
@@ -169,7 +163,7 @@ def test_fastq_scan_runs(gpu, n_chunks, crlf):
     assert fastq_ref.fastq_to_fasta(fq) == fa
     want = oracle.count_fasta(fa, k)
     assert len(want["records"]) == len(names_at)
-    with _lib().Indexer(k, device=0, fmt="fastq") as ix:
+    with lib().Indexer(k, device=0, fmt="fastq") as ix:
         ix.feed(fq)
         fin = ix.finish()
         assert ix.timings()["feeds"] == 1

@@ -11,6 +11,8 @@ import pytest
 
 import inputs
 import oracle
+from host_support import family_indexes, free_port, write_kin
+from merge_ref import oracle_partial
 from pykmer_amd import _lib, merger
 from pykmer_amd.header import Header, HeaderVars, Timer, gen_checksum, stats_from_hist256
 from pykmer_amd.tools import Header as ToolsHeader
@@ -147,26 +149,10 @@ def test_stats_from_hist256_is_np_histogram():
     assert z["vals_min"] == 2 and z["vals_max"] == 9 and z["hist_min"] == 0
 
 
-def _write_index(tmp_path, name, data, k):
-    """Writes <name>.<kk>.kin + .json the way pykmer_amd.indexer does, with the oracle standing in for the GPU."""
-    fa = tmp_path / name
-    fa.write_bytes(data)
-    got = oracle.count_fasta(data, k)
-    h = Header(str(fa), sample_name="s", input_file=str(fa), kmer_len=k)
-    h._init_clean(overwrite=True)
-    h.timer.update(got["total_bp"])
-    h.num_kmers = got["num_kmers"]
-    h.chromosomes = oracle.chromosomes(data, got["records"])
-    got["table"].tofile(h.index_tmp_file)
-    h.write_metadata_index_tmp_file(hist256=np.bincount(got["table"], minlength=256))
-    os.rename(h.index_tmp_file, h.index_file_root)
-    return h, got
-
-
 def test_kin_json_schema_and_values_match_reference(tmp_path, manifest):
     """Every key of the reference's .kin.json, deterministic fields equal to what the reference wrote (G3)."""
     case = manifest["indexer"]["G3_edge_k7"]
-    h, got = _write_index(tmp_path, case["input_file"], inputs.make_input(case["input"]), 7)
+    h = write_kin(tmp_path, case["input_file"], inputs.make_input(case["input"]), 7).header
     with open(h.metadata_file) as fh:
         text = fh.read()
     meta = json.loads(text)
@@ -213,38 +199,14 @@ def test_timer():
 
 
 # ------------------------------------------------------------------ merger host logic -----------
-def _oracle_partial(headers, lo, hi, windows, device, threads):
-    tabs = [h.read_table_slice(lo, hi) for h in headers]      # a rank reads its slice of every file, nothing else
-    N = len(tabs)
-    parts = []
-    for min_count, max_count in windows:
-        m = oracle.gram(tabs, min_count, max_count)
-        pair = np.zeros((N, N), np.uint64)
-        for i in range(N):
-            pair[i, i] = np.count_nonzero((tabs[i] >= min_count) & (tabs[i] <= max_count))
-            for j in range(i + 1, N):
-                pair[i, j] = m[i, j, 2]
-        parts.append(pair)
-    return parts
-
-
-def _family_indexes(tmp_path, manifest, n=13):
-    case = manifest["merger"]["G7_k7_n13_default"]
-    paths = []
-    for i, spec in enumerate(case["inputs"][:n]):
-        h, _ = _write_index(tmp_path, f"s{i:02d}.fa", inputs.make_input(spec), case["k"])
-        paths.append(h.index_file_root)
-    return paths
-
-
 def test_merge_writes_kma_like_reference(tmp_path, manifest):
     import gzip
-    paths = _family_indexes(tmp_path, manifest)
+    paths = family_indexes(tmp_path, manifest)
     with open(paths[4], "rb") as fh, gzip.open(paths[4] + ".bgz", "wb") as out:      # one input as .kin.bgz (tools.py:300-302)
         out.write(fh.read())
     case = manifest["merger"]["G7_k7_n13_min2max5"]
     proj = str(tmp_path / "proj")
-    data, matrix = merger.merge(proj, sorted(paths), min_count=2, max_count=5, partial_fn=_oracle_partial, devices=(0, 1, 2))
+    data, matrix = merger.merge(proj, sorted(paths), min_count=2, max_count=5, partial_fn=oracle_partial, devices=(0, 1, 2))
     want = np.array(case["matrix"], dtype=np.uint64)
     assert np.array_equal(matrix, want)
     kma = np.load(proj + ".002-005.kma")                                             # merger.py:96,207
@@ -258,12 +220,12 @@ def test_merge_writes_kma_like_reference(tmp_path, manifest):
     assert meta["min_count"] == 2 and meta["max_count"] == 5 and isinstance(meta["data"][0]["index_file"], str)
     assert not os.path.exists(proj + ".002-005.kma.tmp")
     with pytest.raises(AssertionError):                                              # refuses to overwrite (merger.py:98-99)
-        merger.merge(proj, sorted(paths), min_count=2, max_count=5, partial_fn=_oracle_partial)
+        merger.merge(proj, sorted(paths), min_count=2, max_count=5, partial_fn=oracle_partial)
 
 
 def test_merge_sweep_writes_one_kma_per_window(tmp_path, manifest):
     """--min/--max sweeps in one run (tables staged once), each window equal to its own golden."""
-    paths = sorted(_family_indexes(tmp_path, manifest))
+    paths = sorted(family_indexes(tmp_path, manifest))
     proj = str(tmp_path / "sweep")
     wins = merger.parse_sweep("1-255, 2-255,1-3,2-5")
     assert wins == [(1, 255), (2, 255), (1, 3), (2, 5)]
@@ -271,7 +233,7 @@ def test_merge_sweep_writes_one_kma_per_window(tmp_path, manifest):
 
     def counting_partial(*a):
         calls.append(a[3])
-        return _oracle_partial(*a)
+        return oracle_partial(*a)
     data, first = merger.merge(proj, paths, partial_fn=counting_partial, windows=wins)
     assert len(calls) == 1 and list(calls[0]) == wins                       # one staging pass for all windows
     for (mn, mx), tag in zip(wins, ("default", "min2", "max3", "min2max5")):
@@ -282,20 +244,20 @@ def test_merge_sweep_writes_one_kma_per_window(tmp_path, manifest):
         assert meta["min_count"] == mn and meta["max_count"] == mx
     assert np.array_equal(first, np.array(manifest["merger"]["G7_k7_n13_default"]["matrix"], dtype=np.uint64))
     with pytest.raises(AssertionError):
-        merger.merge(str(tmp_path / "bad"), paths, partial_fn=_oracle_partial, windows=[(0, 5)])
+        merger.merge(str(tmp_path / "bad"), paths, partial_fn=oracle_partial, windows=[(0, 5)])
 
 
 def test_merge_validation(tmp_path, manifest):
-    paths = _family_indexes(tmp_path, manifest, n=2)
+    paths = family_indexes(tmp_path, manifest, n=2)
     for kw in ({"min_count": 0}, {"max_count": 256}, {"buffer_size": 0}, {"block_size": 0}):   # merger.py:90-93
         with pytest.raises(AssertionError):
-            merger.merge(str(tmp_path / "p"), paths, partial_fn=_oracle_partial, **kw)
-    h9, _ = _write_index(tmp_path, "other.fa", inputs.edge_fasta(), 9)
+            merger.merge(str(tmp_path / "p"), paths, partial_fn=oracle_partial, **kw)
+    h9 = write_kin(tmp_path, "other.fa", inputs.edge_fasta(), 9).header
     with pytest.raises(AssertionError, match="kmer_length differs"):                 # merger.py:119-122
-        merger.merge(str(tmp_path / "p"), paths + [h9.index_file_root], partial_fn=_oracle_partial)
+        merger.merge(str(tmp_path / "p"), paths + [h9.index_file_root], partial_fn=oracle_partial)
     os.remove(paths[1] + ".json")
     with pytest.raises(AssertionError):                                              # merger.py:112-115
-        merger.merge(str(tmp_path / "p"), paths, partial_fn=_oracle_partial)
+        merger.merge(str(tmp_path / "p"), paths, partial_fn=oracle_partial)
     with pytest.raises(SystemExit):
         merger.main(["proj", paths[0]])                                              # argparse: Kmer_N needs one more (merger.py:53-54)
     args = merger.build_parser().parse_args(["p", "a.kin", "b.kin", "--min-count", "3", "--threads", "2"])
@@ -305,7 +267,7 @@ def test_merge_validation(tmp_path, manifest):
 def test_merge_refuses_129_tables_before_reading_any(tmp_path, monkeypatch):
     """The kernels take at most 128 tables: the pair, spectrum and kWIP paths of merge() refuse 129 before a table byte is
     read or a device buffer allocated, with the default (GPU) partials; the tally entry points refuse 0 and 129 tables."""
-    paths = [_write_index(tmp_path, f"t{i:03d}.fa", b">s\nACGTTGCAAC\n", 3)[0].index_file_root for i in range(129)]
+    paths = [write_kin(tmp_path, f"t{i:03d}.fa", b">s\nACGTTGCAAC\n", 3).path for i in range(129)]
     touched = []
     monkeypatch.setattr(Header, "read_table_slice", lambda self, *a, **kw: touched.append("read"))
     monkeypatch.setattr(merger._lib, "DeviceBuffer", lambda *a, **kw: touched.append("alloc"))
@@ -331,8 +293,8 @@ def _cli_rank(rank, world, port, workdir, argv):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                       PK_DIST_BACKEND="gloo")
     from pykmer_amd import merger as m
-    import test_host_layer as here
-    m.gpu_partial = here._oracle_partial                  # the default partial_fn is looked up when pair_matrix runs
+    from merge_ref import oracle_partial
+    m.gpu_partial = oracle_partial                       # the default partial_fn is looked up when pair_matrix runs
     import contextlib
     import io
     out = io.StringIO()
@@ -345,13 +307,9 @@ def _cli_rank(rank, world, port, workdir, argv):
 def test_cli_joins_the_process_group_of_its_launcher(tmp_path, manifest):
     """merger.main under WORLD_SIZE / RANK (what torchrun or `--gpus N` set): every rank validates and scans its address
     slice, one all-reduce (gloo here, RCCL on GPUs) sums the partials, rank 0 alone prints and writes both windows."""
-    import socket
     import torch.multiprocessing as mp
-    paths = sorted(_family_indexes(tmp_path, manifest))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    paths = sorted(family_indexes(tmp_path, manifest))
+    port = free_port()
     proj = str(tmp_path / "cli")
     argv = [proj] + list(reversed(paths)) + ["--sweep", "2-255,1-3", "--threads", "2"]
     mp.spawn(_cli_rank, args=(2, port, str(tmp_path), argv), nprocs=2, join=True)

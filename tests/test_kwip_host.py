@@ -5,53 +5,16 @@ and the tree.  The slice accumulators come from numpy here (no GPU in this suite
 pk_occgram_device_accumulate."""
 import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from gpu_support import run_py
+from host_support import family_indexes, gloo_merge
+from merge_ref import direct_kernel, numpy_occgram, numpy_occgram_partial, numpy_spectrum_partial
 from pykmer_amd import _lib, kwip, merger, spectrum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def numpy_occgram(tabs) -> np.ndarray:
-    """The flat accumulator of pk_occgram_device_accumulate: np.bincount for occ_hist, masked integer products per class
-    (float64 products of u8 counts are exact while a sum stays below 2^53: n * 65025 < 2^53 for any table here)."""
-    N = len(tabs)
-    acc = np.zeros(_lib.occgram_words(N), dtype=np.uint64)
-    occ_hist, lin, gram = kwip.split_accumulator(acc, N)
-    X = np.stack([np.asarray(t, dtype=np.uint8) for t in tabs])
-    occ = (X > 0).sum(axis=0)
-    occ_hist[:] = np.bincount(occ, minlength=N + 1)
-    iu = np.triu_indices(N)
-    for o in range(1, N + 1):
-        sel = X[:, occ == o].astype(np.float64)
-        if not sel.shape[1]:
-            continue
-        lin[o - 1] = sel.sum(axis=1).astype(np.uint64)
-        gram[o - 1] = (sel @ sel.T)[iu].astype(np.uint64)
-    return acc
-
-
-def numpy_occgram_partial(headers, lo, hi, device, threads):
-    return numpy_occgram([h.read_table_slice(lo, hi) for h in headers])
-
-
-def direct_kernel(tabs, unweighted=False):
-    """K straight from the definition, address by address in float64: sum_x w(o(x)) c_i(x) c_j(x) / (S_i S_j)."""
-    N = len(tabs)
-    X = np.stack(tabs).astype(np.float64)
-    occ = (X > 0).sum(axis=0)
-    p = occ / N
-    with np.errstate(divide="ignore", invalid="ignore"):
-        w = np.nan_to_num(-p * np.log2(p) - (1 - p) * np.log2(1 - p))
-    if unweighted:
-        w = np.ones_like(w)
-    s = X.sum(axis=1)
-    return (X * w) @ X.T / np.outer(s, s)
 
 
 def _tables(rng, N, n):
@@ -124,8 +87,7 @@ def test_library_refuses_bad_calls():
 
 
 def _family(tmp_path, manifest, n=13):
-    from test_host_layer import _family_indexes
-    return sorted(_family_indexes(tmp_path, manifest, n=n))
+    return sorted(family_indexes(tmp_path, manifest, n=n))
 
 
 def test_merge_writes_kmo_kern_dist(tmp_path, manifest, monkeypatch):
@@ -165,9 +127,7 @@ def test_merge_writes_kmo_kern_dist(tmp_path, manifest, monkeypatch):
     for p in paths:
         os.remove(p)
     env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-m", "pykmer_amd.kwip", "kw.kmo", "--kernel", "again.kern", "--distance", "again.dist"],
-                       cwd=str(tmp_path), capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr
+    run_py("-m", "pykmer_amd.kwip", "kw.kmo", "--kernel", "again.kern", "--distance", "again.dist", cwd=str(tmp_path), env=env)
     assert (tmp_path / "again.kern").read_bytes() == (tmp_path / "kw.kern").read_bytes()
     assert (tmp_path / "again.dist").read_bytes() == (tmp_path / "kw.dist").read_bytes()
     kwip.main(["kw.kmo", "--kernel", "flat.kern", "--unweighted"])
@@ -181,7 +141,6 @@ def test_merge_writes_kmo_kern_dist(tmp_path, manifest, monkeypatch):
 def test_unweighted_sums_match_spectrum(tmp_path, manifest):
     """sum_o lin[o][i] is table i's sum, and the unweighted cross products sum_o G[o][i][j] equal sum a b J_ij[a][b] of the
     joint spectra the merger writes for the same tables."""
-    from test_spectrum_host import numpy_spectrum_partial
     paths = _family(tmp_path, manifest, n=6)
     merger.merge(str(tmp_path / "s"), paths, spectrum=True, partial_fn=numpy_spectrum_partial)
     merger.merge(str(tmp_path / "k"), paths, kwip=True, partial_fn=numpy_occgram_partial)
@@ -237,9 +196,7 @@ def test_calculate_distance_builds_the_kwip_tree(tmp_path, manifest):
     paths = _family(tmp_path, manifest, n=5)
     proj = str(tmp_path / "tree")
     merger.merge(proj, paths, kwip=True, partial_fn=numpy_occgram_partial)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "calculate_distance.py"), proj + ".kmo"], cwd=str(tmp_path),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+    run_py("calculate_distance.py", proj + ".kmo", cwd=str(tmp_path))
     base = proj + ".kmo.dist.kwip"
     d = np.load(base + ".mat.redundant.np")
     assert np.array_equal(d, kwip.matrices(kwip.load(proj + ".kmo"))[1])
@@ -252,40 +209,10 @@ def test_calculate_distance_builds_the_kwip_tree(tmp_path, manifest):
     assert np.allclose(np.loadtxt(base + ".mat.condensed.txt"), d[np.triu_indices(5, 1)])
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, workdir, paths):
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import torch.distributed as dist
-    from pykmer_amd import merger as m
-    from test_kwip_host import numpy_occgram_partial as part
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-    try:
-        seen = []
-
-        def partial(headers, lo, hi, *a):
-            out = part(headers, lo, hi, *a)
-            seen.append((lo, hi, sum(h.bytes_delivered for h in headers)))
-            return out
-        m.merge(os.path.join(workdir, "dist"), paths, group=True, kwip=True, partial_fn=partial)
-        np.save(os.path.join(workdir, f"slice_rank{rank}.npy"), np.array(seen))
-    finally:
-        dist.destroy_process_group()
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_kwip_matches_single_process(tmp_path, manifest, world):
-    import torch.multiprocessing as mp
     paths = _family(tmp_path, manifest)
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), paths), nprocs=world, join=True)
+    gloo_merge(world, tmp_path, paths, numpy_occgram_partial, kwip=True)
     merger.merge(str(tmp_path / "one"), paths, kwip=True, partial_fn=numpy_occgram_partial)
     one, dist_ = kwip.load(tmp_path / "one.kmo"), kwip.load(tmp_path / "dist.kmo")
     for key in ("occ_hist", "lin", "gram"):

@@ -15,8 +15,8 @@ import mask_ref
 import oracle
 import query_coords_inputs as qci
 import query_ref
+from host_support import stage_host, write_kin
 from pykmer_amd import _lib, mask, query
-from pykmer_amd.header import Header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = mi.CHUNK
@@ -132,25 +132,6 @@ def test_hollow_and_long_inputs():
 FASTA = mi.TOOL_FASTA
 
 
-def _write_kin(tmp_path, name, data, k):
-    fa = tmp_path / name
-    fa.write_bytes(data)
-    got = oracle.count_fasta(data, k)
-    h = Header(str(fa), sample_name=name, input_file=str(fa), kmer_len=k)
-    h._init_clean(overwrite=True)
-    h.timer.update(got["total_bp"])
-    h.num_kmers = got["num_kmers"]
-    h.chromosomes = oracle.chromosomes(data, got["records"])
-    got["table"].tofile(h.index_tmp_file)
-    h.write_metadata_index_tmp_file(hist256=np.bincount(got["table"], minlength=256))
-    os.rename(h.index_tmp_file, h.index_file_root)
-    return h.index_file_root
-
-
-def _stage(group, device):
-    return query.Staged([g.read_table_slice(0, g.data_size) for g in group])
-
-
 def _text_of(path):
     import gzip
     return (gzip.open if str(path).endswith(".gz") else open)(path, "rb").read()
@@ -178,12 +159,12 @@ def _apply(query_file, cover, n_bases, out_file, hard=False, invert=False, devic
     return {"masked": masked, "n_masked": int(masked.sum()), "n_records": want["n_records"], "bytes": len(text), "mask_s": 0.125}
 
 
-FAKES = dict(run=_run, stage=_stage, apply=_apply, hbm_budget=1 << 40)
+FAKES = dict(run=_run, stage=stage_host, apply=_apply, hbm_budget=1 << 40)
 
 
 @pytest.fixture()
 def project(tmp_path):
-    kins = [_write_kin(tmp_path, "donor.fa", b">d\n" + mi.DONOR + b"\n", 5), _write_kin(tmp_path, "host.fa", b">h\n" + mi.HOST + b"\n", 5)]
+    kins = [write_kin(tmp_path, "donor.fa", b">d\n" + mi.DONOR + b"\n", 5).path, write_kin(tmp_path, "host.fa", b">h\n" + mi.HOST + b"\n", 5).path]
     q = tmp_path / "contigs.fa"
     q.write_bytes(FASTA)
     return tmp_path, kins, str(q)
@@ -211,14 +192,14 @@ def test_mask_writes_the_three_files(project):
         assert (meta["mode"], meta["invert"], meta["n_records"], meta["n_bases"], meta["n_masked"], meta["bytes"], meta["output"]) == \
             ("hard" if hard else "soft", invert, want["n_records"], want["n_bases"], n_masked, len(FASTA), proj + ".masked.fa")
         assert meta["lookup_s"] == 0.25 and meta["mask_s"] == 0.125 and meta["records"][0] == "donor piece" and len(meta["data"]) == 2
-    two = mask.cover_bits(q, [query.load_header(kin) for kin in kins], 1, 254, run=_run, stage=_stage, hbm_budget=4 ** 5 + 100)
+    two = mask.cover_bits(q, [query.load_header(kin) for kin in kins], 1, 254, run=_run, stage=stage_host, hbm_budget=4 ** 5 + 100)
     assert two["n_groups"] == 2 and two["lookup_s"] == 0.5 and np.array_equal(two["cover"], want["bits"])        # OR-ed over the groups
 
 
 def test_last_line_of_the_tool(project, capsys, monkeypatch):
     tmp_path, kins, q = project
     monkeypatch.setattr(mask, "run_cover", _run)
-    monkeypatch.setattr(mask, "stage_tables", lambda group, dev, threads: _stage(group, dev))
+    monkeypatch.setattr(mask, "stage_tables", lambda group, dev, threads: stage_host(group, dev))
     monkeypatch.setattr(mask, "apply_mask", _apply)
     monkeypatch.setenv("PK_MERGE_HBM_BUDGET", str(1 << 40))
     proj = str(tmp_path / "cli")
@@ -246,7 +227,7 @@ def test_refusals_come_before_any_file(project, capsys):
         mask.mask(bad, str(tmp_path / "missing.fa"), kins, **FAKES)
     with pytest.raises(ValueError, match="kin"):
         mask.mask(bad, q, [q], **FAKES)
-    k7 = _write_kin(tmp_path, "seven.fa", b">d\n" + mi.DONOR + b"\n", 7)
+    k7 = write_kin(tmp_path, "seven.fa", b">d\n" + mi.DONOR + b"\n", 7).path
     with pytest.raises(ValueError, match="kmer_len 7 differs"):
         mask.mask(bad, q, kins + [k7], **FAKES)
     for existing in ("bad.masked.fa", "bad.kmm", "bad.kmm.json"):

@@ -10,6 +10,7 @@ import inputs
 import query_bins_ref
 import query_ref
 from oracle import pyoracle
+from host_support import query_hooks
 from pykmer_amd import query
 
 
@@ -79,32 +80,11 @@ def test_record_sums_from_rows():
         query.record_sums(np.zeros((3, 1), dtype=np.uint64), [0, 2])
 
 
-def _hooks(text, dense, calls):
-    def stage(group, device):
-        return query.Staged([g.table for g in group])
-
-    def run(query_file, kmer_len, ptrs, mn, mx, device, first, **kw):
-        calls.append(dict(kw))
-        if kw:
-            want = query_bins_ref.expected(text, kmer_len, ptrs, mn, mx, kw["bin_windows"])
-            keys = ("seq_len", "n_valid", "hits", "depth", "bin_hits", "bin_depth", "bin_first")
-        else:
-            want = query_ref.expected(text, kmer_len, ptrs, mn, mx)
-            keys = ("seq_len", "n_valid", "hits", "depth")
-        out = {key: want[key] for key in keys}
-        if first:
-            out["names"] = query_ref.names(text, want["records"])
-        return out
-
-    tables = [types.SimpleNamespace(kmer_len=5, index_file=f"t{i}.kin", data_size=4 ** 5, table=t) for i, t in enumerate(dense)]
-    return tables, stage, run
-
-
 def test_table_groups_concatenate_bin_columns():
     k, W, text = 5, 3, inputs.edge_fasta()
     dense = query_ref.random_tables(k, 5, seed=61)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
     want = query_bins_ref.expected(text, k, dense, 2, 254, W)
     for budget, n_groups in ((1 << 40, 1), (2 * 4 ** k + 100, 3), (1, 5)):
         calls.clear()
@@ -124,7 +104,7 @@ def test_groups_that_disagree_on_bin_first_are_refused():
     k, text = 5, inputs.edge_fasta()
     dense = query_ref.random_tables(k, 2, seed=62)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
 
     def drifting(*args, **kw):
         out = run(*args, **kw)

@@ -1,7 +1,6 @@
 """CPU: base coordinates of binned query hits -- the yardstick (query_coords_ref) against the oracle and against what follows
 from the definition, the refusals of `--coords` without `--bin`, and the `.kmb` writers.  No call here touches a GPU."""
 import json
-import types
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import query_coords_inputs as qci
 import query_coords_ref
 import query_ref
 from fastq_ref import fastq_to_fasta
+from host_support import query_hooks
 from pykmer_amd import query
 
 
@@ -90,29 +90,11 @@ def test_cli_refuses_coords_without_bins(tmp_path, capsys):
     assert query.build_parser().parse_args(["p", "q.fa", "a.kin", "--bin", "50"]).coords is False
 
 
-def _hooks(text, dense, calls):
-    """The stand-ins of tests/test_query_bins_host.py for staging and streaming, with coordinates."""
-    def stage(group, device):
-        return query.Staged([g.table for g in group])
-
-    def run(query_file, kmer_len, ptrs, mn, mx, device, first, **kw):
-        calls.append(dict(kw))
-        want = query_coords_ref.expected(text, kmer_len, ptrs, mn, mx, kw["bin_windows"])
-        keys = ("seq_len", "n_valid", "hits", "depth", "bin_hits", "bin_depth", "bin_first") + (("bin_start", "bin_end") if kw.get("coords") and first else ())
-        out = {key: want[key] for key in keys}
-        if first:
-            out["names"] = query_ref.names(text, want["records"])
-        return out
-
-    tables = [types.SimpleNamespace(kmer_len=5, index_file=f"t{i}.kin", data_size=4 ** 5, table=t) for i, t in enumerate(dense)]
-    return tables, stage, run
-
-
 def test_query_records_passes_coords_through_and_refuses_them_without_bins():
     k, W, text = 5, 3, qci.many_records(127)
     dense = query_ref.random_tables(k, 3, seed=64)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
     with pytest.raises(ValueError, match="coords"):
         query.query_records("q.fa", tables, 1, 255, stage=stage, run=run, coords=True)
     with pytest.raises(ValueError, match="coords"):

@@ -11,6 +11,7 @@ import oracle
 import query_bins_ref
 import query_pairs_ref
 import query_ref
+from host_support import stub_header
 from oracle import pyoracle
 from pykmer_amd import query
 
@@ -84,19 +85,15 @@ def test_writers(tmp_path):
         query.query(proj, "q.fa", [tmp_path / "t0.kin"])
 
 
-def _stub(k, name):
-    return types.SimpleNamespace(kmer_len=k, index_file=name, data_size=4 ** k)
-
-
 def test_argument_errors(tmp_path):
-    a, b = _stub(9, "a.kin"), _stub(9, "b.kin")
+    a, b = stub_header(9, "a.kin"), stub_header(9, "b.kin")
     assert query.validate([a, b], 1, 255) == 9
     with pytest.raises(ValueError, match="c.kin.*differs"):
-        query.validate([a, _stub(11, "c.kin")], 1, 255)
+        query.validate([a, stub_header(11, "c.kin")], 1, 255)
     with pytest.raises(ValueError, match="even.kin"):
-        query.validate([_stub(8, "even.kin")], 1, 255)
+        query.validate([stub_header(8, "even.kin")], 1, 255)
     with pytest.raises(ValueError, match="deep.kin.*19"):
-        query.validate([a, _stub(19, "deep.kin")], 1, 255)
+        query.validate([a, stub_header(19, "deep.kin")], 1, 255)
     for mn, mx in ((5, 4), (0, 3), (1, 256)):
         with pytest.raises(ValueError, match="count window"):
             query.validate([a], mn, mx)

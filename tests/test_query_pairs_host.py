@@ -4,8 +4,6 @@ import json
 import os
 import re
 import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -15,6 +13,8 @@ import oracle
 import query_bins_ref
 import query_pairs_ref as ref
 import query_ref
+from gpu_support import env_with_root, run_py
+from host_support import query_hooks
 from pykmer_amd import _lib, distance, qpairs, query, spectrum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,45 +85,11 @@ def test_jaccard_edge_cases():
 
 
 # ------------------------------------------------------------------ the group loop -----------------
-def _hooks(text, dense, calls, k=5):
-    def stage(group, device=0, threads=None):
-        return query.Staged([g.table for g in group])
-
-    def run(query_file, kmer_len, ptrs, mn, mx, device, first, **kw):
-        calls.append(dict(kw))
-        W = kw.get("bin_windows")
-        if W is not None:
-            want = query_bins_ref.expected(text, kmer_len, ptrs, mn, mx, W)
-            keys = ("seq_len", "n_valid", "hits", "depth", "bin_hits", "bin_depth", "bin_first")
-        else:
-            want = query_ref.expected(text, kmer_len, ptrs, mn, mx)
-            keys = ("seq_len", "n_valid", "hits", "depth")
-        out = {key: want[key] for key in keys}
-        if kw.get("coords"):
-            B = int(want["bin_first"][-1])
-            out.update(bin_start=np.arange(B, dtype=np.uint64), bin_end=np.arange(B, dtype=np.uint64) + 7)
-        if kw.get("pairs"):
-            rows = ref.expected(text, kmer_len, ptrs, mn, mx, W=W)
-            if W is not None:
-                out["bin_shared"] = rows["shared"]
-                out["shared"] = ref.record_sums(rows["shared"], rows["bin_first"])
-            else:
-                out["shared"] = rows["shared"]
-        if first:
-            out["names"] = query_ref.names(text, want["records"])
-        return out
-
-    tables = [types.SimpleNamespace(kmer_len=k, index_file=f"t{i}.kin", project_name=f"t{'abcdefghijklmnopqrs'[i]}", data_size=4 ** k, table=t,
-                                    to_dict=lambda lean=True, i=i: {"kmer_len": k, "project_name": f"t{'abcdefghijklmnopqrs'[i]}"})
-              for i, t in enumerate(dense)]
-    return tables, stage, run
-
-
 def test_query_records_adds_shared_and_the_keyword_goes_only_when_set():
     k, text = 5, inputs.edge_fasta()
     dense = query_ref.random_tables(k, 17, seed=71)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
     for N in (1, 4, 16):
         calls.clear()
         want = ref.expected(text, k, dense[:N], 2, 254)
@@ -257,9 +223,7 @@ def test_qpairs_runs_as_a_module_and_distance_reads_its_kma(tmp_path):
     res, _, _ = _result()
     query.write_kmp(str(tmp_path / "P"), res, "q.fa", _data(tmp_path), ["ta", "tb", "tc"])
     row = int(np.argmax(res["shared"].sum(axis=1)))
-    r = subprocess.run([sys.executable, "-m", "pykmer_amd.qpairs", "P.kmp", "Q", "--row", str(row)], cwd=str(tmp_path), capture_output=True, text=True,
-                       env=dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
+    run_py("-m", "pykmer_amd.qpairs", "P.kmp", "Q", "--row", str(row), cwd=str(tmp_path), env=env_with_root())
     m = distance.load(tmp_path / "Q.001-255.kma")
     assert m.shape[0] == 3 and np.array_equal(np.load(tmp_path / "Q.001-255.kma")["matrix"], qpairs.row_matrix(res["hits"][row], res["shared"][row]))
 
@@ -269,7 +233,7 @@ def _cli(monkeypatch, tmp_path, n_tables, budget=1 << 40):
     k, text = 5, inputs.edge_fasta()
     dense = query_ref.random_tables(k, n_tables, seed=75)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
     by_name = {}
     for i, t in enumerate(tables):
         kin = tmp_path / f"t{i}.kin"

@@ -4,7 +4,6 @@ import json
 import os
 import re
 import subprocess
-import types
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import inputs
 import query_bins_ref
 import query_ref
 import query_spectrum_ref as ref
+from host_support import query_hooks
 from pykmer_amd import _lib, qspectrum, query
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -82,40 +82,11 @@ def test_window_and_median_from_spectrum_against_brute_force():
 
 
 # ------------------------------------------------------------------ the group loop -----------------
-def _hooks(text, dense, calls):
-    def stage(group, device):
-        return query.Staged([g.table for g in group])
-
-    def run(query_file, kmer_len, ptrs, mn, mx, device, first, **kw):
-        calls.append(dict(kw))
-        W = kw.get("bin_windows")
-        if W is not None:
-            want = query_bins_ref.expected(text, kmer_len, ptrs, mn, mx, W)
-            keys = ("seq_len", "n_valid", "hits", "depth", "bin_hits", "bin_depth", "bin_first")
-        else:
-            want = query_ref.expected(text, kmer_len, ptrs, mn, mx)
-            keys = ("seq_len", "n_valid", "hits", "depth")
-        out = {key: want[key] for key in keys}
-        if kw.get("spectrum"):
-            rows = ref.expected(text, kmer_len, ptrs, W)
-            if W is not None:
-                out["bin_spectrum"] = rows["spectrum"]
-                out["spectrum"] = ref.record_sums(rows["spectrum"], rows["bin_first"])
-            else:
-                out["spectrum"] = rows["spectrum"]
-        if first:
-            out["names"] = query_ref.names(text, want["records"])
-        return out
-
-    tables = [types.SimpleNamespace(kmer_len=5, index_file=f"t{i}.kin", data_size=4 ** 5, table=t) for i, t in enumerate(dense)]
-    return tables, stage, run
-
-
 def test_table_groups_concatenate_spectra_and_the_keyword_goes_only_when_set():
     k, text = 5, inputs.edge_fasta()
     dense = query_ref.random_tables(k, 5, seed=61)
     calls = []
-    tables, stage, run = _hooks(text, dense, calls)
+    tables, stage, run = query_hooks(text, dense, calls)
     per_record = ref.expected(text, k, dense)
     for budget, n_groups in ((1 << 40, 1), (2 * 4 ** k + 100, 3), (1, 5)):
         calls.clear()

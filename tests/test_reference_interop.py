@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from test_host_layer import _family_indexes
+from host_support import family_indexes
 
 
 def _parse_index_name(path):
@@ -19,7 +19,7 @@ def _parse_index_name(path):
 
 def test_reference_reads_our_kin_and_merges_it(tmp_path, manifest):
     written = manifest["indexer"]["G3_edge_k7"]                         # a k = 7 .kin.json the reference wrote
-    paths = sorted(_family_indexes(tmp_path, manifest, n=3))
+    paths = sorted(family_indexes(tmp_path, manifest, n=3))
     tables = []
     for i, path in enumerate(paths):
         assert _parse_index_name(path) == (f"s{i:02d}.fa", 7)

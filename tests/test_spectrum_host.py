@@ -4,34 +4,18 @@ the sharded (gloo) path.  The slice spectra come from numpy here (no GPU in this
 pk_spectrum_device_accumulate."""
 import json
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
+from host_support import family_indexes, gloo_merge
+from merge_ref import numpy_spectrum, numpy_spectrum_partial, oracle_partial
 from pykmer_amd import _lib, merger, spectrum
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WINDOWS = [(1, 255), (2, 255), (1, 3), (2, 5), (1, 1), (255, 255), (7, 3), (1, 50)]
 GOLDEN_WINDOWS = [((1, 255), "default"), ((2, 255), "min2"), ((1, 3), "max3"), ((2, 5), "min2max5")]
-
-
-def numpy_spectrum(tabs) -> np.ndarray:
-    """The flat accumulator of pk_spectrum_device_accumulate, by np.bincount."""
-    N = len(tabs)
-    acc = np.zeros(_lib.spectrum_words(N), dtype=np.uint64)
-    hist, core = spectrum.split_accumulator(acc, N)
-    for i, t in enumerate(tabs):
-        hist[i] = np.bincount(t, minlength=256)
-    for p, (i, j) in enumerate(spectrum.pair_list(N)):
-        core[p] = np.bincount(tabs[i].astype(np.int64) * 256 + tabs[j], minlength=65536).reshape(256, 256)[1:, 1:]
-    return acc
-
-
-def numpy_spectrum_partial(headers, lo, hi, device, threads):
-    return numpy_spectrum([h.read_table_slice(lo, hi) for h in headers])
 
 
 def _tables(rng, N, n):
@@ -93,8 +77,7 @@ def _want(manifest, tag):
 def test_spectrum_merge_and_cli_reproduce_reference_goldens(tmp_path, manifest, monkeypatch):
     """G7 k=7 N=13: ONE spectrum pass writes the .kms and all four windows' .kma; with every .kin deleted the spectrum CLI
     derives them again, and its .kma.json is byte-equal to what a direct merge under the same project name writes."""
-    from test_host_layer import _family_indexes, _oracle_partial
-    paths = sorted(_family_indexes(tmp_path, manifest))
+    paths = sorted(family_indexes(tmp_path, manifest))
     wins = [w for w, _ in GOLDEN_WINDOWS]
     calls = []
 
@@ -111,7 +94,7 @@ def test_spectrum_merge_and_cli_reproduce_reference_goldens(tmp_path, manifest, 
     for (mn, mx), tag in GOLDEN_WINDOWS:
         assert np.array_equal(np.load(f"proj.{mn:03d}-{mx:03d}.kma")["matrix"], _want(manifest, tag)), tag
     monkeypatch.chdir(tmp_path / "c")
-    merger.merge("Q", paths, windows=wins, partial_fn=_oracle_partial)           # the direct merge, for its .kma.json
+    merger.merge("Q", paths, windows=wins, partial_fn=oracle_partial)           # the direct merge, for its .kma.json
     for p in paths:
         os.remove(p)
     assert not any(os.path.exists(p) for p in paths)
@@ -136,8 +119,7 @@ def test_spectrum_merge_and_cli_reproduce_reference_goldens(tmp_path, manifest, 
 
 
 def test_kms_round_trip_and_invariants(tmp_path, manifest):
-    from test_host_layer import _family_indexes
-    paths = sorted(_family_indexes(tmp_path, manifest, n=5))
+    paths = sorted(family_indexes(tmp_path, manifest, n=5))
     proj = str(tmp_path / "rt")
     merger.merge(proj, paths, spectrum=True, partial_fn=numpy_spectrum_partial)
     with np.load(proj + ".kms") as z:
@@ -171,41 +153,10 @@ def test_merger_cli_takes_spectrum_flag():
     assert not merger.build_parser().parse_args(["p", "a.kin", "b.kin"]).spectrum
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, workdir, paths):
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import torch.distributed as dist
-    from pykmer_amd import merger as m
-    from test_spectrum_host import numpy_spectrum_partial as part
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-    try:
-        seen = []
-
-        def partial(headers, lo, hi, *a):
-            out = part(headers, lo, hi, *a)
-            seen.append((lo, hi, sum(h.bytes_delivered for h in headers)))
-            return out
-        m.merge(os.path.join(workdir, "dist"), paths, windows=[(2, 255), (1, 3)], group=True, spectrum=True, partial_fn=partial)
-        np.save(os.path.join(workdir, f"slice_rank{rank}.npy"), np.array(seen))
-    finally:
-        dist.destroy_process_group()
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_spectrum_matches_single_process(tmp_path, manifest, world):
-    import torch.multiprocessing as mp
-    from test_host_layer import _family_indexes
-    paths = sorted(_family_indexes(tmp_path, manifest))
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), paths), nprocs=world, join=True)
+    paths = sorted(family_indexes(tmp_path, manifest))
+    gloo_merge(world, tmp_path, paths, numpy_spectrum_partial, windows=[(2, 255), (1, 3)], spectrum=True)
     merger.merge(str(tmp_path / "one"), paths, windows=[(2, 255)], spectrum=True, partial_fn=numpy_spectrum_partial)
     one, dist_ = spectrum.load(tmp_path / "one.kms"), spectrum.load(tmp_path / "dist.kms")
     assert np.array_equal(one["hist"], dist_["hist"]) and np.array_equal(one["joint"], dist_["joint"])
