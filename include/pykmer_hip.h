@@ -236,6 +236,23 @@ void pk_indexer_destroy(pk_indexer *ix);
  * base counts whether or not its byte changed); *n_bases_seen_out = the valid bases the stream held.  PK_ERR_STATE if that
  * is not the n_bases the mask was made for (the text changed between the phases); PK_ERR_RECS_CAP if R > recs_cap. */
 enum { PK_MASK_HARD = 1, PK_MASK_INVERT = 2 };
+/* Intervals of a mask stream.  POSITIONS are those of pk_query_set_coords: within a record every sequence character gets the
+ * next position, 0-based, valid base or not; a blank inside a sequence line gets one once a non-blank sequence character
+ * follows it on its line; line terminators, leading and trailing blanks, header text and text before the first header get
+ * none.  An INTERVAL is a maximal run of consecutive positions of one record that all hold selected bases: (r, start, end),
+ * half-open, 0 <= start < end <= seq_len[r].  An invalid character, an interior blank, a header, the end of the stream and
+ * a valid base that is not selected end a run; line terminators and leading and trailing blanks do not.  The intervals are
+ * in stream order (by record, then by start), those of a record never touch, and their lengths add up to masked[r].
+ * pk_query_set_intervals: after pk_query_set_mask and before the first feed (PK_ERR_STATE otherwise); 0 is the default,
+ * which a reset restores.  The rows grow with the intervals found; a growth that fails is PK_ERR_HIP naming the size.
+ * pk_query_interval_count: after pk_indexer_finish; *n_out = the intervals of the stream, *seconds_out (may be null) = the
+ * HIP-event seconds of the interval kernels, which are not part of pk_indexer_timings [7].
+ * pk_query_intervals: after pk_indexer_finish; rec_out, start_out and end_out receive one u64 per interval.
+ * PK_ERR_RECS_CAP if there are more than cap; PK_ERR_STATE when the intervals are off, or if the stream did not hold the
+ * valid bases the mask was made for (as pk_query_mask_counts). */
+int pk_query_set_intervals(pk_indexer *q, int on);
+int pk_query_interval_count(pk_indexer *q, uint64_t *n_out, double *seconds_out);
+int pk_query_intervals(pk_indexer *q, uint64_t *rec_out, uint64_t *start_out, uint64_t *end_out, uint64_t cap);
 int pk_query_set_cover(pk_indexer *q, int on);
 int pk_query_cover(pk_indexer *q, uint8_t *bits_out, uint64_t n_bits_cap, uint64_t *n_bases_out);
 int pk_query_set_mask(pk_indexer *q, const uint8_t *bits, uint64_t n_bases, int mode);

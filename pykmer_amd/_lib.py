@@ -65,6 +65,9 @@ _SIGNATURES = {
     "pk_query_set_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]),
     "pk_query_mask_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
     "pk_query_mask_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p]),
+    "pk_query_set_intervals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "pk_query_interval_count": (ctypes.c_int, [ctypes.c_void_p, _u64p, ctypes.POINTER(ctypes.c_double)]),
+    "pk_query_intervals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_table_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
     "pk_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -440,6 +443,28 @@ class QueryIndexer(Indexer):
         n = ctypes.c_uint64(0)
         _check(load().pk_query_mask_counts(self._h, masked.ctypes.data, n_records, ctypes.byref(n)))
         return view, int(n.value)
+
+    def set_intervals(self, on: bool = True):
+        """pk_query_set_intervals, after set_mask and before the first feed: also keep the maximal runs of selected bases as
+        intervals of positions (off by default; a reset clears the setting)."""
+        _check(load().pk_query_set_intervals(self._h, 1 if on else 0))
+
+    def _interval_count(self):
+        n, seconds = ctypes.c_uint64(0), ctypes.c_double(0)
+        _check(load().pk_query_interval_count(self._h, ctypes.byref(n), ctypes.byref(seconds)))
+        return int(n.value), float(seconds.value)
+
+    def intervals(self):
+        """pk_query_intervals after finish(): (iv_record, iv_start, iv_end), each (M,) uint64 in stream order; interval j is the
+        positions iv_start[j] .. iv_end[j] - 1 of record iv_record[j]."""
+        M = self._interval_count()[0]
+        (rec, r), (start, s), (end, e) = self._room(M), self._room(M), self._room(M)
+        _check(load().pk_query_intervals(self._h, rec.ctypes.data, start.ctypes.data, end.ctypes.data, M))
+        return r, s, e
+
+    def interval_seconds(self) -> float:
+        """The HIP-event seconds of the interval kernels (not part of mask_s), after finish()."""
+        return self._interval_count()[1]
 
 
 class Selector:

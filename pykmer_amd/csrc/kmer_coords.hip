@@ -25,84 +25,13 @@
 //   k_coords_write  one workgroup per chunk: positions, runs and records of its pieces again, the windows that end in each
 //                   piece prefix-summed behind slot_first[c] (their ordinals), and the two rules above.  Clean pieces by
 //                   masks (piece_scan and the pack's restart bits), the others by the rolled byte loop
-// Like the kernels of kmer_query.hip all three return at once, writing nothing, when flags[0] is raised.
+// Like the kernels of kmer_query.hip all three return at once, writing nothing, when flags[0] is raised.  The pair, its
+// scans and the byte-wise walk (coords_walk) are in kmer_pieces.h, which kmer_intervals.hip shares.
+#include "kmer_pieces.h"
 #include "kmer_window.h"
-#include "pk_kernels.h"
 #include "wg_scan.h"
 
 namespace pk {
-
-constexpr unsigned long long CP_HDR = 1ull << 63;        // a pair in one word: bit 63 = a record opens, the rest = positions
-
-__device__ __forceinline__ unsigned long long cp_compose(unsigned long long a, unsigned long long b) {   // a first, then b
-    return (b & CP_HDR) ? b : a + b;
-}
-
-// inclusive scan of pairs over a wave
-__device__ __forceinline__ unsigned long long cp_wave_incl(unsigned long long v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d) v = cp_compose(o, v);
-    }
-    return v;
-}
-
-// Exclusive scan of pairs over the workgroup's NW waves (sh: NW words); total = all of them composed.  The pair before
-// lane 0 is the identity (0).
-template <int NW>
-__device__ __forceinline__ unsigned long long cp_block_excl(unsigned long long v, unsigned long long *sh, unsigned long long &total) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const unsigned long long inc = cp_wave_incl(v, lane);
-    __syncthreads();                                         // sh may still be read from an earlier call
-    if (lane == 63u) sh[w] = inc;
-    __syncthreads();
-    unsigned long long pre = 0ull, tot = 0ull;
-    for (uint32_t i = 0; i < (uint32_t)NW; i++) { if (i < w) pre = cp_compose(pre, sh[i]); tot = cp_compose(tot, sh[i]); }
-    total = tot;
-    const unsigned long long up = __shfl_up(inc, 1, 64);
-    return lane == 0u ? pre : cp_compose(pre, up);
-}
-
-// One piece walked byte by byte from its exact start state, as SeqWalker::step walks it (byte i <-> bit i).
-struct CoordPiece {
-    unsigned long long wend;      // a valid window of a live record ends at this byte (the kmer_acc rule)
-    unsigned long long posm;      // the byte holds a position: a sequence character, or a blank that turned out interior
-    unsigned long long hdrm;      // the byte opens a record
-    unsigned long long carried;   // pending blanks carried into the piece that turned out interior in it
-    __device__ __forceinline__ unsigned long long pair() const {
-        if (!hdrm) return carried + (unsigned long long)__popcll(posm);
-        const uint32_t last = 63u - (uint32_t)__builtin_clzll(hdrm);
-        return CP_HDR | (unsigned long long)__popcll(posm & ~((2ull << last) - 1ull));
-    }
-};
-
-__device__ __forceinline__ CoordPiece coords_walk(const uint8_t *mine, uint32_t nb, uint32_t ls_in, const L2 &st, uint32_t k) {
-    CoordPiece cp; cp.wend = 0; cp.posm = 0; cp.hdrm = 0; cp.carried = 0;
-    uint32_t ls = ls_in, run = l2_len(st);
-    bool live = st.rec != 0u;                                // text before the first header is dropped
-    unsigned long long pend_in = st.p_tail, pendm = 0;       // pending blanks: carried in / of this piece
-    for_each_byte_of(mine, nb, [&](uint32_t i, uint32_t c, bool act) {
-        const bool term = is_term(c), ws = is_ws(c), gt = c == '>';
-        const bool at_start = ls == LS_START, in_seq = ls == LS_SEQ;
-        const bool hdr_start = act && at_start && !ws && gt;
-        const bool seqchar = act && !ws && (in_seq || (at_start && !gt));
-        const bool t = act && term;
-        const unsigned long long bit = 1ull << i;
-        if (hdr_start) { live = true; run = 0u; cp.hdrm |= bit; }
-        if (seqchar && (pend_in | pendm)) {                  // blanks were interior: each holds a position and maps to None
-            cp.posm |= pendm; cp.carried += pend_in; run = 0u; pend_in = 0ull; pendm = 0ull;
-        }
-        if (t) { pend_in = 0ull; pendm = 0ull; }
-        else if (act && ws && in_seq) pendm |= bit;
-        ls = t ? (uint32_t)LS_START : hdr_start ? (uint32_t)LS_HEADER : seqchar ? (uint32_t)LS_SEQ : ls;
-        cp.posm |= seqchar ? bit : 0ull;
-        const bool valid = seqchar && base_code(c) < 4u;
-        run = valid ? (run < k ? run + 1u : run) : (seqchar ? 0u : run);
-        cp.wend |= (valid && run == k && live) ? bit : 0ull;
-    });
-    return cp;
-}
 
 __global__ __launch_bounds__(WG) void k_coords_sum(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
                                                    const PiecePack *__restrict__ packs, const L2 *__restrict__ chunk_l2_state,
@@ -268,13 +197,19 @@ __global__ __launch_bounds__(WG) void k_coords_write(const uint8_t *__restrict__
 }
 
 // ------------------------------------------------------------------ host side -------------------
+void launch_coords_positions(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state,
+                             const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, unsigned long long *chunk_pos,
+                             const unsigned long long *pos_in, unsigned long long *pos_out, hipStream_t s) {
+    hipLaunchKernelGGL(k_coords_sum, dim3(pl.n_chunks), dim3(WG), 0, s, fasta, n, lane_state, packs, st2, chunk_odd, pl.k, chunk_pos,
+                       (const uint32_t *)b.flags);
+    hipLaunchKernelGGL(k_coords_scan, dim3(1), dim3(CSNT), 0, s, chunk_pos, pl.n_chunks, pos_in, pos_out, (const uint32_t *)b.flags);
+}
+
 void launch_query_coords(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const uint8_t *fasta, uint64_t n, const LaneState *lane_state,
                          const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, const DevRec *recs, const unsigned long long *P,
                          const unsigned long long *Bf, uint64_t bin_windows, unsigned long long *chunk_pos, const unsigned long long *pos_in,
                          unsigned long long *pos_out, unsigned long long *bin_start, unsigned long long *bin_end, uint64_t rows_cap, hipStream_t s) {
-    hipLaunchKernelGGL(k_coords_sum, dim3(pl.n_chunks), dim3(WG), 0, s, fasta, n, lane_state, packs, st2, chunk_odd, pl.k, chunk_pos,
-                       (const uint32_t *)b.flags);
-    hipLaunchKernelGGL(k_coords_scan, dim3(1), dim3(CSNT), 0, s, chunk_pos, pl.n_chunks, pos_in, pos_out, (const uint32_t *)b.flags);
+    launch_coords_positions(pl, b, fasta, n, lane_state, packs, st2, chunk_odd, chunk_pos, pos_in, pos_out, s);
     hipLaunchKernelGGL(k_coords_write, dim3(pl.n_chunks), dim3(WG), 0, s, fasta, n, lane_state, packs, st2, pl.k, (const unsigned long long *)chunk_pos,
                        (const unsigned long long *)qb.slot_first, P, Bf, (unsigned long long)bin_windows, recs, bin_start, bin_end,
                        (unsigned long long)rows_cap, (const uint32_t *)b.flags);

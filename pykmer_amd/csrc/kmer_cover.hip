@@ -22,6 +22,7 @@
 //                   deposited onto the set bits of the mask, patched into the lane's bytes in LDS; the chunk leaves through
 //                   a buffer of its own, so that a repeated feed parses the text it parsed before.
 // Like the kernels of kmer_query.hip all return at once, writing nothing, when flags[0] is raised; OR is idempotent.
+#include "kmer_pieces.h"
 #include "kmer_qlane.h"
 #include "wg_scan.h"
 
@@ -119,8 +120,6 @@ __device__ __forceinline__ MaskPiece mask_walk(const uint8_t *mine, uint32_t nb,
 // 4 flag bits -> 0xff in every flagged byte of a dword, byte 0 lowest
 __device__ __forceinline__ uint32_t byte_mask4(uint32_t four) { return (((four & 15u) * 0x00204081u) & 0x01010101u) * 0xffu; }
 
-constexpr uint32_t MASK_HARD = 1u, MASK_INVERT = 2u;
-
 __global__ __launch_bounds__(WG) void k_mask_apply(const uint8_t *__restrict__ fasta, uint64_t n_bytes, const LaneState *__restrict__ lane_state,
                                                    const L2 *__restrict__ chunk_l2_state, uint32_t k,
                                                    const unsigned long long *__restrict__ base_first, const uint32_t *__restrict__ bits,
@@ -155,27 +154,8 @@ __global__ __launch_bounds__(WG) void k_mask_apply(const uint8_t *__restrict__ f
     const uint32_t nv = (uint32_t)__popcll(mp.valid);
     uint32_t total;
     const uint32_t off = wg_excl_sum<WG / 64, false>(nv, sh32, total);   // sh32: first use
-    // the lane's cover bits: nv bits from bit g0 of the bitmap; words past its end read as zero
-    unsigned long long sel = 0ull;
-    if (nv) {
-        const unsigned long long g0 = base_first[c] + off, w0 = g0 >> 5;
-        const uint32_t sh = (uint32_t)(g0 & 31ull);
-        const auto word = [&](unsigned long long w) -> unsigned long long { return w < n_words ? (unsigned long long)bits[w] : 0ull; };
-        unsigned long long got = (word(w0) | (word(w0 + 1ull) << 32)) >> sh;
-        if (sh) got |= word(w0 + 2ull) << (64u - sh);
-        if (mode & MASK_INVERT) got = ~got;
-        // onto the set bits of the valid mask, lowest first, a run of set bits at a time (plain sequence text: one or two)
-        unsigned long long rest = mp.valid;
-        while (rest) {
-            const uint32_t at = (uint32_t)__builtin_ctzll(rest);
-            const unsigned long long from = ~(rest >> at);   // the run begins at bit 0 and ends below the first set bit
-            const uint32_t len = from ? (uint32_t)__builtin_ctzll(from) : 64u;
-            const unsigned long long run = len >= 64u ? ~0ull : ((1ull << len) - 1ull);
-            sel |= (got & run) << at;
-            got = len >= 64u ? 0ull : got >> len;
-            rest &= ~(run << at);
-        }
-    }
+    // the lane's cover bits: nv bits from bit g0 of the bitmap, on the bytes of its valid bases
+    const unsigned long long sel = nv ? cover_select(mp.valid, base_first[c] + off, bits, n_words, (mode & MASK_INVERT) != 0u) : 0ull;
     // the lane's own bytes, in LDS; only dwords that change are written
     if (sel) {
         uint32_t *dw = reinterpret_cast<uint32_t *>(mine);

@@ -158,23 +158,38 @@ struct QueryState {
     DevBuf<uint8_t> mask_out;
     uint64_t mask_n_bases = 0, mask_out_n = 0;
     uint32_t mask_mode = 0;
+    // intervals (pk_query_set_intervals, with apply; kmer_intervals.hip): the maximal runs of selected bases as (record, start,
+    // end) rows in stream order.  iv_starts / iv_ends: the starts and ends of the stream, carried from feed to feed (their
+    // difference is the run still open); chunk_iv: two words per chunk; the rows grow with the intervals found (size_intervals),
+    // by half at least.  Positions come from pos and cpos, as for the coordinates.
+    bool intervals = false;
+    DevBuf<unsigned long long> iv_record, iv_start, iv_end, chunk_iv;
+    Carried iv_starts, iv_ends;
+    uint64_t n_intervals = 0;                               // after finish
     hipEvent_t lookup_begin = nullptr, lookup_end = nullptr;       // the kernels of kmer_query.hip, or k_cover_scan + k_query_cover
     hipEvent_t coords_begin = nullptr, coords_end = nullptr;       // the kernels of kmer_coords.hip
     hipEvent_t mask_begin = nullptr, mask_end = nullptr;           // k_mask_apply
-    double t_coords = 0, t_mask = 0;
+    hipEvent_t iv_count_begin = nullptr, iv_count_end = nullptr;   // the position kernels, k_iv_count and k_iv_scan
+    hipEvent_t iv_write_begin = nullptr, iv_write_end = nullptr;   // k_iv_write
+    double t_coords = 0, t_mask = 0, t_intervals = 0;
 
-    ~QueryState() { for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end, mask_begin, mask_end}) if (e) hipEventDestroy(e); }
+    ~QueryState() {
+        for (hipEvent_t e : {lookup_begin, lookup_end, coords_begin, coords_end, mask_begin, mask_end, iv_count_begin, iv_count_end, iv_write_begin, iv_write_end})
+            if (e) hipEventDestroy(e);
+    }
     uint64_t cover_words() const { return cover_bits.bytes / sizeof(uint32_t); }
     int create();                                                  // the events, and P for the record array's first capacity
     int reset(hipStream_t s);                                      // an empty stream; the tables stay; bins, coordinates, spectra and pairs are off
     // every array of the options that are on, for a record array of `cap` records and a stream of `bytes` bytes (the feed
     // under way included): contents kept, the rest zero; nothing but comparisons where the capacities suffice
     int size_rows(uint64_t cap, uint64_t bytes, hipStream_t s);
+    int size_intervals(uint64_t rows, hipStream_t s);              // the three interval arrays for `rows` rows: contents kept
     size_t n_pairs() const { return tables.size() * (tables.size() - 1) / 2; }
 };
 
 int create_indexer(pk_indexer **out, int k, int device, int slice_index, int n_slices, bool query);   // pk_indexer.hip
 int query_count_bins(pk_indexer *ix);                          // pk_query.hip: the rows of a finished binned stream
+int query_close_intervals(pk_indexer *ix);                     // pk_query.hip: the intervals of a finished stream, the open run closed
 }  // namespace pk
 
 // One counting stream on one device: the .kin image, the scratch of the structure pass (kmer_count.hip), the squeeze

@@ -319,7 +319,8 @@ static int count_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
 
 // The feed of a query indexer that applies a mask (pk_query_set_mask): behind the squeeze (for n_bases[]) the base scan and
 // k_mask_apply, which leaves the feed's patched text in a buffer of its own -- the squeeze of a repeated attempt (flag 2)
-// reads the text it read before.  No tables, no lookups.
+// reads the text it read before.  No tables, no lookups.  With intervals (pk_query_set_intervals) the position kernels of
+// kmer_coords.hip and the count and scan of kmer_intervals.hip follow the apply, and the rows are written behind the feed's wait.
 static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     QueryState &q = *ix->q;
     if (ix->format != PK_FORMAT_FASTA) return fail(PK_ERR_STATE, "a mask is applied to FASTA text only");
@@ -331,23 +332,53 @@ static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb);
     if ((rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
     if ((rc = q.mask_out.reserve(n_bytes + 64))) return rc;
+    if (q.intervals && (rc = q.cpos.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
+    if (q.intervals && (rc = q.chunk_iv.reserve((size_t)pl.n_chunks * 2 * sizeof(unsigned long long)))) return rc;
     q.mask_out_n = 0;
+    const uint64_t mask_words = q.mask_bits.bytes / sizeof(uint32_t);
     auto queue = [&](uint32_t raised) -> int {
         if (raised && raised != 2u) return fail(PK_ERR_HIP, "the mask feed did not settle (internal error, flag %u)", raised);
         // a repeated attempt starts from the same base count (Carried) and finds masked[] as the feed before left it: the
         // attempt that backed out added nothing
         launch_cover_scan(pl, pb, q.nb.start(), q.nb.end(), q.base_first.p, ix->stream);
         HIPCHK(hipEventRecord(q.mask_begin, ix->stream));
-        launch_mask_apply(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, q.mask_bits.bytes / sizeof(uint32_t),
+        launch_mask_apply(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, mask_words,
                           q.mask_mode, q.mask_out.p, q.masked.p, q.masked.bytes / sizeof(unsigned long long), ix->stream);
         HIPCHK(hipEventRecord(q.mask_end, ix->stream));
+        if (q.intervals) {
+            // the positions at the chunk starts, then the starts and ends of every chunk and of the stream behind this feed; a
+            // repeated attempt starts from the same position and counts (Carried) and has written no row
+            HIPCHK(hipEventRecord(q.iv_count_begin, ix->stream));
+            launch_coords_positions(pl, pb, f, n_bytes, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, q.cpos.p, q.pos.start(), q.pos.end(),
+                                    ix->stream);
+            launch_iv_count(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, mask_words, q.mask_mode, q.chunk_iv.p,
+                            q.iv_starts.start(), q.iv_ends.start(), q.iv_starts.end(), q.iv_ends.end(), ix->stream);
+            HIPCHK(hipEventRecord(q.iv_count_end, ix->stream));
+        }
         HIPCHK(hipGetLastError());
         return PK_OK;
     };
     if ((rc = run_feed(ix, f, n_bytes, pl, pb, "the mask feed", "masked", queue))) return rc;
     q.nb.settle();                                           // the base count behind this feed is the next feed's start
     q.mask_out_n = n_bytes;
-    return add_elapsed(&q.t_mask, q.mask_begin, q.mask_end);
+    if ((rc = add_elapsed(&q.t_mask, q.mask_begin, q.mask_end))) return rc;
+    if (!q.intervals) return PK_OK;
+    // the feed has settled and the host has waited for it: the rows the stream needs by now are known (one per start; an end
+    // goes to its start's row), the arrays grow to hold them, and the rows are written on the settled state
+    unsigned long long ns = 0;
+    HIPCHK(hipMemcpy(&ns, q.iv_starts.end(), sizeof ns, hipMemcpyDeviceToHost));
+    if ((rc = q.size_intervals(ns, ix->stream))) return rc;
+    HIPCHK(hipEventRecord(q.iv_write_begin, ix->stream));
+    launch_iv_write(pl, pb, f, n_bytes, ix->lane_state.p, ix->c_l2s.p, q.base_first.p, q.mask_bits.p, mask_words, q.mask_mode, q.cpos.p, q.chunk_iv.p,
+                    q.iv_record.p, q.iv_start.p, q.iv_end.p, q.iv_record.bytes / sizeof(unsigned long long), ix->stream);
+    HIPCHK(hipEventRecord(q.iv_write_end, ix->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ix->stream));                // the caller may reuse the feed's text
+    q.pos.settle();
+    q.iv_starts.settle();
+    q.iv_ends.settle();
+    if ((rc = add_elapsed(&q.t_intervals, q.iv_count_begin, q.iv_count_end))) return rc;
+    return add_elapsed(&q.t_intervals, q.iv_write_begin, q.iv_write_end);
 }
 
 // A query indexer's feed: the lookup kernels (kmer_query.hip), and with coordinates those of kmer_coords.hip, where
@@ -664,6 +695,7 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
         }
         if (ix->q) {
             int rc = query_count_bins(ix);
+            if (!rc) rc = query_close_intervals(ix);
             if (rc) return rc;
         }
         ix->finished = true;

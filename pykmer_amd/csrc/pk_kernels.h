@@ -152,6 +152,11 @@ void launch_query_coords(const PartPlan &pl, const PartBuffers &b, const QueryBu
                          const unsigned long long *Bf, uint64_t bin_windows, unsigned long long *chunk_pos, const unsigned long long *pos_in,
                          unsigned long long *pos_out, unsigned long long *bin_start, unsigned long long *bin_end, uint64_t rows_cap, hipStream_t s);
 
+// the first two kernels of launch_query_coords alone: chunk_pos[c] = the position at chunk c's first byte, pos_out as above
+void launch_coords_positions(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state,
+                             const PiecePack *packs, const L2 *st2, const uint32_t *chunk_odd, unsigned long long *chunk_pos,
+                             const unsigned long long *pos_in, unsigned long long *pos_out, hipStream_t s);
+
 // kmer_cover.hip -- the bases of the stream that the tables cover, one bit per valid base, and the text with them marked
 // (DESIGN.md 4.14).  All three run behind the squeeze of the same feed (n_bases[]).
 // nb_in: the valid bases of the stream before the feed; nb_out receives the number behind it; base_first: n_chunks words.
@@ -167,6 +172,21 @@ void launch_query_cover(const PartPlan &pl, const PartBuffers &b, const L2 *st2,
 void launch_mask_apply(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state, const L2 *st2,
                        const unsigned long long *base_first, const uint32_t *bits, uint64_t n_words, uint32_t mode, uint8_t *out,
                        unsigned long long *masked, uint64_t recs_cap, hipStream_t s);
+
+// kmer_intervals.hip -- the selected bases of a mask feed as intervals of positions (DESIGN.md 4.14 "Intervals"), behind
+// launch_cover_scan (base_first) and launch_coords_positions (chunk_pos) of the same feed; fasta .. mode as launch_mask_apply
+// takes them.  chunk_iv: 2 * n_chunks words of scratch.  ns_in / ne_in: the starts and ends of the stream before the feed
+// (their difference is the open run); ns_out / ne_out receive those behind it.
+void launch_iv_count(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state, const L2 *st2,
+                     const unsigned long long *base_first, const uint32_t *bits, uint64_t n_words, uint32_t mode, unsigned long long *chunk_iv,
+                     const unsigned long long *ns_in, const unsigned long long *ne_in, unsigned long long *ns_out, unsigned long long *ne_out,
+                     hipStream_t s);
+// behind launch_iv_count: iv_record / iv_start (row = starts of the stream before) and iv_end (row = ends before); rows at or
+// past `cap` are not written
+void launch_iv_write(const PartPlan &pl, const PartBuffers &b, const uint8_t *fasta, uint64_t n, const LaneState *lane_state, const L2 *st2,
+                     const unsigned long long *base_first, const uint32_t *bits, uint64_t n_words, uint32_t mode, const unsigned long long *chunk_pos,
+                     const unsigned long long *chunk_iv, unsigned long long *iv_record, unsigned long long *iv_start, unsigned long long *iv_end,
+                     uint64_t cap, hipStream_t s);
 
 // fastq.hip -- the FASTQ front end: FASTQ bytes -> the FASTA text they stand for, checked record by record
 struct FqState {             // the stream after some prefix of it

@@ -1,18 +1,20 @@
 // pk_query.hip -- query mode of the host layer: the state a query indexer holds (QueryState, pk_host.h), the one rule that
 // sizes its arrays (size_rows) and the pk_query_* entry points, which share their opening checks (query_check), their
 // setters' tail (switch_option) and their read-outs (read_rows).  The feeds themselves go through pk_indexer.hip, which
-// queues the kernels of kmer_query.hip, kmer_coords.hip and kmer_cover.hip behind the squeeze.
+// queues the kernels of kmer_query.hip, kmer_coords.hip, kmer_cover.hip and kmer_intervals.hip behind the squeeze.
 #include "pk_host.h"
 
 using namespace pk;
 
 int QueryState::create() {
-    for (hipEvent_t *e : {&lookup_begin, &lookup_end, &coords_begin, &coords_end, &mask_begin, &mask_end}) HIPCHK(hipEventCreate(e));
+    for (hipEvent_t *e : {&lookup_begin, &lookup_end, &coords_begin, &coords_end, &mask_begin, &mask_end, &iv_count_begin, &iv_count_end, &iv_write_begin,
+                          &iv_write_end})
+        HIPCHK(hipEventCreate(e));
     return P.reserve(4096 * sizeof(unsigned long long));
 }
 
 int QueryState::reset(hipStream_t s) {
-    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos.words, &spec, &shared, &nb.words, &masked})
+    for (DevBuf<unsigned long long> *b : {&P, &Bf, &hits, &depth, &bin_start, &bin_end, &pos.words, &spec, &shared, &nb.words, &masked, &iv_starts.words, &iv_ends.words})
         if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, s));
     if (cover_bits.p) HIPCHK(hipMemsetAsync(cover_bits.p, 0, cover_bits.bytes, s));
     windows = p_done = 0;
@@ -22,6 +24,7 @@ int QueryState::reset(hipStream_t s) {
     coords = false; pos.in = 0; t_coords = 0;
     cover = apply = false; nb.in = 0; t_mask = 0;
     mask_n_bases = mask_out_n = 0; mask_mode = 0;
+    intervals = false; iv_starts.in = iv_ends.in = 0; n_intervals = 0; t_intervals = 0;   // rows below the counts are always written: not zeroed
     return PK_OK;
 }
 
@@ -90,6 +93,21 @@ int QueryState::size_rows(uint64_t cap, uint64_t bytes, hipStream_t s) {
     const size_t need = (bytes / 32 + 2) * sizeof(uint32_t);
     if (!cover || need <= cover_bits.bytes) return PK_OK;
     return cover_bits.grow_keep(std::max<size_t>(need, cover_bits.bytes + cover_bits.bytes / 2), s);
+}
+
+// The interval rows grow with the intervals found, by half at least, never with the bytes fed.
+int QueryState::size_intervals(uint64_t rows, hipStream_t s) {
+    const size_t need = (size_t)rows * sizeof(unsigned long long);
+    for (DevBuf<unsigned long long> *buf : {&iv_record, &iv_start, &iv_end}) {
+        if (need <= buf->bytes) continue;
+        const size_t want = std::max<size_t>(need, buf->bytes + buf->bytes / 2);
+        const int rc = buf->grow_keep(want, s);
+        if (!rc) continue;
+        (void)hipGetLastError();
+        const std::string why = g_err;
+        return fail(rc, "the intervals need three arrays of %zu bytes (%llu rows): %s", want, (unsigned long long)rows, why.c_str());
+    }
+    return PK_OK;
 }
 
 // The opening checks of the pk_query_* entry points, in the order that decides which message a caller sees: a query
@@ -274,6 +292,56 @@ extern "C" int pk_query_mask_counts(pk_indexer *ix, uint64_t *masked_out, uint64
         return fail(PK_ERR_STATE, "the stream holds %llu valid bases and the mask was made for %llu: the text changed between the phases",
                     (unsigned long long)*n_bases_seen_out, (unsigned long long)q.mask_n_bases);
     return read_rows(ix, ix->n_recs, recs_cap, "records", sizeof(uint64_t), q.masked, masked_out);
+}
+
+extern "C" int pk_query_set_intervals(pk_indexer *ix, int on) {
+    if (int rc = query_check(ix, applying, "pk_query_set_mask comes before pk_query_set_intervals", "the intervals are set before the first feed (reset the indexer first)")) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    // the position word and the two counts, then rows for a first feed
+    return switch_option(ix, &ix->q->intervals, on, [](pk_indexer *x) {
+        QueryState &q = *x->q;
+        for (Carried *c : {&q.pos, &q.iv_starts, &q.iv_ends})
+            if (int rc = c->ready(x->stream)) return rc;
+        return q.size_intervals(1024, x->stream);
+    });
+}
+
+static bool with_intervals(const QueryState &q) { return q.intervals; }
+
+extern "C" int pk_query_interval_count(pk_indexer *ix, uint64_t *n_out, double *seconds_out) {
+    if (!ix || !n_out) return fail(PK_ERR_ARG, "null argument");
+    if (int rc = query_check(ix, with_intervals, "the indexer keeps no intervals (pk_query_set_intervals)", nullptr)) return rc;
+    *n_out = ix->q->n_intervals;
+    if (seconds_out) *seconds_out = ix->q->t_intervals;
+    return PK_OK;
+}
+
+extern "C" int pk_query_intervals(pk_indexer *ix, uint64_t *rec_out, uint64_t *start_out, uint64_t *end_out, uint64_t cap) {
+    if (int rc = query_check(ix, with_intervals, "the indexer keeps no intervals (pk_query_set_intervals)", nullptr)) return rc;
+    HIPCHK(hipSetDevice(ix->device));
+    const QueryState &q = *ix->q;
+    uint64_t seen = 0;
+    if (int rc = bases_seen(ix, &seen)) return rc;
+    if (seen != q.mask_n_bases)
+        return fail(PK_ERR_STATE, "the stream holds %llu valid bases and the mask was made for %llu: the text changed between the phases",
+                    (unsigned long long)seen, (unsigned long long)q.mask_n_bases);
+    if (int rc = read_rows(ix, q.n_intervals, cap, "intervals", sizeof(uint64_t), q.iv_record, rec_out)) return rc;
+    return read_rows(ix, q.n_intervals, cap, "intervals", sizeof(uint64_t), q.iv_start, start_out, &q.iv_end, end_out);
+}
+
+// the intervals of a finished stream: a run still open belongs to the last record and ends with it
+int pk::query_close_intervals(pk_indexer *ix) {
+    QueryState &q = *ix->q;
+    q.n_intervals = 0;
+    if (!q.intervals) return PK_OK;
+    unsigned long long ns = 0, ne = 0;
+    HIPCHK(hipMemcpy(&ns, q.iv_starts.start(), sizeof ns, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ne, q.iv_ends.start(), sizeof ne, hipMemcpyDeviceToHost));
+    if (ns < ne || ns - ne > 1 || ns * sizeof(unsigned long long) > q.iv_end.bytes || (ns > ne && !ix->n_recs))
+        return fail(PK_ERR_HIP, "%llu interval starts and %llu ends (internal error)", ns, ne);
+    if (ns > ne) HIPCHK(hipMemcpy(q.iv_end.p + ne, &ix->recs.p[ix->n_recs - 1].seq_len, sizeof(unsigned long long), hipMemcpyDeviceToDevice));
+    q.n_intervals = ns;
+    return PK_OK;
 }
 
 // the rows of a finished binned stream: the last record's bins are not in Bf
