@@ -331,6 +331,15 @@ int pk_spectrum_device_accumulate(const void *const *dev_tables, int N, uint64_t
 int pk_occgram_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, void *dev_accum, int device,
                                  double *kernel_seconds_out);
 
+/* Presence patterns of N device-resident slices: with m(x) = sum_t [min_count <= T_t[x] <= max_count] << t (bit t = table t
+ * holds address x in the count window), patterns[p] = #{x : m(x) = p} for p = 0 .. 2^N - 1 is ADDED to dev_accum (device,
+ * 2^N u64, zeroed by the caller; patterns[0] counts the addresses no table holds, so a pass adds n_slice in all).  Every
+ * pair tally, occupancy class, intersection, union and difference of any subset of the tables is a sum over these bins.
+ * 1 <= N <= 16, 1 <= min_count <= max_count <= 255, n_slice <= 2^40 (PK_ERR_ARG otherwise: the 2^N bins are a dense array);
+ * table pointers 16-byte aligned.  N = 15 and 16 stream the slices 2 and 4 times. */
+int pk_patterns_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count,
+                                  void *dev_accum, int device, double *kernel_seconds_out);
+
 /* ---- extract: the k-mers behind a condition over N device-resident slices (no reference counterpart: a `jellyfish dump`
  * / `kmc_tools` style answer).  dev_tables lists n_present "present" tables, then n_absent "absent" ones
  * (n_present >= 1, n_present + n_absent <= 128), each n_slice bytes whose first byte is address first_addr of the 4^k-byte

@@ -83,6 +83,8 @@ _SIGNATURES = {
                                                       ctypes.POINTER(ctypes.c_double)]),
     "pk_occgram_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_double)]),
+    "pk_patterns_device_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pk_extract_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_double)]),
@@ -649,6 +651,22 @@ def occgram_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, device: in
     ptrs = _ptr_array(dev_ptrs)
     secs = ctypes.c_double(0)
     _check(load().pk_occgram_device_accumulate(ptrs, N, n_slice, ctypes.c_void_p(dev_accum), device, ctypes.byref(secs)))
+    return secs.value
+
+
+def patterns_words(N: int) -> int:
+    """u64 words of a presence-pattern accumulator for N tables: one bin per subset of them."""
+    return 1 << N
+
+
+def patterns_device_accumulate(dev_ptrs, n_slice: int, dev_accum: int, min_count: int = 1, max_count: int = 255, device: int = 0) -> float:
+    """pk_patterns_device_accumulate: adds the presence-pattern histogram of N <= 16 device-resident slices under one count
+    window to a patterns_words(N) u64 accumulator in HBM; returns kernel seconds."""
+    N = len(dev_ptrs)
+    ptrs = _ptr_array(dev_ptrs)
+    secs = ctypes.c_double(0)
+    _check(load().pk_patterns_device_accumulate(ptrs, N, int(n_slice), int(min_count), int(max_count),
+                                                ctypes.c_void_p(dev_accum) if dev_accum else None, device, ctypes.byref(secs)))
     return secs.value
 
 

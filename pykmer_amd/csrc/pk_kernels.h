@@ -258,6 +258,12 @@ uint64_t occgram_scratch_bytes(int N, uint64_t n_slice);
 int launch_occgram(const void *const *dev_tables, int N, uint64_t n_slice, unsigned long long *dev_accum, const uint8_t **dev_ptrs,
                    uint8_t *occ_scratch, hipStream_t s);
 
+// gram_patterns.hip -- presence patterns: ADDS to dev_accum (2^N u64) the number of addresses per N-bit word "which tables
+// hold the address with min_count <= count <= max_count" (bit t = table t).  1 <= N <= 16, 1 <= min <= max <= 255.
+// dev_tables is a HOST array of N device pointers.
+int launch_patterns(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count, unsigned long long *dev_accum,
+                    hipStream_t s);
+
 // kmer_extract.hip -- the addresses that satisfy a presence / absence condition over N slices, and their count rows
 // (DESIGN.md 4.11).  tables: device array of P present, then A absent table pointers (n_slice bytes each, 16-byte aligned).
 // masks: extract_mask_words(n_slice) u16; wg: extract_workgroups(n_slice) + 1 u64, whose last word receives the number

@@ -1,5 +1,5 @@
 // pk_merge.hip -- host side of the merger and the extractor: sequences the kernels of gram_scan.hip, gram_spectrum.hip,
-// gram_occ.hip and kmer_extract.hip over device-resident table slices, and pk_table_stats.
+// gram_occ.hip, gram_patterns.hip and kmer_extract.hip over device-resident table slices, and pk_table_stats.
 #include <functional>
 
 #include "pk_host.h"
@@ -194,6 +194,20 @@ extern "C" int pk_occgram_device_accumulate(const void *const *dev_tables, int N
     };
     return timed_pass("occgram", dev_tables, N, device, kernel_seconds_out, grow_scratch, [&](GramCtx &c) {
         return launch_occgram(dev_tables, N, n_slice, (unsigned long long *)dev_accum, c.d_ptrs, c.d_occ, c.stream);
+    });
+}
+
+// Presence patterns (gram_patterns.hip): the 2^N tallies of one count window ADDED to the caller's accumulator, so slices
+// and ranks sum like pk_occgram_device_accumulate's.
+extern "C" int pk_patterns_device_accumulate(const void *const *dev_tables, int N, uint64_t n_slice, int min_count, int max_count,
+                                             void *dev_accum, int device, double *kernel_seconds_out) {
+    if (N < 1 || N > 16) return fail(PK_ERR_ARG, "a pattern pass takes 1 to 16 tables (got %d): its 2^N bins are a dense array", N);
+    if (min_count < 1 || max_count > 255 || min_count > max_count)
+        return fail(PK_ERR_ARG, "the count window must satisfy 1 <= min <= max <= 255 (got %d-%d)", min_count, max_count);
+    if (!dev_accum || ((uintptr_t)dev_accum & 7u)) return fail(PK_ERR_ARG, "null accumulator (or not 8-byte aligned)");
+    if (n_slice > (1ull << 40)) return fail(PK_ERR_ARG, "slice of %llu addresses is out of range", (unsigned long long)n_slice);
+    return timed_pass("patterns", dev_tables, N, device, kernel_seconds_out, nullptr, [&](GramCtx &c) {
+        return launch_patterns(dev_tables, N, n_slice, min_count, max_count, (unsigned long long *)dev_accum, c.stream);
     });
 }
 

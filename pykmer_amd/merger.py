@@ -52,6 +52,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="kWIP's entropy-weighted kernel and distance instead of the pair tally: one pass writes <P>.kmo + "
                              ".kmo.json (the exact per-occupancy tallies), <P>.kern and <P>.dist, and no .kma (any weighting "
                              "again, without the .kin files: python -m pykmer_amd.kwip)")
+    parser.add_argument("--patterns", action="store_true",
+                        help="one pass per window that counts the k-mers of every presence pattern (which of the <= 16 tables hold "
+                             "it): writes <P>.<min>-<max>.kmv + .kmv.json + .kmv.tsv (UpSet input) and the window's .kma, derived "
+                             "from them (any subset's count again, without the .kin files: python -m pykmer_amd.patterns)")
     parser.add_argument("--gpus", type=int, default=0,
                         help="one process per GPU: the k-mer address range is split over N ranks and the N x N partials are "
                              "summed by one RCCL all-reduce (also entered under torchrun, which sets WORLD_SIZE / RANK)")
@@ -137,6 +141,18 @@ def occgram_partial(headers: List[Header], lo: int, hi: int, device: int, thread
                          N + 1 if N > 16 else N, True, acc_ptr=acc_ptr, stats=stats)
 
 
+def patterns_partial(headers: List[Header], lo: int, hi: int, windows, device: int, threads: int, acc_ptr: int = None, stats: dict = None):
+    """One presence-pattern pass per window and staged piece of addresses [lo, hi) (pk_patterns_device_accumulate; staging
+    as _flat_partial).  The tallies are accumulated in HBM: at `acc_ptr` (W x 2^N u64, zeroed by the caller) or in a buffer
+    of this call, which is then returned as one flat u64 host array: window after window, 2^N bins each."""
+    N = len(headers)
+    words = _lib.patterns_words(N)
+
+    def accumulate(ptrs, n, acc, device):
+        return sum(_lib.patterns_device_accumulate(ptrs, n, acc + w * words * 8, mn, mx, device=device) for w, (mn, mx) in enumerate(windows))
+    return _flat_partial(headers, lo, hi, device, threads, len(windows) * words, accumulate, N, True, acc_ptr=acc_ptr, stats=stats)
+
+
 def _pair_flat(headers: List[Header], words: int, own_partial, threads: int, devices, group, partial_fn, stats) -> np.ndarray:
     """The one split-and-reduce of every merge pass: a flat accumulator of `words` u64 of all tables over the whole address
     range.  Single process: the range is split over `devices`, one host thread per device, and the partials are summed on
@@ -216,6 +232,26 @@ def pair_occgram(headers: List[Header], threads: int = DEFAULT_THREADS, devices=
     return _pair_flat(headers, _lib.occgram_words(len(headers)), occgram_partial, threads, devices, group, partial_fn, stats)
 
 
+def pair_patterns(headers: List[Header], windows, threads: int = DEFAULT_THREADS, devices=(0,), group=None, partial_fn=None,
+                  stats: dict = None) -> np.ndarray:
+    """The presence patterns of all tables over the whole address range, one row of 2^N u64 per (min, max) window, split
+    and reduced as _pair_flat does (one all-reduce for all windows).  `partial_fn(headers, lo, hi, windows, device, threads)`
+    computes one slice's flat W x 2^N tallies (default: patterns_partial; the CPU-only tests substitute numpy)."""
+    from . import patterns as pat
+    pat.check_tables(len(headers))
+    N, W = len(headers), len(windows)
+
+    def flat(fn):
+        def partial(headers, lo, hi, device, threads, **kw):
+            part = fn(headers, lo, hi, windows, device, threads, **kw)
+            return None if part is None else np.asarray(part, dtype=np.uint64).reshape(-1)
+        return partial
+    own = flat(patterns_partial)
+    total = _pair_flat(headers, W * _lib.patterns_words(N), own, threads, devices, group,
+                       None if partial_fn in (None, patterns_partial) else flat(partial_fn), stats)
+    return total.reshape(W, 1 << N)
+
+
 def write_kma(project_name: str, mn: int, mx: int, data, matrix: np.ndarray) -> None:
     """`<project>.<min>-<max>.kma` (key `matrix`, merger.py:207) and its `.kma.json` (merger.py:189-201), each through
     `.tmp` + rename."""
@@ -234,7 +270,8 @@ def print_matrix(matrix: np.ndarray) -> None:
 
 def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_COUNT, max_count: int = DEFAULT_MAX_COUNT,
           buffer_size: int = DEFAULT_BUFFER_SIZE, block_size: int = DEFAULT_BLOCK_SIZE, threads: int = DEFAULT_THREADS,
-          devices=(0,), group=None, partial_fn=None, windows=None, spectrum: bool = False, kwip: bool = False):
+          devices=(0,), group=None, partial_fn=None, windows=None, spectrum: bool = False, kwip: bool = False,
+          patterns: bool = False):
     """merger.py:80-210.  `windows` (a list of (min_count, max_count)) turns the call into a sweep: the
     tables are staged once and one `.kma` + `.kma.json` is written per window (the reference re-runs
     the whole merge per threshold, README.md:57-61); the first window's matrix is returned.
@@ -243,7 +280,14 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
     the spectrum (pykmer_amd.spectrum), as any later window can be without the tables.
     `kwip` makes the one pass tally the occupancy-stratified Gram products instead (pair_occgram; `partial_fn` then computes
     a slice's accumulator): `<project>.kmo` + `.kmo.json`, `.kern` and `.dist` are written and no `.kma`; the call returns
-    (data, kernel matrix)."""
+    (data, kernel matrix).
+    `patterns` makes one presence-pattern pass per window instead (pair_patterns; `partial_fn` then computes a slice's
+    W x 2^N tallies): per window `<project>.<min>-<max>.kmv` + `.kmv.json` + `.kmv.tsv` are written, and the window's `.kma`
+    is derived from the patterns (pykmer_amd.patterns).  At most 16 tables (ValueError otherwise, before any file is written)."""
+    if patterns:
+        from . import patterns as pat
+        assert not spectrum and not kwip, "patterns takes no spectrum or kwip"
+        pat.check_tables(len(indexes))
     if kwip:
         assert not spectrum and not windows and (min_count, max_count) == (DEFAULT_MIN_COUNT, DEFAULT_MAX_COUNT), \
             "kwip takes no count window, sweep or spectrum"
@@ -251,6 +295,7 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
     for mn, mx in windows:
         assert mn >= 1
         assert mx <= 255
+        assert not patterns or mn <= mx, f"an empty count window ({mn}-{mx}) has no patterns"
     assert buffer_size > 0
     assert block_size > 0
     assert len(indexes) > 0
@@ -263,6 +308,10 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         from . import spectrum as spec
         for f in spec.spectrum_paths(project_name):
             assert not f.exists(), f"spectrum output file ({f}) already exists. not overwriting."
+    if patterns:
+        for mn, mx in windows:
+            for f in pat.pattern_paths(project_name, mn, mx):
+                assert not f.exists(), f"pattern output file ({f}) already exists. not overwriting."
     if kwip:
         from . import kwip as kw
         for f in kw.kmo_paths(project_name):
@@ -296,6 +345,9 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         total = pair_spectrum(headers, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
         hist, joint = spec.expand_accumulator(total, len(headers), headers[0].data_size)
         pairs = spec.window_pairs(hist, joint, windows)
+    elif patterns:
+        bins = pair_patterns(headers, windows, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
+        pairs = [pat.matrix_from_patterns(b, len(headers)) for b in bins]
     else:
         pairs = pair_matrix(headers, windows, threads=threads, devices=devices, group=group, partial_fn=partial_fn)
     lean_headers(data)
@@ -317,7 +369,7 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         return data, kern
 
     matrices = []
-    for (mn, mx), outfile, pair in zip(windows, outfiles, pairs):
+    for w, ((mn, mx), outfile, pair) in enumerate(zip(windows, outfiles, pairs)):
         # (N,N,3): [k][l] = (total_k, total_l, shared) (merger.py:175-176); the diagonal, which the reference
         # never assigns in its uninitialised array (merger.py:136), is zero here
         matrix = _lib.gram_expand(pair)
@@ -325,6 +377,8 @@ def merge(project_name: str, indexes: List[Path], min_count: int = DEFAULT_MIN_C
         print_matrix(matrix)
         if not is_writer:
             continue
+        if patterns:
+            pat.save(project_name, mn, mx, bins[w], kmer_len, headers[0].data_size, data)
         write_kma(project_name, mn, mx, data, matrix)
     return data, matrices[0]
 
@@ -357,14 +411,17 @@ def spawn_ranks(world: int, argv: List[str], script: str = None) -> int:
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         procs.append(subprocess.Popen(cmd, env=env))
+    killed = []
     while any(p.poll() is None for p in procs):
         if any(p.poll() not in (None, 0) for p in procs):       # a rank died: its peers would wait in the all-reduce for ever
             for p in procs:
                 if p.poll() is None:
                     p.kill()                                     # exactly the children started above
+                    killed.append(p)
             break
         time.sleep(0.05)
-    return max(abs(p.wait()) for p in procs)
+    codes = [p.wait() for p in procs]
+    return max(abs(c) for p, c in zip(procs, codes) if p not in killed)   # the ranks' own statuses, not the -9 of those killed here
 
 
 def _join_group():
@@ -401,13 +458,22 @@ def main(argv: List[str] = None) -> None:
     windows = parse_sweep(args.sweep) if args.sweep else None
     if args.kwip and (args.spectrum or args.sweep or args.min_count != DEFAULT_MIN_COUNT or args.max_count != DEFAULT_MAX_COUNT):
         build_parser().error("--kwip takes no --spectrum, --sweep, --min-count or --max-count")
+    if args.patterns and (args.spectrum or args.kwip):
+        build_parser().error("--patterns takes no --spectrum or --kwip")
+    if args.patterns:
+        from . import patterns as pat
+        try:
+            pat.check_tables(len(indexes))
+        except ValueError as e:
+            print(f"error: {e}")
+            sys.exit(1)
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(spawn_ranks(args.gpus, argv))
         devices = tuple(int(d) for d in os.environ.get("PK_DEVICES", "0").split(",") if d != "")
         merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
               block_size=args.block_size, threads=args.threads, devices=devices or (0,), windows=windows, spectrum=args.spectrum,
-              kwip=args.kwip)
+              kwip=args.kwip, patterns=args.patterns)
         return
     # one rank of a multi-process merge: every rank validates and scans its address slice, rank 0 prints and writes
     import contextlib
@@ -417,7 +483,7 @@ def main(argv: List[str] = None) -> None:
         with contextlib.redirect_stdout(None) if rank else contextlib.nullcontext():
             merge(args.Project_Name, indexes, min_count=args.min_count, max_count=args.max_count, buffer_size=args.buffer_size,
                   block_size=args.block_size, threads=args.threads, devices=(device,), group=True, windows=windows,
-                  spectrum=args.spectrum, kwip=args.kwip)
+                  spectrum=args.spectrum, kwip=args.kwip, patterns=args.patterns)
         dist.barrier()                                         # nobody leaves before rank 0 has renamed the outputs
     finally:
         dist.destroy_process_group()
