@@ -418,6 +418,56 @@ int pk_select_finish(pk_select *s, uint64_t totals_out[3]);
 int pk_select_timings(pk_select *s, double out[2]);
 void pk_select_destroy(pk_select *s);
 
+/* ---- trim: the longest covered stretch of every read of a FASTQ stream (no reference counterpart: the khmer `filter-abund` /
+ * `bbduk ktrim` step behind a cover lookup).  No parser state and no tables: the trimmer is given the cover bits of the stream
+ * (pk_query_cover of the same stream, or bits from anywhere) and the stream a second time, cut into WHOLE records by offsets
+ * the caller has (pk_record.name_off - 1 and the length of the stream), and answers per record where lines 2 and 4 lie and
+ * which of its positions to keep.  The stream has passed the FASTQ rules in the lookup; whatever the bytes are, no byte
+ * outside a record's own range is read for it.
+ * Positions, valid bases and covered bases are those of pk_query_set_cover and pk_query_set_coords on the FASTA text the
+ * FASTQ stands for: line 2 is the record's one sequence line, position 0 its first non-blank byte, and every byte up to its last
+ * non-blank one holds a position.  A valid base is a byte of ACGTacgt at a position, unless min_qual_byte = T > 0 and the
+ * byte at the same offset of line 4 is below T as an unsigned byte (pk_indexer_set_min_qual's rule); the valid bases of the
+ * stream are numbered in stream order and base g is covered iff bit g of the cover bits is set.  A run is a maximal stretch
+ * of consecutive positions of one record that all hold covered bases.
+ * pk_trim_create touches no device; pk_trim_set_cover brings it up.
+ * pk_trim_set_cover: cover holds ceil(n_bases / 8) bytes, bit g at byte g / 8, bit g % 8 (as pk_query_cover packs them), copied
+ * to the device; n_bases = 0 is legal (cover may then be null).  A null pointer with n_bases > 0 and a threshold outside 0 .. 255
+ * are PK_ERR_ARG.  Before the first feed; after one it is PK_ERR_STATE, and so is a feed without it.
+ * pk_trim_feed: the next n_bytes of the stream, which are n_records whole records: starts holds n_records + 1 non-decreasing
+ * offsets relative to the feed, record r the bytes [starts[r], starts[r + 1]), and starts[n_records] = n_bytes.  out receives
+ * PK_TRIM_FIELDS * n_records words, field f of record r at out[f * n_records + r]:
+ *   PK_TRIM_POS2    the stream offset of the byte that holds position 0 of line 2 (PK_TRIM_END2 when the record has no position)
+ *   PK_TRIM_POS4    the stream offset of the byte of line 4 at the same offset within its line
+ *   PK_TRIM_END2    the stream offset where line 2's content ends and its terminator begins
+ *   PK_TRIM_END4    the same for line 4, whose content is as long as line 2's
+ *   PK_TRIM_SEQ_LEN the positions of the record
+ *   PK_TRIM_START, PK_TRIM_END   its longest run, half-open and 0-based, among equals the one with the smallest start;
+ *                   0 <= start <= end <= seq_len, and 0, 0 for a record without a covered base
+ *   PK_TRIM_COVERED the covered bases of the record over all its runs
+ *   PK_TRIM_LEAD    the blanks of line 2 in front of position 0: line 2 begins at PK_TRIM_POS2 - lead, line 4 at PK_TRIM_POS4 - lead
+ * Non-monotone offsets, a last offset that is not n_bytes and null pointers with records present are PK_ERR_ARG, and then
+ * nothing is launched and the stream does not move.  n_records = 0 launches nothing (starts may be null; the bytes, blank
+ * lines at most, are counted as fed).
+ * pk_trim_feed_device: the same with the text in device memory on the trimmer's device, at any alignment; starts and out stay
+ * on the host.
+ * pk_trim_finish: totals_out = { records seen, valid bases seen, covered bases }; PK_ERR_STATE, with the totals written, if
+ * the valid bases seen are not n_bases -- the stream is not the one the bits were made for (the guard of
+ * pk_query_mask_counts, and the check that this walker and the parser agree on what a valid base is).  Feeds after it are
+ * PK_ERR_STATE.
+ * pk_trim_timings: out = { seconds of the trim kernels so far, measured with HIP events on the trimmer's stream (the copies
+ * are outside them), feeds (as a double) }. */
+enum { PK_TRIM_POS2 = 0, PK_TRIM_POS4 = 1, PK_TRIM_END2 = 2, PK_TRIM_END4 = 3, PK_TRIM_SEQ_LEN = 4, PK_TRIM_START = 5, PK_TRIM_END = 6,
+       PK_TRIM_COVERED = 7, PK_TRIM_LEAD = 8, PK_TRIM_FIELDS = 9 };
+typedef struct pk_trim pk_trim;
+int pk_trim_create(pk_trim **out, int device);
+int pk_trim_set_cover(pk_trim *t, const uint8_t *cover, uint64_t n_bases, int min_qual_byte);
+int pk_trim_feed(pk_trim *t, const uint8_t *host_text, uint64_t n_bytes, const uint64_t *starts, uint64_t n_records, uint64_t *out);
+int pk_trim_feed_device(pk_trim *t, const void *dev_text, uint64_t n_bytes, const uint64_t *starts, uint64_t n_records, uint64_t *out);
+int pk_trim_finish(pk_trim *t, uint64_t totals_out[3]);
+int pk_trim_timings(pk_trim *t, double out[2]);
+void pk_trim_destroy(pk_trim *t);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

@@ -99,6 +99,13 @@ _SIGNATURES = {
     "pk_select_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_select_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_select_destroy": (None, [ctypes.c_void_p]),
+    "pk_trim_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
+    "pk_trim_set_cover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]),
+    "pk_trim_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_trim_feed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_trim_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_trim_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_trim_destroy": (None, [ctypes.c_void_p]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -541,6 +548,82 @@ class Selector:
         out = np.zeros(2, dtype=np.float64)
         _check(load().pk_select_timings(self._h, out.ctypes.data))
         return {"select_s": float(out[0]), "feeds": int(out[1])}
+
+
+TRIM_FIELDS = ("pos2", "pos4", "end2", "end4", "seq_len", "trim_start", "trim_end", "covered", "lead")   # PK_TRIM_POS2 .. PK_TRIM_LEAD
+
+
+class Trimmer:
+    """The longest covered stretch of every read of a FASTQ stream (pk_trim_*): set_cover once, then feed the stream in
+    consecutive pieces of whole records; every feed hands back the nine TRIM_FIELDS of its records.  Creating one touches no
+    device; set_cover brings it up."""
+
+    def __init__(self, device: int = 0):
+        self._h = ctypes.c_void_p()
+        self.device = device
+        _check(load().pk_trim_create(ctypes.byref(self._h), device))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            load().pk_trim_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_cover(self, cover, n_bases: int, min_qual_byte: int = 0):
+        """pk_trim_set_cover: `cover` packed as QueryIndexer.cover returns it, for n_bases bases (copied); min_qual_byte: the
+        threshold byte Q + offset below which a base is no valid base (0 = off).  ValueError for bits of another length."""
+        bits = np.ascontiguousarray(cover, dtype=np.uint8)
+        if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
+            raise ValueError(f"{int(n_bases)} bases take {(int(n_bases) + 7) // 8} bytes of cover bits, got an array of shape {bits.shape}")
+        _check(load().pk_trim_set_cover(self._h, bits.ctypes.data if bits.size else None, int(n_bases), int(min_qual_byte)))
+
+    @staticmethod
+    def _offsets(starts):
+        """(the offsets as the library takes them, room for the fields of their records)"""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        if starts.ndim != 1 or starts.size < 1:
+            raise ValueError(f"R records need R + 1 offsets, got an array of shape {starts.shape}")
+        return starts, np.zeros((len(TRIM_FIELDS), max(1, starts.size - 1)), dtype=np.uint64)
+
+    @staticmethod
+    def _fields(out, n_records: int) -> dict:
+        flat = out.reshape(-1)[:len(TRIM_FIELDS) * n_records].reshape(len(TRIM_FIELDS), n_records)
+        return {name: flat[f].copy() for f, name in enumerate(TRIM_FIELDS)}
+
+    def feed(self, data, starts) -> dict:
+        """pk_trim_feed: the next piece of the stream (anything with the buffer protocol), whole records cut by `starts`
+        (R + 1,) offsets relative to the piece with starts[R] = its length -> dict of the TRIM_FIELDS, (R,) uint64 each."""
+        buf = _as_u8(data)
+        starts, out = self._offsets(starts)
+        _check(load().pk_trim_feed(self._h, buf.ctypes.data if buf.size else None, buf.size, starts.ctypes.data, starts.size - 1, out.ctypes.data))
+        return self._fields(out, starts.size - 1)
+
+    def feed_device(self, dev_ptr: int, n_bytes: int, starts) -> dict:
+        """pk_trim_feed_device: the same with the next n_bytes of the stream at dev_ptr (HBM, any alignment)."""
+        starts, out = self._offsets(starts)
+        _check(load().pk_trim_feed_device(self._h, ctypes.c_void_p(dev_ptr) if dev_ptr else None, int(n_bytes), starts.ctypes.data, starts.size - 1,
+                                          out.ctypes.data))
+        return self._fields(out, starts.size - 1)
+
+    def finish(self) -> dict:
+        """pk_trim_finish: n_records, n_bases (the valid bases seen) and n_covered; PkError (PK_ERR_STATE) if the stream does not
+        hold the valid bases the cover bits were made for."""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(load().pk_trim_finish(self._h, out.ctypes.data))
+        return {"n_records": int(out[0]), "n_bases": int(out[1]), "n_covered": int(out[2])}
+
+    def timings(self) -> dict:
+        """pk_trim_timings: the HIP-event seconds of the trim kernels so far, and the feeds."""
+        out = np.zeros(2, dtype=np.float64)
+        _check(load().pk_trim_timings(self._h, out.ctypes.data))
+        return {"trim_s": float(out[0]), "feeds": int(out[1])}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

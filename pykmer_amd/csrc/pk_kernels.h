@@ -291,4 +291,15 @@ uint32_t select_chunks(uint64_t n);
 int launch_select(const unsigned long long *starts, const uint8_t *keep, uint64_t R, const uint8_t *text, uint64_t pos, uint64_t n,
                   unsigned long long *masks, unsigned long long *sums, unsigned long long *grand, uint8_t *out, uint64_t expected, hipStream_t s);
 
+// kmer_trim.hip -- the longest covered stretch of every record of a FASTQ feed.  text[0 .. n) (device, any
+// alignment) is the stream from offset pos on and holds R whole records, record r the bytes [starts[r], starts[r + 1]) of it
+// (starts: R + 1 non-decreasing offsets <= n, device).  bits: n_words u32 of cover bits (bit g at word g / 32, bit g % 32);
+// base: the valid bases of the stream before the feed; tq: the quality threshold byte, 0 = off.  cnt: R words, left holding
+// every record's first bit; *total receives base + the feed's valid bases; geo: TRIM_FIELDS * R words, field f of record r at
+// geo[f * R + r].  R = 0: nothing is launched.
+constexpr uint32_t TRIM_FIELDS = 9;   // pos2, pos4, end2, end4, seq_len, trim_start, trim_end, covered, lead
+int launch_trim(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, const uint32_t *bits,
+                uint64_t n_words, unsigned long long base, unsigned long long *cnt, unsigned long long *total, unsigned long long *geo,
+                hipStream_t s);
+
 }  // namespace pk

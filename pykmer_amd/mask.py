@@ -62,6 +62,17 @@ def run_cover(query_file: str, kmer_len: int, ptrs, min_count: int, max_count: i
     return out
 
 
+def or_cover(result, part):
+    """stream_groups' join of cover bits: a later group's bits OR-ed into those of the groups before; the first group's part,
+    its bits copied, is the result."""
+    if result is None:
+        part["cover"] = np.array(part["cover"], dtype=np.uint8)
+        return part
+    assert part["n_bases"] == result["n_bases"], "query changed between table groups"
+    result["cover"] |= np.asarray(part["cover"], dtype=np.uint8)
+    return result
+
+
 def cover_bits(query_file: str, tables: Sequence, min_count: int = 1, max_count: int = 255, device: int = 0, hbm_budget: int = None,
                threads: int = DEFAULT_THREADS, stage=None, run=None) -> dict:
     """The cover bits of `query_file` (FASTA; plain, gzip or BGZF) against `tables`: Headers, merger.ResidentTables or
@@ -73,18 +84,8 @@ def cover_bits(query_file: str, tables: Sequence, min_count: int = 1, max_count:
     check_fasta(query_file)
     tables = as_headers(tables, device)
     kmer_len = validate(tables, min_count, max_count)
-
-    def join(result, part):
-        """A later group's bits OR-ed into those of the groups before; the first group's part, its bits copied, is the result."""
-        if result is None:
-            part["cover"] = np.array(part["cover"], dtype=np.uint8)
-            return part
-        assert part["n_bases"] == result["n_bases"], "query changed between table groups"
-        result["cover"] |= np.asarray(part["cover"], dtype=np.uint8)
-        return result
-
     result = stream_groups(query_file, tables, kmer_len, plan_groups(tables, kmer_len, device, hbm_budget), min_count, max_count, run or run_cover,
-                           join, device, threads, stage or (lambda group, dev: stage_tables(group, dev, threads)))
+                           or_cover, device, threads, stage or (lambda group, dev: stage_tables(group, dev, threads)))
     assert result["cover"].shape == ((result["n_bases"] + 7) // 8,)
     return result
 
