@@ -500,11 +500,16 @@ int pk_bgzf_deflate(const uint8_t *src, uint64_t n_bytes, int level, uint32_t bl
  * capacity, 1 if every record position fits 32 bits }.
  * pk_diag_settled_chunks: how many 16 KiB chunks of the indexer's last feed the structure pass squeezed itself (full chunks
  * of plain sequence text that are not entered inside a header line; the squeeze pass only completes those); 0 for a query
- * indexer and before the first feed.  Copies one small record per chunk from the device. */
+ * indexer and before the first feed.  Copies one small record per chunk from the device.
+ * pk_diag_level2_order: the order in which the level-2 sort walks B1 level-1 buckets of the given sizes (B1 a multiple of
+ * 8, 8 .. 512): buckets ranked by size, descending, ties by lower index; rank r is dealt to round r / 8 and to XCD class
+ * r % 8 in even rounds, 7 - r % 8 in odd ones; order_out[class * (B1 / 8) + round] = bucket.  The device computes its order
+ * with the same code; touches no GPU. */
 int pk_diag_occupancy(int which);
 int pk_diag_plan(int k, uint64_t n_bytes, uint64_t out[8]);
 int pk_diag_settled_chunks(pk_indexer *ix, uint64_t *out);
 int pk_diag_plan_slice(int k, int n_slices, uint64_t n_bytes, uint64_t out[16]);
+int pk_diag_level2_order(const uint32_t *sizes, uint32_t B1, uint32_t *order_out);
 
 #ifdef __cplusplus
 }

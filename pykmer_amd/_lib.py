@@ -115,6 +115,7 @@ _SIGNATURES = {
     "pk_diag_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
     "pk_diag_settled_chunks": (ctypes.c_int, [ctypes.c_void_p, _u64p]),
     "pk_diag_plan_slice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_diag_level2_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -853,6 +854,15 @@ def diag_plan_slice(k: int, n_slices: int = 1, n_bytes: int = 0) -> dict:
     d["variant"] = WS_VARIANTS[d["variant"]]
     d["count_kernel"] = COUNT_KERNELS[d["count_kernel"]]
     return d
+
+
+def diag_level2_order(sizes) -> np.ndarray:
+    """pk_diag_level2_order: the order in which level 2 walks level-1 buckets of these sizes, position class * (B1 / 8) +
+    round (no GPU is touched).  ValueError unless B1 is a multiple of 8 from 8 to 512."""
+    s = np.ascontiguousarray(sizes, dtype=np.uint32)
+    out = np.zeros(max(1, s.size), dtype=np.uint32)
+    _check(load().pk_diag_level2_order(s.ctypes.data, s.size, out.ctypes.data))
+    return out[:s.size]
 
 
 def gram_expand(pair: np.ndarray) -> np.ndarray:

@@ -358,6 +358,16 @@ __global__ __launch_bounds__(WG) void k_hist(const uint8_t *__restrict__ src, ui
     }
 }
 
+// ------------------------------------------------------------------ reset ----------------------
+// An empty stream: the tail (stream state, totals, histogram, signals) becomes a copy of tail0 and the record array zero,
+// grid-stride, 8 bytes of the tail and 16 of the records per lane and round.
+__global__ __launch_bounds__(WG) void k_reset(unsigned long long *__restrict__ tail, const unsigned long long *__restrict__ tail0, uint32_t tail_words,
+                                              uint4 *__restrict__ recs, uint64_t recs_quads) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * WG + threadIdx.x, step = (uint64_t)gridDim.x * WG;
+    for (uint64_t i = i0; i < tail_words; i += step) tail[i] = tail0[i];
+    for (uint64_t i = i0; i < recs_quads; i += step) recs[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // ------------------------------------------------------------------ launchers ------------------
 void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_chunks, hipStream_t s) {
     hipLaunchKernelGGL(k_chunk_l1, dim3((n_chunks + WG / 64 - 1) / (WG / 64)), dim3(WG), 0, s, fasta, n, n_chunks, chunk_l1);
@@ -395,6 +405,12 @@ static uint32_t stream_grid(uint64_t items_per_thread_units) {
 }
 void launch_hist8(const uint8_t *table8, uint64_t n, unsigned long long *hist, hipStream_t s) {
     hipLaunchKernelGGL(k_hist, dim3(stream_grid(n / 16 + 1)), dim3(WG), 0, s, table8, n, hist);
+}
+void launch_reset(void *tail, const void *tail0, size_t tail_bytes, DevRec *recs, size_t recs_bytes, hipStream_t s) {
+    static_assert(sizeof(DevRec) % 16 == 0, "k_reset zeroes the record array 16 bytes at a time");
+    const uint64_t quads = recs ? recs_bytes / 16 : 0;               // recs_bytes: whole records
+    hipLaunchKernelGGL(k_reset, dim3(stream_grid(quads > tail_bytes / 8 ? quads : tail_bytes / 8)), dim3(WG), 0, s, (unsigned long long *)tail,
+                       (const unsigned long long *)tail0, (uint32_t)(tail_bytes / 8), (uint4 *)recs, quads);
 }
 
 }  // namespace pk

@@ -458,26 +458,31 @@ __global__ __launch_bounds__(1024) void k_provision(const uint32_t *__restrict__
 }
 
 // after the level-1 sort: where every bucket's records end, and the level-2 work split -- bucket b gets ceil(n_b / R2)
-// work items, counted up with the buckets in XCD-class order (b % 8 major), which is the order the persistent level-2
-// launch walks them in (kmer_part.hip: k_scatter2)
+// work items, counted up with the buckets in XCD-class order, which is the order the persistent level-2 launch walks
+// them in (kmer_part.hip: k_scatter2).  That order deals the buckets out to the classes by size (part_common.h:
+// level2_rank / level2_position) and is written to l2_order, B1 words.
 __global__ __launch_bounds__(1024) void k_level1_finish(const uint32_t *__restrict__ cursor1, const uint32_t *__restrict__ bucket_base,
                                                         const uint32_t *__restrict__ cap_end, PartPlan pl, uint32_t *__restrict__ bucket_end,
-                                                        uint32_t *__restrict__ wg2_start, const uint32_t *__restrict__ flags) {
+                                                        uint32_t *__restrict__ wg2_start, uint32_t *__restrict__ l2_order,
+                                                        const uint32_t *__restrict__ flags) {
     __shared__ uint32_t wsum[16];
+    __shared__ uint32_t size1[PART_MAX_B1], order[PART_MAX_B1];          // B1 <= PART_MAX_B1: part_plan_check refuses any other plan
     if (flags[0]) return;
     const uint32_t d = threadIdx.x, B1 = pl.B1;
     if (d < B1) bucket_end[d] = min(cursor1[d], cap_end[d]);
     if (B1 >= 8u) {
-        const uint32_t per = B1 >> 3;
-        uint32_t g2 = 0;
+        if (d < B1) size1[d] = min(cursor1[d], cap_end[d]) - bucket_base[d];
+        __syncthreads();
+        if (d < B1) order[level2_position(level2_rank(size1, B1, d), B1)] = d;
+        __syncthreads();
+        uint32_t g2 = 0, b = 0;
         if (d < B1) {
-            const uint32_t b = (d % per) * 8u + d / per;
-            const uint32_t size2 = min(cursor1[b], cap_end[b]) - bucket_base[b];
-            g2 = (uint32_t)(((uint64_t)size2 + pl.R2 - 1) / pl.R2);
+            b = order[d];
+            g2 = (uint32_t)(((uint64_t)size1[b] + pl.R2 - 1) / pl.R2);
         }
         uint32_t sum_g2;
-        const uint32_t ps = wg_excl_sum<16, true>(g2, wsum, sum_g2);   // SH_BUSY only to keep the generated code: wsum is free here, the barrier in front is not needed
-        if (d < B1) wg2_start[d] = ps;
+        const uint32_t ps = wg_excl_sum<16, false>(g2, wsum, sum_g2);
+        if (d < B1) { wg2_start[d] = ps; l2_order[d] = b; }
         if (d == 0) wg2_start[B1] = sum_g2;
     }
 }
@@ -569,7 +574,7 @@ void launch_walk_sort(const PartPlan &pl, const PartBuffers &b, const L2 *st2, c
                      b.cursor1, (const uint32_t *)b.cap_end, dump, b.flags, 0u, 0u, (uint32_t *)nullptr, b.side, b.side_n, b.side_cap,
                      (const unsigned long long *)&carry->deep_in);
     hipLaunchKernelGGL(k_level1_finish, dim3(1), dim3(1024), 0, s, (const uint32_t *)b.cursor1, (const uint32_t *)b.bucket_base,
-                       (const uint32_t *)b.cap_end, pl, b.bucket_end, b.wg2_start, (const uint32_t *)b.flags);
+                       (const uint32_t *)b.cap_end, pl, b.bucket_end, b.wg2_start, b.l2_order, (const uint32_t *)b.flags);
 }
 
 // deep windows: the stream's last bases, for the next feed's first slots

@@ -158,10 +158,12 @@ __global__ __launch_bounds__(1024) void k_starts2(uint32_t n_final, const uint32
 // k_provision / k_rooms2 gave each of them (cap_end; a bucket that outgrows it raises flags[0], see part_common.h).  Where
 // a record lands inside its final bucket then depends on timing -- the bucket's contents as a multiset do not.
 // The launch is persistent (two workgroups per CU) over work items of R2 records and XCD-affine: workgroup x runs on
-// XCD x % 8 (round-robin dispatch), and takes items of the level-1 buckets b with b % 8 == x % 8 only.  All writers of
+// XCD x % 8 (round-robin dispatch), and takes items of the level-1 buckets of class x % 8 only.  All writers of
 // one final bucket then share one L2: the partly written cache lines where one tile's run ends and the next one's
 // begins are merged there instead of travelling to HBM twice, and a bucket's cursor lives in one L2.
-// `pos` (wg2_start) is the running item count over the buckets in that order (k_level1_finish).
+// Which buckets a class holds is decided by size, not by b % 8 (part_common.h: level2_position): position a of l2_order,
+// class a / (B1 / 8), holds the bucket.  `pos` (wg2_start) is the running item count over the buckets in that order
+// (k_level1_finish writes both).
 // NT threads x PER records = one tile.  The launch runs as 512 x 32: two workgroups share a CU (72 KiB of LDS and
 // 128 registers each), so one sorts while the other waits at a barrier or for its stores.
 // REC24: the level-1 records are 3-byte records in two planes (32-bit k-mers; part_common.h), `in` is the 16-bit plane.
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(1024) void k_starts2(uint32_t n_final, const uint32
 // 1.14 -> 1.19 ms with write-out batches of four, 2.1 ms with eight (46 spilled registers).)
 template <int NT, int PER, bool REC24 = false>
 __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__ in, const uint32_t *__restrict__ wg2_start,
-                                                   const uint32_t *__restrict__ bucket_base, const uint32_t *__restrict__ bucket_end, PartPlan pl,
+                                                   const uint32_t *__restrict__ l2_order, const uint32_t *__restrict__ bucket_base, const uint32_t *__restrict__ bucket_end, PartPlan pl,
                                                    void *__restrict__ out, uint32_t *__restrict__ cursor, const uint32_t *__restrict__ cap_end,
                                                    uint32_t dump, uint32_t *__restrict__ flags) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(NT, 4) void k_scatter2(const uint32_t *__restrict__
     for (uint32_t w = pos[o_lo] + first; w < w_end; w += step) {         // uniform per workgroup
         uint32_t a = o_lo, z = o_hi;                                     // last position with pos[a] <= w
         while (z - a > 1) { const uint32_t m = (a + z) >> 1; if (pos[m] <= w) a = m; else z = m; }
-        const uint32_t b = (a % per) * 8u + a / per;
+        const uint32_t b = l2_order[a];                                    // uniform: one scalar load per work item
         const uint64_t s = (uint64_t)bucket_base[b] + (uint64_t)(w - pos[a]) * pl.R2;
         const uint64_t e = min(s + pl.R2, (uint64_t)bucket_end[b]);
         item(b, (uint32_t)s, (uint32_t)e);
@@ -785,7 +787,7 @@ CountKernel bucket_count_kernel(const PartPlan &pl, uint64_t n_bytes) {
 // tallied while sampling (addr_bits <= 30: B1 * B2 > B1) or sized from the level-1 records (sample2).
 int part_plan_check(const PartPlan &pl, uint64_t n_bytes) {
     const auto no = [](const std::string &what) { return set_error(PK_ERR_HIP, "partition plan outside the kernels' limits: " + what); };
-    const uint32_t max_B1 = pl.k <= 15 ? 128u : 512u;
+    const uint32_t max_B1 = pl.k <= 15 ? 128u : PART_MAX_B1;
     if (pl.B1 > max_B1 || pl.B2 > 512u || pl.fb_bits > 16u)
         return no(std::to_string(pl.B1) + " x " + std::to_string(pl.B2) + " buckets of 2^" + std::to_string(pl.fb_bits) + " addresses; the LDS arrays hold " +
                   std::to_string(max_B1) + " x 512 of 2^16");
@@ -797,7 +799,7 @@ int part_plan_check(const PartPlan &pl, uint64_t n_bytes) {
 }
 
 // The workspace layout, stated here and nowhere else: every region starts on a 256-byte boundary, in this order.
-size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base, PartBuffers *view) {
+size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base, PartBuffers *view, PartSignals *signals) {
     PartBuffers unused, &b = view ? *view : unused;
     const size_t nfb = (size_t)pl.B1 * pl.B2, rec1 = (size_t)(pl.capacity1 + TILE + 64);
     size_t o = 0;
@@ -816,8 +818,9 @@ size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base, PartB
     place(b.sampled_n, s2 ? (size_t)pl.B1 * 4 : 0, true);
     place(b.block_tot, s2 ? 1024 * 4 : 0);
     if (!s2) b.sampled_n = b.block_tot = nullptr;
-    // (wg2_start: level-2 work items, buckets in XCD-class order)
+    // (wg2_start: level-2 work items, buckets in XCD-class order; l2_order: that order)
     for (uint32_t **p : {&b.bucket_base, &b.bucket_end, &b.cursor1, &b.cap_end, &b.wg2_start}) place(*p, (size_t)(pl.B1 + 1) * 4);
+    place(b.l2_order, (size_t)pl.B1 * 4);
     for (uint32_t **p : {&b.final_start, &b.cursor2, &b.cap2_end}) place(*p, (nfb + 1) * 4);
     // level-1 buckets + the dump tile: 2-byte records when level 1 is the only level, two planes of 2 + 1 bytes for 32-bit
     // k-mers with a second level (part_common.h), 4-byte records (the low 32 bits) for 64-bit k-mers
@@ -825,7 +828,7 @@ size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base, PartB
     place(b.out2, !pl.b2 ? 256 : (size_t)(pl.capacity2 + TILE + 64) * 2);
     b.side_cap = n_bytes + 16;                             // every side entry stands for >= 1 k-mer
     place(b.side, (size_t)b.side_cap * 8);
-    place(b.signals, sizeof(PartSignals));
+    b.signals = signals;                                   // outside the workspace: next to the stream totals (pk_host.h: Tail)
     b.side_n = &b.signals->side_n;
     b.flags = b.signals->flags;
     return o;
@@ -851,6 +854,15 @@ extern "C" int pk_diag_occupancy(int which) {
     if (which == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_bucket_count_half_lean<1024, true>, 1024, 65536);
     if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_scatter2<512, 32>, 512, SCATTER_LDS_NARROW);
     return e == hipSuccess ? n : -(int)e;
+}
+
+// the order k_level1_finish gives B1 level-1 buckets of these sizes (the same two functions, run on the host); touches no GPU
+extern "C" int pk_diag_level2_order(const uint32_t *sizes, uint32_t B1, uint32_t *order_out) {
+    if (!sizes || !order_out) return set_error(PK_ERR_ARG, "pk_diag_level2_order: null argument");
+    static_assert(PART_MAX_B1 == 512, "the message below and include/pykmer_hip.h name the limit");
+    if (B1 < 8u || B1 > PART_MAX_B1 || (B1 & 7u)) return set_error(PK_ERR_ARG, "pk_diag_level2_order: B1 must be a multiple of 8 from 8 to 512");
+    for (uint32_t b = 0; b < B1; b++) order_out[level2_position(level2_rank(sizes, B1, b), B1)] = b;
+    return PK_OK;
 }
 
 // Everything behind the squeeze pass for one feed: bucket layout (sampled with `stride`; 1 = exact), the fused
@@ -890,7 +902,7 @@ int launch_partitioned(const PartPlan &pl, const PartBuffers &b, const L2 *st2, 
         // do not hide each other (both live on the LDS pipe).
         const uint32_t grid2 = 4096u;
         hipLaunchKernelGGL((pl.k <= 15 ? &k_scatter2<512, 32, true> : &k_scatter2<512, 32>), dim3(grid2), dim3(512), SCATTER_LDS_NARROW, s,
-                           (const uint32_t *)b.out1, b.wg2_start, b.bucket_base, b.bucket_end, pl, b.out2, b.cursor2, (const uint32_t *)b.cap2_end,
+                           (const uint32_t *)b.out1, b.wg2_start, (const uint32_t *)b.l2_order, b.bucket_base, b.bucket_end, pl, b.out2, b.cursor2, (const uint32_t *)b.cap2_end,
                            (uint32_t)pl.capacity2, b.flags);
         stage("level 2");
         final_recs = (const uint16_t *)b.out2; k6_start = b.final_start; k6_end = b.cursor2;   // a final bucket ends where its cursor stopped

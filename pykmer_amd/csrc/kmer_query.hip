@@ -421,7 +421,7 @@ __global__ __launch_bounds__(QNT) void k_query_lookup(const uint32_t *__restrict
 }
 
 // ------------------------------------------------------------------ host side -------------------
-size_t query_workspace(uint32_t n_chunks, uint8_t *base, PartBuffers *view, QueryBuffers *qview) {
+size_t query_workspace(uint32_t n_chunks, uint8_t *base, PartBuffers *view, QueryBuffers *qview, PartSignals *signals) {
     PartBuffers unused_p, &b = view ? *view : unused_p;
     QueryBuffers unused_q, &qb = qview ? *qview : unused_q;
     size_t o = 0;
@@ -435,7 +435,7 @@ size_t query_workspace(uint32_t n_chunks, uint8_t *base, PartBuffers *view, Quer
     place(b.n_bases, (size_t)n_chunks * 4);
     place(qb.slot_count, (size_t)n_chunks * 4);
     place(qb.slot_first, (size_t)n_chunks * 8);
-    place(b.signals, sizeof(PartSignals));
+    b.signals = signals;                                   // outside the workspace: next to the stream totals (pk_host.h: Tail)
     b.side_n = &b.signals->side_n;
     b.flags = b.signals->flags;
     return o;

@@ -91,6 +91,24 @@ __host__ __device__ __forceinline__ size_t level1_hi_plane_offset(uint64_t capac
     return (((size_t)(capacity1 + TILE + 64) * 2u) + 255u) & ~(size_t)255u;
 }
 
+// ------------------------------------------------------------------ level-2 work order ----------
+// The persistent level-2 launch (kmer_part.hip: k_scatter2) gives each of the eight XCD classes the same number of
+// workgroups and B1 / 8 level-1 buckets, and it ends when the class with the most records ends.  A canonical k-mer is the
+// smaller of two words, so bucket sizes fall almost linearly with the bucket index and the classes b % 8 differ by 12 %
+// end to end.  Instead the buckets are ranked by size (descending, ties by lower index) and dealt out snake-wise: rank r
+// goes to round r / 8, and to class r % 8 in even rounds, 7 - r % 8 in odd ones.  Position class * (B1 / 8) + round of the
+// order array holds the bucket.  B1: a multiple of 8.
+__host__ __device__ __forceinline__ uint32_t level2_rank(const uint32_t *sizes, uint32_t B1, uint32_t b) {
+    const uint32_t mine = sizes[b];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < B1; j++) rank += (sizes[j] > mine || (sizes[j] == mine && j < b)) ? 1u : 0u;
+    return rank;
+}
+__host__ __device__ __forceinline__ uint32_t level2_position(uint32_t rank, uint32_t B1) {
+    const uint32_t round = rank >> 3, c = rank & 7u;
+    return ((round & 1u) ? 7u - c : c) * (B1 >> 3) + round;
+}
+
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     // DPP: shifts inside the rows of 16 lanes, then the row totals broadcast into the rows behind them (no LDS traffic;
     // the shuffle form went through ds_bpermute six times per scan, 64 scans per wave in k_provision)

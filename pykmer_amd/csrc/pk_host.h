@@ -205,11 +205,13 @@ struct pk_indexer {
     pk::Events ev;
     std::unique_ptr<pk::QueryState> q;       // query mode: no table, hist_rep or partition of its own
     pk::DevBuf<uint8_t> table8;          // the .kin image
-    // parser state + running totals, and the value histogram, side by side: one copy brings both to the host, one copy resets both
-    struct Tail { pk::Carry carry; unsigned long long hist[256]; pk::FqCarry fq; };
-    pk::DevBuf<Tail> tail, tail0;          // tail0: the state of an empty stream (a reset is a device-to-device copy, no host wait)
-    struct Pinned { Tail tail; uint32_t flags[4]; } *pin = nullptr;   // pinned landing zone of the small read-backs
-    bool tail_on_host = false;         // pin->tail is what the device holds (the last feed brought it along with its flags)
+    // parser state + running totals, the value histogram and what the feed's partition passes signal, side by side: one copy
+    // brings all of it to the host, one kernel resets it
+    struct Tail { pk::Carry carry; unsigned long long hist[256]; pk::FqCarry fq; pk::PartSignals signals; };
+    pk::DevBuf<Tail> tail, tail0;          // tail0: the state of an empty stream (the reset kernel copies it, no host wait)
+    static_assert(sizeof(Tail) % 8 == 0, "launch_reset copies the tail 8 bytes at a time");
+    Tail *pin = nullptr;               // pinned landing zone of the feed's read-back
+    bool tail_on_host = false;         // *pin is what the device holds (the last feed's read-back)
     bool zero_timed = true;            // t_zero of the last reset has been read from its events
     pk::DevBuf<unsigned long long> hist_rep;   // HIST_REPLICAS copies of one feed's histogram change (zero between feeds)
     pk::DevBuf<pk::DevRec> recs;

@@ -35,9 +35,11 @@ static int ix_reset(pk_indexer *ix) {
     // the first feed writes every slice of the u8 table itself (k_bucket_count, fresh); the table is only
     // zeroed if nothing gets fed at all (see pk_indexer_finish).  Nothing here waits for the device: the stream orders
     // the reset behind whatever is still running, and its duration is read at the next point that waits anyway.
-    HIPCHK(hipMemcpyAsync(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToDevice, ix->stream));
+    // One kernel: the tail becomes tail0, the record array zero (where a copy and a fill of the runtime were two stream
+    // operations).
+    launch_reset(ix->tail.p, ix->tail0.p, sizeof(pk_indexer::Tail), ix->recs.p, ix->recs.bytes, ix->stream);
+    HIPCHK(hipGetLastError());
     ix->tail_on_host = false;
-    if (ix->recs.p) HIPCHK(hipMemsetAsync(ix->recs.p, 0, ix->recs.bytes, ix->stream));
     const int rc = ix->q ? ix->q->reset(ix->stream) : PK_OK;
     if (rc) return rc;
     HIPCHK(hipEventRecord(ix->ev.reset_end, ix->stream));
@@ -62,10 +64,10 @@ static void time_reset(pk_indexer *ix) {
     ix->zero_timed = true;
 }
 
-// The stream totals, the value histogram and the FASTQ state to the host, behind everything queued so far; the host waits
-// for it.  This is the wait of a feed: it also surfaces a kernel fault and makes the reset's events readable.
+// The stream totals, the value histogram, the FASTQ state and the feed's signals to the host in one copy, behind everything
+// queued so far; the host waits for it.  This is the wait of a feed: it also surfaces a kernel fault and makes the reset's events readable.
 static int read_tail(pk_indexer *ix) {
-    HIPCHK(hipMemcpyAsync(&ix->pin->tail, ix->tail.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipMemcpyAsync(ix->pin, ix->tail.p, sizeof(pk_indexer::Tail), hipMemcpyDeviceToHost, ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream));
     HIPCHK(hipGetLastError());
     time_reset(ix);
@@ -242,41 +244,40 @@ static int run_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes, const Pa
     launch_scan_l1(ix->c_l1.p, n_chunks, carry, ix->c_l1s.p, ix->t_l1.p, pb.signals, ix->stream);
     launch_chunk_l2(f, n_bytes, ix->c_l1s.p, ix->c_l2.p, ix->lane_state.p, ix->packs.p, ix->chunk_odd.p, fix, pb, n_chunks, (uint32_t)ix->k, ix->stream);
     launch_scan_l2(ix->c_l2.p, n_chunks, carry, ix->c_l2s.p, ix->t_l2.p, (uint32_t)ix->k, ix->stream);
-    HIPCHK(hipEventRecord(ev.scan_end, ix->stream));
+    HIPCHK(hipEventRecord(ev.scan_end, ix->stream));           // where the first squeeze begins, too: one record, not two
+    hipEvent_t squeeze_from = ev.scan_end;
     uint32_t raised = 0;
     uint64_t squeezed_cap = 0;                               // record slots the last squeeze of this feed ran with
     for (int attempt = 0;; attempt++) {
         if (attempt) HIPCHK(hipMemsetAsync(pb.signals, 0, sizeof(PartSignals), ix->stream));   // the scan kernel zeroed them for the first attempt
         if (!raised || raised == 2u) {
             squeezed_cap = ix->recs_cap();
-            HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream));
+            if (attempt) { HIPCHK(hipEventRecord(ev.squeeze_begin, ix->stream)); squeeze_from = ev.squeeze_begin; }
             launch_squeeze(pl, pb, f, n_bytes, ix->bytes_fed, ix->lane_state.p, ix->packs.p, ix->c_l2s.p, ix->chunk_odd.p, fix, ix->recs.p, squeezed_cap,
                            carry, ix->stream);
             if (ix->k > 17) launch_deep_tail(pl, pb, carry, ix->stream);
             HIPCHK(hipEventRecord(ev.squeeze_end, ix->stream));
         }
         if ((rc = queue(raised))) return rc;
-        volatile uint32_t *got = ix->pin->flags;
-        // what the host needs of the feed, in two small copies behind the last kernel: the flags, and the stream totals +
-        // value histogram (pk_indexer_finish then has nothing left to fetch)
-        HIPCHK(hipMemcpyAsync(ix->pin->flags, pb.flags, sizeof ix->pin->flags, hipMemcpyDeviceToHost, ix->stream));
+        // what the host needs of the feed, in one small copy behind the last kernel: the flags (pb.signals lies in the
+        // tail), the stream totals and the value histogram (pk_indexer_finish then has nothing left to fetch)
         if ((rc = read_tail(ix))) return rc;
-        raised = got[0];
+        raised = ix->pin->signals.flags[0];
         if (!raised) break;
         if (attempt >= 3) return fail(PK_ERR_HIP, "%s did not settle (internal error, flag %u)", what, raised);
         // more records than the array holds: grow it, squeeze again
-        if (raised == 2u && (rc = ensure_recs(ix, ix->pin->tail.carry.n_recs, ix->bytes_fed + n_bytes))) return rc;
+        if (raised == 2u && (rc = ensure_recs(ix, ix->pin->carry.n_recs, ix->bytes_fed + n_bytes))) return rc;
     }
     // the text behind the squeeze is this feed's only if its last squeeze had room for every record (it backs out otherwise)
-    if (ix->pin->tail.carry.n_recs > squeezed_cap)
+    if (ix->pin->carry.n_recs > squeezed_cap)
         return fail(PK_ERR_HIP, "feed %s without its squeeze: %llu records, %llu slots (internal error)", done,
-                    (unsigned long long)ix->pin->tail.carry.n_recs, (unsigned long long)squeezed_cap);
+                    (unsigned long long)ix->pin->carry.n_recs, (unsigned long long)squeezed_cap);
     const uint64_t recs_before = ix->n_recs;
-    ix->n_recs = ix->pin->tail.carry.n_recs;
+    ix->n_recs = ix->pin->carry.n_recs;
     // room for the next feed's records before it arrives: as many again as this feed brought, and then some
     if ((rc = ensure_recs(ix, ix->n_recs + 2 * (ix->n_recs - recs_before) + 1024, ix->bytes_fed + n_bytes))) return rc;
     if ((rc = add_elapsed(&ix->t_scan, ev.scan_begin, ev.scan_end))) return rc;
-    if ((rc = add_elapsed(&ix->t_squeeze, ev.squeeze_begin, ev.squeeze_end))) return rc;
+    if ((rc = add_elapsed(&ix->t_squeeze, squeeze_from, ev.squeeze_end))) return rc;
     ix->feeds++;
     ix->bytes_fed += n_bytes;
     if (fix) ix->fix_chunks = n_chunks;
@@ -291,7 +292,7 @@ static int count_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if (rc) return rc;
     if ((rc = ix->ws.reserve(part_workspace(pl, n_bytes)))) return rc;
     PartBuffers pb;
-    part_workspace(pl, n_bytes, ix->ws.p, &pb);
+    part_workspace(pl, n_bytes, ix->ws.p, &pb, &ix->tail.p->signals);
     const Events &ev = ix->ev;
     uint32_t stride = pl.sample_stride;
     // the level-1 buckets are laid out from a sample of the slots; if one of them runs out of room every later kernel
@@ -310,7 +311,7 @@ static int count_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         return PK_OK;
     };
     if ((rc = run_feed(ix, f, n_bytes, pl, pb, "the feed's layout", "counted", queue))) return rc;
-    ix->recounted += ix->pin->flags[1];
+    ix->recounted += ix->pin->signals.flags[1];
     ix->table_fresh = false;
     if ((rc = add_elapsed(&ix->t_part, ev.squeeze_end, ev.part_end))) return rc;
     if ((rc = add_elapsed(&ix->t_bucket, ev.part_end, ev.bucket_end))) return rc;
@@ -329,7 +330,7 @@ static int mask_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if (rc) return rc;
     PartBuffers pb;
     QueryBuffers qb;
-    query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb);
+    query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb, &ix->tail.p->signals);
     if ((rc = q.base_first.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
     if ((rc = q.mask_out.reserve(n_bytes + 64))) return rc;
     if (q.intervals && (rc = q.cpos.reserve((size_t)pl.n_chunks * sizeof(unsigned long long)))) return rc;
@@ -395,7 +396,7 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
     if (rc) return rc;
     PartBuffers pb;
     QueryBuffers qb;
-    query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb);
+    query_workspace(pl.n_chunks, ix->ws.p, &pb, &qb, &ix->tail.p->signals);
     Carry *carry = &ix->tail.p->carry;
     const uint32_t N = (uint32_t)q.tables.size();
     if ((rc = q.size_rows(ix->recs_cap(), ix->bytes_fed + n_bytes, ix->stream))) return rc;
@@ -434,7 +435,7 @@ static int query_feed(pk_indexer *ix, const uint8_t *f, uint64_t n_bytes) {
         return PK_OK;
     };
     if ((rc = run_feed(ix, f, n_bytes, pl, pb, "the query feed", "looked up", queue))) return rc;
-    q.windows = ix->pin->tail.carry.num_kmers;
+    q.windows = ix->pin->carry.num_kmers;
     q.p_done = ix->n_recs;
     if ((rc = add_elapsed(&ix->t_part, q.lookup_begin, q.lookup_end))) return rc;
     if (q.cover) q.nb.settle();                              // the base count behind this feed is the next feed's start
@@ -472,7 +473,7 @@ static int fq_fail(pk_indexer *ix, uint64_t rec, uint32_t rule) {
 
 // the rules the kernels checked, as the feed's read-back left them in pin
 static int fq_verdict(pk_indexer *ix) {
-    const FqCarry &q = ix->pin->tail.fq;
+    const FqCarry &q = ix->pin->fq;
     uint64_t rec = ~0ull;
     uint32_t rule = 0;
     if (q.err != ~0ull) { rec = q.err >> 3; rule = (uint32_t)(q.err & 7u); }
@@ -524,13 +525,13 @@ static int fq_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n) {
     launch_fq_front(f, n, ix->fq_sums.p, ix->fq_st.p, ix->fq_out[b].p, held, ix->fq_recs.p, ix->fq_out2.p, ix->fq_recs_cap(), tq, carry, ix->stream);
     HIPCHK(hipGetLastError());
     if ((rc = fq_flush(ix))) return rc;
-    if (ix->pin->tail.fq.need > ix->fq_recs_cap()) {
-        if ((rc = fq_ensure_recs(ix, ix->pin->tail.fq.need + n / 256 + 1024))) return rc;
+    if (ix->pin->fq.need > ix->fq_recs_cap()) {
+        if ((rc = fq_ensure_recs(ix, ix->pin->fq.need + n / 256 + 1024))) return rc;
         launch_fq_write(f, n, ix->fq_st.p, ix->fq_out[b].p, held, ix->fq_recs.p, ix->fq_out2.p, ix->fq_recs_cap(), tq, carry, ix->stream);
         HIPCHK(hipGetLastError());
         if ((rc = fq_flush(ix))) return rc;
     }
-    const FqCarry &q = ix->pin->tail.fq;
+    const FqCarry &q = ix->pin->fq;
     ix->fq_need = q.need;
     if ((rc = fq_verdict(ix))) return rc;
     const uint64_t out_lo = q.in.out - held;                 // the emitted bytes fq_out[b] begins with
@@ -544,7 +545,7 @@ static int fq_feed_piece(pk_indexer *ix, const uint8_t *f, uint64_t n) {
 // end of stream: after the last complete record only line terminators (checked with the feeds), or a last line 4
 // without a terminator
 static int fq_end_check(pk_indexer *ix) {
-    const FqCarry &q = ix->pin->tail.fq;
+    const FqCarry &q = ix->pin->fq;
     if (q.trail != ~0ull) return PK_OK;
     const uint32_t role = (uint32_t)(q.st.line & 3u);
     const uint64_t rec = q.st.line / 4u;
@@ -578,7 +579,7 @@ extern "C" int pk_indexer_set_min_qual(pk_indexer *ix, int threshold_byte) {
 extern "C" int pk_indexer_fastq_masked(pk_indexer *ix, uint64_t *out) {
     if (!ix || !out) return fail(PK_ERR_ARG, "null argument");
     if (ix->format != PK_FORMAT_FASTQ) return fail(PK_ERR_STATE, "not a FASTQ indexer");
-    *out = ix->fed && ix->fq_tq ? ix->pin->tail.fq.masked : 0;   // every feed ends with its read-back
+    *out = ix->fed && ix->fq_tq ? ix->pin->fq.masked : 0;   // every feed ends with its read-back
     return PK_OK;
 }
 
@@ -587,7 +588,7 @@ extern "C" int pk_indexer_fastq_stats(pk_indexer *ix, uint64_t out[4]) {
     if (ix->format != PK_FORMAT_FASTQ) return fail(PK_ERR_STATE, "not a FASTQ indexer");
     for (int i = 0; i < 4; i++) out[i] = 0;
     if (!ix->fed) return PK_OK;
-    const FqCarry &q = ix->pin->tail.fq;                     // every feed ends with its read-back
+    const FqCarry &q = ix->pin->fq;                     // every feed ends with its read-back
     const uint64_t lines = q.st.line + (q.st.curlen > 0 ? 1u : 0u);
     out[0] = q.trail != ~0ull ? q.trail / 4u : (lines + 3u) / 4u;
     out[1] = lines;
@@ -700,13 +701,13 @@ extern "C" int pk_indexer_finish(pk_indexer *ix, uint64_t *num_kmers_out, uint64
         }
         ix->finished = true;
     }
-    const Carry &c = ix->pin->tail.carry;
+    const Carry &c = ix->pin->carry;
     if (num_kmers_out) *num_kmers_out = c.num_kmers;
     if (total_bp_out) *total_bp_out = c.total_bp;
     if (n_recs_out) *n_recs_out = c.n_recs;
     if (hist256_out) {
         if (ix->q) memset(hist256_out, 0, 256 * sizeof(uint64_t));   // no table of its own
-        else hist_with_zeros(ix->pin->tail.hist, ix->n, hist256_out);
+        else hist_with_zeros(ix->pin->hist, ix->n, hist256_out);
     }
     return PK_OK;
 }

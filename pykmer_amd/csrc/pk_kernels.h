@@ -41,6 +41,8 @@ void launch_chunk_l1(const uint8_t *fasta, uint64_t n, L1 *chunk_l1, uint32_t n_
 void launch_scan_l1(const L1 *in, uint32_t n_chunks, Carry *carry, L1 *out, L1 *tile_ws, PartSignals *zeroed, hipStream_t s);
 void launch_scan_l2(const L2 *in, uint32_t n_chunks, Carry *carry, L2 *out, L2 *tile_ws, uint32_t k, hipStream_t s);
 void launch_hist8(const uint8_t *table8, uint64_t n, unsigned long long *hist, hipStream_t s);
+// the tail (tail_bytes, a multiple of 8) becomes a copy of tail0, the record array (recs_bytes, whole records; may be null) zero
+void launch_reset(void *tail, const void *tail0, size_t tail_bytes, DevRec *recs, size_t recs_bytes, hipStream_t s);
 
 // kmer_pack.hip -- the packed stream: one slot per 16 KiB text chunk
 constexpr uint32_t SLOT_CODE_WORDS = 1024;   // 16384 bases x 2 bits
@@ -65,6 +67,7 @@ struct PartPlan {
     uint64_t capacity1;      // record slots for all level-1 buckets together (the dump area starts there)
     uint64_t capacity2;      // the same for the final buckets, where they are laid out from the estimate
 };
+constexpr uint32_t PART_MAX_B1 = 512;   // level-1 buckets at most (part_plan_check): k_level1_finish ranks them in LDS arrays of this size
 constexpr uint32_t COUNT_WGS = 256;   // workgroups (= tally rows) of the sampling launch
 constexpr uint32_t HIST_REPLICAS = 64;   // copies of the 256-bin histogram change the bucket-count workgroups add into (zeroed by their reader, k_apply_side)
 // The workspace of the partition passes: one device allocation, seen through typed pointers.  part_workspace
@@ -74,6 +77,7 @@ struct PartBuffers {
     uint32_t *tally_rows, *tally_tot;                       // the sampling launch's rows and their column sums
     uint32_t *sampled_n, *block_tot;                        // sample2 only (null otherwise): records sampled per level-1 bucket, k_rooms2's block totals
     uint32_t *bucket_base, *bucket_end, *cursor1, *cap_end, *wg2_start;   // level 1, B1 + 1 words each
+    uint32_t *l2_order;                                     // B1 words: the level-1 buckets in the order level 2 walks them
     uint32_t *final_start, *cursor2, *cap2_end;             // the final buckets, B1 * B2 + 1 words each
     void *out1, *out2;                                      // level-1 and final records, each with its dump tile
     unsigned long long *side, *side_n;                      // hot-key (address, count) entries; side_n = &signals->side_n
@@ -93,8 +97,9 @@ uint32_t bucket_split(const PartPlan &pl, uint64_t n_bytes);          // kmer_pa
 CountKernel bucket_count_kernel(const PartPlan &pl, uint64_t n_bytes);   // kmer_part.hip: k_bucket_count, _bytes or _half_lean
 // PK_OK, or PK_ERR_HIP and a message naming the limit of the kernels that the plan exceeds
 int part_plan_check(const PartPlan &pl, uint64_t n_bytes);
-// the bytes of the workspace for the plan; with `view`, also where its regions lie in an allocation starting at `base`
-size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base = nullptr, PartBuffers *view = nullptr);
+// the bytes of the workspace for the plan; with `view`, also where its regions lie in an allocation starting at `base`.
+// `signals`: the feed's PartSignals, which live outside the workspace (the view's signals, side_n and flags point there)
+size_t part_workspace(const PartPlan &pl, uint64_t n_bytes, uint8_t *base = nullptr, PartBuffers *view = nullptr, PartSignals *signals = nullptr);
 void part_set_attributes();
 void fuse_set_attributes();
 // The launchers take the plan, the view and what lives outside the workspace.  `carry`: its deep_in / deep_out words are
@@ -127,9 +132,10 @@ struct QueryBuffers {
     uint32_t *slot_count;                                   // valid windows per slot
     unsigned long long *slot_first;                         // stream ordinal of a slot's first valid window
 };
-// the workspace of a query feed: the squeezed text and the signals (the PartBuffers fields the squeeze uses; the rest stay
-// null) and the per-slot window counts
-size_t query_workspace(uint32_t n_chunks, uint8_t *base = nullptr, PartBuffers *view = nullptr, QueryBuffers *qview = nullptr);
+// the workspace of a query feed: the squeezed text (the PartBuffers fields the squeeze uses; the rest stay null) and the
+// per-slot window counts; `signals` as for part_workspace
+size_t query_workspace(uint32_t n_chunks, uint8_t *base = nullptr, PartBuffers *view = nullptr, QueryBuffers *qview = nullptr,
+                       PartSignals *signals = nullptr);
 // per-slot window counts -> slot_first; P[p_done .. carry->n_recs) from recs[].n_valid (P[r] = valid windows before record r).
 // bin_windows = W > 0: also Bf over the same r (Bf[r] = bins of W windows in the records before r); 0: Bf is not touched.
 void launch_query_scan(const PartPlan &pl, const PartBuffers &b, const QueryBuffers &qb, const L2 *st2, uint64_t windows_before, const DevRec *recs,

@@ -5,8 +5,8 @@
 // loop, or follows another scan on the same words, with no barrier in between -- so a barrier goes in front of the store
 // of the wave totals.  false: the caller knows that every reader of sh has passed a barrier since (or that there was
 // none), and the scan costs one barrier.  Either way there is none behind the last read of sh.
-// (k_query_count, k_query_lookup and k_level1_finish pass true on free words: their scans have always had the barrier, and
-// it stays so that their code stays as it was.)
+// (k_query_count and k_query_lookup pass true on free words: their scans have always had the barrier, and it stays so that
+// their code stays as it was.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
