@@ -468,6 +468,56 @@ int pk_trim_finish(pk_trim *t, uint64_t totals_out[3]);
 int pk_trim_timings(pk_trim *t, double out[2]);
 void pk_trim_destroy(pk_trim *t);
 
+/* ---- correct: single-base corrections of the reads of a FASTQ stream (no reference counterpart: the step of Musket, Lighter,
+ * BFC and `bbduk` / tadpole `ecc` behind a cover lookup).  Feeds, positions, valid bases, the threshold byte and the cover
+ * bits are pk_trim's: the corrector is given the tables, the cover bits of the stream (pk_query_cover of the same stream
+ * against the same tables, or bits from anywhere) and the stream a second time, cut into WHOLE records.
+ * A valid run is a maximal stretch [lo, hi) of consecutive positions of one record that all hold valid bases.  Window s is
+ * the positions [s, s + k); it is valid iff lo <= s and s + k <= hi for one valid run.  A window MATCHES iff at least one
+ * table holds min_count <= T[a] <= max_count at its canonical address a.  A CANDIDATE is a position p that holds a valid base,
+ * is not covered and lies in a valid run with hi - lo >= k; its windows are W(p) = { s : max(lo, p - k + 1) <= s <=
+ * min(p, hi - k) }, w(p) = |W(p)| of them, 1 <= w(p) <= k.  A candidate is TRIED iff w(p) >= min_windows, UNTRIED otherwise.
+ * A base b of A C G T other than the base at p (case ignored) PASSES iff every window of W(p) matches when read with b at p
+ * and the read's own bases everywhere else.  A tried candidate is CORRECTED iff exactly one base passes, AMBIGUOUS iff two or
+ * three pass, UNFIXABLE iff none does.  Every candidate is judged against the uncorrected read: the result depends neither
+ * on the order of the positions, nor on how the stream is cut into feeds, nor on other corrections.  A corrected position's
+ * byte becomes "ACGT"[b] | (old & 0x20); no other byte of the text changes.
+ * pk_correct_create touches no device; k is odd and at most 17 (PK_ERR_ARG otherwise).
+ * pk_correct_set_tables: N >= 1 (at most 16: one launch reads them all) device tables of 4^k bytes on the corrector's device,
+ * owned by the caller and alive until the last feed, 1 <= min_count <= max_count <= 255; PK_ERR_ARG otherwise.  It brings the
+ * device up.
+ * pk_correct_set_cover: cover and n_bases as for pk_trim_set_cover (copied), min_qual_byte in 0 .. 255, min_windows in
+ * 1 .. k; arguments out of range are PK_ERR_ARG.  It comes after the tables and before the first feed: PK_ERR_STATE out of
+ * order, and so is a feed without it.
+ * pk_correct_feed: text, starts and n_records as for pk_trim_feed.  host_text_out receives n_bytes bytes: the feed's text with
+ * the corrected bytes patched in (it may be host_text itself).  out receives PK_CORR_FIELDS * n_records words, field f of
+ * record r at out[f * n_records + r]:
+ *   PK_CORR_POS2        the stream offset of the byte that holds position 0 of line 2 (as PK_TRIM_POS2)
+ *   PK_CORR_SEQ_LEN     the positions of the record
+ *   PK_CORR_CANDIDATES  its candidates; PK_CORR_UNTRIED, PK_CORR_CORRECTED, PK_CORR_AMBIGUOUS: those of each outcome; the
+ *                       unfixable ones are the rest: candidates = untried + corrected + ambiguous + unfixable
+ * The argument errors of pk_trim_feed, and a null text_out with bytes present, are PK_ERR_ARG; then nothing is launched and
+ * the stream does not move.  n_records = 0 launches no kernel (the bytes are copied and counted as fed).
+ * pk_correct_feed_device: the same with text and text_out in device memory on the corrector's device, at any alignment and
+ * not overlapping (PK_ERR_ARG otherwise); starts and out stay on the host.
+ * pk_correct_finish: totals_out = { records seen, valid bases seen, candidates, untried, corrected, ambiguous };
+ * PK_ERR_STATE, with the totals written, if the valid bases seen are not n_bases.  Feeds after it are PK_ERR_STATE.
+ * pk_correct_timings: out = { seconds of the correct kernels so far, measured with HIP events on the corrector's stream (the
+ * copies are outside them), feeds (as a double) }. */
+enum { PK_CORR_POS2 = 0, PK_CORR_SEQ_LEN = 1, PK_CORR_CANDIDATES = 2, PK_CORR_UNTRIED = 3, PK_CORR_CORRECTED = 4, PK_CORR_AMBIGUOUS = 5,
+       PK_CORR_FIELDS = 6 };
+typedef struct pk_correct pk_correct;
+int pk_correct_create(pk_correct **out, int k, int device);
+int pk_correct_set_tables(pk_correct *c, const void *const *dev_tables, int N, int min_count, int max_count);
+int pk_correct_set_cover(pk_correct *c, const uint8_t *cover, uint64_t n_bases, int min_qual_byte, int min_windows);
+int pk_correct_feed(pk_correct *c, const uint8_t *host_text, uint64_t n_bytes, const uint64_t *starts, uint64_t n_records,
+                    uint8_t *host_text_out, uint64_t *out);
+int pk_correct_feed_device(pk_correct *c, const void *dev_text, uint64_t n_bytes, const uint64_t *starts, uint64_t n_records,
+                           void *dev_text_out, uint64_t *out);
+int pk_correct_finish(pk_correct *c, uint64_t totals_out[6]);
+int pk_correct_timings(pk_correct *c, double out[2]);
+void pk_correct_destroy(pk_correct *c);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

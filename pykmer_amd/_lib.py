@@ -106,6 +106,16 @@ _SIGNATURES = {
     "pk_trim_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_trim_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_trim_destroy": (None, [ctypes.c_void_p]),
+    "pk_correct_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
+    "pk_correct_set_tables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pk_correct_set_cover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int]),
+    "pk_correct_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+    "pk_correct_feed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "pk_correct_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_correct_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_correct_destroy": (None, [ctypes.c_void_p]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -625,6 +635,91 @@ class Trimmer:
         out = np.zeros(2, dtype=np.float64)
         _check(load().pk_trim_timings(self._h, out.ctypes.data))
         return {"trim_s": float(out[0]), "feeds": int(out[1])}
+
+
+CORR_FIELDS = ("pos2", "seq_len", "candidates", "untried", "corrected", "ambiguous")   # PK_CORR_POS2 .. PK_CORR_AMBIGUOUS
+
+
+class Corrector:
+    """Single-base corrections of the reads of a FASTQ stream (pk_correct_*): set_tables, set_cover, then feed the stream in
+    consecutive pieces of whole records; every feed hands back the six CORR_FIELDS of its records and the piece with the
+    corrected bytes patched in.  Creating one touches no device; set_tables brings it up."""
+
+    def __init__(self, kmer_len: int, device: int = 0):
+        self._h = ctypes.c_void_p()
+        self.kmer_len, self.device = int(kmer_len), device
+        _check(load().pk_correct_create(ctypes.byref(self._h), int(kmer_len), device))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            load().pk_correct_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_tables(self, dev_ptrs, min_count: int = 1, max_count: int = 255):
+        """pk_correct_set_tables: device pointers of 4^k-byte tables (at most 16), owned by the caller until the last feed."""
+        _check(load().pk_correct_set_tables(self._h, _ptr_array(dev_ptrs), len(dev_ptrs), int(min_count), int(max_count)))
+
+    def set_cover(self, cover, n_bases: int, min_qual_byte: int = 0, min_windows: int = None):
+        """pk_correct_set_cover: `cover` packed as QueryIndexer.cover returns it, for n_bases bases (copied); min_qual_byte as for
+        Trimmer.set_cover; min_windows: None = (kmer_len + 1) // 2.  ValueError for bits of another length."""
+        bits = np.ascontiguousarray(cover, dtype=np.uint8)
+        if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
+            raise ValueError(f"{int(n_bases)} bases take {(int(n_bases) + 7) // 8} bytes of cover bits, got an array of shape {bits.shape}")
+        M = (self.kmer_len + 1) // 2 if min_windows is None else int(min_windows)
+        _check(load().pk_correct_set_cover(self._h, bits.ctypes.data if bits.size else None, int(n_bases), int(min_qual_byte), M))
+
+    @staticmethod
+    def _offsets(starts):
+        """(the offsets as the library takes them, room for the fields of their records)"""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        if starts.ndim != 1 or starts.size < 1:
+            raise ValueError(f"R records need R + 1 offsets, got an array of shape {starts.shape}")
+        return starts, np.zeros((len(CORR_FIELDS), max(1, starts.size - 1)), dtype=np.uint64)
+
+    @staticmethod
+    def _fields(out, n_records: int) -> dict:
+        flat = out.reshape(-1)[:len(CORR_FIELDS) * n_records].reshape(len(CORR_FIELDS), n_records)
+        return {name: flat[f].copy() for f, name in enumerate(CORR_FIELDS)}
+
+    def feed(self, data, starts):
+        """pk_correct_feed: the next piece of the stream, whole records cut by `starts` (R + 1,) offsets relative to the piece
+        with starts[R] = its length -> (dict of the CORR_FIELDS, (R,) uint64 each; the corrected piece, (n_bytes,) uint8)."""
+        buf = _as_u8(data)
+        starts, out = self._offsets(starts)
+        text_out = np.empty(max(1, buf.size), dtype=np.uint8)
+        _check(load().pk_correct_feed(self._h, buf.ctypes.data if buf.size else None, buf.size, starts.ctypes.data, starts.size - 1,
+                                      text_out.ctypes.data, out.ctypes.data))
+        return self._fields(out, starts.size - 1), text_out[:buf.size]
+
+    def feed_device(self, dev_ptr: int, n_bytes: int, starts, dev_out_ptr: int) -> dict:
+        """pk_correct_feed_device: the same with the next n_bytes of the stream at dev_ptr and the corrected piece written to
+        dev_out_ptr (HBM, any alignment, not overlapping) -> dict of the CORR_FIELDS."""
+        starts, out = self._offsets(starts)
+        _check(load().pk_correct_feed_device(self._h, ctypes.c_void_p(dev_ptr) if dev_ptr else None, int(n_bytes), starts.ctypes.data, starts.size - 1,
+                                             ctypes.c_void_p(dev_out_ptr) if dev_out_ptr else None, out.ctypes.data))
+        return self._fields(out, starts.size - 1)
+
+    def finish(self) -> dict:
+        """pk_correct_finish: n_records, n_bases (the valid bases seen) and the four totals; PkError (PK_ERR_STATE) if the stream
+        does not hold the valid bases the cover bits were made for."""
+        out = np.zeros(6, dtype=np.uint64)
+        _check(load().pk_correct_finish(self._h, out.ctypes.data))
+        return {"n_records": int(out[0]), "n_bases": int(out[1]), "n_candidates": int(out[2]), "n_untried": int(out[3]), "n_corrected": int(out[4]),
+                "n_ambiguous": int(out[5])}
+
+    def timings(self) -> dict:
+        """pk_correct_timings: the HIP-event seconds of the correct kernels so far, and the feeds."""
+        out = np.zeros(2, dtype=np.float64)
+        _check(load().pk_correct_timings(self._h, out.ctypes.data))
+        return {"correct_s": float(out[0]), "feeds": int(out[1])}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

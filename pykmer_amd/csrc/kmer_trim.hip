@@ -16,62 +16,15 @@
 //                 later run replaces only when it is strictly longer, so the smallest start wins a tie
 // Positions are those of query.py --coords on the FASTA text the FASTQ stands for: a record's line 2 is its one sequence
 // line, position 0 is its first non-blank byte, and every byte up to its last non-blank one holds a position.
-#include "kmer_pieces.h"
+// The guarded loads, the line search and the ballot of valid bases live in kmer_trim.h, which kmer_correct.hip shares; its
+// walker runs behind k_trim_count and k_trim_scan (launch_trim_geometry).
+#include "kmer_trim.h"
 #include "wg_scan.h"
 
 namespace pk {
 
-constexpr int TRIM_WAVES = WG / 64;              // records per workgroup and round
 constexpr int TRIM_SCAN_T = 1024;                // threads of the scan
 constexpr int TRIM_SCAN_PER = 4;                 // consecutive records per thread and round
-constexpr uint32_t TRIM_MAX_WGS = 8192;
-constexpr int TRIM_STEPS = 4;                    // 64-byte steps whose loads are in flight together: the walks wait for memory, not for arithmetic
-constexpr uint32_t TRIM_ROUND = 64u * TRIM_STEPS;
-
-// TRIM_STEPS steps of text[q ..) below `end`, one byte per lane and step; a byte the range does not have reads as `fill`
-__device__ __forceinline__ void trim_load(const uint8_t *__restrict__ text, uint64_t q, uint64_t end, uint32_t lane, uint32_t fill,
-                                          uint32_t (&c)[TRIM_STEPS]) {
-#pragma unroll
-    for (int j = 0; j < TRIM_STEPS; j++) {
-        const uint64_t i = q + 64u * (uint32_t)j + lane;
-        c[j] = i < end ? (uint32_t)text[i] : fill;
-    }
-}
-
-// the first line terminator of text[from, end), or end.  The whole wave calls it; the answer is uniform.
-__device__ __forceinline__ uint64_t trim_line_end(const uint8_t *__restrict__ text, uint64_t from, uint64_t end, uint32_t lane) {
-    for (uint64_t q = from; q < end; q += TRIM_ROUND) {
-        uint32_t c[TRIM_STEPS];
-        trim_load(text, q, end, lane, 0u, c);
-#pragma unroll
-        for (int j = 0; j < TRIM_STEPS; j++) {
-            const unsigned long long m = __ballot(is_term(c[j]));
-            if (m) return q + 64u * (uint32_t)j + (uint64_t)__builtin_ctzll(m);
-        }
-    }
-    return end;
-}
-
-// where the line behind the terminator at `at` begins: \n, \r\n and a lone \r end a line (at == end: no terminator, no line)
-__device__ __forceinline__ uint64_t trim_next_line(const uint8_t *__restrict__ text, uint64_t at, uint64_t end) {
-    if (at >= end) return end;
-    return at + ((text[at] == 13u && at + 1u < end && text[at + 1u] == 10u) ? 2u : 1u);
-}
-
-// The bytes of line 4 at the offsets of the TRIM_STEPS steps of line 2 at i2 (line 2 ends at e2; i4: the offset of line 4 that
-// goes with i2, line 4 ends at e4).  Without a threshold nothing is loaded; a byte that line 4 does not have passes none.
-__device__ __forceinline__ void trim_load_qual(const uint8_t *__restrict__ text, uint64_t i2, uint64_t e2, uint64_t i4, uint64_t e4, uint32_t lane,
-                                               uint32_t tq, uint32_t (&qv)[TRIM_STEPS]) {
-#pragma unroll
-    for (int j = 0; j < TRIM_STEPS; j++) {
-        const uint64_t d = 64u * (uint32_t)j + lane;
-        qv[j] = (tq && i2 + d < e2 && i4 + d < e4) ? (uint32_t)text[i4 + d] : 0u;
-    }
-}
-// the valid bases of one step: bit = lane.  c: the byte of line 2 (a blank where the line has none), qv: that of line 4.
-__device__ __forceinline__ unsigned long long trim_valid(uint32_t c, uint32_t qv, uint32_t tq) {
-    return __ballot(base_code(c) < 4u && (!tq || qv >= tq));
-}
 
 // Per record r of the feed (text[0 .. n) at stream offset pos): geo + f * R + r for the fields f below, and cnt[r] = its
 // valid bases.  Stream offsets throughout.
@@ -186,15 +139,23 @@ __global__ __launch_bounds__(WG) void k_trim_runs(const uint8_t *__restrict__ te
     }
 }
 
+static uint32_t trim_workgroups(uint64_t R) {
+    const uint64_t want = (R + TRIM_WAVES - 1u) / TRIM_WAVES;
+    return (uint32_t)(want < TRIM_MAX_WGS ? want : TRIM_MAX_WGS);
+}
+
+void launch_trim_geometry(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, unsigned long long base,
+                          unsigned long long *cnt, unsigned long long *total, unsigned long long *geo, hipStream_t s) {
+    hipLaunchKernelGGL(k_trim_count, dim3(trim_workgroups(R)), dim3(WG), 0, s, text, starts, R, pos, tq, geo, cnt);
+    hipLaunchKernelGGL(k_trim_scan, dim3(1), dim3(TRIM_SCAN_T), 0, s, cnt, R, base, total);
+}
+
 int launch_trim(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, const uint32_t *bits,
                 uint64_t n_words, unsigned long long base, unsigned long long *cnt, unsigned long long *total, unsigned long long *geo,
                 hipStream_t s) {
     if (!R) return 0;
-    const uint64_t want = (R + TRIM_WAVES - 1u) / TRIM_WAVES;
-    const uint32_t wgs = (uint32_t)(want < TRIM_MAX_WGS ? want : TRIM_MAX_WGS);
-    hipLaunchKernelGGL(k_trim_count, dim3(wgs), dim3(WG), 0, s, text, starts, R, pos, tq, geo, cnt);
-    hipLaunchKernelGGL(k_trim_scan, dim3(1), dim3(TRIM_SCAN_T), 0, s, cnt, R, base, total);
-    hipLaunchKernelGGL(k_trim_runs, dim3(wgs), dim3(WG), 0, s, text, R, pos, tq, (const unsigned long long *)cnt, bits,
+    launch_trim_geometry(text, starts, R, pos, tq, base, cnt, total, geo, s);
+    hipLaunchKernelGGL(k_trim_runs, dim3(trim_workgroups(R)), dim3(WG), 0, s, text, R, pos, tq, (const unsigned long long *)cnt, bits,
                        (unsigned long long)n_words, geo);
     return hipGetLastError() != hipSuccess;
 }

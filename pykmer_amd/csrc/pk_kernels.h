@@ -307,5 +307,20 @@ constexpr uint32_t TRIM_FIELDS = 9;   // pos2, pos4, end2, end4, seq_len, trim_s
 int launch_trim(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, const uint32_t *bits,
                 uint64_t n_words, unsigned long long base, unsigned long long *cnt, unsigned long long *total, unsigned long long *geo,
                 hipStream_t s);
+// the first two kernels of launch_trim alone (R > 0): geo fields pos2, pos4, end2, end4, seq_len and lead, cnt and *total
+void launch_trim_geometry(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, unsigned long long base,
+                          unsigned long long *cnt, unsigned long long *total, unsigned long long *geo, hipStream_t s);
+
+// kmer_correct.hip -- single-base corrections of every record of a FASTQ feed.  text .. geo as launch_trim
+// takes them (geo: TRIM_FIELDS * R words of scratch, of which the geometry fields are written).  tables[0 .. n_tab), n_tab <=
+// QUERY_MAX_TABLES: device tables of 4^k bytes; a window matches iff min_count <= T[a] <= max_count in one of them.
+// min_windows: a candidate with fewer windows is not tried.  text_out[0 .. n): a copy of text made by the caller on the same
+// stream (it may not overlap text); the corrected bytes are patched into it.  out: CORR_FIELDS * R words, field f of record r
+// at out[f * R + r].  R = 0: nothing is launched.
+constexpr uint32_t CORR_FIELDS = 6;   // pos2, seq_len, candidates, untried, corrected, ambiguous
+int launch_correct(const uint8_t *text, const unsigned long long *starts, uint64_t R, uint64_t pos, uint32_t tq, const uint32_t *bits,
+                   uint64_t n_words, unsigned long long base, unsigned long long *cnt, unsigned long long *total, unsigned long long *geo,
+                   uint32_t k, const uint8_t *const *tables, uint32_t n_tab, uint32_t min_count, uint32_t max_count, uint32_t min_windows,
+                   uint8_t *text_out, unsigned long long *out, hipStream_t s);
 
 }  // namespace pk

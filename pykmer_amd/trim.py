@@ -93,44 +93,73 @@ def cover_bits(reads_file: str, tables: Sequence, min_count: int = 1, max_count:
     return result
 
 
-def trim_runs(reads_file: str, cover, n_bases: int, starts, min_qual: int = 0, qual_offset: int = 33, device: int = 0) -> dict:
-    """The kept run of every record of `reads_file` under the cover bits `cover` (packed as cover_bits returns them, for
-    n_bases bases; the bits may come from anywhere).  `starts`: (R + 1,) record offsets (filter.record_starts).  The stream is
-    re-cut at record offsets, the tail of a piece carried into the next.  Returns dict of the nine _lib.TRIM_FIELDS, (R,) uint64
-    each, and n_records, n_covered, trim_s.  ValueError if a single record is longer than one feed, if `cover` does not hold
-    n_bases bits or the file does not hold n_bases valid bases."""
-    check_fastq(reads_file)
-    bits = np.ascontiguousarray(cover, dtype=np.uint8)
-    if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
-        raise ValueError(f"{int(n_bases)} bases take {(int(n_bases) + 7) // 8} bytes of cover bits, got an array of shape {bits.shape}")
-    starts = np.ascontiguousarray(starts, dtype=np.uint64)
-    R = starts.size - 1
-    if starts.ndim != 1 or R < 0 or (R and int(starts[0]) != 0):
-        raise ValueError(f"{reads_file}: the record offsets of a FASTQ stream begin at 0 and end with its length")
-    tq = qual_threshold(str(reads_file), min_qual, qual_offset) if min_qual else 0
-    block = min(TRIM_FEED, max(1 << 16, int(os.environ.get("PK_FEED_PIECE", TRIM_FEED))))
-    src = _Input(reads_file, keep=False, quiet=True)
-    parts = []
-    with _lib.Trimmer(device) as t:
-        t.set_cover(bits, n_bases, tq)
+class RecordFeeds:
+    """The second pass over a FASTQ stream whose record offsets are known: iterating yields (piece, offsets) -- consecutive
+    pieces of the stream, each the whole records of at most one block and of the tail carried from the block before, with
+    the (n + 1,) offsets of its n records relative to the piece.  The bytes behind the last record (blank lines at most) come
+    as pieces without a record, offsets = [their length].  `starts`: (R + 1,) record offsets (filter.record_starts).
+    ValueError if a single record is longer than one block; check(), after the loop, raises it if the stream is not the one
+    the offsets were found in."""
+
+    def __init__(self, reads_file: str, starts):
+        self.reads_file = reads_file
+        self.starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        self.R = self.starts.size - 1
+        if self.starts.ndim != 1 or self.R < 0 or (self.R and int(self.starts[0]) != 0):
+            raise ValueError(f"{reads_file}: the record offsets of a FASTQ stream begin at 0 and end with its length")
+        self.block = min(TRIM_FEED, max(1 << 16, int(os.environ.get("PK_FEED_PIECE", TRIM_FEED))))
+        self.pos, self.r, self.held = 0, 0, 0            # the stream offset of the carried tail = starts[r], the next record; its bytes
+
+    def __iter__(self):
+        starts, R, block = self.starts, self.R, self.block
+        src = _Input(self.reads_file, keep=False, quiet=True)
         tail = np.zeros(0, dtype=np.uint8)
-        pos, r = 0, 0                                        # the stream offset of tail[0] = starts[r], the next record
         for piece in src.pieces():
             view = np.frombuffer(piece, dtype=np.uint8)
             for off in range(0, view.size, block):
                 buf = np.concatenate([tail, view[off:off + block]]) if tail.size else view[off:off + block]
-                if r == R:                                   # behind the last record (a stream of blank lines has none): no feed
-                    tail, pos = tail[:0], pos + buf.size
+                if self.r == R:                              # behind the last record (a stream of blank lines has none)
+                    tail, self.held = tail[:0], 0
+                    yield buf, np.array([buf.size], dtype=np.uint64)
+                    self.pos += buf.size
                     continue
-                hi = int(np.searchsorted(starts, pos + buf.size, side="right")) - 1   # records r .. hi - 1 lie whole in buf
-                if hi <= r:
+                hi = int(np.searchsorted(starts, self.pos + buf.size, side="right")) - 1   # records r .. hi - 1 lie whole in buf
+                if hi <= self.r:
                     if buf.size > block:
-                        raise ValueError(f"{reads_file}: record {r + 1} is longer than one feed of {block:,d} bytes")
+                        raise ValueError(f"{self.reads_file}: record {self.r + 1} is longer than one feed of {block:,d} bytes")
                     tail = np.array(buf)
+                    self.held = tail.size
                     continue
-                cut = int(starts[hi]) - pos
-                parts.append(t.feed(buf[:cut], starts[r:hi + 1] - np.uint64(pos)))
-                tail, pos, r = np.array(buf[cut:]), pos + cut, hi
+                cut = int(starts[hi]) - self.pos
+                tail = np.array(buf[cut:])
+                self.held = tail.size
+                yield buf[:cut], starts[self.r:hi + 1] - np.uint64(self.pos)
+                self.pos, self.r = self.pos + cut, hi
+
+    def check(self) -> None:
+        if self.r != self.R or self.held or self.pos != int(self.starts[-1]):
+            raise ValueError(f"{self.reads_file} changed between the passes: {self.pos + self.held} bytes now, {int(self.starts[-1])} when its records "
+                             f"were found")
+
+
+def trim_runs(reads_file: str, cover, n_bases: int, starts, min_qual: int = 0, qual_offset: int = 33, device: int = 0) -> dict:
+    """The kept run of every record of `reads_file` under the cover bits `cover` (packed as cover_bits returns them, for
+    n_bases bases; the bits may come from anywhere).  `starts`: (R + 1,) record offsets (filter.record_starts).  The stream is
+    re-cut at record offsets, the tail of a piece carried into the next (RecordFeeds).  Returns dict of the nine
+    _lib.TRIM_FIELDS, (R,) uint64 each, and n_records, n_covered, trim_s.  ValueError if a single record is longer than one
+    feed, if `cover` does not hold n_bases bits or the file does not hold n_bases valid bases."""
+    check_fastq(reads_file)
+    bits = np.ascontiguousarray(cover, dtype=np.uint8)
+    if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
+        raise ValueError(f"{int(n_bases)} bases take {(int(n_bases) + 7) // 8} bytes of cover bits, got an array of shape {bits.shape}")
+    feeds = RecordFeeds(reads_file, starts)
+    tq = qual_threshold(str(reads_file), min_qual, qual_offset) if min_qual else 0
+    parts = []
+    with _lib.Trimmer(device) as t:
+        t.set_cover(bits, n_bases, tq)
+        for piece, offsets in feeds:
+            if offsets.size > 1:                             # the bytes behind the last record: no feed
+                parts.append(t.feed(piece, offsets))
         try:
             fin = t.finish()
         except _lib.PkError as exc:
@@ -138,8 +167,7 @@ def trim_runs(reads_file: str, cover, n_bases: int, starts, min_qual: int = 0, q
                 raise
             raise ValueError(f"{reads_file}: {exc}") from exc
         trim_s = t.timings()["trim_s"]
-    if r != R or tail.size or pos != int(starts[-1]):
-        raise ValueError(f"{reads_file} changed between the passes: {pos + tail.size} bytes now, {int(starts[-1])} when its records were found")
+    feeds.check()
     out = {name: np.concatenate([p[name] for p in parts]) if parts else np.zeros(0, dtype=np.uint64) for name in _lib.TRIM_FIELDS}
     out.update(n_records=fin["n_records"], n_covered=fin["n_covered"], trim_s=trim_s)
     return out
