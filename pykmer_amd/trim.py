@@ -98,8 +98,9 @@ class RecordFeeds:
     pieces of the stream, each the whole records of at most one block and of the tail carried from the block before, with
     the (n + 1,) offsets of its n records relative to the piece.  The bytes behind the last record (blank lines at most) come
     as pieces without a record, offsets = [their length].  `starts`: (R + 1,) record offsets (filter.record_starts).
-    ValueError if a single record is longer than one block; check(), after the loop, raises it if the stream is not the one
-    the offsets were found in."""
+    A record that ends in the block in which it begins or in the one behind it is fed whole, so a record of up to about two
+    blocks is; ValueError when the carried tail and one further block still do not hold its end.  check(), after the loop,
+    raises it if the stream is not the one the offsets were found in."""
 
     def __init__(self, reads_file: str, starts):
         self.reads_file = reads_file
@@ -146,8 +147,9 @@ def trim_runs(reads_file: str, cover, n_bases: int, starts, min_qual: int = 0, q
     """The kept run of every record of `reads_file` under the cover bits `cover` (packed as cover_bits returns them, for
     n_bases bases; the bits may come from anywhere).  `starts`: (R + 1,) record offsets (filter.record_starts).  The stream is
     re-cut at record offsets, the tail of a piece carried into the next (RecordFeeds).  Returns dict of the nine
-    _lib.TRIM_FIELDS, (R,) uint64 each, and n_records, n_covered, trim_s.  ValueError if a single record is longer than one
-    feed, if `cover` does not hold n_bases bits or the file does not hold n_bases valid bases."""
+    _lib.TRIM_FIELDS, (R,) uint64 each, and n_records, n_covered, trim_s.  ValueError if the carried tail and one further block of
+    TRIM_FEED bytes do not hold the end of a record (one of up to about two blocks is fed whole), if `cover` does not hold
+    n_bases bits or the file does not hold n_bases valid bases."""
     check_fastq(reads_file)
     bits = np.ascontiguousarray(cover, dtype=np.uint8)
     if bits.ndim != 1 or bits.size != (int(n_bases) + 7) // 8:
