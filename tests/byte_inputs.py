@@ -295,3 +295,35 @@ def placement_fastq(crlf: bool) -> bytes:
     text = b"".join(out)
     assert len(text) < 1_000_000
     return text
+
+
+WALKER_AT = (10, 63, 64, 130)                # positions of a read: inside step 0, on either side of the first step seam, in step 2
+WALKER_LEN = 200
+
+
+@functools.lru_cache(maxsize=None)
+def walker_fastq(genome: bytes = None) -> bytes:
+    """Reads of 200 positions for the record walkers (kmer_trim.hip, kmer_correct.hip), whose steps are 64 positions: per
+    value except 10 and 13 one read with the value at positions 10 and 64 of line 2, one with it at 63 and 130, and one
+    with it at all four offsets of line 4 -- '>' too, which cannot lead line 2 but may stand inside it.  The other bases
+    are cut from `genome` (random without one) with a substitution next to every placement, so that the value's neighbours
+    are candidates of a correction; the other qualities are 50 .. 73, one in eight below the threshold byte 53."""
+    rng = np.random.default_rng(940)
+    source = np.frombuffer(genome, dtype=np.uint8) if genome else BASES[rng.integers(0, 4, 4000)]
+    assert source.size >= WALKER_LEN
+    out = []
+    for b in range(256):
+        if b in (10, 13):
+            continue
+        for where, in_qual in (((10, 64), False), ((63, 130), False), (WALKER_AT, True)):
+            at = int(rng.integers(0, source.size - WALKER_LEN + 1))
+            seq = source[at:at + WALKER_LEN].copy()
+            qual = rng.integers(50, 74, WALKER_LEN).astype(np.uint8)
+            for p in where:
+                for near in (p - 2, p + 3):                  # a wrong base on either side, within reach of any k >= 5
+                    seq[near] = BASES[(int(np.flatnonzero(BASES == (seq[near] & 0xDF))[0]) + 1 + int(rng.integers(0, 3))) % 4] | (seq[near] & 0x20)
+                (qual if in_qual else seq)[p] = b
+            out.append(b"@w%d %d\n" % (b, where[0]) + seq.tobytes() + b"\n+\n" + qual.tobytes() + b"\n")
+    text = b"".join(out)
+    assert len(text) < 1_000_000
+    return text

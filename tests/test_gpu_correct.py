@@ -1,7 +1,8 @@
 """GPU: the correct path -- the Corrector (kmer_correct.hip, pk_correct_*) against correct_ref with exact equality of the six
 fields, the patched bytes and the totals: small dense tables at k = 5 and 7, whole and cut into feeds, host and device forms,
-the threshold, bits from anywhere, the u32 and u64 instantiations at k = 15 and 17 on tables counted on the GPU, the guards,
-and correct.py end to end as a child process.  tests/test_correct_host.py holds correct_ref against hand-worked records and
+the threshold, bits from anywhere, the u32 and u64 instantiations at k = 15 and 17 on tables counted on the GPU -- planted
+errors, and seam_inputs' enumeration of every candidate around the first step seam -- sixteen tables, the guards, and
+correct.py end to end as a child process.  tests/test_correct_host.py holds correct_ref against hand-worked records and
 asserts on the CPU that the inputs used here reach every outcome class and the seams of the kernel's 64-position steps."""
 import contextlib
 import functools
@@ -20,6 +21,7 @@ import gpu_support as gs
 import mask_ref
 import oracle
 import query_ref
+import seam_inputs
 import trim_inputs
 import trim_ref
 from gpu_support import Device, SentinelOut, lib, run_py, stream
@@ -195,6 +197,49 @@ def test_counted_tables_and_planted_errors(request, k):
             c.set_cover(want["bits"], want["n_bases"], 0, M)
             _same(*_feed_all(c, fq, starts, 400), want)
             assert c.finish() == correct_ref.totals(want)
+
+
+@pytest.mark.parametrize("k", [15, 17])
+def test_counted_tables_at_the_first_step_seam(request, k):
+    """seam_inputs.correct_cases on the u32 kernel's widest k and on the u64 kernel: every candidate position around position
+    64 with every distance to an N below and above it, reads cut from the first counted source."""
+    at_k = request.getfixturevalue(f"k{k}")
+    fq, cover, cases = seam_inputs.correct_cases(k, 64, query_ref.sequence(at_k.sources[0]), "N", seed=1900 + k)
+    starts = trim_ref.starts(fq)
+    assert len(starts) - 1 == len(cases) == (2 * k + 2) * (k + 1) ** 2
+    want = correct_ref.expected(fq, k, at_k.sparse, M=1, cover=cover)       # M = 1: every window count 1 .. k is tried, 3 k lanes at the most
+    assert np.array_equal(want["candidates"], np.array([seam_inputs.is_candidate(k, a, b) for _, a, b in cases], dtype=np.uint64))
+    assert int(want["untried"].sum()) == 0 and int(want["corrected"].sum()) >= 0.9 * int(want["candidates"].sum())
+    with lib().Corrector(k, 0) as c:
+        c.set_tables(at_k.ptrs, 1, 255)
+        c.set_cover(mask_ref.pack(cover), int(cover.size), 0, 1)
+        _same(*_feed_all(c, fq, starts, 1000), want)
+        assert c.finish() == correct_ref.totals(want)
+
+
+# ------------------------------------------------------------------ sixteen tables: the limit of one correction
+def test_sixteen_tables_each_with_a_sixteenth_of_the_kmers(gpu):
+    """A candidate's windows match in different tables, some in the sixteenth only: the gather loop runs to its last table."""
+    k = 5
+    tabs, _ = seam_inputs.sixteen_tables(k)
+    fq = seam_inputs.sixteen_stream(k)
+    starts = trim_ref.starts(fq)
+    assert len(tabs) == 16
+    with Device(tabs) as dev:
+        for M in (1, None):
+            want = correct_ref.expected(fq, k, tabs, M=M)
+            less = correct_ref.expected(fq, k, tabs[:-1], M=M)
+            assert int(want["corrected"].sum()) >= 10 and want["patched"] != less["patched"]     # the last table changes the result
+            for per in (None, 7):
+                with lib().Corrector(k, 0) as c:
+                    c.set_tables(dev.ptrs, 1, 255)
+                    c.set_cover(want["bits"], want["n_bases"], 0, M)
+                    _same(*_feed_all(c, fq, starts, per), want)
+                    assert c.finish() == correct_ref.totals(want)
+            with lib().QueryIndexer(k, device=0, fmt="fastq") as q:       # the lookup's bits over the same sixteen
+                q.set_tables(dev.ptrs, 1, 255)
+                cover = stream(q, fq, cover=True, reset=False)
+            assert cover["n_bases"] == want["n_bases"] and np.array_equal(cover["bits"], want["bits"])
 
 
 # ------------------------------------------------------------------ guards
