@@ -518,6 +518,49 @@ int pk_correct_finish(pk_correct *c, uint64_t totals_out[6]);
 int pk_correct_timings(pk_correct *c, double out[2]);
 void pk_correct_destroy(pk_correct *c);
 
+/* ---- unitigs: the compacted de Bruijn graph of ONE table, spelled as FASTA on the device (no reference counterpart: the
+ * BCALM step behind a k-mer count).  Input: one table T of 4^k bytes, k odd, 1 <= k <= 17, and a count window
+ * 1 <= min <= max <= 255.
+ * NODE: a canonical address x with min <= T[x] <= max; S is the node set, n_nodes = |S|.
+ * ORIENTED K-MER: any value o in [0, 4^k), codes A,C,G,T = 0..3, first base in the highest bits; rc(o) is its reverse
+ * complement and canon(o) = min(o, rc(o)); k is odd, so o != rc(o) always.
+ * EDGES: out(o) = { t = ((o << 2) | b) & (4^k - 1), b = 0..3 : canon(t) in S } and in(t) = { rc(u) : u in out(rc(t)) }.  Edges
+ * are counted as strings: two successors that are each other's reverse complement count as two.
+ * COMPACTABLE EDGE: o -> t is compactable iff |out(o)| = 1, |in(t)| = 1 and canon(o) != canon(t).  Self-loops such as poly-A,
+ * and hairpins o -> rc(o), count in the degrees but are never compacted.  Compactable edges are symmetric (o -> t iff
+ * rc(t) -> rc(o)), so they form a matching on (node, side), and every component is a simple path or a simple cycle that
+ * meets each node once.
+ * UNITIG: a maximal sequence o_1 -> ... -> o_n of compactable edges, n >= 1; every node lies in exactly one.  Its text is
+ * the k letters of o_1 followed by the last letter of each o_i, i >= 2; its length is L = n + k - 1.
+ * ORIENTATION AND ORDER: a linear unitig with n >= 2 has two different end nodes; it is spelled starting from the end node
+ * with the smaller canonical address, leaving that node towards the rest, and first_addr is that address.  A single node is
+ * spelled as its canonical k-mer, first_addr = x.  A cycle (circular = 1) starts at its smallest canonical address x_min,
+ * spelled forward from the canonical string of x_min, and stops before returning to it: the text is linear, n + k - 1
+ * letters, its last k - 1 letters overlap its start; first_addr = x_min.  The rows are all linear unitigs by ascending
+ * first_addr, then all circular ones by ascending first_addr.
+ * PER UNITIG: n_kmers = n, depth = the sum of T[x] over its nodes (u64), circular.
+ * min_kmers M >= 1: unitigs with n_kmers < M are not written and get no row; n_short counts them and nodes_short their
+ * nodes.  Row indices are those of the written rows.  A BRANCHING node has |out(o)| >= 2 for o = x or o = rc(x).
+ * The FASTA text is, per row in row order, `>` + the row index in decimal + `\n` + the text + `\n`.
+ * pk_unitig_create touches no device; k odd and at most 17, PK_ERR_ARG otherwise.
+ * pk_unitig_build: dev_table is 4^k bytes on the builder's device, 16-byte aligned, owned by the caller and not changed; a
+ * window or an M out of range is PK_ERR_ARG.  The library owns the link array (4^k bytes), the rows and the text; the rows and
+ * the text are sized from what the passes count, and where they do not fit the device the call is PK_ERR_RECS_CAP with a
+ * message that names the size.  Every walk carries a step bound that a correct walk cannot reach; PK_ERR_STATE if one is
+ * reached.  totals_out = { nodes, branching nodes, linear rows, circular rows, n_short, nodes_short, FASTA bytes, the
+ * largest n_kmers of a row }.  A builder may build again; the results are those of the last build.
+ * pk_unitig_rows: the four row arrays, U = linear + circular rows each; PK_ERR_RECS_CAP if cap < U, PK_ERR_STATE before a
+ * build.  pk_unitig_text: bytes [offset, offset + n_bytes) of the FASTA text; PK_ERR_ARG outside it.
+ * pk_unitig_timings: out = { seconds of the link pass, of the linear phase (ends, measure, spell), of the circular phase --
+ * HIP events on the builder's stream, the copies and allocations outside them --, builds (as a double) }. */
+typedef struct pk_unitig pk_unitig;
+int pk_unitig_create(pk_unitig **out, int k, int device);
+int pk_unitig_build(pk_unitig *u, const void *dev_table, int min_count, int max_count, uint64_t min_kmers, uint64_t totals_out[8]);
+int pk_unitig_rows(pk_unitig *u, uint64_t *first_addr, uint64_t *n_kmers, uint64_t *depth, uint8_t *circular, uint64_t cap);
+int pk_unitig_text(pk_unitig *u, uint8_t *host_out, uint64_t offset, uint64_t n_bytes);
+int pk_unitig_timings(pk_unitig *u, double out[4]);
+void pk_unitig_destroy(pk_unitig *u);
+
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one
  * Python gzip.open stream (tools.py:294-305, indexer.py:112-115); bgzip output (README.md:26) is a series of independent
  * gzip members, inflated here block-parallel on native threads straight into the caller's buffer.

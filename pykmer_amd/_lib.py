@@ -116,6 +116,12 @@ _SIGNATURES = {
     "pk_correct_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_correct_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_correct_destroy": (None, [ctypes.c_void_p]),
+    "pk_unitig_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
+    "pk_unitig_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]),
+    "pk_unitig_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_unitig_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "pk_unitig_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_unitig_destroy": (None, [ctypes.c_void_p]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_int]),
@@ -720,6 +726,63 @@ class Corrector:
         out = np.zeros(2, dtype=np.float64)
         _check(load().pk_correct_timings(self._h, out.ctypes.data))
         return {"correct_s": float(out[0]), "feeds": int(out[1])}
+
+
+UNITIG_TOTALS = ("n_nodes", "n_branching", "n_linear", "n_circular", "n_short", "nodes_short", "bytes", "longest_kmers")
+
+
+class Unitigs:
+    """The unitigs of one table in HBM (pk_unitig_*): build once per table and window, then read the rows and any slice of
+    the FASTA text.  Creating one touches no device; ValueError for an even kmer_len or one above 17."""
+
+    def __init__(self, kmer_len: int, device: int = 0):
+        self._h = ctypes.c_void_p()
+        self.k, self.device = int(kmer_len), device
+        _check(load().pk_unitig_create(ctypes.byref(self._h), int(kmer_len), device))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            load().pk_unitig_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def build(self, dev_table: int, min_count: int = 1, max_count: int = 255, min_kmers: int = 1) -> dict:
+        """pk_unitig_build on the 4^k bytes at dev_table: the UNITIG_TOTALS.  PkError (PK_ERR_STATE) if a walk met its step
+        bound, (PK_ERR_RECS_CAP) if the rows or the text do not fit the device."""
+        if int(min_kmers) < 1:
+            raise ValueError(f"min_kmers must be at least 1, got {min_kmers}")
+        out = np.zeros(8, dtype=np.uint64)
+        _check(load().pk_unitig_build(self._h, ctypes.c_void_p(dev_table), int(min_count), int(max_count), int(min_kmers), out.ctypes.data))
+        self.totals = {name: int(v) for name, v in zip(UNITIG_TOTALS, out)}
+        return dict(self.totals)
+
+    def rows(self) -> dict:
+        """pk_unitig_rows: first_addr, n_kmers, depth (U,) uint64 and circular (U,) uint8, linear rows first."""
+        U = self.totals["n_linear"] + self.totals["n_circular"]
+        out = {"first_addr": np.zeros(U, dtype=np.uint64), "n_kmers": np.zeros(U, dtype=np.uint64), "depth": np.zeros(U, dtype=np.uint64),
+               "circular": np.zeros(U, dtype=np.uint8)}
+        _check(load().pk_unitig_rows(self._h, *(out[key].ctypes.data if U else None for key in ("first_addr", "n_kmers", "depth", "circular")), U))
+        return out
+
+    def text(self, offset: int = 0, n_bytes: int = None) -> np.ndarray:
+        """pk_unitig_text: bytes [offset, offset + n_bytes) of the FASTA text (to its end by default), uint8."""
+        n = self.totals["bytes"] - int(offset) if n_bytes is None else int(n_bytes)
+        out = np.empty(max(0, n), dtype=np.uint8)
+        _check(load().pk_unitig_text(self._h, out.ctypes.data if out.size else None, int(offset), n))
+        return out
+
+    def timings(self) -> dict:
+        """pk_unitig_timings: the HIP-event seconds of the link pass, the linear and the circular phase, and the builds."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(load().pk_unitig_timings(self._h, out.ctypes.data))
+        return {"links_s": float(out[0]), "paths_s": float(out[1]), "cycles_s": float(out[2]), "builds": int(out[3])}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

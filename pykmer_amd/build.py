@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libpykmer_hip.so")
-SOURCES = ["kmer_count.hip", "kmer_pack.hip", "kmer_fuse.hip", "kmer_part.hip", "kmer_query.hip", "kmer_coords.hip", "kmer_cover.hip", "kmer_intervals.hip", "kmer_extract.hip", "kmer_select.hip", "kmer_trim.hip", "kmer_correct.hip", "gram_scan.hip", "gram_spectrum.hip", "gram_occ.hip", "gram_patterns.hip", "fastq.hip", "pk_common.hip", "pk_indexer.hip", "pk_query.hip", "pk_select.hip", "pk_trim.hip", "pk_correct.hip", "pk_merge.hip", "bgzf_host.cpp"]   # the .cpp is host-only (zlib)
+SOURCES = ["kmer_count.hip", "kmer_pack.hip", "kmer_fuse.hip", "kmer_part.hip", "kmer_query.hip", "kmer_coords.hip", "kmer_cover.hip", "kmer_intervals.hip", "kmer_extract.hip", "kmer_select.hip", "kmer_trim.hip", "kmer_correct.hip", "kmer_unitig.hip", "gram_scan.hip", "gram_spectrum.hip", "gram_occ.hip", "gram_patterns.hip", "fastq.hip", "pk_common.hip", "pk_indexer.hip", "pk_query.hip", "pk_select.hip", "pk_trim.hip", "pk_correct.hip", "pk_unitig.hip", "pk_merge.hip", "bgzf_host.cpp"]   # the .cpp is host-only (zlib)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 

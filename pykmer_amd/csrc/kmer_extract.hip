@@ -256,6 +256,11 @@ __global__ __launch_bounds__(XT) void k_extract_text(const unsigned long long *_
 uint32_t extract_workgroups(uint64_t n_slice) { return (uint32_t)((n_slice + X_WG - 1) / X_WG); }
 uint64_t extract_mask_words(uint64_t n_slice) { return (n_slice + X_ADDR - 1) / X_ADDR; }
 
+int launch_extract_scan(unsigned long long *wg, uint32_t n_wg, hipStream_t s) {
+    hipLaunchKernelGGL(k_extract_scan, dim3(1), dim3(XS), 0, s, wg, n_wg);
+    return hipGetLastError() != hipSuccess;
+}
+
 static ExtractParams extract_params(int min_count, int max_count, int min_present, int max_absent) {
     ExtractParams ep;
     ep.lo_rep = (uint32_t)(min_count & 0x7f) * 0x01010101u;

@@ -1,4 +1,4 @@
-// pk_host.h -- what the files of the host layer share (pk_common.hip, pk_indexer.hip, pk_query.hip, pk_merge.hip, pk_select.hip, pk_trim.hip, pk_correct.hip): the error
+// pk_host.h -- what the files of the host layer share (pk_common.hip, pk_indexer.hip, pk_query.hip, pk_merge.hip, pk_select.hip, pk_trim.hip, pk_correct.hip, pk_unitig.hip): the error
 // helper, owned device memory and the host <-> HBM copy for all of them, struct pk_indexer and the state of a query (with
 // the value it carries from feed to feed, Carried) for pk_indexer.hip (which feeds both kinds of indexer) and pk_query.hip,
 // and the standard headers they use.  Every allocation of

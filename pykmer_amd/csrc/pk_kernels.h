@@ -279,6 +279,8 @@ uint64_t extract_mask_words(uint64_t n_slice);
 int launch_extract(const uint8_t *const *dev_tables, int P, int A, uint64_t n_slice, uint64_t first_addr, int min_count, int max_count, int min_present,
                    int max_absent, uint16_t *masks, unsigned long long *wg, unsigned long long *addr_out, uint8_t *counts_out, uint64_t cap,
                    hipStream_t s);
+// k_extract_scan alone: wg[0 .. n_wg) counts -> their exclusive prefix sums in place, wg[n_wg] = the total (kmer_unitig.hip's scans)
+int launch_extract_scan(unsigned long long *wg, uint32_t n_wg, hipStream_t s);
 // The same selection as a dense table: out[x] (n_slice bytes, 16-byte aligned, no input) = 0 where x is not selected, else
 // the reduction `op` (TABLE_SUM .. TABLE_COUNT) over the present bytes inside the window; nothing at or beyond n_slice is
 // written.  One launch, no scratch.
@@ -322,5 +324,28 @@ int launch_correct(const uint8_t *text, const unsigned long long *starts, uint64
                    uint64_t n_words, unsigned long long base, unsigned long long *cnt, unsigned long long *total, unsigned long long *geo,
                    uint32_t k, const uint8_t *const *tables, uint32_t n_tab, uint32_t min_count, uint32_t max_count, uint32_t min_windows,
                    uint8_t *text_out, unsigned long long *out, hipStream_t s);
+
+// kmer_unitig.hip -- the unitigs of one table of n = 4^k bytes (16-byte aligned), k odd.  link: n bytes of
+// scratch that hold one link byte per address from launch_unitig_links on.  totals: UT_WORDS words, zeroed by the caller
+// before the links; UT_ERR != 0 afterwards: a walk met its step bound or an impossible link byte (which one: its value).
+// A phase (mode UT_ENDS: the linear unitigs, then UT_LOOPS: the circular ones) is
+//   launch_unitig_count    wg: unitig_workgroups(n) + 1 words; wg[last] receives the candidates m of the phase
+//   launch_unitig_measure  (m > 0) cand, c_n, c_depth (m words) and c_keep (m bytes): the candidates, ascending, and what each
+//                          owns; bound: the steps no walk can reach; wgA, wgB: unitig_rank_workgroups(m) + 1 words each, whose
+//                          last words receive the phase's rows and the bytes of their records; row_base: the rows before
+//   launch_unitig_spell    (rows > 0) the row arrays (rows words each) and the records, text_bytes of them
+enum { UT_NODES = 0, UT_BRANCHING = 1, UT_SHORT = 2, UT_NODES_SHORT = 3, UT_LONGEST = 4, UT_ERR = 5, UT_WORDS = 8 };
+enum { UT_ENDS = 0, UT_LOOPS = 1 };
+uint32_t unitig_workgroups(uint64_t n);
+uint32_t unitig_rank_workgroups(uint64_t m);
+int launch_unitig_links(const uint8_t *table, uint64_t n, int k, int min_count, int max_count, uint8_t *link, unsigned long long *totals, hipStream_t s);
+int launch_unitig_count(int mode, const uint8_t *link, uint64_t n, unsigned long long *wg, hipStream_t s);
+int launch_unitig_measure(int mode, const uint8_t *table, uint8_t *link, uint64_t n, int k, int min_count, int max_count, const unsigned long long *wg,
+                          unsigned long long *cand, uint64_t m, uint64_t bound, uint64_t min_kmers, unsigned long long *c_n, unsigned long long *c_depth,
+                          uint8_t *c_keep, uint64_t row_base, unsigned long long *wgA, unsigned long long *wgB, unsigned long long *totals, hipStream_t s);
+int launch_unitig_spell(const uint8_t *link, int k, const unsigned long long *cand, const uint8_t *c_keep, const unsigned long long *c_n,
+                        const unsigned long long *c_depth, uint64_t m, const unsigned long long *wgA, const unsigned long long *wgB, uint64_t row_base,
+                        uint64_t rows, unsigned long long *r_addr, unsigned long long *r_n, unsigned long long *r_depth, unsigned long long *r_off,
+                        uint8_t *text, uint64_t text_bytes, unsigned long long *totals, hipStream_t s);
 
 }  // namespace pk
