@@ -10,48 +10,14 @@ import gpu_support as gs
 import synth
 import unitig_inputs as ui
 import unitig_ref as ref
+from unitig_support import build_at, check, same
 
 pytestmark = pytest.mark.gpu
-
-TOTALS = ("n_nodes", "n_branching", "n_linear", "n_circular", "n_short", "nodes_short", "longest_kmers")
 
 
 @pytest.fixture(scope="module")
 def gpu():
     return gs.lib()
-
-
-def build_at(ptr, k, mn=1, mx=255, M=1):
-    """pk_unitig_build on the table at ptr: totals, rows, fasta, timings."""
-    with gs.lib().Unitigs(k, device=0) as u:
-        got = u.build(ptr, mn, mx, M)
-        got.update(u.rows())
-        got["fasta"] = u.text().tobytes()
-        assert u.text(0, 0).size == 0
-        if got["bytes"] >= 3:                                # any slice of the text
-            assert u.text(1, got["bytes"] - 2).tobytes() == got["fasta"][1:-1]
-        got["timings"] = u.timings()
-    return got
-
-
-def same(got, want):
-    for key in TOTALS:
-        assert got[key] == want[key], (key, got[key], want[key])
-    assert got["bytes"] == len(want["fasta"]), ("bytes", got["bytes"], len(want["fasta"]))
-    for key in ("first_addr", "n_kmers", "depth", "circular"):
-        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (key, got[key].dtype, got[key].shape, want[key].shape)
-        assert np.array_equal(got[key], want[key]), (key, np.flatnonzero(got[key] != want[key])[:5], got[key][:8], want[key][:8])
-    if got["fasta"] != want["fasta"]:
-        at = next(i for i, (a, b) in enumerate(zip(got["fasta"], want["fasta"])) if a != b)
-        raise AssertionError(("fasta", at, got["fasta"][max(0, at - 40):at + 40], want["fasta"][max(0, at - 40):at + 40]))
-
-
-def check(counts, k, mn=1, mx=255, M=1, want=None):
-    want = want or ref.expected(counts, k, mn, mx, M)
-    with gs.Device([ref.table_of(counts, k)]) as dev:
-        got = build_at(dev.ptrs[0], k, mn, mx, M)
-    same(got, want)
-    return got, want
 
 
 # ------------------------------------------------------------------ 1. every edge rule -------------

@@ -104,6 +104,97 @@ def test_window_selects_the_nodes():
     assert int(got["depth"].sum()) == 3 + 200 + 3 + 3
 
 
+# ------------------------------------------------------------------ the inputs of the seam tests --
+def _marked(text, *rows):
+    return all(f"\n>{r}\n".encode("ascii") in text for r in rows)
+
+
+def test_small_graph_inputs_hold_every_feature():
+    """What test_gpu_unitig_seams.py relies on at k = 1 and k = 3, on the reference alone."""
+    assert ui.canonical(1) == [0, 1] and len(ui.k1_tables()) == 9 and len(ui.canonical(3)) == 32
+    for mn, mx in ui.K1_WINDOWS:
+        rows = set()
+        for counts in ui.k1_tables():
+            want = ref.expected(counts, 1, mn, mx)
+            ref.check_invariants(want)
+            rows.add(len(want["n_kmers"]))
+            assert want["n_nodes"] == want["n_branching"] == want["n_linear"] == len(want["n_kmers"]) and want["n_circular"] == 0
+            assert want["n_kmers"].tolist() == [1] * want["n_nodes"] and len(want["fasta"]) == 5 * want["n_nodes"]      # every node branches
+        assert rows == {0, 1, 2}, (mn, mx, rows)
+    cases = ui.k3_cases()
+    assert len(ui.k3_subsets()) == 1500 and len(cases) == 2000 and sum(c[2:4] == (2, 3) for c in cases) == 500
+    found, linear, rings, empty = set(), set(), [], 0
+    for name, counts, mn, mx, want in cases:
+        assert all(1 <= v <= 3 for v in counts.values()) and set(counts) <= set(ui.canonical(3))
+        empty += want["n_nodes"] == 0
+        if (mn, mx) != (1, 255):
+            continue
+        found |= ui.features(want["graph"])
+        linear |= set(want["n_kmers"][want["circular"] == 0].tolist())
+        rings += want["n_kmers"][want["circular"] == 1].tolist()
+    assert found == {"self_loop", "hairpin", "double_edge"}, found
+    assert linear >= {1, 2, 3, 4, 5}, linear
+    assert len(rings) >= 3 and set(rings) >= {2, 3}, rings
+    assert empty >= 1                                        # a table without a node among them
+    for name, counts, mn, mx, want in cases[::40]:
+        ref.check_invariants(want)
+
+
+def test_ring_inputs_hold_what_the_ring_tests_rely_on():
+    """What sections B, C and E of test_gpu_unitig_seams.py rely on, on the reference alone."""
+    counts = ui.ring_table()
+    assert ui.RING_K == 11 and sum(v == ui.RING_COUNT for v in counts.values()) == 18174 and len(counts) == 19314
+    rows = {}
+    for mn, mx, M in ui.RING_BUILDS:
+        want = ui.ring_expected(mn, mx, M)
+        ref.check_invariants(want, M)
+        rows[mn, mx, M] = (want["n_linear"], want["n_circular"], want["n_short"])
+        assert want["n_branching"] == 0
+    assert rows == {(1, 2, 1): (0, 1100, 0), (1, 255, 1): (95, 1100, 0), (1, 2, 12): (0, 1028, 72), (1, 255, 12): (51, 1028, 116), (5, 5, 1): (95, 0, 0)}, rows
+    full, only = ui.ring_expected(1, 255, 1), ui.ring_expected(1, 2, 1)
+    assert full["n_nodes"] == 19314 and len(full["fasta"]) == 38519 and only["n_nodes"] == 18174
+    # row_base = 0: every decimal width begins inside the circular text; row_base = 95: the widths 3 and 4 do
+    assert ui.linear_bytes(only) == 0 and _marked(b"\n" + only["fasta"], 0, 9, 10, 99, 100, 999, 1000)
+    lin = ui.linear_bytes(full)
+    assert 17 < lin < len(full["fasta"]) - 17 and _marked(full["fasta"][lin - 1:], 95, 99, 100, 999, 1000) and not _marked(full["fasta"][lin - 1:], 94)
+    for M12, M1 in ((ui.ring_expected(1, 2, 12), only), (ui.ring_expected(1, 255, 12), full)):        # renumbered, not thinned out
+        keep = M1["n_kmers"] >= 12
+        assert np.array_equal(M12["first_addr"], M1["first_addr"][keep]) and M12["nodes_short"] == int(M1["n_kmers"][~keep].sum()) > 0
+        assert ref.texts(M12) == [t for t, kept in zip(ref.texts(M1), keep) if kept]
+    assert ui.linear_bytes(ui.ring_expected(5, 5, 1)) == len(ui.ring_expected(5, 5, 1)["fasta"]) == lin
+    # the rebuild sequence: a window without a node, and an M above every unitig
+    assert [b[:2] for b in ui.REBUILDS] == [(1, 255), (1, 2), (5, 5), (200, 255), (1, 255), (1, 255)]
+    none, short = ui.ring_expected(*ui.REBUILDS[3]), ui.ring_expected(*ui.REBUILDS[5])
+    assert none["n_nodes"] == 0 and len(none["n_kmers"]) == 0 and none["fasta"] == b""
+    assert ui.REBUILDS[5][2] > full["longest_kmers"] and len(short["n_kmers"]) == 0 and short["fasta"] == b""
+    assert short["nodes_short"] == short["n_nodes"] == 19314 and short["n_short"] == 1195 and short["longest_kmers"] == 0
+    # One kept row per ring among all its nodes, spread over the rank workgroups (256 candidates each).  A ring's minimum is
+    # the smallest of 11 to 22 random addresses, so the minima of these 1100 rings lie in the low third of their 71 groups
+    # and cannot reach 50 of them; the 3000 rings of wide_ring_table() do.
+    groups = ui.loop_candidate_groups(only)
+    assert groups == ui.loop_candidate_groups(full) and 20 <= len(groups) < 50 and (only["n_nodes"] + 255) // 256 == 71
+    wide = ui.wide_ring_expected(1)
+    ref.check_invariants(wide)
+    assert (wide["n_linear"], wide["n_circular"], wide["n_branching"]) == (0, ui.WIDE_RINGS, 0) and _marked(wide["fasta"], 999, 1000, 2999)
+    assert len(ui.loop_candidate_groups(wide)) >= 50
+    cut = ui.wide_ring_expected(12)
+    assert 0 < cut["n_short"] == ui.WIDE_RINGS - cut["n_circular"] and len(ui.loop_candidate_groups(cut)) >= 50
+
+
+def test_dense_input_needs_two_scan_rounds_and_six_digits():
+    """More than 1024 rank workgroups of 256 ends each, and more than 100 000 rows; M = 3 keeps few of the candidates."""
+    want = ui.dense_expected(1)
+    ends = ui.ends_of(want)
+    assert len(ends) > 262_144 + 256 and (len(ends) + 255) // 256 > 1024
+    assert want["n_linear"] > 100_000 and _marked(want["fasta"], 99_999, 100_000) and want["n_branching"] > 0
+    assert int(np.count_nonzero(ui.dense_table())) == want["n_nodes"] and want["graph"].S == set(np.flatnonzero(ui.dense_table()).tolist())
+    kept = int((want["n_kmers"] >= 3).sum())                 # the rows of M = 3, without a second run of the reference
+    assert 1000 < kept and 20 * kept < len(ends) and want["longest_kmers"] >= 3
+    owners = set(want["first_addr"][want["n_kmers"] >= 3].tolist())
+    kept_groups = {i // 256 for i, x in enumerate(sorted(ends)) if x in owners}
+    assert max(kept_groups) >= 1024 and min(kept_groups) < 1024        # kept rows on both sides of the scan's seam
+
+
 # ------------------------------------------------------------------ n50 ---------------------------
 def test_n50():
     assert unitigs.n50([]) == 0 and unitigs.n50([7]) == 7
