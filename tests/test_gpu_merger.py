@@ -150,6 +150,63 @@ def test_gram_packed_tallies_worst_case_at_size(gpu, N, log4n):
     torch.cuda.empty_cache()
 
 
+def _gram_scan_constants():
+    """From gram_scan.hip as written: the (tile width, packed) of k_gram_mw's launches, the default grid and the cap of grid_for."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pykmer_amd", "csrc", "gram_scan.hip")).read()
+    shapes = [(int(tw), pack == "true") for tw, pack in re.findall(r"k_gram_mw<[^>]*>\), dim3\(grid_for\((\d+), (true|false)\)\)", src)]
+    grid = re.search(r"uint64_t grid = n_tiles < (\d+)u \? n_tiles : (\d+)u;", src)
+    cap = re.search(r"const uint64_t max_tiles = (\d+)u / \(\(uint64_t\)\(tw / 64\) \* 32u\);", src)
+    assert len(shapes) == 3 and grid and grid.group(1) == grid.group(2) and cap, "gram_scan.hip: grid_for is no longer written as this test reads it"
+    return shapes, int(grid.group(1)), int(cap.group(1))
+
+
+@pytest.mark.parametrize("N,W", [(13, 8), (16, 8), (24, 5), (32, 3)])
+def test_window_sweep_packed_tallies_worst_case_at_size(gpu, N, W):
+    """k_gram_mw packs two 16-bit tallies per register for every N from 9 to 32, and only grid_for(tw, pack) in
+    launch_gram_windows keeps the low one from carrying into its neighbour.  n = 4^16 with every address valid is the
+    size at which that matters: 2^27 words of 32 addresses, and at the default grid of 1024 workgroups a lane would add
+    exactly 65 536 to a tally with either tile width --
+        tile of 128 words: 2^20 tiles, 1024 per workgroup x 64 per tile (2 rounds x popcount 32)
+        tile of  64 words: 2^21 tiles, 2048 per workgroup x 32 per tile
+    so the low half would wrap to 0 and add 1 to the high half.  The cap of 65 535 resizes the grid to 1026 and 1025
+    workgroups; a cap of 65 536 would not.  Every table is a constant, table i holds (i % 3) + 1 (three buffers of 4 GiB
+    aliased over the N tables), and each call is one full pass of windows that hold all, some and none of the three values.
+    Expected values in closed form: pair[w][i][j] = n where both constants lie in window w (i <= j), else 0."""
+    import torch
+    n = 4 ** 16
+    shapes, grid, cap = _gram_scan_constants()
+    assert cap == 65535
+    assert sorted(tw for tw, pack in shapes if pack) == [64, 128]
+    for tw in (64, 128):                                                 # the arithmetic above, from the source as it stands
+        n_tiles = (n // 32 + tw - 1) // tw
+        per_tile = (tw // 64) * 32
+        assert (n_tiles // grid) * per_tile == 65536 and n_tiles % grid == 0, (tw, "this size is no longer the worst case of the default grid")
+        resized = -(-n_tiles // (cap // per_tile))
+        assert resized == {128: 1026, 64: 1025}[tw] and -(-n_tiles // resized) * per_tile <= cap
+    windows = [(1, 255), (2, 3), (4, 255), (1, 1), (1, 3), (3, 3), (2, 255), (1, 2)][:W]
+    assert {(1, 255), (2, 3), (4, 255)} <= set(windows)                  # all three values, some, none: in every pass
+    torch.cuda.empty_cache()
+    bufs = [torch.full((n,), v, dtype=torch.uint8, device="cuda") for v in (1, 2, 3)]
+    values = [(i % 3) + 1 for i in range(N)]
+    ptrs = [bufs[i % 3].data_ptr() for i in range(N)]
+    acc = torch.zeros((W, N, N), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    secs = gpu.gram_device_accumulate_windows(ptrs, n, acc.data_ptr(), windows)
+    got = acc.cpu().numpy().view(np.uint64)
+    want = np.zeros((W, N, N), dtype=np.uint64)
+    for w, (mn, mx) in enumerate(windows):
+        ok = [mn <= v <= mx for v in values]
+        for i in range(N):
+            for j in range(i, N):
+                want[w, i, j] = n if ok[i] and ok[j] else 0
+    assert np.array_equal(got, want), (N, [w for w in range(W) if not np.array_equal(got[w], want[w])], np.argwhere(got != want)[:5])
+    print(f"sweep N={N} W={W} n=4^16 dense: kernel {secs * 1e3:.2f} ms")
+    del bufs, acc
+    torch.cuda.empty_cache()
+
+
 def test_merge_host_path_sub_slices_and_threads(gpu, tmp_path, monkeypatch):
     """merger.pair_matrix on real files: a small HBM budget forces several sub-slices per device slice
     (partials accumulate in HBM), two host threads drive two plan entries on the same GPU at once, one
