@@ -552,13 +552,48 @@ void pk_correct_destroy(pk_correct *c);
  * pk_unitig_rows: the four row arrays, U = linear + circular rows each; PK_ERR_RECS_CAP if cap < U, PK_ERR_STATE before a
  * build.  pk_unitig_text: bytes [offset, offset + n_bytes) of the FASTA text; PK_ERR_ARG outside it.
  * pk_unitig_timings: out = { seconds of the link pass, of the linear phase (ends, measure, spell), of the circular phase --
- * HIP events on the builder's stream, the copies and allocations outside them --, builds (as a double) }. */
+ * HIP events on the builder's stream, the copies and allocations outside them --, builds (as a double) }.
+ *
+ * THE GRAPH of the last build (pk_unitig_graph; nothing of it is computed or reserved before that call).
+ * ORIENTED ROW: let a written row r have the path o_1 -> ... -> o_n.  Its two oriented rows are (r,+) and (r,-).  (r,+) reads
+ * the row's text as written: its first k-mer is tail(r,+) = o_1 and its last is head(r,+) = o_n.  (r,-) reads the reverse
+ * complement of the text: tail(r,-) = rc(o_n) and head(r,-) = rc(o_1).  All 2U tails are different oriented k-mers.
+ * EDGE: (r,s) -> (q,u) is an edge iff tail(q,u) is in out(head(r,s)), with out() as above.  Both rows must be written rows,
+ * the overlap is always k - 1 bases, and nothing else is an edge.  What follows: for a linear row no edge out of head(r,s)
+ * is compactable; every t in out(head(r,s)) is the tail of exactly one oriented unitig of the graph, which may be one that
+ * min_kmers dropped; an edge whose target unitig was dropped is not written, and edges_dropped counts these; a circular row
+ * c has exactly the two edges (c,+) -> (c,+) and (c,-) -> (c,-), its closing edge read both ways, and no other edge
+ * touches it.
+ * MIRROR: (r,s) -> (q,u) is an edge iff (q,~u) -> (r,~s) is, ~ flipping the sign.  Both are written, as BCALM's GFA
+ * conversion writes them; an edge that is its own mirror, (r,+) -> (r,-) or (r,-) -> (r,+), a hairpin at a unitig end, is
+ * written once.
+ * ORDER: edges are ordered by the `from` row ascending, then + before -, then by the base b = 0..3 of the successor
+ * ((head << 2) | b) & (4^k - 1).  One (row, sign, b) gives at most one edge, so the order is total; a row has at most 8
+ * outgoing edges.
+ * COUNT IDENTITY: at M = 1, n_edges = the sum over x in S of (|out(x)| + |out(rc(x))|) - 2 * the sum over the rows of
+ * (n_kmers - 1), and edges_dropped = 0.
+ * The GFA 1.0 text is `H\tVN:Z:1.0\n`, then per row in row order `S\t<row>\t<text>\tLN:i:<n+k-1>\tKC:i:<depth>\n`, then per
+ * edge in edge order `L\t<from>\t<+|->\t<to>\t<+|->\t<k-1>M\n`.
+ * pk_unitig_graph: totals_out = { n_edges, edges_dropped, n_dead_ends (the oriented rows without an outgoing written edge),
+ * the bytes of the GFA text }.  PK_ERR_STATE before a build, and if a lane of the pass met what cannot be (a record beyond
+ * its text, an end that no candidate holds, a line beyond its array); PK_ERR_RECS_CAP, with the size in the message, where
+ * the device does not hold the end -> row map (8 bytes per end of a linear unitig), the edge arrays (17 bytes per edge) or
+ * the GFA text.  pk_unitig_edges: from, to (E u64 each) and orient (E bytes: bit 0 set: the from side is -, bit 1 set: the
+ * to side is -); PK_ERR_RECS_CAP if cap < E.  pk_unitig_gfa_text: bytes [offset, offset + n_bytes) of the GFA text;
+ * PK_ERR_ARG outside it.  Both are PK_ERR_STATE before pk_unitig_graph, and again after a later pk_unitig_build until
+ * pk_unitig_graph has run anew.  pk_unitig_graph_timings: out = { seconds of the edge passes (end map, count, scan, fill),
+ * seconds of the GFA passes (sizes, scans, lines) } of the last pk_unitig_graph, HIP events as above.  Like
+ * pk_unitig_timings it needs no build: before one, and before a pk_unitig_graph, it is PK_OK with two zeros. */
 typedef struct pk_unitig pk_unitig;
 int pk_unitig_create(pk_unitig **out, int k, int device);
 int pk_unitig_build(pk_unitig *u, const void *dev_table, int min_count, int max_count, uint64_t min_kmers, uint64_t totals_out[8]);
 int pk_unitig_rows(pk_unitig *u, uint64_t *first_addr, uint64_t *n_kmers, uint64_t *depth, uint8_t *circular, uint64_t cap);
 int pk_unitig_text(pk_unitig *u, uint8_t *host_out, uint64_t offset, uint64_t n_bytes);
 int pk_unitig_timings(pk_unitig *u, double out[4]);
+int pk_unitig_graph(pk_unitig *u, uint64_t totals_out[4]);
+int pk_unitig_edges(pk_unitig *u, uint64_t *from, uint64_t *to, uint8_t *orient, uint64_t cap);
+int pk_unitig_gfa_text(pk_unitig *u, uint8_t *host_out, uint64_t offset, uint64_t n_bytes);
+int pk_unitig_graph_timings(pk_unitig *u, double out[2]);
 void pk_unitig_destroy(pk_unitig *u);
 
 /* ---- BGZF on the host (no device work): the reference reads `.kin.bgz` tables and `.fa.gz` / `.bgz` inputs through one

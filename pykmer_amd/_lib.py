@@ -121,6 +121,10 @@ _SIGNATURES = {
     "pk_unitig_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "pk_unitig_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
     "pk_unitig_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_unitig_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "pk_unitig_edges": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "pk_unitig_gfa_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "pk_unitig_graph_timings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "pk_unitig_destroy": (None, [ctypes.c_void_p]),
     "pk_bgzf_scan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u64p]),
     "pk_bgzf_inflate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
@@ -729,6 +733,7 @@ class Corrector:
 
 
 UNITIG_TOTALS = ("n_nodes", "n_branching", "n_linear", "n_circular", "n_short", "nodes_short", "bytes", "longest_kmers")
+UNITIG_GRAPH_TOTALS = ("n_edges", "edges_dropped", "n_dead_ends", "gfa_bytes")
 
 
 class Unitigs:
@@ -738,6 +743,7 @@ class Unitigs:
     def __init__(self, kmer_len: int, device: int = 0):
         self._h = ctypes.c_void_p()
         self.k, self.device = int(kmer_len), device
+        self.graph_totals = dict.fromkeys(UNITIG_GRAPH_TOTALS, 0)            # before graph(): the library refuses edges() and gfa_text()
         _check(load().pk_unitig_create(ctypes.byref(self._h), int(kmer_len), device))
 
     def close(self):
@@ -783,6 +789,34 @@ class Unitigs:
         out = np.zeros(4, dtype=np.float64)
         _check(load().pk_unitig_timings(self._h, out.ctypes.data))
         return {"links_s": float(out[0]), "paths_s": float(out[1]), "cycles_s": float(out[2]), "builds": int(out[3])}
+
+    def graph(self) -> dict:
+        """pk_unitig_graph on the last build: the UNITIG_GRAPH_TOTALS.  PkError (PK_ERR_STATE) before a build,
+        (PK_ERR_RECS_CAP) if the edges or the GFA text do not fit the device."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(load().pk_unitig_graph(self._h, out.ctypes.data))
+        self.graph_totals = {name: int(v) for name, v in zip(UNITIG_GRAPH_TOTALS, out)}
+        return dict(self.graph_totals)
+
+    def edges(self) -> dict:
+        """pk_unitig_edges: edge_from, edge_to (E,) uint64 and edge_orient (E,) uint8 (bit 0: from is -, bit 1: to is -)."""
+        E = self.graph_totals["n_edges"]
+        out = {"edge_from": np.zeros(E, dtype=np.uint64), "edge_to": np.zeros(E, dtype=np.uint64), "edge_orient": np.zeros(E, dtype=np.uint8)}
+        _check(load().pk_unitig_edges(self._h, *(out[key].ctypes.data if E else None for key in ("edge_from", "edge_to", "edge_orient")), E))
+        return out
+
+    def gfa_text(self, offset: int = 0, n_bytes: int = None) -> np.ndarray:
+        """pk_unitig_gfa_text: bytes [offset, offset + n_bytes) of the GFA text (to its end by default), uint8."""
+        n = self.graph_totals["gfa_bytes"] - int(offset) if n_bytes is None else int(n_bytes)
+        out = np.empty(max(0, n), dtype=np.uint8)
+        _check(load().pk_unitig_gfa_text(self._h, out.ctypes.data if out.size else None, int(offset), n))
+        return out
+
+    def graph_timings(self) -> dict:
+        """pk_unitig_graph_timings: the HIP-event seconds of the edge passes and of the GFA passes of the last graph()."""
+        out = np.zeros(2, dtype=np.float64)
+        _check(load().pk_unitig_graph_timings(self._h, out.ctypes.data))
+        return {"edges_s": float(out[0]), "gfa_s": float(out[1])}
 
 
 def count_fasta(data, k: int, device: int = 0, table_out: np.ndarray = None):

@@ -27,6 +27,23 @@
 //   k_ut_spell     one lane per row walks again and writes its record
 // Every walk carries a step bound that a correct walk cannot reach (the nodes for paths, the candidates for cycles); a lane
 // that reaches it, or meets a link byte that cannot be, raises the error word and returns.
+//
+// The graph pass (pk_unitig_graph, after a build; no table): the edges between the written rows and the GFA text.  With
+// tail(r,+) = o_1, head(r,+) = o_n, tail(r,-) = rc(o_n), head(r,-) = rc(o_1), (r,s) -> (q,u) is an edge iff
+// tail(q,u) in out(head(r,s)); membership of t is link[canon(t)] & LK_NODE.  Heads and tails are read off the FASTA records.
+//   k_ug_ends      one lane per linear row: end_row[i] = row << 1 | s for the candidate i (an index into the ends of the linear
+//                  phase, ascending) of each of its two end nodes y, where a successor t with canon(t) = y is the tail
+//                  (row, s ^ (t != y)); UG_NONE stays where the end belongs to a unitig that min_kmers dropped
+//   k_ug_count     one lane per (row, sign): the head, its four successors, four link bytes, and per member a binary search
+//                  of canon(t) in the ends; the edges per workgroup, and the tallies of dropped edges and dead ends
+//   k_ug_fill      the same again behind the scan: from, to, orient at the scanned offsets, in (row, sign, base) order.  A
+//                  circular row emits (c,s) -> (c,s) without a lookup.
+//   k_ug_sizes_*   the bytes of the S-lines per 256 rows and of the L-lines per 256 edges, for the two scans
+//   k_ug_slines    a workgroup writes the S-lines of its 256 rows, k_ug_llines the L-lines of its 256 edges: one thread per
+//                  output byte, which finds its line in the workgroup's scanned sizes in LDS and its place in the line; the
+//                  sequence is copied out of the FASTA text
+// No loop here depends on the data beyond its length: the searches take at most 64 steps.  Checks 9 to 12 of the error word:
+// a record that passes its text, an end or a member that no candidate holds, an edge or a line beyond its array.
 #include "pk_kernels.h"
 #include "wg_scan.h"
 
@@ -323,6 +340,267 @@ __global__ __launch_bounds__(UW) void k_ut_spell(const uint8_t *__restrict__ lin
     *w = (uint8_t)'\n';
 }
 
+// ------------------------------------------------------------------ the graph pass: edges and GFA text ----------------
+constexpr unsigned long long UG_NONE = ~0ull;
+
+__device__ __forceinline__ uint64_t ug_kmer(const uint8_t *__restrict__ s, uint32_t k) {
+    uint64_t o = 0;
+    for (uint32_t c = 0; c < k; c++) { const uint32_t a = s[c]; o = (o << 2) | (((a >> 1) & 3u) ^ ((a >> 2) & 1u)); }      // A, C, G, T -> 0 .. 3
+    return o;
+}
+
+// the index of x in cand[0, m), ascending; m where it is absent
+__device__ __forceinline__ uint64_t ug_find(const unsigned long long *__restrict__ cand, uint64_t m, uint64_t x) {
+    uint64_t lo = 0, hi = m;
+    for (uint32_t step = 0; step < 64u && lo < hi; step++) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (cand[mid] < x) lo = mid + 1u; else hi = mid;
+    }
+    return lo < m && cand[lo] == x ? lo : m;
+}
+
+// row g of all rows: its k-mers, its depth and the first letter of its sequence in its phase's FASTA text; false where the
+// record passes the end of that text
+__device__ __forceinline__ bool ug_row(const UgRows &R, uint32_t k, uint64_t g, uint64_t &n, uint64_t &depth, const uint8_t *&seq) {
+    const uint32_t ph = g >= R.rows0;
+    const uint64_t i = g - (ph ? R.rows0 : 0ull), off = R.off[ph][i];
+    n = R.n[ph][i];
+    depth = R.depth[ph][i];
+    if (n == 0u || off > R.text_bytes[ph] || ut_record(g, n, k) > R.text_bytes[ph] - off) return false;
+    seq = R.text[ph] + off + 2u + ut_digits(g);
+    return true;
+}
+
+__global__ __launch_bounds__(UT) void k_ug_ends(UgRows R, uint32_t k, const unsigned long long *__restrict__ r_addr,
+                                                const unsigned long long *__restrict__ cand, uint64_t m, unsigned long long *__restrict__ end_row,
+                                                unsigned long long *__restrict__ totals) {
+    const uint64_t g = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    if (g >= R.rows0) return;
+    uint64_t n, depth;
+    const uint8_t *seq;
+    if (!ug_row(R, k, g, n, depth, seq)) { ut_raise(totals, 9); return; }
+    const uint64_t o1 = ug_kmer(seq, k), y1 = ut_canon(o1, k), i = ug_find(cand, m, y1);
+    if (y1 != r_addr[g] || i == m) { ut_raise(totals, 10); return; }
+    end_row[i] = (g << 1) | (unsigned long long)(o1 != y1);              // tail(g,+) = o_1
+    if (n == 1u) return;
+    const uint64_t t = ut_rc(ug_kmer(seq + (n - 1u), k), k), y2 = ut_canon(t, k), j = ug_find(cand, m, y2);
+    if (j == m || j == i) { ut_raise(totals, 10); return; }
+    end_row[j] = (g << 1) | (unsigned long long)(t == y2);               // tail(g,-) = rc(o_n)
+}
+
+// What leaves the oriented row `lane` = row << 1 | sign.  bit b of mask: the successor with base b is the tail of the written
+// row to[b], read as sign[b]; dropped: the members whose unitig has no row.  false (the error word is raised): nothing to use.
+__device__ __forceinline__ bool ug_out(const UgRows &R, const UtParams &p, const uint8_t *__restrict__ link, const unsigned long long *__restrict__ cand,
+                                       uint64_t m, const unsigned long long *__restrict__ end_row, uint64_t lane, uint32_t &mask, uint64_t (&to)[4],
+                                       uint32_t (&sign)[4], uint32_t &dropped, unsigned long long *__restrict__ totals) {
+    const uint64_t g = lane >> 1;
+    const uint32_t s = (uint32_t)(lane & 1u);
+    mask = 0; dropped = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b++) { to[b] = 0; sign[b] = 0; }
+    if (g >= R.rows0) { mask = 1u; to[0] = g; sign[0] = s; return true; }       // a cycle's closing edge, read this way round
+    uint64_t n, depth;
+    const uint8_t *seq;
+    if (!ug_row(R, p.k, g, n, depth, seq)) { ut_raise(totals, 9); return false; }
+    const uint64_t head = s ? ut_rc(ug_kmer(seq, p.k), p.k) : ug_kmer(seq + (n - 1u), p.k);
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b++) {
+        const uint64_t t = ((head << 2) | b) & p.mask, y = ut_canon(t, p.k);
+        if (!(link[y] & LK_NODE)) continue;
+        const uint64_t j = ug_find(cand, m, y);
+        if (j == m) { ut_raise(totals, 10); mask = 0; return false; }
+        const unsigned long long e = end_row[j];
+        if (e == UG_NONE) { dropped++; continue; }
+        mask |= 1u << b;
+        to[b] = e >> 1;
+        sign[b] = (uint32_t)(e & 1u) ^ (uint32_t)(t != y);
+    }
+    return true;
+}
+
+// a lane's tallies in one word for one workgroup sum: edges (at most 4 * 256), dropped edges, dead ends
+constexpr uint32_t UG_F = 16;
+constexpr unsigned long long UG_FMASK = (1ull << UG_F) - 1ull;
+
+__global__ __launch_bounds__(UT) void k_ug_count(UgRows R, UtParams p, const uint8_t *__restrict__ link, const unsigned long long *__restrict__ cand,
+                                                 uint64_t m, const unsigned long long *__restrict__ end_row, unsigned long long *__restrict__ wgE,
+                                                 unsigned long long *__restrict__ totals) {
+    __shared__ unsigned long long sh[UT / 64];
+    const uint64_t lane = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    unsigned long long v = 0;
+    if (lane < 2u * R.rows) {
+        uint32_t mask, dropped, sign[4];
+        uint64_t to[4];
+        if (ug_out(R, p, link, cand, m, end_row, lane, mask, to, sign, dropped, totals))
+            v = (unsigned long long)__popc(mask) | ((unsigned long long)dropped << UG_F) | ((unsigned long long)(mask == 0u) << (2u * UG_F));
+    }
+    unsigned long long total;
+    wg_excl_sum<UT / 64, false>(v, sh, total);
+    if (threadIdx.x == 0) {
+        wgE[blockIdx.x] = total & UG_FMASK;
+        if ((total >> UG_F) & UG_FMASK) atomicAdd(totals + UG_DROPPED, (total >> UG_F) & UG_FMASK);
+        if (total >> (2u * UG_F)) atomicAdd(totals + UG_DEAD, total >> (2u * UG_F));
+    }
+}
+
+// wgE scanned
+__global__ __launch_bounds__(UT) void k_ug_fill(UgRows R, UtParams p, const uint8_t *__restrict__ link, const unsigned long long *__restrict__ cand,
+                                                uint64_t m, const unsigned long long *__restrict__ end_row, const unsigned long long *__restrict__ wgE,
+                                                uint64_t n_edges, unsigned long long *__restrict__ from, unsigned long long *__restrict__ to_out,
+                                                uint8_t *__restrict__ orient, unsigned long long *__restrict__ totals) {
+    __shared__ unsigned long long sh[UT / 64];
+    const uint64_t lane = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    uint32_t mask = 0, dropped, sign[4];
+    uint64_t to[4];
+    if (lane < 2u * R.rows && !ug_out(R, p, link, cand, m, end_row, lane, mask, to, sign, dropped, totals)) mask = 0;
+    unsigned long long total;
+    const uint32_t cnt = __popc(mask);
+    uint64_t at = wgE[blockIdx.x] + wg_excl_sum<UT / 64, false>((unsigned long long)cnt, sh, total);
+    if (!cnt) return;
+    if (at > n_edges || cnt > n_edges - at) { ut_raise(totals, 11); return; }
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b++) {
+        if (!((mask >> b) & 1u)) continue;
+        from[at] = lane >> 1;
+        to_out[at] = to[b];
+        orient[at] = (uint8_t)((uint32_t)(lane & 1u) | (sign[b] << 1));
+        at++;
+    }
+}
+
+// little-endian: byte i of the word is s[i]
+constexpr uint64_t ug_word(const char *s) {
+    uint64_t v = 0;
+    for (int i = 0; i < 8 && s[i]; i++) v |= (uint64_t)(uint8_t)s[i] << (8 * i);
+    return v;
+}
+__device__ __forceinline__ uint8_t ug_at(uint64_t word, uint64_t i) { return (uint8_t)(word >> (8u * (uint32_t)i)); }
+// digit j, from the left, of the d digits of v
+__device__ __forceinline__ uint8_t ug_digit(uint64_t v, uint32_t d, uint64_t j) {
+    for (uint32_t i = (uint32_t)j + 1u; i < d; i++) v /= 10ull;
+    return (uint8_t)('0' + (uint32_t)(v % 10ull));
+}
+
+// S <row> <text> LN:i:<L> KC:i:<depth>, tab separated
+__device__ __forceinline__ uint64_t ug_s_size(uint64_t g, uint64_t n, uint64_t depth, uint32_t k) {
+    const uint64_t L = n + k - 1u;
+    return L + 16u + ut_digits(g) + ut_digits(L) + ut_digits(depth);
+}
+__device__ __forceinline__ uint8_t ug_s_byte(uint64_t g, uint64_t n, uint64_t depth, const uint8_t *__restrict__ seq, uint32_t k, uint64_t q) {
+    const uint64_t L = n + k - 1u;
+    const uint32_t dg = ut_digits(g), dl = ut_digits(L), dd = ut_digits(depth);
+    if (q < 2u) return ug_at(ug_word("S\t"), q);
+    q -= 2u;
+    if (q < dg) return ug_digit(g, dg, q);
+    q -= dg;
+    if (q == 0u) return (uint8_t)'\t';
+    q -= 1u;
+    if (q < L) return seq[q];
+    q -= L;
+    if (q < 6u) return ug_at(ug_word("\tLN:i:"), q);
+    q -= 6u;
+    if (q < dl) return ug_digit(L, dl, q);
+    q -= dl;
+    if (q < 6u) return ug_at(ug_word("\tKC:i:"), q);
+    q -= 6u;
+    return q < dd ? ug_digit(depth, dd, q) : (uint8_t)'\n';
+}
+
+// L <from> <sign> <to> <sign> <k-1>M, tab separated
+__device__ __forceinline__ uint64_t ug_l_size(uint64_t from, uint64_t to, uint32_t k) { return 10u + ut_digits(from) + ut_digits(to) + ut_digits(k - 1u); }
+__device__ __forceinline__ uint8_t ug_l_byte(uint64_t from, uint64_t to, uint32_t orient, uint32_t k, uint64_t q) {
+    const uint32_t df = ut_digits(from), dt = ut_digits(to), dk = ut_digits(k - 1u);
+    if (q < 2u) return ug_at(ug_word("L\t"), q);
+    q -= 2u;
+    if (q < df) return ug_digit(from, df, q);
+    q -= df;
+    if (q < 3u) return q == 1u ? (uint8_t)((orient & 1u) ? '-' : '+') : (uint8_t)'\t';
+    q -= 3u;
+    if (q < dt) return ug_digit(to, dt, q);
+    q -= dt;
+    if (q < 3u) return q == 1u ? (uint8_t)((orient & 2u) ? '-' : '+') : (uint8_t)'\t';
+    q -= 3u;
+    if (q < dk) return ug_digit(k - 1u, dk, q);
+    return q == dk ? (uint8_t)'M' : (uint8_t)'\n';
+}
+
+__global__ __launch_bounds__(UT) void k_ug_sizes_s(UgRows R, uint32_t k, unsigned long long *__restrict__ wgS) {
+    __shared__ unsigned long long sh[UT / 64];
+    const uint64_t g = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    uint64_t n, depth;
+    const uint8_t *seq;
+    unsigned long long total;
+    wg_excl_sum<UT / 64, false>((unsigned long long)(g < R.rows && ug_row(R, k, g, n, depth, seq) ? ug_s_size(g, n, depth, k) : 0ull), sh, total);
+    if (threadIdx.x == 0) wgS[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(UT) void k_ug_sizes_l(const unsigned long long *__restrict__ from, const unsigned long long *__restrict__ to, uint64_t n_edges,
+                                                   uint32_t k, unsigned long long *__restrict__ wgL) {
+    __shared__ unsigned long long sh[UT / 64];
+    const uint64_t e = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    unsigned long long total;
+    wg_excl_sum<UT / 64, false>((unsigned long long)(e < n_edges ? ug_l_size(from[e], to[e], k) : 0ull), sh, total);
+    if (threadIdx.x == 0) wgL[blockIdx.x] = total;
+}
+
+// the line that holds byte q of a workgroup's lines: the last r with off[r] <= q (lines of no bytes lie on the next one)
+__device__ __forceinline__ uint32_t ug_line(const unsigned long long *off, uint64_t q) {
+    uint32_t lo = 0, hi = UT - 1;
+    for (uint32_t step = 0; step < 8u && lo < hi; step++) {              // 2^8 = UT
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (off[mid] <= q) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// wgS scanned; the S-lines begin behind the header line
+__global__ __launch_bounds__(UT) void k_ug_slines(UgRows R, uint32_t k, const unsigned long long *__restrict__ wgS, uint8_t *__restrict__ gfa,
+                                                  uint64_t gfa_bytes, unsigned long long *__restrict__ totals) {
+    __shared__ unsigned long long sh[UT / 64], off[UT], s_n[UT], s_depth[UT];
+    __shared__ const uint8_t *s_seq[UT];
+    const uint64_t g = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    uint64_t n = 0, depth = 0;
+    const uint8_t *seq = nullptr;
+    unsigned long long size = 0, total;
+    if (g < R.rows) {
+        if (ug_row(R, k, g, n, depth, seq)) size = ug_s_size(g, n, depth, k);
+        else ut_raise(totals, 9);
+    }
+    off[threadIdx.x] = wg_excl_sum<UT / 64, false>(size, sh, total);
+    s_n[threadIdx.x] = n; s_depth[threadIdx.x] = depth; s_seq[threadIdx.x] = seq;
+    __syncthreads();
+    const uint64_t base = (uint64_t)UG_HEADER + wgS[blockIdx.x];
+    if (base > gfa_bytes || total > gfa_bytes - base) { if (threadIdx.x == 0) ut_raise(totals, 12); return; }      // uniform
+    for (uint64_t q = threadIdx.x; q < total; q += UT) {
+        const uint32_t r = ug_line(off, q);
+        gfa[base + q] = ug_s_byte((uint64_t)blockIdx.x * UT + r, s_n[r], s_depth[r], s_seq[r], k, q - off[r]);
+    }
+}
+
+// wgS and wgL scanned; the L-lines begin behind the last S-line
+__global__ __launch_bounds__(UT) void k_ug_llines(const unsigned long long *__restrict__ from, const unsigned long long *__restrict__ to,
+                                                  const uint8_t *__restrict__ orient, uint64_t n_edges, uint32_t k,
+                                                  const unsigned long long *__restrict__ wgS, uint32_t n_wgS, const unsigned long long *__restrict__ wgL,
+                                                  uint8_t *__restrict__ gfa, uint64_t gfa_bytes, unsigned long long *__restrict__ totals) {
+    __shared__ unsigned long long sh[UT / 64], off[UT], s_from[UT], s_to[UT];
+    __shared__ uint8_t s_orient[UT];
+    const uint64_t e = (uint64_t)blockIdx.x * UT + threadIdx.x;
+    const uint64_t f = e < n_edges ? from[e] : 0ull, t = e < n_edges ? to[e] : 0ull;
+    unsigned long long total;
+    off[threadIdx.x] = wg_excl_sum<UT / 64, false>((unsigned long long)(e < n_edges ? ug_l_size(f, t, k) : 0ull), sh, total);
+    s_from[threadIdx.x] = f; s_to[threadIdx.x] = t; s_orient[threadIdx.x] = e < n_edges ? orient[e] : (uint8_t)0;
+    __syncthreads();
+    const uint64_t lines = (uint64_t)UG_HEADER + wgS[n_wgS];
+    if (lines > gfa_bytes || wgL[blockIdx.x] > gfa_bytes - lines || total > gfa_bytes - lines - wgL[blockIdx.x]) {       // uniform
+        if (threadIdx.x == 0) ut_raise(totals, 12);
+        return;
+    }
+    const uint64_t base = lines + wgL[blockIdx.x];
+    for (uint64_t q = threadIdx.x; q < total; q += UT) {
+        const uint32_t r = ug_line(off, q);
+        gfa[base + q] = ug_l_byte(s_from[r], s_to[r], s_orient[r], k, q - off[r]);
+    }
+}
+
 static UtParams ut_params(int k, int min_count, int max_count) {
     UtParams p;
     p.k = (uint32_t)k; p.lo = (uint32_t)min_count; p.hi = (uint32_t)max_count;
@@ -376,6 +654,44 @@ int launch_unitig_spell(const uint8_t *link, int k, const unsigned long long *ca
                        r_addr, r_n, r_depth, r_off, totals);
     hipLaunchKernelGGL(k_ut_spell, dim3((uint32_t)((rows + UW - 1) / UW)), dim3(UW), 0, s, link, ut_params(k, 1, 255), (const unsigned long long *)r_addr,
                        (const unsigned long long *)r_n, (const unsigned long long *)r_off, rows, row_base, text, text_bytes, totals);
+    return hipGetLastError() != hipSuccess;
+}
+
+int launch_unitig_edges_count(const UgRows &R, int k, const uint8_t *link, const unsigned long long *r_addr, const unsigned long long *cand, uint64_t m,
+                              unsigned long long *end_row, unsigned long long *wgE, unsigned long long *totals, hipStream_t s) {
+    const uint32_t n_wg = unitig_rank_workgroups(2u * R.rows);
+    if (R.rows0) hipLaunchKernelGGL(k_ug_ends, dim3(unitig_rank_workgroups(R.rows0)), dim3(UT), 0, s, R, (uint32_t)k, r_addr, cand, m, end_row, totals);
+    hipLaunchKernelGGL(k_ug_count, dim3(n_wg), dim3(UT), 0, s, R, ut_params(k, 1, 255), link, cand, m, (const unsigned long long *)end_row, wgE, totals);
+    if (hipGetLastError() != hipSuccess) return 1;
+    return launch_extract_scan(wgE, n_wg, s);
+}
+
+int launch_unitig_edges_fill(const UgRows &R, int k, const uint8_t *link, const unsigned long long *cand, uint64_t m, const unsigned long long *end_row,
+                             const unsigned long long *wgE, uint64_t n_edges, unsigned long long *from, unsigned long long *to, uint8_t *orient,
+                             unsigned long long *totals, hipStream_t s) {
+    hipLaunchKernelGGL(k_ug_fill, dim3(unitig_rank_workgroups(2u * R.rows)), dim3(UT), 0, s, R, ut_params(k, 1, 255), link, cand, m, end_row, wgE, n_edges,
+                       from, to, orient, totals);
+    return hipGetLastError() != hipSuccess;
+}
+
+int launch_unitig_gfa_sizes(const UgRows &R, int k, const unsigned long long *from, const unsigned long long *to, uint64_t n_edges,
+                            unsigned long long *wgS, unsigned long long *wgL, hipStream_t s) {
+    const uint32_t n_wgS = unitig_rank_workgroups(R.rows), n_wgL = unitig_rank_workgroups(n_edges);
+    hipLaunchKernelGGL(k_ug_sizes_s, dim3(n_wgS), dim3(UT), 0, s, R, (uint32_t)k, wgS);
+    if (hipGetLastError() != hipSuccess || launch_extract_scan(wgS, n_wgS, s)) return 1;
+    if (n_edges) hipLaunchKernelGGL(k_ug_sizes_l, dim3(n_wgL), dim3(UT), 0, s, from, to, n_edges, (uint32_t)k, wgL);
+    if (hipGetLastError() != hipSuccess) return 1;
+    return launch_extract_scan(wgL, n_wgL, s);
+}
+
+int launch_unitig_gfa_write(const UgRows &R, int k, const unsigned long long *from, const unsigned long long *to, const uint8_t *orient, uint64_t n_edges,
+                            const unsigned long long *wgS, const unsigned long long *wgL, uint8_t *gfa, uint64_t gfa_bytes, unsigned long long *totals,
+                            hipStream_t s) {
+    const uint32_t n_wgS = unitig_rank_workgroups(R.rows);
+    hipLaunchKernelGGL(k_ug_slines, dim3(n_wgS), dim3(UT), 0, s, R, (uint32_t)k, wgS, gfa, gfa_bytes, totals);
+    if (n_edges)
+        hipLaunchKernelGGL(k_ug_llines, dim3(unitig_rank_workgroups(n_edges)), dim3(UT), 0, s, from, to, orient, n_edges, (uint32_t)k, wgS, n_wgS, wgL, gfa,
+                           gfa_bytes, totals);
     return hipGetLastError() != hipSuccess;
 }
 

@@ -347,5 +347,32 @@ int launch_unitig_spell(const uint8_t *link, int k, const unsigned long long *ca
                         const unsigned long long *c_depth, uint64_t m, const unsigned long long *wgA, const unsigned long long *wgB, uint64_t row_base,
                         uint64_t rows, unsigned long long *r_addr, unsigned long long *r_n, unsigned long long *r_depth, unsigned long long *r_off,
                         uint8_t *text, uint64_t text_bytes, unsigned long long *totals, hipStream_t s);
+// The graph pass behind a build (no table): the edges between the written rows, then the GFA text.  UgRows: the row arrays
+// and the FASTA text of the two phases as one array of `rows` rows, the first rows0 of them linear.  totals: the builder's;
+// its words UG_DROPPED and UG_DEAD are zeroed by the caller before the count, checks 9 to 12 go to UT_ERR.
+//   launch_unitig_edges_count  end_row: m words preset to ~0 (m: the ends of the linear phase, cand); wgE:
+//                              unitig_rank_workgroups(2 * rows) + 1 words, whose last receives the edges E
+//   launch_unitig_edges_fill   (E > 0) from, to (E words) and orient (E bytes)
+//   launch_unitig_gfa_sizes    wgS: unitig_rank_workgroups(rows) + 1 words, wgL: unitig_rank_workgroups(E) + 1 words; their last
+//                              words receive the bytes of the S-lines and of the L-lines
+//   launch_unitig_gfa_write    gfa: UG_HEADER + S + L bytes; the header line is the caller's
+enum { UG_DROPPED = 6, UG_DEAD = 7 };
+enum { UG_HEADER = 11 };                         // "H\tVN:Z:1.0\n"
+struct UgRows {
+    const unsigned long long *n[2], *depth[2], *off[2];
+    const uint8_t *text[2];
+    uint64_t text_bytes[2];
+    uint64_t rows0, rows;
+};
+int launch_unitig_edges_count(const UgRows &R, int k, const uint8_t *link, const unsigned long long *r_addr, const unsigned long long *cand, uint64_t m,
+                              unsigned long long *end_row, unsigned long long *wgE, unsigned long long *totals, hipStream_t s);
+int launch_unitig_edges_fill(const UgRows &R, int k, const uint8_t *link, const unsigned long long *cand, uint64_t m, const unsigned long long *end_row,
+                             const unsigned long long *wgE, uint64_t n_edges, unsigned long long *from, unsigned long long *to, uint8_t *orient,
+                             unsigned long long *totals, hipStream_t s);
+int launch_unitig_gfa_sizes(const UgRows &R, int k, const unsigned long long *from, const unsigned long long *to, uint64_t n_edges,
+                            unsigned long long *wgS, unsigned long long *wgL, hipStream_t s);
+int launch_unitig_gfa_write(const UgRows &R, int k, const unsigned long long *from, const unsigned long long *to, const uint8_t *orient, uint64_t n_edges,
+                            const unsigned long long *wgS, const unsigned long long *wgL, uint8_t *gfa, uint64_t gfa_bytes, unsigned long long *totals,
+                            hipStream_t s);
 
 }  // namespace pk

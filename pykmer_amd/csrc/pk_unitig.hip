@@ -1,6 +1,7 @@
 // pk_unitig.hip -- the host layer of the unitig builder (pk_unitig_*, include/pykmer_hip.h): the link array, the candidates
 // and rows of the two phases (linear unitigs, then circular ones) and their FASTA text on the device, sized from what the
-// passes of kmer_unitig.hip count, and the copies back.  The table is the caller's.
+// passes of kmer_unitig.hip count, and the copies back.  The table is the caller's.  pk_unitig_graph adds, behind a build
+// and only when it is called, the end -> row map, the edge arrays and the GFA text.
 #include "pk_host.h"
 
 using namespace pk;
@@ -27,6 +28,12 @@ struct pk_unitig {
     unsigned long long tot[UT_WORDS] = {};
     double t_links = 0, t_paths = 0, t_cycles = 0;
     uint64_t builds = 0;
+    // the graph of the last build (pk_unitig_graph): nothing of it is reserved before that call
+    bool graphed = false;
+    DevBuf<unsigned long long> end_row, wgE, wgS, wgL, e_from, e_to;
+    DevBuf<uint8_t> e_orient, gfa;
+    uint64_t n_edges = 0, edges_dropped = 0, n_dead_ends = 0, gfa_bytes = 0;
+    double t_edges = 0, t_gfa = 0;
 
     ~pk_unitig() {
         if (!ready) return;
@@ -138,7 +145,7 @@ extern "C" int pk_unitig_build(pk_unitig *u, const void *dev_table, int min_coun
     if (!(1 <= min_count && min_count <= max_count && max_count <= 255))
         return fail(PK_ERR_ARG, "the count window must satisfy 1 <= min <= max <= 255, got %d-%d", min_count, max_count);
     if (min_kmers < 1) return fail(PK_ERR_ARG, "min_kmers must be at least 1");
-    u->built = false;
+    u->built = u->graphed = false;
     if (int rc = ensure_device(u)) return rc;
     const uint8_t *table = (const uint8_t *)dev_table;
     if (int rc = reserve_counted(u->link, (u->n + 15u) & ~15ull, "the link bytes")) return rc;
@@ -206,5 +213,117 @@ extern "C" int pk_unitig_timings(pk_unitig *u, double out[4]) {
     out[1] = u->t_paths;
     out[2] = u->t_cycles;
     out[3] = (double)u->builds;
+    return PK_OK;
+}
+
+// settle() for the graph pass: its checks are 9 and above
+static int settle_graph(pk_unitig *u, double &acc) {
+    const int rc = settle(u, acc);
+    if (rc == PK_ERR_STATE && u->tot[UT_ERR] >= 9)
+        return fail(PK_ERR_STATE, "the graph pass met a record beyond its text, an end that no candidate holds or a line beyond its array (check %llu): "
+                    "the rows are not what the link array gives", u->tot[UT_ERR]);
+    return rc;
+}
+
+extern "C" int pk_unitig_graph(pk_unitig *u, uint64_t totals_out[4]) {
+    if (!u || !totals_out) return fail(PK_ERR_ARG, "null argument");
+    if (!u->built) return fail(PK_ERR_STATE, "pk_unitig_build comes first");
+    u->graphed = false;
+    HIPCHK(hipSetDevice(u->device));
+    u->n_edges = u->edges_dropped = u->n_dead_ends = 0;
+    u->gfa_bytes = UG_HEADER;
+    u->t_edges = u->t_gfa = 0;
+    UgRows R;
+    for (int mode = 0; mode < 2; mode++) {
+        const Phase &f = u->ph[mode];
+        R.n[mode] = f.r_n.p; R.depth[mode] = f.r_depth.p; R.off[mode] = f.r_off.p; R.text[mode] = f.text.p; R.text_bytes[mode] = f.bytes;
+    }
+    R.rows0 = u->ph[0].rows;
+    R.rows = R.rows0 + u->ph[1].rows;
+    const uint64_t m = u->ph[0].m;
+    if (R.rows) {
+        const uint32_t n_wgE = unitig_rank_workgroups(2u * R.rows), n_wgS = unitig_rank_workgroups(R.rows);
+        if (int rc = reserve_counted(u->end_row, m * 8u, "the rows of the unitig ends")) return rc;
+        if (int rc = reserve_counted(u->wgE, (n_wgE + 1ull) * 8u, "the edge counts")) return rc;
+        HIPCHK(hipMemsetAsync(u->totals.p + UG_DROPPED, 0, 2 * sizeof(unsigned long long), u->stream));
+        if (m) HIPCHK(hipMemsetAsync(u->end_row.p, 0xff, m * 8u, u->stream));
+        HIPCHK(hipEventRecord(u->ev_begin, u->stream));
+        if (launch_unitig_edges_count(R, u->k, u->link.p, u->ph[0].r_addr.p, u->ph[0].cand.p, m, u->end_row.p, u->wgE.p, u->totals.p, u->stream))
+            return fail(PK_ERR_HIP, "launching the unitig edge count kernels failed: %s", hipGetErrorString(hipGetLastError()));
+        if (int rc = settle_graph(u, u->t_edges)) return rc;
+        if (int rc = read_word(u, u->wgE.p + n_wgE, &u->n_edges)) return rc;
+        u->edges_dropped = u->tot[UG_DROPPED];
+        u->n_dead_ends = u->tot[UG_DEAD];
+        const uint64_t E = u->n_edges;
+        if (E) {
+            const char *what = "the edges between the unitigs";
+            if (int rc = reserve_counted(u->e_from, E * 8u, what)) return rc;
+            if (int rc = reserve_counted(u->e_to, E * 8u, what)) return rc;
+            if (int rc = reserve_counted(u->e_orient, E, what)) return rc;
+            HIPCHK(hipEventRecord(u->ev_begin, u->stream));
+            if (launch_unitig_edges_fill(R, u->k, u->link.p, u->ph[0].cand.p, m, u->end_row.p, u->wgE.p, E, u->e_from.p, u->e_to.p, u->e_orient.p,
+                                         u->totals.p, u->stream))
+                return fail(PK_ERR_HIP, "launching the unitig edge fill kernel failed: %s", hipGetErrorString(hipGetLastError()));
+            if (int rc = settle_graph(u, u->t_edges)) return rc;
+        }
+        const uint32_t n_wgL = unitig_rank_workgroups(E);
+        if (int rc = reserve_counted(u->wgS, (n_wgS + 1ull) * 8u, "the sizes of the GFA lines")) return rc;
+        if (int rc = reserve_counted(u->wgL, (n_wgL + 1ull) * 8u, "the sizes of the GFA lines")) return rc;
+        HIPCHK(hipEventRecord(u->ev_begin, u->stream));
+        if (launch_unitig_gfa_sizes(R, u->k, u->e_from.p, u->e_to.p, E, u->wgS.p, u->wgL.p, u->stream))
+            return fail(PK_ERR_HIP, "launching the GFA size kernels failed: %s", hipGetErrorString(hipGetLastError()));
+        if (int rc = settle_graph(u, u->t_gfa)) return rc;
+        uint64_t s_bytes = 0, l_bytes = 0;
+        if (int rc = read_word(u, u->wgS.p + n_wgS, &s_bytes)) return rc;
+        if (int rc = read_word(u, u->wgL.p + n_wgL, &l_bytes)) return rc;
+        u->gfa_bytes = UG_HEADER + s_bytes + l_bytes;
+        if (int rc = reserve_counted(u->gfa, u->gfa_bytes, "the GFA text")) return rc;
+        HIPCHK(hipEventRecord(u->ev_begin, u->stream));
+        if (launch_unitig_gfa_write(R, u->k, u->e_from.p, u->e_to.p, u->e_orient.p, E, u->wgS.p, u->wgL.p, u->gfa.p, u->gfa_bytes, u->totals.p, u->stream))
+            return fail(PK_ERR_HIP, "launching the GFA line kernels failed: %s", hipGetErrorString(hipGetLastError()));
+        if (int rc = settle_graph(u, u->t_gfa)) return rc;
+    } else if (int rc = reserve_counted(u->gfa, UG_HEADER, "the GFA text")) {
+        return rc;
+    }
+    static const char header[UG_HEADER + 1] = "H\tVN:Z:1.0\n";
+    HIPCHK(hipMemcpyAsync(u->gfa.p, header, UG_HEADER, hipMemcpyHostToDevice, u->stream));
+    HIPCHK(hipStreamSynchronize(u->stream));
+    u->graphed = true;
+    totals_out[0] = u->n_edges;
+    totals_out[1] = u->edges_dropped;
+    totals_out[2] = u->n_dead_ends;
+    totals_out[3] = u->gfa_bytes;
+    return PK_OK;
+}
+
+extern "C" int pk_unitig_edges(pk_unitig *u, uint64_t *from, uint64_t *to, uint8_t *orient, uint64_t cap) {
+    if (!u) return fail(PK_ERR_ARG, "null unitig builder");
+    if (!u->built) return fail(PK_ERR_STATE, "pk_unitig_build comes first");
+    if (!u->graphed) return fail(PK_ERR_STATE, "pk_unitig_graph comes first, after the last pk_unitig_build");
+    const uint64_t E = u->n_edges;
+    if (E > cap) return fail(PK_ERR_RECS_CAP, "%llu edges do not fit arrays of %llu", (unsigned long long)E, (unsigned long long)cap);
+    if (!E) return PK_OK;
+    if (!from || !to || !orient) return fail(PK_ERR_ARG, "null pointer with %llu edges", (unsigned long long)E);
+    if (int rc = bounce_copy(u->e_from.p, from, E * 8u, false, u->device)) return rc;
+    if (int rc = bounce_copy(u->e_to.p, to, E * 8u, false, u->device)) return rc;
+    return bounce_copy(u->e_orient.p, orient, E, false, u->device);
+}
+
+extern "C" int pk_unitig_gfa_text(pk_unitig *u, uint8_t *host_out, uint64_t offset, uint64_t n_bytes) {
+    if (!u) return fail(PK_ERR_ARG, "null unitig builder");
+    if (!u->built) return fail(PK_ERR_STATE, "pk_unitig_build comes first");
+    if (!u->graphed) return fail(PK_ERR_STATE, "pk_unitig_graph comes first, after the last pk_unitig_build");
+    if (offset > u->gfa_bytes || n_bytes > u->gfa_bytes - offset)
+        return fail(PK_ERR_ARG, "bytes %llu + %llu lie outside the %llu bytes of GFA text", (unsigned long long)offset, (unsigned long long)n_bytes,
+                    (unsigned long long)u->gfa_bytes);
+    if (!n_bytes) return PK_OK;
+    if (!host_out) return fail(PK_ERR_ARG, "null output pointer");
+    return bounce_copy(u->gfa.p + offset, host_out, n_bytes, false, u->device);
+}
+
+extern "C" int pk_unitig_graph_timings(pk_unitig *u, double out[2]) {
+    if (!u || !out) return fail(PK_ERR_ARG, "null argument");
+    out[0] = u->t_edges;
+    out[1] = u->t_gfa;
     return PK_OK;
 }

@@ -14,10 +14,12 @@ hipMemcpyDtoDAsync of the table between two HIP events on the null stream (the f
 times it) and pk_extract_device counting the same window on the same table (count + scan, no arrays), one warm-up and the
 median of the same number of runs each.
 
-    python tools/unitig_bench.py [out.json] [--runs R] [--only NAME]
+    python tools/unitig_bench.py [out.json] [--runs R] [--only NAME] [--gfa]
+    --gfa also runs pk_unitig_graph behind every build and reports edges_s and gfa_s (pk_unitig_graph_timings), the edge totals
+    and the GFA bytes beside links_s + paths_s + cycles_s of the same runs; it writes profiles/unitigs_gfa.json instead.
     PK_UNITIG_BENCH_SCALE=0.01 scales the three genomes down for a rehearsal.
 
-Writes profiles/unitigs.json (or out.json)."""
+Writes profiles/unitigs.json (profiles/unitigs_gfa.json with --gfa), or out.json."""
 import json
 import os
 import statistics
@@ -35,17 +37,20 @@ from pykmer_amd import _lib  # noqa: E402
 P, A = 7, 6
 
 
-def time_table(name: str, ptr: int, k: int, hip, runs: int) -> dict:
+def time_table(name: str, ptr: int, k: int, hip, runs: int, gfa: bool = False) -> dict:
     n = 4 ** k
-    builds = []
+    builds, graphs, graph_totals = [], [], {}
     for i in range(runs + 1):
         with _lib.Unitigs(k) as u:
             totals = u.build(ptr, 1, 255, 1)
+            if gfa:
+                graph_totals = u.graph()
             if i:
                 builds.append(u.timings())
+                graphs.append(u.graph_timings() if gfa else {})
             else:
                 n_kmers = u.rows()["n_kmers"]
-        print(name, "build", i, builds[-1] if builds else "warm-up", flush=True)
+        print(name, "build", i, dict(builds[-1], **graphs[-1]) if builds else "warm-up", flush=True)
     counts = []
     for i in range(runs + 1):
         m, _, s = _lib.extract_device([ptr], 1, n, 0, 1, 255, 1, 0)
@@ -65,7 +70,16 @@ def time_table(name: str, ptr: int, k: int, hip, runs: int) -> dict:
     n50 = int(sizes[np.searchsorted(np.cumsum(bases_at), (bases + 1) // 2)] + k - 1) if sizes.size else 0
     top = np.repeat(sizes[:8], by_n[sizes[:8]])[:8]
     copy, count = statistics.median(copies), statistics.median(counts)
-    return {"kmer_len": k, "table_bytes": n, **totals, "n_unitigs": totals["n_linear"] + totals["n_circular"], "longest_bases": totals["longest_kmers"] + k - 1,
+    graph = {}
+    if gfa:                                                  # beside the three phases of the same runs
+        build_s = [b["links_s"] + b["paths_s"] + b["cycles_s"] for b in builds]
+        graph = {**graph_totals, "edges_s_runs": [g["edges_s"] for g in graphs], "gfa_s_runs": [g["gfa_s"] for g in graphs], "build_s_runs": build_s,
+                 "edges_s_median": statistics.median(g["edges_s"] for g in graphs), "gfa_s_median": statistics.median(g["gfa_s"] for g in graphs),
+                 "build_s_median": statistics.median(build_s)}
+        graph["edges_over_build"] = graph["edges_s_median"] / graph["build_s_median"]
+        graph["gfa_over_build"] = graph["gfa_s_median"] / graph["build_s_median"]
+        graph["edges_over_copy"] = graph["edges_s_median"] / copy
+    return {**graph, "kmer_len": k, "table_bytes": n, **totals, "n_unitigs": totals["n_linear"] + totals["n_circular"], "longest_bases": totals["longest_kmers"] + k - 1,
             "n50": n50, "bases": bases, "largest_n_kmers": [int(v) for v in top],
             "links_s_runs": [b["links_s"] for b in builds], "paths_s_runs": [b["paths_s"] for b in builds], "cycles_s_runs": [b["cycles_s"] for b in builds],
             "links_s_median": med["links_s"], "paths_s_median": med["paths_s"], "cycles_s_median": med["cycles_s"],
@@ -83,13 +97,15 @@ def counted(k: int, text):
 
 
 def main():
-    argv, args, runs, only = sys.argv[1:], [], 3, None
+    argv, args, runs, only, gfa = sys.argv[1:], [], 3, None, False
     while argv:
         a = argv.pop(0)
         if a == "--runs":
             runs = int(argv.pop(0))
         elif a == "--only":
             only = argv.pop(0)
+        elif a == "--gfa":
+            gfa = True
         elif not a.startswith("--"):
             args.append(a)
     scale = float(os.environ.get("PK_UNITIG_BENCH_SCALE", "1"))
@@ -101,7 +117,11 @@ def main():
                      "cycles_s from HIP events on the builder's stream around the kernels of each phase (pk_unitig_timings; allocations and the "
                      "read-backs of the counts lie outside the events); copy_s: hipMemcpyDtoDAsync of the table between two HIP events; "
                      "extract_count_s: pk_extract_device with cap = 0 on the same table and window (its own HIP events)"}
-    path = args[0] if args else os.path.join(ROOT, "profiles", "unitigs.json")
+    if gfa:
+        out["method"] += ("; --gfa: pk_unitig_graph behind every build, the warm-up too; edges_s (end map, count, scan, fill) and gfa_s (line sizes, "
+                          "scans, S- and L-lines) from HIP events on the same stream (pk_unitig_graph_timings), their allocations and read-backs "
+                          "outside; build_s = links_s + paths_s + cycles_s of the same run")
+    path = args[0] if args else os.path.join(ROOT, "profiles", "unitigs_gfa.json" if gfa else "unitigs.json")
 
     def done(name, result):
         out[name] = result
@@ -112,7 +132,7 @@ def main():
 
     if only in (None, "genome_k17"):
         with counted(17, synth.c2(int(100_000_000 * scale), seed=2)[0]) as ix:
-            done("genome_k17", time_table("genome_k17", ix.table_device_ptr(), 17, hip, runs))
+            done("genome_k17", time_table("genome_k17", ix.table_device_ptr(), 17, hip, runs, gfa))
     if only in (None, "markers_k15"):
         n = 4 ** 15
         bufs, marker, hist = [], _lib.DeviceBuffer(n), _lib.DeviceBuffer(256 * 8)
@@ -129,13 +149,13 @@ def main():
             for b in bufs:
                 b.free()
             bufs = []
-            done("markers_k15", time_table("markers_k15", marker.ptr, 15, hip, runs))
+            done("markers_k15", time_table("markers_k15", marker.ptr, 15, hip, runs, gfa))
         finally:
             for b in bufs + [marker, hist]:
                 b.free()
     if only in (None, "genome_k15"):
         with counted(15, synth.c2(int(800_000_000 * scale), seed=2)[0]) as ix:
-            done("genome_k15", time_table("genome_k15", ix.table_device_ptr(), 15, hip, runs))
+            done("genome_k15", time_table("genome_k15", ix.table_device_ptr(), 15, hip, runs, gfa))
     print(json.dumps(out), flush=True)
 
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""unitigs.py Project_Name table.kin[.bgz] [--min-count A --max-count B] [--min-kmers M]
+"""unitigs.py Project_Name table.kin[.bgz] [--min-count A --max-count B] [--min-kmers M] [--gfa]
 
 Builds the unitigs of ONE k-mer table (no counterpart in the reference: the BCALM step behind a k-mer count): the k-mers
 whose count lies in the count window are the nodes of a de Bruijn graph, and the k-mers that overlap by k-1 bases without
 ambiguity are joined into sequences on the GPU (README "Unitigs").  `<project>.unitigs.fa` holds one record per unitig,
 named by its row index; `<project>.kmu` (np.savez_compressed: first_addr, n_kmers, depth, circular and the parameters) and
-`<project>.kmu.json` record the run.  Several tables are combined into one first with `extract.py --table`.  One device
-(PK_DEVICE).
+`<project>.kmu.json` record the run; `--gfa` adds `<project>.unitigs.gfa`, the unitigs and the edges between their ends.
+Several tables are combined into one first with `extract.py --table`.  One device (PK_DEVICE).
 """
 import os
 import sys
